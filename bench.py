@@ -19,10 +19,20 @@ N > 1   BASELINE config 5, STRONG scaling: the fixed 3840x2160 frame at 256 spp,
         its own watchdog for the launcher-started form.
 
 Prints ONE JSON line on rank 0.  `roofline` is the algorithmic VALU roofline of the render kernel (SURVEY 8d flops / kernel
-time from HIP events on the launch stream), `roofline_issue` the machine's own view from rocprofv3 PMC passes collected in
-this run (VALU issue rate against the measured 888 G wave-instructions/s, lane utilisation, SALU:VALU, wait share),
-`roofline_hbm` the HBM side with measured FETCH_SIZE / WRITE_SIZE, `cpu_baseline` the CPU oracle's hitable_list path on this
-host's cores.
+time from HIP events on the launch stream), `roofline_hbm` its HBM side.  A plain run does only what that line needs: set-up,
+--warmup steps, the --steps timed steps, the outputs (--dump-outputs) and the line.  --full adds what takes runs of its own:
+`roofline_issue`, the machine's own view from rocprofv3 PMC passes (VALU issue rate against the measured 888 G
+wave-instructions/s, lane utilisation, SALU:VALU, wait share) and the measured FETCH_SIZE / WRITE_SIZE of `roofline_hbm`;
+`cpu_baseline`, the CPU oracle's hitable_list path on this host's cores; and, N > 1, the same frame on one GPU
+(`single_gpu_same_frame`).
+
+--dump-outputs DIR writes what the timed path computed in its last step as DIR/<name>.npy (float32 / float64, 64 MiB at
+most, every value finite): the framebuffer (framebuffer.npy, ny x nx x 3; a seeded sample of pixels with
+framebuffer_pixels.npy when the whole would not fit) and, N = 1, the RNG states the render wrote back (rand_state.npy: d and
+v[5] of a seeded sample of pixels, rand_state_pixels.npy).  A colour is sqrt(...) in [0, 1], or NaN where the reference's
+dielectric takes the root of a negative number (material.h:95): a non-finite channel is written as a negative code (NaN -1,
++inf -2, -inf -3), which no colour can be.  The inputs are fixed by the arguments (create_world seed 1984), so two builds
+compare output for output.
 """
 import argparse
 import csv
@@ -101,6 +111,51 @@ def cpu_baseline(cfg, threads, use_octree, rows, spp):
     dt = time.perf_counter() - t0
     samples = rows * cfg["nx"] * spp
     return samples / dt / 1e6, dt, samples
+
+
+DUMP_BYTES_MAX = 64 << 20              # --dump-outputs: all files together
+DUMP_FB_BYTES_MAX = 48 << 20           # a framebuffer above this is sampled (C5: 3840 x 2160 x 3 x 4 B = 99.5 MB)
+DUMP_FB_PIXELS = 1 << 20               # ... at this many pixels
+DUMP_STATE_PIXELS = 1 << 16            # RNG states written back: always a sample of this many pixels
+DUMP_SEED = 1984
+DUMP_NAN, DUMP_POS_INF, DUMP_NEG_INF = -1.0, -2.0, -3.0   # codes of non-finite colour channels (colours lie in [0, 1])
+
+
+def sample_pixels(npix, k):
+    """a fixed, seeded, sorted sample of k of npix pixel indices (all of them when k >= npix)"""
+    import numpy as np
+    if k >= npix:
+        return np.arange(npix, dtype=np.int64)
+    return np.sort(np.random.default_rng(DUMP_SEED).choice(npix, size=k, replace=False))
+
+
+def dump_outputs(d, fb, nx, ny, state=None):
+    """--dump-outputs: fb = the framebuffer (numpy, nx*ny*3 binary32 or binary16, pixel j*nx+i), state = the RNG states as
+    rand_state_dtype records (one per pixel) or None.  Returns the names written."""
+    import numpy as np
+    os.makedirs(d, exist_ok=True)
+    npix = nx * ny
+    img = np.asarray(fb).reshape(npix, 3).astype(np.float32)        # binary16 widens exactly (a copy: coded below)
+    img[np.isnan(img)] = DUMP_NAN
+    img[img == np.inf] = DUMP_POS_INF
+    img[img == -np.inf] = DUMP_NEG_INF
+    out = {}
+    if img.nbytes <= DUMP_FB_BYTES_MAX:
+        out["framebuffer"] = img.reshape(ny, nx, 3)
+    else:
+        px = sample_pixels(npix, DUMP_FB_PIXELS)
+        out["framebuffer"], out["framebuffer_pixels"] = img[px], px.astype(np.float64)
+    if state is not None:
+        px = sample_pixels(npix, DUMP_STATE_PIXELS)
+        s = np.asarray(state)[px]
+        out["rand_state"] = np.concatenate([s["d"][:, None], s["v"]], axis=1).astype(np.float64)     # uint32 words: exact
+        out["rand_state_pixels"] = px.astype(np.float64)
+    assert all(np.isfinite(a).all() for a in out.values())
+    total = sum(a.nbytes for a in out.values())
+    assert total <= DUMP_BYTES_MAX, "outputs of %d bytes exceed the %d-byte budget" % (total, DUMP_BYTES_MAX)
+    for name, a in out.items():
+        np.save(os.path.join(d, name + ".npy"), a)
+    return sorted(out)
 
 
 def parse_pmc_dir(d):
@@ -279,14 +334,19 @@ def main():
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--config", default=None, choices=sorted(CONFIGS), help="default: c3 on one GPU, c5 (strong-scaled) on several")
     ap.add_argument("--scaling", default="strong", choices=["strong", "weak"], help="N>1 only: strong = fixed C5 frame (default), weak = C3 frame grown N-fold")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-pmc", action="store_true", help="skip the rocprofv3 counter passes (roofline_issue / traffic become null)")
+    ap.add_argument("--full", action="store_true", help="also the measurements that take runs of their own: rocprofv3 counter passes (roofline_issue, "
+                    "traffic), the CPU oracle baseline and, N > 1, the same frame on one GPU.  Off: only the timed steps and the result line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="after the timed steps, write what the last one computed as DIR/<name>.npy")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU oracle baseline")
+    ap.add_argument("--no-pmc", action="store_true", help="--full without the rocprofv3 counter passes (roofline_issue / traffic become null)")
     ap.add_argument("--list-reference", action="store_true", help="octree-off configs: plain list-order scan instead of the candidate grid")
     ap.add_argument("--arith", default="ieee", choices=["ieee", "contract"], help="contract: the opt-in tolerance mode with FMA contraction allowed (rt_world_set_arith) — never the parity mode, reported separately")
     ap.add_argument("--split", default="runs", choices=["runs", "balanced", "balanced-cached"], help="N>1: how rt_multi_render divides the frame — runs of 64 tiles dealt round-robin (default), "
                     "bands of equal predicted cost from a whole-frame pilot pass on every rank and frame, or those bands kept from frame to frame (rt_multi_set_split)")
     ap.add_argument("--timeout", type=int, default=900, help="N>1: seconds after which the job is killed (self-launched: by the parent; every rank also watches itself)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ and "RANK" not in os.environ:
         sys.exit(self_launch(args.gpus, sys.argv[1:], args.timeout))      # before torch, before any GPU call
@@ -315,8 +375,8 @@ def main():
     # counters first, in child processes, while NO rank of this job has touched a GPU yet.  N = 1: the workload itself.
     # N > 1 (strong-scaled C5): rank 0 profiles the same frame on one GPU; a rank's share of those instructions over its own
     # kernel time is its issue rate (the tile split deals the frame's work out evenly: per_rank_render_ms shows how evenly).
-    pmc, pmc_note = ({}, "skipped")
-    if not args.no_pmc and not weak and rank == 0:
+    pmc, pmc_note = ({}, "skipped" if args.full else "a plain run (--full runs the counter passes)")
+    if args.full and not args.no_pmc and not weak and rank == 0:
         # (N > 1: the other ranks wait at the barrier below with their watchdogs armed: the passes get a third of --timeout at most)
         pmc, pmc_note = collect_pmc(cfg_key, args.list_reference, args.arith, timeout=240 if world == 1 else 400,
                                     deadline=None if world == 1 else time.monotonic() + args.timeout / 3.0)
@@ -463,9 +523,16 @@ def main():
     local_samples = rank_pixels[rank] * spp if world > 1 else samples_step
     value = samples_step * args.steps / dt / 1e6
 
+    # what the last timed step left: the framebuffer (rank 0 holds the assembled frame) and, N = 1, the RNG states
+    if args.dump_outputs and rank == 0:
+        if M is not None:
+            dump_outputs(args.dump_outputs, full.cpu().numpy(), nx, ny)
+        else:
+            dump_outputs(args.dump_outputs, fb.cpu().numpy(), nx, ny, state=st.cpu().numpy().view(rt.rand_state_dtype))
+
     # strong scaling: the same frame on ONE GPU (rank 0 alone, after the timed region) as the reference point of the curve
     single = None
-    if world > 1 and not weak:
+    if args.full and world > 1 and not weak:
         fence()
         if rank == 0:
             st1 = rt.alloc_rand_state(nx, ny); fb1 = rt.alloc_fb(nx, ny, precision=precision)
@@ -575,7 +642,7 @@ def main():
             out["single_gpu_same_frame"] = single
             out["speedup_vs_single_gpu_same_frame"] = round(single["ms_per_step"] / (dt / args.steps * 1e3), 4)
             out["value_1gpu_same_workload"] = single["msamples_per_s"]      # the like-for-like reference point of `value` (the driver's N = 1 line is C3, another workload)
-        if not args.no_cpu_baseline:
+        if args.full and not args.no_cpu_baseline:
             threads = usable_cores()
             # hitable_list is O(N) per ray: the sample is cut so that it stays ~10 s of wall time on any core count
             if cfg.get("fp16"):

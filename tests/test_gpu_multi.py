@@ -98,14 +98,15 @@ def test_multi_render_rejects_a_precision_that_is_not_the_worlds(rt, cuda):
 
 
 def test_bench_self_launch_two_ranks_one_gpu(cuda):
-    """plain `python3 bench.py --gpus 2` (no launcher, no WORLD_SIZE) starts its own ranks as fresh child processes,
+    """`python3 bench.py --gpus 2` (no launcher, no WORLD_SIZE) starts its own ranks as fresh child processes,
     runs the strong-scaled C5 frame through rt_multi_render and prints ONE result line — here with both ranks on the box's one GPU
-    (RT_BENCH_SAME_GPU=1: the exchange goes through the custom-gather form over gloo; RCCL refuses two ranks on one device)."""
+    (RT_BENCH_SAME_GPU=1: the exchange goes through the custom-gather form over gloo; RCCL refuses two ranks on one device).
+    --full: the counter passes, the one-GPU frame and the CPU baseline asserted below are not part of a plain run."""
     import json
     env = dict(os.environ, RT_BENCH_SAME_GPU="1")
     for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT"):
         env.pop(k, None)
-    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1"],
+    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--full"],
                        stdout=subprocess.PIPE, stderr=subprocess.PIPE, env=env, timeout=900)
     assert p.returncode == 0, (p.returncode, p.stderr.decode()[-3000:])
     lines = [l for l in p.stdout.decode().splitlines() if l.strip()]
