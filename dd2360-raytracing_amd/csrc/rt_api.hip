@@ -732,6 +732,14 @@ static int render_common(rt_render_ctx* ctx, void* fb, int max_x, int max_y, int
     if (!rc && !cap) rc = ctx_prepare(C);
     if (rc) return rc;
     if (!C.d_queue) return RT_EINVAL;                                  // a context first used inside a capture: prepare it before (rt_render_ctx_reserve)
+    // the frame a progressive sequence's kept tile order belongs to: world and tree serials, frame size, partition, traversal
+    const uint64_t key[5] = {world->serial, d_octree ? d_octree->serial : 0, ((uint64_t)(uint32_t)max_x << 32) | (uint32_t)max_y,
+                             (((uint64_t)(uint32_t)part.part << 32) | (uint32_t)part.nparts) ^ ((uint64_t)part.tile_begin * 0x9e3779b97f4a7c15ull) ^ ((uint64_t)part.tile_end << 20),
+                             (uint64_t)(d_octree ? d_octree->traversal : 0)};
+    // once a captured pass has baked the kept order into a hipGraph, the first pass of ANOTHER frame would rewrite it under the
+    // graph (a smaller frame or another part: an order that is no longer a permutation of the graph's tiles) — refused before
+    // anything is launched.  A restart of the same frame recomputes an order of the same tiles.
+    if (mode == 1 && ns == 1 && !cap && C.p_pinned && memcmp(C.p_key, key, sizeof(key)) != 0) return RT_EINVAL;
     RenderArgs A;
     A.fb = fb; A.rand_state = d_rand_state; A.max_x = max_x; A.max_y = max_y; A.ns = ns;
     A.tiles_x = (max_x + 7) / 8; A.tiles_y = (max_y + 7) / 8;
@@ -762,9 +770,6 @@ static int render_common(rt_render_ctx* ctx, void* fb, int max_x, int max_y, int
         // the following passes of the same frame reuse it at no cost (C3: 0.594 -> 0.567 ms per pass; the pilot pass itself is
         // 0.5 ms).  The long-chain list is not kept: a pass is one sample, and waves set aside for the crevice pixels' ~40 bounces cost
         // a pass more than they save (0.70 - 0.88 ms).  Scheduling only: which lane renders a pixel and when never changes the pixel.
-        const uint64_t key[5] = {world->serial, d_octree ? d_octree->serial : 0, ((uint64_t)(uint32_t)max_x << 32) | (uint32_t)max_y,
-                                 (((uint64_t)(uint32_t)part.part << 32) | (uint32_t)part.nparts) ^ ((uint64_t)part.tile_begin * 0x9e3779b97f4a7c15ull) ^ ((uint64_t)part.tile_end << 20),
-                                 (uint64_t)(d_octree ? d_octree->traversal : 0)};
         if (ns == 1 && !cap) {
             C.p_valid = false;
             if ((rc = ctx_reserve_progressive(C, A.n_local_tiles))) return rc;
@@ -827,6 +832,29 @@ int rt_world_render_counters(rt_world* W, uint32_t* out4) {
 int rt_render_ctx_counters(rt_render_ctx* C, uint32_t* out4) {
     if (!C || !out4) return RT_EINVAL;
     return ctx_counters(*C, out4);
+}
+// the words of the context's latest launch that decided its hand-out (rt_device.h: the thresholds in the queue's second line;
+// the raw long / solo chain counts, before k_render's use_long gate), once it has finished
+static int ctx_schedule(rt_render_ctx& C, uint32_t* out, int n) {
+    if (n > RT_SCHEDULE_WORDS) n = RT_SCHEDULE_WORDS;
+    uint32_t w[RT_SCHEDULE_WORDS] = {0, 0, 0, 0, 0, 0, 0, 0};
+    if (C.last_queue) {
+        if (C.has_done) RT_TRY(hipEventSynchronize(C.done));
+        uint32_t q[kQueueThr + 6];
+        RT_TRY(hipMemcpy(q, C.last_queue, sizeof(q), hipMemcpyDeviceToHost));
+        for (int k = 0; k < 6; ++k) w[k] = q[kQueueThr + k];
+        w[6] = q[2]; w[7] = q[4];
+    }
+    for (int k = 0; k < n; ++k) out[k] = w[k];
+    return 0;
+}
+int rt_world_render_schedule(rt_world* W, uint32_t* out, int n) {
+    if (!W || n < 0 || (n > 0 && !out)) return RT_EINVAL;
+    return ctx_schedule(W->z->ctx, out, n);
+}
+int rt_render_ctx_schedule(rt_render_ctx* C, uint32_t* out, int n) {
+    if (!C || n < 0 || (n > 0 && !out)) return RT_EINVAL;
+    return ctx_schedule(*C, out, n);
 }
 int rt_world_render_times(rt_world* W, float* ms_out, int max, int* count) {
     if (!W || !ms_out || !count || max < 0) return RT_EINVAL;

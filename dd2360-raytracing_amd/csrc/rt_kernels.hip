@@ -1234,6 +1234,8 @@ __global__ __launch_bounds__(256, RT_RENDER_WAVES) void k_render(RenderArgs A) {
                 local_tile = (long long)(pid >> 6); l = (int)(pid & 63u);
             } else {
                 constexpr int kIl = COOPG == 2 ? RT_INTERLEAVE_DENSE : (COOPG == 5 ? RT_INTERLEAVE_SOLO : RT_INTERLEAVE);   // tiles whose pixels interleave (consecutive slots: one pixel position of kIl tiles)
+                // (k_tile_order starts the tail on a multiple of 64 tiles: a block of kIl tiles that straddled it would skip some pixels and render others twice)
+                static_assert(kIl > 0 && 64 % kIl == 0, "RT_INTERLEAVE, RT_INTERLEAVE_DENSE and RT_INTERLEAVE_SOLO must divide 64 (the tail starts on a multiple of 64 tiles)");
                 const long long ms = slot - head;                                  // the tiles' own slots
                 const long long blk = ms / (64 * kIl);
                 const long long tiles_in_blk = (A.n_local_tiles - blk * kIl) < kIl ? (A.n_local_tiles - blk * kIl) : kIl;

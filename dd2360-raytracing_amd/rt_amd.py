@@ -42,6 +42,8 @@ class Partition(C.Structure):
 
 WHOLE = Partition(0, 1)
 PART_RUN = 64          # rt_amd.h RT_PART_RUN: consecutive tiles per run of the tile split (tests restate the split with it)
+# rt_amd.h RT_SCHEDULE_WORDS: the words rt_render_ctx_schedule / rt_world_render_schedule copy, in this order
+SCHEDULE_FIELDS = ("inflight_thr", "static_thr", "tail_mark", "head", "head_thr", "from_end", "long_raw", "solo_raw")
 
 # every symbol include/rt_amd.h declares: (restype, argtypes)
 _vp, _i, _i64, _f = C.c_void_p, C.c_int, C.c_int64, C.c_float
@@ -82,6 +84,8 @@ SYMBOLS = {
     "rt_render_ctx_times": (_i, [_vp, _vp, _i, _vp]),
     "rt_render_ctx_counters": (_i, [_vp, _vp]),
     "rt_world_render_counters": (_i, [_vp, _vp]),
+    "rt_render_ctx_schedule": (_i, [_vp, _vp, _i]),
+    "rt_world_render_schedule": (_i, [_vp, _vp, _i]),
     "rt_render_kernel_name": (_i, [_vp, _vp, _i, _vp, _i]),
     "rt_multi_unique_id": (_i, [_vp]),
     "rt_multi_init": (_i, [_vp, _i, _i, _vp]),
@@ -187,6 +191,13 @@ class RenderCtx:
         out = np.zeros(4, np.uint32)
         check(lib().rt_render_ctx_counters(self.h, _np(out)), "rt_render_ctx_counters")
         return dict(zip(("slots", "thin_waves", "long_chains", "long_handles"), (int(v) for v in out)))
+
+    def schedule(self):
+        """the words that decided the latest launch's hand-out (rt_render_ctx_schedule): in-flight and pilot thresholds, tail mark
+        (first tail slot + 1), head count, head threshold, from-end flag, raw long / solo chain counts (before the use_long gate)"""
+        out = np.zeros(len(SCHEDULE_FIELDS), np.uint32)
+        check(lib().rt_render_ctx_schedule(self.h, _np(out), len(out)), "rt_render_ctx_schedule")
+        return dict(zip(SCHEDULE_FIELDS, (int(v) for v in out)))
 
     def close(self):
         if getattr(self, "h", None):
@@ -365,6 +376,12 @@ class World:
         out = np.zeros(4, np.uint32)
         check(lib().rt_world_render_counters(self.h, _np(out)), "rt_world_render_counters")
         return dict(zip(("slots", "thin_waves", "long_chains", "long_handles"), (int(v) for v in out)))
+
+    def render_schedule(self):
+        """the words that decided the hand-out of the latest render() on this world (see RenderCtx.schedule)"""
+        out = np.zeros(len(SCHEDULE_FIELDS), np.uint32)
+        check(lib().rt_world_render_schedule(self.h, _np(out), len(out)), "rt_world_render_schedule")
+        return dict(zip(SCHEDULE_FIELDS, (int(v) for v in out)))
 
     def close(self):
         if getattr(self, "h", None):

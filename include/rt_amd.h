@@ -209,8 +209,10 @@ int rt_render_progressive(void* fb, int max_x, int max_y, int current_sample, co
  * context each and go through the *_on entry points.  A context first used inside a hipGraph capture must have been
  * prepared before (rt_render_ctx_reserve, or one uncaptured call of the same frame size — in either precision: the binary16
  * render has a pilot pass and a workspace too); timing events are not recorded during a capture.  A captured rt_render_progressive pass
- * bakes the context's tile-order buffer into the graph: from then on the context refuses (RT_EINVAL) a progressive sequence of a
- * larger frame, which would have to move that buffer — give such a sequence a context of its own for the graph's lifetime. */
+ * bakes the context's tile-order buffer into the graph: from then on the context refuses (RT_EINVAL) the uncaptured first pass
+ * (current_sample == 1) of a progressive sequence of any other frame — another world or tree, size or partition — which would
+ * rewrite that order under the graph (or, for a larger frame, move it); a restart of the captured frame itself recomputes an
+ * order of the same tiles and is accepted.  Give another sequence a context of its own for the graph's lifetime. */
 int rt_render_ctx_create(rt_render_ctx** out);
 int rt_render_ctx_reserve(rt_render_ctx* ctx, int max_x, int max_y, rt_partition part);   /* workspace for frames of this size, now */
 int rt_render_ctx_destroy(rt_render_ctx* ctx);
@@ -239,6 +241,19 @@ int rt_world_render_times(rt_world* world, float* ms_out, int max, int* count);
  * give every captured render a context of its own (rt_render_ctx_create). */
 int rt_world_render_counters(rt_world* world, uint32_t* out4);
 int rt_render_ctx_counters(rt_render_ctx* ctx, uint32_t* out4);
+
+/* The words that decided the hand-out of the most recent rt_render on this world / context, read once that launch has finished
+ * (waits for it).  Copies the first min(n, RT_SCHEDULE_WORDS) of them into out (0 before any launch):
+ * out[0] = in-flight chain threshold (iterations; 0 = off), [1] = the pilot's long-chain threshold (3x3 pilot sum; 0 = off),
+ * [2] = first slot of the sorted tail + 1 (0 = no tail; the tail starts on a multiple of 64 tiles), [3] = tail pixels handed out
+ * before the tiles, [4] = the 3x3 pilot sum that decided them (0 = none), [5] = 1 when they come from the tail's cheap end,
+ * [6] / [7] = long chains / chains started alone in a wave that the pilot listed, before the render kernel's rule that honours
+ * them only while they are at most 1/64 of the slots.  [0]..[5] are written by the scheduling pass of the fp32 tree paths (from 4
+ * samples per pixel; the tail from 16): the binary16 and list paths leave them at 0.  Diagnostics only, like the counters —
+ * which lane renders a pixel never changes the pixel. */
+#define RT_SCHEDULE_WORDS 8
+int rt_world_render_schedule(rt_world* world, uint32_t* out, int n);
+int rt_render_ctx_schedule(rt_render_ctx* ctx, uint32_t* out, int n);
 
 /* Reassemble a full row-major frame from nparts tile-major part buffers laid out back to back, each padded to
  * rt_part_pixels(max_x,max_y,{0,nparts}) elements (the layout an all-gather of the parts produces). */
