@@ -31,6 +31,10 @@ hipError_t launch_trace_h(const DevScene& S, const DevTree& T, bool tree, const 
 hipError_t launch_assemble_h(void* full, const void* parts, int max_x, int max_y, int nparts, hipStream_t st);
 hipError_t launch_trace(const DevScene& S, const DevTree& T, bool tree, const float* rays, long long n, rt_hit_record* out, hipStream_t st);
 hipError_t launch_assemble(float* full, const float* parts, int max_x, int max_y, int nparts, hipStream_t st);
+hipError_t launch_render_adaptive(const RenderArgs& A, bool tree, hipStream_t st);
+hipError_t launch_adapt_check(float* fb, const float* sl, const float* q, const unsigned int* list_in, const unsigned int* count_in, long long n_all,
+                              unsigned int* list_out, unsigned int* count_out, int32_t* spp, int k, bool last, float rel_error, float floor_lum, hipStream_t st);
+hipError_t launch_adapt_zero(unsigned int* p, int n, hipStream_t st);
 const char* render_kernel_name(bool tree, int mode, const DevAccel& acc);
 namespace gpubuild { int build(rt_octree* O, const float4* d_geom, const int32_t* d_kind, int n, int spl, hipStream_t st); }
 const char* render_kernel_name_h(bool tree, int mode);
@@ -283,9 +287,39 @@ static int ctx_reserve_progressive(rt_render_ctx& C, int64_t tiles) {
     C.p_tiles = tiles;
     return 0;
 }
+// the workspace of rt_render_adaptive for frames of up to `pixels` pixels and `rounds` checks
+static int ctx_reserve_adaptive(rt_render_ctx& C, int64_t pixels, int rounds) {
+    if (C.a_pixels < pixels) {
+        void* old[3] = {C.a_sl, C.a_q, C.a_list};
+        C.a_sl = nullptr; C.a_q = nullptr; C.a_list = nullptr; C.a_pixels = 0;
+        int rc = free_all(old, 3);
+        if (rc) return rc;
+        void* nw[3] = {nullptr, nullptr, nullptr};
+        const size_t bytes[3] = {sizeof(float) * (size_t)pixels, sizeof(float) * (size_t)pixels, sizeof(unsigned int) * (size_t)pixels * 2};
+        for (int k = 0; k < 3; ++k) {
+            const hipError_t e = hipMalloc(&nw[k], bytes[k]);
+            if (e != hipSuccess) { (void)free_all(nw, 3); return (int)e; }
+        }
+        C.a_sl = (float*)nw[0]; C.a_q = (float*)nw[1]; C.a_list = (unsigned int*)nw[2]; C.a_pixels = pixels;
+    }
+    if (C.a_rounds < rounds) {
+        void* old[1] = {C.a_count};
+        C.a_count = nullptr; C.a_rounds = 0;
+        int rc = free_all(old, 1);
+        if (rc) return rc;
+        void* q = nullptr;
+        RT_TRY(hipMalloc(&q, sizeof(unsigned int) * (size_t)rounds));
+        C.a_count = (unsigned int*)q; C.a_rounds = rounds;
+    }
+    return 0;
+}
 static int ctx_release(rt_render_ctx& C) {
+    void* abufs[4] = {C.a_sl, C.a_q, C.a_list, C.a_count};
+    const int arc = free_all(abufs, 4);
+    C.a_sl = nullptr; C.a_q = nullptr; C.a_list = nullptr; C.a_count = nullptr; C.a_pixels = 0; C.a_rounds = 0;
     void* bufs[8] = {C.d_queue, C.d_cost, C.d_order, C.d_flags, C.d_long, C.p_cost, C.p_order, C.d_work};
-    const int rc = free_all(bufs, 8);
+    const int brc = free_all(bufs, 8);
+    const int rc = brc ? brc : arc;
     C.d_queue = nullptr; C.d_cost = nullptr; C.d_order = nullptr; C.d_flags = nullptr; C.d_long = nullptr; C.d_work = nullptr; C.sched_tiles = 0;
     C.p_cost = nullptr; C.p_order = nullptr; C.p_tiles = 0; C.p_valid = false;
     for (int k = 0; k < 64; ++k) { if (C.ev0[k]) (void)hipEventDestroy(C.ev0[k]); if (C.ev1[k]) (void)hipEventDestroy(C.ev1[k]); C.ev0[k] = nullptr; C.ev1[k] = nullptr; }
@@ -720,6 +754,33 @@ static bool capturing(hipStream_t st) {
     return cs != hipStreamCaptureStatusNone;
 }
 
+// the launch arguments every render kernel of a frame shares (no scheduling workspace yet)
+static RenderArgs frame_args(void* fb, int max_x, int max_y, int ns, const rt_world* world, rt_rand_state* d_rand_state, const rt_octree* d_octree, rt_partition part) {
+    RenderArgs A;
+    A.fb = fb; A.rand_state = d_rand_state; A.max_x = max_x; A.max_y = max_y; A.ns = ns;
+    A.tiles_x = (max_x + 7) / 8; A.tiles_y = (max_y + 7) / 8;
+    A.part = part.part; A.nparts = part.nparts; A.tile_begin = part.tile_begin; A.tile_end = part.tile_end;
+    const int64_t tiles = (int64_t)A.tiles_x * A.tiles_y;
+    A.n_local_tiles = local_tiles_of(tiles, part);
+    A.scene = world->z->dev;
+    A.tree = tree_args(d_octree);
+    A.order = nullptr; A.long_flag = nullptr; A.long_list = nullptr;
+    A.tail_list = nullptr; A.tail_ws = nullptr; A.f_tail = 0.f; A.head_sum = 0; A.head_sum_dense = 0; A.head_min_load = 0.f;
+    A.n_lanes = 0; A.f_inflight = tune_value("RT_F_INFLIGHT", RT_F_INFLIGHT); A.f_inflight_dense = tune_value("RT_F_INFLIGHT_DENSE", RT_F_INFLIGHT_DENSE); A.f_static = tune_value("RT_F_STATIC", RT_F_STATIC);
+    A.ad_list = nullptr; A.ad_count = nullptr; A.ad_sl = nullptr; A.ad_q = nullptr;
+    return A;
+}
+// the scheduling pass of rt_render (ns >= 4): pilot, tile order and — from 16 samples — the long chains and the sorted tail
+static int schedule_frame(rt_render_ctx& C, RenderArgs& A, const rt_world* world, const rt_octree* d_octree, int ns, hipStream_t st) {
+    const bool classify = ns >= 16;          // long-chain pre-classification pays only when chains are long
+    if (classify && world->precision != RT_PRECISION_FP16) { A.tail_list = C.d_long + (size_t)A.n_local_tiles * 64; A.tail_ws = C.d_long + (size_t)C.sched_tiles * 128; A.f_tail = tune_value("RT_F_TAIL", RT_F_TAIL); A.head_sum = (int)tune_value("RT_HEAD_SUM_SPARSE", (float)RT_HEAD_SUM_SPARSE); A.head_sum_dense = (int)tune_value("RT_HEAD_SUM_DENSE", (float)RT_HEAD_SUM_DENSE); A.head_min_load = tune_value("RT_HEAD_LOAD_DENSE", (float)RT_HEAD_LOAD_DENSE); }
+    if (world->precision == RT_PRECISION_FP16) RT_TRY(launch_tile_order_h(A, d_octree != nullptr, C.d_cost, C.d_order, classify ? C.d_flags : nullptr, classify ? C.d_long : nullptr, st));
+    else RT_TRY(launch_tile_order(A, d_octree != nullptr, C.d_cost, C.d_order, classify ? C.d_flags : nullptr, classify ? C.d_long : nullptr, st));
+    A.order = C.d_order;
+    if (classify) { A.long_flag = C.d_flags; A.long_list = C.d_long; }
+    return 0;
+}
+
 static int render_common(rt_render_ctx* ctx, void* fb, int max_x, int max_y, int ns, const rt_world* world, rt_rand_state* d_rand_state, const rt_octree* d_octree, rt_partition part, void* stream, int mode) {
     if (!world || max_x <= 0 || max_y <= 0 || ns <= 0 || !valid_partition(part)) return RT_EINVAL;
     if (d_octree && d_octree->precision != world->precision) return RT_EINVAL;
@@ -740,17 +801,7 @@ static int render_common(rt_render_ctx* ctx, void* fb, int max_x, int max_y, int
     // graph (a smaller frame or another part: an order that is no longer a permutation of the graph's tiles) — refused before
     // anything is launched.  A restart of the same frame recomputes an order of the same tiles.
     if (mode == 1 && ns == 1 && !cap && C.p_pinned && memcmp(C.p_key, key, sizeof(key)) != 0) return RT_EINVAL;
-    RenderArgs A;
-    A.fb = fb; A.rand_state = d_rand_state; A.max_x = max_x; A.max_y = max_y; A.ns = ns;
-    A.tiles_x = (max_x + 7) / 8; A.tiles_y = (max_y + 7) / 8;
-    A.part = part.part; A.nparts = part.nparts; A.tile_begin = part.tile_begin; A.tile_end = part.tile_end;
-    const int64_t tiles = (int64_t)A.tiles_x * A.tiles_y;
-    A.n_local_tiles = local_tiles_of(tiles, part);
-    A.scene = world->z->dev;
-    A.tree = tree_args(d_octree);
-    A.order = nullptr; A.long_flag = nullptr; A.long_list = nullptr;
-    A.tail_list = nullptr; A.tail_ws = nullptr; A.f_tail = 0.f; A.head_sum = 0; A.head_sum_dense = 0; A.head_min_load = 0.f;
-    A.n_lanes = 0; A.f_inflight = tune_value("RT_F_INFLIGHT", RT_F_INFLIGHT); A.f_inflight_dense = tune_value("RT_F_INFLIGHT_DENSE", RT_F_INFLIGHT_DENSE); A.f_static = tune_value("RT_F_STATIC", RT_F_STATIC);
+    RenderArgs A = frame_args(fb, max_x, max_y, ns, world, d_rand_state, d_octree, part);
     const bool sched = mode == 0 && ns >= 4;
     // expensive tiles first (k_tile_cost / k_tile_order).  The workspace grows on first use of a larger frame: call rt_render
     // (or rt_render_ctx_reserve) once before capturing it into a hipGraph.
@@ -779,14 +830,7 @@ static int render_common(rt_render_ctx* ctx, void* fb, int max_x, int max_y, int
         }
         if (C.p_valid && memcmp(C.p_key, key, sizeof(key)) == 0 && C.p_tiles >= A.n_local_tiles) { A.order = C.p_order; if (cap) C.p_pinned = true; }
     }
-    if (sched) {
-        const bool classify = ns >= 16;          // long-chain pre-classification pays only when chains are long
-        if (classify && world->precision != RT_PRECISION_FP16) { A.tail_list = C.d_long + (size_t)A.n_local_tiles * 64; A.tail_ws = C.d_long + (size_t)C.sched_tiles * 128; A.f_tail = tune_value("RT_F_TAIL", RT_F_TAIL); A.head_sum = (int)tune_value("RT_HEAD_SUM_SPARSE", (float)RT_HEAD_SUM_SPARSE); A.head_sum_dense = (int)tune_value("RT_HEAD_SUM_DENSE", (float)RT_HEAD_SUM_DENSE); A.head_min_load = tune_value("RT_HEAD_LOAD_DENSE", (float)RT_HEAD_LOAD_DENSE); }
-        if (world->precision == RT_PRECISION_FP16) RT_TRY(launch_tile_order_h(A, d_octree != nullptr, C.d_cost, C.d_order, classify ? C.d_flags : nullptr, classify ? C.d_long : nullptr, st));
-        else RT_TRY(launch_tile_order(A, d_octree != nullptr, C.d_cost, C.d_order, classify ? C.d_flags : nullptr, classify ? C.d_long : nullptr, st));
-        A.order = C.d_order;
-        if (classify) { A.long_flag = C.d_flags; A.long_list = C.d_long; }
-    }
+    if (sched && (rc = schedule_frame(C, A, world, d_octree, ns, st))) return rc;
     // timing events only outside a capture (recorded into a graph they would never be "recorded" for hipEventElapsedTime)
     const unsigned ek = C.ev_head % 64u;
     if (!cap) RT_TRY(hipEventRecord(C.ev0[ek], st));
@@ -878,6 +922,74 @@ int rt_render_on(rt_render_ctx* ctx, void* fb, int max_x, int max_y, int ns, con
 int rt_render_progressive_on(rt_render_ctx* ctx, void* fb, int max_x, int max_y, int current_sample, const rt_world* world, rt_rand_state* d_rand_state, const rt_octree* d_octree, rt_partition part, void* stream) {
     if (!ctx) return RT_EINVAL;
     return render_common(ctx, fb, max_x, max_y, current_sample, world, d_rand_state, d_octree, part, stream, 1);
+}
+
+// ---- adaptive sampling ------------------------------------------------------------------------------
+static bool adaptive_params_ok(const rt_adaptive* P) {
+    if (!P || P->min_spp < 2 || P->batch < 1 || P->max_spp < P->min_spp || (P->max_spp - P->min_spp) % P->batch != 0) return false;
+    return P->rel_error >= 0.f && P->floor >= 0.f;                    // (NaN fails both)
+}
+// Round 0: rt_render's scheduled launch with ns = min_spp, ending in the running sums; then a check, and (max_spp - min_spp) / batch
+// rounds of `batch` samples over the pixels the previous check left active, each followed by its check.  The number of launches
+// depends on the parameters alone: every round reads its active count from device memory, nothing comes back to the host.
+static int render_adaptive_common(rt_render_ctx* ctx, void* fb, int max_x, int max_y, const rt_adaptive* P, const rt_world* world,
+                                  rt_rand_state* d_rand_state, const rt_octree* d_octree, int32_t* d_spp, void* stream) {
+    if (!adaptive_params_ok(P) || !world || max_x <= 0 || max_y <= 0 || !fb || !d_rand_state) return RT_EINVAL;
+    if ((int64_t)max_x * max_y > (int64_t)0xffffffffll) return RT_EINVAL;          // pixel ids of the active lists are 32-bit
+    if (d_octree && d_octree->precision != world->precision) return RT_EINVAL;
+    if (world->precision == RT_PRECISION_FP16 || world->arith == RT_ARITH_CONTRACT) return RT_ENOTSUP;
+    const hipStream_t st = (hipStream_t)stream;
+    if (capturing(st)) return RT_EINVAL;                                 // the workspace may grow, the launches read it: never captured
+    int rc = ensure_on_device(world, d_octree);
+    rt_render_ctx& C = ctx ? *ctx : world->z->ctx;
+    if (!rc) rc = ctx_prepare(C);
+    if (rc) return rc;
+    const rt_partition whole = {0, 1, 0, 0};
+    const int64_t npx = (int64_t)max_x * max_y;
+    const int rounds = (P->max_spp - P->min_spp) / P->batch;
+    RenderArgs A = frame_args(fb, max_x, max_y, P->min_spp, world, d_rand_state, d_octree, whole);
+    const bool sched = P->min_spp >= 4;
+    if (sched && (rc = ctx_reserve(C, A.n_local_tiles))) return rc;
+    if ((rc = ctx_reserve_adaptive(C, npx, rounds + 1))) return rc;
+    if (C.has_done && C.last_stream != st) RT_TRY(hipStreamWaitEvent(st, C.done, 0));
+    const bool tree = d_octree != nullptr;
+    unsigned int* lists[2] = {C.a_list, C.a_list + npx};
+    A.ad_sl = C.a_sl; A.ad_q = C.a_q;
+    RT_TRY(launch_adapt_zero(C.a_count, rounds + 1, st));
+    A.queue = C.d_queue + (size_t)(C.launches++ % kQueueSlots) * kQueueStride;
+    RT_TRY(launch_zero_counters(A.queue, (int)kQueueStride, st));
+    if (sched && (rc = schedule_frame(C, A, world, d_octree, P->min_spp, st))) return rc;
+    const unsigned ek = C.ev_head % 64u;
+    RT_TRY(hipEventRecord(C.ev0[ek], st));
+    RT_TRY(launch_render_adaptive(A, tree, st));
+    RT_TRY(launch_adapt_check((float*)fb, C.a_sl, C.a_q, nullptr, nullptr, npx, lists[0], C.a_count, d_spp, P->min_spp, rounds == 0, P->rel_error, P->floor, st));
+    // resumed rounds: the previous check's list, no scheduling pass (the list is short and its order is the check's)
+    A.ns = P->batch;
+    A.order = nullptr; A.long_flag = nullptr; A.long_list = nullptr;
+    A.tail_list = nullptr; A.tail_ws = nullptr; A.f_tail = 0.f; A.head_sum = 0; A.head_sum_dense = 0; A.head_min_load = 0.f;
+    for (int r = 1; r <= rounds; ++r) {
+        A.ad_list = lists[(r - 1) & 1]; A.ad_count = C.a_count + (r - 1);
+        A.queue = C.d_queue + (size_t)(C.launches++ % kQueueSlots) * kQueueStride;
+        RT_TRY(launch_zero_counters(A.queue, (int)kQueueStride, st));
+        RT_TRY(launch_render_adaptive(A, tree, st));
+        RT_TRY(launch_adapt_check((float*)fb, C.a_sl, C.a_q, A.ad_list, A.ad_count, npx, lists[r & 1], C.a_count + r, d_spp,
+                                  P->min_spp + r * P->batch, r == rounds, P->rel_error, P->floor, st));
+    }
+    C.last_queue = A.queue;
+    RT_TRY(hipEventRecord(C.ev1[ek], st));
+    C.ev_head++; if (C.ev_count < 64) C.ev_count++;
+    RT_TRY(hipEventRecord(C.done, st));
+    C.has_done = true; C.last_stream = st;
+    return 0;
+}
+int rt_render_adaptive(void* fb, int max_x, int max_y, const rt_adaptive* params, const rt_world* world, rt_rand_state* d_rand_state,
+                       const rt_octree* d_octree, int32_t* d_spp, void* stream) {
+    return render_adaptive_common(nullptr, fb, max_x, max_y, params, world, d_rand_state, d_octree, d_spp, stream);
+}
+int rt_render_adaptive_on(rt_render_ctx* ctx, void* fb, int max_x, int max_y, const rt_adaptive* params, const rt_world* world,
+                          rt_rand_state* d_rand_state, const rt_octree* d_octree, int32_t* d_spp, void* stream) {
+    if (!ctx) return RT_EINVAL;
+    return render_adaptive_common(ctx, fb, max_x, max_y, params, world, d_rand_state, d_octree, d_spp, stream);
 }
 
 // the kernel rt_render (mode 0) / rt_render_progressive (mode 1) launches for this world and tree — the library's own

@@ -155,6 +155,13 @@ struct RenderArgs {
     const unsigned int* long_list;        // the pre-classified long chains (queue[2] = count, queue[3] = next to hand out)
     DevScene scene;
     DevTree tree;
+    // adaptive rounds (k_render<*, 2, *>, rt_render_adaptive): the lane leaves the running sums behind — fb = S_rgb, ad_sl = sum of the
+    // samples' luminance, ad_q = sum of its squares — instead of the final colour.  ad_list == NULL: round 0, the whole frame through
+    // the scheduled hand-out, from zero; otherwise the pixels (row-major indices) still active, *ad_count of them, resumed from the sums.
+    const unsigned int* ad_list;
+    const unsigned int* ad_count;
+    float* ad_sl;
+    float* ad_q;
 };
 
 } // namespace rt

@@ -1144,7 +1144,9 @@ __global__ __launch_bounds__(256) void k_render_init(rt_rand_state* rand_state, 
 }
 #endif
 
-// MODE 0: render (ns samples, /ns, sqrt).  MODE 1: render_progressive (one sample, accumulate).
+// MODE 0: render (ns samples, /ns, sqrt).  MODE 1: render_progressive (one sample, accumulate).  MODE 2: one round of
+// rt_render_adaptive — ns samples more per pixel, the running sums left behind instead of the colour (RenderArgs::ad_*); every
+// line that only MODE 2 needs sits behind `if constexpr`, so the MODE 0 / 1 instantiations compile to what they were.
 //
 // Persistent waves: the grid is sized to what the chip holds at once.  Pixel slots are numbered tile-major
 // (slot = local_tile*64 + ly*8 + lx, the 8x8 block shape of the reference); every lane starts on slot
@@ -1164,8 +1166,8 @@ __global__ __launch_bounds__(256, RT_RENDER_WAVES) void k_render(RenderArgs A) {
     extern __shared__ float4 s_nodes[];
     if (TREE) stage_tree_fp32<COOPG != 1>(A.scene, A.tree, s_nodes);
     const int lane = threadIdx.x & 63;
-    const long long n_slots = A.n_local_tiles * 64;
-    const int ns = (MODE == 0) ? A.ns : 1;
+    const long long n_slots = (MODE == 2 && A.ad_list) ? (long long)*A.ad_count : A.n_local_tiles * 64;
+    const int ns = (MODE != 1) ? A.ns : 1;
 
     const long long n_waves = (long long)gridDim.x * 4;
     long long slot = 0;
@@ -1186,6 +1188,7 @@ __global__ __launch_bounds__(256, RT_RENDER_WAVES) void k_render(RenderArgs A) {
     Rng s = {0, 0, 0, 0, 0, 0};
     V3 col = {0.0f, 0.0f, 0.0f};
     V3 att = {1.0f, 1.0f, 1.0f};
+    float sum_l = 0.0f, sum_q = 0.0f;   // MODE 2: the pixel's running luminance sum and sum of squares
     RayF r; r.o = {0.f, 0.f, 0.f}; r.d = {0.f, 1.f, 0.f};
     int sample = 0, depth = 0;
     bool live = false;
@@ -1216,6 +1219,14 @@ __global__ __launch_bounds__(256, RT_RENDER_WAVES) void k_render(RenderArgs A) {
 #endif
         iters = 0; is_long = false; is_med = false;
         while (slot < n_slots) {
+            if constexpr (MODE == 2) {
+                if (A.ad_list) {                                   // a resumed round: the list of the pixels still active, in any order
+                    const unsigned int pid = A.ad_list[slot];
+                    idx = (long long)pid; i = (int)(pid % (unsigned int)A.max_x); j = (int)(pid / (unsigned int)A.max_x);
+                    live = true;
+                    break;
+                }
+            }
             // Slots are interleaved over blocks of 64 tiles (in hand-out order): consecutive slots are the same pixel
             // position of 64 different tiles, so the pixels of one tile (long chains cluster) never travel together.
             // The END of the queue is handed out per pixel, most expensive 2x2 pilot block first (k_tail_hist / k_tail_scatter): a launch with few pixels
@@ -1223,7 +1234,7 @@ __global__ __launch_bounds__(256, RT_RENDER_WAVES) void k_render(RenderArgs A) {
             long long local_tile; int l;
             // On sparse grids that list is handed out FIRST (its first `head` entries, k_tail_scatter: all of it but the blocks outside the
             // frame), then the tiles, most expensive class first: C3 13.9 -> 13.2 ms, C2 10.4 -> 9.3 (rt_tuning.h RT_HEAD_SUM_SPARSE).
-            const long long tail0 = (MODE == 0 && A.tail_list) ? (long long)A.queue[kQueueThr + 2] : 0;
+            const long long tail0 = (MODE != 1 && A.tail_list) ? (long long)A.queue[kQueueThr + 2] : 0;
             const long long head = tail0 > 0 ? (long long)A.queue[kQueueThr + 3] : 0;
             if (tail0 > 0 && (slot < head || slot >= tail0 - 1 + head)) {
                 // (head taken from the list's cheap END — queue[kQueueThr + 5] — : the sky first, the rest of the list, most expensive first, last)
@@ -1263,6 +1274,13 @@ __global__ __launch_bounds__(256, RT_RENDER_WAVES) void k_render(RenderArgs A) {
             const rt_rand_state* st = A.rand_state + idx;
             s.d = st->d; s.v0 = st->v[0]; s.v1 = st->v[1]; s.v2 = st->v[2]; s.v3 = st->v[3]; s.v4 = st->v[4];
             col = {0.0f, 0.0f, 0.0f}; att = {1.0f, 1.0f, 1.0f}; sample = 0; depth = 0;
+            if constexpr (MODE == 2) {
+                sum_l = 0.0f; sum_q = 0.0f;
+                if (A.ad_list) {
+                    const float* f = (const float*)A.fb + idx * 3;
+                    col.x = f[0]; col.y = f[1]; col.z = f[2]; sum_l = A.ad_sl[idx]; sum_q = A.ad_q[idx];
+                }
+            }
             r = primary_ray(A.scene.cam, i, j, A.max_x, A.max_y, s);
         }
     };
@@ -1298,6 +1316,7 @@ __global__ __launch_bounds__(256, RT_RENDER_WAVES) void k_render(RenderArgs A) {
         const rt_rand_state* st = A.rand_state + idx;
         s.d = st->d; s.v0 = st->v[0]; s.v1 = st->v[1]; s.v2 = st->v[2]; s.v3 = st->v[3]; s.v4 = st->v[4];
         col = {0.0f, 0.0f, 0.0f}; att = {1.0f, 1.0f, 1.0f}; sample = 0; depth = 0;
+        if constexpr (MODE == 2) { sum_l = 0.0f; sum_q = 0.0f; }     // (long chains are listed in round 0 only)
         r = primary_ray(A.scene.cam, i, j, A.max_x, A.max_y, s);
         return true;
     };
@@ -1307,7 +1326,10 @@ __global__ __launch_bounds__(256, RT_RENDER_WAVES) void k_render(RenderArgs A) {
         rt_rand_state* st_out = A.rand_state + idx;
         st_out->d = s.d; st_out->v[0] = s.v0; st_out->v[1] = s.v1; st_out->v[2] = s.v2; st_out->v[3] = s.v3; st_out->v[4] = s.v4;
         float* fb = (float*)A.fb + idx * 3;
-        if (MODE == 0) {
+        if constexpr (MODE == 2) {
+            fb[0] = col.x; fb[1] = col.y; fb[2] = col.z;                 // S_rgb: the check kernel divides and takes the root
+            A.ad_sl[idx] = sum_l; A.ad_q[idx] = sum_q;
+        } else if (MODE == 0) {
             const float k = (float)(1.0 / (double)(float)A.ns);          // vec3::operator/=(real_t): 1.0/t in double (vec3.h:137)
             col.x *= k; col.y *= k; col.z *= k;
             fb[0] = sqrtf(col.x); fb[1] = sqrtf(col.y); fb[2] = sqrtf(col.z);
@@ -1405,6 +1427,7 @@ __global__ __launch_bounds__(256, RT_RENDER_WAVES) void k_render(RenderArgs A) {
         if (live && !(TREE && ts.pending)) {
             ++iters;
             bool done;                                     // this sample's path has ended
+            float lum = 0.0f;                              // MODE 2: (c.x + c.y) + c.z of the sample (0 for an absorbed path)
             if (best >= 0) {
                 const bool cont = scatter(cold_args()->scene, best, closest, r, att, s);
                 ++depth;
@@ -1412,9 +1435,12 @@ __global__ __launch_bounds__(256, RT_RENDER_WAVES) void k_render(RenderArgs A) {
             } else {
                 const V3 c = sky(r, att);
                 col.x += c.x; col.y += c.y; col.z += c.z;
+                if constexpr (MODE == 2) lum = (c.x + c.y) + c.z;
                 done = true;
             }
             if (done) {
+                if constexpr (MODE == 2) { sum_l += lum; sum_q += lum * lum; }
+                (void)lum;
                 ++sample; depth = 0; att = {1.0f, 1.0f, 1.0f};
                 if (sample < ns) {
                     { const RenderArgs& C = *cold_args(); r = primary_ray(C.scene.cam, i, j, C.max_x, C.max_y, s); }
@@ -1423,7 +1449,7 @@ __global__ __launch_bounds__(256, RT_RENDER_WAVES) void k_render(RenderArgs A) {
                     // part of what ONE lane works through in this launch (queue[kQueueThr]; 0 when no scheduling pass ran)
                     bool now_long = false;
                     if ((sample & (RT_LONG_CHECK - 1)) == 0 && sample + 8 <= ns) {
-                        const unsigned int long_thr = MODE == 0 ? cold_args()->queue[kQueueThr] : 0u;
+                        const unsigned int long_thr = MODE != 1 ? cold_args()->queue[kQueueThr] : 0u;
                         now_long = iters >= (unsigned int)((COOPG == 2 ? RT_LONG_RATE_DENSE : RT_LONG_RATE) * sample) ||
                                    (long_thr != 0u && (unsigned long long)iters * (unsigned int)ns >= (unsigned long long)long_thr * (unsigned int)sample);
                     }
@@ -1475,6 +1501,58 @@ __global__ __launch_bounds__(256, RT_RENDER_WAVES) void k_render(RenderArgs A) {
     }
     )
 }
+
+// ---------------------------------------------------------------------------------------------------- adaptive sampling
+#if !defined(RT_TU_LIST) && !defined(RT_TU_CONTRACT)
+// rt_render_adaptive's check after a round that left every active pixel at k samples.  The stop rule of
+// include/rt_amd.h, one IEEE binary32 rounding per operation: a pixel stops when rel_error > 0 and
+// k*Q - S*S <= (rel_error^2 * (k-1)) * max(S, k*floor)^2 (S, Q: sums of the samples' luminance and of its squares), or when the
+// round is the last one.  A stopped pixel gets rt_render's colour at ns = k (k_render MODE 0's end_pixel: the reciprocal in
+// double, then sqrtf) and its count; the others are appended to list_out, one atomic per wave — their order never changes a pixel.
+// list_in == NULL: round 0, pixel t of the frame for thread t.
+__global__ __launch_bounds__(256) void k_adapt_check(float* __restrict__ fb, const float* __restrict__ sl, const float* __restrict__ q,
+                                                     const unsigned int* __restrict__ list_in, const unsigned int* __restrict__ count_in, long long n_all,
+                                                     unsigned int* __restrict__ list_out, unsigned int* __restrict__ count_out, int32_t* __restrict__ spp,
+                                                     int k, int last, float rel_error, float floor_lum) {
+    const long long t = (long long)blockIdx.x * 256 + threadIdx.x;
+    const long long n = count_in ? (long long)*count_in : n_all;
+    bool active = false;
+    unsigned int pid = 0;
+    if (t < n) {
+        pid = list_in ? list_in[t] : (unsigned int)t;
+        bool stop = last != 0;
+        if (!stop) {
+            const float nk = (float)k;
+            const float S = sl[pid], Q = q[pid];
+            const float d = nk * Q - S * S;
+            const float nf = nk * floor_lum;
+            const float m = S > nf ? S : nf;
+            const float tt = rel_error * rel_error;
+            stop = rel_error > 0.f && d <= (tt * (nk - 1.f)) * (m * m);      // NaN anywhere: false, the pixel runs on
+        }
+        if (stop) {
+            float* f = fb + (size_t)pid * 3;
+            const float kk = (float)(1.0 / (double)(float)k);                // vec3::operator/=(real_t), as k_render MODE 0
+            f[0] = sqrtf(f[0] * kk); f[1] = sqrtf(f[1] * kk); f[2] = sqrtf(f[2] * kk);
+            if (spp) spp[pid] = k;
+        } else {
+            active = true;
+        }
+    }
+    const unsigned long long mask = __ballot(active);
+    if (mask != 0ull) {
+        unsigned int base = 0;
+        if ((threadIdx.x & 63) == 0) base = atomicAdd(count_out, (unsigned int)__popcll(mask));
+        base = __shfl(base, 0);
+        const unsigned int rank = __builtin_amdgcn_mbcnt_hi((unsigned)(mask >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)mask, 0u));
+        if (active) list_out[base + rank] = pid;
+    }
+}
+__global__ __launch_bounds__(256) void k_adapt_zero(unsigned int* p, int n) {
+    const int t = blockIdx.x * 256 + threadIdx.x;
+    if (t < n) p[t] = 0u;
+}
+#endif
 
 // ---------------------------------------------------------------------------------------------------- scheduling
 // Longest-processing-time-first hand-out order for the persistent render kernel.  A pixel is a strictly serial chain
@@ -1933,10 +2011,19 @@ hipError_t RT_LIST_FN(launch_trace)(const RenderArgs& A, unsigned blocks, const 
     hipLaunchKernelGGL((k_trace<false>), dim3(blocks), dim3(256), 0, st, A, rays, n, out);
     return hipGetLastError();
 }
+#ifndef RT_TU_CONTRACT
+hipError_t RT_LIST_FN(launch_render_adaptive)(const RenderArgs& A, hipStream_t st) {
+    const unsigned need = (unsigned)((A.n_local_tiles + 3) / 4);
+    const unsigned cap = resident_blocks(k_render<false, 2, 1>, 0);
+    hipLaunchKernelGGL((k_render<false, 2, 1>), dim3(need < cap ? need : cap), dim3(256), 0, st, A);
+    return hipGetLastError();
+}
+#endif
 #else
 hipError_t launch_tile_cost_list(const RenderArgs& A, unsigned blocks, int* cost, unsigned char* pilot, hipStream_t st);
 hipError_t launch_render_list(const RenderArgs& A, int mode, hipStream_t st);
 hipError_t launch_trace_list(const RenderArgs& A, unsigned blocks, const float* rays, long long n, rt_hit_record* out, hipStream_t st);
+hipError_t launch_render_adaptive_list(const RenderArgs& A, hipStream_t st);
 #endif
 
 #ifndef RT_TU_LIST
@@ -2050,6 +2137,32 @@ hipError_t launch_render(const RenderArgs& A, bool tree, int mode, hipStream_t s
     if (variant == 2) return mode == 0 ? launch_render_tree<0, 2>(A, lds, st) : launch_render_tree<1, 2>(A, lds, st);
     return mode == 0 ? launch_render_tree<0, 1>(A, lds, st) : launch_render_tree<1, 1>(A, lds, st);
 }
+
+#ifndef RT_TU_CONTRACT
+// one round of rt_render_adaptive: k_render<*, 2, *> of the variant rt_render would launch (the contracted arithmetic has no adaptive mode)
+hipError_t launch_render_adaptive(const RenderArgs& A, bool tree, hipStream_t st) {
+    if (A.n_local_tiles <= 0) return hipSuccess;
+    const int variant = render_variant(tree, 0, A.tree.acc);
+    if (variant == 0) return launch_render_adaptive_list(A, st);
+    const size_t lds = tree_lds_bytes(A.tree.n_nodes, variant != 1);
+    if (variant == 5) return launch_render_tree<2, 5>(A, lds, st);
+    if (variant == 4) return launch_render_tree<2, 4>(A, lds, st);
+    if (variant == 2) return launch_render_tree<2, 2>(A, lds, st);
+    return launch_render_tree<2, 1>(A, lds, st);
+}
+hipError_t launch_adapt_check(float* fb, const float* sl, const float* q, const unsigned int* list_in, const unsigned int* count_in, long long n_all,
+                              unsigned int* list_out, unsigned int* count_out, int32_t* spp, int k, bool last, float rel_error, float floor_lum, hipStream_t st) {
+    if (n_all <= 0) return hipSuccess;
+    hipLaunchKernelGGL(k_adapt_check, dim3((unsigned)((n_all + 255) / 256)), dim3(256), 0, st, fb, sl, q, list_in, count_in, n_all, list_out, count_out, spp,
+                       k, last ? 1 : 0, rel_error, floor_lum);
+    return hipGetLastError();
+}
+hipError_t launch_adapt_zero(unsigned int* p, int n, hipStream_t st) {
+    if (n <= 0) return hipSuccess;
+    hipLaunchKernelGGL(k_adapt_zero, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, p, n);
+    return hipGetLastError();
+}
+#endif
 
 hipError_t launch_trace(const DevScene& S, const DevTree& T, bool tree, const float* rays, long long n, rt_hit_record* out, hipStream_t st) {
     if (n <= 0) return hipSuccess;

@@ -6,6 +6,10 @@
 //   rt_main [output_mode] [NUM_SPHERES] [nx] [ny] [ns] [USE_OCTREE 0|1] [SPHERES_PER_LEAF] [SPHERE_RADIUS] [USE_FP16 0|1] [BUILD_ON_GPU 0|1]
 // with the reference's values as defaults (main.cu:22-24, :348-350; acceleration_structure.h:15).  BUILD_ON_GPU 1 replaces
 // buildOctree + upload (main.cu:405-417) by rt_build_octree_gpu: the same tree, built on the device.
+// Adaptive sampling (no reference counterpart) takes four more optional arguments:
+//   ... [REL_ERROR] [MIN_SPP] [BATCH] [FLOOR]
+// REL_ERROR > 0 renders through rt_render_adaptive with max_spp = ns: MIN_SPP defaults to 4 (ns if smaller), BATCH to the largest of
+// 4, 2, 1 that divides ns - MIN_SPP, FLOOR to 0.  Without REL_ERROR (or with 0) the program does exactly what it does without them.
 #include <iostream>
 #include <string>
 #include <vector>
@@ -33,6 +37,8 @@ int main(int argc, char** argv) {
     float sphere_radius = 0.1f;          // SPHERE_RADIUS
     int use_fp16 = 0;                    // USE_FP16
     int build_on_gpu = 0;
+    float rel_error = 0.f, floor_lum = 0.f;   // adaptive sampling (rt_render_adaptive): off
+    int min_spp = -1, batch = -1;
     const int tx = 8, ty = 8;
     if (argc > 1) output_mode = std::stoi(argv[1]);
     if (argc > 2) num_spheres = std::stoi(argv[2]);
@@ -44,6 +50,13 @@ int main(int argc, char** argv) {
     if (argc > 8) sphere_radius = std::stof(argv[8]);
     if (argc > 9) use_fp16 = std::stoi(argv[9]);
     if (argc > 10) build_on_gpu = std::stoi(argv[10]);
+    if (argc > 11) rel_error = std::stof(argv[11]);
+    if (argc > 12) min_spp = std::stoi(argv[12]);
+    if (argc > 13) batch = std::stoi(argv[13]);
+    if (argc > 14) floor_lum = std::stof(argv[14]);
+    const bool adaptive = rel_error > 0.f;
+    if (min_spp < 0) min_spp = ns < 4 ? ns : 4;
+    if (batch < 0) batch = (ns - min_spp) % 4 == 0 ? 4 : ((ns - min_spp) % 2 == 0 ? 2 : 1);
     const int precision = use_fp16 ? RT_PRECISION_FP16 : RT_PRECISION_FP32;
 
     std::cerr << "Rendering a " << nx << "x" << ny << " image with " << ns << " samples per pixel ";
@@ -52,6 +65,9 @@ int main(int argc, char** argv) {
     std::cerr << "Sphere radius: " << sphere_radius << "\n";
     std::cerr << (use_octree ? "Use octree: ON\n" : "Use octree: OFF\n");
     std::cerr << "Output mode: " << output_mode << "\n";
+    if (adaptive)
+        std::cerr << "Adaptive sampling: " << min_spp << " to " << ns << " samples per pixel in steps of " << batch << ", relative error " << rel_error
+                  << ", floor " << floor_lum << "\n";
 
     checkHipErrors(rt_device_check(nullptr));
     const rt_partition whole = {0, 1};
@@ -92,11 +108,26 @@ int main(int argc, char** argv) {
     start = clock();
     checkHipErrors(rt_render_init(nx, ny, d_rand_state, whole, nullptr));
     checkHipErrors(hipDeviceSynchronize());
-    checkHipErrors(rt_render(fb, nx, ny, ns, d_world, d_rand_state, d_octree, whole, nullptr));
+    int32_t* d_spp = nullptr;
+    if (adaptive) {
+        const rt_adaptive params = {min_spp, ns, batch, rel_error, floor_lum};
+        checkHipErrors(hipMalloc(reinterpret_cast<void**>(&d_spp), num_pixels * sizeof(int32_t)));
+        checkHipErrors(rt_render_adaptive(fb, nx, ny, &params, d_world, d_rand_state, d_octree, d_spp, nullptr));
+    } else {
+        checkHipErrors(rt_render(fb, nx, ny, ns, d_world, d_rand_state, d_octree, whole, nullptr));
+    }
     checkHipErrors(hipDeviceSynchronize());
     stop = clock();
     const double timer_seconds = static_cast<double>(stop - start) / CLOCKS_PER_SEC;
     std::cerr << "took " << timer_seconds << " seconds.\n";
+    if (adaptive) {
+        std::vector<int32_t> spp(num_pixels);
+        checkHipErrors(hipMemcpy(spp.data(), d_spp, num_pixels * sizeof(int32_t), hipMemcpyDeviceToHost));
+        double total = 0.0;
+        for (int32_t k : spp) total += k;
+        std::cerr << "mean samples per pixel: " << total / (double)num_pixels << "\n";
+        checkHipErrors(hipFree(d_spp));
+    }
 
     if (output_mode == 0 || output_mode == 3) {
         std::vector<char> host(fb_size);

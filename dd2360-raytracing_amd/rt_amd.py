@@ -45,6 +45,12 @@ PART_RUN = 64          # rt_amd.h RT_PART_RUN: consecutive tiles per run of the 
 # rt_amd.h RT_SCHEDULE_WORDS: the words rt_render_ctx_schedule / rt_world_render_schedule copy, in this order
 SCHEDULE_FIELDS = ("inflight_thr", "static_thr", "tail_mark", "head", "head_thr", "from_end", "long_raw", "solo_raw")
 
+class Adaptive(C.Structure):
+    """rt_adaptive: min_spp samples for every pixel, then `batch` more at a time for the pixels whose relative standard error of the
+    mean luminance (the mean floored at `floor`) is still above rel_error, up to max_spp (include/rt_amd.h states the exact rule)"""
+    _fields_ = [("min_spp", C.c_int32), ("max_spp", C.c_int32), ("batch", C.c_int32), ("rel_error", C.c_float), ("floor", C.c_float)]
+
+
 # every symbol include/rt_amd.h declares: (restype, argtypes)
 _vp, _i, _i64, _f = C.c_void_p, C.c_int, C.c_int64, C.c_float
 SYMBOLS = {
@@ -81,6 +87,8 @@ SYMBOLS = {
     "rt_render_ctx_destroy": (_i, [_vp]),
     "rt_render_on": (_i, [_vp, _vp, _i, _i, _i, _vp, _vp, _vp, Partition, _vp]),
     "rt_render_progressive_on": (_i, [_vp, _vp, _i, _i, _i, _vp, _vp, _vp, Partition, _vp]),
+    "rt_render_adaptive": (_i, [_vp, _i, _i, C.POINTER(Adaptive), _vp, _vp, _vp, _vp, _vp]),
+    "rt_render_adaptive_on": (_i, [_vp, _vp, _i, _i, C.POINTER(Adaptive), _vp, _vp, _vp, _vp, _vp]),
     "rt_render_ctx_times": (_i, [_vp, _vp, _i, _vp]),
     "rt_render_ctx_counters": (_i, [_vp, _vp]),
     "rt_world_render_counters": (_i, [_vp, _vp]),
@@ -179,6 +187,12 @@ class RenderCtx:
     def render(self, fb, max_x, max_y, ns, world, d_rand_state, octree=None, part=None, stream=None):
         check(lib().rt_render_on(self.h, _dev(fb), max_x, max_y, ns, world.h, _dev(d_rand_state), octree.h if octree is not None else None,
                                  part or WHOLE, C.c_void_p(stream) if stream is not None else _stream()), "rt_render_on")
+
+    def render_adaptive(self, fb, max_x, max_y, params, world, d_rand_state, octree=None, d_spp=None, stream=None):
+        """rt_render_adaptive_on: params is an Adaptive; d_spp (optional) an int32 tensor of max_x * max_y"""
+        check(lib().rt_render_adaptive_on(self.h, _dev(fb), max_x, max_y, C.byref(params), world.h, _dev(d_rand_state),
+                                          octree.h if octree is not None else None, _dev(d_spp) if d_spp is not None else None,
+                                          C.c_void_p(stream) if stream is not None else _stream()), "rt_render_adaptive_on")
 
     def times(self):
         out = np.zeros(64, np.float32)
@@ -496,6 +510,12 @@ def render(fb, max_x, max_y, ns, world, d_rand_state, octree=None, part=WHOLE):
 def render_progressive(fb, max_x, max_y, current_sample, world, d_rand_state, octree=None, part=WHOLE):
     check(lib().rt_render_progressive(_dev(fb), max_x, max_y, current_sample, world.h, _dev(d_rand_state),
                                       octree.h if octree is not None else None, part, _stream()), "rt_render_progressive")
+
+
+def render_adaptive(fb, max_x, max_y, params, world, d_rand_state, octree=None, d_spp=None):
+    """rt_render_adaptive on the current stream: params is an Adaptive; d_spp (optional) an int32 tensor of max_x * max_y"""
+    check(lib().rt_render_adaptive(_dev(fb), max_x, max_y, C.byref(params), world.h, _dev(d_rand_state), octree.h if octree is not None else None,
+                                   _dev(d_spp) if d_spp is not None else None, _stream()), "rt_render_adaptive")
 
 
 def assemble(fb_full, fb_parts, max_x, max_y, nparts, precision=FP32):

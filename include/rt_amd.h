@@ -222,6 +222,38 @@ int rt_render_progressive_on(rt_render_ctx* ctx, void* fb, int max_x, int max_y,
                              rt_rand_state* d_rand_state, const rt_octree* d_octree, rt_partition part, void* stream);
 int rt_render_ctx_times(rt_render_ctx* ctx, float* ms_out, int max, int* count);           /* as rt_world_render_times */
 
+/* Adaptive sampling: every pixel takes min_spp samples, then, every `batch` samples, only the pixels whose estimated error is
+ * still above the target take more, up to max_spp (no reference counterpart; extends rt_render, main.cu:96-117).
+ * The stop rule, after k samples of a pixel (k = min_spp, min_spp + batch, ...), in IEEE binary32, one rounding per operation:
+ *   S_rgb = the sum of the sample colours (rt_render's col), SL = sum of l, Q = sum of l * l, where l = (c.x + c.y) + c.z is the
+ *   sample's colour c (0 for an absorbed path), all summed in sample order;
+ *   n = (float)k;  d = n * Q - SL * SL;  m = SL > n * floor ? SL : n * floor;  t = rel_error * rel_error;
+ *   the pixel stops when  rel_error > 0 && d <= (t * (n - 1)) * (m * m)
+ * (relative standard error of the mean luminance <= rel_error, the mean floored at `floor`, both sides multiplied out), or at
+ * k == max_spp.  A NaN sample makes the comparison false: such a pixel runs to max_spp.  rel_error == 0: every pixel runs to max_spp.
+ * Every pixel has its own RNG stream, so the frame is a per-pixel truncation of the uniform render, bit for bit: a pixel that stopped
+ * after k samples holds exactly the colour and the written-back RNG state that rt_render with ns = k gives it. */
+typedef struct rt_adaptive {
+    int32_t min_spp;    /* samples every pixel takes before the first check (>= 2) */
+    int32_t max_spp;    /* cap; (max_spp - min_spp) % batch == 0 */
+    int32_t batch;      /* samples between two checks (>= 1) */
+    float rel_error;    /* target relative standard error of the pixel's mean luminance; 0 = never stop early */
+    float floor;        /* luminance level below which the error is measured against this level instead (>= 0) */
+} rt_adaptive;
+/* The whole frame (no partition), reference layout.  d_rand_state has been through rt_render_init, as for rt_render; d_octree == NULL
+ * selects the hitable_list path.  fb receives the gamma-corrected colour (3 x float per pixel), d_spp (optional, may be NULL; one
+ * int32 per pixel) each pixel's sample count, d_rand_state the written-back states.  Asynchronous on `stream`, no host
+ * synchronisation: 1 + (max_spp - min_spp) / batch rounds of a render and a check kernel, each round reading its active-pixel count
+ * from device memory.  Until that work has finished, fb holds running sums for some pixels.
+ * RT_EINVAL for bad parameters and frames of more than 2^32 - 1 pixels; RT_ENOTSUP for USE_FP16 worlds and RT_ARITH_CONTRACT worlds.
+ * Graph capture is not supported: RT_EINVAL while `stream` is capturing.  The workspace (two floats and two list entries per pixel,
+ * one word per round) lives in the render context, grown on demand; the _on form takes a context of the caller's, as
+ * rt_render_on does. */
+int rt_render_adaptive(void* fb, int max_x, int max_y, const rt_adaptive* params, const rt_world* world, rt_rand_state* d_rand_state,
+                       const rt_octree* d_octree, int32_t* d_spp, void* stream);
+int rt_render_adaptive_on(rt_render_ctx* ctx, void* fb, int max_x, int max_y, const rt_adaptive* params, const rt_world* world,
+                          rt_rand_state* d_rand_state, const rt_octree* d_octree, int32_t* d_spp, void* stream);
+
 /* Name of the kernel rt_render (mode 0) / rt_render_progressive (mode 1) launches for this world and tree (d_octree NULL =
  * the hitable_list path), as rocprofv3 shows it without the namespace: "k_render<true,0,4>", "k_render_h<true,0>", ... */
 int rt_render_kernel_name(const rt_world* world, const rt_octree* d_octree, int mode, char* out, int cap);
