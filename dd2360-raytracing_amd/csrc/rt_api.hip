@@ -33,7 +33,8 @@ hipError_t launch_trace(const DevScene& S, const DevTree& T, bool tree, const fl
 hipError_t launch_assemble(float* full, const float* parts, int max_x, int max_y, int nparts, hipStream_t st);
 hipError_t launch_render_adaptive(const RenderArgs& A, bool tree, hipStream_t st);
 hipError_t launch_adapt_check(float* fb, const float* sl, const float* q, const unsigned int* list_in, const unsigned int* count_in, long long n_all,
-                              unsigned int* list_out, unsigned int* count_out, int32_t* spp, int k, bool last, float rel_error, float floor_lum, hipStream_t st);
+                              unsigned int* list_out, unsigned int* count_out, int32_t* spp, int k, bool last, float rel_error, float floor_lum,
+                              const AdaptFrame& fr, hipStream_t st);
 hipError_t launch_adapt_zero(unsigned int* p, int n, hipStream_t st);
 const char* render_kernel_name(bool tree, int mode, const DevAccel& acc);
 namespace gpubuild { int build(rt_octree* O, const float4* d_geom, const int32_t* d_kind, int n, int spl, hipStream_t st); }
@@ -112,6 +113,11 @@ static bool valid_partition(rt_partition p) {
     if (!(p.nparts >= 1 && p.part >= 0 && p.part < p.nparts)) return false;
     if (p.tile_begin == 0 && p.tile_end == 0) return true;                          // runs of RT_PART_RUN tiles
     return p.tile_begin >= 0 && p.tile_end > p.tile_begin;                          // a range of tiles (checked against the frame where the frame is known)
+}
+// rt_adaptive's parameter rule (rt_multi_render_adaptive checks it too)
+bool adaptive_params_ok(const rt_adaptive* P) {
+    if (!P || P->min_spp < 2 || P->batch < 1 || P->max_spp < P->min_spp || (P->max_spp - P->min_spp) % P->batch != 0) return false;
+    return P->rel_error >= 0.f && P->floor >= 0.f;                    // (NaN fails both)
 }
 static bool range_in_frame(rt_partition p, int64_t tiles) { return p.tile_end <= p.tile_begin || p.tile_end <= tiles; }
 static int64_t local_tiles_of(int64_t tiles, rt_partition p) { return part_local_tiles(tiles, p.part, p.nparts, p.tile_begin, p.tile_end); }
@@ -925,17 +931,18 @@ int rt_render_progressive_on(rt_render_ctx* ctx, void* fb, int max_x, int max_y,
 }
 
 // ---- adaptive sampling ------------------------------------------------------------------------------
-static bool adaptive_params_ok(const rt_adaptive* P) {
-    if (!P || P->min_spp < 2 || P->batch < 1 || P->max_spp < P->min_spp || (P->max_spp - P->min_spp) % P->batch != 0) return false;
-    return P->rel_error >= 0.f && P->floor >= 0.f;                    // (NaN fails both)
-}
 // Round 0: rt_render's scheduled launch with ns = min_spp, ending in the running sums; then a check, and (max_spp - min_spp) / batch
 // rounds of `batch` samples over the pixels the previous check left active, each followed by its check.  The number of launches
 // depends on the parameters alone: every round reads its active count from device memory, nothing comes back to the host.
+// A part (rt_partition) works on its compact tile-major buffers: round 0 is rt_render(part)'s scheduled launch, the lists hold local
+// ids (local_tile * 64 + l) and the check skips the padding of edge tiles.
 static int render_adaptive_common(rt_render_ctx* ctx, void* fb, int max_x, int max_y, const rt_adaptive* P, const rt_world* world,
-                                  rt_rand_state* d_rand_state, const rt_octree* d_octree, int32_t* d_spp, void* stream) {
-    if (!adaptive_params_ok(P) || !world || max_x <= 0 || max_y <= 0 || !fb || !d_rand_state) return RT_EINVAL;
-    if ((int64_t)max_x * max_y > (int64_t)0xffffffffll) return RT_EINVAL;          // pixel ids of the active lists are 32-bit
+                                  rt_rand_state* d_rand_state, const rt_octree* d_octree, int32_t* d_spp, rt_partition part, void* stream) {
+    if (!adaptive_params_ok(P) || !world || max_x <= 0 || max_y <= 0 || !valid_partition(part)) return RT_EINVAL;
+    const int64_t npx = rt_part_pixels(max_x, max_y, part);             // buffer elements (a part's padding included)
+    if (npx < 0 || npx > (int64_t)0xffffffffll) return RT_EINVAL;       // ids of the active lists are 32-bit
+    if (npx == 0) return 0;                                              // a part without tiles (more parts than tiles): nothing to do
+    if (!fb || !d_rand_state) return RT_EINVAL;
     if (d_octree && d_octree->precision != world->precision) return RT_EINVAL;
     if (world->precision == RT_PRECISION_FP16 || world->arith == RT_ARITH_CONTRACT) return RT_ENOTSUP;
     const hipStream_t st = (hipStream_t)stream;
@@ -944,10 +951,9 @@ static int render_adaptive_common(rt_render_ctx* ctx, void* fb, int max_x, int m
     rt_render_ctx& C = ctx ? *ctx : world->z->ctx;
     if (!rc) rc = ctx_prepare(C);
     if (rc) return rc;
-    const rt_partition whole = {0, 1, 0, 0};
-    const int64_t npx = (int64_t)max_x * max_y;
     const int rounds = (P->max_spp - P->min_spp) / P->batch;
-    RenderArgs A = frame_args(fb, max_x, max_y, P->min_spp, world, d_rand_state, d_octree, whole);
+    RenderArgs A = frame_args(fb, max_x, max_y, P->min_spp, world, d_rand_state, d_octree, part);
+    const AdaptFrame fr = {max_x, max_y, A.tiles_x, part.part, part.nparts, part.tile_begin, part.tile_end};
     const bool sched = P->min_spp >= 4;
     if (sched && (rc = ctx_reserve(C, A.n_local_tiles))) return rc;
     if ((rc = ctx_reserve_adaptive(C, npx, rounds + 1))) return rc;
@@ -962,7 +968,7 @@ static int render_adaptive_common(rt_render_ctx* ctx, void* fb, int max_x, int m
     const unsigned ek = C.ev_head % 64u;
     RT_TRY(hipEventRecord(C.ev0[ek], st));
     RT_TRY(launch_render_adaptive(A, tree, st));
-    RT_TRY(launch_adapt_check((float*)fb, C.a_sl, C.a_q, nullptr, nullptr, npx, lists[0], C.a_count, d_spp, P->min_spp, rounds == 0, P->rel_error, P->floor, st));
+    RT_TRY(launch_adapt_check((float*)fb, C.a_sl, C.a_q, nullptr, nullptr, npx, lists[0], C.a_count, d_spp, P->min_spp, rounds == 0, P->rel_error, P->floor, fr, st));
     // resumed rounds: the previous check's list, no scheduling pass (the list is short and its order is the check's)
     A.ns = P->batch;
     A.order = nullptr; A.long_flag = nullptr; A.long_list = nullptr;
@@ -973,7 +979,7 @@ static int render_adaptive_common(rt_render_ctx* ctx, void* fb, int max_x, int m
         RT_TRY(launch_zero_counters(A.queue, (int)kQueueStride, st));
         RT_TRY(launch_render_adaptive(A, tree, st));
         RT_TRY(launch_adapt_check((float*)fb, C.a_sl, C.a_q, A.ad_list, A.ad_count, npx, lists[r & 1], C.a_count + r, d_spp,
-                                  P->min_spp + r * P->batch, r == rounds, P->rel_error, P->floor, st));
+                                  P->min_spp + r * P->batch, r == rounds, P->rel_error, P->floor, fr, st));
     }
     C.last_queue = A.queue;
     RT_TRY(hipEventRecord(C.ev1[ek], st));
@@ -982,14 +988,24 @@ static int render_adaptive_common(rt_render_ctx* ctx, void* fb, int max_x, int m
     C.has_done = true; C.last_stream = st;
     return 0;
 }
+static const rt_partition kWhole = {0, 1, 0, 0};
 int rt_render_adaptive(void* fb, int max_x, int max_y, const rt_adaptive* params, const rt_world* world, rt_rand_state* d_rand_state,
                        const rt_octree* d_octree, int32_t* d_spp, void* stream) {
-    return render_adaptive_common(nullptr, fb, max_x, max_y, params, world, d_rand_state, d_octree, d_spp, stream);
+    return render_adaptive_common(nullptr, fb, max_x, max_y, params, world, d_rand_state, d_octree, d_spp, kWhole, stream);
 }
 int rt_render_adaptive_on(rt_render_ctx* ctx, void* fb, int max_x, int max_y, const rt_adaptive* params, const rt_world* world,
                           rt_rand_state* d_rand_state, const rt_octree* d_octree, int32_t* d_spp, void* stream) {
     if (!ctx) return RT_EINVAL;
-    return render_adaptive_common(ctx, fb, max_x, max_y, params, world, d_rand_state, d_octree, d_spp, stream);
+    return render_adaptive_common(ctx, fb, max_x, max_y, params, world, d_rand_state, d_octree, d_spp, kWhole, stream);
+}
+int rt_render_adaptive_part(void* fb, int max_x, int max_y, const rt_adaptive* params, const rt_world* world, rt_rand_state* d_rand_state,
+                            const rt_octree* d_octree, int32_t* d_spp, rt_partition part, void* stream) {
+    return render_adaptive_common(nullptr, fb, max_x, max_y, params, world, d_rand_state, d_octree, d_spp, part, stream);
+}
+int rt_render_adaptive_part_on(rt_render_ctx* ctx, void* fb, int max_x, int max_y, const rt_adaptive* params, const rt_world* world,
+                               rt_rand_state* d_rand_state, const rt_octree* d_octree, int32_t* d_spp, rt_partition part, void* stream) {
+    if (!ctx) return RT_EINVAL;
+    return render_adaptive_common(ctx, fb, max_x, max_y, params, world, d_rand_state, d_octree, d_spp, part, stream);
 }
 
 // the kernel rt_render (mode 0) / rt_render_progressive (mode 1) launches for this world and tree — the library's own

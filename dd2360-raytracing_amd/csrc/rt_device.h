@@ -46,6 +46,8 @@ __host__ __device__ inline bool part_has(long long tile, int part, int nparts, l
     int owner; part_owner(tile, nparts, owner, local_tile);
     return owner == part;
 }
+// the frame and the part an adaptive check runs over (k_adapt_check: which elements of a compact part buffer are padding)
+struct AdaptFrame { int max_x, max_y, tiles_x, part, nparts; long long tile_begin, tile_end; };
 constexpr int kMaxSplitParts = 64;
 struct SplitStarts { long long s[kMaxSplitParts + 1]; };      // first tile of every band of a balanced split, and the tile count (k_assemble_split)
 

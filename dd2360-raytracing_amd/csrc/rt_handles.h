@@ -84,3 +84,6 @@ struct rt_octree {
     int n_world = 0, bit_rows = 1;          // world list size, rows of the membership bitmaps (>= 1)
 };
 
+
+// rt_adaptive's parameter rule (rt_api.hip), shared with rt_multi_render_adaptive, which refuses before any rank renders or exchanges
+bool adaptive_params_ok(const rt_adaptive* P);

@@ -1221,8 +1221,15 @@ __global__ __launch_bounds__(256, RT_RENDER_WAVES) void k_render(RenderArgs A) {
         while (slot < n_slots) {
             if constexpr (MODE == 2) {
                 if (A.ad_list) {                                   // a resumed round: the list of the pixels still active, in any order
+                    // (entries are buffer indices: row-major for the whole frame, local_tile * 64 + l in a part — decoded as the tile hand-out does)
                     const unsigned int pid = A.ad_list[slot];
-                    idx = (long long)pid; i = (int)(pid % (unsigned int)A.max_x); j = (int)(pid / (unsigned int)A.max_x);
+                    idx = (long long)pid;
+                    if (part_whole(A.nparts, A.tile_begin, A.tile_end)) { i = (int)(pid % (unsigned int)A.max_x); j = (int)(pid / (unsigned int)A.max_x); }
+                    else {
+                        const long long tile = part_tile((long long)(pid >> 6), A.part, A.nparts, A.tile_begin, A.tile_end);
+                        const int tx = (int)(tile % A.tiles_x), ty = (int)(tile / A.tiles_x);
+                        i = tx * 8 + (int)(pid & 7u); j = ty * 8 + (int)((pid >> 3) & 7u);
+                    }
                     live = true;
                     break;
                 }
@@ -1509,16 +1516,24 @@ __global__ __launch_bounds__(256, RT_RENDER_WAVES) void k_render(RenderArgs A) {
 // k*Q - S*S <= (rel_error^2 * (k-1)) * max(S, k*floor)^2 (S, Q: sums of the samples' luminance and of its squares), or when the
 // round is the last one.  A stopped pixel gets rt_render's colour at ns = k (k_render MODE 0's end_pixel: the reciprocal in
 // double, then sqrtf) and its count; the others are appended to list_out, one atomic per wave — their order never changes a pixel.
-// list_in == NULL: round 0, pixel t of the frame for thread t.
+// list_in == NULL: round 0, element t of the buffer for thread t.  In a part (a compact tile-major buffer, rt_partition) the elements
+// of edge tiles that fall outside the frame are padding: round 0 never rendered them, and the check leaves them alone — no colour,
+// no count, never listed (the lists hold in-frame pixels only, so later rounds need no such test).
 __global__ __launch_bounds__(256) void k_adapt_check(float* __restrict__ fb, const float* __restrict__ sl, const float* __restrict__ q,
                                                      const unsigned int* __restrict__ list_in, const unsigned int* __restrict__ count_in, long long n_all,
                                                      unsigned int* __restrict__ list_out, unsigned int* __restrict__ count_out, int32_t* __restrict__ spp,
-                                                     int k, int last, float rel_error, float floor_lum) {
+                                                     int k, int last, float rel_error, float floor_lum, AdaptFrame fr) {
     const long long t = (long long)blockIdx.x * 256 + threadIdx.x;
     const long long n = count_in ? (long long)*count_in : n_all;
     bool active = false;
     unsigned int pid = 0;
-    if (t < n) {
+    bool inside = true;
+    if (!list_in && t < n && !part_whole(fr.nparts, fr.tile_begin, fr.tile_end)) {
+        const long long tile = part_tile(t >> 6, fr.part, fr.nparts, fr.tile_begin, fr.tile_end);
+        const int tx = (int)(tile % fr.tiles_x), ty = (int)(tile / fr.tiles_x);
+        inside = tx * 8 + (int)(t & 7) < fr.max_x && ty * 8 + (int)((t >> 3) & 7) < fr.max_y;
+    }
+    if (t < n && inside) {
         pid = list_in ? list_in[t] : (unsigned int)t;
         bool stop = last != 0;
         if (!stop) {
@@ -1922,6 +1937,18 @@ __global__ __launch_bounds__(256) void k_assemble(float* full, const float* part
     const long long dst = (long long)j * max_x + i;
     full[dst * 3 + 0] = parts[src * 3 + 0]; full[dst * 3 + 1] = parts[src * 3 + 1]; full[dst * 3 + 2] = parts[src * 3 + 2];
 }
+// its one-channel twin: the per-pixel sample counts of an adaptive multi-GPU frame (rt_multi_render_adaptive), one word per pixel
+__global__ __launch_bounds__(256) void k_assemble_spp(int32_t* full, const int32_t* parts, int max_x, int max_y, int tiles_x, int nparts, long long part_stride_px, long long n_tiles) {
+    const int lane = threadIdx.x & 63;
+    const long long tile = (long long)blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (tile >= n_tiles) return;
+    const int tx = (int)(tile % tiles_x), ty = (int)(tile / tiles_x);
+    const int i = tx * 8 + (lane & 7), j = ty * 8 + (lane >> 3);
+    if (i >= max_x || j >= max_y) return;
+    int owner; long long local_tile;
+    part_owner(tile, nparts, owner, local_tile);
+    full[(long long)j * max_x + i] = parts[owner * part_stride_px + local_tile * 64 + lane];
+}
 #endif
 
 // the same for the bands of a balanced split (rt_split_balanced): band p holds the tiles [starts.s[p], starts.s[p + 1]), its buffer begins
@@ -2151,10 +2178,11 @@ hipError_t launch_render_adaptive(const RenderArgs& A, bool tree, hipStream_t st
     return launch_render_tree<2, 1>(A, lds, st);
 }
 hipError_t launch_adapt_check(float* fb, const float* sl, const float* q, const unsigned int* list_in, const unsigned int* count_in, long long n_all,
-                              unsigned int* list_out, unsigned int* count_out, int32_t* spp, int k, bool last, float rel_error, float floor_lum, hipStream_t st) {
+                              unsigned int* list_out, unsigned int* count_out, int32_t* spp, int k, bool last, float rel_error, float floor_lum,
+                              const AdaptFrame& fr, hipStream_t st) {
     if (n_all <= 0) return hipSuccess;
     hipLaunchKernelGGL(k_adapt_check, dim3((unsigned)((n_all + 255) / 256)), dim3(256), 0, st, fb, sl, q, list_in, count_in, n_all, list_out, count_out, spp,
-                       k, last ? 1 : 0, rel_error, floor_lum);
+                       k, last ? 1 : 0, rel_error, floor_lum, fr);
     return hipGetLastError();
 }
 hipError_t launch_adapt_zero(unsigned int* p, int n, hipStream_t st) {
@@ -2184,6 +2212,14 @@ hipError_t launch_assemble(float* full, const float* parts, int max_x, int max_y
     const long long per_part = part_local_tiles(tiles, 0, nparts) * 64;
     const unsigned blocks = (unsigned)((tiles + 3) / 4);
     hipLaunchKernelGGL(k_assemble, dim3(blocks), dim3(256), 0, st, full, parts, max_x, max_y, tiles_x, nparts, per_part, tiles);
+    return hipGetLastError();
+}
+hipError_t launch_assemble_spp(int32_t* full, const int32_t* parts, int max_x, int max_y, int nparts, hipStream_t st) {
+    const int tiles_x = (max_x + 7) / 8, tiles_y = (max_y + 7) / 8;
+    const long long tiles = (long long)tiles_x * tiles_y;
+    const long long per_part = part_local_tiles(tiles, 0, nparts) * 64;
+    const unsigned blocks = (unsigned)((tiles + 3) / 4);
+    hipLaunchKernelGGL(k_assemble_spp, dim3(blocks), dim3(256), 0, st, full, parts, max_x, max_y, tiles_x, nparts, per_part, tiles);
     return hipGetLastError();
 }
 #endif

@@ -28,7 +28,7 @@ namespace {
 // the few RCCL entry points used, with the types of /opt/rocm/include/rccl/rccl.h (ncclResult_t and the enums are ints)
 struct NcclId { char internal[128]; };
 typedef void* NcclComm;
-enum { kNcclFloat16 = 6, kNcclFloat32 = 7 };        // ncclFloat16 / ncclFloat32 of rccl.h
+enum { kNcclInt32 = 2, kNcclFloat16 = 6, kNcclFloat32 = 7 };        // ncclInt32 / ncclFloat16 / ncclFloat32 of rccl.h
 struct Rccl {
     void* lib = nullptr;
     int (*GetUniqueId)(NcclId*) = nullptr;
@@ -64,6 +64,8 @@ Rccl& rccl() {                                        // bound once per process,
 
 }  // namespace
 
+namespace rt { hipError_t launch_assemble_spp(int32_t* full, const int32_t* parts, int max_x, int max_y, int nparts, hipStream_t st); }   // rt_kernels.hip
+
 struct rt_multi {
     int rank = 0, nranks = 1;
     NcclComm comm = nullptr;
@@ -73,6 +75,9 @@ struct rt_multi {
     void* d_rand = nullptr; size_t rand_bytes = 0;
     void* d_local = nullptr; size_t local_bytes = 0;
     void* d_parts = nullptr; size_t parts_bytes = 0;
+    // rt_multi_render_adaptive: this rank's sample counts when it is not the root, the root's staging slots for them (one int32 per pixel)
+    void* d_spp_local = nullptr; size_t spp_local_bytes = 0;
+    void* d_spp_parts = nullptr; size_t spp_parts_bytes = 0;
     hipEvent_t ev0 = nullptr, ev1 = nullptr; bool timed = false;
     // how the frame is divided (rt_multi_set_split) and the bands of the last balanced split, with what they were computed for
     int split_mode = RT_SPLIT_RUNS;
@@ -148,7 +153,7 @@ int rt_multi_destroy(rt_multi* M) {
     if (!M) return 0;
     int rc = 0;
     if (M->comm && rccl().ok && rccl().CommDestroy(M->comm) != 0) rc = RT_ECOMM;
-    void* bufs[3] = {M->d_rand, M->d_local, M->d_parts};
+    void* bufs[5] = {M->d_rand, M->d_local, M->d_parts, M->d_spp_local, M->d_spp_parts};
     for (void* b : bufs) if (b) { const hipError_t e = hipFree(b); if (e != hipSuccess && !rc) rc = (int)e; }
     if (M->ev0) (void)hipEventDestroy(M->ev0);
     if (M->ev1) (void)hipEventDestroy(M->ev1);
@@ -256,6 +261,63 @@ int rt_multi_render(rt_multi* M, void* fb_full, int max_x, int max_y, int ns, co
         rc = balanced ? rt_assemble_split(fb_full, M->d_parts, max_x, max_y, M->nranks, M->starts, per, precision, stream)
                       : rt_assemble(fb_full, M->d_parts, max_x, max_y, M->nranks, precision, stream);
     return rc;
+}
+
+// rt_multi_render with adaptive sampling, runs only: every rank runs render_init + rt_render_adaptive_part_on on its runs, then the
+// colour parts and the sample-count parts go to the root — RCCL: both in one group (4-byte words for the counts); a custom gather:
+// two calls, colours first — where rt_assemble and its one-channel twin write the row-major frame and map.
+int rt_multi_render_adaptive(rt_multi* M, void* fb_full, int max_x, int max_y, const rt_adaptive* params, const rt_world* world, const rt_octree* d_octree,
+                             int precision, int root, int32_t* d_spp_full, void* stream) {
+    if (!M || !world || max_x <= 0 || max_y <= 0 || root < 0 || root >= M->nranks || !adaptive_params_ok(params)) return RT_EINVAL;
+    if (M->rank == root && !fb_full) return RT_EINVAL;
+    if (precision != world->precision) return RT_EINVAL;
+    if (world->precision == RT_PRECISION_FP16 || world->arith == RT_ARITH_CONTRACT) return RT_ENOTSUP;
+    // balanced bands are cut on a uniform-cost pilot pass: they say nothing about where adaptive sampling spends its samples
+    if (M->split_mode != RT_SPLIT_RUNS) return RT_ENOTSUP;
+    const hipStream_t st = (hipStream_t)stream;
+    const size_t px = 12, spx = sizeof(int32_t);
+    int rc = 0;
+    const rt_partition mine = {M->rank, M->nranks, 0, 0};
+    RT_TRY(hipEventRecord(M->ev0, st));
+    M->have_split = false;
+    if ((rc = rt_multi_reserve(M, max_x, max_y, precision, root))) return rc;
+    const int64_t per = rt_part_pixels(max_x, max_y, rt_partition{0, M->nranks, 0, 0});
+    const int64_t n_mine = rt_part_pixels(max_x, max_y, mine);
+    if (M->nranks > 1 && M->rank == root && (rc = grow(&M->d_spp_parts, &M->spp_parts_bytes, (size_t)per * spx * (size_t)M->nranks))) return rc;
+    if (M->nranks > 1 && M->rank != root && (rc = grow(&M->d_spp_local, &M->spp_local_bytes, (size_t)(n_mine > 0 ? n_mine : 1) * spx))) return rc;
+    const size_t stride = (size_t)per * px, spp_stride = (size_t)per * spx;
+    // as rt_multi_render: the root renders into its staging slots, a single rank straight into fb_full / d_spp_full
+    void* local = M->nranks == 1 ? fb_full : M->rank == root ? (void*)((char*)M->d_parts + stride * (size_t)root) : M->d_local;
+    int32_t* spp = M->nranks == 1 ? d_spp_full : M->rank == root ? (int32_t*)((char*)M->d_spp_parts + spp_stride * (size_t)root) : (int32_t*)M->d_spp_local;
+    if ((rc = rt_render_init(max_x, max_y, (rt_rand_state*)M->d_rand, mine, stream))) return rc;
+    if ((rc = rt_render_adaptive_part_on(M->ctx, local, max_x, max_y, params, world, (rt_rand_state*)M->d_rand, d_octree, spp, mine, stream))) return rc;
+    RT_TRY(hipEventRecord(M->ev1, st));
+    M->timed = true;
+    if (M->nranks == 1) return 0;
+    const size_t mine_bytes = (size_t)n_mine * px, mine_spp_bytes = (size_t)n_mine * spx;
+    if (M->gather) {
+        if ((rc = M->gather(M->user, local, mine_bytes, M->rank == root ? M->d_parts : nullptr, stride, root, stream))) return rc > 0 ? RT_ECOMM : rc;
+        if ((rc = M->gather(M->user, spp, mine_spp_bytes, M->rank == root ? M->d_spp_parts : nullptr, spp_stride, root, stream))) return rc > 0 ? RT_ECOMM : rc;
+    } else {
+        Rccl& R = rccl();
+        RT_NCCL(R.GroupStart());                                  // both exchanges in one group
+        if (M->rank == root) {
+            for (int r = 0; r < M->nranks; ++r) {
+                if (r == root) continue;
+                const size_t count = (size_t)rt_part_pixels(max_x, max_y, rt_partition{r, M->nranks, 0, 0});
+                if (count && (R.Recv((char*)M->d_parts + stride * (size_t)r, count * 3, kNcclFloat32, r, M->comm, st) != 0 ||
+                              R.Recv((char*)M->d_spp_parts + spp_stride * (size_t)r, count, kNcclInt32, r, M->comm, st) != 0)) { (void)R.GroupEnd(); return RT_ECOMM; }
+            }
+        } else if (n_mine) {
+            if (R.Send(local, (size_t)n_mine * 3, kNcclFloat32, root, M->comm, st) != 0 ||
+                R.Send(spp, (size_t)n_mine, kNcclInt32, root, M->comm, st) != 0) { (void)R.GroupEnd(); return RT_ECOMM; }
+        }
+        RT_NCCL(R.GroupEnd());
+    }
+    if (M->rank != root) return 0;
+    if ((rc = rt_assemble(fb_full, M->d_parts, max_x, max_y, M->nranks, precision, stream))) return rc;
+    if (d_spp_full) RT_TRY(rt::launch_assemble_spp(d_spp_full, (const int32_t*)M->d_spp_parts, max_x, max_y, M->nranks, st));
+    return 0;
 }
 
 // device time of this rank's own share of the last rt_multi_render (render_init + render, before the exchange), and of

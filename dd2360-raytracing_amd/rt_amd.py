@@ -89,6 +89,8 @@ SYMBOLS = {
     "rt_render_progressive_on": (_i, [_vp, _vp, _i, _i, _i, _vp, _vp, _vp, Partition, _vp]),
     "rt_render_adaptive": (_i, [_vp, _i, _i, C.POINTER(Adaptive), _vp, _vp, _vp, _vp, _vp]),
     "rt_render_adaptive_on": (_i, [_vp, _vp, _i, _i, C.POINTER(Adaptive), _vp, _vp, _vp, _vp, _vp]),
+    "rt_render_adaptive_part": (_i, [_vp, _i, _i, C.POINTER(Adaptive), _vp, _vp, _vp, _vp, Partition, _vp]),
+    "rt_render_adaptive_part_on": (_i, [_vp, _vp, _i, _i, C.POINTER(Adaptive), _vp, _vp, _vp, _vp, Partition, _vp]),
     "rt_render_ctx_times": (_i, [_vp, _vp, _i, _vp]),
     "rt_render_ctx_counters": (_i, [_vp, _vp]),
     "rt_world_render_counters": (_i, [_vp, _vp]),
@@ -102,6 +104,7 @@ SYMBOLS = {
     "rt_multi_destroy": (_i, [_vp]),
     "rt_multi_reserve": (_i, [_vp, _i, _i, _i, _i]),
     "rt_multi_render": (_i, [_vp, _vp, _i, _i, _i, _vp, _vp, _i, _i, _vp]),
+    "rt_multi_render_adaptive": (_i, [_vp, _vp, _i, _i, C.POINTER(Adaptive), _vp, _vp, _i, _i, _vp, _vp]),
     "rt_multi_last_render_ms": (_i, [_vp, _vp, _vp]),
     "rt_multi_selftest": (_i, [_vp, _vp, _vp, C.c_size_t, _vp]),
     "rt_assemble": (_i, [_vp, _vp, _i, _i, _i, _i, _vp]),
@@ -194,6 +197,12 @@ class RenderCtx:
                                           octree.h if octree is not None else None, _dev(d_spp) if d_spp is not None else None,
                                           C.c_void_p(stream) if stream is not None else _stream()), "rt_render_adaptive_on")
 
+    def render_adaptive_part(self, fb, max_x, max_y, params, world, d_rand_state, octree=None, d_spp=None, part=None, stream=None):
+        """rt_render_adaptive_part_on: buffers of rt_part_pixels(part) elements (d_spp: int32), tile-major unless part is the whole frame"""
+        check(lib().rt_render_adaptive_part_on(self.h, _dev(fb), max_x, max_y, C.byref(params), world.h, _dev(d_rand_state),
+                                               octree.h if octree is not None else None, _dev(d_spp) if d_spp is not None else None,
+                                               part or WHOLE, C.c_void_p(stream) if stream is not None else _stream()), "rt_render_adaptive_part_on")
+
     def times(self):
         out = np.zeros(64, np.float32)
         n = C.c_int(0)
@@ -266,6 +275,12 @@ class Multi:
         check(lib().rt_multi_render(self.h, _dev(fb_full) if fb_full is not None else None, max_x, max_y, ns, world.h,
                                     octree.h if octree is not None else None, world.precision if precision is None else precision,
                                     root, _stream()), "rt_multi_render")
+
+    def render_adaptive(self, fb_full, max_x, max_y, params, world, octree=None, root=0, d_spp_full=None, precision=None):
+        """rt_multi_render_adaptive (RT_SPLIT_RUNS only): the root gets the frame and, d_spp_full given (int32, max_x * max_y), the count map"""
+        check(lib().rt_multi_render_adaptive(self.h, _dev(fb_full) if fb_full is not None else None, max_x, max_y, C.byref(params), world.h,
+                                             octree.h if octree is not None else None, world.precision if precision is None else precision,
+                                             root, _dev(d_spp_full) if d_spp_full is not None else None, _stream()), "rt_multi_render_adaptive")
 
     def set_split(self, mode):
         check(lib().rt_multi_set_split(self.h, mode), "rt_multi_set_split")
@@ -516,6 +531,12 @@ def render_adaptive(fb, max_x, max_y, params, world, d_rand_state, octree=None, 
     """rt_render_adaptive on the current stream: params is an Adaptive; d_spp (optional) an int32 tensor of max_x * max_y"""
     check(lib().rt_render_adaptive(_dev(fb), max_x, max_y, C.byref(params), world.h, _dev(d_rand_state), octree.h if octree is not None else None,
                                    _dev(d_spp) if d_spp is not None else None, _stream()), "rt_render_adaptive")
+
+
+def render_adaptive_part(fb, max_x, max_y, params, world, d_rand_state, octree=None, d_spp=None, part=WHOLE):
+    """rt_render_adaptive_part on the current stream: buffers of rt_part_pixels(part) elements (d_spp: int32), tile-major unless part is the whole frame"""
+    check(lib().rt_render_adaptive_part(_dev(fb), max_x, max_y, C.byref(params), world.h, _dev(d_rand_state), octree.h if octree is not None else None,
+                                        _dev(d_spp) if d_spp is not None else None, part, _stream()), "rt_render_adaptive_part")
 
 
 def assemble(fb_full, fb_parts, max_x, max_y, nparts, precision=FP32):

@@ -253,6 +253,19 @@ int rt_render_adaptive(void* fb, int max_x, int max_y, const rt_adaptive* params
                        const rt_octree* d_octree, int32_t* d_spp, void* stream);
 int rt_render_adaptive_on(rt_render_ctx* ctx, void* fb, int max_x, int max_y, const rt_adaptive* params, const rt_world* world,
                           rt_rand_state* d_rand_state, const rt_octree* d_octree, int32_t* d_spp, void* stream);
+/* The same for a part of the frame (rt_partition: runs or a range), placed as rt_render places it.  nparts == 1 without a range is the
+ * whole frame: exactly rt_render_adaptive.  Otherwise fb, d_rand_state and d_spp are the part's compact tile-major buffers, element
+ * (local_tile*64 + ly*8 + lx) as for rt_render, rt_part_pixels() elements each (d_spp: one int32 per element).  The elements of edge
+ * tiles that fall outside the frame are padding: the call never writes them (fb, d_spp and d_rand_state keep what they held — the
+ * states what rt_render_init(part) wrote).  Every pixel is bit for bit what rt_render_adaptive gives it in the whole frame (colour,
+ * count, state): its RNG stream is keyed by its absolute pixel_index.  A part without tiles: 0, nothing launched.  RT_EINVAL for an
+ * invalid partition and for parts of more than 2^32 - 1 elements (the active lists hold 32-bit local ids), otherwise the errors of
+ * rt_render_adaptive (RT_ENOTSUP for USE_FP16 and RT_ARITH_CONTRACT worlds, RT_EINVAL during a capture).  Round 0 runs rt_render(part)'s
+ * scheduling pass; the workspace is sized by the part's tiles and elements. */
+int rt_render_adaptive_part(void* fb, int max_x, int max_y, const rt_adaptive* params, const rt_world* world, rt_rand_state* d_rand_state,
+                            const rt_octree* d_octree, int32_t* d_spp, rt_partition part, void* stream);
+int rt_render_adaptive_part_on(rt_render_ctx* ctx, void* fb, int max_x, int max_y, const rt_adaptive* params, const rt_world* world,
+                               rt_rand_state* d_rand_state, const rt_octree* d_octree, int32_t* d_spp, rt_partition part, void* stream);
 
 /* Name of the kernel rt_render (mode 0) / rt_render_progressive (mode 1) launches for this world and tree (d_octree NULL =
  * the hitable_list path), as rocprofv3 shows it without the namespace: "k_render<true,0,4>", "k_render_h<true,0>", ... */
@@ -309,7 +322,7 @@ int rt_assemble_split(void* fb_full, const void* fb_parts, int max_x, int max_y,
 
 /* ---- multi-GPU: one frame over the GPUs of one node, one process per GPU -------------------------------------------------
  * No reference counterpart (the reference is single-GPU, launch surface main.cu:422-427).  Every rank computes the same split of
- * the frame's tiles (default RT_SPLIT_BALANCED: rt_split_balanced's bands, recomputed for every frame; RT_SPLIT_RUNS: runs of
+ * the frame's tiles (RT_SPLIT_BALANCED: rt_split_balanced's bands, recomputed for every frame; RT_SPLIT_RUNS, the default: runs of
  * RT_PART_RUN tiles dealt round-robin, no pilot pass over the whole frame), renders its part into a compact tile-major buffer, and
  * ONE exchange brings the parts to the root (RCCL over xGMI: one ncclGroupStart / ncclRecv x (nranks-1) | ncclSend / ncclGroupEnd,
  * straight from the render buffer into the root's staging slots, on the caller's stream), where rt_assemble / rt_assemble_split
@@ -333,8 +346,8 @@ typedef int (*rt_gather_fn)(void* user, const void* d_send, size_t send_bytes, v
 int rt_multi_init_custom(rt_multi** out, int rank, int nranks, rt_gather_fn gather, void* user);
 int rt_multi_destroy(rt_multi* m);
 /* how rt_multi_render divides the frame (the same on every rank): */
-#define RT_SPLIT_RUNS 0             /* runs of RT_PART_RUN tiles, round-robin */
-#define RT_SPLIT_BALANCED 1         /* bands of equal predicted cost, from a pilot pass over the whole frame on every rank, every frame (default) */
+#define RT_SPLIT_RUNS 0             /* runs of RT_PART_RUN tiles, round-robin (default) */
+#define RT_SPLIT_BALANCED 1         /* bands of equal predicted cost, from a pilot pass over the whole frame on every rank, every frame */
 #define RT_SPLIT_BALANCED_CACHED 2  /* ... kept while world, tree, frame size stay the same (a static scene rendered again and again) */
 int rt_multi_set_split(rt_multi* m, int mode);
 /* the split of the last rt_multi_render: starts[nranks + 1] (RT_SPLIT_RUNS: RT_EINVAL) */
@@ -348,6 +361,19 @@ int rt_multi_render(rt_multi* m, void* fb_full, int max_x, int max_y, int ns, co
                     int precision, int root, void* stream);
 /* device time of this rank's own share of the last rt_multi_render: render_init + render (call_ms) and the render kernel
  * alone (kernel_ms) — the ranks' values side by side show the load balance of the tile split.  Synchronises. */
+/* rt_multi_render with adaptive sampling (rt_adaptive, the rule of rt_render_adaptive): every rank runs rt_render_init +
+ * rt_render_adaptive_part_on on its runs, and the root receives the assembled frame in fb_full and — d_spp_full != NULL — the row-major
+ * map of every pixel's sample count (max_x*max_y int32; ignored on the other ranks).  Both equal the whole-frame rt_render_adaptive bit
+ * for bit.  RT_SPLIT_RUNS only: the balanced modes return RT_ENOTSUP (their bands are cut on a pilot pass of uniform sampling, which
+ * says nothing about where adaptive sampling spends its samples).  RT_ENOTSUP for USE_FP16 and RT_ARITH_CONTRACT worlds, RT_EINVAL for
+ * bad parameters, before any rank renders.  Two exchanges: the colour parts, then the count parts (every rank sends its counts,
+ * whatever the root asked for).  RCCL: all of them in one ncclGroupStart / ncclGroupEnd, the counts as 4-byte words.  A custom gather
+ * (rt_gather_fn) is called twice per frame: first for the colours as in rt_multi_render, then for the counts with send_bytes =
+ * 4 x the rank's rt_part_pixels and part_stride_bytes = 4 x the elements of part 0.  A single rank renders straight into fb_full and
+ * d_spp_full.  Buffers (a count part per rank, count staging on the root) grow on demand.  rt_multi_last_render_ms covers the
+ * rank's adaptive share (render_init to the last check; kernel_ms: round 0 to the last check).  Asynchronous on `stream`. */
+int rt_multi_render_adaptive(rt_multi* m, void* fb_full, int max_x, int max_y, const rt_adaptive* params, const rt_world* world,
+                             const rt_octree* d_octree, int precision, int root, int32_t* d_spp_full, void* stream);
 int rt_multi_last_render_ms(rt_multi* m, float* call_ms, float* kernel_ms);
 /* RCCL contexts only: one ncclSend + ncclRecv of `bytes` bytes from this rank to itself inside one group on `stream` */
 int rt_multi_selftest(rt_multi* m, const void* d_src, void* d_dst, size_t bytes, void* stream);
