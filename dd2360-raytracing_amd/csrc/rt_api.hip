@@ -9,6 +9,7 @@
 #include <cstring>
 #include <new>
 #include <limits>
+#include <cmath>
 #include <algorithm>
 #include <mutex>
 #include <cstdlib>
@@ -36,6 +37,14 @@ hipError_t launch_adapt_check(float* fb, const float* sl, const float* q, const 
                               unsigned int* list_out, unsigned int* count_out, int32_t* spp, int k, bool last, float rel_error, float floor_lum,
                               const AdaptFrame& fr, hipStream_t st);
 hipError_t launch_adapt_zero(unsigned int* p, int n, hipStream_t st);
+hipError_t launch_adapt_check_keep(float* fb, const AdaptState& s, const unsigned int* list_in, const unsigned int* count_in, long long n_all,
+                                   unsigned int* list_out, unsigned int* count_out, int32_t* spp, int k, bool last, float rel_error, float floor_lum,
+                                   const AdaptFrame& fr, hipStream_t st);
+hipError_t launch_adapt_refine_seed(float* fb, const AdaptState& s, long long n_all, unsigned int* list_out, unsigned int* count_out, int32_t* spp,
+                                    int max_spp, float rel_error, float floor_lum, const AdaptFrame& fr, hipStream_t st);
+hipError_t launch_adapt_refine_check(float* fb, const AdaptState& s, const unsigned int* list_in, const unsigned int* count_in, long long n_all,
+                                     unsigned int* list_out, unsigned int* count_out, int32_t* spp, int batch, int max_spp, float rel_error, float floor_lum,
+                                     hipStream_t st);
 const char* render_kernel_name(bool tree, int mode, const DevAccel& acc);
 namespace gpubuild { int build(rt_octree* O, const float4* d_geom, const int32_t* d_kind, int n, int spl, hipStream_t st); }
 const char* render_kernel_name_h(bool tree, int mode);
@@ -118,6 +127,20 @@ static bool valid_partition(rt_partition p) {
 bool adaptive_params_ok(const rt_adaptive* P) {
     if (!P || P->min_spp < 2 || P->batch < 1 || P->max_spp < P->min_spp || (P->max_spp - P->min_spp) % P->batch != 0) return false;
     return P->rel_error >= 0.f && P->floor >= 0.f;                    // (NaN fails both)
+}
+// rt_render_adaptive_refine's rule for `to` to continue a frame left at `from` (DESIGN.md §5.9 "Refinement"): for every k the stop
+// rule of `to` holds only where that of `from` holds, so a pixel that ran on under `from` runs on under `to`
+static bool adaptive_refines(const rt_adaptive* from, const rt_adaptive* to) {
+    if (!adaptive_params_ok(from) || !adaptive_params_ok(to)) return false;
+    if (to->min_spp != from->min_spp || to->batch != from->batch || to->max_spp < from->max_spp || !(to->floor <= from->floor)) return false;
+    if (!(to->rel_error == 0.f || (to->rel_error > 0.f && to->rel_error <= from->rel_error))) return false;
+    // t * (n - 1) as the check kernels evaluate it, at the largest n of `from`: inf there would meet m == 0 as inf * 0 = NaN
+    const float t = from->rel_error * from->rel_error;
+    const float tn = t * ((float)from->max_spp - 1.f);
+    if (!std::isfinite(tn)) return false;
+    // rel_error^2 underflowing to 0 meets an overflowing (k * floor)^2 as 0 * inf = NaN: a lower floor could then stop a pixel
+    if (from->rel_error > 0.f && t == 0.f && to->rel_error > 0.f && to->floor != from->floor) return false;
+    return true;
 }
 static bool range_in_frame(rt_partition p, int64_t tiles) { return p.tile_end <= p.tile_begin || p.tile_end <= tiles; }
 static int64_t local_tiles_of(int64_t tiles, rt_partition p) { return part_local_tiles(tiles, p.part, p.nparts, p.tile_begin, p.tile_end); }
@@ -936,13 +959,15 @@ int rt_render_progressive_on(rt_render_ctx* ctx, void* fb, int max_x, int max_y,
 // depends on the parameters alone: every round reads its active count from device memory, nothing comes back to the host.
 // A part (rt_partition) works on its compact tile-major buffers: round 0 is rt_render(part)'s scheduled launch, the lists hold local
 // ids (local_tile * 64 + l) and the check skips the padding of edge tiles.
+// d_state != NULL (rt_render_adaptive_begin): the sums live in the caller's refinement state, and the check keeps S_rgb and k there.
 static int render_adaptive_common(rt_render_ctx* ctx, void* fb, int max_x, int max_y, const rt_adaptive* P, const rt_world* world,
-                                  rt_rand_state* d_rand_state, const rt_octree* d_octree, int32_t* d_spp, rt_partition part, void* stream) {
+                                  rt_rand_state* d_rand_state, const rt_octree* d_octree, int32_t* d_spp, rt_partition part, void* stream,
+                                  void* d_state = nullptr, bool need_state = false) {
     if (!adaptive_params_ok(P) || !world || max_x <= 0 || max_y <= 0 || !valid_partition(part)) return RT_EINVAL;
     const int64_t npx = rt_part_pixels(max_x, max_y, part);             // buffer elements (a part's padding included)
     if (npx < 0 || npx > (int64_t)0xffffffffll) return RT_EINVAL;       // ids of the active lists are 32-bit
     if (npx == 0) return 0;                                              // a part without tiles (more parts than tiles): nothing to do
-    if (!fb || !d_rand_state) return RT_EINVAL;
+    if (!fb || !d_rand_state || (need_state && !d_state)) return RT_EINVAL;
     if (d_octree && d_octree->precision != world->precision) return RT_EINVAL;
     if (world->precision == RT_PRECISION_FP16 || world->arith == RT_ARITH_CONTRACT) return RT_ENOTSUP;
     const hipStream_t st = (hipStream_t)stream;
@@ -951,6 +976,7 @@ static int render_adaptive_common(rt_render_ctx* ctx, void* fb, int max_x, int m
     rt_render_ctx& C = ctx ? *ctx : world->z->ctx;
     if (!rc) rc = ctx_prepare(C);
     if (rc) return rc;
+    const AdaptState keep = adapt_state(d_state, npx);
     const int rounds = (P->max_spp - P->min_spp) / P->batch;
     RenderArgs A = frame_args(fb, max_x, max_y, P->min_spp, world, d_rand_state, d_octree, part);
     const AdaptFrame fr = {max_x, max_y, A.tiles_x, part.part, part.nparts, part.tile_begin, part.tile_end};
@@ -960,7 +986,7 @@ static int render_adaptive_common(rt_render_ctx* ctx, void* fb, int max_x, int m
     if (C.has_done && C.last_stream != st) RT_TRY(hipStreamWaitEvent(st, C.done, 0));
     const bool tree = d_octree != nullptr;
     unsigned int* lists[2] = {C.a_list, C.a_list + npx};
-    A.ad_sl = C.a_sl; A.ad_q = C.a_q;
+    A.ad_sl = d_state ? keep.sl : C.a_sl; A.ad_q = d_state ? keep.q : C.a_q;
     RT_TRY(launch_adapt_zero(C.a_count, rounds + 1, st));
     A.queue = C.d_queue + (size_t)(C.launches++ % kQueueSlots) * kQueueStride;
     RT_TRY(launch_zero_counters(A.queue, (int)kQueueStride, st));
@@ -968,7 +994,11 @@ static int render_adaptive_common(rt_render_ctx* ctx, void* fb, int max_x, int m
     const unsigned ek = C.ev_head % 64u;
     RT_TRY(hipEventRecord(C.ev0[ek], st));
     RT_TRY(launch_render_adaptive(A, tree, st));
-    RT_TRY(launch_adapt_check((float*)fb, C.a_sl, C.a_q, nullptr, nullptr, npx, lists[0], C.a_count, d_spp, P->min_spp, rounds == 0, P->rel_error, P->floor, fr, st));
+    auto check = [&](const unsigned int* list_in, const unsigned int* count_in, unsigned int* list_out, unsigned int* count_out, int k, bool last) {
+        return d_state ? launch_adapt_check_keep((float*)fb, keep, list_in, count_in, npx, list_out, count_out, d_spp, k, last, P->rel_error, P->floor, fr, st)
+                       : launch_adapt_check((float*)fb, C.a_sl, C.a_q, list_in, count_in, npx, list_out, count_out, d_spp, k, last, P->rel_error, P->floor, fr, st);
+    };
+    RT_TRY(check(nullptr, nullptr, lists[0], C.a_count, P->min_spp, rounds == 0));
     // resumed rounds: the previous check's list, no scheduling pass (the list is short and its order is the check's)
     A.ns = P->batch;
     A.order = nullptr; A.long_flag = nullptr; A.long_list = nullptr;
@@ -978,8 +1008,7 @@ static int render_adaptive_common(rt_render_ctx* ctx, void* fb, int max_x, int m
         A.queue = C.d_queue + (size_t)(C.launches++ % kQueueSlots) * kQueueStride;
         RT_TRY(launch_zero_counters(A.queue, (int)kQueueStride, st));
         RT_TRY(launch_render_adaptive(A, tree, st));
-        RT_TRY(launch_adapt_check((float*)fb, C.a_sl, C.a_q, A.ad_list, A.ad_count, npx, lists[r & 1], C.a_count + r, d_spp,
-                                  P->min_spp + r * P->batch, r == rounds, P->rel_error, P->floor, fr, st));
+        RT_TRY(check(A.ad_list, A.ad_count, lists[r & 1], C.a_count + r, P->min_spp + r * P->batch, r == rounds));
     }
     C.last_queue = A.queue;
     RT_TRY(hipEventRecord(C.ev1[ek], st));
@@ -1006,6 +1035,74 @@ int rt_render_adaptive_part_on(rt_render_ctx* ctx, void* fb, int max_x, int max_
                                rt_rand_state* d_rand_state, const rt_octree* d_octree, int32_t* d_spp, rt_partition part, void* stream) {
     if (!ctx) return RT_EINVAL;
     return render_adaptive_common(ctx, fb, max_x, max_y, params, world, d_rand_state, d_octree, d_spp, part, stream);
+}
+
+// ---- refinement of an adaptive frame (DESIGN.md §5.9 "Refinement") ----------------------------------------------------
+// rt_render_adaptive_begin is render_adaptive_common with the caller's state.  rt_render_adaptive_refine continues from that state: a
+// seed pass decides, from each pixel's k and sums, which pixels `to` stops where they are (finalised again) and lists the others, then
+// (max_spp - min_spp) / batch resumed rounds, each a k_render<*, 2, *> of `batch` samples over the list and a check with the pixel's
+// own k.  As in rt_render_adaptive, the number of launches depends on the parameters alone; rounds with an empty list exit at once.
+static int render_adaptive_refine_common(rt_render_ctx* ctx, void* fb, int max_x, int max_y, const rt_adaptive* from, const rt_adaptive* to,
+                                         const rt_world* world, rt_rand_state* d_rand_state, const rt_octree* d_octree, int32_t* d_spp,
+                                         void* d_state, rt_partition part, void* stream) {
+    if (!adaptive_refines(from, to) || !world || max_x <= 0 || max_y <= 0 || !valid_partition(part)) return RT_EINVAL;
+    const int64_t npx = rt_part_pixels(max_x, max_y, part);
+    if (npx < 0 || npx > (int64_t)0xffffffffll) return RT_EINVAL;
+    if (npx == 0) return 0;
+    if (!fb || !d_rand_state || !d_state) return RT_EINVAL;
+    if (d_octree && d_octree->precision != world->precision) return RT_EINVAL;
+    if (world->precision == RT_PRECISION_FP16 || world->arith == RT_ARITH_CONTRACT) return RT_ENOTSUP;
+    const hipStream_t st = (hipStream_t)stream;
+    if (capturing(st)) return RT_EINVAL;
+    int rc = ensure_on_device(world, d_octree);
+    rt_render_ctx& C = ctx ? *ctx : world->z->ctx;
+    if (!rc) rc = ctx_prepare(C);
+    if (rc) return rc;
+    const AdaptState S = adapt_state(d_state, npx);
+    const int rounds = (to->max_spp - to->min_spp) / to->batch;
+    RenderArgs A = frame_args(fb, max_x, max_y, to->batch, world, d_rand_state, d_octree, part);
+    const AdaptFrame fr = {max_x, max_y, A.tiles_x, part.part, part.nparts, part.tile_begin, part.tile_end};
+    if ((rc = ctx_reserve_adaptive(C, npx, rounds + 1))) return rc;
+    if (C.has_done && C.last_stream != st) RT_TRY(hipStreamWaitEvent(st, C.done, 0));
+    const bool tree = d_octree != nullptr;
+    unsigned int* lists[2] = {C.a_list, C.a_list + npx};
+    A.ad_sl = S.sl; A.ad_q = S.q;
+    RT_TRY(launch_adapt_zero(C.a_count, rounds + 1, st));
+    const unsigned ek = C.ev_head % 64u;
+    RT_TRY(hipEventRecord(C.ev0[ek], st));
+    RT_TRY(launch_adapt_refine_seed((float*)fb, S, npx, lists[0], C.a_count, d_spp, to->max_spp, to->rel_error, to->floor, fr, st));
+    for (int r = 1; r <= rounds; ++r) {
+        A.ad_list = lists[(r - 1) & 1]; A.ad_count = C.a_count + (r - 1);
+        A.queue = C.d_queue + (size_t)(C.launches++ % kQueueSlots) * kQueueStride;
+        RT_TRY(launch_zero_counters(A.queue, (int)kQueueStride, st));
+        RT_TRY(launch_render_adaptive(A, tree, st));
+        RT_TRY(launch_adapt_refine_check((float*)fb, S, A.ad_list, A.ad_count, npx, lists[r & 1], C.a_count + r, d_spp, to->batch, to->max_spp,
+                                         to->rel_error, to->floor, st));
+    }
+    if (rounds > 0) C.last_queue = A.queue;
+    RT_TRY(hipEventRecord(C.ev1[ek], st));
+    C.ev_head++; if (C.ev_count < 64) C.ev_count++;
+    RT_TRY(hipEventRecord(C.done, st));
+    C.has_done = true; C.last_stream = st;
+    return 0;
+}
+int rt_render_adaptive_begin(void* fb, int max_x, int max_y, const rt_adaptive* params, const rt_world* world, rt_rand_state* d_rand_state,
+                             const rt_octree* d_octree, int32_t* d_spp, void* d_state, rt_partition part, void* stream) {
+    return render_adaptive_common(nullptr, fb, max_x, max_y, params, world, d_rand_state, d_octree, d_spp, part, stream, d_state, true);
+}
+int rt_render_adaptive_begin_on(rt_render_ctx* ctx, void* fb, int max_x, int max_y, const rt_adaptive* params, const rt_world* world,
+                                rt_rand_state* d_rand_state, const rt_octree* d_octree, int32_t* d_spp, void* d_state, rt_partition part, void* stream) {
+    if (!ctx) return RT_EINVAL;
+    return render_adaptive_common(ctx, fb, max_x, max_y, params, world, d_rand_state, d_octree, d_spp, part, stream, d_state, true);
+}
+int rt_render_adaptive_refine(void* fb, int max_x, int max_y, const rt_adaptive* from, const rt_adaptive* to, const rt_world* world,
+                              rt_rand_state* d_rand_state, const rt_octree* d_octree, int32_t* d_spp, void* d_state, rt_partition part, void* stream) {
+    return render_adaptive_refine_common(nullptr, fb, max_x, max_y, from, to, world, d_rand_state, d_octree, d_spp, d_state, part, stream);
+}
+int rt_render_adaptive_refine_on(rt_render_ctx* ctx, void* fb, int max_x, int max_y, const rt_adaptive* from, const rt_adaptive* to, const rt_world* world,
+                                 rt_rand_state* d_rand_state, const rt_octree* d_octree, int32_t* d_spp, void* d_state, rt_partition part, void* stream) {
+    if (!ctx) return RT_EINVAL;
+    return render_adaptive_refine_common(ctx, fb, max_x, max_y, from, to, world, d_rand_state, d_octree, d_spp, d_state, part, stream);
 }
 
 // the kernel rt_render (mode 0) / rt_render_progressive (mode 1) launches for this world and tree — the library's own

@@ -48,6 +48,13 @@ __host__ __device__ inline bool part_has(long long tile, int part, int nparts, l
 }
 // the frame and the part an adaptive check runs over (k_adapt_check: which elements of a compact part buffer are padding)
 struct AdaptFrame { int max_x, max_y, tiles_x, part, nparts; long long tile_begin, tile_end; };
+// the caller's refinement state of rt_render_adaptive_begin / _refine, structure of arrays over the n buffer elements:
+// S_rgb[3n] (interleaved like fb), SL[n], Q[n], k[n] (int32) — RT_ADAPTIVE_STATE_BYTES = 24 per element
+struct AdaptState { float* rgb; float* sl; float* q; int32_t* k; };
+__host__ __device__ inline AdaptState adapt_state(void* base, long long n) {
+    float* f = (float*)base;
+    return AdaptState{f, f + 3 * n, f + 4 * n, (int32_t*)(f + 5 * n)};
+}
 constexpr int kMaxSplitParts = 64;
 struct SplitStarts { long long s[kMaxSplitParts + 1]; };      // first tile of every band of a balanced split, and the tile count (k_assemble_split)
 

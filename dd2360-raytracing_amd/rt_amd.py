@@ -50,6 +50,7 @@ class Adaptive(C.Structure):
     mean luminance (the mean floored at `floor`) is still above rel_error, up to max_spp (include/rt_amd.h states the exact rule)"""
     _fields_ = [("min_spp", C.c_int32), ("max_spp", C.c_int32), ("batch", C.c_int32), ("rel_error", C.c_float), ("floor", C.c_float)]
 
+ADAPTIVE_STATE_BYTES = 24      # rt_amd.h RT_ADAPTIVE_STATE_BYTES: the refinement state per buffer element (S_rgb, SL, Q, k)
 
 # every symbol include/rt_amd.h declares: (restype, argtypes)
 _vp, _i, _i64, _f = C.c_void_p, C.c_int, C.c_int64, C.c_float
@@ -91,6 +92,10 @@ SYMBOLS = {
     "rt_render_adaptive_on": (_i, [_vp, _vp, _i, _i, C.POINTER(Adaptive), _vp, _vp, _vp, _vp, _vp]),
     "rt_render_adaptive_part": (_i, [_vp, _i, _i, C.POINTER(Adaptive), _vp, _vp, _vp, _vp, Partition, _vp]),
     "rt_render_adaptive_part_on": (_i, [_vp, _vp, _i, _i, C.POINTER(Adaptive), _vp, _vp, _vp, _vp, Partition, _vp]),
+    "rt_render_adaptive_begin": (_i, [_vp, _i, _i, C.POINTER(Adaptive), _vp, _vp, _vp, _vp, _vp, Partition, _vp]),
+    "rt_render_adaptive_begin_on": (_i, [_vp, _vp, _i, _i, C.POINTER(Adaptive), _vp, _vp, _vp, _vp, _vp, Partition, _vp]),
+    "rt_render_adaptive_refine": (_i, [_vp, _i, _i, C.POINTER(Adaptive), C.POINTER(Adaptive), _vp, _vp, _vp, _vp, _vp, Partition, _vp]),
+    "rt_render_adaptive_refine_on": (_i, [_vp, _vp, _i, _i, C.POINTER(Adaptive), C.POINTER(Adaptive), _vp, _vp, _vp, _vp, _vp, Partition, _vp]),
     "rt_render_ctx_times": (_i, [_vp, _vp, _i, _vp]),
     "rt_render_ctx_counters": (_i, [_vp, _vp]),
     "rt_world_render_counters": (_i, [_vp, _vp]),
@@ -202,6 +207,18 @@ class RenderCtx:
         check(lib().rt_render_adaptive_part_on(self.h, _dev(fb), max_x, max_y, C.byref(params), world.h, _dev(d_rand_state),
                                                octree.h if octree is not None else None, _dev(d_spp) if d_spp is not None else None,
                                                part or WHOLE, C.c_void_p(stream) if stream is not None else _stream()), "rt_render_adaptive_part_on")
+
+    def render_adaptive_begin(self, fb, max_x, max_y, params, world, d_rand_state, d_state, octree=None, d_spp=None, part=None, stream=None):
+        """rt_render_adaptive_begin_on: rt_render_adaptive_part_on that also fills d_state (alloc_adaptive_state) for later refinement"""
+        check(lib().rt_render_adaptive_begin_on(self.h, _dev(fb), max_x, max_y, C.byref(params), world.h, _dev(d_rand_state),
+                                                octree.h if octree is not None else None, _dev(d_spp) if d_spp is not None else None, _dev(d_state),
+                                                part or WHOLE, C.c_void_p(stream) if stream is not None else _stream()), "rt_render_adaptive_begin_on")
+
+    def render_adaptive_refine(self, fb, max_x, max_y, frm, to, world, d_rand_state, d_state, octree=None, d_spp=None, part=None, stream=None):
+        """rt_render_adaptive_refine_on: continue the frame that d_state holds at target `frm` (an Adaptive) to the target `to`"""
+        check(lib().rt_render_adaptive_refine_on(self.h, _dev(fb), max_x, max_y, C.byref(frm), C.byref(to), world.h, _dev(d_rand_state),
+                                                 octree.h if octree is not None else None, _dev(d_spp) if d_spp is not None else None, _dev(d_state),
+                                                 part or WHOLE, C.c_void_p(stream) if stream is not None else _stream()), "rt_render_adaptive_refine_on")
 
     def times(self):
         out = np.zeros(64, np.float32)
@@ -537,6 +554,26 @@ def render_adaptive_part(fb, max_x, max_y, params, world, d_rand_state, octree=N
     """rt_render_adaptive_part on the current stream: buffers of rt_part_pixels(part) elements (d_spp: int32), tile-major unless part is the whole frame"""
     check(lib().rt_render_adaptive_part(_dev(fb), max_x, max_y, C.byref(params), world.h, _dev(d_rand_state), octree.h if octree is not None else None,
                                         _dev(d_spp) if d_spp is not None else None, part, _stream()), "rt_render_adaptive_part")
+
+
+def alloc_adaptive_state(max_x, max_y, part=WHOLE, device="cuda"):
+    """the refinement state of rt_render_adaptive_begin / _refine: ADAPTIVE_STATE_BYTES per buffer element of the part"""
+    import torch
+    return torch.zeros(part_pixels(max_x, max_y, part) * ADAPTIVE_STATE_BYTES, dtype=torch.uint8, device=device)
+
+
+def render_adaptive_begin(fb, max_x, max_y, params, world, d_rand_state, d_state, octree=None, d_spp=None, part=WHOLE):
+    """rt_render_adaptive_begin on the current stream: rt_render_adaptive_part that also fills d_state (alloc_adaptive_state)"""
+    check(lib().rt_render_adaptive_begin(_dev(fb), max_x, max_y, C.byref(params), world.h, _dev(d_rand_state), octree.h if octree is not None else None,
+                                         _dev(d_spp) if d_spp is not None else None, _dev(d_state), part, _stream()), "rt_render_adaptive_begin")
+
+
+def render_adaptive_refine(fb, max_x, max_y, frm, to, world, d_rand_state, d_state, octree=None, d_spp=None, part=WHOLE):
+    """rt_render_adaptive_refine on the current stream: continue the frame that d_state holds at target `frm` to the target `to`;
+    afterwards fb, d_spp, d_rand_state and d_state hold what render_adaptive_begin(to) would have left"""
+    check(lib().rt_render_adaptive_refine(_dev(fb), max_x, max_y, C.byref(frm), C.byref(to), world.h, _dev(d_rand_state),
+                                          octree.h if octree is not None else None, _dev(d_spp) if d_spp is not None else None, _dev(d_state),
+                                          part, _stream()), "rt_render_adaptive_refine")
 
 
 def assemble(fb_full, fb_parts, max_x, max_y, nparts, precision=FP32):

@@ -267,6 +267,32 @@ int rt_render_adaptive_part(void* fb, int max_x, int max_y, const rt_adaptive* p
 int rt_render_adaptive_part_on(rt_render_ctx* ctx, void* fb, int max_x, int max_y, const rt_adaptive* params, const rt_world* world,
                                rt_rand_state* d_rand_state, const rt_octree* d_octree, int32_t* d_spp, rt_partition part, void* stream);
 
+/* Refinement: an adaptive frame that can be tightened afterwards without starting over (no reference counterpart; the adaptive
+ * counterpart of main.cu:222-345's pass-by-pass refinement).  rt_render_adaptive_begin is rt_render_adaptive_part (same launches, the
+ * same fb, d_spp and d_rand_state, bit for bit; part = {0, 1, 0, 0} is the whole row-major frame) that also fills d_state, a device
+ * buffer of the caller's of RT_ADAPTIVE_STATE_BYTES x rt_part_pixels(max_x, max_y, part) bytes: every pixel's sums and sample count.
+ * rt_render_adaptive_refine continues a frame that begin(from), or a chain of refines ending in `from`, left behind — same world, tree,
+ * frame, part, d_rand_state and d_state — to the target `to`: afterwards fb, d_spp, d_rand_state and d_state hold exactly what
+ * begin(to) would have left, bit for bit.  Only the pixels that `to` does not stop where they are take more samples.  The earlier
+ * contents of fb and d_spp do not matter: every in-frame element is written again (the padding of edge tiles never is).
+ * `to` refines `from` when both are valid rt_adaptive parameters with equal min_spp and batch, to.max_spp >= from.max_spp,
+ * to.floor <= from.floor, to.rel_error == 0 or 0 < to.rel_error <= from.rel_error, from.rel_error^2 * (from.max_spp - 1) is finite in
+ * binary32, and — when from.rel_error^2 underflows to 0 and to.rel_error > 0 — to.floor == from.floor; otherwise RT_EINVAL
+ * (DESIGN.md §5.9 "Refinement": the rule of `to` then stops no pixel earlier than the rule of `from`).  Other errors as for
+ * rt_render_adaptive_part, and RT_EINVAL for a NULL d_state.  Asynchronous on `stream`, no host synchronisation, never captured; the
+ * _on forms take a context of the caller's.  A state from another frame, world, tree or part is undefined behaviour, as a progressive
+ * pass on a foreign fb is. */
+#define RT_ADAPTIVE_STATE_BYTES 24   /* per buffer element of the caller's refinement state */
+int rt_render_adaptive_begin(void* fb, int max_x, int max_y, const rt_adaptive* params, const rt_world* world, rt_rand_state* d_rand_state,
+                             const rt_octree* d_octree, int32_t* d_spp, void* d_state, rt_partition part, void* stream);
+int rt_render_adaptive_begin_on(rt_render_ctx* ctx, void* fb, int max_x, int max_y, const rt_adaptive* params, const rt_world* world,
+                                rt_rand_state* d_rand_state, const rt_octree* d_octree, int32_t* d_spp, void* d_state, rt_partition part, void* stream);
+int rt_render_adaptive_refine(void* fb, int max_x, int max_y, const rt_adaptive* from, const rt_adaptive* to, const rt_world* world,
+                              rt_rand_state* d_rand_state, const rt_octree* d_octree, int32_t* d_spp, void* d_state, rt_partition part, void* stream);
+int rt_render_adaptive_refine_on(rt_render_ctx* ctx, void* fb, int max_x, int max_y, const rt_adaptive* from, const rt_adaptive* to,
+                                 const rt_world* world, rt_rand_state* d_rand_state, const rt_octree* d_octree, int32_t* d_spp, void* d_state,
+                                 rt_partition part, void* stream);
+
 /* Name of the kernel rt_render (mode 0) / rt_render_progressive (mode 1) launches for this world and tree (d_octree NULL =
  * the hitable_list path), as rocprofv3 shows it without the namespace: "k_render<true,0,4>", "k_render_h<true,0>", ... */
 int rt_render_kernel_name(const rt_world* world, const rt_octree* d_octree, int mode, char* out, int cap);
