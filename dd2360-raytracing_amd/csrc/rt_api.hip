@@ -31,6 +31,9 @@ hipError_t launch_tile_order_h(const RenderArgs& A, bool tree, int* cost, unsign
 hipError_t launch_trace_h(const DevScene& S, const DevTree& T, bool tree, const float* rays, long long n, rt_hit_record* out, hipStream_t st);
 hipError_t launch_assemble_h(void* full, const void* parts, int max_x, int max_y, int nparts, hipStream_t st);
 hipError_t launch_trace(const DevScene& S, const DevTree& T, bool tree, const float* rays, long long n, rt_hit_record* out, hipStream_t st);
+hipError_t launch_guides(const DevScene& S, const DevTree& T, bool tree, int max_x, int max_y, rt_hit_record* out, hipStream_t st);
+hipError_t launch_denoise(float* fb_out, const float* fb_in, int max_x, int max_y, const rt_hit_record* hits, const rt_denoise_params& P,
+                          float4* work, hipStream_t st);      // rt_denoise.hip
 hipError_t launch_assemble(float* full, const float* parts, int max_x, int max_y, int nparts, hipStream_t st);
 hipError_t launch_render_adaptive(const RenderArgs& A, bool tree, hipStream_t st);
 hipError_t launch_adapt_check(float* fb, const float* sl, const float* q, const unsigned int* list_in, const unsigned int* count_in, long long n_all,
@@ -1204,6 +1207,47 @@ int rt_trace_rays(const rt_world* world, const rt_octree* d_octree, const float*
     const DevTree T = tree_args(d_octree);
     if (world->precision == RT_PRECISION_FP16) return (int)launch_trace_h(world->z->dev, T, d_octree != nullptr, d_rays, n, d_out, (hipStream_t)stream);
     return (int)launch_trace(world->z->dev, T, d_octree != nullptr, d_rays, n, d_out, (hipStream_t)stream);
+}
+
+// ------------------------------------------------------------------------------------------------ denoising
+// the filter kernels index pixels and guide halves (2 * pixel + 1) in int; colour offsets (3 * pixel + c) are 64-bit (rt_denoise.hip)
+static_assert(2ll * (RT_DENOISE_MAX_PIXELS - 1) + 1 <= 0x7fffffffll, "RT_DENOISE_MAX_PIXELS: the last guide half must fit an int");
+
+int rt_render_guides(const rt_world* world, const rt_octree* d_octree, int max_x, int max_y, rt_hit_record* d_hits, void* stream) {
+    if (!world || !d_hits || max_x <= 0 || max_y <= 0 || (long long)max_x * max_y > RT_DENOISE_MAX_PIXELS) return RT_EINVAL;
+    if (d_octree && d_octree->precision != world->precision) return RT_EINVAL;
+    if (world->precision == RT_PRECISION_FP16) return RT_ENOTSUP;
+    const int rc = ensure_on_device(world, d_octree);
+    if (rc) return rc;
+    // always the IEEE kernels (rt::launch_guides, not rt::fmac): guides are rt_trace_rays's records, whatever the world's arithmetic
+    return (int)launch_guides(world->z->dev, tree_args(d_octree), d_octree != nullptr, max_x, max_y, d_hits, (hipStream_t)stream);
+}
+
+// a sigma is 0 (its term off) or positive and finite with a finite scale factor `num / sigma^2` (else 0 * inf at the centre tap)
+static bool denoise_sigma_ok(float sigma, float num) {
+    if (!(sigma >= 0.0f) || !std::isfinite(sigma)) return false;
+    return sigma == 0.0f || std::isfinite(num / (sigma * sigma));
+}
+
+// the frame size and parameter checks of rt_denoise (host only)
+int rt_denoise_check(int max_x, int max_y, const rt_denoise_params* params) {
+    if (!params || max_x <= 0 || max_y <= 0 || (long long)max_x * max_y > RT_DENOISE_MAX_PIXELS) return RT_EINVAL;
+    const rt_denoise_params& P = *params;
+    if (P.input != RT_DENOISE_INPUT_GAMMA && P.input != RT_DENOISE_INPUT_SUM) return RT_EINVAL;
+    if (P.input == RT_DENOISE_INPUT_SUM && P.samples < 1) return RT_EINVAL;
+    if (P.levels < 1 || P.levels > RT_DENOISE_MAX_LEVELS) return RT_EINVAL;
+    if (P.normal_pow_log2 < -1 || P.normal_pow_log2 > 10) return RT_EINVAL;
+    if (!denoise_sigma_ok(P.sigma_position, 1.0f) || !denoise_sigma_ok(P.sigma_color, (float)(1 << (2 * (P.levels - 1))))) return RT_EINVAL;
+    return 0;
+}
+
+int rt_denoise(void* fb_out, const void* fb_in, int max_x, int max_y, const rt_hit_record* d_hits, const rt_denoise_params* params,
+               void* d_work, void* stream) {
+    if (!fb_out || !fb_in || !d_hits || !d_work) return RT_EINVAL;
+    if (((uintptr_t)d_hits & 15) || ((uintptr_t)d_work & 15)) return RT_EINVAL;        // read and written as float4
+    const int rc = rt_denoise_check(max_x, max_y, params);
+    if (rc) return rc;
+    return (int)launch_denoise((float*)fb_out, (const float*)fb_in, max_x, max_y, d_hits, *params, (float4*)d_work, (hipStream_t)stream);
 }
 
 #ifdef RT_H16_STATS

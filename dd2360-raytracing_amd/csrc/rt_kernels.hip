@@ -1970,16 +1970,11 @@ __global__ __launch_bounds__(256) void k_tail_scatter(const unsigned int* __rest
 }
 #endif
 
-// hitTree / hitable_list::hit for a batch of rays (one lane per ray)
-template <bool TREE, int COOPG = 1>
-__global__ __launch_bounds__(256) void k_trace(RenderArgs A, const float* rays, long long n, rt_hit_record* out) {
+// the closest hit of one ray per lane, stored as an rt_hit_record (k_trace, k_guides): every lane of the block calls it, live or not
+// (the tree walk is a wave-wide loop); the tree is already staged in s_nodes
+template <bool TREE, int COOPG>
+RT_DEV void trace_record(const RenderArgs& A, const float4* s_nodes, const RayF& r, bool live, rt_hit_record* out) {
     const DevScene& S = A.scene; const DevTree& T = A.tree;
-    extern __shared__ float4 s_nodes[];
-    if (TREE) stage_tree_fp32<COOPG != 1>(S, T, s_nodes);
-    const long long gid = (long long)blockIdx.x * 256 + threadIdx.x;
-    const bool live = gid < n;
-    RayF r; r.o = {0.f, 0.f, 0.f}; r.d = {0.f, 1.f, 0.f};
-    if (live) { const float* p = rays + gid * 6; r.o = {p[0], p[1], p[2]}; r.d = {p[3], p[4], p[5]}; }
     const float a = dot3(r.d, r.d);
     float closest = FLT_MAX; int best = -1;
     RT_STATS_ONLY(
@@ -2000,8 +1995,44 @@ __global__ __launch_bounds__(256) void k_trace(RenderArgs A, const float* rays, 
         h.p[0] = r.o.x + closest * r.d.x; h.p[1] = r.o.y + closest * r.d.y; h.p[2] = r.o.z + closest * r.d.z;
         h.normal[0] = (h.p[0] - g.x) / g.w; h.normal[1] = (h.p[1] - g.y) / g.w; h.normal[2] = (h.p[2] - g.z) / g.w;
     }
-    out[gid] = h;
+    *out = h;
 }
+
+// hitTree / hitable_list::hit for a batch of rays (one lane per ray)
+template <bool TREE, int COOPG = 1>
+__global__ __launch_bounds__(256) void k_trace(RenderArgs A, const float* rays, long long n, rt_hit_record* out) {
+    extern __shared__ float4 s_nodes[];
+    if (TREE) stage_tree_fp32<COOPG != 1>(A.scene, A.tree, s_nodes);
+    const long long gid = (long long)blockIdx.x * 256 + threadIdx.x;
+    const bool live = gid < n;
+    RayF r; r.o = {0.f, 0.f, 0.f}; r.d = {0.f, 1.f, 0.f};
+    if (live) { const float* p = rays + gid * 6; r.o = {p[0], p[1], p[2]}; r.d = {p[3], p[4], p[5]}; }
+    trace_record<TREE, COOPG>(A, s_nodes, r, live, out + gid);
+}
+
+#ifndef RT_TU_CONTRACT
+// rt_render_guides: the first hit of every pixel's centre ray, row-major (pixel_index = j*max_x + i, one lane per pixel).  The ray is
+// primary_ray's with both jitter draws replaced by 0.5 and no lens offset: a pinhole at the camera origin.
+template <bool TREE, int COOPG = 1>
+__global__ __launch_bounds__(256) void k_guides(RenderArgs A, long long n, rt_hit_record* out) {
+    extern __shared__ float4 s_nodes[];
+    if (TREE) stage_tree_fp32<COOPG != 1>(A.scene, A.tree, s_nodes);
+    const long long gid = (long long)blockIdx.x * 256 + threadIdx.x;
+    const bool live = gid < n;
+    RayF r; r.o = {0.f, 0.f, 0.f}; r.d = {0.f, 1.f, 0.f};
+    if (live) {
+        const rt_camera& c = A.scene.cam;
+        const int i = (int)(gid % A.max_x), j = (int)(gid / A.max_x);
+        const float u = ((float)i + 0.5f) / (float)A.max_x;
+        const float v = ((float)j + 0.5f) / (float)A.max_y;
+        r.o = {c.origin[0], c.origin[1], c.origin[2]};
+        r.d.x = ((c.lower_left_corner[0] + u * c.horizontal[0]) + v * c.vertical[0]) - c.origin[0];
+        r.d.y = ((c.lower_left_corner[1] + u * c.horizontal[1]) + v * c.vertical[1]) - c.origin[1];
+        r.d.z = ((c.lower_left_corner[2] + u * c.horizontal[2]) + v * c.vertical[2]) - c.origin[2];
+    }
+    trace_record<TREE, COOPG>(A, s_nodes, r, live, out + gid);
+}
+#endif
 
 // gather of tile-major part buffers into the row-major frame (after the multi-GPU all-gather)
 #ifndef RT_TU_LIST
@@ -2120,6 +2151,10 @@ hipError_t RT_LIST_FN(launch_trace)(const RenderArgs& A, unsigned blocks, const 
     return hipGetLastError();
 }
 #ifndef RT_TU_CONTRACT
+hipError_t RT_LIST_FN(launch_guides)(const RenderArgs& A, unsigned blocks, long long n, rt_hit_record* out, hipStream_t st) {
+    hipLaunchKernelGGL((k_guides<false>), dim3(blocks), dim3(256), 0, st, A, n, out);
+    return hipGetLastError();
+}
 hipError_t RT_LIST_FN(launch_render_adaptive)(const RenderArgs& A, hipStream_t st) {
     const unsigned need = (unsigned)((A.n_local_tiles + 3) / 4);
     const unsigned cap = resident_blocks(k_render<false, 2, 1>, 0);
@@ -2131,6 +2166,7 @@ hipError_t RT_LIST_FN(launch_render_adaptive)(const RenderArgs& A, hipStream_t s
 hipError_t launch_tile_cost_list(const RenderArgs& A, unsigned blocks, int* cost, unsigned char* pilot, hipStream_t st);
 hipError_t launch_render_list(const RenderArgs& A, int mode, hipStream_t st);
 hipError_t launch_trace_list(const RenderArgs& A, unsigned blocks, const float* rays, long long n, rt_hit_record* out, hipStream_t st);
+hipError_t launch_guides_list(const RenderArgs& A, unsigned blocks, long long n, rt_hit_record* out, hipStream_t st);
 hipError_t launch_render_adaptive_list(const RenderArgs& A, hipStream_t st);
 #endif
 
@@ -2309,6 +2345,24 @@ hipError_t launch_trace(const DevScene& S, const DevTree& T, bool tree, const fl
     else hipLaunchKernelGGL((k_trace<true>), dim3(blocks), dim3(256), tree_lds_bytes(T.n_nodes), st, A, rays, n, out);
     return hipGetLastError();
 }
+
+#ifndef RT_TU_CONTRACT
+// the guides of a max_x x max_y frame (max_x * max_y < 2^31), launched as launch_trace launches k_trace: the same walk for every tree variant
+hipError_t launch_guides(const DevScene& S, const DevTree& T, bool tree, int max_x, int max_y, rt_hit_record* out, hipStream_t st) {
+    const long long n = (long long)max_x * max_y;
+    if (n <= 0) return hipSuccess;
+    const unsigned blocks = (unsigned)((n + 255) / 256);
+    RenderArgs A{};
+    A.scene = S; A.tree = T; A.max_x = max_x; A.max_y = max_y;
+    if (!tree) return launch_guides_list(A, blocks, n, out, st);
+    const int variant = render_variant(true, 0, T.acc);
+    if (variant == 5) hipLaunchKernelGGL((k_guides<true, 5>), dim3(blocks), dim3(256), tree_lds_bytes(T.n_nodes, true), st, A, n, out);
+    else if (variant == 4) hipLaunchKernelGGL((k_guides<true, 4>), dim3(blocks), dim3(256), tree_lds_bytes(T.n_nodes, true), st, A, n, out);
+    else if (variant == 2) hipLaunchKernelGGL((k_guides<true, 2>), dim3(blocks), dim3(256), tree_lds_bytes(T.n_nodes, true), st, A, n, out);
+    else hipLaunchKernelGGL((k_guides<true>), dim3(blocks), dim3(256), tree_lds_bytes(T.n_nodes), st, A, n, out);
+    return hipGetLastError();
+}
+#endif
 
 hipError_t launch_assemble(float* full, const float* parts, int max_x, int max_y, int nparts, hipStream_t st) {
     const int tiles_x = (max_x + 7) / 8, tiles_y = (max_y + 7) / 8;

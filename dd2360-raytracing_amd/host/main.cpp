@@ -10,6 +10,10 @@
 //   ... [REL_ERROR] [MIN_SPP] [BATCH] [FLOOR]
 // REL_ERROR > 0 renders through rt_render_adaptive with max_spp = ns: MIN_SPP defaults to 4 (ns if smaller), BATCH to the largest of
 // 4, 2, 1 that divides ns - MIN_SPP, FLOOR to 0.  Without REL_ERROR (or with 0) the program does exactly what it does without them.
+// Denoising (no reference counterpart) takes one more:
+//   ... [DENOISE]
+// DENOISE > 0: after the render, rt_render_guides + rt_denoise (GAMMA input, DENOISE levels, the header's default weights) filter the
+// frame before it is written.  0 or absent: exactly the program without it.  fp32 only: USE_FP16 1 with DENOISE > 0 is an error.
 #include <iostream>
 #include <string>
 #include <vector>
@@ -39,6 +43,7 @@ int main(int argc, char** argv) {
     int build_on_gpu = 0;
     float rel_error = 0.f, floor_lum = 0.f;   // adaptive sampling (rt_render_adaptive): off
     int min_spp = -1, batch = -1;
+    int denoise_levels = 0;              // rt_denoise: off
     const int tx = 8, ty = 8;
     if (argc > 1) output_mode = std::stoi(argv[1]);
     if (argc > 2) num_spheres = std::stoi(argv[2]);
@@ -54,10 +59,15 @@ int main(int argc, char** argv) {
     if (argc > 12) min_spp = std::stoi(argv[12]);
     if (argc > 13) batch = std::stoi(argv[13]);
     if (argc > 14) floor_lum = std::stof(argv[14]);
+    if (argc > 15) denoise_levels = std::stoi(argv[15]);
     const bool adaptive = rel_error > 0.f;
     if (min_spp < 0) min_spp = ns < 4 ? ns : 4;
     if (batch < 0) batch = (ns - min_spp) % 4 == 0 ? 4 : ((ns - min_spp) % 2 == 0 ? 2 : 1);
     const int precision = use_fp16 ? RT_PRECISION_FP16 : RT_PRECISION_FP32;
+    if (denoise_levels > 0 && use_fp16) {
+        std::cerr << "DENOISE needs a binary32 frame (USE_FP16 0)\n";
+        return 99;
+    }
 
     std::cerr << "Rendering a " << nx << "x" << ny << " image with " << ns << " samples per pixel ";
     std::cerr << "in " << tx << "x" << ty << " blocks.\n";
@@ -68,6 +78,7 @@ int main(int argc, char** argv) {
     if (adaptive)
         std::cerr << "Adaptive sampling: " << min_spp << " to " << ns << " samples per pixel in steps of " << batch << ", relative error " << rel_error
                   << ", floor " << floor_lum << "\n";
+    if (denoise_levels > 0) std::cerr << "Denoising: " << denoise_levels << " levels\n";
 
     checkHipErrors(rt_device_check(nullptr));
     const rt_partition whole = {0, 1};
@@ -127,6 +138,21 @@ int main(int argc, char** argv) {
         for (int32_t k : spp) total += k;
         std::cerr << "mean samples per pixel: " << total / (double)num_pixels << "\n";
         checkHipErrors(hipFree(d_spp));
+    }
+
+    if (denoise_levels > 0) {
+        // guides of the pixel centres, then the filter in place (fb_out == fb_in), default weights
+        const rt_denoise_params params = {RT_DENOISE_INPUT_GAMMA, 1, denoise_levels, RT_DENOISE_DEFAULT_NORMAL_POW_LOG2,
+                                          RT_DENOISE_DEFAULT_SIGMA_POSITION, RT_DENOISE_DEFAULT_SIGMA_COLOR};
+        rt_hit_record* d_hits = nullptr;
+        void* d_work = nullptr;
+        checkHipErrors(hipMalloc(reinterpret_cast<void**>(&d_hits), num_pixels * sizeof(rt_hit_record)));
+        checkHipErrors(hipMalloc(&d_work, num_pixels * RT_DENOISE_WORK_BYTES));
+        checkHipErrors(rt_render_guides(d_world, d_octree, nx, ny, d_hits, nullptr));
+        checkHipErrors(rt_denoise(fb, fb, nx, ny, d_hits, &params, d_work, nullptr));
+        checkHipErrors(hipDeviceSynchronize());
+        checkHipErrors(hipFree(d_work));
+        checkHipErrors(hipFree(d_hits));
     }
 
     if (output_mode == 0 || output_mode == 3) {

@@ -52,6 +52,27 @@ class Adaptive(C.Structure):
 
 ADAPTIVE_STATE_BYTES = 24      # rt_amd.h RT_ADAPTIVE_STATE_BYTES: the refinement state per buffer element (S_rgb, SL, Q, k)
 
+
+class DenoiseParams(C.Structure):
+    """rt_denoise_params: input mode (DENOISE_INPUT_*), the progressive sample count (SUM), levels (step 2^L at level L), the normal
+    exponent's log2 (-1 = off) and the position / colour sigmas (0 = off); include/rt_amd.h states the exact filter"""
+    _fields_ = [("input", C.c_int32), ("samples", C.c_int32), ("levels", C.c_int32), ("normal_pow_log2", C.c_int32),
+                ("sigma_position", C.c_float), ("sigma_color", C.c_float)]
+
+DENOISE_INPUT_GAMMA, DENOISE_INPUT_SUM = 0, 1      # rt_amd.h RT_DENOISE_INPUT_*
+DENOISE_MAX_LEVELS = 8
+DENOISE_MAX_PIXELS = 1 << 30   # rt_amd.h RT_DENOISE_MAX_PIXELS: the largest frame of render_guides / denoise
+DENOISE_WORK_BYTES = 32        # rt_amd.h RT_DENOISE_WORK_BYTES: the workspace per pixel (two float4 colour buffers)
+# rt_amd.h RT_DENOISE_DEFAULT_*: chosen on C3 at 16 spp for the lowest RMSE against 1024 spp (tools/denoise_study.py)
+DENOISE_DEFAULTS = dict(levels=2, normal_pow_log2=4, sigma_position=0.01, sigma_color=0.3)
+
+
+def denoise_params(input=DENOISE_INPUT_GAMMA, samples=1, **kw):
+    """a DenoiseParams with the library's defaults for whatever kw does not set"""
+    p = dict(DENOISE_DEFAULTS)
+    p.update(kw)
+    return DenoiseParams(input, samples, p["levels"], p["normal_pow_log2"], p["sigma_position"], p["sigma_color"])
+
 # every symbol include/rt_amd.h declares: (restype, argtypes)
 _vp, _i, _i64, _f = C.c_void_p, C.c_int, C.c_int64, C.c_float
 SYMBOLS = {
@@ -118,6 +139,9 @@ SYMBOLS = {
     "rt_multi_set_split": (_i, [_vp, _i]),
     "rt_multi_last_split": (_i, [_vp, _vp]),
     "rt_trace_rays": (_i, [_vp, _vp, _vp, _i64, _vp, _vp]),
+    "rt_render_guides": (_i, [_vp, _vp, _i, _i, _vp, _vp]),
+    "rt_denoise": (_i, [_vp, _vp, _i, _i, _vp, C.POINTER(DenoiseParams), _vp, _vp]),
+    "rt_denoise_check": (_i, [_i, _i, C.POINTER(DenoiseParams)]),
     "rt_write_ppm": (_i, [C.c_char_p, _i, _i, _vp, _i]),
     "rt_format_ppm": (_i64, [_i, _i, _vp, _i, _vp, _i64]),
     "rt_write_image": (_i, [C.c_char_p, _i, _i, _vp, _i, _i]),
@@ -582,6 +606,33 @@ def assemble(fb_full, fb_parts, max_x, max_y, nparts, precision=FP32):
 
 def trace_rays(world, octree, d_rays, n, d_out):
     check(lib().rt_trace_rays(world.h, octree.h if octree is not None else None, _dev(d_rays), n, _dev(d_out), _stream()), "rt_trace_rays")
+
+
+def alloc_guides(max_x, max_y, device="cuda"):
+    """the guide buffer of render_guides: one 32-byte rt_hit_record per pixel (view it on the host with hit_record_dtype)"""
+    import torch
+    return torch.zeros(max_x * max_y * 32, dtype=torch.uint8, device=device)
+
+
+def alloc_denoise_work(max_x, max_y, device="cuda"):
+    """the workspace of denoise: DENOISE_WORK_BYTES per pixel"""
+    import torch
+    return torch.empty(max_x * max_y * DENOISE_WORK_BYTES // 4, dtype=torch.float32, device=device)
+
+
+def render_guides(world, octree, max_x, max_y, d_hits):
+    """rt_render_guides on the current stream: the first hit of every pixel's centre ray, row-major, into d_hits (alloc_guides)"""
+    check(lib().rt_render_guides(world.h, octree.h if octree is not None else None, max_x, max_y, _dev(d_hits), _stream()), "rt_render_guides")
+
+
+def denoise_check(max_x, max_y, params):
+    """rt_denoise_check: True when denoise accepts a frame of this size with these parameters (host only, nothing is launched)"""
+    return lib().rt_denoise_check(max_x, max_y, C.byref(params)) == 0
+
+
+def denoise(fb_out, fb_in, max_x, max_y, d_hits, params, d_work):
+    """rt_denoise on the current stream: params is a DenoiseParams (denoise_params()); fb_out may be fb_in"""
+    check(lib().rt_denoise(_dev(fb_out), _dev(fb_in), max_x, max_y, _dev(d_hits), C.byref(params), _dev(d_work), _stream()), "rt_denoise")
 
 
 def write_image(path, fb_host, nx, ny, precision=FP32, fmt=IMAGE_P6):

@@ -409,6 +409,64 @@ int rt_multi_selftest(rt_multi* m, const void* d_src, void* d_dst, size_t bytes,
 int rt_trace_rays(const rt_world* world, const rt_octree* d_octree, const float* d_rays, int64_t n,
                   rt_hit_record* d_out, void* stream);
 
+/* ---- denoising (no reference counterpart; filters what render / render_progressive leave, main.cu:96-142) ----------------
+ * Frames of at most RT_DENOISE_MAX_PIXELS pixels: the filter kernels index pixels and the halves of their guide records in int. */
+#define RT_DENOISE_MAX_PIXELS 1073741824   /* 2^30 */
+/* Guide buffers: the first hit of every pixel's centre ray.  d_hits = max_x*max_y records on the device, the reference's row-major
+ * layout (pixel_index = j*max_x + i, row 0 at the bottom).  The ray, in binary32 with one rounding per operation:
+ *   u = ((float)i + 0.5f) / (float)max_x;  v = ((float)j + 0.5f) / (float)max_y;  o = cam.origin;
+ *   d[c] = ((lower_left_corner[c] + u*horizontal[c]) + v*vertical[c]) - origin[c]
+ * — camera::get_ray with both pixel-jitter draws 0.5 and no lens offset: a pinhole, so the guides are sharp where a camera with an
+ * aperture (C3's is 0.1) renders the frame slightly defocused.  Each record is bit for bit what rt_trace_rays returns for that ray
+ * (sphere = -1 and zeros on a miss), through the walk rt_render uses for this world and tree, always in the IEEE arithmetic (also for
+ * RT_ARITH_CONTRACT worlds).  RT_EINVAL for NULL pointers, non-positive sizes, frames of more than RT_DENOISE_MAX_PIXELS pixels and a
+ * tree whose precision is not the world's; then RT_ENOTSUP for USE_FP16 worlds.  Uploads the world and tree if need be, as
+ * rt_trace_rays does. */
+int rt_render_guides(const rt_world* world, const rt_octree* d_octree, int max_x, int max_y, rt_hit_record* d_hits, void* stream);
+
+/* An edge-avoiding a-trous filter guided by those records (fp32 frames only).  Everything in IEEE binary32, one rounding per operation,
+ * no contraction, no transcendental function, sums in tap order (tests/denoise_model.py is the model, bit for bit):
+ *   linear input x:  GAMMA x = c*c per channel;  SUM x = c / (float)samples (the reference viewer's fb / n).
+ *   pass-through:    a pixel whose d_hits[p].sphere == -1 (the sky) or whose x has a channel that is not finite keeps its display value —
+ *                    GAMMA the bits of fb_in, SUM sqrtf(x) — and is never a tap of another pixel (skipped, not weighted by 0).
+ *   level L = 0 .. levels-1, h = 2^L: the taps of pixel p are q = p + h*(dx, dy), dx, dy in -2..2, dy outer, both from -2; a tap is
+ *                    skipped when it lies outside the frame, on another sphere (sphere_q != sphere_p) or is a pass-through pixel.
+ *   tap weight:      w = (k[dx]*k[dy] * w_n) / ((1 + a_pos) * (1 + a_col)),   k = {1/16, 1/4, 3/8, 1/4, 1/16}
+ *                    d = (n_p.x*n_q.x + n_p.y*n_q.y) + n_p.z*n_q.z;  w_n = d > 0 ? d : 0, then w_n = w_n*w_n normal_pow_log2 times
+ *                    a_pos = (((P_p - P_q).x^2 + (P_p - P_q).y^2) + (P_p - P_q).z^2) / (t_p*t_p) * (1 / sigma_position^2)
+ *                    a_col = (((x_p - x_q).r^2 + (x_p - x_q).g^2) + (x_p - x_q).b^2) * (4^L / sigma_color^2), x = this level's input
+ *                    (the factors in brackets are rounded once on the host; a term that is off is w_n = 1, a_pos = 0 or a_col = 0).
+ *   level result:    y_p = sum(w * x_q) / sum(w) per channel, the centre tap included; the next level's input.
+ *   output:          fb_out = sqrtf(y) after the last level, the gamma of rt_render.
+ * Pass-through is decided once, on the input.  fb_out may equal fb_in (no other overlap).  d_work: caller-owned workspace of
+ * RT_DENOISE_WORK_BYTES per pixel (two float4 colour buffers); d_hits and d_work 16-byte aligned.  One prepare launch and one launch per
+ * level, no allocation, no synchronisation: the call can be captured into a hipGraph.  RT_EINVAL for NULL pointers, misaligned d_hits /
+ * d_work, and whatever rt_denoise_check refuses: non-positive sizes, frames of more than RT_DENOISE_MAX_PIXELS pixels, a NULL params,
+ * an unknown input mode, samples < 1 with SUM, levels outside 1..RT_DENOISE_MAX_LEVELS, normal_pow_log2 outside -1..10, negative or
+ * non-finite sigmas, and a sigma > 0 whose scale factor above is not finite (0 * inf at the centre tap).  Defaults
+ * (RT_DENOISE_DEFAULT_*): chosen on C3 at 16 spp for the lowest RMSE against rt_render at 1024 spp. */
+#define RT_DENOISE_INPUT_GAMMA 0   /* fb_in holds sqrt(mean), as rt_render / rt_render_adaptive write it */
+#define RT_DENOISE_INPUT_SUM 1     /* fb_in holds the sum of `samples` sample colours, as rt_render_progressive leaves it */
+#define RT_DENOISE_MAX_LEVELS 8
+#define RT_DENOISE_WORK_BYTES 32   /* per pixel */
+#define RT_DENOISE_DEFAULT_LEVELS 2
+#define RT_DENOISE_DEFAULT_NORMAL_POW_LOG2 4
+#define RT_DENOISE_DEFAULT_SIGMA_POSITION 0.01f
+#define RT_DENOISE_DEFAULT_SIGMA_COLOR 0.3f
+typedef struct rt_denoise_params {
+    int32_t input;            /* RT_DENOISE_INPUT_* */
+    int32_t samples;          /* SUM: the current_sample of the progressive sequence (>= 1); GAMMA: ignored */
+    int32_t levels;           /* 1 .. RT_DENOISE_MAX_LEVELS; level L uses step 2^L */
+    int32_t normal_pow_log2;  /* normal weight = max(dot, 0)^(2^k); -1 = no normal term */
+    float sigma_position;     /* relative to the centre's distance t; 0 = no position term */
+    float sigma_color;        /* in linear colour, halved every level; 0 = no colour term */
+} rt_denoise_params;
+int rt_denoise(void* fb_out, const void* fb_in, int max_x, int max_y, const rt_hit_record* d_hits, const rt_denoise_params* params,
+               void* d_work, void* stream);
+/* The frame-size and parameter checks of rt_denoise alone, on the host, no device work: 0 when rt_denoise accepts a frame of this size
+ * with these parameters (given valid buffers), RT_EINVAL otherwise — before the workspace is allocated, for instance. */
+int rt_denoise_check(int max_x, int max_y, const rt_denoise_params* params);
+
 /* ---- host side: output --------------------------------------------------------------------------------------- */
 /* output_to_stream — main.cu:321-333: ASCII P3, top row first, int(255.99*c).  fb is a HOST buffer.
  * path == NULL writes to stdout (output mode 0), otherwise to the file (output mode 3 uses "output.ppm"). */
