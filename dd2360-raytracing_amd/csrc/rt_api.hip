@@ -34,6 +34,8 @@ hipError_t launch_trace(const DevScene& S, const DevTree& T, bool tree, const fl
 hipError_t launch_guides(const DevScene& S, const DevTree& T, bool tree, int max_x, int max_y, rt_hit_record* out, hipStream_t st);
 hipError_t launch_denoise(float* fb_out, const float* fb_in, int max_x, int max_y, const rt_hit_record* hits, const rt_denoise_params& P,
                           float4* work, hipStream_t st);      // rt_denoise.hip
+hipError_t launch_denoise_var(float* fb_out, const float* fb_in, int max_x, int max_y, const rt_hit_record* hits, const void* state,
+                              const rt_denoise_var_params& P, float4* work, hipStream_t st);      // rt_denoise.hip
 hipError_t launch_assemble(float* full, const float* parts, int max_x, int max_y, int nparts, hipStream_t st);
 hipError_t launch_render_adaptive(const RenderArgs& A, bool tree, hipStream_t st);
 hipError_t launch_adapt_check(float* fb, const float* sl, const float* q, const unsigned int* list_in, const unsigned int* count_in, long long n_all,
@@ -1248,6 +1250,27 @@ int rt_denoise(void* fb_out, const void* fb_in, int max_x, int max_y, const rt_h
     const int rc = rt_denoise_check(max_x, max_y, params);
     if (rc) return rc;
     return (int)launch_denoise((float*)fb_out, (const float*)fb_in, max_x, max_y, d_hits, *params, (float4*)d_work, (hipStream_t)stream);
+}
+
+// the frame size and parameter checks of rt_denoise_adaptive (host only)
+int rt_denoise_adaptive_check(int max_x, int max_y, const rt_denoise_var_params* params) {
+    if (!params || max_x <= 0 || max_y <= 0 || (long long)max_x * max_y > RT_DENOISE_MAX_PIXELS) return RT_EINVAL;
+    const rt_denoise_var_params& P = *params;
+    if (P.levels < 1 || P.levels > RT_DENOISE_MAX_LEVELS) return RT_EINVAL;
+    if (P.normal_pow_log2 < -1 || P.normal_pow_log2 > 10) return RT_EINVAL;
+    if (P.prefilter != 0 && P.prefilter != 1) return RT_EINVAL;
+    if (!denoise_sigma_ok(P.sigma_position, 1.0f)) return RT_EINVAL;
+    if (!(P.sigma_variance >= 0.0f) || !std::isfinite(P.sigma_variance * P.sigma_variance)) return RT_EINVAL;      // sv2 multiplies the variance
+    return 0;
+}
+
+int rt_denoise_adaptive(void* fb_out, const void* fb_in, int max_x, int max_y, const rt_hit_record* d_hits, const void* d_state,
+                        const rt_denoise_var_params* params, void* d_work, void* stream) {
+    if (!fb_out || !fb_in || !d_hits || !d_state || !d_work) return RT_EINVAL;
+    if (((uintptr_t)d_hits & 15) || ((uintptr_t)d_work & 15)) return RT_EINVAL;        // read and written as float4
+    const int rc = rt_denoise_adaptive_check(max_x, max_y, params);
+    if (rc) return rc;
+    return (int)launch_denoise_var((float*)fb_out, (const float*)fb_in, max_x, max_y, d_hits, d_state, *params, (float4*)d_work, (hipStream_t)stream);
 }
 
 #ifdef RT_H16_STATS

@@ -14,6 +14,11 @@
 //   ... [DENOISE]
 // DENOISE > 0: after the render, rt_render_guides + rt_denoise (GAMMA input, DENOISE levels, the header's default weights) filter the
 // frame before it is written.  0 or absent: exactly the program without it.  fp32 only: USE_FP16 1 with DENOISE > 0 is an error.
+// The variance-guided filter (no reference counterpart) takes one more:
+//   ... [DENOISE_SIGMA_VARIANCE]
+// > 0 together with REL_ERROR > 0 and DENOISE > 0: the frame is rendered through rt_render_adaptive_begin, which keeps every pixel's
+// sums, and filtered by rt_denoise_adaptive (DENOISE levels, this sigma_variance, the header's other defaults).  0 or absent: exactly
+// the program without it.  A positive value without a positive REL_ERROR and a positive DENOISE is an error.
 #include <iostream>
 #include <string>
 #include <vector>
@@ -44,6 +49,7 @@ int main(int argc, char** argv) {
     float rel_error = 0.f, floor_lum = 0.f;   // adaptive sampling (rt_render_adaptive): off
     int min_spp = -1, batch = -1;
     int denoise_levels = 0;              // rt_denoise: off
+    float denoise_sigma_variance = 0.f;  // rt_denoise_adaptive: off
     const int tx = 8, ty = 8;
     if (argc > 1) output_mode = std::stoi(argv[1]);
     if (argc > 2) num_spheres = std::stoi(argv[2]);
@@ -60,12 +66,19 @@ int main(int argc, char** argv) {
     if (argc > 13) batch = std::stoi(argv[13]);
     if (argc > 14) floor_lum = std::stof(argv[14]);
     if (argc > 15) denoise_levels = std::stoi(argv[15]);
+    if (argc > 16) denoise_sigma_variance = std::stof(argv[16]);
     const bool adaptive = rel_error > 0.f;
     if (min_spp < 0) min_spp = ns < 4 ? ns : 4;
     if (batch < 0) batch = (ns - min_spp) % 4 == 0 ? 4 : ((ns - min_spp) % 2 == 0 ? 2 : 1);
     const int precision = use_fp16 ? RT_PRECISION_FP16 : RT_PRECISION_FP32;
     if (denoise_levels > 0 && use_fp16) {
         std::cerr << "DENOISE needs a binary32 frame (USE_FP16 0)\n";
+        return 99;
+    }
+
+    const bool denoise_var = denoise_sigma_variance > 0.f;
+    if (denoise_var && !(adaptive && denoise_levels > 0)) {
+        std::cerr << "DENOISE_SIGMA_VARIANCE needs adaptive sampling and the filter (REL_ERROR > 0 and DENOISE > 0)\n";
         return 99;
     }
 
@@ -79,6 +92,7 @@ int main(int argc, char** argv) {
         std::cerr << "Adaptive sampling: " << min_spp << " to " << ns << " samples per pixel in steps of " << batch << ", relative error " << rel_error
                   << ", floor " << floor_lum << "\n";
     if (denoise_levels > 0) std::cerr << "Denoising: " << denoise_levels << " levels\n";
+    if (denoise_var) std::cerr << "Variance-guided weights: sigma_variance " << denoise_sigma_variance << "\n";
 
     checkHipErrors(rt_device_check(nullptr));
     const rt_partition whole = {0, 1};
@@ -120,10 +134,16 @@ int main(int argc, char** argv) {
     checkHipErrors(rt_render_init(nx, ny, d_rand_state, whole, nullptr));
     checkHipErrors(hipDeviceSynchronize());
     int32_t* d_spp = nullptr;
+    void* d_state = nullptr;             // every pixel's sums and sample count, for rt_denoise_adaptive
     if (adaptive) {
         const rt_adaptive params = {min_spp, ns, batch, rel_error, floor_lum};
         checkHipErrors(hipMalloc(reinterpret_cast<void**>(&d_spp), num_pixels * sizeof(int32_t)));
-        checkHipErrors(rt_render_adaptive(fb, nx, ny, &params, d_world, d_rand_state, d_octree, d_spp, nullptr));
+        if (denoise_var) {
+            checkHipErrors(hipMalloc(&d_state, num_pixels * RT_ADAPTIVE_STATE_BYTES));
+            checkHipErrors(rt_render_adaptive_begin(fb, nx, ny, &params, d_world, d_rand_state, d_octree, d_spp, d_state, whole, nullptr));
+        } else {
+            checkHipErrors(rt_render_adaptive(fb, nx, ny, &params, d_world, d_rand_state, d_octree, d_spp, nullptr));
+        }
     } else {
         checkHipErrors(rt_render(fb, nx, ny, ns, d_world, d_rand_state, d_octree, whole, nullptr));
     }
@@ -140,7 +160,21 @@ int main(int argc, char** argv) {
         checkHipErrors(hipFree(d_spp));
     }
 
-    if (denoise_levels > 0) {
+    if (denoise_var) {
+        // guides of the pixel centres, then the variance-guided filter in place on the state the render left
+        const rt_denoise_var_params params = {denoise_levels, RT_DENOISE_VAR_DEFAULT_NORMAL_POW_LOG2, RT_DENOISE_VAR_DEFAULT_PREFILTER,
+                                              RT_DENOISE_VAR_DEFAULT_SIGMA_POSITION, denoise_sigma_variance};
+        rt_hit_record* d_hits = nullptr;
+        void* d_work = nullptr;
+        checkHipErrors(hipMalloc(reinterpret_cast<void**>(&d_hits), num_pixels * sizeof(rt_hit_record)));
+        checkHipErrors(hipMalloc(&d_work, num_pixels * RT_DENOISE_WORK_BYTES));
+        checkHipErrors(rt_render_guides(d_world, d_octree, nx, ny, d_hits, nullptr));
+        checkHipErrors(rt_denoise_adaptive(fb, fb, nx, ny, d_hits, d_state, &params, d_work, nullptr));
+        checkHipErrors(hipDeviceSynchronize());
+        checkHipErrors(hipFree(d_work));
+        checkHipErrors(hipFree(d_hits));
+        checkHipErrors(hipFree(d_state));
+    } else if (denoise_levels > 0) {
         // guides of the pixel centres, then the filter in place (fb_out == fb_in), default weights
         const rt_denoise_params params = {RT_DENOISE_INPUT_GAMMA, 1, denoise_levels, RT_DENOISE_DEFAULT_NORMAL_POW_LOG2,
                                           RT_DENOISE_DEFAULT_SIGMA_POSITION, RT_DENOISE_DEFAULT_SIGMA_COLOR};

@@ -73,6 +73,24 @@ def denoise_params(input=DENOISE_INPUT_GAMMA, samples=1, **kw):
     p.update(kw)
     return DenoiseParams(input, samples, p["levels"], p["normal_pow_log2"], p["sigma_position"], p["sigma_color"])
 
+
+class DenoiseVarParams(C.Structure):
+    """rt_denoise_var_params: levels, the normal exponent's log2 (-1 = off), prefilter (1 = the centre's variance is its 3x3 blur), the
+    position sigma and the variance sigma in standard errors of the centre's mean luminance (0 = off); include/rt_amd.h states the rule"""
+    _fields_ = [("levels", C.c_int32), ("normal_pow_log2", C.c_int32), ("prefilter", C.c_int32), ("sigma_position", C.c_float),
+                ("sigma_variance", C.c_float)]
+
+DENOISE_VAR_EPS = 1e-8         # rt_amd.h RT_DENOISE_VAR_EPS
+# rt_amd.h RT_DENOISE_VAR_DEFAULT_*: one setting for C3 at 16, 64 and 128 spp (tools/denoise_variance_study.py)
+DENOISE_VAR_DEFAULTS = dict(levels=1, normal_pow_log2=4, prefilter=1, sigma_position=0.01, sigma_variance=4.0)
+
+
+def denoise_var_params(**kw):
+    """a DenoiseVarParams with the library's defaults for whatever kw does not set"""
+    p = dict(DENOISE_VAR_DEFAULTS)
+    p.update(kw)
+    return DenoiseVarParams(p["levels"], p["normal_pow_log2"], p["prefilter"], p["sigma_position"], p["sigma_variance"])
+
 # every symbol include/rt_amd.h declares: (restype, argtypes)
 _vp, _i, _i64, _f = C.c_void_p, C.c_int, C.c_int64, C.c_float
 SYMBOLS = {
@@ -142,6 +160,8 @@ SYMBOLS = {
     "rt_render_guides": (_i, [_vp, _vp, _i, _i, _vp, _vp]),
     "rt_denoise": (_i, [_vp, _vp, _i, _i, _vp, C.POINTER(DenoiseParams), _vp, _vp]),
     "rt_denoise_check": (_i, [_i, _i, C.POINTER(DenoiseParams)]),
+    "rt_denoise_adaptive": (_i, [_vp, _vp, _i, _i, _vp, _vp, C.POINTER(DenoiseVarParams), _vp, _vp]),
+    "rt_denoise_adaptive_check": (_i, [_i, _i, C.POINTER(DenoiseVarParams)]),
     "rt_write_ppm": (_i, [C.c_char_p, _i, _i, _vp, _i]),
     "rt_format_ppm": (_i64, [_i, _i, _vp, _i, _vp, _i64]),
     "rt_write_image": (_i, [C.c_char_p, _i, _i, _vp, _i, _i]),
@@ -633,6 +653,18 @@ def denoise_check(max_x, max_y, params):
 def denoise(fb_out, fb_in, max_x, max_y, d_hits, params, d_work):
     """rt_denoise on the current stream: params is a DenoiseParams (denoise_params()); fb_out may be fb_in"""
     check(lib().rt_denoise(_dev(fb_out), _dev(fb_in), max_x, max_y, _dev(d_hits), C.byref(params), _dev(d_work), _stream()), "rt_denoise")
+
+
+def denoise_adaptive_check(max_x, max_y, params):
+    """rt_denoise_adaptive_check: True when denoise_adaptive accepts a frame of this size with these parameters (host only)"""
+    return lib().rt_denoise_adaptive_check(max_x, max_y, C.byref(params)) == 0
+
+
+def denoise_adaptive(fb_out, fb_in, max_x, max_y, d_hits, d_state, params, d_work):
+    """rt_denoise_adaptive on the current stream: d_state is the whole-frame state render_adaptive_begin / _refine left, fb_in the frame
+    of the same call, params a DenoiseVarParams (denoise_var_params()); fb_out may be fb_in"""
+    check(lib().rt_denoise_adaptive(_dev(fb_out), _dev(fb_in), max_x, max_y, _dev(d_hits), _dev(d_state), C.byref(params), _dev(d_work),
+                                    _stream()), "rt_denoise_adaptive")
 
 
 def write_image(path, fb_host, nx, ny, precision=FP32, fmt=IMAGE_P6):

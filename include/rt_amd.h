@@ -467,6 +467,53 @@ int rt_denoise(void* fb_out, const void* fb_in, int max_x, int max_y, const rt_h
  * with these parameters (given valid buffers), RT_EINVAL otherwise — before the workspace is allocated, for instance. */
 int rt_denoise_check(int max_x, int max_y, const rt_denoise_params* params);
 
+/* The same filter with variance-guided weights, on the state an adaptive render left (fp32 frames only): a tap is down-weighted by how
+ * many standard errors its luminance lies from the centre's, so the filter blurs where the frame is noisy and fades out where it has
+ * converged, pixel by pixel, whatever sample count each pixel stopped at.  d_state is the state of a WHOLE frame — what
+ * rt_render_adaptive_begin or a chain of rt_render_adaptive_refine left for part = {0, 1, 0, 0}: row-major, RT_ADAPTIVE_STATE_BYTES per
+ * pixel (parts are not offered: a tile-major part has no neighbours to filter with) — and fb_in the frame the same call left (gamma).
+ * Everything in IEEE binary32, one rounding per operation, no contraction, no transcendental function, sums in tap order
+ * (tests/denoise_var_model.py is the model, bit for bit):
+ *   per pixel:       n = (float)k;  x_c = S_c / n per channel;  d = n*Q - SL*SL;  d = d > 0 ? d : 0 (a NaN d becomes 0);
+ *                    v = d / ((n*n) * (n - 1)) — the variance of the pixel's mean luminance.
+ *   pass-through:    decided once: d_hits[p].sphere == -1, k < 2, or a channel of x or v not finite (an overflowing n*Q or SL*SL included).
+ *                    Such a pixel keeps the bits of fb_in and is never a tap of another pixel (skipped, not weighted by 0).
+ *   level L = 0 .. levels-1, h = 2^L, this level's input x, v:  l = (x.r + x.g) + x.b.  Taps and skip rules are those of rt_denoise:
+ *                    q = p + h*(dx, dy), dx, dy in -2..2, dy outer, both from -2; skipped outside the frame, on another sphere, pass-through.
+ *   centre variance: prefilter == 1:  vb_p = sum(g * v_q) / sum(g) over q = p + (dx, dy), dx, dy in -1..1 at step 1 whatever h is, dy
+ *                    outer, both from -1, g = k3[dx]*k3[dy], k3 = {1/4, 1/2, 1/4}, the same skip rules;  prefilter == 0:  vb_p = v_p.
+ *   tap weight:      w = (k[dx]*k[dy] * w_n) / ((1 + a_pos) * (1 + a_var)),  k, w_n and a_pos exactly as in rt_denoise;
+ *                    a_var = ((l_p - l_q)*(l_p - l_q)) / (sv2 * vb_p + RT_DENOISE_VAR_EPS),  sv2 = sigma_variance^2 rounded once on the
+ *                    host; a_var = 0 when sigma_variance == 0.  Only the centre's variance enters: a converged pixel refuses a noisy
+ *                    neighbour.  sv2 * vb_p may overflow to +inf in a later level (then a_var = 0, or NaN for an infinite l difference):
+ *                    nothing is clamped, the operations are performed as written.
+ *   level result:    y_p = sum(w * x_q) / sum(w) per channel;  v'_p = sum((w*w) * v_q) / (sum(w) * sum(w));  both the next level's input.
+ *   output:          fb_out = sqrtf(y) after the last level.
+ * fb_out may equal fb_in (no other overlap).  d_hits from rt_render_guides, d_work of RT_DENOISE_WORK_BYTES per pixel, both 16-byte
+ * aligned, as for rt_denoise.  One prepare launch and one launch per level, no allocation, no synchronisation, no atomics: the call can
+ * be captured into a hipGraph.  RT_EINVAL for NULL pointers, misaligned d_hits / d_work, and whatever rt_denoise_adaptive_check (host
+ * only) refuses: non-positive sizes, frames of more than RT_DENOISE_MAX_PIXELS pixels, a NULL params, levels outside
+ * 1..RT_DENOISE_MAX_LEVELS, normal_pow_log2 outside -1..10, prefilter outside 0..1, negative or non-finite sigmas, a sigma_position > 0
+ * whose 1 / sigma^2 is not finite and a sigma_variance whose square is not finite.  With sigma_variance == 0, prefilter == 0 and one k
+ * for all pixels, every filtered pixel is what rt_denoise gives for RT_DENOISE_INPUT_SUM, samples = k, sigma_color = 0 on S_rgb.
+ * Defaults (RT_DENOISE_VAR_DEFAULT_*): one setting for C3 at 16, 64 and 128 spp. */
+#define RT_DENOISE_VAR_EPS 1e-8f   /* keeps the centre tap's a_var from 0 / 0 where the variance is 0 */
+#define RT_DENOISE_VAR_DEFAULT_LEVELS 1
+#define RT_DENOISE_VAR_DEFAULT_NORMAL_POW_LOG2 4
+#define RT_DENOISE_VAR_DEFAULT_PREFILTER 1
+#define RT_DENOISE_VAR_DEFAULT_SIGMA_POSITION 0.01f
+#define RT_DENOISE_VAR_DEFAULT_SIGMA_VARIANCE 4.0f
+typedef struct rt_denoise_var_params {
+    int32_t levels;           /* 1 .. RT_DENOISE_MAX_LEVELS; level L uses step 2^L */
+    int32_t normal_pow_log2;  /* as rt_denoise_params */
+    int32_t prefilter;        /* 1: the centre's variance is the 3x3 blur above; 0: its own */
+    float sigma_position;     /* as rt_denoise_params; 0 = off */
+    float sigma_variance;     /* luminance distance in standard errors of the centre's mean; 0 = no variance term */
+} rt_denoise_var_params;
+int rt_denoise_adaptive(void* fb_out, const void* fb_in, int max_x, int max_y, const rt_hit_record* d_hits, const void* d_state,
+                        const rt_denoise_var_params* params, void* d_work, void* stream);
+int rt_denoise_adaptive_check(int max_x, int max_y, const rt_denoise_var_params* params);
+
 /* ---- host side: output --------------------------------------------------------------------------------------- */
 /* output_to_stream — main.cu:321-333: ASCII P3, top row first, int(255.99*c).  fb is a HOST buffer.
  * path == NULL writes to stdout (output mode 0), otherwise to the file (output mode 3 uses "output.ppm"). */

@@ -14,7 +14,8 @@ cd $root
 /opt/rocm/bin/hipcc $F -c -o $obj/a.o csrc/rt_api.hip &
 /opt/rocm/bin/hipcc $F -c -o $obj/m.o csrc/rt_multi.hip &
 /opt/rocm/bin/hipcc $F -c -o $obj/b.o csrc/rt_build.hip &
+/opt/rocm/bin/hipcc $F -c -o $obj/d.o csrc/rt_denoise.hip &
 wait
-/opt/rocm/bin/hipcc --offload-arch=gfx950 -shared -fPIC -o variants/lib_$name.so $obj/k.o $obj/l.o $obj/c.o $obj/h.o $obj/a.o $obj/m.o $obj/b.o -ldl
+/opt/rocm/bin/hipcc --offload-arch=gfx950 -shared -fPIC -o variants/lib_$name.so $obj/k.o $obj/l.o $obj/c.o $obj/h.o $obj/a.o $obj/m.o $obj/b.o $obj/d.o -ldl
 rm -rf $obj
 echo "built variants/lib_$name.so"
