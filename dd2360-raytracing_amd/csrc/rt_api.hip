@@ -50,6 +50,12 @@ hipError_t launch_adapt_refine_seed(float* fb, const AdaptState& s, long long n_
 hipError_t launch_adapt_refine_check(float* fb, const AdaptState& s, const unsigned int* list_in, const unsigned int* count_in, long long n_all,
                                      unsigned int* list_out, unsigned int* count_out, int32_t* spp, int batch, int max_spp, float rel_error, float floor_lum,
                                      hipStream_t st);
+size_t budget_ws_bytes(long long n);                                   // rt_budget.hip
+hipError_t launch_budget_select(const AdaptState& s, long long n, const AdaptFrame& fr, int batch, int max_spp, float floor_lum, unsigned int K,
+                                unsigned int* keys, unsigned int* ws, unsigned int* list, unsigned int* count, hipStream_t st);
+hipError_t launch_budget_seed(float* fb, const AdaptState& s, const unsigned int* list, const unsigned int* count, unsigned int cap, hipStream_t st);
+hipError_t launch_budget_final(float* fb, const AdaptState& s, const unsigned int* list, const unsigned int* count, unsigned int cap, int32_t* spp, int batch,
+                               uint32_t* picked, hipStream_t st);
 const char* render_kernel_name(bool tree, int mode, const DevAccel& acc);
 namespace gpubuild { int build(rt_octree* O, const float4* d_geom, const int32_t* d_kind, int n, int spl, hipStream_t st); }
 const char* render_kernel_name_h(bool tree, int mode);
@@ -347,10 +353,23 @@ static int ctx_reserve_adaptive(rt_render_ctx& C, int64_t pixels, int rounds) {
     }
     return 0;
 }
+// ... and of the budget selection for states of up to `pixels` elements (rt_budget.hip)
+static int ctx_reserve_budget(rt_render_ctx& C, int64_t pixels) {
+    const size_t bytes = budget_ws_bytes(pixels);
+    if (C.b_bytes >= bytes) return 0;
+    void* old[1] = {C.b_ws};
+    C.b_ws = nullptr; C.b_bytes = 0;
+    int rc = free_all(old, 1);
+    if (rc) return rc;
+    void* q = nullptr;
+    RT_TRY(hipMalloc(&q, bytes));
+    C.b_ws = (unsigned int*)q; C.b_bytes = bytes;
+    return 0;
+}
 static int ctx_release(rt_render_ctx& C) {
-    void* abufs[4] = {C.a_sl, C.a_q, C.a_list, C.a_count};
-    const int arc = free_all(abufs, 4);
-    C.a_sl = nullptr; C.a_q = nullptr; C.a_list = nullptr; C.a_count = nullptr; C.a_pixels = 0; C.a_rounds = 0;
+    void* abufs[5] = {C.a_sl, C.a_q, C.a_list, C.a_count, C.b_ws};
+    const int arc = free_all(abufs, 5);
+    C.a_sl = nullptr; C.a_q = nullptr; C.a_list = nullptr; C.a_count = nullptr; C.a_pixels = 0; C.a_rounds = 0; C.b_ws = nullptr; C.b_bytes = 0;
     void* bufs[8] = {C.d_queue, C.d_cost, C.d_order, C.d_flags, C.d_long, C.p_cost, C.p_order, C.d_work};
     const int brc = free_all(bufs, 8);
     const int rc = brc ? brc : arc;
@@ -1108,6 +1127,103 @@ int rt_render_adaptive_refine_on(rt_render_ctx* ctx, void* fb, int max_x, int ma
                                  rt_rand_state* d_rand_state, const rt_octree* d_octree, int32_t* d_spp, void* d_state, rt_partition part, void* stream) {
     if (!ctx) return RT_EINVAL;
     return render_adaptive_refine_common(ctx, fb, max_x, max_y, from, to, world, d_rand_state, d_octree, d_spp, d_state, part, stream);
+}
+
+// ---- adaptive sample budgets (DESIGN.md §5.9 "Budgets") ----------------------------------------------------------------
+float rt_adaptive_priority(float SL, float Q, int k, float floor) { return adapt_priority(SL, Q, k, floor); }
+// q = samples / batch picks, dealt over the rounds: K_r = q (r + 1) / rounds - q r / rounds
+static bool budget_params_ok(const rt_budget* P) {
+    if (!P || P->samples < 0 || P->rounds < 1 || P->batch < 1) return false;
+    if (!(P->floor >= 0.f) || !std::isfinite(P->floor)) return false;
+    const int64_t q = P->samples / P->batch;
+    if (q > std::numeric_limits<int64_t>::max() / P->rounds) return false;                  // q * rounds, the largest product
+    return q / P->rounds + (q % P->rounds != 0) <= (int64_t)0xffffffffll;                  // the largest K_r
+}
+static int64_t budget_picks(const rt_budget* P, int r) {
+    const int64_t q = P->samples / P->batch;
+    return q * (r + 1) / P->rounds - q * r / P->rounds;
+}
+int rt_adaptive_budget_check(const rt_budget* params) { return budget_params_ok(params) ? 0 : RT_EINVAL; }
+int rt_adaptive_budget_picks(const rt_budget* params, int round, int64_t* picks) {
+    if (!budget_params_ok(params) || !picks || round < 0 || round >= params->rounds) return RT_EINVAL;
+    *picks = budget_picks(params, round);
+    return 0;
+}
+// The selection alone.  The key bits go to the second half of the context's lists, the caller's list receives the ids.
+int rt_adaptive_budget_select(rt_render_ctx* ctx, const void* d_state, int max_x, int max_y, rt_partition part, const rt_budget* params,
+                              int64_t picks, uint32_t* d_list, uint32_t* d_count, void* stream) {
+    if (!ctx || !budget_params_ok(params) || picks < 0 || picks > (int64_t)0xffffffffll || max_x <= 0 || max_y <= 0 || !valid_partition(part)) return RT_EINVAL;
+    const int64_t npx = rt_part_pixels(max_x, max_y, part);
+    if (npx < 0 || npx > (int64_t)0xffffffffll) return RT_EINVAL;
+    if (npx == 0) return 0;
+    if (!d_state || !d_list || !d_count) return RT_EINVAL;
+    const hipStream_t st = (hipStream_t)stream;
+    if (capturing(st)) return RT_EINVAL;
+    rt_render_ctx& C = *ctx;
+    int rc = ctx_prepare(C);
+    if (!rc) rc = ctx_reserve_adaptive(C, npx, 1);
+    if (!rc) rc = ctx_reserve_budget(C, npx);
+    if (rc) return rc;
+    if (C.has_done && C.last_stream != st) RT_TRY(hipStreamWaitEvent(st, C.done, 0));
+    const AdaptFrame fr = {max_x, max_y, (max_x + 7) / 8, part.part, part.nparts, part.tile_begin, part.tile_end};
+    RT_TRY(launch_budget_select(adapt_state(const_cast<void*>(d_state), npx), npx, fr, params->batch, params->max_spp, params->floor,
+                                (unsigned int)std::min(picks, npx), C.a_list + npx, C.b_ws, d_list, d_count, st));
+    RT_TRY(hipEventRecord(C.done, st));
+    C.has_done = true; C.last_stream = st;
+    return 0;
+}
+// rt_render_adaptive_spend: `rounds` times — select K_r pixels, seed fb with their sums, `batch` samples for each through the resumed
+// k_render<*, 2, *>, finalise them.  Every round ends with every pixel finalised, so R rounds are R calls of one round.
+static int render_adaptive_spend_common(rt_render_ctx* ctx, void* fb, int max_x, int max_y, const rt_budget* P, const rt_world* world,
+                                        rt_rand_state* d_rand_state, const rt_octree* d_octree, int32_t* d_spp, void* d_state, rt_partition part,
+                                        uint32_t* d_picked, void* stream) {
+    if (!budget_params_ok(P) || !world || max_x <= 0 || max_y <= 0 || !valid_partition(part)) return RT_EINVAL;
+    const int64_t npx = rt_part_pixels(max_x, max_y, part);
+    if (npx < 0 || npx > (int64_t)0xffffffffll) return RT_EINVAL;
+    if (npx == 0) return 0;
+    if (!fb || !d_rand_state || !d_state) return RT_EINVAL;
+    if (d_octree && d_octree->precision != world->precision) return RT_EINVAL;
+    if (world->precision == RT_PRECISION_FP16 || world->arith == RT_ARITH_CONTRACT) return RT_ENOTSUP;
+    const hipStream_t st = (hipStream_t)stream;
+    if (capturing(st)) return RT_EINVAL;
+    int rc = ensure_on_device(world, d_octree);
+    rt_render_ctx& C = ctx ? *ctx : world->z->ctx;
+    if (!rc) rc = ctx_prepare(C);
+    if (rc) return rc;
+    const AdaptState S = adapt_state(d_state, npx);
+    RenderArgs A = frame_args(fb, max_x, max_y, P->batch, world, d_rand_state, d_octree, part);
+    const AdaptFrame fr = {max_x, max_y, A.tiles_x, part.part, part.nparts, part.tile_begin, part.tile_end};
+    if ((rc = ctx_reserve_adaptive(C, npx, 1)) || (rc = ctx_reserve_budget(C, npx))) return rc;
+    if (C.has_done && C.last_stream != st) RT_TRY(hipStreamWaitEvent(st, C.done, 0));
+    const bool tree = d_octree != nullptr;
+    A.ad_sl = S.sl; A.ad_q = S.q; A.ad_list = C.a_list; A.ad_count = C.a_count;      // (one count serves every round: the stream orders them)
+    const unsigned ek = C.ev_head % 64u;
+    RT_TRY(hipEventRecord(C.ev0[ek], st));
+    for (int r = 0; r < P->rounds; ++r) {
+        const unsigned int K = (unsigned int)std::min(budget_picks(P, r), npx);
+        RT_TRY(launch_budget_select(S, npx, fr, P->batch, P->max_spp, P->floor, K, C.a_list + npx, C.b_ws, C.a_list, C.a_count, st));
+        RT_TRY(launch_budget_seed((float*)fb, S, A.ad_list, A.ad_count, K, st));
+        A.queue = C.d_queue + (size_t)(C.launches++ % kQueueSlots) * kQueueStride;
+        RT_TRY(launch_zero_counters(A.queue, (int)kQueueStride, st));
+        RT_TRY(launch_render_adaptive(A, tree, st));
+        RT_TRY(launch_budget_final((float*)fb, S, A.ad_list, A.ad_count, K, d_spp, P->batch, d_picked ? d_picked + r : nullptr, st));
+    }
+    C.last_queue = A.queue;
+    RT_TRY(hipEventRecord(C.ev1[ek], st));
+    C.ev_head++; if (C.ev_count < 64) C.ev_count++;
+    RT_TRY(hipEventRecord(C.done, st));
+    C.has_done = true; C.last_stream = st;
+    return 0;
+}
+int rt_render_adaptive_spend(void* fb, int max_x, int max_y, const rt_budget* params, const rt_world* world, rt_rand_state* d_rand_state,
+                             const rt_octree* d_octree, int32_t* d_spp, void* d_state, rt_partition part, uint32_t* d_picked, void* stream) {
+    return render_adaptive_spend_common(nullptr, fb, max_x, max_y, params, world, d_rand_state, d_octree, d_spp, d_state, part, d_picked, stream);
+}
+int rt_render_adaptive_spend_on(rt_render_ctx* ctx, void* fb, int max_x, int max_y, const rt_budget* params, const rt_world* world,
+                                rt_rand_state* d_rand_state, const rt_octree* d_octree, int32_t* d_spp, void* d_state, rt_partition part,
+                                uint32_t* d_picked, void* stream) {
+    if (!ctx) return RT_EINVAL;
+    return render_adaptive_spend_common(ctx, fb, max_x, max_y, params, world, d_rand_state, d_octree, d_spp, d_state, part, d_picked, stream);
 }
 
 // the kernel rt_render (mode 0) / rt_render_progressive (mode 1) launches for this world and tree — the library's own

@@ -55,6 +55,18 @@ __host__ __device__ inline AdaptState adapt_state(void* base, long long n) {
     float* f = (float*)base;
     return AdaptState{f, f + 3 * n, f + 4 * n, (int32_t*)(f + 5 * n)};
 }
+// rt_adaptive_priority (rt_amd.h): the squared relative standard error of a pixel's mean luminance, the mean floored at floor_lum —
+// what adapt_rule compares with rel_error^2, divided out.  IEEE binary32, one rounding per operation (its callers, rt_budget.hip and rt_api.hip,
+// are compiled with -ffp-contract=off).  Never negative and never NaN, so its bits read as uint32 order it.
+__host__ __device__ inline float adapt_priority(float SL, float Q, int k, float floor_lum) {
+    const float n = (float)k;
+    float d = n * Q - SL * SL;
+    d = d > 0.f ? d : 0.f;                                  // (a NaN d becomes 0)
+    const float nf = n * floor_lum;
+    const float m = SL > nf ? SL : nf;
+    const float e = d / ((n - 1.f) * (m * m));
+    return e > 0.f ? e : 0.f;                               // NaN (0/0, a NaN sum) becomes 0; +inf stays
+}
 constexpr int kMaxSplitParts = 64;
 struct SplitStarts { long long s[kMaxSplitParts + 1]; };      // first tile of every band of a balanced split, and the tile count (k_assemble_split)
 

@@ -31,6 +31,9 @@ struct rt_render_ctx {
     // rt_render_adaptive: per pixel the luminance sum and sum of squares between rounds, the two lists of active pixels (ping-pong),
     // and one active-pixel count per round; grown on demand
     float* a_sl = nullptr; float* a_q = nullptr; unsigned int* a_list = nullptr; int64_t a_pixels = 0; unsigned int* a_count = nullptr; int a_rounds = 0;
+    // rt_adaptive_budget_select / rt_render_adaptive_spend: the selection's histograms, threshold and per-block tie counts (the key bits
+    // live in the second half of a_list, which is free outside a render round); grown on demand
+    unsigned int* b_ws = nullptr; size_t b_bytes = 0;
     // HIP events around the dominant kernel of each render call (ring of the last 64), see rt_render_ctx_times
     hipEvent_t ev0[64] = {}, ev1[64] = {}; unsigned ev_head = 0, ev_count = 0; bool ev_ready = false;
     // ordering of successive launches that share this context

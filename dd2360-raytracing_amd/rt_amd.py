@@ -53,6 +53,12 @@ class Adaptive(C.Structure):
 ADAPTIVE_STATE_BYTES = 24      # rt_amd.h RT_ADAPTIVE_STATE_BYTES: the refinement state per buffer element (S_rgb, SL, Q, k)
 
 
+class Budget(C.Structure):
+    """rt_budget: `samples` to spend in `rounds` selections; a chosen pixel takes `batch` samples a round and is eligible while
+    k + batch <= max_spp; floor as Adaptive.floor (include/rt_amd.h states the priority and the selection rule)"""
+    _fields_ = [("samples", C.c_int64), ("rounds", C.c_int32), ("batch", C.c_int32), ("max_spp", C.c_int32), ("floor", C.c_float)]
+
+
 class DenoiseParams(C.Structure):
     """rt_denoise_params: input mode (DENOISE_INPUT_*), the progressive sample count (SUM), levels (step 2^L at level L), the normal
     exponent's log2 (-1 = off) and the position / colour sigmas (0 = off); include/rt_amd.h states the exact filter"""
@@ -135,6 +141,12 @@ SYMBOLS = {
     "rt_render_adaptive_begin_on": (_i, [_vp, _vp, _i, _i, C.POINTER(Adaptive), _vp, _vp, _vp, _vp, _vp, Partition, _vp]),
     "rt_render_adaptive_refine": (_i, [_vp, _i, _i, C.POINTER(Adaptive), C.POINTER(Adaptive), _vp, _vp, _vp, _vp, _vp, Partition, _vp]),
     "rt_render_adaptive_refine_on": (_i, [_vp, _vp, _i, _i, C.POINTER(Adaptive), C.POINTER(Adaptive), _vp, _vp, _vp, _vp, _vp, Partition, _vp]),
+    "rt_adaptive_priority": (_f, [_f, _f, _i, _f]),
+    "rt_adaptive_budget_check": (_i, [C.POINTER(Budget)]),
+    "rt_adaptive_budget_picks": (_i, [C.POINTER(Budget), _i, _vp]),
+    "rt_adaptive_budget_select": (_i, [_vp, _vp, _i, _i, Partition, C.POINTER(Budget), _i64, _vp, _vp, _vp]),
+    "rt_render_adaptive_spend": (_i, [_vp, _i, _i, C.POINTER(Budget), _vp, _vp, _vp, _vp, _vp, Partition, _vp, _vp]),
+    "rt_render_adaptive_spend_on": (_i, [_vp, _vp, _i, _i, C.POINTER(Budget), _vp, _vp, _vp, _vp, _vp, Partition, _vp, _vp]),
     "rt_render_ctx_times": (_i, [_vp, _vp, _i, _vp]),
     "rt_render_ctx_counters": (_i, [_vp, _vp]),
     "rt_world_render_counters": (_i, [_vp, _vp]),
@@ -263,6 +275,19 @@ class RenderCtx:
         check(lib().rt_render_adaptive_refine_on(self.h, _dev(fb), max_x, max_y, C.byref(frm), C.byref(to), world.h, _dev(d_rand_state),
                                                  octree.h if octree is not None else None, _dev(d_spp) if d_spp is not None else None, _dev(d_state),
                                                  part or WHOLE, C.c_void_p(stream) if stream is not None else _stream()), "rt_render_adaptive_refine_on")
+
+    def render_adaptive_spend(self, fb, max_x, max_y, params, world, d_rand_state, d_state, octree=None, d_spp=None, part=None, d_picked=None,
+                              stream=None):
+        """rt_render_adaptive_spend_on: spend the Budget `params` on the frame that d_state holds; d_picked (optional): uint32 per round"""
+        check(lib().rt_render_adaptive_spend_on(self.h, _dev(fb), max_x, max_y, C.byref(params), world.h, _dev(d_rand_state),
+                                                octree.h if octree is not None else None, _dev(d_spp) if d_spp is not None else None, _dev(d_state),
+                                                part or WHOLE, _dev(d_picked) if d_picked is not None else None,
+                                                C.c_void_p(stream) if stream is not None else _stream()), "rt_render_adaptive_spend_on")
+
+    def adaptive_budget_select(self, d_state, max_x, max_y, params, picks, d_list, d_count, part=None, stream=None):
+        """rt_adaptive_budget_select: the ids of the `picks` pixels a round would choose into d_list (uint32), their number into d_count"""
+        check(lib().rt_adaptive_budget_select(self.h, _dev(d_state), max_x, max_y, part or WHOLE, C.byref(params), picks, _dev(d_list), _dev(d_count),
+                                              C.c_void_p(stream) if stream is not None else _stream()), "rt_adaptive_budget_select")
 
     def times(self):
         out = np.zeros(64, np.float32)
@@ -618,6 +643,36 @@ def render_adaptive_refine(fb, max_x, max_y, frm, to, world, d_rand_state, d_sta
     check(lib().rt_render_adaptive_refine(_dev(fb), max_x, max_y, C.byref(frm), C.byref(to), world.h, _dev(d_rand_state),
                                           octree.h if octree is not None else None, _dev(d_spp) if d_spp is not None else None, _dev(d_state),
                                           part, _stream()), "rt_render_adaptive_refine")
+
+
+def adaptive_priority(SL, Q, k, floor):
+    """rt_adaptive_priority: the key a budget ranks a pixel by (host, binary32)"""
+    return np.float32(lib().rt_adaptive_priority(float(np.float32(SL)), float(np.float32(Q)), int(k), float(np.float32(floor))))
+
+
+def adaptive_budget_check(params):
+    """rt_adaptive_budget_check: True when the Budget is accepted (host only)"""
+    return lib().rt_adaptive_budget_check(C.byref(params)) == 0
+
+
+def adaptive_budget_picks(params, round):
+    """rt_adaptive_budget_picks: K_r, the picks of round `round`"""
+    k = C.c_int64(0)
+    check(lib().rt_adaptive_budget_picks(C.byref(params), round, C.byref(k)), "rt_adaptive_budget_picks")
+    return k.value
+
+
+def adaptive_budget_select(ctx, d_state, max_x, max_y, params, picks, d_list, d_count, part=WHOLE):
+    """rt_adaptive_budget_select on the current stream, with the workspace of the RenderCtx `ctx`"""
+    ctx.adaptive_budget_select(d_state, max_x, max_y, params, picks, d_list, d_count, part)
+
+
+def render_adaptive_spend(fb, max_x, max_y, params, world, d_rand_state, d_state, octree=None, d_spp=None, part=WHOLE, d_picked=None):
+    """rt_render_adaptive_spend on the current stream: spend the Budget `params` on the frame that d_state holds (render_adaptive_begin,
+    _refine or an earlier spend left it); d_picked (optional): one uint32 per round, the round's pick count"""
+    check(lib().rt_render_adaptive_spend(_dev(fb), max_x, max_y, C.byref(params), world.h, _dev(d_rand_state), octree.h if octree is not None else None,
+                                         _dev(d_spp) if d_spp is not None else None, _dev(d_state), part,
+                                         _dev(d_picked) if d_picked is not None else None, _stream()), "rt_render_adaptive_spend")
 
 
 def assemble(fb_full, fb_parts, max_x, max_y, nparts, precision=FP32):

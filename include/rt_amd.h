@@ -293,6 +293,58 @@ int rt_render_adaptive_refine_on(rt_render_ctx* ctx, void* fb, int max_x, int ma
                                  const rt_world* world, rt_rand_state* d_rand_state, const rt_octree* d_octree, int32_t* d_spp, void* d_state,
                                  rt_partition part, void* stream);
 
+/* Budgets: the opposite contract to a noise target — "this many samples, put them where the frame is noisiest" (no reference
+ * counterpart).  A spend continues the state of rt_render_adaptive_begin: it ranks the pixels by their priority and gives the first K
+ * of them `batch` samples more, `rounds` times.
+ * The priority of a pixel with sums SL, Q after k samples, IEEE binary32, one rounding per operation, no contraction:
+ *   n = (float)k;  d = n * Q - SL * SL;  d = d > 0 ? d : 0              (a NaN d becomes 0)
+ *   nf = n * floor;  m = SL > nf ? SL : nf
+ *   e = d / ((n - 1) * (m * m));  key = e > 0 ? e : 0                    (NaN, e.g. 0 / 0, becomes 0; +inf stays)
+ * — the squared relative standard error of the mean luminance, the mean floored at `floor`: the quantity the stop rule of rt_adaptive
+ * compares with rel_error^2, divided out.  key is never negative, so its bits read as uint32 order it.  A pixel with a NaN sample has
+ * key 0 and is never picked: a budget does not pour samples into a pixel whose error it cannot estimate.  (This differs from the
+ * threshold rule of rt_render_adaptive, which runs such a pixel to max_spp.) */
+float rt_adaptive_priority(float SL, float Q, int k, float floor);
+typedef struct rt_budget {
+    int64_t samples;   /* what this call may spend in total, >= 0 */
+    int32_t rounds;    /* >= 1: the selection is repeated this many times */
+    int32_t batch;     /* samples a chosen pixel takes in one round, >= 1 */
+    int32_t max_spp;   /* a pixel with k + batch > max_spp is not eligible */
+    float floor;       /* as rt_adaptive.floor: >= 0, finite */
+} rt_budget;
+/* q = samples / batch picks in total; round r = 0 .. rounds-1 gets K_r = q*(r+1)/rounds - q*r/rounds of them (integer divisions in
+ * int64).  rt_adaptive_budget_check: 0, or RT_EINVAL for parameters outside the ranges above, for an overflowing q * rounds and for a
+ * K_r above 2^32 - 1.  rt_adaptive_budget_picks: K_r for `round` into *picks (RT_EINVAL also for a round outside 0 .. rounds-1).
+ * Host only, no device work. */
+int rt_adaptive_budget_check(const rt_budget* params);
+int rt_adaptive_budget_picks(const rt_budget* params, int round, int64_t* picks);
+/* The selection of one round, alone.  An element of the part's buffer is eligible when it lies inside the frame (not the padding of an
+ * edge tile), its k + batch <= max_spp, and its key is greater than 0.  The eligible elements are ordered by key descending and, among
+ * equal keys, by element id ascending; the first min(picks, eligible) are chosen.  A budget is an upper bound: what cannot be placed
+ * is not carried over.  Only the SET is defined: d_list (device, capacity min(picks, rt_part_pixels)) receives the chosen element
+ * ids in no particular order, *d_count (device) their number.  d_state is the state of that frame and part, read only.  Asynchronous
+ * on `stream`, a fixed number of launches, nothing comes back to the host.  `ctx` owns the workspace (key bits, histograms, per-block
+ * tie counts; grown on demand) and must not be NULL.  RT_EINVAL for that, for bad parameters, picks outside 0 .. 2^32 - 1, NULL
+ * buffers, an invalid partition and during a capture; 0 for a part without tiles. */
+int rt_adaptive_budget_select(rt_render_ctx* ctx, const void* d_state, int max_x, int max_y, rt_partition part, const rt_budget* params,
+                              int64_t picks, uint32_t* d_list, uint32_t* d_count, void* stream);
+/* Spend a budget on a frame that rt_render_adaptive_begin, a chain of rt_render_adaptive_refine, or an earlier spend left — same world,
+ * tree, frame, part, d_rand_state and d_state.  For every round r: the selection above with K_r; `batch` more samples for every chosen
+ * pixel, continued from its sums and its RNG state; then k += batch, the new S_rgb in the state, fb = sqrtf(S * (float)(1.0 /
+ * (double)(float)k)) and d_spp = k for each of them.  Every round ends with every pixel finalised, so rounds = R is, bit for bit, R
+ * calls with rounds = 1 and samples = K_r * batch; a pixel at k samples holds what rt_render with ns = k gives it.  d_picked (device,
+ * `rounds` words, may be NULL) receives every round's pick count.  The parameters alone fix the number of launches.
+ * RT_EINVAL for bad parameters, a NULL state, an invalid partition and during a capture; RT_ENOTSUP for USE_FP16 and RT_ARITH_CONTRACT
+ * worlds, after the parameter checks; 0 for a part without tiles.
+ * A part selects among its own elements: a frame spent part by part is not the frame spent whole, and multi-GPU budgets (which need
+ * a histogram exchange) are not provided.  rt_render_adaptive_refine after a spend is not supported: the state is no longer the state
+ * of a threshold.  rt_denoise_adaptive accepts the state as it is. */
+int rt_render_adaptive_spend(void* fb, int max_x, int max_y, const rt_budget* params, const rt_world* world, rt_rand_state* d_rand_state,
+                             const rt_octree* d_octree, int32_t* d_spp, void* d_state, rt_partition part, uint32_t* d_picked, void* stream);
+int rt_render_adaptive_spend_on(rt_render_ctx* ctx, void* fb, int max_x, int max_y, const rt_budget* params, const rt_world* world,
+                                rt_rand_state* d_rand_state, const rt_octree* d_octree, int32_t* d_spp, void* d_state, rt_partition part,
+                                uint32_t* d_picked, void* stream);
+
 /* Name of the kernel rt_render (mode 0) / rt_render_progressive (mode 1) launches for this world and tree (d_octree NULL =
  * the hitable_list path), as rocprofv3 shows it without the namespace: "k_render<true,0,4>", "k_render_h<true,0>", ... */
 int rt_render_kernel_name(const rt_world* world, const rt_octree* d_octree, int mode, char* out, int cap);

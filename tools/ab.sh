@@ -3,10 +3,19 @@
 # "base" = the product library, any other name = dd2360-raytracing_amd/variants/lib_<name>.so (built by hand with -D switches).
 # The variants are timed in ROUNDS interleaved passes (clock / thermal drift hits all alike); prints per variant the
 # median and minimum kernel time and the median step time.  -p also runs the GPU parity suite against the LAST variant.
-cfg=c3; parity=0; rounds=3
-while getopts "c:pr:" o; do case $o in c) cfg=$OPTARG;; p) parity=1;; r) rounds=$OPTARG;; esac; done
+# -s: time the budget selection instead (tools/adaptive_budget_study.py --select, which bench.py never runs): one table per variant,
+# with a checksum of the chosen sets (e.g. tools/ab.sh -s base budget_sort after tools/mkvariant.sh budget_sort -DRT_BUDGET_SORT).
+cfg=c3; parity=0; rounds=3; selection=0
+while getopts "c:pr:s" o; do case $o in c) cfg=$OPTARG;; p) parity=1;; r) rounds=$OPTARG;; s) selection=1;; esac; done
 shift $((OPTIND - 1))
 root=$(cd "$(dirname "$0")/.." && pwd)
+if [ $selection = 1 ]; then
+  for v in "$@"; do
+    if [ "$v" = base ]; then unset RT_AMD_LIB; else export RT_AMD_LIB=$root/dd2360-raytracing_amd/variants/lib_$v.so; fi
+    timeout -k 10 180 python "$root/tools/adaptive_budget_study.py" --select || { echo "$v FAILED"; exit 1; }
+  done
+  exit 0
+fi
 tmp=$(mktemp)
 for ((k = 0; k < rounds; k++)); do
   for v in "$@"; do
