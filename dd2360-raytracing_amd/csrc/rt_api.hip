@@ -64,6 +64,7 @@ hipError_t read_h16_stats(unsigned long long* out, int reset);
 #endif
 #ifdef RT_STATS
 hipError_t read_stats(unsigned long long* out, int reset);
+hipError_t read_wp_classes(unsigned long long* out, int reset);
 hipError_t read_wave_dbg(unsigned long long* out);
 hipError_t read_pilot_dbg(int* out, int n);
 #endif
@@ -412,6 +413,24 @@ static int world_upload(const rt_world* W) {
     std::vector<float4> shade(2 * (size_t)W->n);
     std::vector<uint8_t> kind8((size_t)W->n);
     for (int i = 0; i < W->n; ++i) { shade[2 * (size_t)i] = W->h_geom[i]; shade[2 * (size_t)i + 1] = W->h_mat[i]; kind8[i] = (uint8_t)W->h_kind[i]; }
+    // A binary32 world's dielectric records carry, in the albedo fields the dielectric branch never reads (attenuation (1,1,1), material.h:110),
+    // the three values of that branch that depend on the sphere alone — the same binary32 expressions in the same order, one IEEE rounding per
+    // operation (this file is compiled without contraction), so the kernel reads the bits it used to compute at every glass hit:
+    //   .x = 1.0f / ref_idx                                  ni_over_nt, material.h:98
+    //   .y = r0 * r0, r0 = (1 - ref_idx) / (1 + ref_idx)     schlick(), material.h:12-13
+    //   .z = ref_idx * ref_idx                               material.h:94 (ref_idx * ref_idx * (1 - cosine * cosine), left to right)
+    // A NaN among them (ref_idx infinite or NaN) only ever reaches comparisons or poisons the ray as before.  Binary16 worlds keep the plain
+    // record: k_render_h reads the albedo fields of every kind.  h_mat / DevScene::mat (rt_world_octree's sphere list) are untouched, and
+    // nothing changes a world's materials after rt_world_create, so the table is filled here once.
+    if (W->precision == RT_PRECISION_FP32) {
+        for (int i = 0; i < W->n; ++i) {
+            if (W->h_kind[i] != RT_MAT_DIELECTRIC) continue;
+            const float ri = W->h_mat[i].w;
+            float r0 = (1.0f - ri) / (1.0f + ri);
+            r0 = r0 * r0;
+            shade[2 * (size_t)i + 1] = make_float4(1.0f / ri, r0, ri * ri, ri);
+        }
+    }
     if ((rc = upload(W->h_hot, &Z.d_list_hot)) || (rc = upload(W->h_ids, &Z.d_list_id)) || (rc = upload(W->h_geom, &Z.d_geom)) ||
         (rc = upload(W->h_mat, &Z.d_mat)) || (rc = upload(W->h_kind, &Z.d_kind)) || (rc = upload(shade, &Z.d_shade)) || (rc = upload(kind8, &Z.d_kind8))) {
         void* bufs[7] = {Z.d_list_hot, Z.d_list_id, Z.d_geom, Z.d_mat, Z.d_kind, Z.d_shade, Z.d_kind8};       // nothing half-made stays behind
@@ -1395,6 +1414,7 @@ int rt_debug_h16(unsigned long long* out8, int reset) { return (int)rt::read_h16
 #ifdef RT_STATS
 // diagnostic build only (librt_amd_stats.so): 16 work counters, see rt_kernels.hip
 int rt_debug_stats(unsigned long long* out16, int reset) { return (int)read_stats(out16, reset); }
+int rt_debug_wp_classes(unsigned long long* out96, int reset) { return (int)read_wp_classes(out96, reset); }      // 4 live-lane classes x 24 blocks
 int rt_debug_waves(unsigned long long* out) { return (int)read_wave_dbg(out); }
 int rt_debug_pilot(int* out, int n) { return (int)read_pilot_dbg(out, n); }
 #endif

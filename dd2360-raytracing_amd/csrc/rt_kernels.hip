@@ -21,11 +21,13 @@
 // Numeric contract: every floating-point operation below is one IEEE binary32 operation in the reference's
 // order; FMA contraction is off for the whole file (and on the command line); division and sqrt are the
 // correctly-rounded forms (hipcc default).  Values that are merely hoisted (a = d.d, radius^2) are bitwise the
-// values the reference recomputes.
+// values the reference recomputes.  Two affine maps of the sampling code are explicit fused multiply-adds whose product is exact,
+// so their single rounding gives the two-step form's bits (rt_sampling.h: checked for all 2^32 draws).
 #include <hip/hip_runtime.h>
 #include <float.h>
 #include "rt_device.h"
 #include "rt_tuning.h"
+#include "rt_sampling.h"
 
 // RT_TU_CONTRACT (rt_kernels_contract.hip): the same source once more with FMA contraction ALLOWED — what nvcc's default -fmad=true
 // does to the reference (Makefile:9) — in a namespace of its own, for rt_world_set_arith(RT_ARITH_CONTRACT).  Never the parity mode.
@@ -46,15 +48,13 @@ namespace fmac {
 
 struct Rng { uint32_t d, v0, v1, v2, v3, v4; };
 
-// curand (XORWOW) + curand_uniform: x * 2^-32 + 2^-33, one rounding per operation
+// curand (XORWOW) + curand_uniform: x * 2^-32 + 2^-33 — the product is exact, so one fused rounding gives the reference's bits (rt_sampling.h)
 RT_DEV float rng_uniform(Rng& s) {
     const uint32_t t = s.v0 ^ (s.v0 >> 2);
     s.v0 = s.v1; s.v1 = s.v2; s.v2 = s.v3; s.v3 = s.v4;
     s.v4 = (s.v4 ^ (s.v4 << 4)) ^ (t ^ (t << 1));
     s.d += 362437u;
-    const float x = (float)(s.d + s.v4);
-    const float m = x * 2.3283064e-10f;
-    return m + (2.3283064e-10f / 2.0f);
+    return uniform_from_bits(s.d + s.v4);
 }
 
 RT_DEV void rng_seed(Rng& s, unsigned long long seed) {       // curand_init(seed, 0, 0)
@@ -1008,7 +1008,7 @@ RT_DEV V3 random_in_unit_sphere(Rng& s) {               // material.h:35-41
     do {
         WPASS(WP_REJ_ITER);
         const float x = rng_uniform(s); const float y = rng_uniform(s); const float z = rng_uniform(s);
-        p.x = 2.0f * x - 1.0f; p.y = 2.0f * y - 1.0f; p.z = 2.0f * z - 1.0f;
+        p.x = signed_unit(x); p.y = signed_unit(y); p.z = signed_unit(z);       // 2x - 1, the product exact (rt_sampling.h)
     } while (p.x * p.x + p.y * p.y + p.z * p.z >= 1.0f);
     return p;
 }
@@ -1022,7 +1022,7 @@ RT_DEV RayF primary_ray(const rt_camera& c, int i, int j, int max_x, int max_y, 
     do {
         WPASS(WP_DISK_ITER);
         const float x = rng_uniform(s); const float y = rng_uniform(s);
-        px = 2.0f * x - 1.0f; py = 2.0f * y - 1.0f;
+        px = signed_unit(x); py = signed_unit(y);
     } while (px * px + py * py + 0.0f >= 1.0f);
     const float rdx = c.lens_radius * px, rdy = c.lens_radius * py;
     RayF r;
@@ -1072,9 +1072,10 @@ RT_DEV bool scatter(const DevScene& S, int sphere, float t, RayF& r, V3& att, Rn
         att.x *= m.x; att.y *= m.y; att.z *= m.z;
         return dot3(r.d, n) > 0.0f;
     }
-    // dielectric — material.h:81-113 (attenuation (1,1,1): the multiply is exact and omitted)
+    // dielectric — material.h:81-113 (attenuation (1,1,1): the multiply is exact and omitted).  What depends on the sphere alone comes with
+    // its record, computed once at upload by the same expressions (world_upload, rt_api.hip): 1 / ri, schlick's r0 squared, ri * ri.
     WPASS(WP_SC_DIEL);
-    const float ri = m.w;
+    const float ri = m.w, inv_ri = m.x, r0sq = m.y, ri2 = m.z;
     const float dn = dot3(r.d, n);
     const float k = 2.0f * dn;
     const float rx = r.d.x - k * n.x, ry = r.d.y - k * n.y, rz = r.d.z - k * n.z;            // reflect(dir, normal), dir not normalised
@@ -1082,9 +1083,9 @@ RT_DEV bool scatter(const DevScene& S, int sphere, float t, RayF& r, V3& att, Rn
     if (dn > 0.0f) {
         on.x = -n.x; on.y = -n.y; on.z = -n.z; ni = ri;
         cosine = dn / len;
-        cosine = sqrtf(1.0f - ri * ri * (1.0f - cosine * cosine));
+        cosine = sqrtf(1.0f - ri2 * (1.0f - cosine * cosine));
     } else {
-        on = n; ni = 1.0f / ri;
+        on = n; ni = inv_ri;
         cosine = -dn / len;
     }
     const V3 uv = ud;                                                                         // refract(), material.h:17-31
@@ -1096,8 +1097,7 @@ RT_DEV bool scatter(const DevScene& S, int sphere, float t, RayF& r, V3& att, Rn
         fx = ni * (uv.x - dt * on.x) - sq * on.x;
         fy = ni * (uv.y - dt * on.y) - sq * on.y;
         fz = ni * (uv.z - dt * on.z) - sq * on.z;
-        float r0 = (1.0f - ri) / (1.0f + ri);                                                // schlick(), material.h:11-15
-        r0 = r0 * r0;
+        const float r0 = r0sq;                                                                // schlick(), material.h:11-15
         reflect_prob = r0 + (1.0f - r0) * pow5(1.0f - cosine);
     } else {
         reflect_prob = 1.0f;
@@ -1362,7 +1362,7 @@ __global__ __launch_bounds__(256, RT_RENDER_WAVES) void k_render(RenderArgs A) {
     if (kSolo && lane == 0 && begin_long_pixel(true)) solo = true;
     if (__ballot(live) == 0ull && lane < RT_LONG_PER_WAVE) begin_long_pixel(false);
     if (__ballot(live) != 0ull) { thin = true; __builtin_amdgcn_s_setprio(3); }
-    else if (!kChunked) { slot = take_slot(); begin_pixel(); }
+    // (every other lane takes its first pixel at the top of the loop: ONE inlined copy of the pixel switch, not three)
 
     const unsigned int thin_cap = (unsigned int)(n_waves / RT_THIN_CAP_DEN);
     float closest = FLT_MAX; int best = -1;
@@ -1415,7 +1415,8 @@ __global__ __launch_bounds__(256, RT_RENDER_WAVES) void k_render(RenderArgs A) {
           dbg_t_prev = now; }
         )
         RT_STATS_ONLY(
-        { const int nl = __popcll(__ballot(live)); STAT(st, nl >= 56 ? ST_LIVE_GE56 : nl >= 32 ? ST_LIVE_32 : nl >= 8 ? ST_LIVE_8 : ST_LIVE_LT8, 1); }
+        { const int nl = __popcll(__ballot(live)); STAT(st, nl >= 56 ? ST_LIVE_GE56 : nl >= 32 ? ST_LIVE_32 : nl >= 8 ? ST_LIVE_8 : ST_LIVE_LT8, 1);
+          WPASS_CLASS(nl >= 56 ? 0 : nl >= 32 ? 1 : nl >= 8 ? 2 : 3); }
         )
         const float a = dot3(r.d, r.d);
         if (!TREE) { closest = FLT_MAX; best = -1; }
@@ -1477,7 +1478,7 @@ __global__ __launch_bounds__(256, RT_RENDER_WAVES) void k_render(RenderArgs A) {
                     live = false; is_long = false; is_med = false;
                     if (kSolo && solo && begin_long_pixel(true)) { /* the next of the longest chains, alone again */ }
                     else if (lane < RT_LONG_PER_WAVE && begin_long_pixel(false)) { solo = false; /* next long chain */ }
-                    else if (!thin && !kChunked) { slot = take_slot(); begin_pixel(); }      // (progressive passes refill at the top of the loop)
+                    // (otherwise the lane refills at the top of the loop, before the next traversal: the one copy of take_slot + begin_pixel)
                 }
             }
         }

@@ -27,10 +27,19 @@ struct Stats { unsigned int c[ST_N]; unsigned long long cyc[8]; };
 #else
 #define STAT(st, k, v) ((st).c[k] += (v))
 #endif
+// ... and the same wave passes split by the live-lane class of the main-loop iteration they ran in (0: >= 56 live lanes, 1: 32-55, 2: 8-31,
+// 3: < 8 — the classes of ST_LIVE_*): k_render notes its wave's class in LDS at the top of every iteration (WPASS_CLASS), the blocks read it.
+// (Kernels that never note one — the pilot, k_trace — land in whatever class the word holds: they are a few per cent of a frame's passes.)
+constexpr int kWpBlocks = WP_ENDPIX - WP_GROUND + 1;
+__device__ unsigned long long g_wp_cls[4 * kWpBlocks];
 #ifdef RT_STATS_WPASS      // (the atomics distort every timing of the same run: a build of its own, librt_amd_wpass.so)
-#define WPASS(k) do { const int l_ = (int)(threadIdx.x & 63); if (__builtin_amdgcn_readfirstlane(l_) == l_) atomicAdd(&g_stats[k], 1ull); } while (0)
+__shared__ int s_wp_cls[4];
+#define WPASS(k) do { const int l_ = (int)(threadIdx.x & 63); if (__builtin_amdgcn_readfirstlane(l_) == l_) { atomicAdd(&g_stats[k], 1ull); \
+    atomicAdd(&g_wp_cls[(s_wp_cls[(threadIdx.x >> 6) & 3] & 3) * kWpBlocks + ((k) - WP_GROUND)], 1ull); } } while (0)
+#define WPASS_CLASS(c) do { const int l_ = (int)(threadIdx.x & 63); if (__builtin_amdgcn_readfirstlane(l_) == l_) s_wp_cls[(threadIdx.x >> 6) & 3] = (c); } while (0)
 #else
 #define WPASS(k) ((void)0)
+#define WPASS_CLASS(c) ((void)0)
 #endif
 #define STAT_ARG , Stats& st
 #define STAT_PASS , st
@@ -38,6 +47,12 @@ struct Stats { unsigned int c[ST_N]; unsigned long long cyc[8]; };
 #define RT_STATS_READERS \
 hipError_t read_pilot_dbg(int* out, int n) { return hipMemcpyFromSymbol(out, HIP_SYMBOL(g_pilot_dbg), sizeof(int) * (size_t)(n < (1 << 20) ? n : (1 << 20))); } \
 hipError_t read_wave_dbg(unsigned long long* out) { return hipMemcpyFromSymbol(out, HIP_SYMBOL(g_wave_dbg), sizeof(unsigned long long) * 8192 * 4); } \
+hipError_t read_wp_classes(unsigned long long* out, int reset) { \
+    hipError_t e = hipMemcpyFromSymbol(out, HIP_SYMBOL(g_wp_cls), sizeof(unsigned long long) * 4 * kWpBlocks); \
+    if (e != hipSuccess) return e; \
+    if (reset) { unsigned long long z[4 * kWpBlocks] = {0}; e = hipMemcpyToSymbol(HIP_SYMBOL(g_wp_cls), z, sizeof(z)); } \
+    return e; \
+} \
 hipError_t read_stats(unsigned long long* out, int reset) { \
     hipError_t e = hipMemcpyFromSymbol(out, HIP_SYMBOL(g_stats), sizeof(unsigned long long) * ST_N); \
     if (e != hipSuccess) return e; \
@@ -47,6 +62,7 @@ hipError_t read_stats(unsigned long long* out, int reset) { \
 #else
 #define STAT(st, k, v) ((void)0)
 #define WPASS(k) ((void)0)
+#define WPASS_CLASS(c) ((void)0)
 #define STAT_ARG
 #define STAT_PASS
 #define RT_STATS_ONLY(...)

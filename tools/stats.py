@@ -94,3 +94,13 @@ li = max(1, v["loop_iters_wave"])
 print("wave passes per main-loop iteration (a block executed by >= 1 lane of the wave):")
 for k, name in enumerate(wp):
     print("  %-14s %8.3f" % (name, raw[35 + k] / li))
+if hasattr(L, "rt_debug_wp_classes"):
+    # the same passes by the live-lane class of the iteration they ran in, per iteration OF THAT CLASS (wave-pass build only: zeros otherwise)
+    cb = (C.c_ulonglong * (4 * len(wp)))()
+    L.rt_debug_wp_classes.restype = C.c_int; L.rt_debug_wp_classes.argtypes = [C.c_void_p, C.c_int]
+    L.rt_debug_wp_classes(cb, 1)
+    cls = ("live_ge56", "live_32_55", "live_8_31", "live_lt8")
+    print("wave passes per iteration of each live-lane class (iterations: %s):" % "  ".join("%s %d" % (c, v[c]) for c in cls))
+    print("  %-14s %10s %10s %10s %10s" % ("", ">=56", "32-55", "8-31", "<8"))
+    for k, name in enumerate(wp):
+        print("  %-14s %10.3f %10.3f %10.3f %10.3f" % (name, *[cb[c * len(wp) + k] / max(1, v[cls[c]]) for c in range(4)]))
