@@ -97,6 +97,35 @@ def denoise_var_params(**kw):
     p.update(kw)
     return DenoiseVarParams(p["levels"], p["normal_pow_log2"], p["prefilter"], p["sigma_position"], p["sigma_variance"])
 
+
+class LevelsParams(C.Structure):
+    """rt_levels_params: input mode (DENOISE_INPUT_*), the progressive sample count (SUM), the output format (LEVELS_*) and top_first
+    (1 = the PPM's row order, 0 = the framebuffer's); include/rt_amd.h states the quantisation"""
+    _fields_ = [("input", C.c_int32), ("samples", C.c_int32), ("format", C.c_int32), ("top_first", C.c_int32)]
+
+LEVELS_RGB8, LEVELS_RGBA8, LEVELS_GRAY8 = 0, 1, 2      # rt_amd.h RT_LEVELS_*
+
+
+class FrameMetrics(C.Structure):
+    """rt_frame_metrics: the 64-byte record frame_compare leaves; psnr and ssim are the notebook's grey metrics (evaluations.ipynb
+    :1021-1027), rmse the float error over the finite pixels — each through the library's host function"""
+    _fields_ = [("pixels", C.c_int64), ("gray_sse", C.c_int64), ("gray_differ", C.c_int64), ("windows", C.c_int64), ("ssim_sum", C.c_double),
+                ("finite_pixels", C.c_int64), ("sq_err", C.c_double), ("reserved", C.c_int64)]
+
+    @property
+    def psnr(self):
+        return lib().rt_frame_psnr(C.byref(self))
+
+    @property
+    def ssim(self):
+        return lib().rt_frame_ssim(C.byref(self))
+
+    @property
+    def rmse(self):
+        return lib().rt_frame_rmse(C.byref(self))
+
+assert C.sizeof(FrameMetrics) == 64 and C.sizeof(LevelsParams) == 16
+
 # every symbol include/rt_amd.h declares: (restype, argtypes)
 _vp, _i, _i64, _f = C.c_void_p, C.c_int, C.c_int64, C.c_float
 SYMBOLS = {
@@ -174,6 +203,14 @@ SYMBOLS = {
     "rt_denoise_check": (_i, [_i, _i, C.POINTER(DenoiseParams)]),
     "rt_denoise_adaptive": (_i, [_vp, _vp, _i, _i, _vp, _vp, C.POINTER(DenoiseVarParams), _vp, _vp]),
     "rt_denoise_adaptive_check": (_i, [_i, _i, C.POINTER(DenoiseVarParams)]),
+    "rt_frame_levels": (_i, [_vp, _vp, _i, _i, _i, C.POINTER(LevelsParams), _vp]),
+    "rt_frame_levels_check": (_i, [_i, _i, _i, C.POINTER(LevelsParams)]),
+    "rt_frame_levels_bytes": (_i64, [_i, _i, _i]),
+    "rt_frame_compare_work_bytes": (_i64, [_i, _i]),
+    "rt_frame_compare": (_i, [_vp, _i, _vp, _i, _i, _i, _vp, _vp, _vp, _vp]),
+    "rt_frame_psnr": (C.c_double, [C.POINTER(FrameMetrics)]),
+    "rt_frame_ssim": (C.c_double, [C.POINTER(FrameMetrics)]),
+    "rt_frame_rmse": (C.c_double, [C.POINTER(FrameMetrics)]),
     "rt_write_ppm": (_i, [C.c_char_p, _i, _i, _vp, _i]),
     "rt_format_ppm": (_i64, [_i, _i, _vp, _i, _vp, _i64]),
     "rt_write_image": (_i, [C.c_char_p, _i, _i, _vp, _i, _i]),
@@ -720,6 +757,48 @@ def denoise_adaptive(fb_out, fb_in, max_x, max_y, d_hits, d_state, params, d_wor
     of the same call, params a DenoiseVarParams (denoise_var_params()); fb_out may be fb_in"""
     check(lib().rt_denoise_adaptive(_dev(fb_out), _dev(fb_in), max_x, max_y, _dev(d_hits), _dev(d_state), C.byref(params), _dev(d_work),
                                     _stream()), "rt_denoise_adaptive")
+
+
+def frame_levels_bytes(max_x, max_y, fmt=LEVELS_RGB8):
+    """rt_frame_levels_bytes: the size of frame_levels' output"""
+    n = lib().rt_frame_levels_bytes(max_x, max_y, fmt)
+    if n < 0:
+        raise RtError("rt_frame_levels_bytes: invalid argument")
+    return n
+
+
+def frame_levels(d_out, fb, max_x, max_y, params, precision=FP32):
+    """rt_frame_levels on the current stream: the frame as 8-bit levels into d_out (a uint8 tensor of frame_levels_bytes), params a
+    LevelsParams"""
+    check(lib().rt_frame_levels(_dev(d_out), _dev(fb), max_x, max_y, precision, C.byref(params), _stream()), "rt_frame_levels")
+
+
+def alloc_compare_work(max_x, max_y, device="cuda"):
+    """the workspace of frame_compare: rt_frame_compare_work_bytes bytes (one partial record per block)"""
+    import torch
+    n = lib().rt_frame_compare_work_bytes(max_x, max_y)
+    if n < 0:
+        raise RtError("rt_frame_compare_work_bytes: invalid argument")
+    return torch.empty(n // 8, dtype=torch.float64, device=device)
+
+
+def frame_metrics(d_metrics):
+    """the FrameMetrics a frame_compare with d_metrics left on the device (synchronises: a 64-byte copy)"""
+    return FrameMetrics.from_buffer_copy(d_metrics.cpu().numpy().tobytes())
+
+
+def frame_compare(fb_a, fb_b, max_x, max_y, d_work, precision_a=FP32, precision_b=FP32, d_ssim_map=None, d_metrics=None):
+    """rt_frame_compare on the current stream: two gamma frames, each with its own precision; d_work from alloc_compare_work, d_ssim_map
+    (optional) a float64 tensor of (max_y-6) * (max_x-6).  Returns the record as a FrameMetrics (.psnr, .ssim, .rmse) after copying its
+    64 bytes back; with d_metrics (a 64-byte device tensor, 8-byte aligned) the call only enqueues, for a capture, and returns None:
+    read it with frame_metrics(d_metrics)"""
+    import torch
+    own = d_metrics is None
+    if own:
+        d_metrics = torch.empty(8, dtype=torch.int64, device=fb_a.device)
+    check(lib().rt_frame_compare(_dev(fb_a), precision_a, _dev(fb_b), precision_b, max_x, max_y, _dev(d_metrics),
+                                 _dev(d_ssim_map) if d_ssim_map is not None else None, _dev(d_work), _stream()), "rt_frame_compare")
+    return frame_metrics(d_metrics) if own else None
 
 
 def write_image(path, fb_host, nx, ny, precision=FP32, fmt=IMAGE_P6):

@@ -566,6 +566,74 @@ int rt_denoise_adaptive(void* fb_out, const void* fb_in, int max_x, int max_y, c
                         const rt_denoise_var_params* params, void* d_work, void* stream);
 int rt_denoise_adaptive_check(int max_x, int max_y, const rt_denoise_var_params* params);
 
+/* ---- the image end on the device: 8-bit levels and frame comparison (no reference counterpart) ------------
+ * What main.cu:321-333 and evaluations.ipynb:1021-1027 do on the host — quantise a frame, grey it, SSIM / PSNR — for frames that stay
+ * on the device.  Frames are in the reference's row-major layout (pixel_index = j*max_x + i, row 0 at the bottom), at most
+ * RT_DENOISE_MAX_PIXELS pixels.  tests/frame_metrics_model.py is the model.
+ *
+ * rt_frame_levels: d_out receives rt_frame_levels_bytes bytes, one pixel after the other in rows of max_x pixels; top_first = 1 puts
+ * the frame's row max_y-1 first (the order of a PPM's pixel bytes), 0 keeps the framebuffer's own row order.  Per channel:
+ *   value c:  GAMMA the framebuffer's value (RT_PRECISION_FP16: the exact binary32 image of the binary16 value);
+ *             SUM (fp32 only) sqrtf(fb / (float)samples), what rt_denoise's pass-through rule and the reference's viewer show.
+ *   level:    v = 255.99 * (double)c, one binary64 multiply; the level is INT32_MIN unless v > -2147483649.0 && v < 2147483648.0, else
+ *             (int)v, truncated; then clamped to 0..255.  This is the library's P6 rule (rt_write_image), stated on every input: NaN,
+ *             +inf, -inf and finite values whose v lies beyond the int range — large positive ones too — all give level 0.
+ *   GRAY8:    (r*4899 + g*9617 + b*1868 + 8192) >> 14 on the three levels (cv2's fixed-point RGB to gray).
+ * One launch, no allocation, no synchronisation: the call can be captured into a hipGraph.  RT_EINVAL for NULL pointers and whatever
+ * rt_frame_levels_check (host only) refuses — a NULL params, non-positive sizes, more than RT_DENOISE_MAX_PIXELS pixels, an unknown
+ * precision, input or format, samples < 1 with SUM, top_first outside 0..1 —, then RT_ENOTSUP for SUM with RT_PRECISION_FP16. */
+#define RT_LEVELS_RGB8  0   /* 3 bytes a pixel */
+#define RT_LEVELS_RGBA8 1   /* 4 bytes, A = 255 */
+#define RT_LEVELS_GRAY8 2   /* 1 byte */
+typedef struct rt_levels_params {
+    int32_t input;      /* RT_DENOISE_INPUT_GAMMA or RT_DENOISE_INPUT_SUM */
+    int32_t samples;    /* SUM: the current_sample of the progressive sequence (>= 1); GAMMA: ignored */
+    int32_t format;     /* RT_LEVELS_* */
+    int32_t top_first;  /* 1: top row first (PPM order); 0: the framebuffer's own row order */
+} rt_levels_params;
+int rt_frame_levels(void* d_out, const void* fb, int max_x, int max_y, int precision, const rt_levels_params* params, void* stream);
+int rt_frame_levels_check(int max_x, int max_y, int precision, const rt_levels_params* params);
+/* host only: the size of d_out, -1 for non-positive sizes, more than RT_DENOISE_MAX_PIXELS pixels or an unknown format */
+int64_t rt_frame_levels_bytes(int max_x, int max_y, int format);
+
+/* rt_frame_compare: two GAMMA frames of one size, each with its own precision (an fp16 frame against an fp32 one is one call), compared
+ * three ways into one 64-byte record in DEVICE memory.  ga, gb are the GRAY8 levels above, computed in the kernel from the float frames.
+ *   grey error:  gray_sse = sum (ga - gb)^2 and gray_differ = the pixels with ga != gb; PSNR is cv2.PSNR's 10 log10(255^2 / MSE).
+ *   SSIM:        skimage's default (uniform 7x7 window, sample covariance, K1 = 0.01, K2 = 0.03, data range 255, borders cropped), exact
+ *                in integers until the last three operations.  For the window whose lowest-index pixel is (i, j), i <= max_x-7,
+ *                j <= max_y-7, with the sums over its 49 pixels Sx, Sy, Sxx, Syy, Sxy, P = Sx*Sy in int64, K = 10000, c1 = 65025,
+ *                c2 = 585225:
+ *                  A1 = K*2*P + 2401*c1                 B1 = K*(Sx*Sx + Sy*Sy) + 2401*c1
+ *                  A2 = K*2*(49*Sxy - P) + 2352*c2      B2 = K*((49*Sxx - Sx*Sx) + (49*Syy - Sy*Sy)) + 2352*c2
+ *                  S  = ((double)A1 * (double)A2) / ((double)B1 * (double)B2)     three binary64 roundings, no contraction
+ *                Every term is below 2^53 (the conversions are exact), B1 and B2 are positive, identical windows give S == 1.0.
+ *                d_ssim_map, when not NULL, receives S of every window: (max_y-6) rows of (max_x-6) doubles, framebuffer row order.
+ *   float error: over the pixels whose six channels are all finite, sq_err = sum over their 3 channels of ((double)a - (double)b)^2.
+ * The integer fields are exact; the two double sums are taken in a fixed order (per block, then over the blocks in index order) without
+ * atomics, so the 64 bytes are the same on every run.  A frame with a side below 7 is valid: windows = 0, ssim_sum = 0, the map is not
+ * written.  d_work: caller-owned, rt_frame_compare_work_bytes bytes (host only; -1 for non-positive sizes and more than
+ * RT_DENOISE_MAX_PIXELS pixels).  Two launches, no allocation, no synchronisation: the call can be captured into a hipGraph.  RT_EINVAL
+ * for a NULL fb_a, fb_b, d_metrics or d_work, non-positive sizes, more than RT_DENOISE_MAX_PIXELS pixels, an unknown precision, and a
+ * d_metrics, d_work or d_ssim_map that is not 8-byte aligned. */
+typedef struct rt_frame_metrics {
+    int64_t pixels;          /* max_x * max_y */
+    int64_t gray_sse;        /* sum over pixels of (ga - gb)^2 */
+    int64_t gray_differ;     /* pixels with ga != gb */
+    int64_t windows;         /* (max_x - 6) * (max_y - 6), or 0 when either side is < 7 */
+    double  ssim_sum;        /* sum of S over all windows */
+    int64_t finite_pixels;   /* pixels whose six channels (a and b) are all finite */
+    double  sq_err;          /* over those pixels and their 3 channels: sum of ((double)a - (double)b)^2 */
+    int64_t reserved;        /* 0 */
+} rt_frame_metrics;
+int64_t rt_frame_compare_work_bytes(int max_x, int max_y);
+int rt_frame_compare(const void* fb_a, int precision_a, const void* fb_b, int precision_b, int max_x, int max_y,
+                     rt_frame_metrics* d_metrics, double* d_ssim_map, void* d_work, void* stream);
+/* host only, on a record copied from the device: gray_sse == 0 ? +inf : 10*log10(65025.0 * pixels / gray_sse);  ssim_sum / windows (NaN
+ * when windows == 0);  sqrt(sq_err / (3.0 * finite_pixels)) (NaN when finite_pixels == 0).  NaN for a NULL record. */
+double rt_frame_psnr(const rt_frame_metrics* m);
+double rt_frame_ssim(const rt_frame_metrics* m);
+double rt_frame_rmse(const rt_frame_metrics* m);
+
 /* ---- host side: output --------------------------------------------------------------------------------------- */
 /* output_to_stream — main.cu:321-333: ASCII P3, top row first, int(255.99*c).  fb is a HOST buffer.
  * path == NULL writes to stdout (output mode 0), otherwise to the file (output mode 3 uses "output.ppm"). */
