@@ -50,7 +50,10 @@ hipError_t launch_adapt_refine_seed(float* fb, const AdaptState& s, long long n_
 hipError_t launch_adapt_refine_check(float* fb, const AdaptState& s, const unsigned int* list_in, const unsigned int* count_in, long long n_all,
                                      unsigned int* list_out, unsigned int* count_out, int32_t* spp, int batch, int max_spp, float rel_error, float floor_lum,
                                      hipStream_t st);
-size_t budget_ws_bytes(long long n);                                   // rt_budget.hip
+size_t budget_ws_bytes(long long n, bool filtered);                    // rt_budget.hip
+hipError_t launch_budget_select_filtered(const AdaptState& s, const rt_hit_record* hits, int max_x, int max_y, const rt_denoise_var_params& P, int batch,
+                                         int max_spp, float floor_lum, unsigned int K, unsigned int* keys, float* keys_out, unsigned int* ws,
+                                         unsigned int* list, unsigned int* count, hipStream_t st);
 hipError_t launch_budget_select(const AdaptState& s, long long n, const AdaptFrame& fr, int batch, int max_spp, float floor_lum, unsigned int K,
                                 unsigned int* keys, unsigned int* ws, unsigned int* list, unsigned int* count, hipStream_t st);
 hipError_t launch_budget_seed(float* fb, const AdaptState& s, const unsigned int* list, const unsigned int* count, unsigned int cap, hipStream_t st);
@@ -355,8 +358,8 @@ static int ctx_reserve_adaptive(rt_render_ctx& C, int64_t pixels, int rounds) {
     return 0;
 }
 // ... and of the budget selection for states of up to `pixels` elements (rt_budget.hip)
-static int ctx_reserve_budget(rt_render_ctx& C, int64_t pixels) {
-    const size_t bytes = budget_ws_bytes(pixels);
+static int ctx_reserve_budget(rt_render_ctx& C, int64_t pixels, bool filtered = false) {
+    const size_t bytes = budget_ws_bytes(pixels, filtered);
     if (C.b_bytes >= bytes) return 0;
     void* old[1] = {C.b_ws};
     C.b_ws = nullptr; C.b_bytes = 0;
@@ -1150,6 +1153,7 @@ int rt_render_adaptive_refine_on(rt_render_ctx* ctx, void* fb, int max_x, int ma
 
 // ---- adaptive sample budgets (DESIGN.md §5.9 "Budgets") ----------------------------------------------------------------
 float rt_adaptive_priority(float SL, float Q, int k, float floor) { return adapt_priority(SL, Q, k, floor); }
+float rt_adaptive_priority_filtered(float l, float v, float floor) { return adapt_priority_filtered(l, v, floor); }
 // q = samples / batch picks, dealt over the rounds: K_r = q (r + 1) / rounds - q r / rounds
 static bool budget_params_ok(const rt_budget* P) {
     if (!P || P->samples < 0 || P->rounds < 1 || P->batch < 1) return false;
@@ -1191,16 +1195,40 @@ int rt_adaptive_budget_select(rt_render_ctx* ctx, const void* d_state, int max_x
     C.has_done = true; C.last_stream = st;
     return 0;
 }
+// The same with the filter-aware key (whole frames only): every refusal comes before the context is looked at.
+int rt_adaptive_budget_select_filtered(rt_render_ctx* ctx, const void* d_state, const rt_hit_record* d_hits, int max_x, int max_y, const rt_budget* params,
+                                       const rt_denoise_var_params* filter, int64_t picks, uint32_t* d_list, uint32_t* d_count, float* d_keys, void* stream) {
+    if (!ctx || !budget_params_ok(params) || picks < 0 || picks > (int64_t)0xffffffffll || max_x <= 0 || max_y <= 0) return RT_EINVAL;
+    if (rt_denoise_adaptive_check(max_x, max_y, filter)) return RT_EINVAL;
+    if (!d_state || !d_list || !d_count || !d_hits || ((uintptr_t)d_hits & 15)) return RT_EINVAL;       // (the guides are read as float4)
+    const int64_t npx = (int64_t)max_x * max_y;
+    const hipStream_t st = (hipStream_t)stream;
+    if (capturing(st)) return RT_EINVAL;
+    rt_render_ctx& C = *ctx;
+    int rc = ctx_prepare(C);
+    if (!rc) rc = ctx_reserve_adaptive(C, npx, 1);
+    if (!rc) rc = ctx_reserve_budget(C, npx, true);
+    if (rc) return rc;
+    if (C.has_done && C.last_stream != st) RT_TRY(hipStreamWaitEvent(st, C.done, 0));
+    RT_TRY(launch_budget_select_filtered(adapt_state(const_cast<void*>(d_state), npx), d_hits, max_x, max_y, *filter, params->batch, params->max_spp,
+                                         params->floor, (unsigned int)std::min(picks, npx), C.a_list + npx, d_keys, C.b_ws, d_list, d_count, st));
+    RT_TRY(hipEventRecord(C.done, st));
+    C.has_done = true; C.last_stream = st;
+    return 0;
+}
 // rt_render_adaptive_spend: `rounds` times — select K_r pixels, seed fb with their sums, `batch` samples for each through the resumed
 // k_render<*, 2, *>, finalise them.  Every round ends with every pixel finalised, so R rounds are R calls of one round.
 static int render_adaptive_spend_common(rt_render_ctx* ctx, void* fb, int max_x, int max_y, const rt_budget* P, const rt_world* world,
                                         rt_rand_state* d_rand_state, const rt_octree* d_octree, int32_t* d_spp, void* d_state, rt_partition part,
-                                        uint32_t* d_picked, void* stream) {
+                                        uint32_t* d_picked, void* stream, bool filtered = false, const rt_denoise_var_params* filter = nullptr,
+                                        const rt_hit_record* d_hits = nullptr) {
     if (!budget_params_ok(P) || !world || max_x <= 0 || max_y <= 0 || !valid_partition(part)) return RT_EINVAL;
+    if (filtered && rt_denoise_adaptive_check(max_x, max_y, filter)) return RT_EINVAL;
     const int64_t npx = rt_part_pixels(max_x, max_y, part);
     if (npx < 0 || npx > (int64_t)0xffffffffll) return RT_EINVAL;
     if (npx == 0) return 0;
     if (!fb || !d_rand_state || !d_state) return RT_EINVAL;
+    if (filtered && (!d_hits || ((uintptr_t)d_hits & 15))) return RT_EINVAL;
     if (d_octree && d_octree->precision != world->precision) return RT_EINVAL;
     if (world->precision == RT_PRECISION_FP16 || world->arith == RT_ARITH_CONTRACT) return RT_ENOTSUP;
     const hipStream_t st = (hipStream_t)stream;
@@ -1212,7 +1240,7 @@ static int render_adaptive_spend_common(rt_render_ctx* ctx, void* fb, int max_x,
     const AdaptState S = adapt_state(d_state, npx);
     RenderArgs A = frame_args(fb, max_x, max_y, P->batch, world, d_rand_state, d_octree, part);
     const AdaptFrame fr = {max_x, max_y, A.tiles_x, part.part, part.nparts, part.tile_begin, part.tile_end};
-    if ((rc = ctx_reserve_adaptive(C, npx, 1)) || (rc = ctx_reserve_budget(C, npx))) return rc;
+    if ((rc = ctx_reserve_adaptive(C, npx, 1)) || (rc = ctx_reserve_budget(C, npx, filtered))) return rc;
     if (C.has_done && C.last_stream != st) RT_TRY(hipStreamWaitEvent(st, C.done, 0));
     const bool tree = d_octree != nullptr;
     A.ad_sl = S.sl; A.ad_q = S.q; A.ad_list = C.a_list; A.ad_count = C.a_count;      // (one count serves every round: the stream orders them)
@@ -1220,7 +1248,9 @@ static int render_adaptive_spend_common(rt_render_ctx* ctx, void* fb, int max_x,
     RT_TRY(hipEventRecord(C.ev0[ek], st));
     for (int r = 0; r < P->rounds; ++r) {
         const unsigned int K = (unsigned int)std::min(budget_picks(P, r), npx);
-        RT_TRY(launch_budget_select(S, npx, fr, P->batch, P->max_spp, P->floor, K, C.a_list + npx, C.b_ws, C.a_list, C.a_count, st));
+        if (filtered) RT_TRY(launch_budget_select_filtered(S, d_hits, max_x, max_y, *filter, P->batch, P->max_spp, P->floor, K, C.a_list + npx, nullptr,
+                                                           C.b_ws, C.a_list, C.a_count, st));
+        else RT_TRY(launch_budget_select(S, npx, fr, P->batch, P->max_spp, P->floor, K, C.a_list + npx, C.b_ws, C.a_list, C.a_count, st));
         RT_TRY(launch_budget_seed((float*)fb, S, A.ad_list, A.ad_count, K, st));
         A.queue = C.d_queue + (size_t)(C.launches++ % kQueueSlots) * kQueueStride;
         RT_TRY(launch_zero_counters(A.queue, (int)kQueueStride, st));
@@ -1243,6 +1273,20 @@ int rt_render_adaptive_spend_on(rt_render_ctx* ctx, void* fb, int max_x, int max
                                 uint32_t* d_picked, void* stream) {
     if (!ctx) return RT_EINVAL;
     return render_adaptive_spend_common(ctx, fb, max_x, max_y, params, world, d_rand_state, d_octree, d_spp, d_state, part, d_picked, stream);
+}
+// ... with the filter-aware key: the whole frame (a tile-major part has no neighbours to filter with)
+int rt_render_adaptive_spend_filtered(void* fb, int max_x, int max_y, const rt_budget* params, const rt_denoise_var_params* filter,
+                                      const rt_hit_record* d_hits, const rt_world* world, rt_rand_state* d_rand_state, const rt_octree* d_octree,
+                                      int32_t* d_spp, void* d_state, uint32_t* d_picked, void* stream) {
+    return render_adaptive_spend_common(nullptr, fb, max_x, max_y, params, world, d_rand_state, d_octree, d_spp, d_state, rt_partition{0, 1, 0, 0}, d_picked,
+                                        stream, true, filter, d_hits);
+}
+int rt_render_adaptive_spend_filtered_on(rt_render_ctx* ctx, void* fb, int max_x, int max_y, const rt_budget* params, const rt_denoise_var_params* filter,
+                                         const rt_hit_record* d_hits, const rt_world* world, rt_rand_state* d_rand_state, const rt_octree* d_octree,
+                                         int32_t* d_spp, void* d_state, uint32_t* d_picked, void* stream) {
+    if (!ctx) return RT_EINVAL;
+    return render_adaptive_spend_common(ctx, fb, max_x, max_y, params, world, d_rand_state, d_octree, d_spp, d_state, rt_partition{0, 1, 0, 0}, d_picked,
+                                        stream, true, filter, d_hits);
 }
 
 // the kernel rt_render (mode 0) / rt_render_progressive (mode 1) launches for this world and tree — the library's own

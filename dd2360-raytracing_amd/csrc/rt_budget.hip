@@ -11,6 +11,12 @@
 // each) in its prologue.  Nothing comes back to the host, and the number of launches is fixed.
 // -DRT_BUDGET_SORT (tools/mkvariant.sh): the same set by sorting (~key << 32) | id with rocprim and taking the first K — the
 // on-device cross-check and the A/B baseline of tools/adaptive_budget_study.py.
+// The filter-aware budget (rt_adaptive_budget_select_filtered, DESIGN.md §5.9 "Filter-aware priority") replaces k_budget_keys by
+//   k_budget_keys_filtered   per 16x16 tile: the state's (x, v) of the tile and its apron staged in LDS, level 0 of rt_denoise_adaptive
+//                            on them, the key of the filtered pixel (rt_adaptive_priority_filtered) and the histogram of the top digit
+// and leaves the other launches as they are.  -DRT_BUDGET_FILTER_UNFUSED (tools/mkvariant.sh): the same keys from the denoiser's own
+// kernels (k_denoise_var_prepare, k_denoise_var_level<false,1>) and a third that only forms the key — the on-device cross-check and the
+// A/B baseline of tools/filtered_budget_study.py.
 #include <hip/hip_runtime.h>
 #ifdef RT_BUDGET_SORT
 #include <rocprim/device/device_radix_sort.hpp>
@@ -250,8 +256,8 @@ static size_t budget_sort_temp(long long n) {
 }
 #endif
 
-// bytes of the selection workspace for a state of n elements
-size_t budget_ws_bytes(long long n) {
+// bytes of the selection workspace for a state of n elements (filtered: and of what the unfused variant of the filtered key needs)
+static size_t budget_ws_head(long long n) {
     size_t b = sizeof(unsigned int) * (size_t)kBudgetWsWords;
 #ifdef RT_BUDGET_SORT
     b = (b + 255) / 256 * 256 + (2 * sizeof(unsigned long long) * (size_t)n + 255) / 256 * 256 + budget_sort_temp(n);
@@ -260,33 +266,246 @@ size_t budget_ws_bytes(long long n) {
 #endif
     return b;
 }
-// The K (<= n) elements of the state with the largest keys into list, their number into *count.  keys: n words, ws: budget_ws_bytes(n).
-hipError_t launch_budget_select(const AdaptState& s, long long n, const AdaptFrame& fr, int batch, int max_spp, float floor_lum, unsigned int K,
-                                unsigned int* keys, unsigned int* ws, unsigned int* list, unsigned int* count, hipStream_t st) {
-    const long long span = budget_span(n);
-    const unsigned nblk = (unsigned)((n + span - 1) / span);          // <= kBudgetMaxBlocks
+size_t budget_ws_bytes(long long n, bool filtered) {
+    size_t b = budget_ws_head(n);
+#ifdef RT_BUDGET_FILTER_UNFUSED
+    if (filtered) b = (b + 255) / 256 * 256 + (size_t)RT_DENOISE_WORK_BYTES * (size_t)n;
+#else
+    (void)filtered;
+#endif
+    return b;
+}
+// A selection is: budget_select_begin, one launch that writes the n key words and adds the histogram of their top digit to `hist`
+// (NULL: the sorting variant needs none), budget_select_finish.
+static hipError_t budget_select_begin(unsigned int* ws, unsigned int*& hist, hipStream_t st) {
+#ifdef RT_BUDGET_SORT
+    (void)ws; (void)st;
+    hist = nullptr;
+    return hipSuccess;
+#else
+    hist = ws;
+    return hipMemsetAsync(hist, 0, sizeof(unsigned int) * kBudgetHistWords, st);
+#endif
+}
+static hipError_t budget_select_finish(long long n, unsigned int K, unsigned int* keys, unsigned int* ws, unsigned int* list, unsigned int* count, hipStream_t st) {
 #ifdef RT_BUDGET_SORT
     const size_t head = (sizeof(unsigned int) * (size_t)kBudgetWsWords + 255) / 256 * 256;
     unsigned long long* in = (unsigned long long*)((char*)ws + head);
     unsigned long long* out = in + n;
     void* temp = (char*)in + (2 * sizeof(unsigned long long) * (size_t)n + 255) / 256 * 256;
     size_t need = budget_sort_temp(n);
-    hipLaunchKernelGGL(k_budget_keys, dim3(nblk), dim3(256), 0, st, s, n, span, fr, batch, max_spp, floor_lum, keys, (unsigned int*)nullptr);
     hipLaunchKernelGGL(k_budget_sort_pack, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, keys, n, in, count);
     const hipError_t e = rocprim::radix_sort_keys(temp, need, in, out, (size_t)n, 0u, 64u, st);
     if (e != hipSuccess) return e;
     hipLaunchKernelGGL(k_budget_sort_take, dim3(K / 256 + 1), dim3(256), 0, st, out, K, list, count);
 #else
+    const long long span = budget_span(n);
+    const unsigned nblk = (unsigned)((n + span - 1) / span);          // <= kBudgetMaxBlocks
     unsigned int* hist = ws; unsigned int* sel = ws + kBudgetHistWords; unsigned int* blk_tie = sel + kBudgetSelWords; unsigned int* blk_above = blk_tie + kBudgetMaxBlocks;
-    const hipError_t e = hipMemsetAsync(hist, 0, sizeof(unsigned int) * kBudgetHistWords, st);
-    if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(k_budget_keys, dim3(nblk), dim3(256), 0, st, s, n, span, fr, batch, max_spp, floor_lum, keys, hist);
     for (int pass = 1; pass < 4; ++pass) hipLaunchKernelGGL(k_budget_hist, dim3(nblk), dim3(256), 0, st, keys, n, span, K, hist, pass);
     hipLaunchKernelGGL(k_budget_ties, dim3(nblk), dim3(256), 0, st, keys, n, span, K, hist, blk_tie, blk_above);
     hipLaunchKernelGGL(k_budget_scan, dim3(1), dim3(256), 0, st, hist, K, blk_tie, blk_above, (int)nblk, sel, count);
     hipLaunchKernelGGL(k_budget_compact, dim3(nblk), dim3(256), 0, st, keys, n, span, sel, blk_tie, blk_above, list, K);
 #endif
     return hipGetLastError();
+}
+// The K (<= n) elements of the state with the largest keys into list, their number into *count.  keys: n words, ws: budget_ws_bytes(n).
+hipError_t launch_budget_select(const AdaptState& s, long long n, const AdaptFrame& fr, int batch, int max_spp, float floor_lum, unsigned int K,
+                                unsigned int* keys, unsigned int* ws, unsigned int* list, unsigned int* count, hipStream_t st) {
+    const long long span = budget_span(n);
+    const unsigned nblk = (unsigned)((n + span - 1) / span);          // <= kBudgetMaxBlocks
+    unsigned int* hist;
+    const hipError_t e = budget_select_begin(ws, hist, st);
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(k_budget_keys, dim3(nblk), dim3(256), 0, st, s, n, span, fr, batch, max_spp, floor_lum, keys, hist);
+    return budget_select_finish(n, K, keys, ws, list, count, st);
+}
+
+// ---- the filter-aware key (rt_amd.h, rt_adaptive_budget_select_filtered) ---------------------------------------------------------
+// Whole row-major frames of at most RT_DENOISE_MAX_PIXELS pixels: a pixel index, 2 * p + 1 and a tile count fit an int, 3 * p does not.
+#ifndef RT_BUDGET_FILTER_UNFUSED
+// A block owns `per` consecutive 16x16 tiles (at most kBudgetMaxBlocks blocks: one global add per bin and block, as k_budget_keys).
+// Per tile: the tile and its apron of 2 in k_denoise_var_level<*, 1>'s LDS layout — colour + variance and both guide halves, 20 rows
+// of 32 16-byte slots each, 30 KB, the same slots read by the same lanes, so its bank argument holds here (rt_denoise.hip) — but
+// filled straight from the state: every staged pixel computes k_denoise_var_prepare's (x, v) and pass-through mark itself (a pixel
+// of the apron is computed by up to four tiles; 144 of 400 per tile, against a float4 written and read back per pixel).  Then one
+// lane per pixel: level 0 of the filter as that kernel writes it, the key, the key bits (0 = not eligible) and the top digit's count.
+// 30 KB + 1 KB of LDS: four blocks a CU.  The arithmetic is copied, not shared, so that the denoiser's kernels stay as they compile.
+__global__ __launch_bounds__(256) void k_budget_keys_filtered(AdaptState s, const float4* __restrict__ g, int max_x, int max_y, int tiles_x, int tiles, int per,
+                                                              DenoiseVarLevel L, int batch, int max_spp, float floor_lum, unsigned int* __restrict__ keys,
+                                                              float* __restrict__ keys_out, unsigned int* __restrict__ hist) {
+    constexpr int S = 20, ST = 32;
+    __shared__ float4 sx[S * ST], sg0[S * ST], sg1[S * ST];
+    __shared__ unsigned int sh_hist[256];
+    sh_hist[threadIdx.x] = 0u;                                       // (published by the first tile's barrier)
+    const int li = (int)(threadIdx.x & 15), lj = (int)(threadIdx.x >> 4);
+    const int c = (lj + 2) * ST + li + 2;                            // the centre's slot
+    const int first = (int)blockIdx.x * per;
+    const int last = first + per < tiles ? first + per : tiles;
+    for (int tile = first; tile < last; ++tile) {
+        const int tx = tile % tiles_x, ty = tile / tiles_x;
+        const int i0 = tx * 16 - 2, j0 = ty * 16 - 2;
+        for (int e = (int)threadIdx.x; e < S * S; e += 256) {
+            const int ej = e / S, ei = e - ej * S;
+            const int qi = i0 + ei, qj = j0 + ej;
+            float4 v = make_float4(0.0f, 0.0f, 0.0f, -1.0f);         // outside the frame: pass-through
+            if (qi >= 0 && qi < max_x && qj >= 0 && qj < max_y) {
+                const int q = qj * max_x + qi;
+                const long long e3 = 3 * (long long)q;
+                const int k = s.k[q];
+                const float nf = (float)k;
+                v.x = s.rgb[e3] / nf; v.y = s.rgb[e3 + 1] / nf; v.z = s.rgb[e3 + 2] / nf;
+                const float sl = s.sl[q];
+                float d = nf * s.q[q] - sl * sl;
+                d = d > 0.0f ? d : 0.0f;
+                v.w = d / ((nf * nf) * (nf - 1.0f));
+                const float4 g1 = g[2 * q + 1];
+                if (__float_as_int(g1.w) == -1 || k < 2 || !__builtin_isfinite(v.x) || !__builtin_isfinite(v.y) || !__builtin_isfinite(v.z) || !__builtin_isfinite(v.w))
+                    v = make_float4(0.0f, 0.0f, 0.0f, -1.0f);
+                else { sg0[ej * ST + ei] = g[2 * q]; sg1[ej * ST + ei] = g1; }
+            }
+            sx[ej * ST + ei] = v;
+        }
+        __syncthreads();
+        const int i = tx * 16 + li, j = ty * 16 + lj;
+        const bool inside = i < max_x && j < max_y;
+        unsigned int key = 0u;
+        if (inside) {
+            const int p = j * max_x + i;
+            const int k = s.k[p];
+            const float4 xp = sx[c];
+            float pr;
+            if (xp.w < 0.0f) {                                       // pass-through: the raw rule
+                pr = adapt_priority(s.sl[p], s.q[p], k, floor_lum);
+            } else {
+                const float4 gp0 = sg0[c], gp1 = sg1[c];             // (t, P) and (N, sphere)
+                const int sp = __float_as_int(gp1.w);
+                const float tt = gp0.x * gp0.x;
+                float vb = xp.w;
+                if (L.prefilter) {
+                    const float k3[3] = {0.25f, 0.5f, 0.25f};
+                    float sg = 0.0f, sv = 0.0f;
+#pragma unroll
+                    for (int dy = -1; dy <= 1; ++dy) {
+#pragma unroll
+                        for (int dx = -1; dx <= 1; ++dx) {
+                            const int t = c + dy * ST + dx;
+                            const float vq = sx[t].w;
+                            if (vq < 0.0f) continue;
+                            if (__float_as_int(sg1[t].w) != sp) continue;
+                            const float gw = k3[dx + 1] * k3[dy + 1];
+                            sg = sg + gw;
+                            sv = sv + gw * vq;
+                        }
+                    }
+                    vb = sv / sg;
+                }
+                const float den = L.sv2 * vb + RT_DENOISE_VAR_EPS;
+                const float lp = (xp.x + xp.y) + xp.z;
+                const float k5[5] = {0.0625f, 0.25f, 0.375f, 0.25f, 0.0625f};
+                float sw = 0.0f, s0 = 0.0f, s1 = 0.0f, s2 = 0.0f, s3 = 0.0f;
+#pragma unroll
+                for (int dy = -2; dy <= 2; ++dy) {
+#pragma unroll
+                    for (int dx = -2; dx <= 2; ++dx) {
+                        const int t = c + dy * ST + dx;
+                        const float4 xq = sx[t];
+                        if (xq.w < 0.0f) continue;                   // a pass-through pixel (or one outside the frame) is never a tap
+                        const float4 gq1 = sg1[t];
+                        if (__float_as_int(gq1.w) != sp) continue;   // another sphere
+                        float wn = 1.0f;
+                        if (L.npow >= 0) {
+                            const float d = (gp1.x * gq1.x + gp1.y * gq1.y) + gp1.z * gq1.z;
+                            wn = d > 0.0f ? d : 0.0f;
+                            for (int e = 0; e < L.npow; ++e) wn = wn * wn;
+                        }
+                        float apos = 0.0f;
+                        if (L.use_pos) {
+                            const float4 gq0 = sg0[t];
+                            const float ex = gp0.y - gq0.y, ey = gp0.z - gq0.z, ez = gp0.w - gq0.w;
+                            apos = (((ex * ex + ey * ey) + ez * ez) / tt) * L.inv_sp2;
+                        }
+                        float avar = 0.0f;
+                        if (L.use_var) {
+                            const float dl = lp - ((xq.x + xq.y) + xq.z);
+                            avar = (dl * dl) / den;
+                        }
+                        const float w = (k5[dx + 2] * k5[dy + 2] * wn) / ((1.0f + apos) * (1.0f + avar));
+                        sw = sw + w;
+                        s0 = s0 + w * xq.x; s1 = s1 + w * xq.y; s2 = s2 + w * xq.z;
+                        s3 = s3 + (w * w) * xq.w;
+                    }
+                }
+                const float y0 = s0 / sw, y1 = s1 / sw, y2 = s2 / sw;
+                pr = adapt_priority_filtered((y0 + y1) + y2, s3 / (sw * sw), floor_lum);
+            }
+            if (keys_out) keys_out[p] = pr;
+            if ((long long)k + batch <= (long long)max_spp) key = __float_as_uint(pr);
+            keys[p] = key;
+        }
+        if (hist) budget_hist_add(inside, key >> 24, sh_hist);
+        __syncthreads();                                             // the tile has been read: the next one may be staged
+    }
+    __syncthreads();
+    const unsigned int cnt = sh_hist[threadIdx.x];
+    if (hist && cnt) atomicAdd(&hist[threadIdx.x], cnt);
+}
+#else
+hipError_t launch_denoise_var_level0(const float* fb_in, int max_x, int max_y, const rt_hit_record* hits, const void* state,
+                                     const rt_denoise_var_params& P, float4* work, hipStream_t st);      // rt_denoise.hip
+// the third kernel of the unfused variant: y = what level 0 left, (y, v') or .w < 0 for a pass-through pixel; laid out as k_budget_keys
+__global__ __launch_bounds__(256) void k_budget_keys_from_level(const float4* __restrict__ y, AdaptState s, long long n, long long span, int batch, int max_spp,
+                                                                float floor_lum, unsigned int* __restrict__ keys, float* __restrict__ keys_out,
+                                                                unsigned int* __restrict__ hist) {
+    __shared__ unsigned int sh_hist[256];
+    sh_hist[threadIdx.x] = 0u;
+    __syncthreads();
+    const long long begin = (long long)blockIdx.x * span;
+    for (long long o = 0; o < span && begin + o < n; o += 256) {
+        const long long t = begin + o + threadIdx.x;
+        const bool valid = t < n;
+        unsigned int key = 0u;
+        if (valid) {
+            const int k = s.k[t];
+            const float4 v = y[t];
+            const float pr = v.w < 0.0f ? adapt_priority(s.sl[t], s.q[t], k, floor_lum) : adapt_priority_filtered((v.x + v.y) + v.z, v.w, floor_lum);
+            if (keys_out) keys_out[t] = pr;
+            if ((long long)k + batch <= (long long)max_spp) key = __float_as_uint(pr);
+            keys[t] = key;
+        }
+        if (hist) budget_hist_add(valid, key >> 24, sh_hist);
+    }
+    __syncthreads();
+    const unsigned int c = sh_hist[threadIdx.x];
+    if (hist && c) atomicAdd(&hist[threadIdx.x], c);
+}
+#endif
+// launch_budget_select with the filtered key: the state of a whole row-major frame and its guides (both checked by the caller: 16-byte
+// aligned hits, max_x * max_y <= RT_DENOISE_MAX_PIXELS).  keys_out (may be NULL): the key of every pixel before the eligibility mask.
+// ws: budget_ws_bytes(n, true).
+hipError_t launch_budget_select_filtered(const AdaptState& s, const rt_hit_record* hits, int max_x, int max_y, const rt_denoise_var_params& P, int batch,
+                                         int max_spp, float floor_lum, unsigned int K, unsigned int* keys, float* keys_out, unsigned int* ws,
+                                         unsigned int* list, unsigned int* count, hipStream_t st) {
+    const long long n = (long long)max_x * max_y;
+    unsigned int* hist;
+    hipError_t e = budget_select_begin(ws, hist, st);
+    if (e != hipSuccess) return e;
+#ifndef RT_BUDGET_FILTER_UNFUSED
+    const int tiles_x = (max_x + 15) / 16, tiles_y = (max_y + 15) / 16;
+    const int tiles = tiles_x * tiles_y;                              // (<= 2^30 / 256 + two edges: fits)
+    const int per = (tiles + kBudgetMaxBlocks - 1) / kBudgetMaxBlocks;
+    const unsigned nblk = (unsigned)((tiles + per - 1) / per);        // <= kBudgetMaxBlocks, every block owns at least one tile
+    hipLaunchKernelGGL(k_budget_keys_filtered, dim3(nblk), dim3(256), 0, st, s, (const float4*)hits, max_x, max_y, tiles_x, tiles, per,
+                       denoise_var_level(P, 0), batch, max_spp, floor_lum, keys, keys_out, hist);
+#else
+    float4* work = (float4*)((char*)ws + (budget_ws_head(n) + 255) / 256 * 256);
+    e = launch_denoise_var_level0(s.rgb, max_x, max_y, hits, s.rgb, P, work, st);      // (fb_in: only copied into pass-through pixels, whose colour nobody reads)
+    if (e != hipSuccess) return e;
+    const long long span = budget_span(n);
+    hipLaunchKernelGGL(k_budget_keys_from_level, dim3((unsigned)((n + span - 1) / span)), dim3(256), 0, st, work + n, s, n, span, batch, max_spp, floor_lum,
+                       keys, keys_out, hist);
+#endif
+    return budget_select_finish(n, K, keys, ws, list, count, st);
 }
 
 // ---- the bookkeeping of a spend round --------------------------------------------------------------------------------------

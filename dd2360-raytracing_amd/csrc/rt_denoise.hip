@@ -144,13 +144,7 @@ hipError_t launch_denoise(float* fb_out, const float* fb_in, int max_x, int max_
 #define RT_DENOISE_VAR_LDS_MAX_STEP 2
 #endif
 
-struct DenoiseVarLevel {
-    int32_t h;             // tap step 2^L
-    int32_t npow;          // normal_pow_log2 (-1 = no normal term)
-    int32_t use_pos, use_var, prefilter;
-    float inv_sp2;         // 1 / sigma_position^2
-    float sv2;             // sigma_variance^2
-};
+// (DenoiseVarLevel, one level's parameters: rt_device.h)
 
 // mean colour and the variance of the mean luminance of every pixel, from the state (one lane per pixel, row-major); a pass-through
 // pixel holds the bits of fb_in and .w = -1 (a kept variance is never negative)
@@ -306,14 +300,7 @@ hipError_t launch_denoise_var(float* fb_out, const float* fb_in, int max_x, int 
     const int tiles_x = (max_x + 15) / 16, tiles_y = (max_y + 15) / 16;
     const unsigned blocks = (unsigned)tiles_x * (unsigned)tiles_y;
     for (int l = 0; l < P.levels; ++l) {
-        DenoiseVarLevel L;
-        L.h = 1 << l;
-        L.npow = P.normal_pow_log2;
-        L.use_pos = P.sigma_position > 0.0f;
-        L.use_var = P.sigma_variance > 0.0f;
-        L.prefilter = P.prefilter;
-        L.inv_sp2 = L.use_pos ? 1.0f / (P.sigma_position * P.sigma_position) : 0.0f;
-        L.sv2 = L.use_var ? P.sigma_variance * P.sigma_variance : 0.0f;
+        const DenoiseVarLevel L = denoise_var_level(P, l);
         const float4* src = work + (size_t)(l & 1) * (size_t)n;
         float4* dst = work + (size_t)((l + 1) & 1) * (size_t)n;
         const bool last = l == P.levels - 1;
@@ -325,5 +312,21 @@ hipError_t launch_denoise_var(float* fb_out, const float* fb_in, int max_x, int 
     }
     return hipGetLastError();
 }
+
+#ifdef RT_BUDGET_FILTER_UNFUSED
+// -DRT_BUDGET_FILTER_UNFUSED (tools/mkvariant.sh): the inputs of the filtered budget key from the kernels above, unchanged — prepare,
+// then level 0 into the second half of `work` (RT_DENOISE_WORK_BYTES a pixel): (y, v') of every filtered pixel, .w < 0 for a
+// pass-through pixel.  The cross-check and the A/B baseline of k_budget_keys_filtered (rt_budget.hip); fb_in is any 3n readable floats.
+hipError_t launch_denoise_var_level0(const float* fb_in, int max_x, int max_y, const rt_hit_record* hits, const void* state,
+                                     const rt_denoise_var_params& P, float4* work, hipStream_t st) {
+    const int n = max_x * max_y;
+    hipLaunchKernelGGL(k_denoise_var_prepare, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, work, fb_in, hits,
+                       adapt_state(const_cast<void*>(state), (long long)n), n);
+    const int tiles_x = (max_x + 15) / 16, tiles_y = (max_y + 15) / 16;
+    launch_var_level<1>(false, (unsigned)tiles_x * (unsigned)tiles_y, st, work, work + (size_t)n, nullptr, (const float4*)hits, max_x, max_y, tiles_x,
+                        denoise_var_level(P, 0));
+    return hipGetLastError();
+}
+#endif
 
 } // namespace rt

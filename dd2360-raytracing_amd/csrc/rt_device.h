@@ -67,6 +67,32 @@ __host__ __device__ inline float adapt_priority(float SL, float Q, int k, float 
     const float e = d / ((n - 1.f) * (m * m));
     return e > 0.f ? e : 0.f;                               // NaN (0/0, a NaN sum) becomes 0; +inf stays
 }
+// rt_adaptive_priority_filtered (rt_amd.h): the same quantity for a pixel after one level of rt_denoise_adaptive's filter — l the
+// luminance of the filtered mean, v the variance of that mean (v' of the level).  Same compilation rule, same properties.
+__host__ __device__ inline float adapt_priority_filtered(float l, float v, float floor_lum) {
+    const float m = l > floor_lum ? l : floor_lum;          // (a NaN l takes the floor)
+    const float e = v / (m * m);
+    return e > 0.f ? e : 0.f;                               // NaN becomes 0; +inf stays
+}
+// one level of rt_denoise_adaptive, as its level kernel and the filtered budget key take it (rt_denoise.hip, rt_budget.hip)
+struct DenoiseVarLevel {
+    int32_t h;             // tap step 2^L
+    int32_t npow;          // normal_pow_log2 (-1 = no normal term)
+    int32_t use_pos, use_var, prefilter;
+    float inv_sp2;         // 1 / sigma_position^2
+    float sv2;             // sigma_variance^2
+};
+inline DenoiseVarLevel denoise_var_level(const rt_denoise_var_params& P, int l) {
+    DenoiseVarLevel L;
+    L.h = 1 << l;
+    L.npow = P.normal_pow_log2;
+    L.use_pos = P.sigma_position > 0.0f;
+    L.use_var = P.sigma_variance > 0.0f;
+    L.prefilter = P.prefilter;
+    L.inv_sp2 = L.use_pos ? 1.0f / (P.sigma_position * P.sigma_position) : 0.0f;
+    L.sv2 = L.use_var ? P.sigma_variance * P.sigma_variance : 0.0f;
+    return L;
+}
 constexpr int kMaxSplitParts = 64;
 struct SplitStarts { long long s[kMaxSplitParts + 1]; };      // first tile of every band of a balanced split, and the tile count (k_assemble_split)
 

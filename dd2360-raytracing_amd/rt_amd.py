@@ -203,6 +203,10 @@ SYMBOLS = {
     "rt_denoise_check": (_i, [_i, _i, C.POINTER(DenoiseParams)]),
     "rt_denoise_adaptive": (_i, [_vp, _vp, _i, _i, _vp, _vp, C.POINTER(DenoiseVarParams), _vp, _vp]),
     "rt_denoise_adaptive_check": (_i, [_i, _i, C.POINTER(DenoiseVarParams)]),
+    "rt_adaptive_priority_filtered": (_f, [_f, _f, _f]),
+    "rt_adaptive_budget_select_filtered": (_i, [_vp, _vp, _vp, _i, _i, C.POINTER(Budget), C.POINTER(DenoiseVarParams), _i64, _vp, _vp, _vp, _vp]),
+    "rt_render_adaptive_spend_filtered": (_i, [_vp, _i, _i, C.POINTER(Budget), C.POINTER(DenoiseVarParams), _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "rt_render_adaptive_spend_filtered_on": (_i, [_vp, _vp, _i, _i, C.POINTER(Budget), C.POINTER(DenoiseVarParams), _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "rt_frame_levels": (_i, [_vp, _vp, _i, _i, _i, C.POINTER(LevelsParams), _vp]),
     "rt_frame_levels_check": (_i, [_i, _i, _i, C.POINTER(LevelsParams)]),
     "rt_frame_levels_bytes": (_i64, [_i, _i, _i]),
@@ -325,6 +329,23 @@ class RenderCtx:
         """rt_adaptive_budget_select: the ids of the `picks` pixels a round would choose into d_list (uint32), their number into d_count"""
         check(lib().rt_adaptive_budget_select(self.h, _dev(d_state), max_x, max_y, part or WHOLE, C.byref(params), picks, _dev(d_list), _dev(d_count),
                                               C.c_void_p(stream) if stream is not None else _stream()), "rt_adaptive_budget_select")
+
+    def render_adaptive_spend_filtered(self, fb, max_x, max_y, params, filter, d_hits, world, d_rand_state, d_state, octree=None, d_spp=None,
+                                       d_picked=None, stream=None):
+        """rt_render_adaptive_spend_filtered_on: the spend ranked by the error left after denoise_adaptive's first level (whole frames);
+        filter is the DenoiseVarParams the frame will be filtered with, d_hits the guides of render_guides"""
+        check(lib().rt_render_adaptive_spend_filtered_on(self.h, _dev(fb), max_x, max_y, C.byref(params), C.byref(filter), _dev(d_hits), world.h,
+                                                         _dev(d_rand_state), octree.h if octree is not None else None,
+                                                         _dev(d_spp) if d_spp is not None else None, _dev(d_state),
+                                                         _dev(d_picked) if d_picked is not None else None,
+                                                         C.c_void_p(stream) if stream is not None else _stream()), "rt_render_adaptive_spend_filtered_on")
+
+    def adaptive_budget_select_filtered(self, d_state, d_hits, max_x, max_y, params, filter, picks, d_list, d_count, d_keys=None, stream=None):
+        """rt_adaptive_budget_select_filtered: adaptive_budget_select with the filter-aware key; d_keys (optional, float32 per pixel)
+        receives every pixel's key before the eligibility mask"""
+        check(lib().rt_adaptive_budget_select_filtered(self.h, _dev(d_state), _dev(d_hits), max_x, max_y, C.byref(params), C.byref(filter), picks,
+                                                       _dev(d_list), _dev(d_count), _dev(d_keys) if d_keys is not None else None,
+                                                       C.c_void_p(stream) if stream is not None else _stream()), "rt_adaptive_budget_select_filtered")
 
     def times(self):
         out = np.zeros(64, np.float32)
@@ -710,6 +731,24 @@ def render_adaptive_spend(fb, max_x, max_y, params, world, d_rand_state, d_state
     check(lib().rt_render_adaptive_spend(_dev(fb), max_x, max_y, C.byref(params), world.h, _dev(d_rand_state), octree.h if octree is not None else None,
                                          _dev(d_spp) if d_spp is not None else None, _dev(d_state), part,
                                          _dev(d_picked) if d_picked is not None else None, _stream()), "rt_render_adaptive_spend")
+
+
+def adaptive_priority_filtered(l, v, floor):
+    """rt_adaptive_priority_filtered: the key of a filtered pixel — l the luminance of its filtered mean, v that mean's variance"""
+    return np.float32(lib().rt_adaptive_priority_filtered(float(np.float32(l)), float(np.float32(v)), float(np.float32(floor))))
+
+
+def adaptive_budget_select_filtered(ctx, d_state, d_hits, max_x, max_y, params, filter, picks, d_list, d_count, d_keys=None):
+    """rt_adaptive_budget_select_filtered on the current stream, with the workspace of the RenderCtx `ctx`"""
+    ctx.adaptive_budget_select_filtered(d_state, d_hits, max_x, max_y, params, filter, picks, d_list, d_count, d_keys)
+
+
+def render_adaptive_spend_filtered(fb, max_x, max_y, params, filter, d_hits, world, d_rand_state, d_state, octree=None, d_spp=None, d_picked=None):
+    """rt_render_adaptive_spend_filtered on the current stream: render_adaptive_spend with the pixels ranked by the error that is left
+    after the first level of denoise_adaptive (filter: its DenoiseVarParams, d_hits: the guides); fb stays unfiltered"""
+    check(lib().rt_render_adaptive_spend_filtered(_dev(fb), max_x, max_y, C.byref(params), C.byref(filter), _dev(d_hits), world.h, _dev(d_rand_state),
+                                                  octree.h if octree is not None else None, _dev(d_spp) if d_spp is not None else None, _dev(d_state),
+                                                  _dev(d_picked) if d_picked is not None else None, _stream()), "rt_render_adaptive_spend_filtered")
 
 
 def assemble(fb_full, fb_parts, max_x, max_y, nparts, precision=FP32):

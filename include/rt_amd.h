@@ -338,7 +338,8 @@ int rt_adaptive_budget_select(rt_render_ctx* ctx, const void* d_state, int max_x
  * worlds, after the parameter checks; 0 for a part without tiles.
  * A part selects among its own elements: a frame spent part by part is not the frame spent whole, and multi-GPU budgets (which need
  * a histogram exchange) are not provided.  rt_render_adaptive_refine after a spend is not supported: the state is no longer the state
- * of a threshold.  rt_denoise_adaptive accepts the state as it is. */
+ * of a threshold.  rt_denoise_adaptive accepts the state as it is.  rt_render_adaptive_spend_filtered (below, after rt_denoise_adaptive)
+ * ranks by the error that is left after that filter. */
 int rt_render_adaptive_spend(void* fb, int max_x, int max_y, const rt_budget* params, const rt_world* world, rt_rand_state* d_rand_state,
                              const rt_octree* d_octree, int32_t* d_spp, void* d_state, rt_partition part, uint32_t* d_picked, void* stream);
 int rt_render_adaptive_spend_on(rt_render_ctx* ctx, void* fb, int max_x, int max_y, const rt_budget* params, const rt_world* world,
@@ -565,6 +566,45 @@ typedef struct rt_denoise_var_params {
 int rt_denoise_adaptive(void* fb_out, const void* fb_in, int max_x, int max_y, const rt_hit_record* d_hits, const void* d_state,
                         const rt_denoise_var_params* params, void* d_work, void* stream);
 int rt_denoise_adaptive_check(int max_x, int max_y, const rt_denoise_var_params* params);
+
+/* Filter-aware budgets: the same selection and the same rounds with a second priority — the relative variance of the pixel AFTER one
+ * level of rt_denoise_adaptive's filter, for frames that go through that filter anyway: samples go where the filtered frame is still
+ * noisy (DESIGN.md §5.9 "Filter-aware priority").  Whole frames only, row-major, fp32 worlds, at most RT_DENOISE_MAX_PIXELS pixels; the
+ * state is that of part = {0, 1, 0, 0}, d_hits what rt_render_guides left (16-byte aligned), `filter` the parameters the frame will be
+ * filtered with.  IEEE binary32, one rounding per operation, no contraction, no transcendental function, sums in tap order
+ * (tests/filtered_budget_model.py is the model, bit for bit):
+ *   per pixel:       x_c = S_c / n, d, v and the pass-through decision exactly as rt_denoise_adaptive's "per pixel" and "pass-through"
+ *                    lines state them (sky, k < 2, a channel of x or v not finite); fb_in is not needed.
+ *   filtered values: (y_p, v'_p) = what level L = 0 (step 1) of rt_denoise_adaptive computes with `filter`: the same taps, skip rules,
+ *                    vb_p (prefilter), w_n, a_pos, a_var and w;  y_p = sum(w * x_q) / sum(w) per channel;
+ *                    v'_p = sum((w*w) * v_q) / (sum(w) * sum(w)).  Only this first level is evaluated, whatever filter->levels says
+ *                    (rt_denoise_adaptive_check validates levels as usual).
+ *   filtered pixel:  l = (y.r + y.g) + y.b;  m = l > floor ? l : floor;  e = v' / (m * m);  key = e > 0 ? e : 0
+ *                    (a NaN e becomes 0, +inf stays; nothing is clamped, the operations are performed as written) —
+ *                    rt_adaptive_priority_filtered(l, v', floor) on the host.
+ *   pass-through:    key = rt_adaptive_priority(SL, Q, k, floor), the raw rule: the filter leaves such a pixel as it is.
+ * Both keys estimate one quantity — the variance of a mean over the squared floored mean (the raw key is v / max(SL / n, floor)^2 up
+ * to rounding) — so one ordering holds both.  Eligibility (k + batch <= max_spp, key > 0), the ordering, ties by the lower pixel id,
+ * K_r and "only the set is defined" are those of rt_adaptive_budget_select. */
+float rt_adaptive_priority_filtered(float l, float v, float floor);
+/* rt_adaptive_budget_select with that key.  d_keys (device, may be NULL) receives one float per pixel: the key above, before the
+ * eligibility mask — the map of where the filtered frame is still noisy.  Errors as for rt_adaptive_budget_select, and RT_EINVAL for
+ * whatever rt_denoise_adaptive_check(max_x, max_y, filter) refuses and for a NULL or misaligned d_hits. */
+int rt_adaptive_budget_select_filtered(rt_render_ctx* ctx, const void* d_state, const rt_hit_record* d_hits, int max_x, int max_y,
+                                       const rt_budget* params, const rt_denoise_var_params* filter, int64_t picks, uint32_t* d_list,
+                                       uint32_t* d_count, float* d_keys, void* stream);
+/* rt_render_adaptive_spend with that key: the same round, the selection's key kernel exchanged, nothing else.  A state may be continued
+ * by either spend in any order; every statement of rt_render_adaptive_spend holds (rounds compose, a pixel at k samples holds what
+ * rt_render with ns = k gives it).  fb stays unfiltered: the caller runs rt_denoise_adaptive when it wants the picture.  Errors as for
+ * rt_render_adaptive_spend, and RT_EINVAL for the filter checks and a NULL or misaligned d_hits (with the parameter checks, before
+ * RT_ENOTSUP). */
+int rt_render_adaptive_spend_filtered(void* fb, int max_x, int max_y, const rt_budget* params, const rt_denoise_var_params* filter,
+                                      const rt_hit_record* d_hits, const rt_world* world, rt_rand_state* d_rand_state, const rt_octree* d_octree,
+                                      int32_t* d_spp, void* d_state, uint32_t* d_picked, void* stream);
+int rt_render_adaptive_spend_filtered_on(rt_render_ctx* ctx, void* fb, int max_x, int max_y, const rt_budget* params,
+                                         const rt_denoise_var_params* filter, const rt_hit_record* d_hits, const rt_world* world,
+                                         rt_rand_state* d_rand_state, const rt_octree* d_octree, int32_t* d_spp, void* d_state, uint32_t* d_picked,
+                                         void* stream);
 
 /* ---- the image end on the device: 8-bit levels and frame comparison (no reference counterpart) ------------
  * What main.cu:321-333 and evaluations.ipynb:1021-1027 do on the host — quantise a frame, grey it, SSIM / PSNR — for frames that stay
