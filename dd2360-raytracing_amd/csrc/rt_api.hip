@@ -20,6 +20,8 @@
 namespace rt {
 hipError_t launch_render_init(rt_rand_state* rs, int max_x, int max_y, int part, int nparts, long long begin, long long end, hipStream_t st);
 hipError_t launch_zero_counters(unsigned int* p, int n, hipStream_t st);
+hipError_t launch_keep_counters(const unsigned int* queue, unsigned int* kept, hipStream_t st);
+hipError_t launch_restore_counters(unsigned int* queue, const unsigned int* kept, hipStream_t st);
 hipError_t launch_pilot(const RenderArgs& A, bool tree, int* cost, unsigned char* pilot, int* work, hipStream_t st);
 hipError_t launch_pilot_h(const RenderArgs& A, bool tree, int* cost, hipStream_t st);
 hipError_t launch_assemble_split(void* full, const void* parts, int max_x, int max_y, int nparts, const long long* starts, long long part_stride_px, bool half, hipStream_t st);
@@ -279,10 +281,12 @@ int rt_world_list_accel_info(const rt_world* W, int* enabled, int* grid_dim, flo
 static int ctx_prepare(rt_render_ctx& C) {          // device counters and events; not inside a stream capture
     if (!C.d_queue) {
         void* q = nullptr;
-        RT_TRY(hipMalloc(&q, kQueueSlots * kQueueStride * sizeof(unsigned int)));
-        const hipError_t e = hipMemset(q, 0, kQueueSlots * kQueueStride * sizeof(unsigned int));
+        // (one more slot behind the ring: the kept schedule's queue words, rt_sched_keep.h)
+        RT_TRY(hipMalloc(&q, (kQueueSlots + 1) * kQueueStride * sizeof(unsigned int)));
+        const hipError_t e = hipMemset(q, 0, (kQueueSlots + 1) * kQueueStride * sizeof(unsigned int));
         if (e != hipSuccess) { (void)hipFree(q); return (int)e; }
-        C.d_queue = (unsigned int*)q;
+        C.d_queue = (unsigned int*)q; C.d_kept = C.d_queue + (size_t)kQueueSlots * kQueueStride;
+        sched_keep_drop(C.keep);
     }
     if (!C.ev_ready) {
         for (int k = 0; k < 64; ++k) {
@@ -298,6 +302,7 @@ static int ctx_prepare(rt_render_ctx& C) {          // device counters and event
 // device, so launches still queued on it finish first.
 static int ctx_reserve(rt_render_ctx& C, int64_t tiles) {
     if (C.sched_tiles >= tiles) return 0;
+    sched_keep_drop(C.keep);                 // the kept schedule lived in the buffers freed below
     void* old[5] = {C.d_cost, C.d_order, C.d_flags, C.d_long, C.d_work};
     C.d_cost = nullptr; C.d_order = nullptr; C.d_flags = nullptr; C.d_long = nullptr; C.d_work = nullptr; C.sched_tiles = 0;
     int rc = free_all(old, 5);
@@ -375,6 +380,7 @@ static int ctx_release(rt_render_ctx& C) {
     const int arc = free_all(abufs, 5);
     C.a_sl = nullptr; C.a_q = nullptr; C.a_list = nullptr; C.a_count = nullptr; C.a_pixels = 0; C.a_rounds = 0; C.b_ws = nullptr; C.b_bytes = 0;
     void* bufs[8] = {C.d_queue, C.d_cost, C.d_order, C.d_flags, C.d_long, C.p_cost, C.p_order, C.d_work};
+    sched_keep_drop(C.keep); C.d_kept = nullptr;      // (the kept words live in d_queue's allocation)
     const int brc = free_all(bufs, 8);
     const int rc = brc ? brc : arc;
     C.d_queue = nullptr; C.d_cost = nullptr; C.d_order = nullptr; C.d_flags = nullptr; C.d_long = nullptr; C.d_work = nullptr; C.sched_tiles = 0;
@@ -845,12 +851,37 @@ static RenderArgs frame_args(void* fb, int max_x, int max_y, int ns, const rt_wo
     A.ad_list = nullptr; A.ad_count = nullptr; A.ad_sl = nullptr; A.ad_q = nullptr;
     return A;
 }
-// the scheduling pass of rt_render (ns >= 4): pilot, tile order and — from 16 samples — the long chains and the sorted tail
-static int schedule_frame(rt_render_ctx& C, RenderArgs& A, const rt_world* world, const rt_octree* d_octree, int ns, hipStream_t st) {
+// the key of a launch's scheduling pass (rt_sched_keep.h), and what the context does with its record for this launch — decided
+// BEFORE the launch's first kernel: a launch that reuses the pass starts with k_restore_counters instead of k_zero_counters
+static int schedule_decide(rt_render_ctx& C, const RenderArgs& A, const rt_world* world, const rt_octree* d_octree, int ns, bool cap, SchedKey& key, SchedAction& act) {
+    int dev = 0;
+    RT_TRY(hipGetDevice(&dev));
+    key.world = world->serial; key.tree = d_octree ? d_octree->serial : 0;
+    key.max_x = A.max_x; key.max_y = A.max_y;
+    key.part = A.part; key.nparts = A.nparts; key.tile_begin = A.tile_begin; key.tile_end = A.tile_end;
+    key.traversal = d_octree ? d_octree->traversal : 0; key.ns = ns;
+    key.half = world->precision == RT_PRECISION_FP16 ? 1 : 0; key.device = dev;
+    act = sched_keep_decide(C.keep, key, tune_value("RT_SCHED_CACHE", (float)RT_SCHED_CACHE) != 0.f, cap);
+    return 0;
+}
+static int begin_counters(rt_render_ctx& C, const RenderArgs& A, SchedAction act, hipStream_t st) {
+    if (act == kSchedReuse) RT_TRY(launch_restore_counters(A.queue, C.d_kept, st));
+    else RT_TRY(launch_zero_counters(A.queue, (int)kQueueStride, st));
+    return 0;
+}
+// the scheduling pass of rt_render (ns >= 4): pilot, tile order and — from 16 samples — the long chains and the sorted tail.
+// act == kSchedReuse: the context's workspace holds this very pass (and begin_counters has written its queue words): no launch.
+static int schedule_frame(rt_render_ctx& C, RenderArgs& A, const rt_world* world, const rt_octree* d_octree, int ns, hipStream_t st, SchedAction act, const SchedKey& key) {
     const bool classify = ns >= 16;          // long-chain pre-classification pays only when chains are long
     if (classify && world->precision != RT_PRECISION_FP16) { A.tail_list = C.d_long + (size_t)A.n_local_tiles * 64; A.tail_ws = C.d_long + (size_t)C.sched_tiles * 128; A.f_tail = tune_value("RT_F_TAIL", RT_F_TAIL); A.head_sum = (int)tune_value("RT_HEAD_SUM_SPARSE", (float)RT_HEAD_SUM_SPARSE); A.head_sum_dense = (int)tune_value("RT_HEAD_SUM_DENSE", (float)RT_HEAD_SUM_DENSE); A.head_min_load = tune_value("RT_HEAD_LOAD_DENSE", (float)RT_HEAD_LOAD_DENSE); }
-    if (world->precision == RT_PRECISION_FP16) RT_TRY(launch_tile_order_h(A, d_octree != nullptr, C.d_cost, C.d_order, classify ? C.d_flags : nullptr, classify ? C.d_long : nullptr, st));
-    else RT_TRY(launch_tile_order(A, d_octree != nullptr, C.d_cost, C.d_order, classify ? C.d_flags : nullptr, classify ? C.d_long : nullptr, st));
+    if (act != kSchedReuse) {
+        if (world->precision == RT_PRECISION_FP16) RT_TRY(launch_tile_order_h(A, d_octree != nullptr, C.d_cost, C.d_order, classify ? C.d_flags : nullptr, classify ? C.d_long : nullptr, st));
+        else RT_TRY(launch_tile_order(A, d_octree != nullptr, C.d_cost, C.d_order, classify ? C.d_flags : nullptr, classify ? C.d_long : nullptr, st));
+        if (act == kSchedCompute) {          // the pass's last kernel is behind this one on the stream; valid only after every launch succeeded
+            RT_TRY(launch_keep_counters(A.queue, C.d_kept, st));
+            sched_keep_commit(C.keep, key);
+        }
+    }
     A.order = C.d_order;
     if (classify) { A.long_flag = C.d_flags; A.long_list = C.d_long; }
     return 0;
@@ -889,7 +920,9 @@ static int render_common(rt_render_ctx* ctx, void* fb, int max_x, int max_y, int
     if (!cap && C.has_done && C.last_stream != st) RT_TRY(hipStreamWaitEvent(st, C.done, 0));
     A.queue = C.d_queue + (size_t)(C.launches++ % kQueueSlots) * kQueueStride;
     C.last_queue = A.queue;
-    RT_TRY(launch_zero_counters(A.queue, (int)kQueueStride, st));
+    SchedKey skey; SchedAction act = kSchedBypass;
+    if (sched && (rc = schedule_decide(C, A, world, d_octree, ns, cap, skey, act))) return rc;
+    if ((rc = begin_counters(C, A, act, st))) return rc;
     if (mode == 1) {
         // render_progressive is one sample per launch (main.cu:119-142, called once per displayed frame, :275).  The pass with
         // current_sample == 1 runs the pilot pass of rt_render and KEEPS the tile order (most expensive tiles first) in the context;
@@ -905,7 +938,7 @@ static int render_common(rt_render_ctx* ctx, void* fb, int max_x, int max_y, int
         }
         if (C.p_valid && memcmp(C.p_key, key, sizeof(key)) == 0 && C.p_tiles >= A.n_local_tiles) { A.order = C.p_order; if (cap) C.p_pinned = true; }
     }
-    if (sched && (rc = schedule_frame(C, A, world, d_octree, ns, st))) return rc;
+    if (sched && (rc = schedule_frame(C, A, world, d_octree, ns, st, act, skey))) return rc;
     // timing events only outside a capture (recorded into a graph they would never be "recorded" for hipEventElapsedTime)
     const unsigned ek = C.ev_head % 64u;
     if (!cap) RT_TRY(hipEventRecord(C.ev0[ek], st));
@@ -975,6 +1008,16 @@ int rt_render_ctx_schedule(rt_render_ctx* C, uint32_t* out, int n) {
     if (!C || n < 0 || (n > 0 && !out)) return RT_EINVAL;
     return ctx_schedule(*C, out, n);
 }
+// how often the context reused its kept schedule / issued a scheduling pass, since it was created (host counters: no device work)
+int rt_render_ctx_schedule_reuse(rt_render_ctx* C, uint64_t* reused, uint64_t* computed) {
+    if (!C || !reused || !computed) return RT_EINVAL;
+    *reused = C->keep.reused; *computed = C->keep.computed;
+    return 0;
+}
+int rt_world_render_schedule_reuse(rt_world* W, uint64_t* reused, uint64_t* computed) {
+    if (!W) return RT_EINVAL;
+    return rt_render_ctx_schedule_reuse(&W->z->ctx, reused, computed);
+}
 int rt_world_render_times(rt_world* W, float* ms_out, int max, int* count) {
     if (!W || !ms_out || !count || max < 0) return RT_EINVAL;
     return ctx_times(W->z->ctx, ms_out, max, count);
@@ -1035,8 +1078,10 @@ static int render_adaptive_common(rt_render_ctx* ctx, void* fb, int max_x, int m
     A.ad_sl = d_state ? keep.sl : C.a_sl; A.ad_q = d_state ? keep.q : C.a_q;
     RT_TRY(launch_adapt_zero(C.a_count, rounds + 1, st));
     A.queue = C.d_queue + (size_t)(C.launches++ % kQueueSlots) * kQueueStride;
-    RT_TRY(launch_zero_counters(A.queue, (int)kQueueStride, st));
-    if (sched && (rc = schedule_frame(C, A, world, d_octree, P->min_spp, st))) return rc;
+    SchedKey skey; SchedAction act = kSchedBypass;
+    if (sched && (rc = schedule_decide(C, A, world, d_octree, P->min_spp, false, skey, act))) return rc;
+    if ((rc = begin_counters(C, A, act, st))) return rc;
+    if (sched && (rc = schedule_frame(C, A, world, d_octree, P->min_spp, st, act, skey))) return rc;
     const unsigned ek = C.ev_head % 64u;
     RT_TRY(hipEventRecord(C.ev0[ek], st));
     RT_TRY(launch_render_adaptive(A, tree, st));

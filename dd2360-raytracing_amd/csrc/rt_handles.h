@@ -5,6 +5,7 @@
 #include "rt_device.h"
 #include "../host/rt_scene.hpp"
 #include "rt_accel.h"
+#include "rt_sched_keep.h"
 
 using rt::DevScene; using rt::DevTree; using rt::DevNode; using rt::DevAccel; using rt::AccelHost; using rt::Octree;
 
@@ -24,6 +25,10 @@ struct rt_render_ctx {
     // scheduling workspace (tile costs, hand-out order, long-chain flags and list), grown on demand
     int* d_cost = nullptr; unsigned int* d_order = nullptr; unsigned char* d_flags = nullptr; unsigned int* d_long = nullptr; int* d_work = nullptr; int64_t sched_tiles = 0;
     unsigned int* last_queue = nullptr;      // the counters of the latest launch (rt_render_ctx_counters)
+    // the kept schedule (rt_sched_keep.h): the key of the scheduling pass whose results lie in d_order / d_flags / d_long, and the words
+    // that pass left in its launch's slot (kSchedKeptWords of them, behind the ring in d_queue's allocation) — a launch with an equal
+    // key runs no scheduling kernel.  One record per context, shared by rt_render and round 0 of rt_render_adaptive*.
+    rt::SchedKeep keep; unsigned int* d_kept = nullptr;
     // tile order of a progressive sequence (rt_render_progressive): the pilot pass that the call with current_sample == 1 runs, kept
     // in buffers of its own and reused by the following passes of the same frame (p_key: world and tree serials, frame size, partition)
     int* p_cost = nullptr; unsigned int* p_order = nullptr; int64_t p_tiles = 0; bool p_valid = false; uint64_t p_key[5] = {0, 0, 0, 0, 0};

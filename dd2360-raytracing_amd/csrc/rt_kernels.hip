@@ -28,6 +28,7 @@
 #include "rt_device.h"
 #include "rt_tuning.h"
 #include "rt_sampling.h"
+#include "rt_sched_keep.h"
 
 // RT_TU_CONTRACT (rt_kernels_contract.hip): the same source once more with FMA contraction ALLOWED — what nvcc's default -fmad=true
 // does to the reference (Makefile:9) — in a namespace of its own, for rt_world_set_arith(RT_ARITH_CONTRACT).  Never the parity mode.
@@ -2099,6 +2100,32 @@ hipError_t launch_assemble_split(void* full, const void* parts, int max_x, int m
 __global__ void k_zero_counters(unsigned int* p, int n) { if ((int)threadIdx.x < n) p[threadIdx.x] = 0u; }
 hipError_t launch_zero_counters(unsigned int* p, int n, hipStream_t st) {
     hipLaunchKernelGGL(k_zero_counters, dim3(1), dim3(64), 0, st, p, n);
+    return hipGetLastError();
+}
+// The kept schedule (rt_sched_keep.h): the words of a launch's slot that its scheduling pass wrote and the render kernel only reads —
+// queue[2], queue[4] (long and solo counts), queue[kQueueThr .. kQueueThr + 5] — as kSchedKeptWords words of the context.
+// k_keep_counters saves them once the pass's last kernel is behind it on the stream; k_restore_counters takes the place of
+// k_zero_counters in a launch that reuses the pass: the slot's 64 words zeroed, the kept ones written.
+__device__ __forceinline__ int kept_word_slot(int k) { return k == 0 ? 2 : k == 1 ? 4 : kQueueThr + (k - 2); }
+__global__ void k_keep_counters(const unsigned int* __restrict__ queue, unsigned int* __restrict__ kept) {
+    if (threadIdx.x < (unsigned)rt::kSchedKeptWords) kept[threadIdx.x] = queue[kept_word_slot((int)threadIdx.x)];
+}
+__global__ void k_restore_counters(unsigned int* __restrict__ queue, const unsigned int* __restrict__ kept) {
+    // (one wave, one word per lane: lane t owns queue[t], so no word is written twice)
+    const int t = (int)threadIdx.x;
+    unsigned int v = 0u;
+    if (t == 2) v = kept[0];
+    else if (t == 4) v = kept[1];
+    else if (t >= kQueueThr && t < kQueueThr + 6) v = kept[2 + t - kQueueThr];
+    queue[t] = v;
+}
+hipError_t launch_keep_counters(const unsigned int* queue, unsigned int* kept, hipStream_t st) {
+    hipLaunchKernelGGL(k_keep_counters, dim3(1), dim3(64), 0, st, queue, kept);
+    return hipGetLastError();
+}
+hipError_t launch_restore_counters(unsigned int* queue, const unsigned int* kept, hipStream_t st) {
+    static_assert(kQueueThr + 6 <= 64 && rt::kSchedKeptWords == 8, "the restore kernel covers a slot of 64 words with one wave");
+    hipLaunchKernelGGL(k_restore_counters, dim3(1), dim3(64), 0, st, queue, kept);
     return hipGetLastError();
 }
 

@@ -1,0 +1,74 @@
+// rt_sched_keep.h — when a render context may reuse the scheduling pass it ran before (DESIGN.md §5.4 "The kept schedule").
+//
+// rt_render's scheduling pass (pilot, tile order, long chains, sorted tail: five kernels) reads the world, the tree and how it is
+// walked, the frame size, the partition, the sample count, the process-wide knobs of rt_tuning.h and the lane count of the device's
+// persistent grid — never the framebuffer or the RNG states.  A context therefore keeps ONE record: the key of the pass whose results
+// lie in its workspace (d_order, d_flags, d_long) and in its kept queue words.  This header is the whole decision: plain host C++, no
+// HIP, so a stand-alone program exercises every transition on the CPU (tests/test_sched_keep_host.py).
+#pragma once
+#include <cstdint>
+
+namespace rt {
+
+// everything the scheduling pass reads that can differ between two calls of one process
+struct SchedKey {
+    uint64_t world = 0, tree = 0;              // handle serials (tree: the caller's octree or the world's list tree; 0 = none)
+    int32_t max_x = 0, max_y = 0;
+    int32_t part = 0, nparts = 0;              // rt_partition, all four fields
+    int64_t tile_begin = 0, tile_end = 0;
+    int32_t traversal = 0;                     // the tree's traversal mode (0 without a tree)
+    int32_t ns = 0;
+    int32_t half = 0;                          // 1 = a binary16 launch
+    int32_t device = 0;
+};
+inline bool sched_key_equal(const SchedKey& a, const SchedKey& b) {
+    return a.world == b.world && a.tree == b.tree && a.max_x == b.max_x && a.max_y == b.max_y && a.part == b.part && a.nparts == b.nparts &&
+           a.tile_begin == b.tile_begin && a.tile_end == b.tile_end && a.traversal == b.traversal && a.ns == b.ns && a.half == b.half &&
+           a.device == b.device;
+}
+
+// the number of queue words a pass leaves for the render kernel: queue[2], queue[4] (long and solo counts) and
+// queue[kQueueThr .. kQueueThr + 5] (thresholds, tail mark, head count, head sum, from-end flag)
+constexpr int kSchedKeptWords = 8;
+
+enum SchedAction {
+    kSchedBypass = 0,       // run the pass exactly as a context without a record would; the record is neither read nor written
+    kSchedCompute = 1,      // run the pass, then keep it (sched_keep_commit once its last launch returned success)
+    kSchedReuse = 2,        // launch none of the pass's kernels: the workspace and the kept queue words are those of this key
+};
+
+struct SchedKeep {
+    bool valid = false;         // the workspace and the kept words hold the finished pass of `key`
+    bool captured = false;      // a scheduling pass of this context has been captured into a graph: off for the rest of its life
+    SchedKey key;
+    uint64_t reused = 0, computed = 0;      // calls that reused the record / passes issued (captured ones count where they are captured)
+};
+
+// The ONE place that decides, called before the first kernel of a scheduled launch.  Every way a record is dropped or bypassed:
+//  - Drop before launching: whatever is not a hit leaves `valid` false BEFORE the pass's first kernel is launched (the pass is about to
+//    overwrite the workspace); only sched_keep_commit, after the last launch returned success, sets it again.  An early return between
+//    the two therefore leaves no valid record.
+//  - Drop on workspace changes: sched_keep_drop, called where the workspace is regrown (ctx_reserve) or freed (ctx_release).  The other
+//    writers of d_order / d_flags / d_long were audited: launch_tile_order / launch_tile_order_h from schedule_frame are the only ones
+//    (this function runs in front of them); the progressive path writes p_cost / p_order, rt_split_balanced d_cost / d_work only, the
+//    adaptive, budget and refinement rounds none of the three; k_render and k_render_h only read them.
+//  - Bypass inside a stream capture: the whole pass is captured as before.  Replays of that graph rewrite the workspace without the
+//    host knowing, so the record is dropped and `captured` keeps the context's cache off for good.
+//  - Switch: RT_SCHED_CACHE=0 (`enabled` false) runs the pass on every call, kernels and order as without this header.
+//  - The progressive path (p_order / p_key / p_pinned) never comes here.
+inline SchedAction sched_keep_decide(SchedKeep& K, const SchedKey& key, bool enabled, bool capturing) {
+    if (capturing) K.captured = true;
+    if (capturing || K.captured || !enabled) { K.valid = false; ++K.computed; return kSchedBypass; }
+    if (K.valid && sched_key_equal(K.key, key)) { ++K.reused; return kSchedReuse; }
+    K.valid = false; ++K.computed;
+    return kSchedCompute;
+}
+// after the last launch of a kSchedCompute pass (the kept words' copy included) returned success
+inline void sched_keep_commit(SchedKeep& K, const SchedKey& key) {
+    if (K.captured) return;
+    K.key = key; K.valid = true;
+}
+// the workspace was regrown or freed
+inline void sched_keep_drop(SchedKeep& K) { K.valid = false; }
+
+}  // namespace rt

@@ -110,6 +110,14 @@
 #ifndef RT_PILOT_CAP
 #define RT_PILOT_CAP 35         // (the pass is as long as its longest sample; 25: C4 +2 ms, 50 = the reference's depth limit)
 #endif
+// The kept schedule (rt_sched_keep.h): a render context keeps the scheduling pass it ran last — tile order, long-chain flags and list,
+// sorted tail, the pass's queue words — and a launch with the same world, tree, traversal, frame, partition, sample count, precision
+// and device reuses it: k_restore_counters and the render kernel, nothing else.  0 = every launch runs the pass (pilot, k_tile_order,
+// k_long_select, k_tail_hist, k_tail_scatter behind k_zero_counters), as before round 10: the A/B switch on one build and the
+// tests' reference.  Read from the environment like the knobs above (RT_SCHED_CACHE=0).  What was measured: HISTORY.md round 10.
+#ifndef RT_SCHED_CACHE
+#define RT_SCHED_CACHE 1
+#endif
 #ifndef RT_PROG_OWN
 #define RT_PROG_OWN 64          // render_progressive: pixel slots a wave owns before it takes chunks of 64 from the counter.  C3, ms per pass: 0: 0.645, 64: 0.567, 128: 0.611 (one request per lane and pixel: 1.05)
 #endif

@@ -181,6 +181,8 @@ SYMBOLS = {
     "rt_world_render_counters": (_i, [_vp, _vp]),
     "rt_render_ctx_schedule": (_i, [_vp, _vp, _i]),
     "rt_world_render_schedule": (_i, [_vp, _vp, _i]),
+    "rt_render_ctx_schedule_reuse": (_i, [_vp, _vp, _vp]),
+    "rt_world_render_schedule_reuse": (_i, [_vp, _vp, _vp]),
     "rt_render_kernel_name": (_i, [_vp, _vp, _i, _vp, _i]),
     "rt_multi_unique_id": (_i, [_vp]),
     "rt_multi_init": (_i, [_vp, _i, _i, _vp]),
@@ -365,6 +367,12 @@ class RenderCtx:
         out = np.zeros(len(SCHEDULE_FIELDS), np.uint32)
         check(lib().rt_render_ctx_schedule(self.h, _np(out), len(out)), "rt_render_ctx_schedule")
         return dict(zip(SCHEDULE_FIELDS, (int(v) for v in out)))
+
+    def schedule_reuse(self):
+        """(reused, computed): launches that reused the context's kept schedule / scheduling passes issued, since it was created"""
+        a, b = C.c_uint64(0), C.c_uint64(0)
+        check(lib().rt_render_ctx_schedule_reuse(self.h, C.byref(a), C.byref(b)), "rt_render_ctx_schedule_reuse")
+        return a.value, b.value
 
     def close(self):
         if getattr(self, "h", None):
@@ -555,6 +563,12 @@ class World:
         out = np.zeros(len(SCHEDULE_FIELDS), np.uint32)
         check(lib().rt_world_render_schedule(self.h, _np(out), len(out)), "rt_world_render_schedule")
         return dict(zip(SCHEDULE_FIELDS, (int(v) for v in out)))
+
+    def schedule_reuse(self):
+        """(reused, computed) of the context this world's render() calls use (see RenderCtx.schedule_reuse)"""
+        a, b = C.c_uint64(0), C.c_uint64(0)
+        check(lib().rt_world_render_schedule_reuse(self.h, C.byref(a), C.byref(b)), "rt_world_render_schedule_reuse")
+        return a.value, b.value
 
     def close(self):
         if getattr(self, "h", None):

@@ -379,6 +379,19 @@ int rt_render_ctx_counters(rt_render_ctx* ctx, uint32_t* out4);
 int rt_world_render_schedule(rt_world* world, uint32_t* out, int n);
 int rt_render_ctx_schedule(rt_render_ctx* ctx, uint32_t* out, int n);
 
+/* The kept schedule.  The scheduling pass of rt_render reads the world, the tree and its traversal mode, the frame size, the partition,
+ * the sample count, the precision and the device — never fb or d_rand_state — so a context keeps the pass it ran last, and an rt_render
+ * (or the first launch of rt_render_adaptive*) with all of these equal launches no scheduling kernel: it reuses the tile order, the
+ * long-chain set and the sorted tail, and rt_*_render_counters / rt_*_render_schedule return what the recomputed pass would.  Which lane
+ * renders a pixel never changes the pixel: the frame and the RNG states are the same bits either way.  One record per context; any
+ * other key, a regrown or released workspace, or a failed pass drops it.  Inside a stream capture rt_render captures the whole pass as
+ * before and the record is not used — and since the graph's replays rewrite the workspace unseen, a context whose scheduling pass has
+ * been captured never reuses again.  RT_SCHED_CACHE=0 in the environment turns the reuse off for the process.
+ * *reused = launches that reused the record, *computed = scheduling passes issued (or captured), both since the context was created.
+ * Host counters: no device work, no synchronisation. */
+int rt_render_ctx_schedule_reuse(rt_render_ctx* ctx, uint64_t* reused, uint64_t* computed);
+int rt_world_render_schedule_reuse(rt_world* world, uint64_t* reused, uint64_t* computed);
+
 /* Reassemble a full row-major frame from nparts tile-major part buffers laid out back to back, each padded to
  * rt_part_pixels(max_x,max_y,{0,nparts}) elements (the layout an all-gather of the parts produces). */
 int rt_assemble(void* fb_full, const void* fb_parts, int max_x, int max_y, int nparts, int precision, void* stream);
