@@ -1,6 +1,7 @@
 // rt_handles.h — the opaque handles of include/rt_amd.h as the library's translation units see them (rt_api.hip, rt_build.hip).
 #pragma once
 #include <hip/hip_runtime.h>
+#include <cassert>
 #include <vector>
 #include "rt_device.h"
 #include "../host/rt_scene.hpp"
@@ -14,6 +15,52 @@ using rt::DevScene; using rt::DevTree; using rt::DevNode; using rt::DevAccel; us
 // logically constant: what such a call may create lazily (device copies, the list grid, the default render context) lives
 // behind a pointer in a `Lazy` block of its own.
 struct rt_octree;
+
+// A group of device buffers that are allocated and freed together.  A handle describes each of its groups ONCE, as a function that
+// returns a DevGroup: where every pointer is kept, its bytes at the asked capacity and, for a copy of a host array, that array.
+// Whatever grows, uploads or frees device buffers goes through the three functions below.
+struct DevBuf { void** at; size_t bytes; const void* src; size_t src_bytes; };      // bytes == 0: freed with the group, allocated elsewhere
+struct DevGroup {
+    int n = 0; DevBuf b[16];          // (16: the largest group, a tree's)
+    DevGroup& add(void* at, size_t bytes) { assert(n < 16); b[n++] = DevBuf{(void**)at, bytes, nullptr, 0}; return *this; }      // at: the address of the (typed) pointer
+    // a copy of a host vector; an empty one still gets a buffer (of one element), so no kernel argument is ever null
+    template <class V> DevGroup& add_copy(void* at, const V& v) {
+        const size_t sz = sizeof(typename V::value_type);
+        assert(n < 16);
+        b[n++] = DevBuf{(void**)at, (v.empty() ? 1 : v.size()) * sz, v.empty() ? nullptr : v.data(), v.size() * sz};
+        return *this;
+    }
+};
+// frees every buffer of the group and nulls its pointer; the first hipFree error is the one returned, the others are still freed
+inline int group_free(const DevGroup& g) {
+    int rc = 0;
+    for (int k = 0; k < g.n; ++k) {
+        void*& p = *g.b[k].at;
+        if (p) { const hipError_t e = hipFree(p); if (e != hipSuccess && !rc) rc = (int)e; p = nullptr; }
+    }
+    return rc;
+}
+// free all, then allocate (and fill) all or none, in the group's order.  The old buffers go first: hipFree waits for the device, so
+// launches still queued on them finish.  On any error the group is left empty and the first error is returned.
+inline int group_regrow(const DevGroup& g) {
+    int rc = group_free(g);
+    for (int k = 0; k < g.n && !rc; ++k) {
+        const DevBuf& b = g.b[k];
+        if (!b.bytes) continue;
+        rc = (int)hipMalloc(b.at, b.bytes);
+        if (!rc && b.src) rc = (int)hipMemcpy(*b.at, b.src, b.src_bytes, hipMemcpyHostToDevice);
+        if (rc) (void)group_free(g);
+    }
+    return rc;
+}
+// a group kept at a capacity `have` (g: the group at `need`): regrown when that is too small; 0 while it is empty
+inline int group_reserve(int64_t& have, int64_t need, const DevGroup& g) {
+    if (have >= need) return 0;
+    have = 0;
+    const int rc = group_regrow(g);
+    if (!rc) have = need;
+    return rc;
+}
 
 // Per-launch state of rt_render: work counters, scheduling workspace, timing events.  One context serves one launch at a
 // time: calls on the same context are ordered by the library (an event recorded behind the render kernel, which the next
@@ -30,15 +77,15 @@ struct rt_render_ctx {
     // key runs no scheduling kernel.  One record per context, shared by rt_render and round 0 of rt_render_adaptive*.
     rt::SchedKeep keep; unsigned int* d_kept = nullptr;
     // tile order of a progressive sequence (rt_render_progressive): the pilot pass that the call with current_sample == 1 runs, kept
-    // in buffers of its own and reused by the following passes of the same frame (p_key: world and tree serials, frame size, partition)
-    int* p_cost = nullptr; unsigned int* p_order = nullptr; int64_t p_tiles = 0; bool p_valid = false; uint64_t p_key[5] = {0, 0, 0, 0, 0};
+    // in buffers of its own and reused by the following passes of the same frame (p_key: the frame's SchedKey with ns = 0 and device = 0)
+    int* p_cost = nullptr; unsigned int* p_order = nullptr; int64_t p_tiles = 0; bool p_valid = false; rt::SchedKey p_key;
     bool p_pinned = false;      // a captured progressive pass has baked p_order's address into a hipGraph: the buffers are never freed or moved again
     // rt_render_adaptive: per pixel the luminance sum and sum of squares between rounds, the two lists of active pixels (ping-pong),
     // and one active-pixel count per round; grown on demand
-    float* a_sl = nullptr; float* a_q = nullptr; unsigned int* a_list = nullptr; int64_t a_pixels = 0; unsigned int* a_count = nullptr; int a_rounds = 0;
+    float* a_sl = nullptr; float* a_q = nullptr; unsigned int* a_list = nullptr; int64_t a_pixels = 0; unsigned int* a_count = nullptr; int64_t a_rounds = 0;
     // rt_adaptive_budget_select / rt_render_adaptive_spend: the selection's histograms, threshold and per-block tie counts (the key bits
     // live in the second half of a_list, which is free outside a render round); grown on demand
-    unsigned int* b_ws = nullptr; size_t b_bytes = 0;
+    unsigned int* b_ws = nullptr; int64_t b_bytes = 0;
     // HIP events around the dominant kernel of each render call (ring of the last 64), see rt_render_ctx_times
     hipEvent_t ev0[64] = {}, ev1[64] = {}; unsigned ev_head = 0, ev_count = 0; bool ev_ready = false;
     // ordering of successive launches that share this context

@@ -72,24 +72,22 @@ struct rt_multi {
     rt_gather_fn gather = nullptr; void* user = nullptr;
     rt_render_ctx* ctx = nullptr;
     // this rank's RNG states (compact, tile-major), its frame part when it is not the root, the root's staging slots
-    void* d_rand = nullptr; size_t rand_bytes = 0;
-    void* d_local = nullptr; size_t local_bytes = 0;
-    void* d_parts = nullptr; size_t parts_bytes = 0;
+    void* d_rand = nullptr; int64_t rand_bytes = 0;
+    void* d_local = nullptr; int64_t local_bytes = 0;
+    void* d_parts = nullptr; int64_t parts_bytes = 0;
     // rt_multi_render_adaptive: this rank's sample counts when it is not the root, the root's staging slots for them (one int32 per pixel)
-    void* d_spp_local = nullptr; size_t spp_local_bytes = 0;
-    void* d_spp_parts = nullptr; size_t spp_parts_bytes = 0;
+    void* d_spp_local = nullptr; int64_t spp_local_bytes = 0;
+    void* d_spp_parts = nullptr; int64_t spp_parts_bytes = 0;
     hipEvent_t ev0 = nullptr, ev1 = nullptr; bool timed = false;
     // how the frame is divided (rt_multi_set_split) and the bands of the last balanced split, with what they were computed for
     int split_mode = RT_SPLIT_RUNS;
     int64_t starts[rt::kMaxSplitParts + 1] = {0}; bool have_split = false; uint64_t split_key[4] = {0, 0, 0, 0};
 };
 
-static int grow(void** p, size_t* have, size_t need) {
-    if (*have >= need) return 0;
-    if (*p) { RT_TRY(hipFree(*p)); *p = nullptr; *have = 0; }
-    RT_TRY(hipMalloc(p, need));
-    *have = need;
-    return 0;
+// one buffer with its size, grown on its own demand
+static int grow(void** p, int64_t* have, size_t need) { return group_reserve(*have, (int64_t)need, DevGroup().add(p, need)); }
+static DevGroup multi_group(rt_multi* M) {
+    return DevGroup().add(&M->d_rand, 0).add(&M->d_local, 0).add(&M->d_parts, 0).add(&M->d_spp_local, 0).add(&M->d_spp_parts, 0);
 }
 
 static int multi_new(rt_multi** out, int rank, int nranks) {
@@ -153,8 +151,7 @@ int rt_multi_destroy(rt_multi* M) {
     if (!M) return 0;
     int rc = 0;
     if (M->comm && rccl().ok && rccl().CommDestroy(M->comm) != 0) rc = RT_ECOMM;
-    void* bufs[5] = {M->d_rand, M->d_local, M->d_parts, M->d_spp_local, M->d_spp_parts};
-    for (void* b : bufs) if (b) { const hipError_t e = hipFree(b); if (e != hipSuccess && !rc) rc = (int)e; }
+    const int r1 = group_free(multi_group(M)); if (!rc) rc = r1;
     if (M->ev0) (void)hipEventDestroy(M->ev0);
     if (M->ev1) (void)hipEventDestroy(M->ev1);
     const int r2 = rt_render_ctx_destroy(M->ctx); if (!rc) rc = r2;

@@ -17,7 +17,7 @@ struct SchedKey {
     int32_t part = 0, nparts = 0;              // rt_partition, all four fields
     int64_t tile_begin = 0, tile_end = 0;
     int32_t traversal = 0;                     // the tree's traversal mode (0 without a tree)
-    int32_t ns = 0;
+    int32_t ns = 0;                            // (0 in the key of a progressive sequence's tile order, as is `device`)
     int32_t half = 0;                          // 1 = a binary16 launch
     int32_t device = 0;
 };
@@ -50,12 +50,13 @@ struct SchedKeep {
 //    the two therefore leaves no valid record.
 //  - Drop on workspace changes: sched_keep_drop, called where the workspace is regrown (ctx_reserve) or freed (ctx_release).  The other
 //    writers of d_order / d_flags / d_long were audited: launch_tile_order / launch_tile_order_h from schedule_frame are the only ones
-//    (this function runs in front of them); the progressive path writes p_cost / p_order, rt_split_balanced d_cost / d_work only, the
+//    (this function runs in front of them, both inside scheduled_round); the progressive path writes p_cost / p_order, rt_split_balanced d_cost / d_work only, the
 //    adaptive, budget and refinement rounds none of the three; k_render and k_render_h only read them.
 //  - Bypass inside a stream capture: the whole pass is captured as before.  Replays of that graph rewrite the workspace without the
 //    host knowing, so the record is dropped and `captured` keeps the context's cache off for good.
 //  - Switch: RT_SCHED_CACHE=0 (`enabled` false) runs the pass on every call, kernels and order as without this header.
-//  - The progressive path (p_order / p_key / p_pinned) never comes here.
+//  - The progressive path (p_order / p_key / p_pinned) never comes here; it only borrows the key type: p_key is a SchedKey with ns = 0 and
+//    device = 0, compared with sched_key_equal.
 inline SchedAction sched_keep_decide(SchedKeep& K, const SchedKey& key, bool enabled, bool capturing) {
     if (capturing) K.captured = true;
     if (capturing || K.captured || !enabled) { K.valid = false; ++K.computed; return kSchedBypass; }

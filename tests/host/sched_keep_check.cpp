@@ -51,6 +51,20 @@ int main() {
         CHECK(launch(K, k0) == kSchedCompute);         // one record per context: k0 was replaced
         CHECK(K.reused == 2 && K.computed == 3);
     }
+    // the key of a progressive sequence's tile order: the same frame with ns = 0 and device = 0 — never equal to a scheduled launch's,
+    // equal to itself, and exact where a hash of the partition words could collide (tile_end << 20 against part << 32)
+    {
+        SchedKey p0 = k0; p0.ns = 0; p0.device = 0;
+        CHECK(!sched_key_equal(p0, k0) && sched_key_equal(p0, p0));
+        SchedKey a = p0, b = p0;
+        a.part = 1; a.tile_begin = 0; a.tile_end = 8192;           // (1 << 32) ^ (8192 << 20)
+        b.part = 2; b.tile_begin = 0; b.tile_end = 4096;           // (2 << 32) ^ (4096 << 20): the same word
+        CHECK(!sched_key_equal(a, b));
+        for (size_t i = 0; i < other.size(); ++i) {                // every other field still tells two frames apart
+            SchedKey k = other[i]; k.ns = 0; k.device = 0;
+            CHECK(sched_key_equal(k, p0) == (i == 9 || i == 11));  // (9 and 11 differed in ns and device alone)
+        }
+    }
     // a new context: nothing kept
     { SchedKeep K; CHECK(!K.valid && !K.captured && K.reused == 0 && K.computed == 0); }
     // drop before launching: a miss leaves no valid record until the commit, so a failed pass (an early return) keeps none
