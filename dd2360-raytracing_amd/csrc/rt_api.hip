@@ -38,6 +38,11 @@ hipError_t launch_denoise(float* fb_out, const float* fb_in, int max_x, int max_
                           float4* work, hipStream_t st);      // rt_denoise.hip
 hipError_t launch_denoise_var(float* fb_out, const float* fb_in, int max_x, int max_y, const rt_hit_record* hits, const void* state,
                               const rt_denoise_var_params& P, float4* work, hipStream_t st);      // rt_denoise.hip
+hipError_t launch_temporal_accumulate(void* hist_out, const void* hist_in, const rt_hit_record* hits, const rt_hit_record* hits_prev,
+                                      const rt_camera* cam_prev, const void* state, const int32_t* kind, int n_kind, int max_x, int max_y,
+                                      const rt_temporal_params& P, hipStream_t st);      // rt_temporal.hip
+hipError_t launch_denoise_hist(float* fb_out, const float* fb_in, int max_x, int max_y, const rt_hit_record* hits, const void* hist,
+                               const rt_denoise_var_params& P, float4* work, hipStream_t st);      // rt_temporal.hip
 hipError_t launch_assemble(float* full, const float* parts, int max_x, int max_y, int nparts, hipStream_t st);
 hipError_t launch_render_adaptive(const RenderArgs& A, bool tree, hipStream_t st);
 hipError_t launch_adapt_check(float* fb, const float* sl, const float* q, const unsigned int* list_in, const unsigned int* count_in, long long n_all,
@@ -1444,6 +1449,46 @@ int rt_denoise_adaptive(void* fb_out, const void* fb_in, int max_x, int max_y, c
     const int rc = rt_denoise_adaptive_check(max_x, max_y, params);
     if (rc) return rc;
     return (int)launch_denoise_var((float*)fb_out, (const float*)fb_in, max_x, max_y, d_hits, d_state, *params, (float4*)d_work, (hipStream_t)stream);
+}
+
+// ---- temporal accumulation (DESIGN.md §5.10 "Temporal accumulation") -------------------------------------------------------------------
+// the frame size and parameter checks of rt_temporal_accumulate (host only)
+int rt_temporal_check(int max_x, int max_y, const rt_temporal_params* params) {
+    if (!params || max_x <= 0 || max_y <= 0 || (long long)max_x * max_y > RT_DENOISE_MAX_PIXELS) return RT_EINVAL;
+    const rt_temporal_params& P = *params;
+    if (P.max_history < 0) return RT_EINVAL;
+    if (P.reuse_specular != 0 && P.reuse_specular != 1) return RT_EINVAL;
+    if (!(P.position_tolerance > 0.0f) || !std::isfinite(P.position_tolerance) || !std::isfinite(P.position_tolerance * P.position_tolerance)) return RT_EINVAL;
+    if (!(P.normal_min_dot >= -1.0f && P.normal_min_dot <= 1.0f)) return RT_EINVAL;
+    return 0;
+}
+
+int rt_temporal_accumulate(void* d_hist_out, const void* d_hist_in, const rt_hit_record* d_hits, const rt_hit_record* d_hits_prev,
+                           const rt_camera* cam_prev, const void* d_state, const rt_world* world, int max_x, int max_y,
+                           const rt_temporal_params* params, void* stream) {
+    if (!d_hist_out || !d_hits || !d_state || !world) return RT_EINVAL;
+    if (d_hist_in && (!d_hits_prev || !cam_prev)) return RT_EINVAL;
+    if (((uintptr_t)d_hist_out & 15) || ((uintptr_t)d_hist_in & 15) || ((uintptr_t)d_hits & 15) || (d_hist_in && ((uintptr_t)d_hits_prev & 15))) return RT_EINVAL;
+    const int rc = rt_temporal_check(max_x, max_y, params);
+    if (rc) return rc;
+    if (d_hist_in) {                                                          // the kernel gathers from one while it writes the other
+        const uintptr_t a = (uintptr_t)d_hist_out, b = (uintptr_t)d_hist_in, bytes = (uintptr_t)RT_TEMPORAL_HISTORY_BYTES * (uintptr_t)max_x * (uintptr_t)max_y;
+        if ((a > b ? a - b : b - a) < bytes) return RT_EINVAL;
+    }
+    if (world->precision == RT_PRECISION_FP16) return RT_ENOTSUP;
+    const int up = world_upload(world);                                       // (nothing to do once rt_world_upload has run: the call can be captured)
+    if (up) return up;
+    return (int)launch_temporal_accumulate(d_hist_out, d_hist_in, d_hits, d_hits_prev, cam_prev, d_state, world->z->dev.kind, world->n, max_x, max_y,
+                                           *params, (hipStream_t)stream);
+}
+
+int rt_denoise_history(void* fb_out, const void* fb_in, int max_x, int max_y, const rt_hit_record* d_hits, const void* d_hist,
+                       const rt_denoise_var_params* params, void* d_work, void* stream) {
+    if (!fb_out || !fb_in || !d_hits || !d_hist || !d_work) return RT_EINVAL;
+    if (((uintptr_t)d_hits & 15) || ((uintptr_t)d_hist & 15) || ((uintptr_t)d_work & 15)) return RT_EINVAL;      // read and written as float4
+    const int rc = rt_denoise_adaptive_check(max_x, max_y, params);
+    if (rc) return rc;
+    return (int)launch_denoise_hist((float*)fb_out, (const float*)fb_in, max_x, max_y, d_hits, d_hist, *params, (float4*)d_work, (hipStream_t)stream);
 }
 
 #ifdef RT_H16_STATS

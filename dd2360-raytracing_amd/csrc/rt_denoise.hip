@@ -291,12 +291,11 @@ static void launch_var_level(bool last, unsigned blocks, hipStream_t st, const f
     else hipLaunchKernelGGL((k_denoise_var_level<false, H>), dim3(blocks), dim3(256), 0, st, src, dst, fb_out, g, max_x, max_y, tiles_x, L);
 }
 
-// the whole filter on `st`; the arguments have been checked by rt_denoise_adaptive (as launch_denoise's; `state` is only read)
-hipError_t launch_denoise_var(float* fb_out, const float* fb_in, int max_x, int max_y, const rt_hit_record* hits, const void* state,
-                              const rt_denoise_var_params& P, float4* work, hipStream_t st) {
+// the levels of the filter on a prepared workspace (its first float4 buffer: mean colour and variance, .w < 0 = pass-through): shared by
+// rt_denoise_adaptive and rt_denoise_history (rt_temporal.hip), whose prepare kernels differ
+hipError_t launch_denoise_var_levels(float* fb_out, int max_x, int max_y, const rt_hit_record* hits, const rt_denoise_var_params& P, float4* work,
+                                     hipStream_t st) {
     const int n = max_x * max_y;
-    hipLaunchKernelGGL(k_denoise_var_prepare, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, work, fb_in, hits,
-                       adapt_state(const_cast<void*>(state), (long long)n), n);
     const int tiles_x = (max_x + 15) / 16, tiles_y = (max_y + 15) / 16;
     const unsigned blocks = (unsigned)tiles_x * (unsigned)tiles_y;
     for (int l = 0; l < P.levels; ++l) {
@@ -311,6 +310,15 @@ hipError_t launch_denoise_var(float* fb_out, const float* fb_in, int max_x, int 
         if (e != hipSuccess) return e;
     }
     return hipGetLastError();
+}
+
+// the whole filter on `st`; the arguments have been checked by rt_denoise_adaptive (as launch_denoise's; `state` is only read)
+hipError_t launch_denoise_var(float* fb_out, const float* fb_in, int max_x, int max_y, const rt_hit_record* hits, const void* state,
+                              const rt_denoise_var_params& P, float4* work, hipStream_t st) {
+    const int n = max_x * max_y;
+    hipLaunchKernelGGL(k_denoise_var_prepare, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, work, fb_in, hits,
+                       adapt_state(const_cast<void*>(state), (long long)n), n);
+    return launch_denoise_var_levels(fb_out, max_x, max_y, hits, P, work, st);
 }
 
 #ifdef RT_BUDGET_FILTER_UNFUSED

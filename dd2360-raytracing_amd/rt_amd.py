@@ -98,6 +98,24 @@ def denoise_var_params(**kw):
     return DenoiseVarParams(p["levels"], p["normal_pow_log2"], p["prefilter"], p["sigma_position"], p["sigma_variance"])
 
 
+class TemporalParams(C.Structure):
+    """rt_temporal_params: the cap on the effective sample count taken over from the history (0 = take nothing), reuse_specular (0 = a
+    first hit on metal or glass starts again), the relative position tolerance and the smallest normal dot product of an accepted history
+    tap; include/rt_amd.h states the rule"""
+    _fields_ = [("max_history", C.c_int32), ("reuse_specular", C.c_int32), ("position_tolerance", C.c_float), ("normal_min_dot", C.c_float)]
+
+TEMPORAL_HISTORY_BYTES = 20    # rt_amd.h RT_TEMPORAL_HISTORY_BYTES: float4 (x.r, x.g, x.b, v) [n], then float neff [n]
+# rt_amd.h RT_TEMPORAL_DEFAULT_*: DESIGN.md §5.10 "Temporal accumulation" (tools/temporal_study.py)
+TEMPORAL_DEFAULTS = dict(max_history=32, reuse_specular=0, position_tolerance=0.03, normal_min_dot=0.9)
+
+
+def temporal_params(**kw):
+    """a TemporalParams with the library's defaults for whatever kw does not set"""
+    p = dict(TEMPORAL_DEFAULTS)
+    p.update(kw)
+    return TemporalParams(p["max_history"], p["reuse_specular"], p["position_tolerance"], p["normal_min_dot"])
+
+
 class LevelsParams(C.Structure):
     """rt_levels_params: input mode (DENOISE_INPUT_*), the progressive sample count (SUM), the output format (LEVELS_*) and top_first
     (1 = the PPM's row order, 0 = the framebuffer's); include/rt_amd.h states the quantisation"""
@@ -205,6 +223,9 @@ SYMBOLS = {
     "rt_denoise_check": (_i, [_i, _i, C.POINTER(DenoiseParams)]),
     "rt_denoise_adaptive": (_i, [_vp, _vp, _i, _i, _vp, _vp, C.POINTER(DenoiseVarParams), _vp, _vp]),
     "rt_denoise_adaptive_check": (_i, [_i, _i, C.POINTER(DenoiseVarParams)]),
+    "rt_temporal_check": (_i, [_i, _i, C.POINTER(TemporalParams)]),
+    "rt_temporal_accumulate": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, C.POINTER(TemporalParams), _vp]),
+    "rt_denoise_history": (_i, [_vp, _vp, _i, _i, _vp, _vp, C.POINTER(DenoiseVarParams), _vp, _vp]),
     "rt_adaptive_priority_filtered": (_f, [_f, _f, _f]),
     "rt_adaptive_budget_select_filtered": (_i, [_vp, _vp, _vp, _i, _i, C.POINTER(Budget), C.POINTER(DenoiseVarParams), _i64, _vp, _vp, _vp, _vp]),
     "rt_render_adaptive_spend_filtered": (_i, [_vp, _i, _i, C.POINTER(Budget), C.POINTER(DenoiseVarParams), _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
@@ -810,6 +831,36 @@ def denoise_adaptive(fb_out, fb_in, max_x, max_y, d_hits, d_state, params, d_wor
     of the same call, params a DenoiseVarParams (denoise_var_params()); fb_out may be fb_in"""
     check(lib().rt_denoise_adaptive(_dev(fb_out), _dev(fb_in), max_x, max_y, _dev(d_hits), _dev(d_state), C.byref(params), _dev(d_work),
                                     _stream()), "rt_denoise_adaptive")
+
+
+def alloc_temporal_history(max_x, max_y, device="cuda"):
+    """a history of temporal_accumulate: TEMPORAL_HISTORY_BYTES per pixel, zeroed (neff = 0: nothing accumulated); view the first
+    4 * n floats as (n, 4) for (x.r, x.g, x.b, v) and the last n as neff"""
+    import torch
+    return torch.zeros(max_x * max_y * TEMPORAL_HISTORY_BYTES // 4, dtype=torch.float32, device=device)
+
+
+def temporal_check(max_x, max_y, params):
+    """rt_temporal_check: True when temporal_accumulate accepts a frame of this size with these parameters (host only)"""
+    return lib().rt_temporal_check(max_x, max_y, C.byref(params)) == 0
+
+
+def temporal_accumulate(d_hist_out, d_hist_in, d_hits, d_hits_prev, cam_prev, d_state, world, max_x, max_y, params):
+    """rt_temporal_accumulate on the current stream: this frame's history into d_hist_out from its state and guides and, unless
+    d_hist_in is None (the first frame), the history, guides and camera (a camera_dtype array) of the last frame; params is a
+    TemporalParams (temporal_params())"""
+    first = d_hist_in is None
+    cam = None if first else np.ascontiguousarray(cam_prev, camera_dtype).reshape(1)
+    check(lib().rt_temporal_accumulate(_dev(d_hist_out), None if first else _dev(d_hist_in), _dev(d_hits), None if first else _dev(d_hits_prev),
+                                       None if first else _np(cam), _dev(d_state), world.h, max_x, max_y, C.byref(params), _stream()),
+          "rt_temporal_accumulate")
+
+
+def denoise_history(fb_out, fb_in, max_x, max_y, d_hits, d_hist, params, d_work):
+    """rt_denoise_history on the current stream: denoise_adaptive with the mean and variance of every pixel taken from the history
+    d_hist (temporal_accumulate); fb_in supplies the pass-through pixels, fb_out may be fb_in"""
+    check(lib().rt_denoise_history(_dev(fb_out), _dev(fb_in), max_x, max_y, _dev(d_hits), _dev(d_hist), C.byref(params), _dev(d_work), _stream()),
+          "rt_denoise_history")
 
 
 def frame_levels_bytes(max_x, max_y, fmt=LEVELS_RGB8):

@@ -580,6 +580,63 @@ int rt_denoise_adaptive(void* fb_out, const void* fb_in, int max_x, int max_y, c
                         const rt_denoise_var_params* params, void* d_work, void* stream);
 int rt_denoise_adaptive_check(int max_x, int max_y, const rt_denoise_var_params* params);
 
+/* Temporal accumulation: the history of one frame from the history of the last one, across a camera move (DESIGN.md §5.10 "Temporal
+ * accumulation"; fp32 worlds, whole row-major frames, a static scene: both frames use the same sphere list).  A history is
+ * RT_TEMPORAL_HISTORY_BYTES per pixel: float4 (x.r, x.g, x.b, v) [n] — the accumulated mean colour and the variance of its luminance —
+ * then float neff [n], the effective sample count behind it (0 = nothing); the base 16-byte aligned.  d_state is the state of this
+ * frame (as rt_denoise_adaptive takes it), d_hits its guides; d_hits_prev and cam_prev (a host POD, passed to the kernel by value)
+ * belong to the frame that wrote d_hist_in.  d_hist_in == NULL marks the first frame (d_hits_prev and cam_prev may then be NULL too).
+ * The world supplies kind[sphere] only.  IEEE binary32, one rounding per operation, no contraction; a dot product is
+ * (a.x*b.x + a.y*b.y) + a.z*b.z (tests/temporal_model.py is the model, bit for bit):
+ *   this frame:      n, x_c = S_c / n, d and v_c exactly as rt_denoise_adaptive's "per pixel" line.  The pixel is EMPTY when it is sky
+ *                    (sphere == -1), when k < 2, or when a channel of x_c or v_c is not finite: it writes (0, 0, 0, 0) and neff = 0.
+ *   asked at all:    not when d_hist_in == NULL, when max_history == 0, or when reuse_specular == 0 and kind[sphere_p] is not
+ *                    RT_MAT_LAMBERTIAN (a sphere index outside the world's list counts as not lambertian).
+ *   where it was:    the pinhole inverse of get_ray on cam_prev = (O, LL, H, V):  A = LL - O;  D = P_p - O;  W = H x V, each component
+ *                    two products and one subtraction (W.x = H.y*V.z - H.z*V.y, W.y = H.z*V.x - H.x*V.z, W.z = H.x*V.y - H.y*V.x);
+ *                    lam = (D.W) / (A.W), rejected unless lam > 0;  s = ((D.H) / lam - A.H) / (H.H);  t likewise with V;
+ *                    fx = s * (float)max_x - 0.5f;  fy = t * (float)max_y - 0.5f;  rejected unless fx > -1 && fx < (float)max_x and the
+ *                    same for fy (a NaN rejects);  i0 = (int)floorf(fx), ax = fx - (float)i0;  j0, ay likewise.  The mapping is exact for
+ *                    cameras of rt_camera_init / rt_create_world, whose horizontal is perpendicular to their vertical; for another
+ *                    camera it is the stated arithmetic, not the inverse.
+ *   the four taps:   q = (i0 + a, j0 + b), b outer, both from 0;  g = (a ? ax : 1 - ax) * (b ? ay : 1 - ay).  A tap is skipped, not
+ *                    weighted by 0, when it lies outside the frame, when neff_in[q] is not > 0, when sphere_q != sphere_p, when
+ *                    N_p.N_q is not >= normal_min_dot, or when ((e.x*e.x + e.y*e.y) + e.z*e.z) <= tol2 * (t_p*t_p) does not hold,
+ *                    e = P_p - P_q, tol2 = position_tolerance^2 rounded once on the host.  Over the accepted taps, in tap order:
+ *                    sg = sum(g);  x_h = sum(g * x_q) / sg per channel;  v_h = sum(g * v_q) / sg;  n_h = sum(g * neff_q) / sg.
+ *                    The variance is interpolated, not combined with squared weights: resampled neighbours are correlated, the
+ *                    linear form is the conservative one.  No history unless sg > 0.
+ *   merging:         m = n_h < (float)max_history ? n_h : (float)max_history;  a = n / (m + n);  x = x_h + a*(x_c - x_h) per channel;
+ *                    v = ((1 - a)*(1 - a))*v_h + (a*a)*v_c;  neff = m + n.  Without history x = x_c, v = v_c, neff = n.  Nothing is clamped.
+ * d_hist_in and d_hist_out must not overlap.  One launch, no allocation, no synchronisation, no atomics: the call can be captured into a
+ * hipGraph once rt_world_upload has run.  RT_EINVAL for NULL or 16-byte-misaligned buffers (histories and guides), a d_hist_in without
+ * d_hits_prev or cam_prev, overlapping histories, and whatever rt_temporal_check (host only) refuses: sizes as for rt_denoise, a NULL
+ * params, max_history < 0, reuse_specular outside 0..1, a position_tolerance that is not finite and > 0 or whose square is not finite,
+ * a normal_min_dot outside [-1, 1]; after those checks RT_ENOTSUP for USE_FP16 worlds.
+ * Defaults (RT_TEMPORAL_DEFAULT_*): the setting that loses least on C3 over a static camera and an orbit of 3.5 pixels a frame
+ * (tools/temporal_study.py). */
+#define RT_TEMPORAL_HISTORY_BYTES 20   /* per pixel: float4 (x.r, x.g, x.b, v) [n], then float neff [n]; base 16-byte aligned */
+#define RT_TEMPORAL_DEFAULT_MAX_HISTORY 32
+#define RT_TEMPORAL_DEFAULT_REUSE_SPECULAR 0
+#define RT_TEMPORAL_DEFAULT_POSITION_TOLERANCE 0.03f
+#define RT_TEMPORAL_DEFAULT_NORMAL_MIN_DOT 0.9f
+typedef struct rt_temporal_params {
+    int32_t max_history;       /* cap on the effective sample count taken over from the history, >= 0; 0 = take nothing */
+    int32_t reuse_specular;    /* 0: a first hit on RT_MAT_METAL / RT_MAT_DIELECTRIC starts again; 1: reprojected like any other */
+    float position_tolerance;  /* a history tap is accepted when |P_p - P_q|^2 <= tol^2 * t_p^2; finite, > 0, tol^2 finite */
+    float normal_min_dot;      /* ... and N_p . N_q >= this; in [-1, 1] */
+} rt_temporal_params;
+int rt_temporal_check(int max_x, int max_y, const rt_temporal_params* params);             /* host only */
+int rt_temporal_accumulate(void* d_hist_out, const void* d_hist_in, const rt_hit_record* d_hits, const rt_hit_record* d_hits_prev,
+                           const rt_camera* cam_prev, const void* d_state, const rt_world* world, int max_x, int max_y,
+                           const rt_temporal_params* params, void* stream);
+/* rt_denoise_adaptive with its "per pixel" values taken from a history: x = hist.xyz, v = hist.w; a pixel is pass-through, and keeps
+ * the bits of fb_in, when neff == 0 or a channel of x or v is not finite (or v < 0, which rt_temporal_accumulate never writes).  The
+ * levels, fb_out == fb_in, buffers, alignment (d_hist 16-byte aligned too), capture and errors are those of rt_denoise_adaptive; d_hits
+ * are the guides of the frame the history belongs to.  After rt_temporal_accumulate(NULL history) it is rt_denoise_adaptive bit for bit. */
+int rt_denoise_history(void* fb_out, const void* fb_in, int max_x, int max_y, const rt_hit_record* d_hits, const void* d_hist,
+                       const rt_denoise_var_params* params, void* d_work, void* stream);
+
 /* Filter-aware budgets: the same selection and the same rounds with a second priority — the relative variance of the pixel AFTER one
  * level of rt_denoise_adaptive's filter, for frames that go through that filter anyway: samples go where the filtered frame is still
  * noisy (DESIGN.md §5.9 "Filter-aware priority").  Whole frames only, row-major, fp32 worlds, at most RT_DENOISE_MAX_PIXELS pixels; the
