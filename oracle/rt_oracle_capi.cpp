@@ -47,6 +47,30 @@ template <class R> static void fill_custom(World<R>& W, int n, const float* geom
     if (use_octree) W.tree = build_octree(W.list, spl);
 }
 
+// helpers of orc_get_ray / orc_make_camera
+template <class R> static Camera<R> camera_of(const float* cam) {
+    Camera<R> c; int o = 0;
+    auto get = [&](V3<R>& v) { for (int k = 0; k < 3; ++k) v.e[k] = from_f<R>(cam[o++]); };
+    get(c.origin); get(c.lower_left_corner); get(c.horizontal); get(c.vertical); get(c.u); get(c.v); get(c.w);
+    c.lens_radius = from_f<R>(cam[o++]);
+    return c;
+}
+template <class R> static void get_rays(const float* cam, int64_t n, const float* s, const float* t, Xorwow* st, float* rays) {
+    const Camera<R> c = camera_of<R>(cam);
+    for (int64_t i = 0; i < n; ++i) {
+        const Ray<R> r = get_ray(c, from_f<R>(s[i]), from_f<R>(t[i]), st[i]);
+        for (int k = 0; k < 3; ++k) { rays[i * 6 + k] = to_f(r.A.e[k]); rays[i * 6 + 3 + k] = to_f(r.B.e[k]); }
+    }
+}
+template <class R> static void camera_from(const float* a, float* out) {
+    auto v3 = [&](int o) { return mk<R>(from_f<R>(a[o]), from_f<R>(a[o + 1]), from_f<R>(a[o + 2])); };
+    const Camera<R> c = make_camera<R>(v3(0), v3(3), v3(6), from_f<R>(a[9]), from_f<R>(a[10]), from_f<R>(a[11]), from_f<R>(a[12]));
+    int o = 0;
+    auto put = [&](const V3<R>& v) { for (int k = 0; k < 3; ++k) out[o++] = to_f(v.e[k]); };
+    put(c.origin); put(c.lower_left_corner); put(c.horizontal); put(c.vertical); put(c.u); put(c.v); put(c.w);
+    out[o++] = to_f(c.lens_radius);
+}
+
 extern "C" {
 
 orc_scene* orc_scene_create(int num_spheres, float radius, int nx, int ny, int fp16, int use_octree, int spl) {
@@ -137,6 +161,39 @@ void orc_trace(orc_scene* s, int64_t n, const float* rays, int mode, int32_t* hi
         }
         return 0;
     });
+}
+
+// One bounce, for the comparison with a build of the reference's headers (tests/test_reference_pins_host.py): material::scatter of
+// sphere sph[i] on n (ray 6 floats, record t p normal 7 floats, 48-byte state advanced in place).  ret: scatter's return value,
+// -1 for a ghost slot (nothing is called).
+void orc_scatter(orc_scene* s, int64_t n, const int32_t* sph, const float* rays, const float* recs, void* states, int32_t* ret, float* att, float* out) {
+    with_world(s, [&](auto& W) {
+        using R = decltype(W.cam.lens_radius);
+        Xorwow* st = (Xorwow*)states;
+        for (int64_t i = 0; i < n; ++i) {
+            const Sphere<R>& m = W.list[sph[i]];
+            if (m.kind == MAT_NONE) { ret[i] = -1; continue; }
+            Ray<R> r, sc; Hit<R> rec; V3<R> a;
+            for (int k = 0; k < 3; ++k) {
+                r.A.e[k] = from_f<R>(rays[i * 6 + k]); r.B.e[k] = from_f<R>(rays[i * 6 + 3 + k]);
+                rec.p.e[k] = from_f<R>(recs[i * 7 + 1 + k]); rec.normal.e[k] = from_f<R>(recs[i * 7 + 4 + k]);
+                a.e[k] = from_i<R>(0); sc.A.e[k] = from_i<R>(0); sc.B.e[k] = from_i<R>(0);
+            }
+            rec.t = from_f<R>(recs[i * 7]); rec.sphere = sph[i];
+            ret[i] = scatter(m, r, rec, a, sc, st[i]) ? 1 : 0;
+            for (int k = 0; k < 3; ++k) { att[i * 3 + k] = to_f(a.e[k]); out[i * 6 + k] = to_f(sc.A.e[k]); out[i * 6 + 3 + k] = to_f(sc.B.e[k]); }
+        }
+        return 0;
+    });
+}
+
+// camera::get_ray(s[i], t[i]) of the camera given by its 22 floats, each from its own 48-byte state
+void orc_get_ray(int fp16, const float* cam, int64_t n, const float* s, const float* t, void* states, float* rays) {
+    if (fp16) get_rays<h16>(cam, n, s, t, (Xorwow*)states, rays); else get_rays<float>(cam, n, s, t, (Xorwow*)states, rays);
+}
+// camera::camera from its arguments (lookfrom 3, lookat 3, vup 3, vfov, aspect, aperture, focus_dist): the 22 floats
+void orc_make_camera(int fp16, const float* args, float* out) {
+    if (fp16) camera_from<h16>(args, out); else camera_from<float>(args, out);
 }
 
 // render_init (main.cu:84-94): seed 1984 + absolute pixel_index; states is a compact array for rows [row0,row0+rows)

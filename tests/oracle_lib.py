@@ -38,6 +38,9 @@ def lib():
         L.orc_scene_octree_nodes.argtypes = [C.c_void_p] + [C.c_void_p] * 3
         L.orc_scene_octree_leaves.argtypes = [C.c_void_p] + [C.c_void_p] * 2
         L.orc_trace.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_int] + [C.c_void_p] * 5
+        L.orc_scatter.argtypes = [C.c_void_p, C.c_int64] + [C.c_void_p] * 7
+        L.orc_get_ray.argtypes = [C.c_int, C.c_void_p, C.c_int64] + [C.c_void_p] * 4
+        L.orc_make_camera.argtypes = [C.c_int, C.c_void_p, C.c_void_p]
         L.orc_render_init.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p]
         L.orc_render.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p]
         L.orc_render_progressive.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int]
@@ -134,6 +137,17 @@ class OracleScene:
         self.L.orc_trace(self.h, n, _p(rays), mode, _p(hit), _p(sph), _p(t), _p(p), _p(nrm))
         return dict(hit=hit, sphere=sph, t=t, p=p, normal=nrm)
 
+    def scatter(self, sphere, rays, recs, states):
+        """material::scatter, one bounce each: sphere n, rays n x 6, recs n x 7 (t, p, normal), states n x 12 words (not written to).
+        Returns ret (-1: ghost slot), attenuation, scattered rays, states after."""
+        sphere = np.ascontiguousarray(sphere, np.int32)
+        n = sphere.size
+        rays, recs = np.ascontiguousarray(rays, np.float32).reshape(n, 6), np.ascontiguousarray(recs, np.float32).reshape(n, 7)
+        st = np.array(states, np.uint32).reshape(n, 12)
+        ret, att, out = np.zeros(n, np.int32), np.zeros((n, 3), np.float32), np.zeros((n, 6), np.float32)
+        self.L.orc_scatter(self.h, n, _p(sphere), _p(rays), _p(recs), _p(st), _p(ret), _p(att), _p(out))
+        return ret, att, out, st
+
     def render_init(self, row0=0, rows=None):
         rows = self.ny if rows is None else rows
         st = np.zeros((rows * self.nx, 12), np.uint32)
@@ -155,6 +169,24 @@ class OracleScene:
     def render_progressive(self, fb, current_sample, states, nthreads=1):
         self.L.orc_render_progressive(self.h, _p(fb), self.nx, self.ny, current_sample, _p(states), nthreads)
         return fb
+
+
+def get_ray(cam, s, t, states, fp16=False):
+    """camera::get_ray (camera.h:45-49) of the camera given by its 22 floats: rays n x 6 and the states after"""
+    cam, s, t = np.ascontiguousarray(cam, np.float32).ravel(), np.ascontiguousarray(s, np.float32), np.ascontiguousarray(t, np.float32)
+    assert cam.size == 22 and s.shape == t.shape
+    st = np.array(states, np.uint32).reshape(s.size, 12)
+    rays = np.zeros((s.size, 6), np.float32)
+    lib().orc_get_ray(int(fp16), _p(cam), s.size, _p(s), _p(t), _p(st), _p(rays))
+    return rays, st
+
+
+def make_camera(lookfrom, lookat, vup, vfov, aspect, aperture, focus_dist, fp16=False):
+    """camera::camera (camera.h:22-44): the 22 floats"""
+    args = np.array(list(lookfrom) + list(lookat) + list(vup) + [vfov, aspect, aperture, focus_dist], np.float32)
+    out = np.zeros(22, np.float32)
+    lib().orc_make_camera(int(fp16), _p(args), _p(out))
+    return out
 
 
 def ppm_bytes(fb):

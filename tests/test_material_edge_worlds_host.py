@@ -1,4 +1,5 @@
-"""The worlds of tests/material_edge_worlds.py on the CPU oracle alone: each one really reaches the branch it is named for, so the GPU
+"""The worlds of tests/material_edge_worlds.py on the CPU oracle alone (that the oracle's bounces in these worlds are the reference's is
+tests/test_reference_pins_host.py's business): each one really reaches the branch it is named for, so the GPU
 comparisons of tests/test_gpu_material_edges.py cannot pass vacuously.  The bounds are conditions with wide margins over what the
 oracle gives (every test prints its figures; 64 x 40, 16 spp, list / tree: about 47 / 48 rays per sample in the white and the mirror
 room, 17 / 16 in tir_room; extremes: hundreds of NaN and of infinite pixels, over two thirds finite).  A recipe that misses one is
