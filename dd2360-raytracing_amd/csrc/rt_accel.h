@@ -154,7 +154,8 @@ inline void build_accel(AccelHost& A, const std::vector<DevNode>& nodes, const s
     for (int s = 0; s < n_world; ++s) if (in_tree[s]) radii.push_back(std::sqrt((double)hot_of[s].w));
     DevAccel& p = A.p;
     p = DevAccel{};
-    if (radii.empty()) { p.enabled = 0; A.cs.assign(4, 0); return; }
+    // (an empty tree has no grid; large_brick keeps its one placeholder pair, which rt_octree_debug_array reads whatever n_large is)
+    if (radii.empty()) { p.enabled = 0; A.cs.assign(4, 0); A.large_brick.assign(2, make_float4(0, 0, 0, 0)); return; }
     std::nth_element(radii.begin(), radii.begin() + radii.size() / 2, radii.end());
     const double rmed = radii[radii.size() / 2];
     double h = 2.0 * accel_Rp(rmed * rmed);

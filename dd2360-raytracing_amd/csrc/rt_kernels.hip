@@ -936,9 +936,11 @@ RT_DEV void closest_tree(const DevScene& S, const DevTree& T, const float4* s_no
     )
     bool slow = fresh;
     if (COOPG != 1 && T.acc.enabled) {
-        // preconditions of the exactness argument; any NaN/inf makes a comparison false and sends the ray to the scan
+        // preconditions of the exactness argument; any NaN/inf makes a comparison false and sends the ray to the scan.  d.x and d.z must
+        // be NORMAL numbers, not merely non-zero: walk_setup divides by the larger of the two through v_rcp_f32, and the reciprocal of a
+        // subnormal below 2^-128 is +-inf - an infinite (then NaN) slope skipped every column of an all but vertical ray
         const float zx = r.o.x, zy = r.o.y - 1.0f, zz = r.o.z;
-        const bool fast = fresh && (a >= 9.094947e-13f) && (a <= 1.0995116e12f) && (r.d.x != 0.0f) && (r.d.z != 0.0f)
+        const bool fast = fresh && (a >= 9.094947e-13f) && (a <= 1.0995116e12f) && (fabsf(r.d.x) >= FLT_MIN) && (fabsf(r.d.z) >= FLT_MIN)
                           && (fabsf(r.d.y) >= 9.094947e-13f) && (zx * zx + zy * zy + zz * zz <= T.acc.zone2);
         slow = fresh && !fast;
         STAT(st, ST_FAST, fast ? 1 : 0); STAT(st, ST_SLOW, slow ? 1 : 0);

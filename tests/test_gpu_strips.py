@@ -15,10 +15,12 @@ def bits(a):
     return np.ascontiguousarray(a, np.float32).view(np.uint32)
 
 
-def lattice_rays(info, centers, radii, n, seed):
+def lattice_rays(info, centers, radii, n, seed, g0=None):
+    """g0: the grid's origin where it is not the root box's (a list whose grid follows its spheres further out)"""
     rng = np.random.default_rng(seed)
     G, h = info["grid_dim"], float(info["cell_size"])
-    g0 = -(11.0 + 5.0 * h)                                    # build_accel: half = root half-width + 2 Rlim + 2 h, Rlim = 1.5 h
+    if g0 is None:
+        g0 = -(11.0 + 5.0 * h)                                # build_accel: half = root half-width + 2 Rlim + 2 h, Rlim = 1.5 h
     F = 8
     o = np.zeros((n, 3), np.float64)
     d = np.zeros((n, 3), np.float64)
