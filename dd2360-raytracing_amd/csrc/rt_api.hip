@@ -61,6 +61,10 @@ size_t budget_ws_bytes(long long n, bool filtered);                    // rt_bud
 hipError_t launch_budget_select_filtered(const AdaptState& s, const rt_hit_record* hits, int max_x, int max_y, const rt_denoise_var_params& P, int batch,
                                          int max_spp, float floor_lum, unsigned int K, unsigned int* keys, float* keys_out, unsigned int* ws,
                                          unsigned int* list, unsigned int* count, hipStream_t st);
+hipError_t launch_budget_select_temporal(const void* state, const void* hist_in, const rt_hit_record* hits, const rt_hit_record* hits_prev,
+                                         const rt_camera* cam_prev, const int32_t* kind, int n_kind, int max_x, int max_y, const rt_temporal_params& P,
+                                         int batch, int max_spp, float floor_lum, unsigned int K, unsigned int* keys, float* keys_out, unsigned int* ws,
+                                         unsigned int* list, unsigned int* count, hipStream_t st);
 hipError_t launch_budget_select(const AdaptState& s, long long n, const AdaptFrame& fr, int batch, int max_spp, float floor_lum, unsigned int K,
                                 unsigned int* keys, unsigned int* ws, unsigned int* list, unsigned int* count, hipStream_t st);
 hipError_t launch_budget_seed(float* fb, const AdaptState& s, const unsigned int* list, const unsigned int* count, unsigned int cap, hipStream_t st);
@@ -1043,7 +1047,9 @@ int rt_render_progressive_on(rt_render_ctx* ctx, void* fb, int max_x, int max_y,
 //   tree and world of one precision -> RT_ENOTSUP for binary16 and contracted worlds -> never inside a stream capture.
 // Then the world and its tree are uploaded, the context is chosen and prepared.  `params_ok` and `pointers_ok` are the caller's own
 // checks (its parameter block, the world, its buffers), evaluated where the order puts them.  The selections pass no world: their
-// workspace is the caller's context, nothing is rendered.
+// workspace is the caller's context, nothing is rendered.  `kinds` is the world of a selection that reads kind[sphere] and nothing
+// else (the history-aware key): binary16 is refused where the order puts RT_ENOTSUP, a contracted world is not (nothing is rendered),
+// and it is uploaded without a tree, as rt_temporal_accumulate uploads it.
 struct FrameCall {
     hipStream_t st = nullptr; rt_render_ctx* C = nullptr;
     int64_t npx = 0;          // buffer elements (a part's padding included); 0 after frame_begin returned 0: the call has nothing to do
@@ -1051,7 +1057,7 @@ struct FrameCall {
     AdaptFrame fr{};
 };
 static int frame_begin(FrameCall& F, rt_render_ctx* ctx, bool params_ok, bool pointers_ok, int max_x, int max_y, rt_partition part,
-                       const rt_world* world, const rt_octree*& d_octree, void* stream) {
+                       const rt_world* world, const rt_octree*& d_octree, void* stream, const rt_world* kinds = nullptr) {
     if (!params_ok || max_x <= 0 || max_y <= 0 || !valid_partition(part)) return RT_EINVAL;
     const int64_t npx = rt_part_pixels(max_x, max_y, part);
     if (npx < 0 || npx > (int64_t)0xffffffffll) return RT_EINVAL;       // ids of the active lists are 32-bit
@@ -1059,9 +1065,11 @@ static int frame_begin(FrameCall& F, rt_render_ctx* ctx, bool params_ok, bool po
     if (!pointers_ok) return RT_EINVAL;
     if (world && d_octree && d_octree->precision != world->precision) return RT_EINVAL;
     if (world && (world->precision == RT_PRECISION_FP16 || world->arith == RT_ARITH_CONTRACT)) return RT_ENOTSUP;
+    if (kinds && kinds->precision == RT_PRECISION_FP16) return RT_ENOTSUP;
     F.st = (hipStream_t)stream;
     if (capturing(F.st)) return RT_EINVAL;                               // the workspace may grow, the launches read it: never captured
     int rc = world ? ensure_on_device(world, d_octree) : 0;
+    if (!rc && kinds) rc = world_upload(kinds);
     F.C = ctx ? ctx : &world->z->ctx;
     if (!rc) rc = ctx_prepare(*F.C);
     if (rc) return rc;
@@ -1229,15 +1237,39 @@ int rt_adaptive_budget_select_filtered(rt_render_ctx* ctx, const void* d_state, 
                                          params->floor, (unsigned int)std::min(picks, F.npx), C.a_list + F.npx, d_keys, C.b_ws, d_list, d_count, F.st));
     return ctx_mark_done(C, F.st);
 }
+// The same with the history-aware key (whole frames only; the world supplies kind[] and is uploaded if need be).
+static bool temporal_inputs_ok(const rt_temporal_inputs* in) {
+    if (!in || !in->d_hits || ((uintptr_t)in->d_hits & 15) || ((uintptr_t)in->d_hist_in & 15)) return false;      // (read as float4)
+    return !in->d_hist_in || (in->d_hits_prev && in->cam_prev && !((uintptr_t)in->d_hits_prev & 15));
+}
+int rt_adaptive_budget_select_temporal(rt_render_ctx* ctx, const void* d_state, const rt_world* world, int max_x, int max_y, const rt_budget* params,
+                                       const rt_temporal_inputs* in, const rt_temporal_params* temporal, int64_t picks, uint32_t* d_list,
+                                       uint32_t* d_count, float* d_keys, void* stream) {
+    FrameCall F; const rt_octree* none = nullptr;
+    const bool params_ok = ctx && world && budget_params_ok(params) && picks >= 0 && picks <= (int64_t)0xffffffffll && !rt_temporal_check(max_x, max_y, temporal);
+    const bool pointers_ok = d_state && d_list && d_count && temporal_inputs_ok(in);
+    const int rc = frame_begin(F, ctx, params_ok, pointers_ok, max_x, max_y, kWhole, nullptr, none, stream, world);
+    if (rc || !F.npx) return rc;
+    rt_render_ctx& C = *F.C;
+    RT_TRY(ctx_reserve_adaptive(C, F.npx, 1));
+    RT_TRY(ctx_reserve_budget(C, F.npx));
+    RT_TRY(ctx_wait_previous(C, F.st));
+    RT_TRY(launch_budget_select_temporal(d_state, in->d_hist_in, in->d_hits, in->d_hits_prev, in->cam_prev, world->z->dev.kind, world->n, max_x, max_y,
+                                         *temporal, params->batch, params->max_spp, params->floor, (unsigned int)std::min(picks, F.npx), C.a_list + F.npx,
+                                         d_keys, C.b_ws, d_list, d_count, F.st));
+    return ctx_mark_done(C, F.st);
+}
 // rt_render_adaptive_spend: `rounds` times — select K_r pixels, seed fb with their sums, `batch` samples for each through the resumed
 // k_render<*, 2, *>, finalise them.  Every round ends with every pixel finalised, so R rounds are R calls of one round.
 static int render_adaptive_spend_common(rt_render_ctx* ctx, void* fb, int max_x, int max_y, const rt_budget* P, const rt_world* world,
                                         rt_rand_state* d_rand_state, const rt_octree* d_octree, int32_t* d_spp, void* d_state, rt_partition part,
                                         uint32_t* d_picked, void* stream, bool filtered = false, const rt_denoise_var_params* filter = nullptr,
-                                        const rt_hit_record* d_hits = nullptr) {
+                                        const rt_hit_record* d_hits = nullptr, bool history = false, const rt_temporal_inputs* tin = nullptr,
+                                        const rt_temporal_params* tpar = nullptr) {
     FrameCall F;
-    const bool params_ok = budget_params_ok(P) && world && !(filtered && rt_denoise_adaptive_check(max_x, max_y, filter));
-    const bool pointers_ok = fb && d_rand_state && d_state && !(filtered && (!d_hits || ((uintptr_t)d_hits & 15)));
+    const bool params_ok = budget_params_ok(P) && world && !(filtered && rt_denoise_adaptive_check(max_x, max_y, filter)) &&
+                           !(history && rt_temporal_check(max_x, max_y, tpar));
+    const bool pointers_ok = fb && d_rand_state && d_state && !(filtered && (!d_hits || ((uintptr_t)d_hits & 15))) && !(history && !temporal_inputs_ok(tin));
     const int rc = frame_begin(F, ctx, params_ok, pointers_ok, max_x, max_y, part, world, d_octree, stream);
     if (rc || !F.npx) return rc;
     rt_render_ctx& C = *F.C; const hipStream_t st = F.st; const int64_t npx = F.npx;
@@ -1252,6 +1284,9 @@ static int render_adaptive_spend_common(rt_render_ctx* ctx, void* fb, int max_x,
         const unsigned int K = (unsigned int)std::min(budget_picks(P, r), npx);
         if (filtered) RT_TRY(launch_budget_select_filtered(S, d_hits, max_x, max_y, *filter, P->batch, P->max_spp, P->floor, K, C.a_list + npx, nullptr,
                                                            C.b_ws, C.a_list, C.a_count, st));
+        else if (history) RT_TRY(launch_budget_select_temporal(d_state, tin->d_hist_in, tin->d_hits, tin->d_hits_prev, tin->cam_prev, world->z->dev.kind,
+                                                               world->n, max_x, max_y, *tpar, P->batch, P->max_spp, P->floor, K, C.a_list + npx, nullptr,
+                                                               C.b_ws, C.a_list, C.a_count, st));
         else RT_TRY(launch_budget_select(S, npx, F.fr, P->batch, P->max_spp, P->floor, K, C.a_list + npx, C.b_ws, C.a_list, C.a_count, st));
         RT_TRY(launch_budget_seed((float*)fb, S, A.ad_list, A.ad_count, K, st));
         RT_TRY(resumed_round(C, A, F.tree, st));
@@ -1284,6 +1319,21 @@ int rt_render_adaptive_spend_filtered_on(rt_render_ctx* ctx, void* fb, int max_x
     if (!ctx) return RT_EINVAL;
     return render_adaptive_spend_common(ctx, fb, max_x, max_y, params, world, d_rand_state, d_octree, d_spp, d_state, kWhole, d_picked,
                                         stream, true, filter, d_hits);
+}
+// ... with the history-aware key: the whole frame (a tile-major part has no neighbours to reproject into); the key is formed anew every
+// round from the current state and the unchanged history of the last frame
+int rt_render_adaptive_spend_temporal(void* fb, int max_x, int max_y, const rt_budget* params, const rt_temporal_inputs* in,
+                                      const rt_temporal_params* temporal, const rt_world* world, rt_rand_state* d_rand_state, const rt_octree* d_octree,
+                                      int32_t* d_spp, void* d_state, uint32_t* d_picked, void* stream) {
+    return render_adaptive_spend_common(nullptr, fb, max_x, max_y, params, world, d_rand_state, d_octree, d_spp, d_state, kWhole, d_picked,
+                                        stream, false, nullptr, nullptr, true, in, temporal);
+}
+int rt_render_adaptive_spend_temporal_on(rt_render_ctx* ctx, void* fb, int max_x, int max_y, const rt_budget* params, const rt_temporal_inputs* in,
+                                         const rt_temporal_params* temporal, const rt_world* world, rt_rand_state* d_rand_state,
+                                         const rt_octree* d_octree, int32_t* d_spp, void* d_state, uint32_t* d_picked, void* stream) {
+    if (!ctx) return RT_EINVAL;
+    return render_adaptive_spend_common(ctx, fb, max_x, max_y, params, world, d_rand_state, d_octree, d_spp, d_state, kWhole, d_picked,
+                                        stream, false, nullptr, nullptr, true, in, temporal);
 }
 
 // the kernel rt_render (mode 0) / rt_render_progressive (mode 1) launches for this world and tree — the library's own

@@ -17,11 +17,17 @@
 // and leaves the other launches as they are.  -DRT_BUDGET_FILTER_UNFUSED (tools/mkvariant.sh): the same keys from the denoiser's own
 // kernels (k_denoise_var_prepare, k_denoise_var_level<false,1>) and a third that only forms the key — the on-device cross-check and the
 // A/B baseline of tools/filtered_budget_study.py.
+// The history-aware budget (rt_adaptive_budget_select_temporal, DESIGN.md §5.9 "History-aware priority") replaces it by
+//   k_budget_keys_temporal   per 16x16 tile, one lane per pixel: what rt_temporal_accumulate would write for the pixel (temporal_pixel of
+//                            rt_temporal.h: the reprojection, four gathered taps, the merge), the key of the merged pixel and the
+//                            histogram of the top digit
+// and again leaves the other launches as they are.
 #include <hip/hip_runtime.h>
 #ifdef RT_BUDGET_SORT
 #include <rocprim/device/device_radix_sort.hpp>
 #endif
 #include "rt_device.h"
+#include "rt_temporal.h"
 
 namespace rt {
 
@@ -505,6 +511,60 @@ hipError_t launch_budget_select_filtered(const AdaptState& s, const rt_hit_recor
     hipLaunchKernelGGL(k_budget_keys_from_level, dim3((unsigned)((n + span - 1) / span)), dim3(256), 0, st, work + n, s, n, span, batch, max_spp, floor_lum,
                        keys, keys_out, hist);
 #endif
+    return budget_select_finish(n, K, keys, ws, list, count, st);
+}
+
+// ---- the history-aware key (rt_amd.h, rt_adaptive_budget_select_temporal) ---------------------------------------------------------
+// Whole row-major frames of at most RT_DENOISE_MAX_PIXELS pixels, as the filtered key.  A block owns `per` consecutive 16x16 tiles (at
+// most kBudgetMaxBlocks blocks: one global add per bin and block), one lane per pixel.  The pixel is ranked by what rt_temporal_accumulate
+// would leave of it: temporal_pixel (rt_temporal.h) is that kernel's own body — the state, both guide halves, the reprojection through
+// the previous camera, the four taps' loads issued before any of them is tested, the merge — so the rule exists once.  The taps go
+// straight through the caches: where a tile lands in the last frame depends on the camera, there is no fixed apron to stage.  A pixel
+// without anything accumulated (neff == 0: EMPTY) keeps the raw key, as in k_budget_keys_filtered.  LDS: the 256-word histogram alone.
+__global__ __launch_bounds__(256) void k_budget_keys_temporal(TemporalArgs T, int tiles, int per, int batch, int max_spp, float floor_lum,
+                                                              unsigned int* __restrict__ keys, float* __restrict__ keys_out, unsigned int* __restrict__ hist) {
+    __shared__ unsigned int sh_hist[256];
+    sh_hist[threadIdx.x] = 0u;
+    __syncthreads();
+    const int li = (int)(threadIdx.x & 15), lj = (int)(threadIdx.x >> 4);
+    const int first = (int)blockIdx.x * per;
+    const int last = first + per < tiles ? first + per : tiles;
+    for (int tile = first; tile < last; ++tile) {
+        const int tx = tile % T.tiles_x, ty = tile / T.tiles_x;
+        const int i = tx * 16 + li, j = ty * 16 + lj;
+        const bool inside = i < T.max_x && j < T.max_y;
+        unsigned int key = 0u;
+        if (inside) {
+            const int p = j * T.max_x + i;
+            const TemporalPixel R = temporal_pixel(T, p);
+            const float pr = R.neff == 0.0f ? adapt_priority(R.sl, R.q, R.k, floor_lum)                       // EMPTY: the raw rule
+                                            : adapt_priority_filtered((R.out.x + R.out.y) + R.out.z, R.out.w, floor_lum);
+            if (keys_out) keys_out[p] = pr;
+            if ((long long)R.k + batch <= (long long)max_spp) key = __float_as_uint(pr);
+            keys[p] = key;
+        }
+        if (hist) budget_hist_add(inside, key >> 24, sh_hist);
+    }
+    __syncthreads();
+    const unsigned int cnt = sh_hist[threadIdx.x];
+    if (hist && cnt) atomicAdd(&hist[threadIdx.x], cnt);
+}
+// launch_budget_select with the history-aware key: the state and guides of a whole row-major frame and the last frame's history, guides
+// and camera (all checked by the caller, as launch_temporal_accumulate's; hist_in == nullptr: the first frame).  keys_out (may be
+// NULL): the key of every pixel before the eligibility mask.  ws: budget_ws_bytes(n, false).
+hipError_t launch_budget_select_temporal(const void* state, const void* hist_in, const rt_hit_record* hits, const rt_hit_record* hits_prev,
+                                         const rt_camera* cam_prev, const int32_t* kind, int n_kind, int max_x, int max_y, const rt_temporal_params& P,
+                                         int batch, int max_spp, float floor_lum, unsigned int K, unsigned int* keys, float* keys_out, unsigned int* ws,
+                                         unsigned int* list, unsigned int* count, hipStream_t st) {
+    const long long n = (long long)max_x * max_y;
+    unsigned int* hist;
+    const hipError_t e = budget_select_begin(ws, hist, st);
+    if (e != hipSuccess) return e;
+    const TemporalArgs T = temporal_args(nullptr, hist_in, hits, hits_prev, cam_prev, state, kind, n_kind, max_x, max_y, P);
+    const int tiles = T.tiles_x * ((max_y + 15) / 16);                // (<= 2^30 / 256 + two edges: fits)
+    const int per = (tiles + kBudgetMaxBlocks - 1) / kBudgetMaxBlocks;
+    const unsigned nblk = (unsigned)((tiles + per - 1) / per);        // <= kBudgetMaxBlocks, every block owns at least one tile
+    hipLaunchKernelGGL(k_budget_keys_temporal, dim3(nblk), dim3(256), 0, st, T, tiles, per, batch, max_spp, floor_lum, keys, keys_out, hist);
     return budget_select_finish(n, K, keys, ws, list, count, st);
 }
 

@@ -17,6 +17,7 @@
 #include <hip/hip_runtime.h>
 #include "../../include/rt_amd.h"
 #include "rt_device.h"
+#include "rt_temporal.h"
 
 #pragma clang fp contract(off)
 
@@ -25,101 +26,15 @@ namespace rt {
 hipError_t launch_denoise_var_levels(float* fb_out, int max_x, int max_y, const rt_hit_record* hits, const rt_denoise_var_params& P, float4* work,
                                      hipStream_t st);      // rt_denoise.hip
 
-struct TemporalArgs {
-    float4* out; float* neff_out;             // this frame's history: float4 [n], then float [n]
-    const float4* in; const float* neff_in;   // the last frame's (in == nullptr: none is asked)
-    const float4* g; const float4* g_prev;    // guide records as 16-byte halves: (t, P), (N, sphere)
-    AdaptState S;
-    const int32_t* kind; int32_t n_kind;      // RT_MAT_* of the world list
-    int32_t max_x, max_y, tiles_x;
-    int32_t reuse_specular;
-    float max_history;                        // (float)params->max_history
-    float tol2, min_dot;                      // position_tolerance^2 (rounded once on the host), normal_min_dot
-    rt_camera cam;                            // the camera of the frame that wrote `in`
-};
-
-__device__ inline float dot3(float ax, float ay, float az, float bx, float by, float bz) { return (ax * bx + ay * by) + az * bz; }
-
+// the rule itself is temporal_pixel (rt_temporal.h), shared with the history-aware budget key (k_budget_keys_temporal, rt_budget.hip)
 __global__ __launch_bounds__(256) void k_temporal_accumulate(TemporalArgs T) {
     const int tx = (int)(blockIdx.x % (unsigned)T.tiles_x), ty = (int)(blockIdx.x / (unsigned)T.tiles_x);
     const int i = tx * 16 + (int)(threadIdx.x & 15), j = ty * 16 + (int)(threadIdx.x >> 4);
     if (i >= T.max_x || j >= T.max_y) return;
-    const int p = j * T.max_x + i;                                           // (n <= 2^30: p and the guide index 2 * p + 1 fit an int)
-    const long long e = 3 * (long long)p;                                    // (3 * p does not: 64-bit colour offsets)
-    // this frame's values: the "per pixel" line of rt_denoise_adaptive
-    const int k = T.S.k[p];
-    const float nf = (float)k;
-    float4 c;
-    c.x = T.S.rgb[e] / nf; c.y = T.S.rgb[e + 1] / nf; c.z = T.S.rgb[e + 2] / nf;
-    const float sl = T.S.sl[p];
-    float d = nf * T.S.q[p] - sl * sl;
-    d = d > 0.0f ? d : 0.0f;
-    c.w = d / ((nf * nf) * (nf - 1.0f));
-    const float4 gp0 = T.g[2 * p], gp1 = T.g[2 * p + 1];
-    const int sp = __float_as_int(gp1.w);
-    float4 out = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
-    float neff = 0.0f;
-    const bool empty = sp == -1 || k < 2 || !__builtin_isfinite(c.x) || !__builtin_isfinite(c.y) || !__builtin_isfinite(c.z) || !__builtin_isfinite(c.w);
-    if (!empty) {
-        out = c;
-        neff = nf;
-        bool ask = T.in != nullptr && T.max_history != 0.0f;
-        if (ask && !T.reuse_specular) ask = (unsigned)sp < (unsigned)T.n_kind && T.kind[sp] == RT_MAT_LAMBERTIAN;
-        if (ask) {
-            // where the point was seen before: the pinhole inverse of get_ray on the previous camera
-            const float* O = T.cam.origin; const float* LL = T.cam.lower_left_corner; const float* H = T.cam.horizontal; const float* V = T.cam.vertical;
-            const float Ax = LL[0] - O[0], Ay = LL[1] - O[1], Az = LL[2] - O[2];
-            const float Dx = gp0.y - O[0], Dy = gp0.z - O[1], Dz = gp0.w - O[2];
-            const float Wx = H[1] * V[2] - H[2] * V[1], Wy = H[2] * V[0] - H[0] * V[2], Wz = H[0] * V[1] - H[1] * V[0];
-            const float lam = dot3(Dx, Dy, Dz, Wx, Wy, Wz) / dot3(Ax, Ay, Az, Wx, Wy, Wz);
-            const float s = (dot3(Dx, Dy, Dz, H[0], H[1], H[2]) / lam - dot3(Ax, Ay, Az, H[0], H[1], H[2])) / dot3(H[0], H[1], H[2], H[0], H[1], H[2]);
-            const float t = (dot3(Dx, Dy, Dz, V[0], V[1], V[2]) / lam - dot3(Ax, Ay, Az, V[0], V[1], V[2])) / dot3(V[0], V[1], V[2], V[0], V[1], V[2]);
-            const float mx = (float)T.max_x, my = (float)T.max_y;
-            const float fx = s * mx - 0.5f, fy = t * my - 0.5f;
-            if (lam > 0.0f && fx > -1.0f && fx < mx && fy > -1.0f && fy < my) {          // (a NaN rejects)
-                const int i0 = (int)floorf(fx), j0 = (int)floorf(fy);                    // -1 .. max - 1
-                const float ax = fx - (float)i0, ay = fy - (float)j0;
-                const float lim = T.tol2 * (gp0.x * gp0.x);
-                // the four taps, b outer: every load first (indices clamped into the frame), then the tests
-                float nq[4]; float4 gq0[4], gq1[4], xq[4]; bool in[4];
-#pragma unroll
-                for (int u = 0; u < 4; ++u) {
-                    const int qi = i0 + (u & 1), qj = j0 + (u >> 1);
-                    in[u] = qi >= 0 && qi < T.max_x && qj >= 0 && qj < T.max_y;
-                    const int ci = qi < 0 ? 0 : (qi >= T.max_x ? T.max_x - 1 : qi), cj = qj < 0 ? 0 : (qj >= T.max_y ? T.max_y - 1 : qj);
-                    const int q = cj * T.max_x + ci;
-                    nq[u] = T.neff_in[q];
-                    gq1[u] = T.g_prev[2 * q + 1];
-                    gq0[u] = T.g_prev[2 * q];
-                    xq[u] = T.in[q];
-                }
-                float sg = 0.0f, s0 = 0.0f, s1 = 0.0f, s2 = 0.0f, s3 = 0.0f, s4 = 0.0f;
-#pragma unroll
-                for (int u = 0; u < 4; ++u) {
-                    if (!in[u] || !(nq[u] > 0.0f)) continue;                             // outside the frame; an empty pixel of the last frame
-                    if (__float_as_int(gq1[u].w) != sp) continue;                        // another sphere
-                    if (!(dot3(gp1.x, gp1.y, gp1.z, gq1[u].x, gq1[u].y, gq1[u].z) >= T.min_dot)) continue;
-                    const float ex = gp0.y - gq0[u].y, ey = gp0.z - gq0[u].z, ez = gp0.w - gq0[u].w;
-                    if (!(((ex * ex + ey * ey) + ez * ez) <= lim)) continue;
-                    const float g = ((u & 1) ? ax : 1.0f - ax) * ((u >> 1) ? ay : 1.0f - ay);
-                    sg = sg + g;
-                    s0 = s0 + g * xq[u].x; s1 = s1 + g * xq[u].y; s2 = s2 + g * xq[u].z;
-                    s3 = s3 + g * xq[u].w;
-                    s4 = s4 + g * nq[u];
-                }
-                if (sg > 0.0f) {
-                    const float hx = s0 / sg, hy = s1 / sg, hz = s2 / sg, hv = s3 / sg, hn = s4 / sg;
-                    const float m = hn < T.max_history ? hn : T.max_history;
-                    const float a = nf / (m + nf);
-                    out.x = hx + a * (c.x - hx); out.y = hy + a * (c.y - hy); out.z = hz + a * (c.z - hz);
-                    out.w = ((1.0f - a) * (1.0f - a)) * hv + (a * a) * c.w;
-                    neff = m + nf;
-                }
-            }
-        }
-    }
-    T.out[p] = out;
-    T.neff_out[p] = neff;
+    const int p = j * T.max_x + i;                                           // (n <= 2^30: p fits an int)
+    const TemporalPixel R = temporal_pixel(T, p);
+    T.out[p] = R.out;
+    T.neff_out[p] = R.neff;
 }
 
 // the arguments have been checked by rt_temporal_accumulate (rt_api.hip): 16-byte aligned histories and guides, max_x * max_y <= 2^30,
@@ -127,19 +42,7 @@ __global__ __launch_bounds__(256) void k_temporal_accumulate(TemporalArgs T) {
 hipError_t launch_temporal_accumulate(void* hist_out, const void* hist_in, const rt_hit_record* hits, const rt_hit_record* hits_prev,
                                       const rt_camera* cam_prev, const void* state, const int32_t* kind, int n_kind, int max_x, int max_y,
                                       const rt_temporal_params& P, hipStream_t st) {
-    const long long n = (long long)max_x * max_y;
-    TemporalArgs T;
-    T.out = (float4*)hist_out; T.neff_out = (float*)(T.out + n);
-    T.in = (const float4*)hist_in; T.neff_in = hist_in ? (const float*)(T.in + n) : nullptr;
-    T.g = (const float4*)hits; T.g_prev = (const float4*)hits_prev;
-    T.S = adapt_state(const_cast<void*>(state), n);
-    T.kind = kind; T.n_kind = n_kind;
-    T.max_x = max_x; T.max_y = max_y; T.tiles_x = (max_x + 15) / 16;
-    T.reuse_specular = P.reuse_specular;
-    T.max_history = (float)P.max_history;
-    T.tol2 = P.position_tolerance * P.position_tolerance;
-    T.min_dot = P.normal_min_dot;
-    if (hist_in) T.cam = *cam_prev; else T.cam = rt_camera{};
+    const TemporalArgs T = temporal_args(hist_out, hist_in, hits, hits_prev, cam_prev, state, kind, n_kind, max_x, max_y, P);
     const unsigned blocks = (unsigned)T.tiles_x * (unsigned)((max_y + 15) / 16);
     hipLaunchKernelGGL(k_temporal_accumulate, dim3(blocks), dim3(256), 0, st, T);
     return hipGetLastError();

@@ -116,6 +116,24 @@ def temporal_params(**kw):
     return TemporalParams(p["max_history"], p["reuse_specular"], p["position_tolerance"], p["normal_min_dot"])
 
 
+class TemporalInputs(C.Structure):
+    """rt_temporal_inputs: what temporal_accumulate takes besides the state and the world — the last frame's history (NULL: the first
+    frame), this frame's guides, the last frame's guides and camera (a host pointer); build one with temporal_inputs()"""
+    _fields_ = [("d_hist_in", C.c_void_p), ("d_hits", C.c_void_p), ("d_hits_prev", C.c_void_p), ("cam_prev", C.c_void_p)]
+
+
+def temporal_inputs(d_hits, d_hist_in=None, d_hits_prev=None, cam_prev=None):
+    """a TemporalInputs from device tensors (or raw ints) and the last frame's camera (a camera_dtype array); the result keeps the
+    tensors and a copy of the camera alive.  d_hist_in None marks the first frame"""
+    ptr = lambda t: None if t is None else (t if isinstance(t, int) else t.data_ptr())
+    t = TemporalInputs(ptr(d_hist_in), ptr(d_hits), ptr(d_hits_prev), None)
+    t._keep = (d_hits, d_hist_in, d_hits_prev)
+    if cam_prev is not None:
+        t._cam = np.ascontiguousarray(cam_prev, camera_dtype).reshape(1).copy()
+        t.cam_prev = t._cam.ctypes.data
+    return t
+
+
 class LevelsParams(C.Structure):
     """rt_levels_params: input mode (DENOISE_INPUT_*), the progressive sample count (SUM), the output format (LEVELS_*) and top_first
     (1 = the PPM's row order, 0 = the framebuffer's); include/rt_amd.h states the quantisation"""
@@ -230,6 +248,12 @@ SYMBOLS = {
     "rt_adaptive_budget_select_filtered": (_i, [_vp, _vp, _vp, _i, _i, C.POINTER(Budget), C.POINTER(DenoiseVarParams), _i64, _vp, _vp, _vp, _vp]),
     "rt_render_adaptive_spend_filtered": (_i, [_vp, _i, _i, C.POINTER(Budget), C.POINTER(DenoiseVarParams), _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "rt_render_adaptive_spend_filtered_on": (_i, [_vp, _vp, _i, _i, C.POINTER(Budget), C.POINTER(DenoiseVarParams), _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "rt_adaptive_budget_select_temporal": (_i, [_vp, _vp, _vp, _i, _i, C.POINTER(Budget), C.POINTER(TemporalInputs), C.POINTER(TemporalParams), _i64,
+                                                _vp, _vp, _vp, _vp]),
+    "rt_render_adaptive_spend_temporal": (_i, [_vp, _i, _i, C.POINTER(Budget), C.POINTER(TemporalInputs), C.POINTER(TemporalParams), _vp, _vp, _vp, _vp,
+                                               _vp, _vp, _vp]),
+    "rt_render_adaptive_spend_temporal_on": (_i, [_vp, _vp, _i, _i, C.POINTER(Budget), C.POINTER(TemporalInputs), C.POINTER(TemporalParams), _vp, _vp, _vp,
+                                                  _vp, _vp, _vp, _vp]),
     "rt_frame_levels": (_i, [_vp, _vp, _i, _i, _i, C.POINTER(LevelsParams), _vp]),
     "rt_frame_levels_check": (_i, [_i, _i, _i, C.POINTER(LevelsParams)]),
     "rt_frame_levels_bytes": (_i64, [_i, _i, _i]),
@@ -369,6 +393,25 @@ class RenderCtx:
         check(lib().rt_adaptive_budget_select_filtered(self.h, _dev(d_state), _dev(d_hits), max_x, max_y, C.byref(params), C.byref(filter), picks,
                                                        _dev(d_list), _dev(d_count), _dev(d_keys) if d_keys is not None else None,
                                                        C.c_void_p(stream) if stream is not None else _stream()), "rt_adaptive_budget_select_filtered")
+
+    def render_adaptive_spend_temporal(self, fb, max_x, max_y, params, inputs, temporal, world, d_rand_state, d_state, octree=None, d_spp=None,
+                                       d_picked=None, stream=None):
+        """rt_render_adaptive_spend_temporal_on: the spend ranked by the error left after temporal_accumulate's merge (whole frames);
+        inputs is a TemporalInputs (temporal_inputs()), temporal the TemporalParams the history is kept with"""
+        check(lib().rt_render_adaptive_spend_temporal_on(self.h, _dev(fb), max_x, max_y, C.byref(params), C.byref(inputs), C.byref(temporal), world.h,
+                                                         _dev(d_rand_state), octree.h if octree is not None else None,
+                                                         _dev(d_spp) if d_spp is not None else None, _dev(d_state),
+                                                         _dev(d_picked) if d_picked is not None else None,
+                                                         C.c_void_p(stream) if stream is not None else _stream()), "rt_render_adaptive_spend_temporal_on")
+
+    def adaptive_budget_select_temporal(self, d_state, world, max_x, max_y, params, inputs, temporal, picks, d_list, d_count, d_keys=None,
+                                        stream=None):
+        """rt_adaptive_budget_select_temporal: adaptive_budget_select with the history-aware key; d_keys (optional, float32 per pixel)
+        receives every pixel's key before the eligibility mask"""
+        check(lib().rt_adaptive_budget_select_temporal(self.h, _dev(d_state), world.h, max_x, max_y, C.byref(params), C.byref(inputs),
+                                                       C.byref(temporal), picks, _dev(d_list), _dev(d_count),
+                                                       _dev(d_keys) if d_keys is not None else None,
+                                                       C.c_void_p(stream) if stream is not None else _stream()), "rt_adaptive_budget_select_temporal")
 
     def times(self):
         out = np.zeros(64, np.float32)
@@ -784,6 +827,21 @@ def render_adaptive_spend_filtered(fb, max_x, max_y, params, filter, d_hits, wor
     check(lib().rt_render_adaptive_spend_filtered(_dev(fb), max_x, max_y, C.byref(params), C.byref(filter), _dev(d_hits), world.h, _dev(d_rand_state),
                                                   octree.h if octree is not None else None, _dev(d_spp) if d_spp is not None else None, _dev(d_state),
                                                   _dev(d_picked) if d_picked is not None else None, _stream()), "rt_render_adaptive_spend_filtered")
+
+
+def adaptive_budget_select_temporal(ctx, d_state, world, max_x, max_y, params, inputs, temporal, picks, d_list, d_count, d_keys=None):
+    """rt_adaptive_budget_select_temporal on the current stream, with the workspace of the RenderCtx `ctx`"""
+    ctx.adaptive_budget_select_temporal(d_state, world, max_x, max_y, params, inputs, temporal, picks, d_list, d_count, d_keys)
+
+
+def render_adaptive_spend_temporal(fb, max_x, max_y, params, inputs, temporal, world, d_rand_state, d_state, octree=None, d_spp=None, d_picked=None):
+    """rt_render_adaptive_spend_temporal on the current stream: render_adaptive_spend with the pixels ranked by the error that is left
+    after temporal_accumulate merged them with the last frame's history (inputs: temporal_inputs(), temporal: its TemporalParams); fb
+    stays unfiltered and the history is only read — run temporal_accumulate after the spend"""
+    check(lib().rt_render_adaptive_spend_temporal(_dev(fb), max_x, max_y, C.byref(params), C.byref(inputs), C.byref(temporal), world.h,
+                                                  _dev(d_rand_state), octree.h if octree is not None else None,
+                                                  _dev(d_spp) if d_spp is not None else None, _dev(d_state),
+                                                  _dev(d_picked) if d_picked is not None else None, _stream()), "rt_render_adaptive_spend_temporal")
 
 
 def assemble(fb_full, fb_parts, max_x, max_y, nparts, precision=FP32):

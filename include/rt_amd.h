@@ -676,6 +676,52 @@ int rt_render_adaptive_spend_filtered_on(rt_render_ctx* ctx, void* fb, int max_x
                                          rt_rand_state* d_rand_state, const rt_octree* d_octree, int32_t* d_spp, void* d_state, uint32_t* d_picked,
                                          void* stream);
 
+/* History-aware budgets: the same selection and the same rounds with a third priority — the relative variance of the pixel AFTER
+ * rt_temporal_accumulate's merge with the last frame's history, for viewers that accumulate over frames: samples go where the history
+ * is thin (a disoccluded pixel, a pixel whose taps were refused, a specular first hit with reuse_specular = 0) and not where it
+ * already holds max_history samples (DESIGN.md §5.9 "History-aware priority").  Whole frames only, row-major, fp32 worlds, at most
+ * RT_DENOISE_MAX_PIXELS pixels; the state is that of part = {0, 1, 0, 0}.  rt_temporal_inputs is what rt_temporal_accumulate takes
+ * besides the state and the world: this frame's guides, and the history, guides and camera of the last frame; `temporal` its
+ * parameters; the world supplies kind[sphere] only.  IEEE binary32, one rounding per operation, no contraction
+ * (tests/temporal_budget_model.py is the model, bit for bit):
+ *   merged pixel:    (x.r, x.g, x.b, v) and neff are exactly what rt_temporal_accumulate would write for the pixel with these inputs,
+ *                    bit for bit — its EMPTY rule, "asked at all", the reprojection, the four taps and the merge, none restated here.
+ *   neff == 0:       (EMPTY) key = rt_adaptive_priority(SL, Q, k, floor), the raw rule: rt_temporal_accumulate and rt_denoise_history
+ *                    leave such a pixel as it is.
+ *   otherwise:       l = (x.r + x.g) + x.b;  key = rt_adaptive_priority_filtered(l, v, floor).
+ * Eligibility (k + batch <= max_spp, key > 0), the ordering, ties by the lower pixel id, K_r and "only the set is defined" are those
+ * of rt_adaptive_budget_select.  What follows: with d_hist_in == NULL or max_history == 0 the key of a non-empty pixel is
+ * rt_adaptive_priority_filtered on this frame's own (x_c, v_c) — the same quantity as the raw key, but not its bits (other operations,
+ * other roundings), so the set may differ from rt_adaptive_budget_select's at the cut; with reuse_specular = 0 a specular first hit is
+ * ranked by this frame alone.  A pixel that took history at weight a = n / (m + n) has v = (1 - a)^2 v_h + a^2 v_c. */
+typedef struct rt_temporal_inputs {      /* what rt_temporal_accumulate takes besides the state and the world; POD */
+    const void* d_hist_in;               /* NULL = first frame (d_hits_prev, cam_prev may then be NULL) */
+    const rt_hit_record* d_hits;         /* this frame's guides */
+    const rt_hit_record* d_hits_prev;
+    const rt_camera* cam_prev;           /* host, passed by value to the kernel */
+} rt_temporal_inputs;
+/* rt_adaptive_budget_select with that key.  d_keys (device, may be NULL) receives one float per pixel: the key above, before the
+ * eligibility mask — the map of where the accumulated frame is still noisy.  Errors in the order of rt_adaptive_budget_select:
+ * RT_EINVAL for its own refusals, a NULL world, in or temporal, whatever rt_temporal_check(max_x, max_y, temporal) refuses, NULL or
+ * 16-byte-misaligned guides or history and a d_hist_in without d_hits_prev or cam_prev; then RT_ENOTSUP for a USE_FP16 world (a
+ * contracted world is accepted: nothing is rendered); RT_EINVAL on a capturing stream.  The world is uploaded if need be. */
+int rt_adaptive_budget_select_temporal(rt_render_ctx* ctx, const void* d_state, const rt_world* world, int max_x, int max_y,
+                                       const rt_budget* params, const rt_temporal_inputs* in, const rt_temporal_params* temporal,
+                                       int64_t picks, uint32_t* d_list, uint32_t* d_count, float* d_keys, void* stream);
+/* rt_render_adaptive_spend with that key: the same round, the selection's key kernel exchanged, nothing else.  The key is formed anew
+ * every round from the current state and the unchanged history of the last frame.  A state may be continued by any of the three
+ * spends in any order; every statement of rt_render_adaptive_spend holds (rounds compose, every round ends finalised, a pixel at k
+ * samples holds what rt_render with ns = k gives it).  fb stays unfiltered and d_hist_in is only read: the caller runs
+ * rt_temporal_accumulate after the spend for the history it keeps.  Errors as for rt_render_adaptive_spend, and RT_EINVAL for the
+ * checks named above (with the parameter checks, before RT_ENOTSUP for USE_FP16 and RT_ARITH_CONTRACT worlds). */
+int rt_render_adaptive_spend_temporal(void* fb, int max_x, int max_y, const rt_budget* params, const rt_temporal_inputs* in,
+                                      const rt_temporal_params* temporal, const rt_world* world, rt_rand_state* d_rand_state,
+                                      const rt_octree* d_octree, int32_t* d_spp, void* d_state, uint32_t* d_picked, void* stream);
+int rt_render_adaptive_spend_temporal_on(rt_render_ctx* ctx, void* fb, int max_x, int max_y, const rt_budget* params,
+                                         const rt_temporal_inputs* in, const rt_temporal_params* temporal, const rt_world* world,
+                                         rt_rand_state* d_rand_state, const rt_octree* d_octree, int32_t* d_spp, void* d_state,
+                                         uint32_t* d_picked, void* stream);
+
 /* ---- the image end on the device: 8-bit levels and frame comparison (no reference counterpart) ------------
  * What main.cu:321-333 and evaluations.ipynb:1021-1027 do on the host — quantise a frame, grey it, SSIM / PSNR — for frames that stay
  * on the device.  Frames are in the reference's row-major layout (pixel_index = j*max_x + i, row 0 at the bottom), at most
