@@ -454,6 +454,12 @@ struct WalkLds {
     uint4 cq[kWalkCand];                 // candidates: (bits of b, bits of disc, entry, owner)
     unsigned count, tie_lo, tie_hi, pad_;
 };
+// A thin round (walk_pool, at most kThinWalkers walkers) keeps its walkers' records in `pref` — per walker of rank k two uint4: (lane, next
+// column, step, end column) (bits of om_c, on_c, slope; grid offset) — and deals its entries out through `seg`: slot j = (entry, owner).
+constexpr int kThinWalkers = 16, kThinCols = 4;
+static_assert(kThinWalkers * kThinCols == 64, "a thin round: one lane per (walker, column)");
+static_assert(kThinCols == RT_POOL_COLS_THIN, "a thin round takes the columns a round of few walkers took before it");
+static_assert(sizeof(unsigned) * kWalkPool >= sizeof(uint4) * 2 * kThinWalkers && sizeof(uint2) * kWalkPool >= sizeof(uint2) * 64, "the thin round's records and slots live in pref and seg");
 struct PoolSpan { unsigned cur, end, seg_end, base, sg; int owner; RayF q; float a, abt, atm; };      // a lane's walk through one span of the pool
 RT_DEV void walk_sync() { __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront"); __builtin_amdgcn_wave_barrier(); }
 // exclusive prefix sum over the 64 lanes: row_shr 1/2/4/8 (a row of 16), then row_bcast 15 and 31 — six DPP adds, no LDS
@@ -470,12 +476,10 @@ RT_DEV unsigned walk_excl_scan(unsigned v, unsigned& total) {
 }
 
 // one queued candidate: sphere.h:24-43's offer, eligibility as in `offer`, merged into the owner's key
-RT_DEV void pool_candidate_b(const DevTree& T, const float4* s_nodes, WalkLds& L, const uint4 c, const float4 blo, const float4 bhi STAT_ARG) {
+// (q, a: the owner's ray and |d|^2 — a direct round holds them in registers, the queue's candidates fetch them from L.ray)
+RT_DEV void pool_candidate_b(const DevTree& T, const float4* s_nodes, WalkLds& L, const uint4 c, const RayF& q, const float a, const float4 blo, const float4 bhi STAT_ARG) {
     const int owner = (int)c.w;
     const float b = __uint_as_float(c.x), disc = __uint_as_float(c.y);
-    const float4 r0 = L.ray[2 * owner], r1 = L.ray[2 * owner + 1];
-    RayF q; q.o = {r0.x, r0.y, r0.z}; q.d = {r0.w, r1.x, r1.y};
-    const float a = r1.z;
     const unsigned long long k0 = L.key[owner];
     const float best_t = __uint_as_float((unsigned)(k0 >> 32));
     const int best = (int)(unsigned)k0;
@@ -511,7 +515,9 @@ RT_DEV void pool_candidate(const DevTree& T, const float4* s_nodes, WalkLds& L, 
     // cannot win has fetched it for nothing, a chain alone in its wave has one dependent round trip less per candidate)
     const int e = (int)c.z;
     const float4 blo = T.acc.brick[2 * e], bhi = T.acc.brick[2 * e + 1];
-    pool_candidate_b(T, s_nodes, L, c, blo, bhi STAT_PASS);
+    const float4 r0 = L.ray[2 * c.w], r1 = L.ray[2 * c.w + 1];
+    RayF q; q.o = {r0.x, r0.y, r0.z}; q.d = {r0.w, r1.x, r1.y};
+    pool_candidate_b(T, s_nodes, L, c, q, r1.z, blo, bhi STAT_PASS);
 }
 
 RT_DEV void pool_drain(const DevTree& T, const float4* s_nodes, WalkLds& L, int lane, unsigned& qn STAT_ARG) {
@@ -539,13 +545,103 @@ RT_DEV void walk_pool(const DevTree& T, const float4* s_nodes, WalkLds& L, const
     const float f_atm = a * (0.001f * 0.9999f - 1e-6f);
     bool walking = W.walking && W.i != W.iend;
     const int nw0 = __popcll(__ballot(walking));
+    const bool thin_round = RT_POOL_THIN_ROUND && nw0 <= kThinWalkers;      // (walkers only leave: every round of this call has at most 16)
     L.ray[2 * lane] = make_float4(r.o.x, r.o.y, r.o.z, r.d.x);
     while (true) {
         // ---- this lane's state for whoever tests its spheres; pool and flags cleared
         L.ray[2 * lane + 1] = make_float4(r.d.y, r.d.z, a, __builtin_fmaf(a * best_t, 1.0001f, 1e-6f * a));
         L.key[lane] = ((unsigned long long)__float_as_uint(best_t) << 32) | (unsigned)best;
         if (lane == 0) { L.tie_lo = 0u; L.tie_hi = 0u; }
+        const unsigned long long wmask = __ballot(walking);
+        if (thin_round && walking) {
+            const unsigned rank = __builtin_amdgcn_mbcnt_hi((unsigned)(wmask >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)wmask, 0u));
+            uint4* rec = (uint4*)L.pref;
+            rec[2 * rank] = make_uint4((unsigned)lane, (unsigned)W.i, (unsigned)step, (unsigned)W.iend);
+            rec[2 * rank + 1] = make_uint4(__float_as_uint(W.om_c), __float_as_uint(W.on_c), __float_as_uint(W.slope), (unsigned)W.coff);
+        }
         walk_sync();
+        unsigned n_seg = 0u;                                         // (<= 64 x RT_POOL_COLS: the pool cannot overflow)
+        bool picked = false;                                         // a round that tested entries: the owners pick up their keys
+        bool dealt = false;                                          // the thin round has done the round's tests itself
+        if (thin_round) {
+            // ---- a thin round (at most 16 walkers entered: a thin wave's chains — the frame's critical path — or a drained wave): lane l
+            // forms column (l & 3) of the walker of rank (l >> 2) — phase 1 once, wave-wide, instead of four unrolled copies per walker —
+            // and every range's lane writes its entries into consecutive slots: the testing lane reads its slot, no prefix table, no search
+            const int nwr = __popcll(wmask);
+            const int wk = lane >> 2, c = lane & 3;
+            int f0 = 0; unsigned cnt = 0u;                           // the column's first entry and its count
+            if (wk < nwr) {
+                const uint4* rec = (const uint4*)L.pref;
+                const uint4 ra = rec[2 * wk], rb = rec[2 * wk + 1];
+                const int wstep = (int)ra.z;
+                if (c < ((int)ra.w - (int)ra.y) * wstep) {           // (columns left: a column at or beyond the end is empty)
+                    const int wi = (int)ra.y + c * wstep;
+                    const float w_om = __uint_as_float(rb.x), w_on = __uint_as_float(rb.y), w_slope = __uint_as_float(rb.z);
+                    const float u0 = w_on + ((float)wi - w_om) * w_slope, u1 = u0 + w_slope;          // the line at the column's two edges
+                    const float lo = (fminf(u0, u1) - q_c) * fF, hi = (fmaxf(u0, u1) + q_c) * fF;      // in fine bins (F is a power of two)
+                    if (hi >= 0.0f && lo < fGf) {
+                        const int k0 = (int)fmaxf(lo, 0.0f), k1 = (int)fminf(hi, fGfm);
+                        const unsigned cbase = (unsigned)((int)rb.w + wi * Gf);
+                        const int a0 = cs[cbase + (unsigned)k0], a1 = cs[cbase + (unsigned)k1 + 1u];
+                        if (a1 > a0) { f0 = a0; cnt = (unsigned)(a1 - a0); }
+                    }
+                }
+            }
+            // the owner steps past the columns taken; its four lanes' counts come back to it (two quad adds, one lane read)
+            int qs = (int)cnt;
+            qs += __builtin_amdgcn_update_dpp(0, qs, 0xB1, 0xf, 0xf, false);     // quad_perm:[1,0,3,2]
+            qs += __builtin_amdgcn_update_dpp(0, qs, 0x4E, 0xf, 0xf, false);     // quad_perm:[2,3,0,1]
+            const unsigned rank = __builtin_amdgcn_mbcnt_hi((unsigned)(wmask >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)wmask, 0u));
+            const int mywork = __builtin_amdgcn_ds_bpermute((int)((rank & 15u) << 4), qs);            // from lane 4 x rank
+            if (walking) {
+                const int taken = min(kThinCols, (W.iend - W.i) * step);
+                STAT(st, ST_COLS, taken);
+                W.i += taken * step; W.cols += (unsigned)taken; W.work += (unsigned)mywork;
+            }
+            unsigned total;
+            const unsigned ex = walk_excl_scan(cnt, total);
+            RT_STATS_ONLY(n_seg = (unsigned)__popcll(__ballot(cnt != 0u)); TRSTAT_ROUND(lane, n_seg, total); n_seg = 0u;)
+            if (total <= 64u) {
+                dealt = true;
+                if (total != 0u) {
+                    picked = true;
+                    uint2* slot = (uint2*)L.seg;
+                    // (the owner's lane is read again here, not kept from phase 1: a register less across the scan, and k_render<true,1,5> stays without scratch)
+#pragma nounroll
+                    for (unsigned t = 0u; t < cnt; ++t) slot[ex + t] = make_uint2((unsigned)f0 + t, L.pref[8 * wk]);
+                    walk_sync();
+                    const bool act = (unsigned)lane < total;
+                    STAT(st, ST_A_ITERS_WAVE, 1);
+                    unsigned he = 0u; int owner = 0;
+                    if (act) { const uint2 sl = slot[lane]; he = sl.x; owner = (int)sl.y; }
+                    const float4 r0 = L.ray[2 * owner], r1 = L.ray[2 * owner + 1];
+                    const float4 s4 = hot[he], blo = A.brick[2 * he], bhi = A.brick[2 * he + 1];
+                    RayF q; q.o = {r0.x, r0.y, r0.z}; q.d = {r0.w, r1.x, r1.y};
+                    const float qa = r1.z, abt = r1.w, atm = qa * (0.001f * 0.9999f - 1e-6f);
+                    STAT(st, ST_TESTS, act ? 1 : 0); STAT(st, ST_A_LANE_STEPS, act ? 1 : 0);
+                    const float ocx = q.o.x - s4.x, ocy = q.o.y - s4.y, ocz = q.o.z - s4.z;
+                    const float b = ocx * q.d.x + ocy * q.d.y + ocz * q.d.z;
+                    const float cc = (ocx * ocx + ocy * ocy + ocz * ocz) - s4.w;
+                    const float disc = b * b - qa * cc;
+                    const float ab = fabsf(b);
+                    const float Lm = __builtin_fmaf(ab, -1e-4f, -b) - abt, M = __builtin_fmaf(ab, -1e-4f, b) + atm;
+                    const float P = fmaxf(Lm, M);
+                    if (act && disc > 0.0f && !(P > 0.0f && P * P > disc * 1.0003f)) {
+                        STAT(st, ST_DISCPOS, 1);
+                        pool_candidate_b(T, s_nodes, L, make_uint4(__float_as_uint(b), __float_as_uint(disc), he, (unsigned)owner), q, qa, blo, bhi STAT_PASS);
+                    }
+                    walk_sync();
+                }
+            } else {
+                // more than one entry per lane: the non-empty ranges, compacted, go to the generic loop in its own layout (the records in
+                // `pref` are read: phase 2 below may overwrite them after the fence)
+                const bool has = cnt != 0u;
+                const unsigned long long m = __ballot(has);
+                if (has) L.seg[__builtin_amdgcn_mbcnt_hi((unsigned)(m >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)m, 0u))] = make_uint2((unsigned)f0, cnt | (L.pref[8 * wk] << 26));
+                n_seg = (unsigned)__popcll(m);
+                walk_sync();
+            }
+        } else {
         // ---- phase 1: the entry ranges of the next RT_POOL_COLS columns of every walking lane (their cell-start loads in flight together)
         // (a wave with few walkers — a thin wave's chains, the frame's critical path — takes RT_POOL_COLS_THIN columns per round: as
         // many cell-start loads in flight, fewer rounds and their dependent round trips; the pool holds 64 x RT_POOL_COLS ranges)
@@ -566,7 +662,6 @@ RT_DEV void walk_pool(const DevTree& T, const float4* s_nodes, WalkLds& L, const
                 W.i += step; ++W.cols;
             }
         }
-        unsigned n_seg = 0u;                                         // (<= 64 x RT_POOL_COLS: the pool cannot overflow)
 #pragma unroll
         for (int c = 0; c < RT_POOL_COLS_THIN; ++c) {
             if (c >= RT_POOL_COLS && c >= cols_now) break;          // (wave-uniform)
@@ -580,13 +675,17 @@ RT_DEV void walk_pool(const DevTree& T, const float4* s_nodes, WalkLds& L, const
             n_seg += (unsigned)__popcll(m);
         }
         walk_sync();
-        if (n_seg != 0u) {
+        RT_STATS_ONLY(if (nw0 <= kThinWalkers && n_seg == 0u) TRSTAT_ROUND(lane, 0u, 0u);)
+        }
+        if (!dealt && n_seg != 0u) {
+            picked = true;
             // ---- phase 2: prefix of the ranges, an equal span of the concatenated entries per lane
             unsigned total = 0u;
             {
                 unsigned run = 0u;
 #pragma unroll
                 for (int k = 0; k < RT_POOL_COLS; ++k) {
+                    if (k > 0 && n_seg <= 64u * (unsigned)k) break;          // (wave-uniform: nothing left to count)
                     const unsigned sidx = (unsigned)(k * 64 + lane);
                     const unsigned cnt = sidx < n_seg ? (L.seg[sidx].y & 0x3ffffffu) : 0u;
                     unsigned tot;
@@ -596,6 +695,7 @@ RT_DEV void walk_pool(const DevTree& T, const float4* s_nodes, WalkLds& L, const
                 }
                 total = run;
             }
+            RT_STATS_ONLY(if (nw0 <= kThinWalkers && !thin_round) TRSTAT_ROUND(lane, n_seg, total);)
             walk_sync();
             // RT_POOL_SPANS spans per lane, stepped through side by side: as many entry loads in flight per lane
             const unsigned C = (total + 64u * RT_POOL_SPANS - 1u) / (64u * RT_POOL_SPANS);
@@ -650,7 +750,7 @@ RT_DEV void walk_pool(const DevTree& T, const float4* s_nodes, WalkLds& L, const
                 const float P = fmaxf(Lm, M);
                 if (act && disc > 0.0f && !(P > 0.0f && P * P > disc * 1.0003f)) {
                     STAT(st, ST_DISCPOS, 1);
-                    pool_candidate_b(T, s_nodes, L, make_uint4(__float_as_uint(b), __float_as_uint(disc), he, (unsigned)S.owner), blo, bhi STAT_PASS);
+                    pool_candidate_b(T, s_nodes, L, make_uint4(__float_as_uint(b), __float_as_uint(disc), he, (unsigned)S.owner), S.q, S.a, blo, bhi STAT_PASS);
                 }
             } else                                          // (pool_drain below, with nothing queued, is the fence before the owners pick up)
             while (true) {
@@ -720,6 +820,8 @@ RT_DEV void walk_pool(const DevTree& T, const float4* s_nodes, WalkLds& L, const
             }
             pool_drain(T, s_nodes, L, lane, qn STAT_PASS);
             (void)f_atm;
+        }
+        if (picked) {
             // ---- every owner picks up its result
             const unsigned long long k = L.key[lane];
             best_t = __uint_as_float((unsigned)(k >> 32)); best = (int)(unsigned)k;

@@ -12,7 +12,9 @@ enum { ST_RAYS, ST_FAST, ST_SLOW, ST_TIE, ST_COLS, ST_TESTS, ST_DISCPOS, ST_OFFE
        WP_GROUND, WP_LARGE_K, WP_LARGE_EXACT, WP_OFFER_NODE, WP_OFFER_RAYBOX, WP_ELIG_FN, WP_ELIG_LIST, WP_SETUP, WP_A_COL, WP_A_BATCH, WP_A_HOLD,
        WP_B_OFFER, WP_B_CLIP, WP_COOP_CHUNK, WP_SCAN, WP_SC_ANY, WP_SC_LAMB, WP_SC_METAL, WP_SC_DIEL, WP_REJ_ITER, WP_PRIMARY, WP_DISK_ITER, WP_SKY, WP_ENDPIX,
        // cycles of the iterations of thin waves with <= 2 live lanes, by part (the critical path of the frame's tail)
-       TH_GROUND, TH_LARGE_SETUP, TH_WALK, TH_SCAN, ST_N };
+       TH_GROUND, TH_LARGE_SETUP, TH_WALK, TH_SCAN,
+       // rounds of walk_pool in calls that at most 16 walkers entered: all, by ranges (0, 1, 2-4, 5-16, > 16), and those of at most 64 entries
+       TR_ROUNDS, TR_SEG0, TR_SEG1, TR_SEG4, TR_SEG16, TR_SEGMORE, TR_LE64, ST_N };
 #ifdef RT_STATS_LIGHT      // per-pixel and per-wave time stamps only (librt_amd_stats_light.so): the counters and cycle probes compile to nothing,
 #define TICK() 0ull        // the kernel runs within a few per cent of the product's — the timeline tools/stats.py prints is then the real one
 #else
@@ -24,8 +26,12 @@ __device__ unsigned long long g_wave_dbg[8192 * 4];   // per wave: end time (100
 struct Stats { unsigned int c[ST_N]; unsigned long long cyc[8]; };
 #ifdef RT_STATS_LIGHT
 #define STAT(st, k, v) ((void)0)
+#define TRSTAT_ROUND(lane, n_seg, total) ((void)0)
 #else
 #define STAT(st, k, v) ((st).c[k] += (v))
+#define TRSTAT_ROUND(lane, n_seg, total) do { if ((lane) == 0) { atomicAdd(&g_stats[TR_ROUNDS], 1ull); \
+    atomicAdd(&g_stats[(n_seg) == 0u ? TR_SEG0 : (n_seg) == 1u ? TR_SEG1 : (n_seg) <= 4u ? TR_SEG4 : (n_seg) <= 16u ? TR_SEG16 : TR_SEGMORE], 1ull); \
+    if ((total) <= 64u) atomicAdd(&g_stats[TR_LE64], 1ull); } } while (0)
 #endif
 // ... and the same wave passes split by the live-lane class of the main-loop iteration they ran in (0: >= 56 live lanes, 1: 32-55, 2: 8-31,
 // 3: < 8 — the classes of ST_LIVE_*): k_render notes its wave's class in LDS at the top of every iteration (WPASS_CLASS), the blocks read it.

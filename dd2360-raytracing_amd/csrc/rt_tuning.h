@@ -164,6 +164,9 @@
 #ifndef RT_POOL_COLS_THIN
 #define RT_POOL_COLS_THIN 4     // ... in a wave with few walkers (a thin wave's chains: fewer rounds, fewer dependent round trips).  C2: 14.5 -> 14.1 ms
 #endif
+#ifndef RT_POOL_THIN_ROUND
+#define RT_POOL_THIN_ROUND 1    // walk_pool: a call that at most 16 walkers entered runs thin rounds — one lane per (walker, column), the ranges' lanes write their entries into
+#endif                          // 64 slots, one per testing lane (no prefix table, no search).  0: such waves take the generic round, as before round 16 (the A/B switch; HISTORY.md round 16)
 #ifndef RT_POOL_SPANS
 #define RT_POOL_SPANS 1         // spans a lane steps through side by side in walk_pool (2, 4: within the +-1.5 % run-to-run noise)
 #endif

@@ -14,7 +14,7 @@ names = ["rays", "fast", "slow", "tie", "cols", "tests", "discpos", "offers", "e
 n, nx, ny, ns, spl = (int(x) for x in (sys.argv[1:6] if len(sys.argv) > 5 else (10000, 1200, 800, 8, 32)))
 W = rt.World(n, nx, ny).upload(); O = rt.Octree(W, spl).upload() if spl > 0 else None          # spl 0: the hitable_list path (through its grid)
 st = rt.alloc_rand_state(nx, ny); fb = rt.alloc_fb(nx, ny)
-buf = (C.c_ulonglong * 64)()
+buf = (C.c_ulonglong * 96)()
 rt.render_init(nx, ny, st); torch.cuda.synchronize()
 L.rt_debug_stats(buf, 1)
 rt.render(fb, nx, ny, ns, W, st, O); torch.cuda.synchronize()
@@ -104,3 +104,7 @@ if hasattr(L, "rt_debug_wp_classes"):
     print("  %-14s %10s %10s %10s %10s" % ("", ">=56", "32-55", "8-31", "<8"))
     for k, name in enumerate(wp):
         print("  %-14s %10.3f %10.3f %10.3f %10.3f" % (name, *[cb[c * len(wp) + k] / max(1, v[cls[c]]) for c in range(4)]))
+tr = raw[63:70]          # TR_ROUNDS, TR_SEG0, TR_SEG1, TR_SEG4, TR_SEG16, TR_SEGMORE, TR_LE64 (rt_stats.h)
+if tr[0]:
+    print("walk_pool rounds of calls that at most 16 walkers entered: %d; by ranges: none %.3f  1: %.3f  2-4: %.3f  5-16: %.3f  > 16: %.3f; at most 64 entries: %.4f" % (
+        tr[0], *[x / tr[0] for x in tr[1:7]]))
