@@ -43,6 +43,12 @@ hipError_t launch_temporal_accumulate(void* hist_out, const void* hist_in, const
                                       const rt_temporal_params& P, hipStream_t st);      // rt_temporal.hip
 hipError_t launch_denoise_hist(float* fb_out, const float* fb_in, int max_x, int max_y, const rt_hit_record* hits, const void* hist,
                                const rt_denoise_var_params& P, float4* work, hipStream_t st);      // rt_temporal.hip
+hipError_t launch_world_set_geometry(float4* geom, float4* shade, float4* list_hot, const int32_t* list_id, const float4* src, int n, int n_list,
+                                     bool half, hipStream_t st);      // rt_animate.hip
+hipError_t launch_temporal_accumulate_moving(void* hist_out, const void* hist_in, const rt_hit_record* hits, const rt_hit_record* hits_prev,
+                                             const rt_camera* cam_prev, const float4* geom, const float4* geom_prev, const void* state,
+                                             const int32_t* kind, int n_kind, int max_x, int max_y, const rt_temporal_params& P,
+                                             hipStream_t st);      // rt_animate.hip
 hipError_t launch_assemble(float* full, const float* parts, int max_x, int max_y, int nparts, hipStream_t st);
 hipError_t launch_render_adaptive(const RenderArgs& A, bool tree, hipStream_t st);
 hipError_t launch_adapt_check(float* fb, const float* sl, const float* q, const unsigned int* list_in, const unsigned int* count_in, long long n_all,
@@ -88,6 +94,21 @@ using namespace rt;
 
 #define RT_TRY(expr) do { const int e_ = (int)(expr); if (e_) return e_; } while (0)      // a hipError_t or one of this file's int codes
 
+// The host staging copy of a world's geometry, current: after rt_world_set_geometry the device holds the geometry and h_geom / h_hot
+// are behind — one synchronising download brings them back: the device first finishes what is queued (the setter's kernel may sit on
+// a non-blocking stream, which a plain hipMemcpy does not wait for).  The handle stays logically constant: the copy describes the same
+// world as the device arrays.
+static int world_host_geometry(const rt_world* W) {
+    rt_world::Lazy& Z = *W->z;
+    if (!Z.host_stale) return 0;
+    rt_world* M = const_cast<rt_world*>(W);
+    RT_TRY(hipDeviceSynchronize());
+    RT_TRY(hipMemcpy(M->h_geom.data(), Z.d_geom, M->h_geom.size() * sizeof(float4), hipMemcpyDeviceToHost));
+    if (!M->h_hot.empty()) RT_TRY(hipMemcpy(M->h_hot.data(), Z.d_list_hot, M->h_hot.size() * sizeof(float4), hipMemcpyDeviceToHost));
+    Z.host_stale = false;
+    return 0;
+}
+
 // The list as a tree of ONE node without bounds whose entries are the hittable spheres 1..n-1 in list order: hitTree on
 // it (slot 0 first, then the entries in order, strict "<") is hitable_list::hit, so the fp32 octree kernels — and their
 // candidate grid — serve the list path unchanged.  Null when the grid would not pay or cannot be used.
@@ -118,6 +139,7 @@ static rt_octree* build_list_tree(const rt_world* W) {
 static rt_octree* ensure_list_tree(const rt_world* W) {
     rt_world::Lazy& Z = *W->z;
     if (!Z.list_tree_tried && W->precision == RT_PRECISION_FP32) {
+        if (world_host_geometry(W)) return nullptr;      // (no stale geometry is ever built from: the plain scan this time, tried again next time)
         Z.list_tree_tried = true;
         try { Z.list_tree = build_list_tree(W); } catch (const std::bad_alloc&) { Z.list_tree = nullptr; }
     }
@@ -406,6 +428,42 @@ static int world_upload(const rt_world* W) {
     return 0;
 }
 int rt_world_upload(rt_world* W) { return W ? world_upload(W) : RT_EINVAL; }
+
+// ---- one resident world over a sequence of frames (DESIGN.md §5.10 "Moving scenes") ------------------------------------------------
+// Every launch takes the camera by value from the handle (frame_args: A.scene = dev), so the setter is host work only.  A new serial
+// makes everything keyed on the world miss once: the kept schedule of every context, a progressive sequence's tile order (p_key) and
+// the cached split of RT_SPLIT_BALANCED_CACHED.  Nothing else reads the serial.
+int rt_world_set_camera(rt_world* W, const rt_camera* cam) {
+    if (!W || !cam) return RT_EINVAL;
+    W->z->dev.cam = *cam;
+    W->serial = rt_next_serial();
+    return 0;
+}
+int rt_world_camera(const rt_world* W, rt_camera* out) {
+    if (!W || !out) return RT_EINVAL;
+    *out = W->z->dev.cam;
+    return 0;
+}
+
+int rt_world_set_geometry(rt_world* W, const float* d_geom, void* stream) {
+    if (!W || !d_geom || ((uintptr_t)d_geom & 15)) return RT_EINVAL;            // read as float4
+    RT_TRY(world_upload(W));
+    rt_world::Lazy& Z = *W->z;
+    // the list grid describes the old geometry: the next list-path launch builds another from the refreshed host copy.  (hipFree
+    // waits for the device, so launches still queued on the old grid finish.)
+    if (Z.list_tree) { RT_TRY(rt_free_octree(Z.list_tree)); Z.list_tree = nullptr; }
+    Z.list_tree_tried = false;
+    RT_TRY(launch_world_set_geometry((float4*)Z.d_geom, (float4*)Z.d_shade, (float4*)Z.d_list_hot, (const int32_t*)Z.d_list_id, (const float4*)d_geom,
+                                     W->n, Z.dev.n_list, W->precision == RT_PRECISION_FP16, (hipStream_t)stream));
+    Z.host_stale = true;
+    W->serial = rt_next_serial();
+    return 0;
+}
+int rt_world_get_geometry(const rt_world* W, float* d_out, void* stream) {
+    if (!W || !d_out) return RT_EINVAL;
+    RT_TRY(world_upload(W));
+    return (int)hipMemcpyAsync(d_out, W->z->d_geom, (size_t)W->n * sizeof(float4), hipMemcpyDeviceToDevice, (hipStream_t)stream);
+}
 
 int rt_free_world(rt_world* W) {
     if (!W) return 0;
@@ -717,6 +775,7 @@ int rt_build_octree_gpu(const rt_world* world, int spheres_per_leaf, rt_octree**
         (void)rt_free_octree(O);
         if (rc != RT_ENOTSUP) return rc;
     }
+    RT_TRY(world_host_geometry(world));
     std::vector<rt_sphere> list;
     try {
         list.resize((size_t)world->n);
@@ -1530,6 +1589,27 @@ int rt_temporal_accumulate(void* d_hist_out, const void* d_hist_in, const rt_hit
     if (up) return up;
     return (int)launch_temporal_accumulate(d_hist_out, d_hist_in, d_hits, d_hits_prev, cam_prev, d_state, world->z->dev.kind, world->n, max_x, max_y,
                                            *params, (hipStream_t)stream);
+}
+
+int rt_temporal_accumulate_moving(void* d_hist_out, const void* d_hist_in, const rt_hit_record* d_hits, const rt_hit_record* d_hits_prev,
+                                  const rt_camera* cam_prev, const float* d_geom_prev, const void* d_state, const rt_world* world,
+                                  int max_x, int max_y, const rt_temporal_params* params, void* stream) {
+    if (!d_hist_out || !d_hits || !d_state || !world) return RT_EINVAL;
+    if (d_hist_in && (!d_hits_prev || !cam_prev || !d_geom_prev)) return RT_EINVAL;
+    if (((uintptr_t)d_hist_out & 15) || ((uintptr_t)d_hist_in & 15) || ((uintptr_t)d_hits & 15) || (d_hist_in && ((uintptr_t)d_hits_prev & 15))) return RT_EINVAL;
+    if (d_hist_in && ((uintptr_t)d_geom_prev & 15)) return RT_EINVAL;          // read as float4
+    const int rc = rt_temporal_check(max_x, max_y, params);
+    if (rc) return rc;
+    if (d_hist_in) {                                                          // the kernel gathers from one while it writes the other
+        const uintptr_t a = (uintptr_t)d_hist_out, b = (uintptr_t)d_hist_in, bytes = (uintptr_t)RT_TEMPORAL_HISTORY_BYTES * (uintptr_t)max_x * (uintptr_t)max_y;
+        if ((a > b ? a - b : b - a) < bytes) return RT_EINVAL;
+    }
+    if (world->precision == RT_PRECISION_FP16) return RT_ENOTSUP;
+    const int up = world_upload(world);                                       // (nothing to do once rt_world_upload has run: the call can be captured)
+    if (up) return up;
+    return (int)launch_temporal_accumulate_moving(d_hist_out, d_hist_in, d_hits, d_hits_prev, cam_prev, world->z->dev.geom,
+                                                  d_hist_in ? (const float4*)d_geom_prev : nullptr, d_state, world->z->dev.kind, world->n,
+                                                  max_x, max_y, *params, (hipStream_t)stream);
 }
 
 int rt_denoise_history(void* fb_out, const void* fb_in, int max_x, int max_y, const rt_hit_record* d_hits, const void* d_hist,

@@ -111,6 +111,9 @@ struct rt_world {
         // hitable_list::hit through the candidate grid: the list as a one-node "tree" (fp32 only; null = plain scan)
         rt_octree* list_tree = nullptr; bool list_tree_tried = false;
         rt_render_ctx ctx;                      // the context rt_render / rt_render_progressive use
+        // rt_world_set_geometry has rewritten the device arrays: h_geom / h_hot are behind, and whatever reads them downloads first
+        // (world_host_geometry, rt_api.hip)
+        bool host_stale = false;
     };
     Lazy* z = nullptr;
 };

@@ -1,8 +1,9 @@
 // rt_temporal.h — the per-pixel rule of temporal accumulation (include/rt_amd.h), once: k_temporal_accumulate
 // (rt_temporal.hip) writes what temporal_pixel returns as this frame's history, k_budget_keys_temporal (rt_budget.hip) ranks the
-// pixel by it.  Numeric contract: one IEEE binary32 rounding per operation in the order the header states, no contraction (also on
-// the command line of both files), correctly rounded division (hipcc default), sums in tap order — tests/temporal_model.py
-// reproduces it bit for bit.
+// pixel by it, k_temporal_accumulate_moving (rt_animate.hip) writes its MOVING variant: the rule that follows a translated sphere.
+// Numeric contract: one IEEE binary32 rounding per operation in the order the header states, no contraction (also on the command
+// line of the three files), correctly rounded division (hipcc default), sums in tap order — tests/temporal_model.py and
+// tests/temporal_moving_model.py reproduce it bit for bit.
 #pragma once
 #include <hip/hip_runtime.h>
 #include "../../include/rt_amd.h"
@@ -46,6 +47,10 @@ inline TemporalArgs temporal_args(void* hist_out, const void* hist_in, const rt_
     return T;
 }
 
+// what the MOVING variant takes besides: the world's geometry now and as it was in the frame that wrote `in` ((cx, cy, cz, radius) per
+// world-list index, n_kind of them; geom_prev is only read when `in` is there)
+struct TemporalMotion { const float4* geom; const float4* geom_prev; };
+
 __device__ inline float dot3(float ax, float ay, float az, float bx, float by, float bz) { return (ax * bx + ay * by) + az * bz; }
 
 // what rt_temporal_accumulate writes for pixel p — (x.r, x.g, x.b, v) and neff, zeros for an EMPTY pixel — and the state values it
@@ -53,7 +58,10 @@ __device__ inline float dot3(float ax, float ay, float az, float bx, float by, f
 // 2 * p + 1 fit an int, 3 * p does not (64-bit colour offsets).  Every gathered index is clamped into the frame.
 struct TemporalPixel { float4 out; float neff; int k; float sl, q; };
 
-__device__ __forceinline__ TemporalPixel temporal_pixel(const TemporalArgs& T, int p) {
+// MOVING (rt_temporal_accumulate_moving): a sphere whose radius changed its bits is not asked, and the point of a sphere whose centre
+// changed its bits is carried back by the translation, P' = (P - c1) + c0 per component, before it is projected and compared.
+template <bool MOVING = false>
+__device__ __forceinline__ TemporalPixel temporal_pixel(const TemporalArgs& T, int p, const TemporalMotion* M = nullptr) {
     const long long e = 3 * (long long)p;
     // this frame's values: the "per pixel" line of rt_denoise_adaptive
     const int k = T.S.k[p];
@@ -67,6 +75,17 @@ __device__ __forceinline__ TemporalPixel temporal_pixel(const TemporalArgs& T, i
     c.w = d / ((nf * nf) * (nf - 1.0f));
     const float4 gp0 = T.g[2 * p], gp1 = T.g[2 * p + 1];
     const int sp = __float_as_int(gp1.w);
+    float Px = gp0.y, Py = gp0.z, Pz = gp0.w;                                      // P', where the point was: P_p unless its sphere moved
+    bool resized = false;
+    if constexpr (MOVING) {
+        if (T.in != nullptr && (unsigned)sp < (unsigned)T.n_kind) {
+            const float4 c1 = M->geom[sp], c0 = M->geom_prev[sp];
+            resized = __float_as_int(c0.w) != __float_as_int(c1.w);
+            if (__float_as_int(c0.x) != __float_as_int(c1.x) || __float_as_int(c0.y) != __float_as_int(c1.y) || __float_as_int(c0.z) != __float_as_int(c1.z)) {
+                Px = (Px - c1.x) + c0.x; Py = (Py - c1.y) + c0.y; Pz = (Pz - c1.z) + c0.z;
+            }
+        }
+    }
     float4 out = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
     float neff = 0.0f;
     const bool empty = sp == -1 || k < 2 || !__builtin_isfinite(c.x) || !__builtin_isfinite(c.y) || !__builtin_isfinite(c.z) || !__builtin_isfinite(c.w);
@@ -75,11 +94,12 @@ __device__ __forceinline__ TemporalPixel temporal_pixel(const TemporalArgs& T, i
         neff = nf;
         bool ask = T.in != nullptr && T.max_history != 0.0f;
         if (ask && !T.reuse_specular) ask = (unsigned)sp < (unsigned)T.n_kind && T.kind[sp] == RT_MAT_LAMBERTIAN;
+        if constexpr (MOVING) ask = ask && !resized;
         if (ask) {
             // where the point was seen before: the pinhole inverse of get_ray on the previous camera
             const float* O = T.cam.origin; const float* LL = T.cam.lower_left_corner; const float* H = T.cam.horizontal; const float* V = T.cam.vertical;
             const float Ax = LL[0] - O[0], Ay = LL[1] - O[1], Az = LL[2] - O[2];
-            const float Dx = gp0.y - O[0], Dy = gp0.z - O[1], Dz = gp0.w - O[2];
+            const float Dx = Px - O[0], Dy = Py - O[1], Dz = Pz - O[2];
             const float Wx = H[1] * V[2] - H[2] * V[1], Wy = H[2] * V[0] - H[0] * V[2], Wz = H[0] * V[1] - H[1] * V[0];
             const float lam = dot3(Dx, Dy, Dz, Wx, Wy, Wz) / dot3(Ax, Ay, Az, Wx, Wy, Wz);
             const float s = (dot3(Dx, Dy, Dz, H[0], H[1], H[2]) / lam - dot3(Ax, Ay, Az, H[0], H[1], H[2])) / dot3(H[0], H[1], H[2], H[0], H[1], H[2]);
@@ -109,7 +129,7 @@ __device__ __forceinline__ TemporalPixel temporal_pixel(const TemporalArgs& T, i
                     if (!in[u] || !(nq[u] > 0.0f)) continue;                             // outside the frame; an empty pixel of the last frame
                     if (__float_as_int(gq1[u].w) != sp) continue;                        // another sphere
                     if (!(dot3(gp1.x, gp1.y, gp1.z, gq1[u].x, gq1[u].y, gq1[u].z) >= T.min_dot)) continue;
-                    const float ex = gp0.y - gq0[u].y, ey = gp0.z - gq0[u].z, ez = gp0.w - gq0[u].w;
+                    const float ex = Px - gq0[u].y, ey = Py - gq0[u].z, ez = Pz - gq0[u].w;
                     if (!(((ex * ex + ey * ey) + ez * ez) <= lim)) continue;
                     const float g = ((u & 1) ? ax : 1.0f - ax) * ((u >> 1) ? ay : 1.0f - ay);
                     sg = sg + g;

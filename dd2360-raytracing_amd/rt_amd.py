@@ -173,6 +173,10 @@ SYMBOLS = {
     "rt_camera_init": (_i, [_vp, _vp, _vp, _vp, _f, _f, _f, _f, _i]),
     "rt_world_create": (_i, [_vp, _i, _vp, _i, _vp]),
     "rt_world_upload": (_i, [_vp]),
+    "rt_world_set_camera": (_i, [_vp, _vp]),
+    "rt_world_camera": (_i, [_vp, _vp]),
+    "rt_world_set_geometry": (_i, [_vp, _vp, _vp]),
+    "rt_world_get_geometry": (_i, [_vp, _vp, _vp]),
     "rt_free_world": (_i, [_vp]),
     "rt_build_octree": (_i, [_vp, _i, _i, _i, _vp]),
     "rt_octree_upload": (_i, [_vp]),
@@ -243,6 +247,7 @@ SYMBOLS = {
     "rt_denoise_adaptive_check": (_i, [_i, _i, C.POINTER(DenoiseVarParams)]),
     "rt_temporal_check": (_i, [_i, _i, C.POINTER(TemporalParams)]),
     "rt_temporal_accumulate": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, C.POINTER(TemporalParams), _vp]),
+    "rt_temporal_accumulate_moving": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, C.POINTER(TemporalParams), _vp]),
     "rt_denoise_history": (_i, [_vp, _vp, _i, _i, _vp, _vp, C.POINTER(DenoiseVarParams), _vp, _vp]),
     "rt_adaptive_priority_filtered": (_f, [_f, _f, _f]),
     "rt_adaptive_budget_select_filtered": (_i, [_vp, _vp, _vp, _i, _i, C.POINTER(Budget), C.POINTER(DenoiseVarParams), _i64, _vp, _vp, _vp, _vp]),
@@ -594,6 +599,44 @@ class World:
         check(lib().rt_world_upload(self.h), "rt_world_upload")
         return self
 
+    def set_camera(self, cam):
+        """rt_world_set_camera: the camera (a camera_dtype record) of every launch from now on; host only, launches already enqueued keep
+        theirs"""
+        cam = np.ascontiguousarray(cam, camera_dtype).reshape(1).copy()
+        check(lib().rt_world_set_camera(self.h, _np(cam)), "rt_world_set_camera")
+        self.camera = cam
+        return self
+
+    def get_camera(self):
+        """rt_world_camera: the camera the next launch will use, as a camera_dtype array of one record"""
+        cam = np.zeros(1, camera_dtype)
+        check(lib().rt_world_camera(self.h, _np(cam)), "rt_world_camera")
+        return cam
+
+    def set_geometry(self, d_geom):
+        """rt_world_set_geometry on the current stream: d_geom is a float32 device tensor of num_spheres x 4 (cx, cy, cz, radius) in
+        world-list order.  Octrees built before the call describe the old geometry: build them again (Octree(world, spl, gpu=True))"""
+        check(lib().rt_world_set_geometry(self.h, _dev(d_geom), _stream()), "rt_world_set_geometry")
+        self._spheres_stale = True
+        return self
+
+    def get_geometry(self, d_out=None):
+        """rt_world_get_geometry on the current stream: the world's geometry as a float32 device tensor [num_spheres, 4] (d_out, or a new one)"""
+        if d_out is None:
+            import torch
+            d_out = torch.empty((self.num_spheres, 4), dtype=torch.float32, device="cuda")
+        check(lib().rt_world_get_geometry(self.h, _dev(d_out), _stream()), "rt_world_get_geometry")
+        return d_out
+
+    def host_spheres(self):
+        """self.spheres with the geometry the device holds: downloaded (a synchronising copy) after a set_geometry"""
+        if getattr(self, "_spheres_stale", False):
+            g = self.get_geometry().cpu().numpy()
+            self.spheres["center"] = g[:, :3]
+            self.spheres["radius"] = g[:, 3]
+            self._spheres_stale = False
+        return self.spheres
+
     def set_list_traversal(self, mode):
         """TRAVERSAL_REFERENCE (every sphere in list order) or TRAVERSAL_FAST (default: the candidate grid) for renders without an octree"""
         check(lib().rt_world_set_list_traversal(self.h, mode), "rt_world_set_list_traversal")
@@ -657,7 +700,7 @@ class Octree:
         if gpu:
             check(L.rt_build_octree_gpu(world.h, spheres_per_leaf, C.byref(h), _stream()), "rt_build_octree_gpu")
         else:
-            check(L.rt_build_octree(_np(world.spheres), world.num_spheres, spheres_per_leaf, world.precision, C.byref(h)), "rt_build_octree")
+            check(L.rt_build_octree(_np(world.host_spheres()), world.num_spheres, spheres_per_leaf, world.precision, C.byref(h)), "rt_build_octree")
         self.h = h
 
     def upload(self):
@@ -912,6 +955,17 @@ def temporal_accumulate(d_hist_out, d_hist_in, d_hits, d_hits_prev, cam_prev, d_
     check(lib().rt_temporal_accumulate(_dev(d_hist_out), None if first else _dev(d_hist_in), _dev(d_hits), None if first else _dev(d_hits_prev),
                                        None if first else _np(cam), _dev(d_state), world.h, max_x, max_y, C.byref(params), _stream()),
           "rt_temporal_accumulate")
+
+
+def temporal_accumulate_moving(d_hist_out, d_hist_in, d_hits, d_hits_prev, cam_prev, d_geom_prev, d_state, world, max_x, max_y, params):
+    """rt_temporal_accumulate_moving on the current stream: temporal_accumulate for a world whose spheres moved (World.set_geometry)
+    since the frame that wrote d_hist_in; d_geom_prev is what World.get_geometry returned for that frame (None with d_hist_in None)"""
+    first = d_hist_in is None
+    cam = None if first else np.ascontiguousarray(cam_prev, camera_dtype).reshape(1)
+    check(lib().rt_temporal_accumulate_moving(_dev(d_hist_out), None if first else _dev(d_hist_in), _dev(d_hits),
+                                              None if first else _dev(d_hits_prev), None if first else _np(cam),
+                                              None if first or d_geom_prev is None else _dev(d_geom_prev), _dev(d_state), world.h, max_x, max_y,
+                                              C.byref(params), _stream()), "rt_temporal_accumulate_moving")
 
 
 def denoise_history(fb_out, fb_in, max_x, max_y, d_hits, d_hist, params, d_work):

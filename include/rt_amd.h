@@ -152,6 +152,39 @@ int rt_world_set_list_traversal(rt_world* world, int mode);   /* RT_TRAVERSAL_RE
 #define RT_ARITH_CONTRACT 1
 int rt_world_set_arith(rt_world* world, int mode);
 int rt_world_list_accel_info(const rt_world* world, int* enabled, int* grid_dim, float* cell_size, int* grid_entries, int* large_spheres);
+/* One resident world over a sequence of frames (no reference counterpart, whose scene and camera are fixed; DESIGN.md §5.10 "Moving
+ * scenes").  The camera and the sphere geometry of a world can be replaced between frames; materials, kinds and the list order stay.
+ *
+ * rt_world_set_camera: host only.  Every launch passes the camera by value in its kernel arguments, so the call does no device work
+ * and synchronises with nothing: launches already enqueued keep the camera they were launched with, and a captured hipGraph keeps the
+ * camera it was captured with.  From the next call on, every entry point that takes the world renders what a fresh
+ * rt_world_create(list, n, cam, precision) renders, bit for bit (frames, written-back RNG states, guides, trace records); USE_FP16
+ * worlds expect exact binary16 images in the fields, as rt_world_create does.  What is keyed on the world misses once: the kept
+ * schedule of every context (rt_world_render_schedule_reuse: `computed` one higher for the first rt_render after the call), the tile
+ * order of a progressive sequence, the cached split of RT_SPLIT_BALANCED_CACHED.  A progressive pass with current_sample > 1 after the
+ * call adds a sample seen through the NEW camera to the caller's sums of the old one, in the plain tile order: start the sequence
+ * again at current_sample == 1, as the reference's viewer does when its camera moves.  To a context that a captured progressive pass
+ * has bound to a graph (see "Render contexts"), the moved world is another frame: give the restarted sequence a context of its own.
+ * rt_world_camera returns the camera the next launch will use.  RT_EINVAL for NULL.
+ *
+ * rt_world_set_geometry: d_geom is a device array of world->n x 4 floats (cx, cy, cz, radius) in world-list order, 16-byte aligned,
+ * none of the world's own arrays.  It uploads the world if need be and enqueues ONE kernel on `stream` that rewrites every device
+ * array holding geometry; after it the world is indistinguishable on the device from a fresh world created from the same list with the
+ * new geometry (radius * radius in the world's precision included; values are taken without looking, as rt_world_create takes them:
+ * NaN, negative radii).  Launches on other streams that read the world are the caller's to order against `stream`.  What goes stale:
+ *   - the host staging copy: whatever needs it (the list grid, the host fallback of rt_build_octree_gpu) first downloads the device
+ *     copy — one synchronising copy, only then;
+ *   - the world's list grid (rt_world_set_list_traversal): freed; the next launch without an octree builds another ON THE HOST.  The
+ *     list path of a moved world pays that build per move: the animated path is the octree path, rt_build_octree_gpu per frame;
+ *   - octrees built from the world before the call: they describe the old geometry, and rendering through one is undefined, as through
+ *     the tree of another world.  Free them and call rt_build_octree_gpu(world, ...) again;
+ *   - kept schedules, progressive tile orders and cached splits miss once, as after rt_world_set_camera.
+ * rt_world_get_geometry copies the same layout out, device to device, asynchronously on `stream` (uploads the world if need be): a
+ * viewer keeps last frame's geometry with it for rt_temporal_accumulate_moving.  RT_EINVAL for NULL or a misaligned d_geom. */
+int rt_world_set_camera(rt_world* world, const rt_camera* cam);
+int rt_world_camera(const rt_world* world, rt_camera* out);
+int rt_world_set_geometry(rt_world* world, const float* d_geom, void* stream);
+int rt_world_get_geometry(const rt_world* world, float* d_out, void* stream);
 /* free_world<<<1,1>>> + cudaFree — main.cu:206-219, :464-466. */
 int rt_free_world(rt_world* world);
 
@@ -630,6 +663,26 @@ int rt_temporal_check(int max_x, int max_y, const rt_temporal_params* params);  
 int rt_temporal_accumulate(void* d_hist_out, const void* d_hist_in, const rt_hit_record* d_hits, const rt_hit_record* d_hits_prev,
                            const rt_camera* cam_prev, const void* d_state, const rt_world* world, int max_x, int max_y,
                            const rt_temporal_params* params, void* stream);
+/* rt_temporal_accumulate for a world whose spheres moved since the frame that wrote d_hist_in (rt_world_set_geometry; DESIGN.md §5.10
+ * "Moving scenes").  d_geom_prev is what rt_world_get_geometry returned for that frame: world->n records (cx, cy, cz, radius), 16-byte
+ * aligned; NULL exactly when d_hist_in is NULL.  This frame's geometry is the world's own.  Every other argument, the refusals (plus
+ * RT_EINVAL for a d_hist_in without d_geom_prev or with a misaligned one), fp32 worlds only, one launch, no allocation and capture are
+ * those of rt_temporal_accumulate, and so is the per-pixel rule, with two changes — each operation rounded once to binary32, no
+ * contraction.  With s = sphere_p, c1 = geom[s].xyz, r1 = geom[s].w and c0, r0 the same fields of d_geom_prev[s]:
+ *   asked at all:    also not when 0 <= s < n and the bits of r0 differ from the bits of r1: a sphere that changed size starts again.
+ *   where it was:    when 0 <= s < n and a component of c0 differs in its bits from c1:
+ *                    P' = ((P.x - c1.x) + c0.x, (P.y - c1.y) + c0.y, (P.z - c1.z) + c0.z); otherwise P' = P_p bit for bit (also for an
+ *                    s outside the list, which reads no geometry).  P' replaces P_p in D = P' - O and in the tap test e = P' - P_q.
+ *                    lim = tol2 * (t_p*t_p), the normal test (a translation keeps normals), the taps and the merge are unchanged.
+ * So with nothing moved the call writes the bytes of rt_temporal_accumulate, and on every pixel whose sphere kept its radius it writes
+ * what rt_temporal_accumulate writes for a copy of d_hits whose p fields hold P' (tests/temporal_moving_model.py).
+ * Out of scope: LIGHTING — the history of a static surface goes on showing the old shadows and reflections of a sphere that moved;
+ * max_history bounds that lag.  HISTORY-AWARE BUDGETS keep the static rule (rt_temporal_inputs is a fixed POD): it refuses the taps of
+ * a moved sphere, which then ranks as thin history and is given samples — the wanted direction.  Rotation and radius-aware
+ * reprojection, multi-GPU frames and parts, binary16 histories. */
+int rt_temporal_accumulate_moving(void* d_hist_out, const void* d_hist_in, const rt_hit_record* d_hits, const rt_hit_record* d_hits_prev,
+                                  const rt_camera* cam_prev, const float* d_geom_prev, const void* d_state, const rt_world* world,
+                                  int max_x, int max_y, const rt_temporal_params* params, void* stream);
 /* rt_denoise_adaptive with its "per pixel" values taken from a history: x = hist.xyz, v = hist.w; a pixel is pass-through, and keeps
  * the bits of fb_in, when neff == 0 or a channel of x or v is not finite (or v < 0, which rt_temporal_accumulate never writes).  The
  * levels, fb_out == fb_in, buffers, alignment (d_hist 16-byte aligned too), capture and errors are those of rt_denoise_adaptive; d_hits

@@ -1,0 +1,297 @@
+"""GPU tests of rt_temporal_accumulate_moving (-m gpu).  Every comparison is bit equality through same() of tests/test_gpu_denoise_var.py,
+except the quality check: the kernel against the numpy model of tests/temporal_moving_model.py over a chain of three frames of ONE
+world whose spheres move and whose camera stands or orbits, the two identities of the rule against rt_temporal_accumulate on the GPU,
+tiny frames, a captured graph, the refusals, and the RMSE against 512 spp.
+
+The scene is create_world at N = 10 000 (203x77, SPL 32, the adaptive parameters of tests/test_gpu_temporal.py).  The small spheres
+are the hittable slots 1 .. n-1 of radius below 0.5; every 7th of them moves +0.5 in x per frame, and a second, disjoint set (every 7th
+from the fourth on) has its radius times 1.25 per frame.  Frame f is rendered after World.get_geometry / set_geometry / set_camera and a
+device build of the tree.  Counts are taken at position_tolerance 1, for the reason the docstring of tests/test_gpu_temporal.py gives."""
+import numpy as np
+import pytest
+
+import temporal_model as tm
+import temporal_moving_model as tmm
+from test_gpu_denoise_var import same      # bit equality, except that any two NaNs are equal
+from test_gpu_temporal import orbit_camera
+
+pytestmark = pytest.mark.gpu
+NX, NY = 203, 77
+N, SPL = 10000, 32
+ADAPT = (4, 64, 4, 0.1, 0.02)
+PATHS = dict(static=0.0, orbit=1.0)            # degrees per frame
+F = np.float32
+STEP = F(0.5)
+
+
+def motion_sets(spheres, every=7):
+    """the small spheres that move (every `every`-th) and, disjoint from them for every > 3, those that change radius"""
+    small = np.flatnonzero((spheres["material"] != -1) & (spheres["radius"] < 0.5) & (np.arange(len(spheres)) > 0))
+    return small[::every], small[3::7]
+
+
+class Animation:
+    """frames of ONE world: before frame f > 0 the geometry is read back (what the next accumulate takes as d_geom_prev), the moved set
+    is translated and the second set resized, the camera is set and the tree is built again on the device; every frame leaves its
+    state, gamma frame, guides, camera and geometry on the device and on the host"""
+
+    def __init__(self, rt, torch, n_spheres, spl, nx, ny, degs, adapt, resize=True, every=7):
+        self.rt, self.torch, self.nx, self.ny, self.spl = rt, torch, nx, ny, spl
+        self.W = W = rt.World(n_spheres, nx, ny)
+        self.kind = W.spheres["material"].astype(np.int32)
+        self.moved, self.resized = motion_sets(W.spheres, every)
+        assert len(self.moved) >= 1 and not (resize and set(self.moved) & set(self.resized))
+        st = rt.alloc_rand_state(nx, ny)
+        rt.render_init(nx, ny, st)
+        self.frames, self.tree = [], None
+        for f, deg in enumerate(degs):
+            if f:
+                nxt = W.get_geometry()
+                nxt[torch.from_numpy(self.moved).cuda(), 0] += float(STEP)
+                if resize:
+                    nxt[torch.from_numpy(self.resized).cuda(), 3] *= 1.25
+                W.set_geometry(nxt)
+                W.set_camera(orbit_camera(rt, deg, nx, ny))
+            self.rebuild()
+            fb, state, d_hits = rt.alloc_fb(nx, ny), rt.alloc_adaptive_state(nx, ny), rt.alloc_guides(nx, ny)
+            rt.render_adaptive_begin(fb, nx, ny, rt.Adaptive(*adapt), W, st, state, self.tree)
+            rt.render_guides(W, self.tree, nx, ny, d_hits)
+            d_geom = W.get_geometry()
+            torch.cuda.synchronize()
+            self.frames.append(dict(cam=W.get_camera(), fb=fb, state=state, d_hits=d_hits, d_geom=d_geom, h_state=state.cpu().numpy(),
+                                    hits=d_hits.cpu().numpy().view(rt.hit_record_dtype), geom=d_geom.cpu().numpy()))
+
+    def rebuild(self):
+        if self.tree is not None:
+            self.tree.close()
+        self.tree = self.rt.Octree(self.W, self.spl, gpu=True)
+
+    def at(self, f):
+        """the world with the geometry and camera of frame f again (the moving accumulate reads this frame's geometry from the world)"""
+        self.W.set_geometry(self.frames[f]["d_geom"])
+        self.W.set_camera(self.frames[f]["cam"])
+        return self.frames[f]
+
+    def close(self):
+        if self.tree is not None:
+            self.tree.close()
+        self.W.close()
+
+
+def gpu_chain(rt, torch, A, p, upto=None):
+    out = []
+    for f in range(len(A.frames[:upto])):
+        fr = A.at(f)
+        h = rt.alloc_temporal_history(A.nx, A.ny)
+        h.fill_(7.0)                                                             # every pixel must be written
+        pv = A.frames[f - 1] if f else None
+        rt.temporal_accumulate_moving(h, out[-1] if f else None, fr["d_hits"], pv["d_hits"] if f else None, pv["cam"] if f else None,
+                                      pv["d_geom"] if f else None, fr["state"], A.W, A.nx, A.ny, p)
+        out.append(h)
+    torch.cuda.synchronize()
+    return out
+
+
+def model_chain(A, p, upto=None, moving=True):
+    out, counts = [], []
+    for f, fr in enumerate(A.frames[:upto]):
+        pv = A.frames[f - 1] if f else None
+        c = {}
+        common = (fr["h_state"], A.kind, A.nx, A.ny, p.max_history, p.reuse_specular, p.position_tolerance, p.normal_min_dot)
+        if moving:
+            out.append(tmm.accumulate_moving(out[-1] if f else None, fr["hits"], pv["hits"] if f else None, pv["cam"] if f else None, fr["geom"],
+                                             pv["geom"] if f else None, *common, counts=c))
+        else:
+            out.append(tm.accumulate(out[-1] if f else None, fr["hits"], pv["hits"] if f else None, pv["cam"] if f else None, *common, counts=c))
+        counts.append(c)
+    return out, counts
+
+
+@pytest.fixture(scope="module")
+def anims(rt, cuda):
+    """three frames at 203x77 on each camera path"""
+    tmm.self_check()                               # the model follows the rule before the kernel is held to the model
+    made = {name: Animation(rt, cuda, N, SPL, NX, NY, [0.0, step, 2 * step], ADAPT) for name, step in PATHS.items()}
+    yield made
+    for A in made.values():
+        A.close()
+
+
+# ---- 8. kernel == model over the chain ---------------------------------------------------------------------------------------------
+PARAMS = [dict(), dict(position_tolerance=1.0), dict(position_tolerance=1e-4), dict(max_history=0), dict(max_history=8, position_tolerance=1.0),
+          dict(reuse_specular=1, position_tolerance=1.0), dict(normal_min_dot=-1.0, position_tolerance=1.0)]
+
+
+@pytest.mark.parametrize("kw", PARAMS, ids=[",".join("%s=%s" % kv for kv in c.items()) or "defaults" for c in PARAMS])
+@pytest.mark.parametrize("path", list(PATHS))
+def test_matches_the_model_over_a_chain(rt, cuda, anims, path, kw):
+    A = anims[path]
+    p = rt.temporal_params(**kw)
+    got = gpu_chain(rt, cuda, A, p)
+    ref, counts = model_chain(A, p)
+    for f in range(3):
+        assert same(got[f].cpu().numpy(), ref[f]), (path, kw, f)
+    assert counts[0]["nonempty"] > NX * NY // 2 and counts[0]["took"] == 0
+    if p.max_history == 0:
+        assert all(c["took"] == 0 for c in counts)
+
+
+def test_every_cause_occurs_in_the_chain(rt, cuda, anims):
+    """the model's counts at position_tolerance 1: pixels on a translated sphere took history, pixels were dropped for a changed radius,
+    and pixels on a translated sphere had every tap refused — on both camera paths"""
+    p = rt.temporal_params(position_tolerance=1.0)
+    for name, A in anims.items():
+        _, counts = model_chain(A, p)
+        for c in counts[1:]:
+            print(name, {k: v for k, v in c.items() if not k.endswith("_mask")})
+            assert c["moved_took"] > 0 and c["resized_not_asked"] > 0 and c["moved_refused"] > 0, name
+        _, static = model_chain(A, p, moving=False)
+        assert counts[2]["moved_took"] > int((static[2]["took_mask"] & counts[2]["moved_mask"]).sum())      # the static rule loses them
+
+
+def test_both_identities_on_the_gpu(rt, cuda, anims):
+    torch = cuda
+    p = rt.temporal_params(position_tolerance=1.0)
+    for name, A in anims.items():
+        h = gpu_chain(rt, torch, A, p)
+        fr, pv = A.at(2), A.frames[1]
+        # nothing moved (last frame's geometry is this frame's): the bytes of rt_temporal_accumulate
+        a, b = rt.alloc_temporal_history(NX, NY), rt.alloc_temporal_history(NX, NY)
+        rt.temporal_accumulate_moving(a, h[1], fr["d_hits"], pv["d_hits"], pv["cam"], fr["d_geom"], fr["state"], A.W, NX, NY, p)
+        rt.temporal_accumulate(b, h[1], fr["d_hits"], pv["d_hits"], pv["cam"], fr["state"], A.W, NX, NY, p)
+        torch.cuda.synchronize()
+        assert same(a.cpu().numpy(), b.cpu().numpy()), name
+        # moved: the static call on guides whose p fields hold P', wherever the radius was kept
+        patched = tmm.patched_guides(fr["hits"], fr["geom"], pv["geom"])
+        assert not np.array_equal(patched["p"], fr["hits"]["p"])
+        d_patched = torch.from_numpy(patched.view(np.uint8).copy()).cuda()
+        rt.temporal_accumulate(b, h[1], d_patched, pv["d_hits"], pv["cam"], fr["state"], A.W, NX, NY, p)
+        torch.cuda.synchronize()
+        keep = ~tmm.moved_points(fr["hits"], fr["geom"], pv["geom"])[3]
+        assert 0 < (~keep).sum() < keep.sum()
+        xa, na = tm.history_parts(h[2].cpu().numpy(), NX * NY)
+        xb, nb = tm.history_parts(b.cpu().numpy(), NX * NY)
+        assert same(xa[keep], xb[keep]) and same(na[keep], nb[keep]), name
+        assert not same(xa[~keep], xb[~keep])
+
+
+@pytest.mark.parametrize("nx,ny", [(1, 1), (3, 2), (16, 17)])
+def test_tiny_frames(rt, cuda, nx, ny):
+    A = Animation(rt, cuda, 500, 30, nx, ny, [0.0, 0.0, 2.0], (4, 32, 4, 0.1, 0.02))
+    for p in (rt.temporal_params(position_tolerance=1.0), rt.temporal_params(reuse_specular=1, max_history=8)):
+        got = gpu_chain(rt, cuda, A, p)
+        ref, _ = model_chain(A, p)
+        for f in range(3):
+            assert same(got[f].cpu().numpy(), ref[f]), (nx, ny, f)
+    A.close()
+
+
+def test_captured_in_a_graph(rt, cuda, anims):
+    torch = cuda
+    A = anims["orbit"]
+    p = rt.temporal_params(position_tolerance=1.0)
+    h = gpu_chain(rt, torch, A, p)
+    fr, pv = A.at(2), A.frames[1]
+    hist = rt.alloc_temporal_history(NX, NY)
+    g = torch.cuda.CUDAGraph()
+    with torch.cuda.graph(g):
+        rt.temporal_accumulate_moving(hist, h[1], fr["d_hits"], pv["d_hits"], pv["cam"], pv["d_geom"], fr["state"], A.W, NX, NY, p)
+    hist.fill_(3.0)
+    g.replay()
+    torch.cuda.synchronize()
+    assert same(hist.cpu().numpy(), h[2].cpu().numpy())
+
+
+def test_refusals(rt, cuda, anims):
+    torch = cuda
+    A = anims["static"]
+    a, b = A.frames[0], A.at(1)
+    p = rt.temporal_params()
+    n = NX * NY
+    m = (5 * n + 3) // 4 * 4                                                     # floats to the next 16-byte boundary behind one history
+    big = torch.zeros(2 * m + 16, dtype=torch.float32, device="cuda")
+    first, second = big[:5 * n], big[m:m + 5 * n]                                # both 16-byte aligned, no overlap
+    rt.temporal_accumulate_moving(first, None, a["d_hits"], None, None, None, a["state"], A.W, NX, NY, p)
+    rt.temporal_accumulate_moving(second, first, b["d_hits"], a["d_hits"], a["cam"], a["d_geom"], b["state"], A.W, NX, NY, p)
+    torch.cuda.synchronize()
+
+    def refused(*args):
+        with pytest.raises(rt.RtError) as e:
+            rt.temporal_accumulate_moving(*args)
+        return str(e.value)
+
+    ok = (b["d_hits"], a["d_hits"], a["cam"], a["d_geom"], b["state"], A.W, NX, NY, p)
+    for out in (second, big[m + 4:m + 4 + 5 * n], big[m - 4:m - 4 + 5 * n]):       # in place, and aligned overlaps from either side
+        assert "failed: -1 " in refused(out, second, *ok)
+    assert "failed: -1 " in refused(big[1:5 * n + 1], second, *ok)                 # misaligned histories and guides
+    assert "failed: -1 " in refused(second, big[1:5 * n + 1], *ok)
+    assert "failed: -1 " in refused(second, first, b["d_hits"][4:], *ok[1:])
+    assert "failed: -1 " in refused(second, first, b["d_hits"], a["d_hits"][8:], *ok[2:])
+    assert "failed: -1 " in refused(second, first, b["d_hits"], a["d_hits"], a["cam"], None, *ok[4:])                            # no d_geom_prev
+    assert "failed: -1 " in refused(second, first, b["d_hits"], a["d_hits"], a["cam"], a["d_geom"].reshape(-1)[1:], *ok[4:])     # misaligned
+    assert "failed: -1 " in refused(second, first, b["d_hits"], a["d_hits"], a["cam"], a["d_geom"], b["state"], A.W, NX, NY,
+                                    rt.temporal_params(position_tolerance=0.0))
+    half = rt.World(500, NX, NY, precision=rt.FP16)
+    assert "failed: -4 " in refused(second, first, b["d_hits"], a["d_hits"], a["cam"], a["d_geom"], b["state"], half, NX, NY, p)
+    half.close()
+    torch.cuda.synchronize()
+
+
+# ---- 9. quality ---------------------------------------------------------------------------------------------------------------------
+def test_moving_history_beats_the_static_rule(rt, cuda):
+    """203x77, N = 10 000, SPL 32, four frames of 8 spp each (rel_error 0, min_spp = max_spp) of one world under a static camera, RNG
+    states carried on, library defaults; against rt_render(512) of the last frame's world; gamma frames.  Over the lambertian pixels on
+    moved spheres whose fourth frame took history under the moving rule, sqrt of the moving history has a lower RMSE than sqrt of the
+    history rt_temporal_accumulate gives on the same frames: the static rule finds another sphere where the pixel's sphere is now,
+    refuses every tap and holds one frame's 8 samples.
+
+    The motion: EVERY small sphere moves +0.5 in x per frame (no radius changes), not every 7th.  Chosen on the CPU with the oracle's
+    renders and the two numpy models, before any GPU run.  A sphere that moves ALONE through this dense field (spacing 0.22, radius 0.1)
+    arrives among, often inside, other spheres: what it shows and the light it receives change with every step, and the history
+    that follows it carries the light — at this frame size, where a sphere is two pixels wide, also the background — of the places it
+    came from.  With every 7th sphere moving the claim FAILS there: moving 0.0658 against static 0.0601 over 490 pixels at
+    position_tolerance 1, 0.0662 against 0.0548 over 169 at the default; steps of 0.1, 0.25, 1 and 2, every 49th and every 2nd sphere
+    fail or tie as well (profiles/r17/animate.txt), and a larger frame does not mend it (tools/animate_study.py at 1200x800: 0.0562
+    against 0.0480).  A field that moves as a whole keeps its neighbourhoods: 0.0458 against 0.0558 over 1 782 pixels at the default
+    tolerance on the CPU (0.0488 against 0.0560 over 4 646 at tolerance 1), an 18 % margin over enough pixels to rest on.
+
+    Measured on one MI355X: moving 0.04577 against static 0.05580 over 1 782 pixels, mean neff 19.6 against 8.0 — the CPU's figures,
+    as the frames are the oracle's bit for bit."""
+    torch = cuda
+    A = Animation(rt, torch, N, SPL, NX, NY, [0.0] * 4, (8, 8, 4, 0.0, 0.0), resize=False, every=1)
+    p = rt.temporal_params()
+    moving = gpu_chain(rt, torch, A, p)[3].cpu().numpy()
+    _, counts = model_chain(A, p)
+    last = A.at(3)
+    A.rebuild()
+    fb, st = rt.alloc_fb(NX, NY), rt.alloc_rand_state(NX, NY)
+    rt.render_init(NX, NY, st)
+    rt.render(fb, NX, NY, 512, A.W, st, A.tree)
+    torch.cuda.synchronize()
+    ref = fb.cpu().numpy().reshape(-1, 3).astype(np.float64)
+    # the static rule on the same frames
+    hs = []
+    for f, fr in enumerate(A.frames):
+        h = rt.alloc_temporal_history(NX, NY)
+        pv = A.frames[f - 1] if f else None
+        rt.temporal_accumulate(h, hs[-1] if f else None, fr["d_hits"], pv["d_hits"] if f else None, pv["cam"] if f else None, fr["state"], A.W,
+                               NX, NY, p)
+        hs.append(h)
+    torch.cuda.synchronize()
+    static = hs[3].cpu().numpy()
+    xm, nm = tm.history_parts(moving, NX * NY)
+    xs, ns = tm.history_parts(static, NX * NY)
+    sel = counts[3]["took_mask"] & counts[3]["moved_mask"] & (A.kind[np.clip(last["hits"]["sphere"], 0, None)] == rt.MAT_LAMBERTIAN)
+    assert np.array_equal(nm > 8, counts[3]["took_mask"])                          # the kernel took history exactly where the model did
+    am, as_ = np.sqrt(xm[:, :3].astype(np.float64)), np.sqrt(xs[:, :3].astype(np.float64))
+    sel &= np.isfinite(ref).all(1) & np.isfinite(am).all(1) & np.isfinite(as_).all(1)
+
+    def rmse(img):
+        return float(np.sqrt(((img[sel] - ref[sel]) ** 2).mean()))
+
+    e_moving, e_static = rmse(am), rmse(as_)
+    print("moving %.5f static %.5f over %d lambertian pixels on moved spheres that took history (mean neff %.1f against %.1f)"
+          % (e_moving, e_static, sel.sum(), nm[sel].mean(), ns[sel].mean()))
+    A.close()
+    assert sel.sum() > 100
+    assert e_moving < e_static, (e_moving, e_static)
