@@ -28,6 +28,9 @@ hipError_t launch_assemble_split(void* full, const void* parts, int max_x, int m
 hipError_t launch_render(const RenderArgs& A, bool tree, int mode, hipStream_t st);
 namespace fmac { hipError_t launch_render(const RenderArgs& A, bool tree, int mode, hipStream_t st); }      // rt_kernels_contract.hip
 hipError_t launch_tile_order(const RenderArgs& A, bool tree, int* cost, unsigned int* order, unsigned char* flags, unsigned int* long_list, hipStream_t st);
+int render_variant_of(bool tree, const DevAccel& acc);
+hipError_t launch_count_order(const RenderArgs& A, const unsigned short* iters, int* cost, unsigned int* order, unsigned char* flags, unsigned int* long_list,
+                              float solo_frac, int solo_cap_den, unsigned int* extra, hipStream_t st);
 hipError_t launch_render_h(const RenderArgs& A, bool tree, int mode, hipStream_t st);
 hipError_t launch_tile_order_h(const RenderArgs& A, bool tree, int* cost, unsigned int* order, unsigned char* flags, unsigned int* long_list, hipStream_t st);
 hipError_t launch_trace_h(const DevScene& S, const DevTree& T, bool tree, const float* rays, long long n, rt_hit_record* out, hipStream_t st);
@@ -87,6 +90,7 @@ hipError_t read_stats(unsigned long long* out, int reset);
 hipError_t read_wp_classes(unsigned long long* out, int reset);
 hipError_t read_wave_dbg(unsigned long long* out);
 hipError_t read_pilot_dbg(int* out, int n);
+hipError_t read_chain_dbg(unsigned int* out, int n_pixels);
 #endif
 }
 
@@ -296,7 +300,8 @@ static DevGroup queue_group(rt_render_ctx& C) { return DevGroup().add(&C.d_queue
 // (flags: 64 + 16 + 16 bytes per tile; long chains: 64 entries per tile, then the tail list: up to 64 per tile, then the tail sort's 512 words)
 static DevGroup sched_group(rt_render_ctx& C, size_t tiles) {
     return DevGroup().add(&C.d_cost, sizeof(int) * tiles).add(&C.d_order, sizeof(unsigned int) * tiles).add(&C.d_flags, tiles * 96)
-                     .add(&C.d_long, sizeof(unsigned int) * (tiles * 128 + 512)).add(&C.d_work, sizeof(int) * tiles * 2);
+                     .add(&C.d_long, sizeof(unsigned int) * (tiles * 128 + 512)).add(&C.d_work, sizeof(int) * tiles * 2)
+                     .add(&C.d_iters, sizeof(unsigned short) * tiles * 64);      // (the measured pass: one count per buffer element)
 }
 static DevGroup progressive_group(rt_render_ctx& C, size_t tiles) { return DevGroup().add(&C.p_cost, sizeof(int) * tiles).add(&C.p_order, sizeof(unsigned int) * tiles); }
 static DevGroup adaptive_group(rt_render_ctx& C, size_t pixels) {
@@ -862,6 +867,7 @@ static RenderArgs frame_args(void* fb, int max_x, int max_y, int ns, const rt_wo
     clear_schedule(A);
     A.f_inflight = tune_value("RT_F_INFLIGHT", RT_F_INFLIGHT); A.f_inflight_dense = tune_value("RT_F_INFLIGHT_DENSE", RT_F_INFLIGHT_DENSE); A.f_static = tune_value("RT_F_STATIC", RT_F_STATIC);
     A.ad_list = nullptr; A.ad_count = nullptr; A.ad_sl = nullptr; A.ad_q = nullptr;
+    A.iters_out = nullptr;
     return A;
 }
 
@@ -920,12 +926,25 @@ static int begin_counters(rt_render_ctx& C, const RenderArgs& A, SchedAction act
     else RT_TRY(launch_zero_counters(A.queue, (int)kQueueStride, st));
     return 0;
 }
+// the measured pass (rt_sched_keep.h "Feedback"): does this launch take part at all — the gate, and the process's switch
+static bool feedback_gate(const RenderArgs& A, const rt_world* world, const rt_octree* d_octree, int ns) {
+    const int min_ns = (int)tune_value("RT_FEEDBACK_MIN_NS", (float)RT_FEEDBACK_MIN_NS);
+    const bool half = world->precision == RT_PRECISION_FP16;
+    return sched_feedback_gate(ns, min_ns < 16 ? 16 : min_ns, half ? 0 : render_variant_of(d_octree != nullptr, A.tree.acc), half);
+}
+static bool feedback_enabled() { return tune_value("RT_SCHED_FEEDBACK", (float)RT_SCHED_FEEDBACK) != 0.f; }
 // the scheduling pass of rt_render (ns >= 4): pilot, tile order and — from 16 samples — the long chains and the sorted tail.
-// act == kSchedReuse: the context's workspace holds this very pass (and begin_counters has written its queue words): no launch.
-static int schedule_frame(rt_render_ctx& C, RenderArgs& A, const rt_world* world, const rt_octree* d_octree, int ns, hipStream_t st, SchedAction act, const SchedKey& key) {
+// act == kSchedReuse: the context's workspace holds this very pass (and begin_counters has written its queue words): no launch —
+// unless `refine`: the record's first hit rebuilds the pass from the counts its launch recorded (scheduled_round has dropped the record).
+static int schedule_frame(rt_render_ctx& C, RenderArgs& A, const rt_world* world, const rt_octree* d_octree, int ns, hipStream_t st, SchedAction act, const SchedKey& key, bool refine) {
     const bool classify = ns >= 16;          // long-chain pre-classification pays only when chains are long
     if (classify && world->precision != RT_PRECISION_FP16) { A.tail_list = C.d_long + (size_t)A.n_local_tiles * 64; A.tail_ws = C.d_long + (size_t)C.sched_tiles * 128; A.f_tail = tune_value("RT_F_TAIL", RT_F_TAIL); A.head_sum = (int)tune_value("RT_HEAD_SUM_SPARSE", (float)RT_HEAD_SUM_SPARSE); A.head_sum_dense = (int)tune_value("RT_HEAD_SUM_DENSE", (float)RT_HEAD_SUM_DENSE); A.head_min_load = tune_value("RT_HEAD_LOAD_DENSE", (float)RT_HEAD_LOAD_DENSE); }
-    if (act != kSchedReuse) {
+    if (refine) {
+        RT_TRY(launch_count_order(A, C.d_iters, C.d_cost, C.d_order, C.d_flags, C.d_long, tune_value("RT_FB_SOLO_FRAC", RT_FB_SOLO_FRAC),
+                                  (int)tune_value("RT_FB_SOLO_CAP_DEN", (float)RT_FB_SOLO_CAP_DEN), C.d_kept + kSchedKeptWords, st));
+        RT_TRY(launch_keep_counters(A.queue, C.d_kept, st));
+        sched_keep_refine_commit(C.keep);
+    } else if (act != kSchedReuse) {
         if (world->precision == RT_PRECISION_FP16) RT_TRY(launch_tile_order_h(A, d_octree != nullptr, C.d_cost, C.d_order, classify ? C.d_flags : nullptr, classify ? C.d_long : nullptr, st));
         else RT_TRY(launch_tile_order(A, d_octree != nullptr, C.d_cost, C.d_order, classify ? C.d_flags : nullptr, classify ? C.d_long : nullptr, st));
         if (act == kSchedCompute) {          // the pass's last kernel is behind this one on the stream; valid only after every launch succeeded
@@ -937,13 +956,24 @@ static int schedule_frame(rt_render_ctx& C, RenderArgs& A, const rt_world* world
     if (classify) { A.long_flag = C.d_flags; A.long_list = C.d_long; }
     return 0;
 }
-// round 0 of a scheduled launch (rt_render, rt_render_adaptive*): a slot, the record's decision, the counters, the scheduling pass
-static int scheduled_round(rt_render_ctx& C, RenderArgs& A, const rt_world* world, const rt_octree* d_octree, int ns, bool sched, bool cap, hipStream_t st) {
+// round 0 of a scheduled launch (rt_render, rt_render_adaptive*): a slot, the record's decision, the counters, the scheduling pass.
+// record: the launch is an rt_render (k_render MODE 0 stores the counts of the measured pass): when it computes and keeps a pass and
+// passes the gate, A.iters_out is set — the caller reports the render kernel's launch with sched_keep_counts.
+static int scheduled_round(rt_render_ctx& C, RenderArgs& A, const rt_world* world, const rt_octree* d_octree, int ns, bool sched, bool cap, hipStream_t st, bool record = false) {
     A.queue = next_slot(C);
     SchedKey key; SchedAction act = kSchedBypass;
-    if (sched) RT_TRY(schedule_decide(C, A, world, d_octree, ns, cap, key, act));
-    RT_TRY(begin_counters(C, A, act, st));
-    if (sched) RT_TRY(schedule_frame(C, A, world, d_octree, ns, st, act, key));
+    bool refine = false;
+    if (sched) {
+        RT_TRY(schedule_decide(C, A, world, d_octree, ns, cap, key, act));
+        const bool take_part = act != kSchedBypass && feedback_enabled() && feedback_gate(A, world, d_octree, ns);
+        if (act == kSchedReuse && sched_keep_refine_due(C.keep, feedback_enabled(), take_part)) { refine = true; sched_keep_refine_begin(C.keep); }
+        if (act == kSchedCompute && record && take_part) {
+            RT_TRY(hipMemsetAsync(C.d_iters, 0, sizeof(unsigned short) * (size_t)A.n_local_tiles * 64, st));      // (the padding of a part's edge tiles is never written)
+            A.iters_out = C.d_iters;
+        }
+    }
+    RT_TRY(begin_counters(C, A, refine ? kSchedCompute : act, st));
+    if (sched) RT_TRY(schedule_frame(C, A, world, d_octree, ns, st, act, key, refine));
     return 0;
 }
 
@@ -977,7 +1007,7 @@ static int render_common(rt_render_ctx* ctx, void* fb, int max_x, int max_y, int
         RT_TRY(ctx_reserve(C, A.n_local_tiles));
     }
     if (!cap) RT_TRY(ctx_wait_previous(C, st));
-    RT_TRY(scheduled_round(C, A, world, d_octree, ns, sched, cap, st));
+    RT_TRY(scheduled_round(C, A, world, d_octree, ns, sched, cap, st, mode == 0));
     C.last_queue = A.queue;
     if (mode == 1) {
         // render_progressive is one sample per launch (main.cu:119-142, called once per displayed frame, :275).  The pass with
@@ -999,6 +1029,7 @@ static int render_common(rt_render_ctx* ctx, void* fb, int max_x, int max_y, int
     if (world->precision == RT_PRECISION_FP16) RT_TRY(launch_render_h(A, tree, mode, st));
     else if (world->arith == RT_ARITH_CONTRACT) RT_TRY(fmac::launch_render(A, tree, mode, st));
     else RT_TRY(launch_render(A, tree, mode, st));
+    if (A.iters_out) { sched_keep_counts(C.keep); C.iters_n = rt_part_pixels(max_x, max_y, part); }      // (never inside a capture: that launch bypasses the record)
     if (cap) return 0;
     RT_TRY(ctx_timed_end(C, st));
     return ctx_mark_done(C, st);
@@ -1067,6 +1098,33 @@ int rt_render_ctx_schedule_reuse(rt_render_ctx* C, uint64_t* reused, uint64_t* c
 int rt_world_render_schedule_reuse(rt_world* W, uint64_t* reused, uint64_t* computed) {
     if (!W) return RT_EINVAL;
     return rt_render_ctx_schedule_reuse(&W->z->ctx, reused, computed);
+}
+// the measured pass of the context's record: how often the context rebuilt a pass from recorded counts, and the state of its record
+int rt_render_ctx_schedule_feedback(rt_render_ctx* C, uint64_t* refined, uint32_t* out, int n) {
+    if (!C || !refined || n < 0 || (n > 0 && !out)) return RT_EINVAL;
+    *refined = C->keep.refinements;
+    uint32_t w[RT_FEEDBACK_WORDS] = {C->keep.valid && C->keep.has_counts ? 1u : 0u, C->keep.valid && C->keep.refined ? 1u : 0u, 0u, 0u};
+    if (w[1] && n > 2) {
+        if (C->has_done) RT_TRY(hipEventSynchronize(C->done));
+        RT_TRY(hipMemcpy(w + 2, C->d_kept + kSchedKeptWords, 2 * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    }
+    for (int k = 0; k < n && k < RT_FEEDBACK_WORDS; ++k) out[k] = w[k];
+    return 0;
+}
+int rt_world_render_schedule_feedback(rt_world* W, uint64_t* refined, uint32_t* out, int n) {
+    if (!W) return RT_EINVAL;
+    return rt_render_ctx_schedule_feedback(&W->z->ctx, refined, out, n);
+}
+// a copy of the counts the record's launch left, one per buffer element of that launch (waits for it)
+int rt_render_ctx_schedule_counts(rt_render_ctx* C, uint16_t* out, int64_t n) {
+    if (!C || !out || n < 0) return RT_EINVAL;
+    if (!C->keep.valid || !C->keep.has_counts || !C->d_iters || n != C->iters_n) return RT_EINVAL;
+    if (C->has_done) RT_TRY(hipEventSynchronize(C->done));
+    return (int)hipMemcpy(out, C->d_iters, sizeof(uint16_t) * (size_t)n, hipMemcpyDeviceToHost);
+}
+int rt_world_render_schedule_counts(rt_world* W, uint16_t* out, int64_t n) {
+    if (!W) return RT_EINVAL;
+    return rt_render_ctx_schedule_counts(&W->z->ctx, out, n);
 }
 int rt_world_render_times(rt_world* W, float* ms_out, int max, int* count) {
     if (!W || !ms_out || !count || max < 0) return RT_EINVAL;
@@ -1630,6 +1688,7 @@ int rt_debug_stats(unsigned long long* out16, int reset) { return (int)read_stat
 int rt_debug_wp_classes(unsigned long long* out96, int reset) { return (int)read_wp_classes(out96, reset); }      // 4 live-lane classes x 24 blocks
 int rt_debug_waves(unsigned long long* out) { return (int)read_wave_dbg(out); }
 int rt_debug_pilot(int* out, int n) { return (int)read_pilot_dbg(out, n); }
+int rt_debug_chains(unsigned int* out, int n_pixels) { return (int)read_chain_dbg(out, n_pixels); }      // 8 words per pixel (rt_stats.h g_chain_dbg)
 #endif
 
 // ------------------------------------------------------------------------------------------------ output

@@ -210,6 +210,9 @@ struct RenderArgs {
     const unsigned int* ad_count;
     float* ad_sl;
     float* ad_q;
+    // the measured pass (rt_sched_keep.h "Feedback"): per buffer element (indexed like fb) the iterations the pixel took, saturating at
+    // 65535, stored by MODE 0 of k_render<true,*,4> and <true,*,5> where it ends a pixel; NULL = not recorded (every other launch)
+    unsigned short* iters_out;
 };
 
 } // namespace rt

@@ -76,6 +76,10 @@ struct rt_render_ctx {
     // that pass left in its launch's slot (kSchedKeptWords of them, behind the ring in d_queue's allocation) — a launch with an equal
     // key runs no scheduling kernel.  One record per context, shared by rt_render and round 0 of rt_render_adaptive*.
     rt::SchedKeep keep; unsigned int* d_kept = nullptr;
+    // the measured pass (rt_sched_keep.h "Feedback"): the iteration count of every buffer element of the launch that computed the record
+    // (part of the scheduling workspace: regrown and freed with d_flags), how many elements that launch had, and — behind the kept
+    // words — the two words its rebuild leaves (the largest count, the solo cap)
+    unsigned short* d_iters = nullptr; int64_t iters_n = 0;
     // tile order of a progressive sequence (rt_render_progressive): the pilot pass that the call with current_sample == 1 runs, kept
     // in buffers of its own and reused by the following passes of the same frame (p_key: the frame's SchedKey with ns = 0 and device = 0)
     int* p_cost = nullptr; unsigned int* p_order = nullptr; int64_t p_tiles = 0; bool p_valid = false; rt::SchedKey p_key;

@@ -1298,7 +1298,7 @@ __global__ __launch_bounds__(256, RT_RENDER_WAVES) void k_render(RenderArgs A) {
     int sample = 0, depth = 0;
     bool live = false;
     RT_STATS_ONLY(
-    unsigned int pix_iters = 0;
+    unsigned int pix_iters = 0, pix_alone = 0;
     unsigned long long pix_t0 = 0;
     )
 
@@ -1445,9 +1445,12 @@ __global__ __launch_bounds__(256, RT_RENDER_WAVES) void k_render(RenderArgs A) {
             const float k = (float)(1.0 / (double)(float)A.ns);          // vec3::operator/=(real_t): 1.0/t in double (vec3.h:137)
             col.x *= k; col.y *= k; col.z *= k;
             fb[0] = sqrtf(col.x); fb[1] = sqrtf(col.y); fb[2] = sqrtf(col.z);
+            // the measured pass: what this pixel cost, for the next launch of the same frame (a function of the pixel alone, not of the schedule)
+            if constexpr (TREE && (COOPG == 4 || COOPG == 5)) { if (A.iters_out) A.iters_out[idx] = (unsigned short)(iters < 65535u ? iters : 65535u); }
             RT_STATS_ONLY(
             // diagnostic build: chain length and end / start time (100 MHz ticks mod 2^24) instead of colour
             fb[0] = (float)pix_iters; fb[1] = (float)((__builtin_amdgcn_s_memrealtime() >> 4) & 0xffffffull); fb[2] = (float)((pix_t0 >> 4) & 0xffffffull);
+            if (idx < (1ll << 20)) { unsigned int* cd = g_chain_dbg + idx * 8 + 6; cd[0] = (unsigned int)pix_t0; cd[1] = pix_alone; }
             )
         } else {
             if (A.ns == 1) { fb[0] = col.x; fb[1] = col.y; fb[2] = col.z; }
@@ -1463,8 +1466,10 @@ __global__ __launch_bounds__(256, RT_RENDER_WAVES) void k_render(RenderArgs A) {
     unsigned long long dbg_thin_cyc = 0, dbg_thin_closest = 0, dbg_thin1_cyc = 0; unsigned int dbg_thin1_iters = 0; unsigned long long dbg_t_prev = TICK();
     )
     // start: pre-classified long chains first, RT_LONG_PER_WAVE per wave, in waves that are thin from the beginning
-    constexpr bool kSolo = TREE && COOPG == 5;       // (the pre-classified chains alone in their waves: very sparse grids)
-    if (kSolo && lane == 0 && begin_long_pixel(true)) solo = true;
+    // (the pre-classified chains alone in their waves: very sparse grids, whose pilot names them, and — <true,0,4> and <true,2,4>, which
+    // share a context's record — sparse grids once a measured pass has: a pilot-made pass leaves n_solo = 0 there)
+    constexpr bool kSolo = TREE && (COOPG == 5 || (COOPG == 4 && MODE != 1));
+    if (kSolo && n_solo != 0u && lane == 0 && begin_long_pixel(true)) solo = true;
     if (__ballot(live) == 0ull && lane < RT_LONG_PER_WAVE) begin_long_pixel(false);
     if (__ballot(live) != 0ull) { thin = true; __builtin_amdgcn_s_setprio(3); }
     // (every other lane takes its first pixel at the top of the loop: ONE inlined copy of the pixel switch, not three)
@@ -1535,7 +1540,7 @@ __global__ __launch_bounds__(256, RT_RENDER_WAVES) void k_render(RenderArgs A) {
         RT_STATS_ONLY(
         const unsigned long long tC1 = TICK(); st.cyc[0] += tC1 - tC0; st.cyc[2] += tC0; if (thin) dbg_thin_closest += tC1 - tC0;
         if (TREE && thin12) { th[0] += (st.cyc[4] - c4_) - tC0; th[1] += st.cyc[5] - c5_; th[2] += (st.cyc[1] - c1_) - (st.cyc[5] - c5_); th[3] += st.cyc[3] - c3_; }
-        if (live) { ++pix_iters; }
+        if (live) { ++pix_iters; if (__popcll(__ballot(live)) <= 2) ++pix_alone; }
         )
         if (live && !(TREE && ts.pending)) {
             ++iters;
@@ -1556,6 +1561,12 @@ __global__ __launch_bounds__(256, RT_RENDER_WAVES) void k_render(RenderArgs A) {
                 (void)lum;
                 ++sample; depth = 0; att = {1.0f, 1.0f, 1.0f};
                 if (sample < ns) {
+                    RT_STATS_ONLY(
+                    if (MODE == 0 && idx < (1ll << 20) && (sample == ns / 3 || sample == 2 * (ns / 3))) {
+                        unsigned int* cd = g_chain_dbg + idx * 8 + (sample == ns / 3 ? 0 : 3);
+                        cd[0] = (unsigned int)__builtin_amdgcn_s_memrealtime(); cd[1] = pix_iters; cd[2] = pix_alone;
+                    }
+                    )
                     { const RenderArgs& C = *cold_args(); r = primary_ray(C.scene.cam, i, j, C.max_x, C.max_y, s); }
                     // classify after every 4th sample while enough of the chain is left for it to matter
                     // ... long from RT_LONG_RATE bounces per sample on, or — k_tile_order — when the chain this rate predicts (rate x ns) is a sizeable
@@ -1577,7 +1588,7 @@ __global__ __launch_bounds__(256, RT_RENDER_WAVES) void k_render(RenderArgs A) {
                     WPASS(WP_ENDPIX);
                     end_pixel();
                     RT_STATS_ONLY(
-                    pix_iters = 0;
+                    pix_iters = 0; pix_alone = 0;
                     )
                     STAT(st, ST_SWITCHES, 1);
                     live = false; is_long = false; is_med = false;
@@ -1831,17 +1842,8 @@ __global__ __launch_bounds__(256) void k_tile_cost(RenderArgs A, int* __restrict
 RT_DEV int cost_class(int w) { const int c = (w - 64) / 64; return c < 0 ? 0 : (c > 7 ? 7 : c); }
 
 #ifndef RT_TU_LIST
-// one thread per 2x2 block: the pilot counts of the block and its eight neighbours decide whether its pixels start as long chains.
-// A neighbour outside the frame, or in a tile of another part of a partitioned frame, counts as the block itself.
-__global__ __launch_bounds__(256) void k_long_select(RenderArgs A, const unsigned char* __restrict__ pilot, unsigned char* __restrict__ long_flag,
-                                                    unsigned int* __restrict__ long_list, int long_sum, int solo_sum, unsigned char* __restrict__ sum8) {
-    const long long g = (long long)blockIdx.x * 256 + threadIdx.x;
-    if (g >= A.n_local_tiles * 16) return;
-    const long long local_tile = g >> 4;
-    const int sub = (int)(g & 15);
-    const long long tile = part_tile(local_tile, A.part, A.nparts, A.tile_begin, A.tile_end);
-    const int tx = (int)(tile % A.tiles_x), ty = (int)(tile / A.tiles_x);
-    const int bx = tx * 4 + (sub & 3), by = ty * 4 + (sub >> 2);
+// the per-block counts of 2x2 block g (at block coordinates bx, by) and its eight neighbours, summed
+RT_DEV int block_sum3x3(const RenderArgs& A, const unsigned char* __restrict__ pilot, long long g, int bx, int by) {
     const int own = pilot[g];
     int sum = 0;
 #pragma unroll
@@ -1856,6 +1858,20 @@ __global__ __launch_bounds__(256) void k_long_select(RenderArgs A, const unsigne
             }
             sum += v;
         }
+    return sum;
+}
+// one thread per 2x2 block: the pilot counts of the block and its eight neighbours decide whether its pixels start as long chains.
+// A neighbour outside the frame, or in a tile of another part of a partitioned frame, counts as the block itself.
+__global__ __launch_bounds__(256) void k_long_select(RenderArgs A, const unsigned char* __restrict__ pilot, unsigned char* __restrict__ long_flag,
+                                                    unsigned int* __restrict__ long_list, int long_sum, int solo_sum, unsigned char* __restrict__ sum8) {
+    const long long g = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (g >= A.n_local_tiles * 16) return;
+    const long long local_tile = g >> 4;
+    const int sub = (int)(g & 15);
+    const long long tile = part_tile(local_tile, A.part, A.nparts, A.tile_begin, A.tile_end);
+    const int tx = (int)(tile % A.tiles_x), ty = (int)(tile / A.tiles_x);
+    const int bx = tx * 4 + (sub & 3), by = ty * 4 + (sub >> 2);
+    const int sum = block_sum3x3(A, pilot, g, bx, by);
     if (sum8) sum8[g] = (unsigned char)(sum < 255 ? sum : 255);                    // for the tail sort (k_tail_hist / k_tail_scatter)
     // (k_tile_order, which runs first, may have lowered the threshold: a chain is long relative to the launch's load per lane)
     const int abs_sum = (int)A.queue[kQueueThr + 1];
@@ -1871,6 +1887,71 @@ __global__ __launch_bounds__(256) void k_long_select(RenderArgs A, const unsigne
         if (is_long && in_img) {
             if (sum >= solo_sum) { const unsigned int pos = atomicAdd(A.queue + 4, 1u); long_list[A.n_local_tiles * 64 - 1 - pos] = (unsigned int)pid; }
             else { const unsigned int pos = atomicAdd(A.queue + 2, 1u); long_list[pos] = (unsigned int)pid; }
+        }
+    }
+}
+
+// ---- the measured pass (rt_sched_keep.h "Feedback"): the scheduling pass from the iteration counts the previous launch of this very
+// frame recorded (RenderArgs::iters_out), in place of the pilot's one-sample paths.  k_count_cost takes the place of k_tile_cost and
+// writes what it writes, in its units — cost[tile] = 4 x the bounces of 32 samples = 2 x (the tile's iterations) / ns; the byte of a
+// 2x2 block = the bounces of 2 samples = (its four pixels' iterations) / (2 ns), capped at 255 — so k_tile_order and the tail sort run
+// behind it unchanged; the largest count goes to queue[kQueueMaxCount].  One wave per tile, one lane per pixel.
+constexpr int kQueueMaxCount = 6, kQueueSoloAsked = 7;      // words of the launch's slot that only this pass uses (zeroed with the slot)
+__global__ __launch_bounds__(256) void k_count_cost(RenderArgs A, const unsigned short* __restrict__ iters, int* __restrict__ cost, unsigned char* __restrict__ pilot) {
+    const int lane = threadIdx.x & 63;
+    const long long local_tile = (long long)blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (local_tile >= A.n_local_tiles) return;                                      // (wave-uniform)
+    const long long tile = part_tile(local_tile, A.part, A.nparts, A.tile_begin, A.tile_end);
+    const int tx = (int)(tile % A.tiles_x), ty = (int)(tile / A.tiles_x);
+    const int px = lane & 7, py = lane >> 3;
+    const int i = tx * 8 + px, j = ty * 8 + py;
+    const bool in_img = (i < A.max_x) && (j < A.max_y);
+    const long long idx = part_whole(A.nparts, A.tile_begin, A.tile_end) ? (long long)j * A.max_x + i : local_tile * 64 + lane;
+    const unsigned int v = in_img ? (unsigned int)iters[idx] : 0u;
+    unsigned int b = v;                                                              // the 2x2 block: lanes l, l ^ 1, l ^ 8, l ^ 9
+    b += (unsigned int)__shfl_xor((int)b, 1); b += (unsigned int)__shfl_xor((int)b, 8);
+    unsigned int t = v, m = v;
+    for (int off = 32; off > 0; off >>= 1) { t += (unsigned int)__shfl_xor((int)t, off); const unsigned int o = (unsigned int)__shfl_xor((int)m, off); m = o > m ? o : m; }
+    const unsigned int ns = (unsigned int)(A.ns > 0 ? A.ns : 1);
+    if (lane == 0) { cost[local_tile] = (int)((2u * t) / ns); if (m != 0u) atomicMax(A.queue + kQueueMaxCount, m); }
+    if (((px | py) & 1) == 0) { const unsigned int c = b / (2u * ns); pilot[local_tile * 16 + (py >> 1) * 4 + (px >> 1)] = (unsigned char)(c < 255u ? c : 255u); }
+}
+// k_long_select's sibling: one thread per 2x2 block, the same 3x3 sums for the tail sort — and the long and solo chains chosen by
+// PIXEL, from its own count.  A pixel is long when its count reaches the launch's yardstick queue[kQueueThr] (the threshold k_render
+// applies in flight, k_tile_order: f_inflight x load with its floor — now known before the start); a long pixel whose count reaches
+// solo_frac x the frame's largest starts alone in a wave (listed from the end of long_list), at most solo_cap of them in the order
+// the atomics give; the others stay long.  k_render's 1/64 rule (use_long) stands as it is.  extra: [0] the largest count, [1] solo_cap.
+__global__ __launch_bounds__(256) void k_count_select(RenderArgs A, const unsigned char* __restrict__ pilot, const unsigned short* __restrict__ iters, unsigned char* __restrict__ long_flag,
+                                                     unsigned int* __restrict__ long_list, unsigned char* __restrict__ sum8, float solo_frac, unsigned int solo_cap, unsigned int* __restrict__ extra) {
+    const long long g = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (g >= A.n_local_tiles * 16) return;
+    const long long local_tile = g >> 4;
+    const int sub = (int)(g & 15);
+    const long long tile = part_tile(local_tile, A.part, A.nparts, A.tile_begin, A.tile_end);
+    const int tx = (int)(tile % A.tiles_x), ty = (int)(tile / A.tiles_x);
+    const int sum = block_sum3x3(A, pilot, g, tx * 4 + (sub & 3), ty * 4 + (sub >> 2));
+    if (sum8) sum8[g] = (unsigned char)(sum < 255 ? sum : 255);
+    const unsigned int thr = A.queue[kQueueThr], top = A.queue[kQueueMaxCount];
+    if (g == 0 && extra) { extra[0] = top; extra[1] = solo_cap; }
+    const float solo_from = solo_frac * (float)top;
+    const bool whole = part_whole(A.nparts, A.tile_begin, A.tile_end);
+    const int lx = 2 * (sub & 3), ly = 2 * (sub >> 2);
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+        const int px = lx + (q & 1), py = ly + (q >> 1);
+        const int i = tx * 8 + px, j = ty * 8 + py;
+        const bool in_img = (i < A.max_x) && (j < A.max_y);
+        const long long pid = local_tile * 64 + py * 8 + px;
+        const unsigned int count = in_img ? (unsigned int)iters[whole ? (long long)j * A.max_x + i : pid] : 0u;
+        const bool is_long = in_img && thr != 0u && count >= thr;
+        long_flag[pid] = is_long ? 1 : 0;
+        if (is_long) {
+            bool alone = false;
+            if (solo_frac > 0.f && (float)count >= solo_from) {
+                const unsigned int asked = atomicAdd(A.queue + kQueueSoloAsked, 1u);
+                if (asked < solo_cap) { alone = true; atomicAdd(A.queue + 4, 1u); long_list[A.n_local_tiles * 64 - 1 - asked] = (unsigned int)pid; }
+            }
+            if (!alone) { const unsigned int pos = atomicAdd(A.queue + 2, 1u); long_list[pos] = (unsigned int)pid; }
         }
     }
 }
@@ -2326,7 +2407,13 @@ const char* render_kernel_name(bool tree, int mode, const DevAccel& acc) {
 // after a pilot pass (k_tile_cost here, k_tile_cost_h in rt_kernels_fp16.hip) has written the tile costs and, behind the pixel flags,
 // the per-block counts: the long-chain list (if asked for) and the hand-out order of the tiles
 // (long_sum: the 3x3 pilot sum from which a block's pixels start as long chains; 0 = this translation unit's RT_PILOT_LONG_SUM)
+// (counted != NULL: the measured pass — the selection reads the recorded counts, k_count_select, instead of the pilot's sums)
+struct CountedSelect { const unsigned short* iters; float solo_frac; unsigned int solo_cap; unsigned int* extra; };
+static hipError_t select_and_order(const RenderArgs& A, int* cost, unsigned int* order, unsigned char* flags, unsigned int* long_list, hipStream_t st, int long_sum, int solo_sum, const CountedSelect* counted);
 hipError_t launch_select_and_order(const RenderArgs& A, int* cost, unsigned int* order, unsigned char* flags, unsigned int* long_list, hipStream_t st, int long_sum, int solo_sum) {
+    return select_and_order(A, cost, order, flags, long_list, st, long_sum, solo_sum, nullptr);
+}
+static hipError_t select_and_order(const RenderArgs& A, int* cost, unsigned int* order, unsigned char* flags, unsigned int* long_list, hipStream_t st, int long_sum, int solo_sum, const CountedSelect* counted) {
     // (the order kernel first: it also derives the launch's thresholds for long chains, which the selection reads)
     // flags: 64 bytes per local tile (one per pixel), 16 (the pilot's count per 2x2 block), 16 (that count summed over the block's 3x3 neighbourhood)
     const bool tail = flags && A.tail_list && A.tail_ws && A.f_tail > 0.f;
@@ -2335,7 +2422,8 @@ hipError_t launch_select_and_order(const RenderArgs& A, int* cost, unsigned int*
     if (flags) {
         const unsigned char* pilot = flags + (size_t)A.n_local_tiles * 64;
         unsigned char* sum8 = flags + (size_t)A.n_local_tiles * 80;
-        hipLaunchKernelGGL(k_long_select, dim3((unsigned)((A.n_local_tiles * 16 + 255) / 256)), dim3(256), 0, st, A, pilot, flags, long_list, long_sum > 0 ? long_sum : RT_PILOT_LONG_SUM, solo_sum, sum8);
+        if (counted) hipLaunchKernelGGL(k_count_select, dim3((unsigned)((A.n_local_tiles * 16 + 255) / 256)), dim3(256), 0, st, A, pilot, counted->iters, flags, long_list, sum8, counted->solo_frac, counted->solo_cap, counted->extra);
+        else hipLaunchKernelGGL(k_long_select, dim3((unsigned)((A.n_local_tiles * 16 + 255) / 256)), dim3(256), 0, st, A, pilot, flags, long_list, long_sum > 0 ? long_sum : RT_PILOT_LONG_SUM, solo_sum, sum8);
         if (tail) {
             const unsigned nb = (unsigned)((A.n_local_tiles * 16 + kTailChunk - 1) / kTailChunk);      // (the tail's size is known on the device only: blocks beyond it return at once)
             hipLaunchKernelGGL(k_tail_hist, dim3(nb), dim3(256), 0, st, (const unsigned int*)order, (const unsigned char*)sum8, (long long)A.n_local_tiles, (const unsigned int*)A.queue, A.tail_ws);
@@ -2374,6 +2462,22 @@ hipError_t launch_tile_order(const RenderArgs& A, bool tree, int* cost, unsigned
     { const hipError_t e = launch_pilot(A, tree, cost, pilot, nullptr, st); if (e != hipSuccess) return e; }
     // (chains in waves of their own: the variant for very sparse grids)
     return launch_select_and_order(B, cost, order, flags, long_list, st, 0, variant == 5 ? RT_PILOT_SOLO_SUM : 0x7fffffff);
+}
+
+int render_variant_of(bool tree, const DevAccel& acc) { return render_variant(tree, 0, acc); }      // (for the host's gate: rt_sched_keep.h sched_feedback_gate)
+// the measured pass (rt_sched_keep.h "Feedback") of a launch on k_render<true,*,4> or <true,*,5>: launch_tile_order with the recorded
+// counts in the pilot's place.  extra: two words of the context ([0] the largest count, [1] the solo cap = waves / solo_cap_den).
+hipError_t launch_count_order(const RenderArgs& A, const unsigned short* iters, int* cost, unsigned int* order, unsigned char* flags, unsigned int* long_list,
+                              float solo_frac, int solo_cap_den, unsigned int* extra, hipStream_t st) {
+    if (A.n_local_tiles <= 0) return hipSuccess;
+    const int variant = render_variant(true, 0, A.tree.acc);
+    if ((variant != 4 && variant != 5) || !iters || !flags || !long_list) return hipErrorInvalidValue;
+    RenderArgs B = A;
+    B.n_lanes = (int)render_grid_blocks(A, variant, 0) * 256;
+    B.head_sum = A.head_sum; B.head_min_load = 0.f;
+    hipLaunchKernelGGL(k_count_cost, dim3((unsigned)((A.n_local_tiles + 3) / 4)), dim3(256), 0, st, B, iters, cost, flags + (size_t)A.n_local_tiles * 64);
+    const CountedSelect cs{iters, solo_frac, solo_cap_den > 0 ? (unsigned int)(B.n_lanes / 64 / solo_cap_den) : 0u, extra};
+    return select_and_order(B, cost, order, flags, long_list, st, 0, 0x7fffffff, &cs);
 }
 
 // blocks of the persistent grid of k_render<true, MODE, COOPG> for this launch: what the chip holds, never more than the work

@@ -42,7 +42,13 @@ struct SchedKeep {
     bool captured = false;      // a scheduling pass of this context has been captured into a graph: off for the rest of its life
     SchedKey key;
     uint64_t reused = 0, computed = 0;      // calls that reused the record / passes issued (captured ones count where they are captured)
+    // the measured pass ("Feedback" below): the launch that computed this record also left every pixel's iteration count in the context's
+    // count buffer / the record's pass has been rebuilt from those counts / how often this context did that
+    bool has_counts = false, refined = false;
+    uint64_t refinements = 0;
 };
+// whatever ends a record ends its counts: they are counts of that key's pixels
+inline void sched_keep_forget(SchedKeep& K) { K.valid = false; K.has_counts = false; K.refined = false; }
 
 // The ONE place that decides, called before the first kernel of a scheduled launch.  Every way a record is dropped or bypassed:
 //  - Drop before launching: whatever is not a hit leaves `valid` false BEFORE the pass's first kernel is launched (the pass is about to
@@ -59,9 +65,9 @@ struct SchedKeep {
 //    device = 0, compared with sched_key_equal.
 inline SchedAction sched_keep_decide(SchedKeep& K, const SchedKey& key, bool enabled, bool capturing) {
     if (capturing) K.captured = true;
-    if (capturing || K.captured || !enabled) { K.valid = false; ++K.computed; return kSchedBypass; }
+    if (capturing || K.captured || !enabled) { sched_keep_forget(K); ++K.computed; return kSchedBypass; }
     if (K.valid && sched_key_equal(K.key, key)) { ++K.reused; return kSchedReuse; }
-    K.valid = false; ++K.computed;
+    sched_keep_forget(K); ++K.computed;
     return kSchedCompute;
 }
 // after the last launch of a kSchedCompute pass (the kept words' copy included) returned success
@@ -70,6 +76,31 @@ inline void sched_keep_commit(SchedKeep& K, const SchedKey& key) {
     K.key = key; K.valid = true;
 }
 // the workspace was regrown or freed
-inline void sched_keep_drop(SchedKeep& K) { K.valid = false; }
+inline void sched_keep_drop(SchedKeep& K) { sched_keep_forget(K); }
+
+// ---- Feedback: the pass rebuilt once from the counts of the launch that computed it (DESIGN.md §5.4 "The measured pass") ----------
+// A launch that reuses a record has, by the key, just been preceded by a launch that rendered every pixel of this very frame with this
+// very sample count: k_render knows each pixel's iteration count when it ends it.  The launch that computes and keeps a pass
+// (kSchedCompute) therefore also records those counts, and the FIRST hit of that record runs the pass once more, from the counts instead
+// of the pilot's 18 one-sample paths per neighbourhood.  Later hits reuse the rebuilt pass like any other.  One rebuild per record.
+//
+// The gate — which launches take part at all: binary32, the sparse-grid kernels k_render<true,*,4> and <true,*,5> (the two whose launches
+// end when their longest pixel does), and at least `min_ns` samples (RT_FEEDBACK_MIN_NS): below that chains do not bound
+// a launch, and the hits of such launches keep the pilot's words.
+inline bool sched_feedback_gate(int ns, int min_ns, int render_variant, bool half) { return !half && ns >= min_ns && (render_variant == 4 || render_variant == 5); }
+// the launch of a kSchedCompute pass that passed the gate was given the count buffer, and its render kernel was launched successfully
+inline void sched_keep_counts(SchedKeep& K) { if (K.valid && !K.captured) K.has_counts = true; }
+// after sched_keep_decide returned kSchedReuse: is the rebuild due?  (enabled: RT_SCHED_FEEDBACK; gate: sched_feedback_gate of this launch)
+inline bool sched_keep_refine_due(const SchedKeep& K, bool enabled, bool gate) {
+    return K.valid && K.has_counts && !K.refined && !K.captured && enabled && gate;
+}
+// before the rebuild's first kernel: it overwrites the workspace, so until sched_keep_refine_commit there is NO valid record — a
+// rebuild whose launches did not all succeed leaves the next call a miss (which forgets the counts too)
+inline void sched_keep_refine_begin(SchedKeep& K) { K.valid = false; }
+// after the rebuild's last launch (the kept words' copy included) returned success; the key is the record's own
+inline void sched_keep_refine_commit(SchedKeep& K) {
+    if (K.captured || !K.has_counts) return;
+    K.valid = true; K.refined = true; ++K.refinements;
+}
 
 }  // namespace rt

@@ -23,6 +23,9 @@ enum { ST_RAYS, ST_FAST, ST_SLOW, ST_TIE, ST_COLS, ST_TESTS, ST_DISCPOS, ST_OFFE
 __device__ unsigned long long g_stats[ST_N];
 __device__ int g_pilot_dbg[1 << 20];                  // per 2x2 block (tile * 16 + block): the pilot's bounce count
 __device__ unsigned long long g_wave_dbg[8192 * 4];   // per wave: end time (100 MHz ticks since launch), loop iters, thin iters, long pixels
+// per pixel of a whole frame (row-major, the first 2^20): 100 MHz ticks, loop iterations and iterations in a wave of at most two live lanes
+// when a third and two thirds of the samples were done, then the last two at the pixel's end (tools/chain_pace.py)
+__device__ unsigned int g_chain_dbg[(1 << 20) * 8];
 struct Stats { unsigned int c[ST_N]; unsigned long long cyc[8]; };
 #ifdef RT_STATS_LIGHT
 #define STAT(st, k, v) ((void)0)
@@ -52,6 +55,7 @@ __shared__ int s_wp_cls[4];
 #define RT_STATS_ONLY(...) __VA_ARGS__
 #define RT_STATS_READERS \
 hipError_t read_pilot_dbg(int* out, int n) { return hipMemcpyFromSymbol(out, HIP_SYMBOL(g_pilot_dbg), sizeof(int) * (size_t)(n < (1 << 20) ? n : (1 << 20))); } \
+hipError_t read_chain_dbg(unsigned int* out, int n_pixels) { return hipMemcpyFromSymbol(out, HIP_SYMBOL(g_chain_dbg), sizeof(unsigned int) * 8 * (size_t)(n_pixels < (1 << 20) ? n_pixels : (1 << 20))); } \
 hipError_t read_wave_dbg(unsigned long long* out) { return hipMemcpyFromSymbol(out, HIP_SYMBOL(g_wave_dbg), sizeof(unsigned long long) * 8192 * 4); } \
 hipError_t read_wp_classes(unsigned long long* out, int reset) { \
     hipError_t e = hipMemcpyFromSymbol(out, HIP_SYMBOL(g_wp_cls), sizeof(unsigned long long) * 4 * kWpBlocks); \

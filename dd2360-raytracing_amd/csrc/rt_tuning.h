@@ -118,6 +118,24 @@
 #ifndef RT_SCHED_CACHE
 #define RT_SCHED_CACHE 1
 #endif
+// The measured pass (rt_sched_keep.h "Feedback"): the launch that computes a kept pass also records every pixel's iteration count, and the
+// first launch that reuses the record rebuilds the pass from those counts — tile costs, per-block counts, long chains chosen by pixel
+// against the launch's own in-flight threshold, and the longest of them started ALONE in a wave, on sparse grids too (k_render<true,*,4>).
+// 0 = the pilot's pass on every hit, as before round 18: the A/B switch on one build and the tests' reference (RT_SCHED_FEEDBACK=0).
+// What was measured: HISTORY.md round 18.
+#ifndef RT_SCHED_FEEDBACK
+#define RT_SCHED_FEEDBACK 1
+#endif
+#ifndef RT_FEEDBACK_MIN_NS
+#define RT_FEEDBACK_MIN_NS 32   // launches of fewer samples per pixel neither record nor rebuild: their chains do not bound them (and never below 16, where chains are first classified)
+#endif
+#ifndef RT_FB_SOLO_FRAC
+#define RT_FB_SOLO_FRAC 0.75f   // a long pixel whose count reaches this share of the frame's largest starts alone in a wave; 0 = none.  Step ms, medians of 5, re-seeded steps (pilot's pass: C3 12.97, C2 9.21):
+#endif                          // C3 0: 13.57, 0.6 (152 candidates, cap 128): 13.53, 0.7: 11.97, 0.75: 11.92, 0.8: 12.00, 0.9: 12.61; C2 0: 10.49, 0.6: 8.54, 0.7: 8.69, 0.75: 8.91, 0.8: 9.28, 0.9: 10.10.
+                                // Continuing RNG states (C3, frames 3-12 of 12, parent 12.90 / 13.00): 0.75: 12.39, 0.7: 12.55, 0.65 with cap 1/16: 12.53, 0.6 with cap 1/16: 12.66, 0.5 with cap 1/16: 13.47
+#ifndef RT_FB_SOLO_CAP_DEN
+#define RT_FB_SOLO_CAP_DEN 32   // ... at most (waves of the grid) / this many of them, whichever the atomics admit first; the others stay long.  At 0.75 the cap does not bind on C3 (19 of 128) or C2: 16: C3 12.08, C2 9.14; 64: 12.09 / 8.84 — run-to-run
+#endif                          // noise; with 0.6: cap 1/16 (all 152 alone) C3 12.09, C2 8.71; 0.5 with 1/16: C3 13.94, C2 8.58
 #ifndef RT_PROG_OWN
 #define RT_PROG_OWN 64          // render_progressive: pixel slots a wave owns before it takes chunks of 64 from the counter.  C3, ms per pass: 0: 0.645, 64: 0.567, 128: 0.611 (one request per lane and pixel: 1.05)
 #endif

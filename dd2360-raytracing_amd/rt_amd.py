@@ -44,6 +44,8 @@ WHOLE = Partition(0, 1)
 PART_RUN = 64          # rt_amd.h RT_PART_RUN: consecutive tiles per run of the tile split (tests restate the split with it)
 # rt_amd.h RT_SCHEDULE_WORDS: the words rt_render_ctx_schedule / rt_world_render_schedule copy, in this order
 SCHEDULE_FIELDS = ("inflight_thr", "static_thr", "tail_mark", "head", "head_thr", "from_end", "long_raw", "solo_raw")
+# rt_amd.h RT_FEEDBACK_WORDS: the words rt_render_ctx_schedule_feedback / rt_world_render_schedule_feedback copy, behind the rebuild count
+FEEDBACK_FIELDS = ("has_counts", "rebuilt", "max_count", "solo_cap")
 
 class Adaptive(C.Structure):
     """rt_adaptive: min_spp samples for every pixel, then `batch` more at a time for the pixels whose relative standard error of the
@@ -223,6 +225,10 @@ SYMBOLS = {
     "rt_world_render_schedule": (_i, [_vp, _vp, _i]),
     "rt_render_ctx_schedule_reuse": (_i, [_vp, _vp, _vp]),
     "rt_world_render_schedule_reuse": (_i, [_vp, _vp, _vp]),
+    "rt_render_ctx_schedule_feedback": (_i, [_vp, _vp, _vp, _i]),
+    "rt_world_render_schedule_feedback": (_i, [_vp, _vp, _vp, _i]),
+    "rt_render_ctx_schedule_counts": (_i, [_vp, _vp, C.c_int64]),
+    "rt_world_render_schedule_counts": (_i, [_vp, _vp, C.c_int64]),
     "rt_render_kernel_name": (_i, [_vp, _vp, _i, _vp, _i]),
     "rt_multi_unique_id": (_i, [_vp]),
     "rt_multi_init": (_i, [_vp, _i, _i, _vp]),
@@ -442,6 +448,19 @@ class RenderCtx:
         a, b = C.c_uint64(0), C.c_uint64(0)
         check(lib().rt_render_ctx_schedule_reuse(self.h, C.byref(a), C.byref(b)), "rt_render_ctx_schedule_reuse")
         return a.value, b.value
+
+    def schedule_feedback(self):
+        """the measured pass of the context's record (rt_render_ctx_schedule_feedback): passes rebuilt from recorded counts since the
+        context was created ("refined"), whether the record holds counts / a rebuilt pass, the frame's largest count and the solo cap"""
+        a, out = C.c_uint64(0), np.zeros(len(FEEDBACK_FIELDS), np.uint32)
+        check(lib().rt_render_ctx_schedule_feedback(self.h, C.byref(a), _np(out), len(out)), "rt_render_ctx_schedule_feedback")
+        return dict(zip(("refined",) + FEEDBACK_FIELDS, [a.value] + [int(v) for v in out]))
+
+    def schedule_counts(self, n):
+        """the iteration counts the record's launch left, one uint16 per buffer element of that launch (n of them: rt_part_pixels)"""
+        out = np.zeros(int(n), np.uint16)
+        check(lib().rt_render_ctx_schedule_counts(self.h, _np(out), int(n)), "rt_render_ctx_schedule_counts")
+        return out
 
     def close(self):
         if getattr(self, "h", None):
@@ -676,6 +695,19 @@ class World:
         a, b = C.c_uint64(0), C.c_uint64(0)
         check(lib().rt_world_render_schedule_reuse(self.h, C.byref(a), C.byref(b)), "rt_world_render_schedule_reuse")
         return a.value, b.value
+
+    def schedule_feedback(self):
+        """the measured pass of the record of this world's own context (rt_world_render_schedule_feedback): passes rebuilt from recorded counts since the
+        world was created ("refined"), whether the record holds counts / a rebuilt pass, the frame's largest count and the solo cap"""
+        a, out = C.c_uint64(0), np.zeros(len(FEEDBACK_FIELDS), np.uint32)
+        check(lib().rt_world_render_schedule_feedback(self.h, C.byref(a), _np(out), len(out)), "rt_world_render_schedule_feedback")
+        return dict(zip(("refined",) + FEEDBACK_FIELDS, [a.value] + [int(v) for v in out]))
+
+    def schedule_counts(self, n):
+        """the iteration counts the record's launch left, one uint16 per buffer element of that launch (n of them: rt_part_pixels)"""
+        out = np.zeros(int(n), np.uint16)
+        check(lib().rt_world_render_schedule_counts(self.h, _np(out), int(n)), "rt_world_render_schedule_counts")
+        return out
 
     def close(self):
         if getattr(self, "h", None):

@@ -425,6 +425,26 @@ int rt_render_ctx_schedule(rt_render_ctx* ctx, uint32_t* out, int n);
 int rt_render_ctx_schedule_reuse(rt_render_ctx* ctx, uint64_t* reused, uint64_t* computed);
 int rt_world_render_schedule_reuse(rt_world* world, uint64_t* reused, uint64_t* computed);
 
+/* The measured pass.  A launch that reuses a kept schedule has just been preceded by a launch of the very same frame with the very same
+ * sample count — which knew, when it ended a pixel, how many iterations (scatter or sky events) the pixel took.  On binary32 launches of
+ * the sparse-grid kernels (k_render<true,*,4> and <true,*,5>) with at least RT_FEEDBACK_MIN_NS samples per pixel (32), the rt_render that
+ * computes a record therefore also records those counts, 16 bits a pixel, saturating; the FIRST launch that reuses the record rebuilds
+ * the scheduling pass from them (tile order, sorted tail, the long chains chosen pixel by pixel against the launch's own in-flight
+ * threshold, the longest of them started alone in a wave), once per record; later launches reuse the rebuilt pass.  The counts are an
+ * estimate where the RNG states continue from call to call and exact where they are re-seeded.  Scheduling only: the frame and the RNG
+ * states are the same bits.  The counts end with their record.  RT_SCHED_FEEDBACK=0 in the environment turns recording and rebuilding
+ * off for the process.
+ * *refined = passes rebuilt since the context was created; out receives the first min(n, RT_FEEDBACK_WORDS) of: [0] 1 when the record
+ * holds counts, [1] 1 when its pass is a rebuilt one, and then (waits for the latest launch) [2] the largest count of the frame, [3] the
+ * most chains the rebuild would start alone (waves of the render grid / RT_FB_SOLO_CAP_DEN).
+ * rt_*_render_schedule_counts copies the record's counts into out: n must be the element count of the launch that recorded them
+ * (rt_part_pixels of its frame and partition; indexed like its fb); RT_EINVAL when the record holds none.  Waits for the latest launch. */
+#define RT_FEEDBACK_WORDS 4
+int rt_render_ctx_schedule_feedback(rt_render_ctx* ctx, uint64_t* refined, uint32_t* out, int n);
+int rt_world_render_schedule_feedback(rt_world* world, uint64_t* refined, uint32_t* out, int n);
+int rt_render_ctx_schedule_counts(rt_render_ctx* ctx, uint16_t* out, int64_t n);
+int rt_world_render_schedule_counts(rt_world* world, uint16_t* out, int64_t n);
+
 /* Reassemble a full row-major frame from nparts tile-major part buffers laid out back to back, each padded to
  * rt_part_pixels(max_x,max_y,{0,nparts}) elements (the layout an all-gather of the parts produces). */
 int rt_assemble(void* fb_full, const void* fb_parts, int max_x, int max_y, int nparts, int precision, void* stream);

@@ -1,6 +1,8 @@
 #!/bin/bash
 # A/B timing of kernel variants on the GPU box: tools/ab.sh [-c CONFIG] [-r ROUNDS] [-p] name...
-# "base" = the product library, any other name = dd2360-raytracing_amd/variants/lib_<name>.so (built by hand with -D switches).
+# "base" = the product library, any other name = dd2360-raytracing_amd/variants/lib_<name>.so (built by hand with -D switches);
+# a name with a slash = another checkout of the project, built (its own bench.py, binding and library: a parent commit whose
+# library lacks entry points that this tree's binding asks for).
 # The variants are timed in ROUNDS interleaved passes (clock / thermal drift hits all alike); prints per variant the
 # median and minimum kernel time and the median step time.  -p also runs the GPU parity suite against the LAST variant.
 # -s: time the budget selection instead (tools/adaptive_budget_study.py --select, which bench.py never runs): one table per variant,
@@ -19,8 +21,13 @@ fi
 tmp=$(mktemp)
 for ((k = 0; k < rounds; k++)); do
   for v in "$@"; do
-    if [ "$v" = base ]; then unset RT_AMD_LIB; else export RT_AMD_LIB=$root/dd2360-raytracing_amd/variants/lib_$v.so; fi
-    out=$(timeout -k 10 180 python "$root/bench.py" --config "$cfg" --steps 8 --no-cpu-baseline --no-pmc 2>/dev/null) || { echo "$v FAILED"; exit 1; }
+    tree=$root
+    case "$v" in
+      base) unset RT_AMD_LIB;;
+      */*) unset RT_AMD_LIB; tree=$(cd "$v" && pwd);;
+      *) export RT_AMD_LIB=$root/dd2360-raytracing_amd/variants/lib_$v.so;;
+    esac
+    out=$(timeout -k 10 180 python "$tree/bench.py" --config "$cfg" --steps 8 --no-cpu-baseline --no-pmc 2>/dev/null) || { echo "$v FAILED"; exit 1; }
     echo "$out" | python -c "import sys,json; d=json.loads(sys.stdin.read()); print('$v', d['ms_per_step'], d['roofline']['kernel_ms'])" >> $tmp
   done
 done

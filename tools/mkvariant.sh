@@ -18,7 +18,8 @@ cd $root
 /opt/rocm/bin/hipcc $F -c -o $obj/s.o csrc/rt_budget.hip &
 /opt/rocm/bin/hipcc $F -c -o $obj/f.o csrc/rt_frame.hip &
 /opt/rocm/bin/hipcc $F -c -o $obj/t.o csrc/rt_temporal.hip &
+/opt/rocm/bin/hipcc $F -c -o $obj/n.o csrc/rt_animate.hip &
 wait
-/opt/rocm/bin/hipcc --offload-arch=gfx950 -shared -fPIC -o variants/lib_$name.so $obj/k.o $obj/l.o $obj/c.o $obj/h.o $obj/a.o $obj/m.o $obj/b.o $obj/d.o $obj/s.o $obj/f.o $obj/t.o -ldl
+/opt/rocm/bin/hipcc --offload-arch=gfx950 -shared -fPIC -o variants/lib_$name.so $obj/k.o $obj/l.o $obj/c.o $obj/h.o $obj/a.o $obj/m.o $obj/b.o $obj/d.o $obj/s.o $obj/f.o $obj/t.o $obj/n.o -ldl
 rm -rf $obj
 echo "built variants/lib_$name.so"

@@ -1,10 +1,12 @@
 #!/bin/bash
 # tools/pmc_quick.sh CONFIG [variant]: SQ_INSTS_VALU / SALU / wave cycles of the render kernel for one config (one rocprofv3 --pmc pass)
+# (variant: a library under dd2360-raytracing_amd/variants/, or — a name with a slash — another built checkout of the project, as tools/ab.sh takes them)
 cfg=$1; v=$2
 root=$(cd "$(dirname "$0")/.." && pwd)
-if [ -n "$v" ] && [ "$v" != base ]; then export RT_AMD_LIB=$root/dd2360-raytracing_amd/variants/lib_$v.so; fi
+tree=$root
+case "$v" in ""|base) ;; */*) tree=$(cd "$v" && pwd);; *) export RT_AMD_LIB=$root/dd2360-raytracing_amd/variants/lib_$v.so;; esac
 d=$(mktemp -d /tmp/pmcq_XXXX)
-cd /tmp && TMPDIR=/tmp rocprofv3 --pmc SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_LDS SQ_INSTS_VMEM SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_WAIT_INST_ANY SQ_ACTIVE_INST_VALU --output-format csv -d $d -- python3 $root/bench.py --config $cfg --steps 2 --warmup 1 --no-cpu-baseline --no-pmc > /dev/null 2>&1
+cd /tmp && TMPDIR=/tmp rocprofv3 --pmc SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_LDS SQ_INSTS_VMEM SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_WAIT_INST_ANY SQ_ACTIVE_INST_VALU --output-format csv -d $d -- python3 $tree/bench.py --config $cfg --steps 2 --warmup 2 --no-cpu-baseline --no-pmc > /dev/null 2>&1
 python3 - $d "$cfg" "$v" <<'PY'
 import sys, glob, csv, os
 acc, n = {}, {}

@@ -79,6 +79,7 @@ if sp[4]:
     print("thin waves under load: %.1f k cycles per thin iteration (closest %.1f k); with <= 2 live lanes: %.1f k cycles per iteration (%d iterations)" % (
         sp[0] / sp[4] / 1e3, sp[1] / sp[4] / 1e3, sp[2] / max(1, sp[3]) / 1e3, sp[3]))
 cyc = raw[21:28]
+if cyc[0] == 0: sys.exit(0)          # the time-stamp build (librt_amd_stats_light.so) keeps no cycle probes: what follows is theirs
 print("wave-cycles (summed over waves): total %.0fM, closest-hit %.1f%% (fast path %.1f%%, ground %.1f%%, scan %.1f%%), shade+loop %.1f%%" % (
     cyc[0] / 1e6, 100 * cyc[1] / cyc[0], 100 * cyc[2] / cyc[0], 100 * cyc[3] / cyc[0], 100 * cyc[4] / cyc[0], 100 * cyc[5] / cyc[0]))
 print("  inside the fast path: large spheres + set-up %.1f%% of total wave-cycles" % (100 * raw[33] / cyc[0]))
