@@ -15,6 +15,7 @@
 #include <hip/hip_runtime.h>
 #include "../../include/rt_amd.h"
 #include "rt_device.h"
+#include "rt_launch.h"
 #include "rt_real.h"
 #include "rt_temporal.h"
 

@@ -1,5 +1,5 @@
 // rt_api.hip — the C-ABI of include/rt_amd.h: scene upload, octree flattening, kernel launches, PPM output.
-// Host code only (compiled by hipcc together with rt_kernels.hip into librt_amd.so).  No CPU render path exists
+// Host code only (compiled by hipcc together with the kernel files into librt_amd.so; what it calls in them: rt_launch.h).  No CPU render path exists
 // here: every compute entry point launches the gfx950 kernels or fails with the HIP error.
 #include <hip/hip_runtime.h>
 #include <atomic>
@@ -14,85 +14,9 @@
 #include <mutex>
 #include <cstdlib>
 #include "rt_handles.h"
+#include "rt_launch.h"
 #include "rt_octgeom.h"
 #include "../host/rt_image.hpp"
-
-namespace rt {
-hipError_t launch_render_init(rt_rand_state* rs, int max_x, int max_y, int part, int nparts, long long begin, long long end, hipStream_t st);
-hipError_t launch_zero_counters(unsigned int* p, int n, hipStream_t st);
-hipError_t launch_keep_counters(const unsigned int* queue, unsigned int* kept, hipStream_t st);
-hipError_t launch_restore_counters(unsigned int* queue, const unsigned int* kept, hipStream_t st);
-hipError_t launch_pilot(const RenderArgs& A, bool tree, int* cost, unsigned char* pilot, int* work, hipStream_t st);
-hipError_t launch_pilot_h(const RenderArgs& A, bool tree, int* cost, hipStream_t st);
-hipError_t launch_assemble_split(void* full, const void* parts, int max_x, int max_y, int nparts, const long long* starts, long long part_stride_px, bool half, hipStream_t st);
-hipError_t launch_render(const RenderArgs& A, bool tree, int mode, hipStream_t st);
-namespace fmac { hipError_t launch_render(const RenderArgs& A, bool tree, int mode, hipStream_t st); }      // rt_kernels_contract.hip
-hipError_t launch_tile_order(const RenderArgs& A, bool tree, int* cost, unsigned int* order, unsigned char* flags, unsigned int* long_list, hipStream_t st);
-int render_variant_of(bool tree, const DevAccel& acc);
-hipError_t launch_count_order(const RenderArgs& A, const unsigned short* iters, int* cost, unsigned int* order, unsigned char* flags, unsigned int* long_list,
-                              float solo_frac, int solo_cap_den, unsigned int* extra, hipStream_t st);
-hipError_t launch_render_h(const RenderArgs& A, bool tree, int mode, hipStream_t st);
-hipError_t launch_tile_order_h(const RenderArgs& A, bool tree, int* cost, unsigned int* order, unsigned char* flags, unsigned int* long_list, hipStream_t st);
-hipError_t launch_trace_h(const DevScene& S, const DevTree& T, bool tree, const float* rays, long long n, rt_hit_record* out, hipStream_t st);
-hipError_t launch_assemble_h(void* full, const void* parts, int max_x, int max_y, int nparts, hipStream_t st);
-hipError_t launch_trace(const DevScene& S, const DevTree& T, bool tree, const float* rays, long long n, rt_hit_record* out, hipStream_t st);
-hipError_t launch_guides(const DevScene& S, const DevTree& T, bool tree, int max_x, int max_y, rt_hit_record* out, hipStream_t st);
-hipError_t launch_denoise(float* fb_out, const float* fb_in, int max_x, int max_y, const rt_hit_record* hits, const rt_denoise_params& P,
-                          float4* work, hipStream_t st);      // rt_denoise.hip
-hipError_t launch_denoise_var(float* fb_out, const float* fb_in, int max_x, int max_y, const rt_hit_record* hits, const void* state,
-                              const rt_denoise_var_params& P, float4* work, hipStream_t st);      // rt_denoise.hip
-hipError_t launch_temporal_accumulate(void* hist_out, const void* hist_in, const rt_hit_record* hits, const rt_hit_record* hits_prev,
-                                      const rt_camera* cam_prev, const void* state, const int32_t* kind, int n_kind, int max_x, int max_y,
-                                      const rt_temporal_params& P, hipStream_t st);      // rt_temporal.hip
-hipError_t launch_denoise_hist(float* fb_out, const float* fb_in, int max_x, int max_y, const rt_hit_record* hits, const void* hist,
-                               const rt_denoise_var_params& P, float4* work, hipStream_t st);      // rt_temporal.hip
-hipError_t launch_world_set_geometry(float4* geom, float4* shade, float4* list_hot, const int32_t* list_id, const float4* src, int n, int n_list,
-                                     bool half, hipStream_t st);      // rt_animate.hip
-hipError_t launch_temporal_accumulate_moving(void* hist_out, const void* hist_in, const rt_hit_record* hits, const rt_hit_record* hits_prev,
-                                             const rt_camera* cam_prev, const float4* geom, const float4* geom_prev, const void* state,
-                                             const int32_t* kind, int n_kind, int max_x, int max_y, const rt_temporal_params& P,
-                                             hipStream_t st);      // rt_animate.hip
-hipError_t launch_assemble(float* full, const float* parts, int max_x, int max_y, int nparts, hipStream_t st);
-hipError_t launch_render_adaptive(const RenderArgs& A, bool tree, hipStream_t st);
-hipError_t launch_adapt_check(float* fb, const float* sl, const float* q, const unsigned int* list_in, const unsigned int* count_in, long long n_all,
-                              unsigned int* list_out, unsigned int* count_out, int32_t* spp, int k, bool last, float rel_error, float floor_lum,
-                              const AdaptFrame& fr, hipStream_t st);
-hipError_t launch_adapt_zero(unsigned int* p, int n, hipStream_t st);
-hipError_t launch_adapt_check_keep(float* fb, const AdaptState& s, const unsigned int* list_in, const unsigned int* count_in, long long n_all,
-                                   unsigned int* list_out, unsigned int* count_out, int32_t* spp, int k, bool last, float rel_error, float floor_lum,
-                                   const AdaptFrame& fr, hipStream_t st);
-hipError_t launch_adapt_refine_seed(float* fb, const AdaptState& s, long long n_all, unsigned int* list_out, unsigned int* count_out, int32_t* spp,
-                                    int max_spp, float rel_error, float floor_lum, const AdaptFrame& fr, hipStream_t st);
-hipError_t launch_adapt_refine_check(float* fb, const AdaptState& s, const unsigned int* list_in, const unsigned int* count_in, long long n_all,
-                                     unsigned int* list_out, unsigned int* count_out, int32_t* spp, int batch, int max_spp, float rel_error, float floor_lum,
-                                     hipStream_t st);
-size_t budget_ws_bytes(long long n, bool filtered);                    // rt_budget.hip
-hipError_t launch_budget_select_filtered(const AdaptState& s, const rt_hit_record* hits, int max_x, int max_y, const rt_denoise_var_params& P, int batch,
-                                         int max_spp, float floor_lum, unsigned int K, unsigned int* keys, float* keys_out, unsigned int* ws,
-                                         unsigned int* list, unsigned int* count, hipStream_t st);
-hipError_t launch_budget_select_temporal(const void* state, const void* hist_in, const rt_hit_record* hits, const rt_hit_record* hits_prev,
-                                         const rt_camera* cam_prev, const int32_t* kind, int n_kind, int max_x, int max_y, const rt_temporal_params& P,
-                                         int batch, int max_spp, float floor_lum, unsigned int K, unsigned int* keys, float* keys_out, unsigned int* ws,
-                                         unsigned int* list, unsigned int* count, hipStream_t st);
-hipError_t launch_budget_select(const AdaptState& s, long long n, const AdaptFrame& fr, int batch, int max_spp, float floor_lum, unsigned int K,
-                                unsigned int* keys, unsigned int* ws, unsigned int* list, unsigned int* count, hipStream_t st);
-hipError_t launch_budget_seed(float* fb, const AdaptState& s, const unsigned int* list, const unsigned int* count, unsigned int cap, hipStream_t st);
-hipError_t launch_budget_final(float* fb, const AdaptState& s, const unsigned int* list, const unsigned int* count, unsigned int cap, int32_t* spp, int batch,
-                               uint32_t* picked, hipStream_t st);
-const char* render_kernel_name(bool tree, int mode, const DevAccel& acc);
-namespace gpubuild { int build(rt_octree* O, const float4* d_geom, const int32_t* d_kind, int n, int spl, hipStream_t st); }
-const char* render_kernel_name_h(bool tree, int mode);
-#ifdef RT_H16_STATS
-hipError_t read_h16_stats(unsigned long long* out, int reset);
-#endif
-#ifdef RT_STATS
-hipError_t read_stats(unsigned long long* out, int reset);
-hipError_t read_wp_classes(unsigned long long* out, int reset);
-hipError_t read_wave_dbg(unsigned long long* out);
-hipError_t read_pilot_dbg(int* out, int n);
-hipError_t read_chain_dbg(unsigned int* out, int n_pixels);
-#endif
-}
 
 using namespace rt;
 

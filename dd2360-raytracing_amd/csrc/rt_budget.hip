@@ -27,6 +27,7 @@
 #include <rocprim/device/device_radix_sort.hpp>
 #endif
 #include "rt_device.h"
+#include "rt_launch.h"
 #include "rt_temporal.h"
 
 namespace rt {
@@ -42,12 +43,6 @@ static long long budget_span(long long n) {
     return per <= 1024 ? 1024 : (per + 255) / 256 * 256;
 }
 
-// element t of a part's compact tile-major buffer lies inside the frame (adapt_in_frame of rt_kernels.hip)
-__device__ __forceinline__ bool budget_in_frame(long long t, const AdaptFrame& fr) {
-    const long long tile = part_tile(t >> 6, fr.part, fr.nparts, fr.tile_begin, fr.tile_end);
-    const int tx = (int)(tile % fr.tiles_x), ty = (int)(tile / fr.tiles_x);
-    return tx * 8 + (int)(t & 7) < fr.max_x && ty * 8 + (int)((t >> 3) & 7) < fr.max_y;
-}
 // One count per valid lane into the block's LDS histogram.  The keys of a rendered frame share their exponent bits, so most of a
 // wave meets in a few bins: up to four times, the lanes that hold the first pending lane's digit are counted with one ballot and
 // ONE LDS add; whatever is left after that (a pass over mantissa bits: all digits differ) adds for itself.
@@ -128,7 +123,7 @@ __global__ __launch_bounds__(256) void k_budget_keys(AdaptState s, long long n, 
         const bool valid = t < n;
         unsigned int key = 0u;
         if (valid) {
-            if (whole || budget_in_frame(t, fr)) {
+            if (whole || adapt_in_frame(t, fr)) {
                 const int k = s.k[t];
                 if ((long long)k + batch <= (long long)max_spp) key = __float_as_uint(adapt_priority(s.sl[t], s.q[t], k, floor_lum));
             }
@@ -241,7 +236,7 @@ __global__ __launch_bounds__(256) void k_budget_sort_pack(const unsigned int* __
     if (t == 0) *count = 0u;
     if (t < n) out[t] = ((unsigned long long)~keys[t] << 32) | (unsigned long long)t;
 }
-// the first K of the sorted keys, without those of key 0 (the wave's picked lanes append with one atomic, adapt_append of rt_kernels.hip)
+// the first K of the sorted keys, without those of key 0 (the wave's picked lanes append with one atomic, adapt_append of rt_adaptive.hip)
 __global__ __launch_bounds__(256) void k_budget_sort_take(const unsigned long long* __restrict__ sorted, unsigned int K, unsigned int* __restrict__ list,
                                                           unsigned int* __restrict__ count) {
     const long long t = (long long)blockIdx.x * 256 + threadIdx.x;
@@ -457,8 +452,6 @@ __global__ __launch_bounds__(256) void k_budget_keys_filtered(AdaptState s, cons
     if (hist && cnt) atomicAdd(&hist[threadIdx.x], cnt);
 }
 #else
-hipError_t launch_denoise_var_level0(const float* fb_in, int max_x, int max_y, const rt_hit_record* hits, const void* state,
-                                     const rt_denoise_var_params& P, float4* work, hipStream_t st);      // rt_denoise.hip
 // the third kernel of the unfused variant: y = what level 0 left, (y, v') or .w < 0 for a pass-through pixel; laid out as k_budget_keys
 __global__ __launch_bounds__(256) void k_budget_keys_from_level(const float4* __restrict__ y, AdaptState s, long long n, long long span, int batch, int max_spp,
                                                                 float floor_lum, unsigned int* __restrict__ keys, float* __restrict__ keys_out,

@@ -26,6 +26,7 @@
 #include <limits>
 #include <new>
 #include "rt_handles.h"
+#include "rt_launch.h"
 #include "rt_octgeom.h"
 
 namespace rt {

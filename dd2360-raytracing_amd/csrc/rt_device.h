@@ -1,4 +1,5 @@
-// rt_device.h — device-side data layout shared by the kernels (rt_kernels.hip) and the uploader (rt_api.hip).
+// rt_device.h — device-side data layout shared by the kernels (rt_kernels.hip and its neighbours) and the uploader (rt_api.hip),
+// and the few device helpers that more than one kernel file uses (the partition's tile mapping, adapt_in_frame, wave_excl_scan).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -48,6 +49,12 @@ __host__ __device__ inline bool part_has(long long tile, int part, int nparts, l
 }
 // the frame and the part an adaptive check runs over (k_adapt_check: which elements of a compact part buffer are padding)
 struct AdaptFrame { int max_x, max_y, tiles_x, part, nparts; long long tile_begin, tile_end; };
+// element t of a part's compact tile-major buffer lies inside the frame (the elements of edge tiles outside it are padding)
+__device__ __forceinline__ bool adapt_in_frame(long long t, const AdaptFrame& fr) {
+    const long long tile = part_tile(t >> 6, fr.part, fr.nparts, fr.tile_begin, fr.tile_end);
+    const int tx = (int)(tile % fr.tiles_x), ty = (int)(tile / fr.tiles_x);
+    return tx * 8 + (int)(t & 7) < fr.max_x && ty * 8 + (int)((t >> 3) & 7) < fr.max_y;
+}
 // the caller's refinement state of rt_render_adaptive_begin / _refine, structure of arrays over the n buffer elements:
 // S_rgb[3n] (interleaved like fb), SL[n], Q[n], k[n] (int32) — RT_ADAPTIVE_STATE_BYTES = 24 per element
 struct AdaptState { float* rgb; float* sl; float* q; int32_t* k; };
@@ -175,6 +182,20 @@ struct DevTree {
     int32_t h16_np[3];
     DevAccel acc;
 };
+
+// exclusive prefix sum over the 64 lanes of a wave (the grid walk's pool, the tail sort's bins): row_shr 1/2/4/8 (a row of 16), then
+// row_bcast 15 and 31 — six DPP adds, no LDS
+static __device__ __forceinline__ unsigned wave_excl_scan(unsigned v, unsigned& total) {
+    int x = (int)v;
+    x += __builtin_amdgcn_update_dpp(0, x, 0x111, 0xf, 0xf, false);
+    x += __builtin_amdgcn_update_dpp(0, x, 0x112, 0xf, 0xf, false);
+    x += __builtin_amdgcn_update_dpp(0, x, 0x114, 0xf, 0xf, false);
+    x += __builtin_amdgcn_update_dpp(0, x, 0x118, 0xf, 0xf, false);
+    x += __builtin_amdgcn_update_dpp(0, x, 0x142, 0xa, 0xf, false);     // row_bcast:15 into rows 1 and 3
+    x += __builtin_amdgcn_update_dpp(0, x, 0x143, 0xc, 0xf, false);     // row_bcast:31 into rows 2 and 3
+    total = (unsigned)__builtin_amdgcn_readlane(x, 63);
+    return (unsigned)x - v;
+}
 
 constexpr int kQueueThr = 32;
 struct RenderArgs {

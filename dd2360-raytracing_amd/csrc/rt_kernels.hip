@@ -26,22 +26,37 @@
 #include <hip/hip_runtime.h>
 #include <float.h>
 #include "rt_device.h"
+#include "rt_launch.h"
 #include "rt_tuning.h"
 #include "rt_sampling.h"
-#include "rt_sched_keep.h"
 
-// RT_TU_CONTRACT (rt_kernels_contract.hip): the same source once more with FMA contraction ALLOWED — what nvcc's default -fmad=true
-// does to the reference (Makefile:9) — in a namespace of its own, for rt_world_set_arith(RT_ARITH_CONTRACT).  Never the parity mode.
-#ifdef RT_TU_CONTRACT
+// This file is compiled three times (Makefile).  All three see the device code — what traces a ray, k_render and the other kernel
+// templates, of which a unit emits only what its launchers instantiate; the launchers at the end of the file are dealt out:
+//   the main unit (rt_kernels.o, RT_TU_MAIN, no SLP vectorisation): everything on trees and every launcher that other files call;
+//   RT_TU_LIST (rt_kernels_list.hip, with SLP vectorisation): the hitable_list launchers launch_*_list and nothing else;
+//   RT_TU_CONTRACT (rt_kernels_contract.hip): FMA contraction ALLOWED — what nvcc's default -fmad=true does to the reference
+//     (Makefile:9) — in namespace rt::fmac, for rt_world_set_arith(RT_ARITH_CONTRACT), never the parity mode: launch_render and
+//     the k_render<*, 0|1, *> behind it, list variants included.  The pilot, the ordering pass and everything else stay IEEE.
+// Without RT_SPLIT_LIST (the diagnostic one-unit builds: librt_amd_stats*.so, librt_amd_wpass.so) the main unit holds the list launchers too.
+// The kernels that trace no ray live in rt_schedule.hip, rt_adaptive.hip and rt_assemble.hip.
+#if defined(RT_TU_CONTRACT)
 #pragma clang fp contract(fast)
+#define RT_TU_NAMESPACE rt::fmac
+#define RT_TU_HAS_LIST 1
+#elif defined(RT_TU_LIST)
+#pragma clang fp contract(off)
+#define RT_TU_NAMESPACE rt
+#define RT_TU_HAS_LIST 1
 #else
 #pragma clang fp contract(off)
+#define RT_TU_NAMESPACE rt
+#define RT_TU_MAIN 1
+#ifndef RT_SPLIT_LIST
+#define RT_TU_HAS_LIST 1
+#endif
 #endif
 
-namespace rt {
-#ifdef RT_TU_CONTRACT
-namespace fmac {
-#endif
+namespace RT_TU_NAMESPACE {
 
 #define RT_DEV static __device__ __forceinline__
 
@@ -462,18 +477,6 @@ static_assert(kThinCols == RT_POOL_COLS_THIN, "a thin round takes the columns a 
 static_assert(sizeof(unsigned) * kWalkPool >= sizeof(uint4) * 2 * kThinWalkers && sizeof(uint2) * kWalkPool >= sizeof(uint2) * 64, "the thin round's records and slots live in pref and seg");
 struct PoolSpan { unsigned cur, end, seg_end, base, sg; int owner; RayF q; float a, abt, atm; };      // a lane's walk through one span of the pool
 RT_DEV void walk_sync() { __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront"); __builtin_amdgcn_wave_barrier(); }
-// exclusive prefix sum over the 64 lanes: row_shr 1/2/4/8 (a row of 16), then row_bcast 15 and 31 — six DPP adds, no LDS
-RT_DEV unsigned walk_excl_scan(unsigned v, unsigned& total) {
-    int x = (int)v;
-    x += __builtin_amdgcn_update_dpp(0, x, 0x111, 0xf, 0xf, false);
-    x += __builtin_amdgcn_update_dpp(0, x, 0x112, 0xf, 0xf, false);
-    x += __builtin_amdgcn_update_dpp(0, x, 0x114, 0xf, 0xf, false);
-    x += __builtin_amdgcn_update_dpp(0, x, 0x118, 0xf, 0xf, false);
-    x += __builtin_amdgcn_update_dpp(0, x, 0x142, 0xa, 0xf, false);     // row_bcast:15 into rows 1 and 3
-    x += __builtin_amdgcn_update_dpp(0, x, 0x143, 0xc, 0xf, false);     // row_bcast:31 into rows 2 and 3
-    total = (unsigned)__builtin_amdgcn_readlane(x, 63);
-    return (unsigned)x - v;
-}
 
 // one queued candidate: sphere.h:24-43's offer, eligibility as in `offer`, merged into the owner's key
 // (q, a: the owner's ray and |d|^2 — a direct round holds them in registers, the queue's candidates fetch them from L.ray)
@@ -599,7 +602,7 @@ RT_DEV void walk_pool(const DevTree& T, const float4* s_nodes, WalkLds& L, const
                 W.i += taken * step; W.cols += (unsigned)taken; W.work += (unsigned)mywork;
             }
             unsigned total;
-            const unsigned ex = walk_excl_scan(cnt, total);
+            const unsigned ex = wave_excl_scan(cnt, total);
             RT_STATS_ONLY(n_seg = (unsigned)__popcll(__ballot(cnt != 0u)); TRSTAT_ROUND(lane, n_seg, total); n_seg = 0u;)
             if (total <= 64u) {
                 dealt = true;
@@ -689,7 +692,7 @@ RT_DEV void walk_pool(const DevTree& T, const float4* s_nodes, WalkLds& L, const
                     const unsigned sidx = (unsigned)(k * 64 + lane);
                     const unsigned cnt = sidx < n_seg ? (L.seg[sidx].y & 0x3ffffffu) : 0u;
                     unsigned tot;
-                    const unsigned ex = walk_excl_scan(cnt, tot);
+                    const unsigned ex = wave_excl_scan(cnt, tot);
                     if (sidx < n_seg) L.pref[sidx] = run + ex;
                     run += tot;
                 }
@@ -887,7 +890,7 @@ RT_DEV void walk_pool_dense(const DevTree& T, const float4* s_nodes, WalkLds& L,
             unsigned total;
             {
                 const unsigned cnt = (unsigned)lane < n_seg ? (L.seg[lane].y & 0x3ffffffu) : 0u;
-                const unsigned ex = walk_excl_scan(cnt, total);
+                const unsigned ex = wave_excl_scan(cnt, total);
                 if ((unsigned)lane < n_seg) L.pref[lane] = ex;
             }
             walk_sync();
@@ -1228,27 +1231,6 @@ RT_DEV V3 sky(const RayF& r, const V3& att) {
 }
 
 // ---------------------------------------------------------------------------------------------------- kernels
-#ifndef RT_TU_LIST
-__global__ __launch_bounds__(256) void k_render_init(rt_rand_state* rand_state, int max_x, int max_y, int tiles_x, int part, int nparts, long long begin, long long end, long long n_local_tiles) {
-    const int lane = threadIdx.x & 63;
-    const long long local_tile = (long long)blockIdx.x * 4 + (threadIdx.x >> 6);
-    if (local_tile >= n_local_tiles) return;
-    const long long tile = part_tile(local_tile, part, nparts, begin, end);
-    const int tx = (int)(tile % tiles_x), ty = (int)(tile / tiles_x);
-    const int i = tx * 8 + (lane & 7), j = ty * 8 + (lane >> 3);
-    const bool inside = (i < max_x) && (j < max_y);
-    const bool whole = part_whole(nparts, begin, end);
-    if (whole && !inside) return;
-    const long long idx = whole ? (long long)j * max_x + i : local_tile * 64 + lane;
-    const int pixel_index = j * max_x + i;
-    Rng s; rng_seed(s, 1984ull + (unsigned long long)(long long)pixel_index);
-    rt_rand_state out;
-    out.d = s.d; out.v[0] = s.v0; out.v[1] = s.v1; out.v[2] = s.v2; out.v[3] = s.v3; out.v[4] = s.v4;
-    out.boxmuller_flag = 0; out.boxmuller_flag_double = 0; out.boxmuller_extra = 0.f; out.pad_ = 0; out.boxmuller_extra_double = 0.0;
-    rand_state[idx] = out;
-}
-#endif
-
 // MODE 0: render (ns samples, /ns, sqrt).  MODE 1: render_progressive (one sample, accumulate).  MODE 2: one round of
 // rt_render_adaptive — ns samples more per pixel, the running sums left behind instead of the colour (RenderArgs::ad_*); every
 // line that only MODE 2 needs sits behind `if constexpr`, so the MODE 0 / 1 instantiations compile to what they were.
@@ -1626,153 +1608,12 @@ __global__ __launch_bounds__(256, RT_RENDER_WAVES) void k_render(RenderArgs A) {
     )
 }
 
-// ---------------------------------------------------------------------------------------------------- adaptive sampling
-#if !defined(RT_TU_LIST) && !defined(RT_TU_CONTRACT)
-// The stop rule of include/rt_amd.h after k samples, one IEEE binary32 rounding per operation: rel_error > 0 and
-// k*Q - S*S <= (rel_error^2 * (k-1)) * max(S, k*floor)^2 (S, Q: sums of the samples' luminance and of its squares).  Every check calls it.
-__device__ __forceinline__ bool adapt_rule(float S, float Q, int k, float rel_error, float floor_lum) {
-    const float nk = (float)k;
-    const float d = nk * Q - S * S;
-    const float nf = nk * floor_lum;
-    const float m = S > nf ? S : nf;
-    const float tt = rel_error * rel_error;
-    return rel_error > 0.f && d <= (tt * (nk - 1.f)) * (m * m);       // NaN anywhere: false, the pixel runs on
-}
-// element t of a part's compact tile-major buffer lies inside the frame (the elements of edge tiles outside it are padding)
-__device__ __forceinline__ bool adapt_in_frame(long long t, const AdaptFrame& fr) {
-    const long long tile = part_tile(t >> 6, fr.part, fr.nparts, fr.tile_begin, fr.tile_end);
-    const int tx = (int)(tile % fr.tiles_x), ty = (int)(tile / fr.tiles_x);
-    return tx * 8 + (int)(t & 7) < fr.max_x && ty * 8 + (int)((t >> 3) & 7) < fr.max_y;
-}
-// the wave's active lanes append their pixel to list_out, one atomic per wave — the order never changes a pixel
-__device__ __forceinline__ void adapt_append(bool active, unsigned int pid, unsigned int* list_out, unsigned int* count_out) {
-    const unsigned long long mask = __ballot(active);
-    if (mask != 0ull) {
-        unsigned int base = 0;
-        if ((threadIdx.x & 63) == 0) base = atomicAdd(count_out, (unsigned int)__popcll(mask));
-        base = __shfl(base, 0);
-        const unsigned int rank = __builtin_amdgcn_mbcnt_hi((unsigned)(mask >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)mask, 0u));
-        if (active) list_out[base + rank] = pid;
-    }
-}
-// rt_render_adaptive's check after a round that left every active pixel at k samples: a pixel stops when the rule
-// holds, or when the round is the last one.  A stopped pixel gets rt_render's colour at ns = k (k_render MODE 0's end_pixel: the
-// reciprocal in double, then sqrtf) and its count; the others are appended to list_out.
-// list_in == NULL: round 0, element t of the buffer for thread t.  In a part (a compact tile-major buffer, rt_partition) the elements
-// of edge tiles that fall outside the frame are padding: round 0 never rendered them, and the check leaves them alone — no colour,
-// no count, never listed (the lists hold in-frame pixels only, so later rounds need no such test).
-// KEEP (rt_render_adaptive_begin): a stopped pixel also leaves its S_rgb and k in the caller's refinement state.
-template <bool KEEP>
-__device__ __forceinline__ void adapt_check(float* __restrict__ fb, const float* __restrict__ sl, const float* __restrict__ q,
-                                            const unsigned int* __restrict__ list_in, const unsigned int* __restrict__ count_in, long long n_all,
-                                            unsigned int* __restrict__ list_out, unsigned int* __restrict__ count_out, int32_t* __restrict__ spp,
-                                            int k, int last, float rel_error, float floor_lum, const AdaptFrame& fr, const AdaptState& keep) {
-    const long long t = (long long)blockIdx.x * 256 + threadIdx.x;
-    const long long n = count_in ? (long long)*count_in : n_all;
-    bool active = false;
-    unsigned int pid = 0;
-    bool inside = true;
-    if (!list_in && t < n && !part_whole(fr.nparts, fr.tile_begin, fr.tile_end)) {          // (adapt_in_frame, spelt out: k_adapt_check's ISA stays as it was)
-        const long long tile = part_tile(t >> 6, fr.part, fr.nparts, fr.tile_begin, fr.tile_end);
-        const int tx = (int)(tile % fr.tiles_x), ty = (int)(tile / fr.tiles_x);
-        inside = tx * 8 + (int)(t & 7) < fr.max_x && ty * 8 + (int)((t >> 3) & 7) < fr.max_y;
-    }
-    if (t < n && inside) {
-        pid = list_in ? list_in[t] : (unsigned int)t;
-        bool stop = last != 0;
-        if (!stop) stop = adapt_rule(sl[pid], q[pid], k, rel_error, floor_lum);
-        if (stop) {
-            float* f = fb + (size_t)pid * 3;
-            const float kk = (float)(1.0 / (double)(float)k);                // vec3::operator/=(real_t), as k_render MODE 0
-            if constexpr (KEEP) {
-                float* s = keep.rgb + (size_t)pid * 3;
-                s[0] = f[0]; s[1] = f[1]; s[2] = f[2];
-                keep.k[pid] = k;
-            }
-            f[0] = sqrtf(f[0] * kk); f[1] = sqrtf(f[1] * kk); f[2] = sqrtf(f[2] * kk);
-            if (spp) spp[pid] = k;
-        } else {
-            active = true;
-        }
-    }
-    adapt_append(active, pid, list_out, count_out);
-}
-__global__ __launch_bounds__(256) void k_adapt_check(float* __restrict__ fb, const float* __restrict__ sl, const float* __restrict__ q,
-                                                     const unsigned int* __restrict__ list_in, const unsigned int* __restrict__ count_in, long long n_all,
-                                                     unsigned int* __restrict__ list_out, unsigned int* __restrict__ count_out, int32_t* __restrict__ spp,
-                                                     int k, int last, float rel_error, float floor_lum, AdaptFrame fr) {
-    adapt_check<false>(fb, sl, q, list_in, count_in, n_all, list_out, count_out, spp, k, last, rel_error, floor_lum, fr, AdaptState{});
-}
-__global__ __launch_bounds__(256) void k_adapt_check_keep(float* __restrict__ fb, AdaptState s,
-                                                          const unsigned int* __restrict__ list_in, const unsigned int* __restrict__ count_in, long long n_all,
-                                                          unsigned int* __restrict__ list_out, unsigned int* __restrict__ count_out, int32_t* __restrict__ spp,
-                                                          int k, int last, float rel_error, float floor_lum, AdaptFrame fr) {
-    adapt_check<true>(fb, s.sl, s.q, list_in, count_in, n_all, list_out, count_out, spp, k, last, rel_error, floor_lum, fr, s);
-}
-
-// rt_render_adaptive_refine, before its first round: one thread per buffer element (padding skipped as in round 0's check).  A pixel
-// of the state stopped after k samples under the previous target; under the new one it stops there when k == max_spp or the rule
-// holds — fb gets its colour again from S_rgb, d_spp its count — and otherwise goes on: fb gets S_rgb (where the resumed MODE 2 round
-// reads it) and the pixel is listed.  The state itself is not written.
-__global__ __launch_bounds__(256) void k_adapt_refine_seed(float* __restrict__ fb, AdaptState s, long long n_all, unsigned int* __restrict__ list_out,
-                                                           unsigned int* __restrict__ count_out, int32_t* __restrict__ spp,
-                                                           int max_spp, float rel_error, float floor_lum, AdaptFrame fr) {
-    const long long t = (long long)blockIdx.x * 256 + threadIdx.x;
-    bool active = false;
-    const unsigned int pid = (unsigned int)t;
-    if (t < n_all && (part_whole(fr.nparts, fr.tile_begin, fr.tile_end) || adapt_in_frame(t, fr))) {
-        const int k = s.k[pid];
-        const float* S = s.rgb + (size_t)pid * 3;
-        float* f = fb + (size_t)pid * 3;
-        if (k >= max_spp || adapt_rule(s.sl[pid], s.q[pid], k, rel_error, floor_lum)) {
-            const float kk = (float)(1.0 / (double)(float)k);
-            f[0] = sqrtf(S[0] * kk); f[1] = sqrtf(S[1] * kk); f[2] = sqrtf(S[2] * kk);
-            if (spp) spp[pid] = k;
-        } else {
-            f[0] = S[0]; f[1] = S[1]; f[2] = S[2];
-            active = true;
-        }
-    }
-    adapt_append(active, pid, list_out, count_out);
-}
-// the check after a resumed round of rt_render_adaptive_refine: the listed pixels have taken `batch` samples more than the state's k.
-// k is written back every round; a pixel stops at max_spp or when the rule holds, and is finalised as k_adapt_check_keep does.
-__global__ __launch_bounds__(256) void k_adapt_refine_check(float* __restrict__ fb, AdaptState s,
-                                                            const unsigned int* __restrict__ list_in, const unsigned int* __restrict__ count_in,
-                                                            unsigned int* __restrict__ list_out, unsigned int* __restrict__ count_out, int32_t* __restrict__ spp,
-                                                            int batch, int max_spp, float rel_error, float floor_lum) {
-    const long long t = (long long)blockIdx.x * 256 + threadIdx.x;
-    bool active = false;
-    unsigned int pid = 0;
-    if (t < (long long)*count_in) {
-        pid = list_in[t];
-        const int k = s.k[pid] + batch;
-        s.k[pid] = k;
-        if (k >= max_spp || adapt_rule(s.sl[pid], s.q[pid], k, rel_error, floor_lum)) {
-            float* f = fb + (size_t)pid * 3;
-            float* S = s.rgb + (size_t)pid * 3;
-            const float kk = (float)(1.0 / (double)(float)k);
-            S[0] = f[0]; S[1] = f[1]; S[2] = f[2];
-            f[0] = sqrtf(f[0] * kk); f[1] = sqrtf(f[1] * kk); f[2] = sqrtf(f[2] * kk);
-            if (spp) spp[pid] = k;
-        } else {
-            active = true;
-        }
-    }
-    adapt_append(active, pid, list_out, count_out);
-}
-__global__ __launch_bounds__(256) void k_adapt_zero(unsigned int* p, int n) {
-    const int t = blockIdx.x * 256 + threadIdx.x;
-    if (t < n) p[t] = 0u;
-}
-#endif
-
 // ---------------------------------------------------------------------------------------------------- scheduling
 // Longest-processing-time-first hand-out order for the persistent render kernel.  A pixel is a strictly serial chain
 // (ns samples x bounces on one RNG stream); with only a few pixels per resident lane, a long chain picked up late keeps
 // a nearly empty wave running.  k_tile_cost traces one PILOT sample per pixel on a private RNG stream and counts its
-// bounces: the tile sums feed k_tile_order (8 cost classes, most expensive first, stable), and pixels whose pilot path
-// neighbourhood reaches RT_PILOT_LONG_SUM bounces (k_long_select) are listed as long chains, which the render kernel starts first, in thin waves.
+// bounces: the tile sums feed k_tile_order (rt_schedule.hip: 8 cost classes, most expensive first, stable), and pixels whose pilot path
+// neighbourhood reaches RT_PILOT_LONG_SUM bounces (k_long_select, there too) are listed as long chains, which the render kernel starts first, in thin waves.
 // All of this changes only WHICH lane renders a pixel and WHEN, never the pixel.
 template <bool TREE, int COOPG = 1>
 __global__ __launch_bounds__(256) void k_tile_cost(RenderArgs A, int* __restrict__ cost, unsigned char* __restrict__ pilot, int* __restrict__ work) {
@@ -1839,324 +1680,6 @@ __global__ __launch_bounds__(256) void k_tile_cost(RenderArgs A, int* __restrict
     }
 }
 
-RT_DEV int cost_class(int w) { const int c = (w - 64) / 64; return c < 0 ? 0 : (c > 7 ? 7 : c); }
-
-#ifndef RT_TU_LIST
-// the per-block counts of 2x2 block g (at block coordinates bx, by) and its eight neighbours, summed
-RT_DEV int block_sum3x3(const RenderArgs& A, const unsigned char* __restrict__ pilot, long long g, int bx, int by) {
-    const int own = pilot[g];
-    int sum = 0;
-#pragma unroll
-    for (int dy = -1; dy <= 1; ++dy)
-#pragma unroll
-        for (int dx = -1; dx <= 1; ++dx) {
-            const int nx_ = bx + dx, ny_ = by + dy;
-            int v = own;
-            if (nx_ >= 0 && ny_ >= 0 && nx_ < A.tiles_x * 4 && ny_ < A.tiles_y * 4) {
-                long long nl;
-                if (part_has((long long)(ny_ >> 2) * A.tiles_x + (nx_ >> 2), A.part, A.nparts, A.tile_begin, A.tile_end, nl)) v = pilot[nl * 16 + (ny_ & 3) * 4 + (nx_ & 3)];
-            }
-            sum += v;
-        }
-    return sum;
-}
-// one thread per 2x2 block: the pilot counts of the block and its eight neighbours decide whether its pixels start as long chains.
-// A neighbour outside the frame, or in a tile of another part of a partitioned frame, counts as the block itself.
-__global__ __launch_bounds__(256) void k_long_select(RenderArgs A, const unsigned char* __restrict__ pilot, unsigned char* __restrict__ long_flag,
-                                                    unsigned int* __restrict__ long_list, int long_sum, int solo_sum, unsigned char* __restrict__ sum8) {
-    const long long g = (long long)blockIdx.x * 256 + threadIdx.x;
-    if (g >= A.n_local_tiles * 16) return;
-    const long long local_tile = g >> 4;
-    const int sub = (int)(g & 15);
-    const long long tile = part_tile(local_tile, A.part, A.nparts, A.tile_begin, A.tile_end);
-    const int tx = (int)(tile % A.tiles_x), ty = (int)(tile / A.tiles_x);
-    const int bx = tx * 4 + (sub & 3), by = ty * 4 + (sub >> 2);
-    const int sum = block_sum3x3(A, pilot, g, bx, by);
-    if (sum8) sum8[g] = (unsigned char)(sum < 255 ? sum : 255);                    // for the tail sort (k_tail_hist / k_tail_scatter)
-    // (k_tile_order, which runs first, may have lowered the threshold: a chain is long relative to the launch's load per lane)
-    const int abs_sum = (int)A.queue[kQueueThr + 1];
-    const bool is_long = sum >= (abs_sum > 0 && abs_sum < long_sum ? abs_sum : long_sum);
-    const int lx = 2 * (sub & 3), ly = 2 * (sub >> 2);
-#pragma unroll
-    for (int q = 0; q < 4; ++q) {                          // the 2x2 block this pilot pixel stands for
-        const int px = lx + (q & 1), py = ly + (q >> 1);
-        const bool in_img = (tx * 8 + px < A.max_x) && (ty * 8 + py < A.max_y);
-        const long long pid = local_tile * 64 + py * 8 + px;
-        long_flag[pid] = (is_long && in_img) ? 1 : 0;
-        // the longest of them (3x3 sum >= solo_sum) are listed apart, from the end of the array: k_render starts each in a wave of its own
-        if (is_long && in_img) {
-            if (sum >= solo_sum) { const unsigned int pos = atomicAdd(A.queue + 4, 1u); long_list[A.n_local_tiles * 64 - 1 - pos] = (unsigned int)pid; }
-            else { const unsigned int pos = atomicAdd(A.queue + 2, 1u); long_list[pos] = (unsigned int)pid; }
-        }
-    }
-}
-
-// ---- the measured pass (rt_sched_keep.h "Feedback"): the scheduling pass from the iteration counts the previous launch of this very
-// frame recorded (RenderArgs::iters_out), in place of the pilot's one-sample paths.  k_count_cost takes the place of k_tile_cost and
-// writes what it writes, in its units — cost[tile] = 4 x the bounces of 32 samples = 2 x (the tile's iterations) / ns; the byte of a
-// 2x2 block = the bounces of 2 samples = (its four pixels' iterations) / (2 ns), capped at 255 — so k_tile_order and the tail sort run
-// behind it unchanged; the largest count goes to queue[kQueueMaxCount].  One wave per tile, one lane per pixel.
-constexpr int kQueueMaxCount = 6, kQueueSoloAsked = 7;      // words of the launch's slot that only this pass uses (zeroed with the slot)
-__global__ __launch_bounds__(256) void k_count_cost(RenderArgs A, const unsigned short* __restrict__ iters, int* __restrict__ cost, unsigned char* __restrict__ pilot) {
-    const int lane = threadIdx.x & 63;
-    const long long local_tile = (long long)blockIdx.x * 4 + (threadIdx.x >> 6);
-    if (local_tile >= A.n_local_tiles) return;                                      // (wave-uniform)
-    const long long tile = part_tile(local_tile, A.part, A.nparts, A.tile_begin, A.tile_end);
-    const int tx = (int)(tile % A.tiles_x), ty = (int)(tile / A.tiles_x);
-    const int px = lane & 7, py = lane >> 3;
-    const int i = tx * 8 + px, j = ty * 8 + py;
-    const bool in_img = (i < A.max_x) && (j < A.max_y);
-    const long long idx = part_whole(A.nparts, A.tile_begin, A.tile_end) ? (long long)j * A.max_x + i : local_tile * 64 + lane;
-    const unsigned int v = in_img ? (unsigned int)iters[idx] : 0u;
-    unsigned int b = v;                                                              // the 2x2 block: lanes l, l ^ 1, l ^ 8, l ^ 9
-    b += (unsigned int)__shfl_xor((int)b, 1); b += (unsigned int)__shfl_xor((int)b, 8);
-    unsigned int t = v, m = v;
-    for (int off = 32; off > 0; off >>= 1) { t += (unsigned int)__shfl_xor((int)t, off); const unsigned int o = (unsigned int)__shfl_xor((int)m, off); m = o > m ? o : m; }
-    const unsigned int ns = (unsigned int)(A.ns > 0 ? A.ns : 1);
-    if (lane == 0) { cost[local_tile] = (int)((2u * t) / ns); if (m != 0u) atomicMax(A.queue + kQueueMaxCount, m); }
-    if (((px | py) & 1) == 0) { const unsigned int c = b / (2u * ns); pilot[local_tile * 16 + (py >> 1) * 4 + (px >> 1)] = (unsigned char)(c < 255u ? c : 255u); }
-}
-// k_long_select's sibling: one thread per 2x2 block, the same 3x3 sums for the tail sort — and the long and solo chains chosen by
-// PIXEL, from its own count.  A pixel is long when its count reaches the launch's yardstick queue[kQueueThr] (the threshold k_render
-// applies in flight, k_tile_order: f_inflight x load with its floor — now known before the start); a long pixel whose count reaches
-// solo_frac x the frame's largest starts alone in a wave (listed from the end of long_list), at most solo_cap of them in the order
-// the atomics give; the others stay long.  k_render's 1/64 rule (use_long) stands as it is.  extra: [0] the largest count, [1] solo_cap.
-__global__ __launch_bounds__(256) void k_count_select(RenderArgs A, const unsigned char* __restrict__ pilot, const unsigned short* __restrict__ iters, unsigned char* __restrict__ long_flag,
-                                                     unsigned int* __restrict__ long_list, unsigned char* __restrict__ sum8, float solo_frac, unsigned int solo_cap, unsigned int* __restrict__ extra) {
-    const long long g = (long long)blockIdx.x * 256 + threadIdx.x;
-    if (g >= A.n_local_tiles * 16) return;
-    const long long local_tile = g >> 4;
-    const int sub = (int)(g & 15);
-    const long long tile = part_tile(local_tile, A.part, A.nparts, A.tile_begin, A.tile_end);
-    const int tx = (int)(tile % A.tiles_x), ty = (int)(tile / A.tiles_x);
-    const int sum = block_sum3x3(A, pilot, g, tx * 4 + (sub & 3), ty * 4 + (sub >> 2));
-    if (sum8) sum8[g] = (unsigned char)(sum < 255 ? sum : 255);
-    const unsigned int thr = A.queue[kQueueThr], top = A.queue[kQueueMaxCount];
-    if (g == 0 && extra) { extra[0] = top; extra[1] = solo_cap; }
-    const float solo_from = solo_frac * (float)top;
-    const bool whole = part_whole(A.nparts, A.tile_begin, A.tile_end);
-    const int lx = 2 * (sub & 3), ly = 2 * (sub >> 2);
-#pragma unroll
-    for (int q = 0; q < 4; ++q) {
-        const int px = lx + (q & 1), py = ly + (q >> 1);
-        const int i = tx * 8 + px, j = ty * 8 + py;
-        const bool in_img = (i < A.max_x) && (j < A.max_y);
-        const long long pid = local_tile * 64 + py * 8 + px;
-        const unsigned int count = in_img ? (unsigned int)iters[whole ? (long long)j * A.max_x + i : pid] : 0u;
-        const bool is_long = in_img && thr != 0u && count >= thr;
-        long_flag[pid] = is_long ? 1 : 0;
-        if (is_long) {
-            bool alone = false;
-            if (solo_frac > 0.f && (float)count >= solo_from) {
-                const unsigned int asked = atomicAdd(A.queue + kQueueSoloAsked, 1u);
-                if (asked < solo_cap) { alone = true; atomicAdd(A.queue + 4, 1u); long_list[A.n_local_tiles * 64 - 1 - asked] = (unsigned int)pid; }
-            }
-            if (!alone) { const unsigned int pos = atomicAdd(A.queue + 2, 1u); long_list[pos] = (unsigned int)pid; }
-        }
-    }
-}
-
-// one block of 16 waves: stable counting sort of the tiles by cost class, descending (each wave takes a contiguous chunk)
-//
-// It also sets the launch's yardstick for "long": the pilot's bounce counts predict the launch's iterations (a tile's cost is 4 x
-// the bounces of its 32 pilot samples; 64 pixels x ns samples follow them), and iterations / lanes of the persistent grid is what
-// one lane will work through — the LOAD.  A pixel whose chain is a sizeable fraction of the load decides when the launch ends
-// unless it runs in a thin wave from early on; whether 3000 bounces are long depends on the launch (C5 whole frame: load 18 000;
-// one part of eight: 2 250).  queue[kQueueThr] = in-flight threshold in iterations, queue[kQueueThr + 1] = the same as a 3x3 pilot sum (18 samples).
-__global__ __launch_bounds__(1024) void k_tile_order(const int* __restrict__ cost, unsigned int* __restrict__ order, long long n, unsigned int* __restrict__ queue,
-                                                    int ns, int n_lanes, float f_inflight, float f_static, float f_tail, long long tail_cap_tiles, unsigned int* __restrict__ tail_ws, int head_sum, float head_min_load) {
-    if (tail_ws && threadIdx.x < 512) tail_ws[threadIdx.x] = 0u;   // (the tail sort's counts and cursors: k_tail_hist / k_tail_scatter run after this kernel)
-    __shared__ int s_cnt[16][8];
-    __shared__ long long s_sum[16];
-    __shared__ long long s_ccost[16][8];
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const long long per = ((n + 15) / 16 + 63) / 64 * 64;          // tiles per wave, a multiple of 64
-    const long long lo = wave * per, hi = (lo + per < n) ? lo + per : n;
-    int cnt[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-    long long csum = 0;
-    long long ccost[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-    // (eight loads in flight per lane: one block sorts the whole frame's tiles, and a pass of dependent round trips per 64 tiles is what it costs)
-    for (long long t0 = lo + lane; t0 < hi; t0 += 512) {
-        int wv[8];
-#pragma unroll
-        for (int u = 0; u < 8; ++u) wv[u] = (t0 + 64 * u < hi) ? cost[t0 + 64 * u] : -1;
-#pragma unroll
-        for (int u = 0; u < 8; ++u) {
-            const int w = wv[u] < 0 ? 0 : wv[u];
-            const int c = wv[u] < 0 ? -1 : cost_class(w);
-            csum += w;
-#pragma unroll
-            for (int k = 0; k < 8; ++k) { cnt[k] += (c == k) ? 1 : 0; ccost[k] += (c == k) ? w : 0; }
-        }
-    }
-#pragma unroll
-    for (int k = 0; k < 8; ++k) {
-        for (int off = 32; off > 0; off >>= 1) ccost[k] += __shfl_xor(ccost[k], off);
-        if (lane == 0) s_ccost[wave][k] = ccost[k];
-    }
-#pragma unroll
-    for (int k = 0; k < 8; ++k) {
-        for (int off = 32; off > 0; off >>= 1) cnt[k] += __shfl_xor(cnt[k], off);
-        if (lane == 0) s_cnt[wave][k] = cnt[k];
-    }
-    for (int off = 32; off > 0; off >>= 1) csum += __shfl_xor(csum, off);
-    if (lane == 0) s_sum[wave] = csum;
-    __syncthreads();
-    if (threadIdx.x == 0 && queue && n_lanes > 0 && ns > 0) {       // (s_cnt / s_sum / s_ccost are complete: the barrier above)
-        long long tot = 0;
-        for (int w = 0; w < 16; ++w) tot += s_sum[w];
-        const double load = (double)tot * 0.5 * (double)ns / (double)n_lanes;          // predicted iterations per lane
-        // (floors: in a launch with a pixel or two per lane every pixel is "long" by this measure — a chain must also be long as chains go)
-        double ti = (double)f_inflight * load, tsum = 18.0 * (double)f_static * load / (double)ns;
-        if (ti < (double)RT_LONG_RATE_MIN * ns) ti = (double)RT_LONG_RATE_MIN * ns;
-        if (tsum < (double)RT_PILOT_LONG_SUM_MIN) tsum = (double)RT_PILOT_LONG_SUM_MIN;
-        // the tail of the queue: the last tiles of the order that hold f_tail of the predicted work (tiles of one class taken as alike),
-        // from a multiple of 64 on — their pixels are handed out by the tail sort's list (k_tail_hist / k_tail_scatter)
-        unsigned int tail_mark = 0u;
-        if (f_tail > 0.f && tot > 0) {
-            const double want = (1.0 - (double)f_tail) * (double)tot;
-            double cum = 0.0; long long r0 = n;
-            long long start = 0;
-#pragma unroll 1
-            for (int k = 7; k >= 0; --k) {
-                long long nk = 0, ck = 0;
-#pragma unroll 1
-                for (int w = 0; w < 16; ++w) { nk += s_cnt[w][k]; ck += s_ccost[w][k]; }
-                if (nk > 0 && cum + (double)ck >= want) { r0 = start + (long long)((want - cum) / ((double)ck / (double)nk)); break; }
-                cum += (double)ck; start += nk;
-            }
-            r0 = (r0 / 64) * 64;
-            if (r0 < n && (n - r0) <= tail_cap_tiles) tail_mark = (unsigned int)(r0 * 64 + 1);
-        }
-        queue[kQueueThr + 2] = tail_mark;
-        // the tail's pixels whose 3x3 pilot sum reaches head_sum are handed out before the tiles (k_tail_scatter counts them; 0 = none)
-        // (head_sum < 0: the pixels whose sum is AT MOST -head_sum — the list's cheap end, the sky — are handed out first instead;
-        // launches below head_min_load iterations per lane keep the whole list at the end: they need their cheapest pixels for the drain)
-        if (load < (double)head_min_load) head_sum = 0;
-        queue[kQueueThr + 4] = (tail_mark != 0u && head_sum > 0) ? (unsigned int)(head_sum > 255 ? 255 : head_sum) : (tail_mark != 0u && head_sum < 0) ? (unsigned int)(-head_sum >= 254 ? 255 : -head_sum + 1) : 0u;
-        queue[kQueueThr + 5] = (tail_mark != 0u && head_sum < 0) ? 1u : 0u;
-        queue[kQueueThr] = f_inflight > 0.f ? (unsigned int)(ti < 1.0 ? 1.0 : (ti > 4.0e9 ? 4.0e9 : ti)) : 0u;
-        queue[kQueueThr + 1] = f_static > 0.f ? (unsigned int)(tsum < 1.0 ? 1.0 : (tsum > 1.0e9 ? 1.0e9 : tsum)) : 0u;
-    }
-    // class k: after every higher class, behind the earlier waves' share.  (Computed by 128 threads into LDS: with every thread summing
-    // the 16 x 8 counts itself the kernel needed 1.1 KB of scratch per lane — for a grid of one block the runtime still sets scratch
-    // aside for the whole chip, on a slow path that cost ~80 us a launch.)
-    __shared__ int s_tot[8];
-    __shared__ int s_base[16][8];
-    if (threadIdx.x < 8) {
-        int all = 0;
-#pragma unroll 1
-        for (int w = 0; w < 16; ++w) all += s_cnt[w][threadIdx.x];
-        s_tot[threadIdx.x] = all;
-    }
-    __syncthreads();
-    if (threadIdx.x < 128) {
-        const int w0 = threadIdx.x >> 3, k0 = threadIdx.x & 7;
-        int b = 0;
-#pragma unroll 1
-        for (int k = k0 + 1; k < 8; ++k) b += s_tot[k];
-#pragma unroll 1
-        for (int w = 0; w < w0; ++w) b += s_cnt[w][k0];
-        s_base[w0][k0] = b;
-    }
-    __syncthreads();
-    int base[8];                                                   // (positions: the frame's tiles fit 31 bits many times over)
-#pragma unroll
-    for (int k = 0; k < 8; ++k) base[k] = s_base[wave][k];
-    const unsigned long long lt = (1ull << lane) - 1ull;
-    for (long long t0 = lo; t0 < hi; t0 += 512) {
-        int wv[8];
-#pragma unroll
-        for (int u = 0; u < 8; ++u) wv[u] = (t0 + 64 * u + lane < hi) ? cost[t0 + 64 * u + lane] : -1;
-#pragma unroll
-        for (int u = 0; u < 8; ++u) {
-            if (t0 + 64 * u >= hi) break;                           // (wave-uniform)
-            const long long t = t0 + 64 * u + lane;
-            const int c = wv[u] < 0 ? -1 : cost_class(wv[u]);
-#pragma unroll
-            for (int k = 0; k < 8; ++k) {
-                const unsigned long long m = __ballot(c == k);
-                if (c == k) order[base[k] + __popcll(m & lt)] = (unsigned int)t;
-                base[k] += __popcll(m);
-            }
-        }
-    }
-}
-
-// The pixels of the queue's tail (tiles of rank >= R0 in the hand-out order), sorted by the pilot's count for their 2x2 block and its
-// eight neighbours (k_long_select's sum8), most expensive first: a counting sort over the 256 values in two launches of many blocks
-// (k_tail_hist: the histogram; k_tail_scatter: every block ranks its 1024 blocks among themselves in LDS and reserves its stretch of
-// each value's range with one atomic) — as one block of 1024 threads it took 158 us of C3's 14.5 ms step, whatever its inner loop did.
-// ws: 256 counts + 256 cursors, zeroed by k_tile_order.  Which lane renders a pixel and when never changes the pixel; the order inside
-// one value is left to the atomics.
-constexpr int kTailChunk = 1024;                                     // 2x2 blocks per thread block (four per thread)
-RT_DEV int tail_key(const unsigned int* __restrict__ order, const unsigned char* __restrict__ sum8, long long r0, long long b, long long n_blocks, long long& tile) {
-    tile = b < n_blocks ? (long long)order[r0 + (b >> 4)] : -1;
-    return tile >= 0 ? 255 - (int)sum8[tile * 16 + (b & 15)] : -1;
-}
-__global__ __launch_bounds__(256) void k_tail_hist(const unsigned int* __restrict__ order, const unsigned char* __restrict__ sum8, long long n, const unsigned int* __restrict__ queue, unsigned int* __restrict__ ws) {
-    __shared__ unsigned int s_bin[256];
-    const unsigned int mark = queue[kQueueThr + 2];
-    if (mark == 0u) return;
-    const long long r0 = (long long)(mark - 1u) / 64, n_blocks = (n - r0) * 16;
-    const long long b0 = (long long)blockIdx.x * kTailChunk;
-    if (b0 >= n_blocks) return;
-    s_bin[threadIdx.x] = 0u;
-    __syncthreads();
-    int key[4]; long long tile;
-#pragma unroll
-    for (int u = 0; u < 4; ++u) key[u] = tail_key(order, sum8, r0, b0 + 256 * u + threadIdx.x, n_blocks, tile);
-#pragma unroll
-    for (int u = 0; u < 4; ++u) if (key[u] >= 0) atomicAdd(&s_bin[key[u]], 4u);
-    __syncthreads();
-    const unsigned int c = s_bin[threadIdx.x];
-    if (c != 0u) atomicAdd(&ws[threadIdx.x], c);
-}
-__global__ __launch_bounds__(256) void k_tail_scatter(const unsigned int* __restrict__ order, const unsigned char* __restrict__ sum8, unsigned int* __restrict__ tail_list,
-                                                     long long n, unsigned int* __restrict__ queue, unsigned int* __restrict__ ws) {
-    __shared__ unsigned int s_bin[256], s_base[256], s_wave[4];
-    const unsigned int mark = queue[kQueueThr + 2];
-    if (mark == 0u) return;
-    const long long r0 = (long long)(mark - 1u) / 64, n_blocks = (n - r0) * 16;
-    const long long b0 = (long long)blockIdx.x * kTailChunk;
-    if (b0 >= n_blocks) return;
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    s_bin[threadIdx.x] = 0u;
-    // where value `threadIdx.x` begins in the list: exclusive prefix over the 256 counts (a scan per wave, then the waves' totals)
-    const unsigned int cnt = ws[threadIdx.x];
-    unsigned int wtot;
-    const unsigned int ex = walk_excl_scan(cnt, wtot);
-    if (lane == 0) s_wave[wave] = wtot;
-    int key[4]; long long tile[4];
-#pragma unroll
-    for (int u = 0; u < 4; ++u) key[u] = tail_key(order, sum8, r0, b0 + 256 * u + threadIdx.x, n_blocks, tile[u]);
-    __syncthreads();
-    unsigned int start = ex;
-    for (int w = 0; w < wave; ++w) start += s_wave[w];
-    // the list's first entries — every pixel whose 3x3 sum reaches the head threshold (values 255 ... thr = bins 0 ... 255 - thr) — are
-    // handed out before the tiles: their count is where bin 256 - thr begins
-    // (from the cheap end, queue[kQueueThr + 5]: every entry whose sum is below thr — what follows the entries counted above)
-    { const unsigned int thr = queue[kQueueThr + 4];
-      if (blockIdx.x == 0 && thr != 0u && threadIdx.x == 256u - thr) queue[kQueueThr + 3] = queue[kQueueThr + 5] != 0u ? (unsigned int)(n_blocks * 4) - start : start; }
-    unsigned int local[4];
-#pragma unroll
-    for (int u = 0; u < 4; ++u) local[u] = key[u] >= 0 ? atomicAdd(&s_bin[key[u]], 4u) : 0u;
-    __syncthreads();
-    const unsigned int mine = s_bin[threadIdx.x];
-    s_base[threadIdx.x] = mine != 0u ? start + atomicAdd(&ws[256 + threadIdx.x], mine) : 0u;
-    __syncthreads();
-#pragma unroll
-    for (int u = 0; u < 4; ++u) {
-        if (key[u] < 0) continue;
-        const int sub = (int)((b0 + 256 * u + threadIdx.x) & 15);
-        const unsigned int pos = s_base[key[u]] + local[u];
-        const int lx = 2 * (sub & 3), ly = 2 * (sub >> 2);
-#pragma unroll
-        for (int q = 0; q < 4; ++q) tail_list[pos + q] = (unsigned int)(tile[u] * 64 + (ly + (q >> 1)) * 8 + lx + (q & 1));
-    }
-}
-#endif
-
 // the closest hit of one ray per lane, stored as an rt_hit_record (k_trace, k_guides): every lane of the block calls it, live or not
 // (the tree walk is a wave-wide loop); the tree is already staged in s_nodes
 template <bool TREE, int COOPG>
@@ -2197,7 +1720,6 @@ __global__ __launch_bounds__(256) void k_trace(RenderArgs A, const float* rays, 
     trace_record<TREE, COOPG>(A, s_nodes, r, live, out + gid);
 }
 
-#ifndef RT_TU_CONTRACT
 // rt_render_guides: the first hit of every pixel's centre ray, row-major (pixel_index = j*max_x + i, one lane per pixel).  The ray is
 // primary_ray's with both jitter draws replaced by 0.5 and no lens offset: a pinhole at the camera origin.
 template <bool TREE, int COOPG = 1>
@@ -2219,112 +1741,8 @@ __global__ __launch_bounds__(256) void k_guides(RenderArgs A, long long n, rt_hi
     }
     trace_record<TREE, COOPG>(A, s_nodes, r, live, out + gid);
 }
-#endif
-
-// gather of tile-major part buffers into the row-major frame (after the multi-GPU all-gather)
-#ifndef RT_TU_LIST
-__global__ __launch_bounds__(256) void k_assemble(float* full, const float* parts, int max_x, int max_y, int tiles_x, int nparts, long long part_stride_px, long long n_tiles) {
-    const int lane = threadIdx.x & 63;
-    const long long tile = (long long)blockIdx.x * 4 + (threadIdx.x >> 6);
-    if (tile >= n_tiles) return;
-    const int tx = (int)(tile % tiles_x), ty = (int)(tile / tiles_x);
-    const int i = tx * 8 + (lane & 7), j = ty * 8 + (lane >> 3);
-    if (i >= max_x || j >= max_y) return;
-    int owner; long long local_tile;
-    part_owner(tile, nparts, owner, local_tile);
-    const long long src = owner * part_stride_px + local_tile * 64 + lane;
-    const long long dst = (long long)j * max_x + i;
-    full[dst * 3 + 0] = parts[src * 3 + 0]; full[dst * 3 + 1] = parts[src * 3 + 1]; full[dst * 3 + 2] = parts[src * 3 + 2];
-}
-// its one-channel twin: the per-pixel sample counts of an adaptive multi-GPU frame (rt_multi_render_adaptive), one word per pixel
-__global__ __launch_bounds__(256) void k_assemble_spp(int32_t* full, const int32_t* parts, int max_x, int max_y, int tiles_x, int nparts, long long part_stride_px, long long n_tiles) {
-    const int lane = threadIdx.x & 63;
-    const long long tile = (long long)blockIdx.x * 4 + (threadIdx.x >> 6);
-    if (tile >= n_tiles) return;
-    const int tx = (int)(tile % tiles_x), ty = (int)(tile / tiles_x);
-    const int i = tx * 8 + (lane & 7), j = ty * 8 + (lane >> 3);
-    if (i >= max_x || j >= max_y) return;
-    int owner; long long local_tile;
-    part_owner(tile, nparts, owner, local_tile);
-    full[(long long)j * max_x + i] = parts[owner * part_stride_px + local_tile * 64 + lane];
-}
-#endif
-
-// the same for the bands of a balanced split (rt_split_balanced): band p holds the tiles [starts.s[p], starts.s[p + 1]), its buffer begins
-// part_stride_px elements behind band p - 1's.  One kernel for both precisions (T = float / uint16_t).
-#ifndef RT_TU_LIST
-template <class T>
-__global__ __launch_bounds__(256) void k_assemble_split(T* full, const T* parts, int max_x, int max_y, int tiles_x, int nparts, long long part_stride_px, SplitStarts starts) {
-    const int lane = threadIdx.x & 63;
-    const long long tile = (long long)blockIdx.x * 4 + (threadIdx.x >> 6);
-    if (tile >= starts.s[nparts]) return;
-    const int tx = (int)(tile % tiles_x), ty = (int)(tile / tiles_x);
-    const int i = tx * 8 + (lane & 7), j = ty * 8 + (lane >> 3);
-    if (i >= max_x || j >= max_y) return;
-    int owner = 0;
-    for (int p = 1; p < nparts; ++p) owner += tile >= starts.s[p] ? 1 : 0;
-    const long long src = owner * part_stride_px + (tile - starts.s[owner]) * 64 + lane;
-    const long long dst = (long long)j * max_x + i;
-    full[dst * 3 + 0] = parts[src * 3 + 0]; full[dst * 3 + 1] = parts[src * 3 + 1]; full[dst * 3 + 2] = parts[src * 3 + 2];
-}
-hipError_t launch_assemble_split(void* full, const void* parts, int max_x, int max_y, int nparts, const long long* starts, long long part_stride_px, bool half, hipStream_t st) {
-    SplitStarts S;
-    for (int p = 0; p <= nparts; ++p) S.s[p] = starts[p];
-    const int tiles_x = (max_x + 7) / 8;
-    const unsigned blocks = (unsigned)((starts[nparts] + 3) / 4);
-    if (half) hipLaunchKernelGGL((k_assemble_split<uint16_t>), dim3(blocks), dim3(256), 0, st, (uint16_t*)full, (const uint16_t*)parts, max_x, max_y, tiles_x, nparts, part_stride_px, S);
-    else hipLaunchKernelGGL((k_assemble_split<float>), dim3(blocks), dim3(256), 0, st, (float*)full, (const float*)parts, max_x, max_y, tiles_x, nparts, part_stride_px, S);
-    return hipGetLastError();
-}
-#endif
 
 // ---------------------------------------------------------------------------------------------------- launchers
-#ifndef RT_TU_LIST
-// Zeroes the work counters of a launch.  A kernel of our own instead of hipMemsetAsync: captured into a hipGraph, the memset
-// node took effect on the first replay only (ROCm 7.2) — later replays found the queue exhausted and rendered nothing.
-__global__ void k_zero_counters(unsigned int* p, int n) { if ((int)threadIdx.x < n) p[threadIdx.x] = 0u; }
-hipError_t launch_zero_counters(unsigned int* p, int n, hipStream_t st) {
-    hipLaunchKernelGGL(k_zero_counters, dim3(1), dim3(64), 0, st, p, n);
-    return hipGetLastError();
-}
-// The kept schedule (rt_sched_keep.h): the words of a launch's slot that its scheduling pass wrote and the render kernel only reads —
-// queue[2], queue[4] (long and solo counts), queue[kQueueThr .. kQueueThr + 5] — as kSchedKeptWords words of the context.
-// k_keep_counters saves them once the pass's last kernel is behind it on the stream; k_restore_counters takes the place of
-// k_zero_counters in a launch that reuses the pass: the slot's 64 words zeroed, the kept ones written.
-__device__ __forceinline__ int kept_word_slot(int k) { return k == 0 ? 2 : k == 1 ? 4 : kQueueThr + (k - 2); }
-__global__ void k_keep_counters(const unsigned int* __restrict__ queue, unsigned int* __restrict__ kept) {
-    if (threadIdx.x < (unsigned)rt::kSchedKeptWords) kept[threadIdx.x] = queue[kept_word_slot((int)threadIdx.x)];
-}
-__global__ void k_restore_counters(unsigned int* __restrict__ queue, const unsigned int* __restrict__ kept) {
-    // (one wave, one word per lane: lane t owns queue[t], so no word is written twice)
-    const int t = (int)threadIdx.x;
-    unsigned int v = 0u;
-    if (t == 2) v = kept[0];
-    else if (t == 4) v = kept[1];
-    else if (t >= kQueueThr && t < kQueueThr + 6) v = kept[2 + t - kQueueThr];
-    queue[t] = v;
-}
-hipError_t launch_keep_counters(const unsigned int* queue, unsigned int* kept, hipStream_t st) {
-    hipLaunchKernelGGL(k_keep_counters, dim3(1), dim3(64), 0, st, queue, kept);
-    return hipGetLastError();
-}
-hipError_t launch_restore_counters(unsigned int* queue, const unsigned int* kept, hipStream_t st) {
-    static_assert(kQueueThr + 6 <= 64 && rt::kSchedKeptWords == 8, "the restore kernel covers a slot of 64 words with one wave");
-    hipLaunchKernelGGL(k_restore_counters, dim3(1), dim3(64), 0, st, queue, kept);
-    return hipGetLastError();
-}
-
-hipError_t launch_render_init(rt_rand_state* rs, int max_x, int max_y, int part, int nparts, long long begin, long long end, hipStream_t st) {
-    const int tiles_x = (max_x + 7) / 8, tiles_y = (max_y + 7) / 8;
-    const long long tiles = (long long)tiles_x * tiles_y;
-    const long long local = part_local_tiles(tiles, part, nparts, begin, end);
-    if (local <= 0) return hipSuccess;
-    const unsigned blocks = (unsigned)((local + 3) / 4);
-    hipLaunchKernelGGL(k_render_init, dim3(blocks), dim3(256), 0, st, rs, max_x, max_y, tiles_x, part, nparts, begin, end, local);
-    return hipGetLastError();
-}
-#endif
-
 // LDS of a block of the tree kernels: the nodes, then one WalkLds per wave
 static size_t tree_lds_bytes(int n_nodes, bool pool = false) { return (size_t)n_nodes * sizeof(DevNode) + (pool ? 4 * sizeof(WalkLds) + kHotSlots * sizeof(float4) : 0); }
 
@@ -2340,18 +1758,9 @@ template <class K> static unsigned resident_blocks(K kernel, size_t lds) {
 
 // The hitable_list instantiations live in their own translation unit (rt_kernels_list.hip = this file with RT_TU_LIST):
 // SLP vectorisation (packed fp32, v_pk_*_f32) makes the list scan 10 % faster and the tree walk 4 % slower on gfx950, so
-// the two are compiled with different flags (Makefile).  Without RT_SPLIT_LIST (diagnostic build) everything is here.
-#if defined(RT_TU_LIST) || !defined(RT_SPLIT_LIST)
-#ifdef RT_TU_LIST
-#define RT_LIST_FN(name) name##_list
-#else
-#define RT_LIST_FN(name) static name##_list
-#endif
-hipError_t RT_LIST_FN(launch_tile_cost)(const RenderArgs& A, unsigned blocks, int* cost, unsigned char* pilot, hipStream_t st) {
-    hipLaunchKernelGGL((k_tile_cost<false>), dim3(blocks), dim3(256), 0, st, A, cost, pilot, (int*)nullptr);
-    return hipGetLastError();
-}
-hipError_t RT_LIST_FN(launch_render)(const RenderArgs& A, int mode, hipStream_t st) {
+// the two are compiled with different flags (Makefile).  The contract unit holds its own contracted k_render<false, 0|1, 1>.
+#ifdef RT_TU_HAS_LIST
+hipError_t launch_render_list(const RenderArgs& A, int mode, hipStream_t st) {
     const unsigned need = (unsigned)((A.n_local_tiles + 3) / 4);
     const unsigned cap = mode == 0 ? resident_blocks(k_render<false, 0, 1>, 0) : resident_blocks(k_render<false, 1, 1>, 0);
     const unsigned blocks = need < cap ? need : cap;
@@ -2359,31 +1768,30 @@ hipError_t RT_LIST_FN(launch_render)(const RenderArgs& A, int mode, hipStream_t 
     else hipLaunchKernelGGL((k_render<false, 1, 1>), dim3(blocks), dim3(256), 0, st, A);
     return hipGetLastError();
 }
-hipError_t RT_LIST_FN(launch_trace)(const RenderArgs& A, unsigned blocks, const float* rays, long long n, rt_hit_record* out, hipStream_t st) {
+#ifndef RT_TU_CONTRACT
+hipError_t launch_tile_cost_list(const RenderArgs& A, unsigned blocks, int* cost, unsigned char* pilot, hipStream_t st) {
+    hipLaunchKernelGGL((k_tile_cost<false>), dim3(blocks), dim3(256), 0, st, A, cost, pilot, (int*)nullptr);
+    return hipGetLastError();
+}
+hipError_t launch_trace_list(const RenderArgs& A, unsigned blocks, const float* rays, long long n, rt_hit_record* out, hipStream_t st) {
     hipLaunchKernelGGL((k_trace<false>), dim3(blocks), dim3(256), 0, st, A, rays, n, out);
     return hipGetLastError();
 }
-#ifndef RT_TU_CONTRACT
-hipError_t RT_LIST_FN(launch_guides)(const RenderArgs& A, unsigned blocks, long long n, rt_hit_record* out, hipStream_t st) {
+hipError_t launch_guides_list(const RenderArgs& A, unsigned blocks, long long n, rt_hit_record* out, hipStream_t st) {
     hipLaunchKernelGGL((k_guides<false>), dim3(blocks), dim3(256), 0, st, A, n, out);
     return hipGetLastError();
 }
-hipError_t RT_LIST_FN(launch_render_adaptive)(const RenderArgs& A, hipStream_t st) {
+hipError_t launch_render_adaptive_list(const RenderArgs& A, hipStream_t st) {
     const unsigned need = (unsigned)((A.n_local_tiles + 3) / 4);
     const unsigned cap = resident_blocks(k_render<false, 2, 1>, 0);
     hipLaunchKernelGGL((k_render<false, 2, 1>), dim3(need < cap ? need : cap), dim3(256), 0, st, A);
     return hipGetLastError();
 }
 #endif
-#else
-hipError_t launch_tile_cost_list(const RenderArgs& A, unsigned blocks, int* cost, unsigned char* pilot, hipStream_t st);
-hipError_t launch_render_list(const RenderArgs& A, int mode, hipStream_t st);
-hipError_t launch_trace_list(const RenderArgs& A, unsigned blocks, const float* rays, long long n, rt_hit_record* out, hipStream_t st);
-hipError_t launch_guides_list(const RenderArgs& A, unsigned blocks, long long n, rt_hit_record* out, hipStream_t st);
-hipError_t launch_render_adaptive_list(const RenderArgs& A, hipStream_t st);
 #endif
 
 #ifndef RT_TU_LIST
+// ---- the main unit and the contract unit: launch_render and what it needs
 // Which k_render instantiation a call launches — the ONE place that decides (launch_render and rt_render_kernel_name):
 // 0 = k_render<false,MODE,1> (list scan), 1 = k_render<true,MODE,1> (per-lane walk: trees without a candidate grid, reference
 // traversal), 4 = k_render<true,MODE,4> (sparse grids: walk_pool), 2 = k_render<true,MODE,2> (dense grids: walk_pool_dense) —
@@ -2394,6 +1802,68 @@ static int render_variant(bool tree, int mode, const DevAccel& acc) {
     if (acc.enabled) return acc.coop_groups >= 4 ? (acc.solo_chains ? 5 : 4) : 2;
     return 1;
 }
+
+// blocks of the persistent grid of k_render<true, MODE, COOPG> for this launch: what the chip holds, never more than the work
+template <int MODE, int COOPG>
+static unsigned tree_grid_blocks(const RenderArgs& A, size_t lds) {
+    const unsigned need = (unsigned)((A.n_local_tiles + 3) / 4);
+    // the occupancy query costs as much host time as the launch: remembered per thread for the last (device, LDS size) —
+    // a progressive loop issues the same launch hundreds of times
+    thread_local int c_dev = -1; thread_local size_t c_lds = 0; thread_local unsigned c_cap = 0;
+    int dev = 0;
+    if (hipGetDevice(&dev) != hipSuccess) dev = -2;
+    if (dev != c_dev || lds != c_lds || c_cap == 0) { c_cap = resident_blocks(k_render<true, MODE, COOPG>, lds); c_dev = dev; c_lds = lds; }
+    const unsigned cap = c_cap;
+    return need < cap ? need : cap;
+}
+template <int MODE, int COOPG>
+static hipError_t launch_render_tree(const RenderArgs& A, size_t lds, hipStream_t st) {
+    hipLaunchKernelGGL((k_render<true, MODE, COOPG>), dim3(tree_grid_blocks<MODE, COOPG>(A, lds)), dim3(256), lds, st, A);
+    return hipGetLastError();
+}
+
+hipError_t launch_render(const RenderArgs& A, bool tree, int mode, hipStream_t st) {
+    if (A.n_local_tiles <= 0) return hipSuccess;
+    const int variant = render_variant(tree, mode, A.tree.acc);
+    if (variant == 0) return RT_TU_NAMESPACE::launch_render_list(A, mode, st);      // (qualified: the contract unit's own, not rt::'s that the argument's namespace offers too)
+    const size_t lds = tree_lds_bytes(A.tree.n_nodes, variant != 1);                       // (the variants with a pooled walk)
+    if (variant == 5) return mode == 0 ? launch_render_tree<0, 5>(A, lds, st) : launch_render_tree<1, 5>(A, lds, st);
+    if (variant == 4) return mode == 0 ? launch_render_tree<0, 4>(A, lds, st) : launch_render_tree<1, 4>(A, lds, st);
+    if (variant == 2) return mode == 0 ? launch_render_tree<0, 2>(A, lds, st) : launch_render_tree<1, 2>(A, lds, st);
+    return mode == 0 ? launch_render_tree<0, 1>(A, lds, st) : launch_render_tree<1, 1>(A, lds, st);
+}
+#endif
+
+#ifdef RT_TU_MAIN
+// ---- the main unit alone: k_render_init and the IEEE launchers
+__global__ __launch_bounds__(256) void k_render_init(rt_rand_state* rand_state, int max_x, int max_y, int tiles_x, int part, int nparts, long long begin, long long end, long long n_local_tiles) {
+    const int lane = threadIdx.x & 63;
+    const long long local_tile = (long long)blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (local_tile >= n_local_tiles) return;
+    const long long tile = part_tile(local_tile, part, nparts, begin, end);
+    const int tx = (int)(tile % tiles_x), ty = (int)(tile / tiles_x);
+    const int i = tx * 8 + (lane & 7), j = ty * 8 + (lane >> 3);
+    const bool inside = (i < max_x) && (j < max_y);
+    const bool whole = part_whole(nparts, begin, end);
+    if (whole && !inside) return;
+    const long long idx = whole ? (long long)j * max_x + i : local_tile * 64 + lane;
+    const int pixel_index = j * max_x + i;
+    Rng s; rng_seed(s, 1984ull + (unsigned long long)(long long)pixel_index);
+    rt_rand_state out;
+    out.d = s.d; out.v[0] = s.v0; out.v[1] = s.v1; out.v[2] = s.v2; out.v[3] = s.v3; out.v[4] = s.v4;
+    out.boxmuller_flag = 0; out.boxmuller_flag_double = 0; out.boxmuller_extra = 0.f; out.pad_ = 0; out.boxmuller_extra_double = 0.0;
+    rand_state[idx] = out;
+}
+hipError_t launch_render_init(rt_rand_state* rs, int max_x, int max_y, int part, int nparts, long long begin, long long end, hipStream_t st) {
+    const int tiles_x = (max_x + 7) / 8, tiles_y = (max_y + 7) / 8;
+    const long long tiles = (long long)tiles_x * tiles_y;
+    const long long local = part_local_tiles(tiles, part, nparts, begin, end);
+    if (local <= 0) return hipSuccess;
+    const unsigned blocks = (unsigned)((local + 3) / 4);
+    hipLaunchKernelGGL(k_render_init, dim3(blocks), dim3(256), 0, st, rs, max_x, max_y, tiles_x, part, nparts, begin, end, local);
+    return hipGetLastError();
+}
+
 const char* render_kernel_name(bool tree, int mode, const DevAccel& acc) {
     switch (render_variant(tree, mode, acc)) {
         case 0: return mode == 0 ? "k_render<false,0,1>" : "k_render<false,1,1>";
@@ -2404,36 +1874,15 @@ const char* render_kernel_name(bool tree, int mode, const DevAccel& acc) {
     }
 }
 
-// after a pilot pass (k_tile_cost here, k_tile_cost_h in rt_kernels_fp16.hip) has written the tile costs and, behind the pixel flags,
-// the per-block counts: the long-chain list (if asked for) and the hand-out order of the tiles
-// (long_sum: the 3x3 pilot sum from which a block's pixels start as long chains; 0 = this translation unit's RT_PILOT_LONG_SUM)
-// (counted != NULL: the measured pass — the selection reads the recorded counts, k_count_select, instead of the pilot's sums)
-struct CountedSelect { const unsigned short* iters; float solo_frac; unsigned int solo_cap; unsigned int* extra; };
-static hipError_t select_and_order(const RenderArgs& A, int* cost, unsigned int* order, unsigned char* flags, unsigned int* long_list, hipStream_t st, int long_sum, int solo_sum, const CountedSelect* counted);
-hipError_t launch_select_and_order(const RenderArgs& A, int* cost, unsigned int* order, unsigned char* flags, unsigned int* long_list, hipStream_t st, int long_sum, int solo_sum) {
-    return select_and_order(A, cost, order, flags, long_list, st, long_sum, solo_sum, nullptr);
-}
-static hipError_t select_and_order(const RenderArgs& A, int* cost, unsigned int* order, unsigned char* flags, unsigned int* long_list, hipStream_t st, int long_sum, int solo_sum, const CountedSelect* counted) {
-    // (the order kernel first: it also derives the launch's thresholds for long chains, which the selection reads)
-    // flags: 64 bytes per local tile (one per pixel), 16 (the pilot's count per 2x2 block), 16 (that count summed over the block's 3x3 neighbourhood)
-    const bool tail = flags && A.tail_list && A.tail_ws && A.f_tail > 0.f;
-    hipLaunchKernelGGL(k_tile_order, dim3(1), dim3(1024), 0, st, (const int*)cost, order, (long long)A.n_local_tiles, A.queue, (int)A.ns, (int)A.n_lanes, A.f_inflight, A.f_static,
-                       tail ? A.f_tail : 0.f, (long long)A.n_local_tiles, tail ? A.tail_ws : (unsigned int*)nullptr, tail ? A.head_sum : 0, A.head_min_load);
-    if (flags) {
-        const unsigned char* pilot = flags + (size_t)A.n_local_tiles * 64;
-        unsigned char* sum8 = flags + (size_t)A.n_local_tiles * 80;
-        if (counted) hipLaunchKernelGGL(k_count_select, dim3((unsigned)((A.n_local_tiles * 16 + 255) / 256)), dim3(256), 0, st, A, pilot, counted->iters, flags, long_list, sum8, counted->solo_frac, counted->solo_cap, counted->extra);
-        else hipLaunchKernelGGL(k_long_select, dim3((unsigned)((A.n_local_tiles * 16 + 255) / 256)), dim3(256), 0, st, A, pilot, flags, long_list, long_sum > 0 ? long_sum : RT_PILOT_LONG_SUM, solo_sum, sum8);
-        if (tail) {
-            const unsigned nb = (unsigned)((A.n_local_tiles * 16 + kTailChunk - 1) / kTailChunk);      // (the tail's size is known on the device only: blocks beyond it return at once)
-            hipLaunchKernelGGL(k_tail_hist, dim3(nb), dim3(256), 0, st, (const unsigned int*)order, (const unsigned char*)sum8, (long long)A.n_local_tiles, (const unsigned int*)A.queue, A.tail_ws);
-            hipLaunchKernelGGL(k_tail_scatter, dim3(nb), dim3(256), 0, st, (const unsigned int*)order, (const unsigned char*)sum8, (unsigned int*)A.tail_list, (long long)A.n_local_tiles, A.queue, A.tail_ws);
-        }
-    }
-    return hipGetLastError();
+// tree_grid_blocks for a tree variant chosen at run time (the scheduling pass wants the grid's lanes before the launch)
+static unsigned render_grid_blocks(const RenderArgs& A, int variant, int mode) {
+    const size_t lds = tree_lds_bytes(A.tree.n_nodes, variant != 1);
+    if (variant == 5) return mode == 0 ? tree_grid_blocks<0, 5>(A, lds) : tree_grid_blocks<1, 5>(A, lds);
+    if (variant == 4) return mode == 0 ? tree_grid_blocks<0, 4>(A, lds) : tree_grid_blocks<1, 4>(A, lds);
+    if (variant == 2) return mode == 0 ? tree_grid_blocks<0, 2>(A, lds) : tree_grid_blocks<1, 2>(A, lds);
+    return mode == 0 ? tree_grid_blocks<0, 1>(A, lds) : tree_grid_blocks<1, 1>(A, lds);
 }
 
-static unsigned render_grid_blocks(const RenderArgs& A, int variant, int mode);
 // the pilot pass alone: per tile the bounces (x 4) and — trees with a candidate grid — the grid entries its samples' walks pooled
 hipError_t launch_pilot(const RenderArgs& A, bool tree, int* cost, unsigned char* pilot, int* work, hipStream_t st) {
     if (A.n_local_tiles <= 0) return hipSuccess;
@@ -2475,50 +1924,11 @@ hipError_t launch_count_order(const RenderArgs& A, const unsigned short* iters, 
     RenderArgs B = A;
     B.n_lanes = (int)render_grid_blocks(A, variant, 0) * 256;
     B.head_sum = A.head_sum; B.head_min_load = 0.f;
-    hipLaunchKernelGGL(k_count_cost, dim3((unsigned)((A.n_local_tiles + 3) / 4)), dim3(256), 0, st, B, iters, cost, flags + (size_t)A.n_local_tiles * 64);
+    { const hipError_t e = launch_count_cost(B, iters, cost, flags + (size_t)A.n_local_tiles * 64, st); if (e != hipSuccess) return e; }
     const CountedSelect cs{iters, solo_frac, solo_cap_den > 0 ? (unsigned int)(B.n_lanes / 64 / solo_cap_den) : 0u, extra};
-    return select_and_order(B, cost, order, flags, long_list, st, 0, 0x7fffffff, &cs);
+    return launch_select_and_order(B, cost, order, flags, long_list, st, 0, 0x7fffffff, &cs);
 }
 
-// blocks of the persistent grid of k_render<true, MODE, COOPG> for this launch: what the chip holds, never more than the work
-template <int MODE, int COOPG>
-static unsigned tree_grid_blocks(const RenderArgs& A, size_t lds) {
-    const unsigned need = (unsigned)((A.n_local_tiles + 3) / 4);
-    // the occupancy query costs as much host time as the launch: remembered per thread for the last (device, LDS size) —
-    // a progressive loop issues the same launch hundreds of times
-    thread_local int c_dev = -1; thread_local size_t c_lds = 0; thread_local unsigned c_cap = 0;
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess) dev = -2;
-    if (dev != c_dev || lds != c_lds || c_cap == 0) { c_cap = resident_blocks(k_render<true, MODE, COOPG>, lds); c_dev = dev; c_lds = lds; }
-    const unsigned cap = c_cap;
-    return need < cap ? need : cap;
-}
-template <int MODE, int COOPG>
-static hipError_t launch_render_tree(const RenderArgs& A, size_t lds, hipStream_t st) {
-    hipLaunchKernelGGL((k_render<true, MODE, COOPG>), dim3(tree_grid_blocks<MODE, COOPG>(A, lds)), dim3(256), lds, st, A);
-    return hipGetLastError();
-}
-// the same for a tree variant chosen at run time (the scheduling pass wants the grid's lanes before the launch)
-static unsigned render_grid_blocks(const RenderArgs& A, int variant, int mode) {
-    const size_t lds = tree_lds_bytes(A.tree.n_nodes, variant != 1);
-    if (variant == 5) return mode == 0 ? tree_grid_blocks<0, 5>(A, lds) : tree_grid_blocks<1, 5>(A, lds);
-    if (variant == 4) return mode == 0 ? tree_grid_blocks<0, 4>(A, lds) : tree_grid_blocks<1, 4>(A, lds);
-    if (variant == 2) return mode == 0 ? tree_grid_blocks<0, 2>(A, lds) : tree_grid_blocks<1, 2>(A, lds);
-    return mode == 0 ? tree_grid_blocks<0, 1>(A, lds) : tree_grid_blocks<1, 1>(A, lds);
-}
-
-hipError_t launch_render(const RenderArgs& A, bool tree, int mode, hipStream_t st) {
-    if (A.n_local_tiles <= 0) return hipSuccess;
-    const int variant = render_variant(tree, mode, A.tree.acc);
-    if (variant == 0) return launch_render_list(A, mode, st);
-    const size_t lds = tree_lds_bytes(A.tree.n_nodes, variant != 1);                       // (the variants with a pooled walk)
-    if (variant == 5) return mode == 0 ? launch_render_tree<0, 5>(A, lds, st) : launch_render_tree<1, 5>(A, lds, st);
-    if (variant == 4) return mode == 0 ? launch_render_tree<0, 4>(A, lds, st) : launch_render_tree<1, 4>(A, lds, st);
-    if (variant == 2) return mode == 0 ? launch_render_tree<0, 2>(A, lds, st) : launch_render_tree<1, 2>(A, lds, st);
-    return mode == 0 ? launch_render_tree<0, 1>(A, lds, st) : launch_render_tree<1, 1>(A, lds, st);
-}
-
-#ifndef RT_TU_CONTRACT
 // one round of rt_render_adaptive: k_render<*, 2, *> of the variant rt_render would launch (the contracted arithmetic has no adaptive mode)
 hipError_t launch_render_adaptive(const RenderArgs& A, bool tree, hipStream_t st) {
     if (A.n_local_tiles <= 0) return hipSuccess;
@@ -2530,43 +1940,6 @@ hipError_t launch_render_adaptive(const RenderArgs& A, bool tree, hipStream_t st
     if (variant == 2) return launch_render_tree<2, 2>(A, lds, st);
     return launch_render_tree<2, 1>(A, lds, st);
 }
-hipError_t launch_adapt_check(float* fb, const float* sl, const float* q, const unsigned int* list_in, const unsigned int* count_in, long long n_all,
-                              unsigned int* list_out, unsigned int* count_out, int32_t* spp, int k, bool last, float rel_error, float floor_lum,
-                              const AdaptFrame& fr, hipStream_t st) {
-    if (n_all <= 0) return hipSuccess;
-    hipLaunchKernelGGL(k_adapt_check, dim3((unsigned)((n_all + 255) / 256)), dim3(256), 0, st, fb, sl, q, list_in, count_in, n_all, list_out, count_out, spp,
-                       k, last ? 1 : 0, rel_error, floor_lum, fr);
-    return hipGetLastError();
-}
-hipError_t launch_adapt_check_keep(float* fb, const AdaptState& s, const unsigned int* list_in, const unsigned int* count_in, long long n_all,
-                                   unsigned int* list_out, unsigned int* count_out, int32_t* spp, int k, bool last, float rel_error, float floor_lum,
-                                   const AdaptFrame& fr, hipStream_t st) {
-    if (n_all <= 0) return hipSuccess;
-    hipLaunchKernelGGL(k_adapt_check_keep, dim3((unsigned)((n_all + 255) / 256)), dim3(256), 0, st, fb, s, list_in, count_in, n_all, list_out, count_out, spp,
-                       k, last ? 1 : 0, rel_error, floor_lum, fr);
-    return hipGetLastError();
-}
-hipError_t launch_adapt_refine_seed(float* fb, const AdaptState& s, long long n_all, unsigned int* list_out, unsigned int* count_out, int32_t* spp,
-                                    int max_spp, float rel_error, float floor_lum, const AdaptFrame& fr, hipStream_t st) {
-    if (n_all <= 0) return hipSuccess;
-    hipLaunchKernelGGL(k_adapt_refine_seed, dim3((unsigned)((n_all + 255) / 256)), dim3(256), 0, st, fb, s, n_all, list_out, count_out, spp,
-                       max_spp, rel_error, floor_lum, fr);
-    return hipGetLastError();
-}
-hipError_t launch_adapt_refine_check(float* fb, const AdaptState& s, const unsigned int* list_in, const unsigned int* count_in, long long n_all,
-                                     unsigned int* list_out, unsigned int* count_out, int32_t* spp, int batch, int max_spp, float rel_error, float floor_lum,
-                                     hipStream_t st) {
-    if (n_all <= 0) return hipSuccess;
-    hipLaunchKernelGGL(k_adapt_refine_check, dim3((unsigned)((n_all + 255) / 256)), dim3(256), 0, st, fb, s, list_in, count_in, list_out, count_out, spp,
-                       batch, max_spp, rel_error, floor_lum);
-    return hipGetLastError();
-}
-hipError_t launch_adapt_zero(unsigned int* p, int n, hipStream_t st) {
-    if (n <= 0) return hipSuccess;
-    hipLaunchKernelGGL(k_adapt_zero, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, p, n);
-    return hipGetLastError();
-}
-#endif
 
 hipError_t launch_trace(const DevScene& S, const DevTree& T, bool tree, const float* rays, long long n, rt_hit_record* out, hipStream_t st) {
     if (n <= 0) return hipSuccess;
@@ -2582,7 +1955,6 @@ hipError_t launch_trace(const DevScene& S, const DevTree& T, bool tree, const fl
     return hipGetLastError();
 }
 
-#ifndef RT_TU_CONTRACT
 // the guides of a max_x x max_y frame (max_x * max_y < 2^31), launched as launch_trace launches k_trace: the same walk for every tree variant
 hipError_t launch_guides(const DevScene& S, const DevTree& T, bool tree, int max_x, int max_y, rt_hit_record* out, hipStream_t st) {
     const long long n = (long long)max_x * max_y;
@@ -2598,29 +1970,8 @@ hipError_t launch_guides(const DevScene& S, const DevTree& T, bool tree, int max
     else hipLaunchKernelGGL((k_guides<true>), dim3(blocks), dim3(256), tree_lds_bytes(T.n_nodes), st, A, n, out);
     return hipGetLastError();
 }
-#endif
-
-hipError_t launch_assemble(float* full, const float* parts, int max_x, int max_y, int nparts, hipStream_t st) {
-    const int tiles_x = (max_x + 7) / 8, tiles_y = (max_y + 7) / 8;
-    const long long tiles = (long long)tiles_x * tiles_y;
-    const long long per_part = part_local_tiles(tiles, 0, nparts) * 64;
-    const unsigned blocks = (unsigned)((tiles + 3) / 4);
-    hipLaunchKernelGGL(k_assemble, dim3(blocks), dim3(256), 0, st, full, parts, max_x, max_y, tiles_x, nparts, per_part, tiles);
-    return hipGetLastError();
-}
-hipError_t launch_assemble_spp(int32_t* full, const int32_t* parts, int max_x, int max_y, int nparts, hipStream_t st) {
-    const int tiles_x = (max_x + 7) / 8, tiles_y = (max_y + 7) / 8;
-    const long long tiles = (long long)tiles_x * tiles_y;
-    const long long per_part = part_local_tiles(tiles, 0, nparts) * 64;
-    const unsigned blocks = (unsigned)((tiles + 3) / 4);
-    hipLaunchKernelGGL(k_assemble_spp, dim3(blocks), dim3(256), 0, st, full, parts, max_x, max_y, tiles_x, nparts, per_part, tiles);
-    return hipGetLastError();
-}
-#endif
 
 RT_STATS_READERS
-
-#ifdef RT_TU_CONTRACT
-} // namespace fmac
 #endif
-} // namespace rt
+
+} // namespace RT_TU_NAMESPACE

@@ -10,6 +10,7 @@
 #include <hip/hip_runtime.h>
 #include <float.h>
 #include "rt_device.h"
+#include "rt_launch.h"
 #include "rt_real.h"
 #include "rt_tuning.h"
 #include "rt_divshared.h"
@@ -960,7 +961,7 @@ __global__ __launch_bounds__(256, RT_H16_MINWAVES) void k_render_h(RenderArgs A)
 
 // The pilot pass of the scheduling (k_tile_cost of rt_kernels.hip in binary16): two samples per 2x2 pixel block on a private RNG
 // stream, in adjacent lanes, cut at RT_H16_PILOT_CAP bounces; only the bounce counts are kept — per tile for the hand-out order,
-// per block for k_long_select.  Changes WHEN a pixel is rendered, never the pixel.
+// per block for k_long_select (rt_schedule.hip).  Changes WHEN a pixel is rendered, never the pixel.
 template <bool TREE>
 __global__ __launch_bounds__(256, RT_H16_MINWAVES) void k_tile_cost_h(RenderArgs A, int* __restrict__ cost, unsigned char* __restrict__ pilot) {
     extern __shared__ float4 s_nodes[];
@@ -1069,8 +1070,6 @@ static size_t h16_lds_bytes(bool tree, const DevTree& T) {
     return tree ? (size_t)T.n_nodes * (T.h16_np[0] > 0 ? (regular ? 2 : 1) * sizeof(float4) : sizeof(DevNode)) + (T.h16_np[0] > 0 ? h16::kPlaneLds4 * sizeof(float4) : 0) + 4 * sizeof(h16::WaveLds) : 0;
 }
 
-hipError_t launch_select_and_order(const RenderArgs& A, int* cost, unsigned int* order, unsigned char* flags, unsigned int* long_list, hipStream_t st, int long_sum, int solo_sum);   // rt_kernels.hip
-
 // the pilot pass alone (rt_split_balanced): per tile 4 x the bounces of its pilot samples
 hipError_t launch_pilot_h(const RenderArgs& A, bool tree, int* cost, hipStream_t st) {
     if (A.n_local_tiles <= 0) return hipSuccess;
@@ -1081,7 +1080,7 @@ hipError_t launch_pilot_h(const RenderArgs& A, bool tree, int* cost, hipStream_t
     return hipGetLastError();
 }
 
-// the scheduling pre-pass of a binary16 render: pilot pass in binary16, then the precision-independent selection and ordering
+// the scheduling pre-pass of a binary16 render: pilot pass in binary16, then the precision-independent selection and ordering (rt_schedule.hip)
 hipError_t launch_tile_order_h(const RenderArgs& A, bool tree, int* cost, unsigned int* order, unsigned char* flags, unsigned int* long_list, hipStream_t st) {
     if (A.n_local_tiles <= 0) return hipSuccess;
     const unsigned blocks = (unsigned)((A.n_local_tiles + 7) / 8);                 // a wave covers two tiles

@@ -22,6 +22,7 @@
 #include <algorithm>
 #include "../../include/rt_amd.h"
 #include "rt_handles.h"
+#include "rt_launch.h"
 
 namespace {
 
@@ -64,7 +65,6 @@ Rccl& rccl() {                                        // bound once per process,
 
 }  // namespace
 
-namespace rt { hipError_t launch_assemble_spp(int32_t* full, const int32_t* parts, int max_x, int max_y, int nparts, hipStream_t st); }   // rt_kernels.hip
 
 struct rt_multi {
     int rank = 0, nranks = 1;

@@ -1,5 +1,5 @@
 // rt_stats.h — the instrumentation of the DIAGNOSTIC builds of the render kernels (librt_amd_stats.so: -DRT_STATS, read out by
-// tools/stats.py; librt_amd_wpass.so: -DRT_STATS -DRT_STATS_WPASS).  Included by rt_kernels.hip inside namespace rt.  A product
+// tools/stats.py; librt_amd_wpass.so: -DRT_STATS -DRT_STATS_WPASS).  Included by rt_kernels.hip inside its namespace.  A product
 // build (no RT_STATS) gets empty macros from here and nothing else: STAT / WPASS count, RT_STATS_ONLY(code) keeps `code` in the
 // diagnostic builds only, STAT_ARG / STAT_PASS thread the per-lane counter block through the closest-hit functions.
 #pragma once

@@ -17,14 +17,12 @@
 #include <hip/hip_runtime.h>
 #include "../../include/rt_amd.h"
 #include "rt_device.h"
+#include "rt_launch.h"
 #include "rt_temporal.h"
 
 #pragma clang fp contract(off)
 
 namespace rt {
-
-hipError_t launch_denoise_var_levels(float* fb_out, int max_x, int max_y, const rt_hit_record* hits, const rt_denoise_var_params& P, float4* work,
-                                     hipStream_t st);      // rt_denoise.hip
 
 // the rule itself is temporal_pixel (rt_temporal.h), shared with the history-aware budget key (k_budget_keys_temporal, rt_budget.hip)
 __global__ __launch_bounds__(256) void k_temporal_accumulate(TemporalArgs T) {

@@ -4,7 +4,7 @@
     python tools/predictor.py gpurun_out/c3_pixels.npz
 `it` = main-loop iterations of every pixel (the truth), `pilot` = the pilot's bounce count per 2x2 block (tile x 16).  Prints,
 for several selection rules, how many pixels they pick, the share of the pixels above 800 ... 2000 iterations among them (recall)
-and how much of the pick is short.  RT_PILOT_LONG_SUM in csrc/rt_kernels.hip was chosen from this table."""
+and how much of the pick is short.  RT_PILOT_LONG_SUM (csrc/rt_tuning.h; applied by k_long_select, csrc/rt_schedule.hip) was chosen from this table."""
 import sys
 import numpy as np
 from scipy.ndimage import uniform_filter, maximum_filter

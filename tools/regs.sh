@@ -1,5 +1,5 @@
 #!/bin/bash
-# tools/regs.sh [extra -D flags]: register use of the render kernels (hipcc -Rpass-analysis=kernel-resource-usage on csrc/rt_kernels.hip and rt_kernels_fp16.hip),
+# tools/regs.sh [extra -D flags]: register use of the kernels that trace rays (hipcc -Rpass-analysis=kernel-resource-usage on csrc/rt_kernels.hip and rt_kernels_fp16.hip),
 # then of the kernels that share csrc/rt_temporal.h (k_temporal_accumulate and its moving twin, the budget key kernels) and k_world_set_geometry with the Makefile's flags for their files
 cd "$(dirname "$0")/../dd2360-raytracing_amd"
 F="--offload-arch=gfx950 -std=c++17 -O3 -ffp-contract=off -fno-fast-math -fno-gpu-flush-denormals-to-zero -fPIC -Wno-unused-function $*"
