@@ -1554,9 +1554,11 @@ int rt_temporal_check(int max_x, int max_y, const rt_temporal_params* params) {
     return 0;
 }
 
-int rt_temporal_accumulate(void* d_hist_out, const void* d_hist_in, const rt_hit_record* d_hits, const rt_hit_record* d_hits_prev,
-                           const rt_camera* cam_prev, const void* d_state, const rt_world* world, int max_x, int max_y,
-                           const rt_temporal_params* params, void* stream) {
+// the RT_EINVAL checks the three accumulate calls share (pointers, alignment, parameters, overlap); the callers add their own, then
+// RT_ENOTSUP for a USE_FP16 world
+static int temporal_call_check(void* d_hist_out, const void* d_hist_in, const rt_hit_record* d_hits, const rt_hit_record* d_hits_prev,
+                               const rt_camera* cam_prev, const void* d_state, const rt_world* world, int max_x, int max_y,
+                               const rt_temporal_params* params) {
     if (!d_hist_out || !d_hits || !d_state || !world) return RT_EINVAL;
     if (d_hist_in && (!d_hits_prev || !cam_prev)) return RT_EINVAL;
     if (((uintptr_t)d_hist_out & 15) || ((uintptr_t)d_hist_in & 15) || ((uintptr_t)d_hits & 15) || (d_hist_in && ((uintptr_t)d_hits_prev & 15))) return RT_EINVAL;
@@ -1566,6 +1568,14 @@ int rt_temporal_accumulate(void* d_hist_out, const void* d_hist_in, const rt_hit
         const uintptr_t a = (uintptr_t)d_hist_out, b = (uintptr_t)d_hist_in, bytes = (uintptr_t)RT_TEMPORAL_HISTORY_BYTES * (uintptr_t)max_x * (uintptr_t)max_y;
         if ((a > b ? a - b : b - a) < bytes) return RT_EINVAL;
     }
+    return 0;
+}
+
+int rt_temporal_accumulate(void* d_hist_out, const void* d_hist_in, const rt_hit_record* d_hits, const rt_hit_record* d_hits_prev,
+                           const rt_camera* cam_prev, const void* d_state, const rt_world* world, int max_x, int max_y,
+                           const rt_temporal_params* params, void* stream) {
+    const int rc = temporal_call_check(d_hist_out, d_hist_in, d_hits, d_hits_prev, cam_prev, d_state, world, max_x, max_y, params);
+    if (rc) return rc;
     if (world->precision == RT_PRECISION_FP16) return RT_ENOTSUP;
     const int up = world_upload(world);                                       // (nothing to do once rt_world_upload has run: the call can be captured)
     if (up) return up;
@@ -1576,22 +1586,40 @@ int rt_temporal_accumulate(void* d_hist_out, const void* d_hist_in, const rt_hit
 int rt_temporal_accumulate_moving(void* d_hist_out, const void* d_hist_in, const rt_hit_record* d_hits, const rt_hit_record* d_hits_prev,
                                   const rt_camera* cam_prev, const float* d_geom_prev, const void* d_state, const rt_world* world,
                                   int max_x, int max_y, const rt_temporal_params* params, void* stream) {
-    if (!d_hist_out || !d_hits || !d_state || !world) return RT_EINVAL;
-    if (d_hist_in && (!d_hits_prev || !cam_prev || !d_geom_prev)) return RT_EINVAL;
-    if (((uintptr_t)d_hist_out & 15) || ((uintptr_t)d_hist_in & 15) || ((uintptr_t)d_hits & 15) || (d_hist_in && ((uintptr_t)d_hits_prev & 15))) return RT_EINVAL;
-    if (d_hist_in && ((uintptr_t)d_geom_prev & 15)) return RT_EINVAL;          // read as float4
-    const int rc = rt_temporal_check(max_x, max_y, params);
+    if (d_hist_in && (!d_geom_prev || ((uintptr_t)d_geom_prev & 15))) return RT_EINVAL;      // read as float4
+    const int rc = temporal_call_check(d_hist_out, d_hist_in, d_hits, d_hits_prev, cam_prev, d_state, world, max_x, max_y, params);
     if (rc) return rc;
-    if (d_hist_in) {                                                          // the kernel gathers from one while it writes the other
-        const uintptr_t a = (uintptr_t)d_hist_out, b = (uintptr_t)d_hist_in, bytes = (uintptr_t)RT_TEMPORAL_HISTORY_BYTES * (uintptr_t)max_x * (uintptr_t)max_y;
-        if ((a > b ? a - b : b - a) < bytes) return RT_EINVAL;
-    }
     if (world->precision == RT_PRECISION_FP16) return RT_ENOTSUP;
     const int up = world_upload(world);                                       // (nothing to do once rt_world_upload has run: the call can be captured)
     if (up) return up;
     return (int)launch_temporal_accumulate_moving(d_hist_out, d_hist_in, d_hits, d_hits_prev, cam_prev, world->z->dev.geom,
                                                   d_hist_in ? (const float4*)d_geom_prev : nullptr, d_state, world->z->dev.kind, world->n,
                                                   max_x, max_y, *params, (hipStream_t)stream);
+}
+
+// the parameter checks of rt_temporal_accumulate_rectified (host only)
+int rt_temporal_rectify_check(const rt_temporal_rectify* r) {
+    if (!r) return RT_EINVAL;
+    if (r->radius < 1 || r->radius > 2) return RT_EINVAL;
+    const int side = 2 * r->radius + 1;
+    if (r->min_count < 2 || r->min_count > side * side) return RT_EINVAL;
+    if (!(r->gamma >= 0.0f) || !std::isfinite(r->gamma) || !std::isfinite(r->gamma * r->gamma)) return RT_EINVAL;
+    return 0;
+}
+
+int rt_temporal_accumulate_rectified(void* d_hist_out, const void* d_hist_in, const rt_hit_record* d_hits, const rt_hit_record* d_hits_prev,
+                                     const rt_camera* cam_prev, const float* d_geom_prev, const void* d_state, const rt_world* world,
+                                     int max_x, int max_y, const rt_temporal_params* params, const rt_temporal_rectify* rectify, void* stream) {
+    int rc = temporal_call_check(d_hist_out, d_hist_in, d_hits, d_hits_prev, cam_prev, d_state, world, max_x, max_y, params);
+    if (!rc) rc = rt_temporal_rectify_check(rectify);
+    if (rc) return rc;
+    if ((uintptr_t)d_geom_prev & 15) return RT_EINVAL;                         // read as float4
+    if (world->precision == RT_PRECISION_FP16) return RT_ENOTSUP;
+    const int up = world_upload(world);                                       // (nothing to do once rt_world_upload has run: the call can be captured)
+    if (up) return up;
+    return (int)launch_temporal_accumulate_rectified(d_hist_out, d_hist_in, d_hits, d_hits_prev, cam_prev, world->z->dev.geom,
+                                                     d_hist_in ? (const float4*)d_geom_prev : nullptr, d_state, world->z->dev.kind, world->n,
+                                                     max_x, max_y, *params, *rectify, (hipStream_t)stream);
 }
 
 int rt_denoise_history(void* fb_out, const void* fb_in, int max_x, int max_y, const rt_hit_record* d_hits, const void* d_hist,

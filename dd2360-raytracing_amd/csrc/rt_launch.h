@@ -105,6 +105,12 @@ hipError_t launch_temporal_accumulate_moving(void* hist_out, const void* hist_in
                                              const int32_t* kind, int n_kind, int max_x, int max_y, const rt_temporal_params& P,
                                              hipStream_t st);
 
+// ---- rt_rectify.hip (geom_prev == nullptr: the static rule)
+hipError_t launch_temporal_accumulate_rectified(void* hist_out, const void* hist_in, const rt_hit_record* hits, const rt_hit_record* hits_prev,
+                                                const rt_camera* cam_prev, const float4* geom, const float4* geom_prev, const void* state,
+                                                const int32_t* kind, int n_kind, int max_x, int max_y, const rt_temporal_params& P,
+                                                const rt_temporal_rectify& Rc, hipStream_t st);
+
 // ---- rt_budget.hip
 size_t budget_ws_bytes(long long n, bool filtered);
 hipError_t launch_budget_select(const AdaptState& s, long long n, const AdaptFrame& fr, int batch, int max_spp, float floor_lum, unsigned int K,

@@ -1,6 +1,7 @@
 // rt_temporal.h — the per-pixel rule of temporal accumulation (include/rt_amd.h), once: k_temporal_accumulate
 // (rt_temporal.hip) writes what temporal_pixel returns as this frame's history, k_budget_keys_temporal (rt_budget.hip) ranks the
 // pixel by it, k_temporal_accumulate_moving (rt_animate.hip) writes its MOVING variant: the rule that follows a translated sphere.
+// k_temporal_accumulate_rectified (rt_rectify.hip) is either of the two with a functor in the rule's one hook: history rectification.
 // Numeric contract: one IEEE binary32 rounding per operation in the order the header states, no contraction (also on the command
 // line of the three files), correctly rounded division (hipcc default), sums in tap order — tests/temporal_model.py and
 // tests/temporal_moving_model.py reproduce it bit for bit.
@@ -58,23 +59,46 @@ __device__ inline float dot3(float ax, float ay, float az, float bx, float by, f
 // 2 * p + 1 fit an int, 3 * p does not (64-bit colour offsets).  Every gathered index is clamped into the frame.
 struct TemporalPixel { float4 out; float neff; int k; float sl, q; };
 
+// this frame's values of pixel p, the first lines of the rule: x_c and v_c (c), both halves of its guide record, the state values and
+// the EMPTY decision.  temporal_pixel starts with it; k_temporal_accumulate_rectified (rt_rectify.hip) stages its window from it, so
+// a window pixel is EMPTY exactly when rt_temporal_accumulate writes zeros for it.
+struct TemporalFrame { float4 c, gp0, gp1; float nf, sl, q; int k, sp; bool empty; };
+
+__device__ __forceinline__ TemporalFrame temporal_frame(const TemporalArgs& T, int p) {
+    TemporalFrame f;
+    const long long e = 3 * (long long)p;
+    // the "per pixel" line of rt_denoise_adaptive
+    f.k = T.S.k[p];
+    f.nf = (float)f.k;
+    f.c.x = T.S.rgb[e] / f.nf; f.c.y = T.S.rgb[e + 1] / f.nf; f.c.z = T.S.rgb[e + 2] / f.nf;
+    f.sl = T.S.sl[p];
+    f.q = T.S.q[p];
+    float d = f.nf * f.q - f.sl * f.sl;
+    d = d > 0.0f ? d : 0.0f;
+    f.c.w = d / ((f.nf * f.nf) * (f.nf - 1.0f));
+    f.gp0 = T.g[2 * p]; f.gp1 = T.g[2 * p + 1];
+    f.sp = __float_as_int(f.gp1.w);
+    f.empty = f.sp == -1 || f.k < 2 || !__builtin_isfinite(f.c.x) || !__builtin_isfinite(f.c.y) || !__builtin_isfinite(f.c.z) || !__builtin_isfinite(f.c.w);
+    return f;
+}
+
+// the hook of temporal_pixel: called once for a pixel that has taken history (sg > 0), between m = min(n_h, max_history) and the
+// merge, with the history's colour; what it returns is merged as m.  This one changes nothing: the rule of rt_temporal_accumulate.
+struct TemporalKeep { __device__ __forceinline__ float operator()(float m, float, float, float, int) const { return m; } };
+
 // MOVING (rt_temporal_accumulate_moving): a sphere whose radius changed its bits is not asked, and the point of a sphere whose centre
 // changed its bits is carried back by the translation, P' = (P - c1) + c0 per component, before it is projected and compared.
-template <bool MOVING = false>
-__device__ __forceinline__ TemporalPixel temporal_pixel(const TemporalArgs& T, int p, const TemporalMotion* M = nullptr) {
-    const long long e = 3 * (long long)p;
-    // this frame's values: the "per pixel" line of rt_denoise_adaptive
-    const int k = T.S.k[p];
-    const float nf = (float)k;
-    float4 c;
-    c.x = T.S.rgb[e] / nf; c.y = T.S.rgb[e + 1] / nf; c.z = T.S.rgb[e + 2] / nf;
-    const float sl = T.S.sl[p];
-    const float q = T.S.q[p];
-    float d = nf * q - sl * sl;
-    d = d > 0.0f ? d : 0.0f;
-    c.w = d / ((nf * nf) * (nf - 1.0f));
-    const float4 gp0 = T.g[2 * p], gp1 = T.g[2 * p + 1];
-    const int sp = __float_as_int(gp1.w);
+// temporal_pixel_from takes the pixel's TemporalFrame from the caller, temporal_pixel computes it.
+template <bool MOVING = false, class Hook = TemporalKeep>
+__device__ __forceinline__ TemporalPixel temporal_pixel_from(const TemporalArgs& T, const TemporalFrame& F, const TemporalMotion* M = nullptr,
+                                                             const Hook& hook = Hook()) {
+    const int k = F.k;
+    const float nf = F.nf;
+    const float4 c = F.c;
+    const float sl = F.sl;
+    const float q = F.q;
+    const float4 gp0 = F.gp0, gp1 = F.gp1;
+    const int sp = F.sp;
     float Px = gp0.y, Py = gp0.z, Pz = gp0.w;                                      // P', where the point was: P_p unless its sphere moved
     bool resized = false;
     if constexpr (MOVING) {
@@ -88,7 +112,7 @@ __device__ __forceinline__ TemporalPixel temporal_pixel(const TemporalArgs& T, i
     }
     float4 out = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
     float neff = 0.0f;
-    const bool empty = sp == -1 || k < 2 || !__builtin_isfinite(c.x) || !__builtin_isfinite(c.y) || !__builtin_isfinite(c.z) || !__builtin_isfinite(c.w);
+    const bool empty = F.empty;
     if (!empty) {
         out = c;
         neff = nf;
@@ -139,7 +163,7 @@ __device__ __forceinline__ TemporalPixel temporal_pixel(const TemporalArgs& T, i
                 }
                 if (sg > 0.0f) {
                     const float hx = s0 / sg, hy = s1 / sg, hz = s2 / sg, hv = s3 / sg, hn = s4 / sg;
-                    const float m = hn < T.max_history ? hn : T.max_history;
+                    const float m = hook(hn < T.max_history ? hn : T.max_history, hx, hy, hz, sp);
                     const float a = nf / (m + nf);
                     out.x = hx + a * (c.x - hx); out.y = hy + a * (c.y - hy); out.z = hz + a * (c.z - hz);
                     out.w = ((1.0f - a) * (1.0f - a)) * hv + (a * a) * c.w;
@@ -149,6 +173,11 @@ __device__ __forceinline__ TemporalPixel temporal_pixel(const TemporalArgs& T, i
         }
     }
     return TemporalPixel{out, neff, k, sl, q};
+}
+
+template <bool MOVING = false>
+__device__ __forceinline__ TemporalPixel temporal_pixel(const TemporalArgs& T, int p, const TemporalMotion* M = nullptr) {
+    return temporal_pixel_from<MOVING>(T, temporal_frame(T, p), M);
 }
 
 } // namespace rt

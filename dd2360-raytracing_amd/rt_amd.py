@@ -118,6 +118,23 @@ def temporal_params(**kw):
     return TemporalParams(p["max_history"], p["reuse_specular"], p["position_tolerance"], p["normal_min_dot"])
 
 
+class TemporalRectify(C.Structure):
+    """rt_temporal_rectify: the window radius (1..2), the smallest number of accepted window pixels at which the history is tested, and
+    gamma, the allowed distance of the history from the window mean in standard deviations of the window (0 = off);
+    include/rt_amd.h states the rule"""
+    _fields_ = [("radius", C.c_int32), ("min_count", C.c_int32), ("gamma", C.c_float)]
+
+# rt_amd.h RT_TEMPORAL_RECTIFY_DEFAULT_*: DESIGN.md §5.10 "History rectification" (profiles/r19/rectify.txt)
+TEMPORAL_RECTIFY_DEFAULTS = dict(radius=1, min_count=4, gamma=1.5)
+
+
+def temporal_rectify(**kw):
+    """a TemporalRectify with the library's defaults for whatever kw does not set"""
+    p = dict(TEMPORAL_RECTIFY_DEFAULTS)
+    p.update(kw)
+    return TemporalRectify(p["radius"], p["min_count"], p["gamma"])
+
+
 class TemporalInputs(C.Structure):
     """rt_temporal_inputs: what temporal_accumulate takes besides the state and the world — the last frame's history (NULL: the first
     frame), this frame's guides, the last frame's guides and camera (a host pointer); build one with temporal_inputs()"""
@@ -254,6 +271,9 @@ SYMBOLS = {
     "rt_temporal_check": (_i, [_i, _i, C.POINTER(TemporalParams)]),
     "rt_temporal_accumulate": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, C.POINTER(TemporalParams), _vp]),
     "rt_temporal_accumulate_moving": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, C.POINTER(TemporalParams), _vp]),
+    "rt_temporal_rectify_check": (_i, [C.POINTER(TemporalRectify)]),
+    "rt_temporal_accumulate_rectified": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, C.POINTER(TemporalParams), C.POINTER(TemporalRectify),
+                                              _vp]),
     "rt_denoise_history": (_i, [_vp, _vp, _i, _i, _vp, _vp, C.POINTER(DenoiseVarParams), _vp, _vp]),
     "rt_adaptive_priority_filtered": (_f, [_f, _f, _f]),
     "rt_adaptive_budget_select_filtered": (_i, [_vp, _vp, _vp, _i, _i, C.POINTER(Budget), C.POINTER(DenoiseVarParams), _i64, _vp, _vp, _vp, _vp]),
@@ -998,6 +1018,25 @@ def temporal_accumulate_moving(d_hist_out, d_hist_in, d_hits, d_hits_prev, cam_p
                                               None if first else _dev(d_hits_prev), None if first else _np(cam),
                                               None if first or d_geom_prev is None else _dev(d_geom_prev), _dev(d_state), world.h, max_x, max_y,
                                               C.byref(params), _stream()), "rt_temporal_accumulate_moving")
+
+
+def temporal_rectify_check(rectify):
+    """rt_temporal_rectify_check: True when temporal_accumulate_rectified accepts these rectification parameters (host only)"""
+    return lib().rt_temporal_rectify_check(C.byref(rectify) if rectify is not None else None) == 0
+
+
+def temporal_accumulate_rectified(d_hist_out, d_hist_in, d_hits, d_hits_prev, cam_prev, d_state, world, max_x, max_y, params, rectify,
+                                  d_geom_prev=None):
+    """rt_temporal_accumulate_rectified on the current stream: temporal_accumulate (d_geom_prev None) or temporal_accumulate_moving
+    (d_geom_prev: what World.get_geometry returned for the frame that wrote d_hist_in) whose history sheds effective samples where this
+    frame's neighbourhood contradicts it; rectify is a TemporalRectify (temporal_rectify())"""
+    first = d_hist_in is None
+    cam = None if first else np.ascontiguousarray(cam_prev, camera_dtype).reshape(1)
+    check(lib().rt_temporal_accumulate_rectified(_dev(d_hist_out), None if first else _dev(d_hist_in), _dev(d_hits),
+                                                 None if first else _dev(d_hits_prev), None if first else _np(cam),
+                                                 None if d_geom_prev is None else _dev(d_geom_prev), _dev(d_state), world.h, max_x, max_y,
+                                                 C.byref(params), C.byref(rectify) if rectify is not None else None, _stream()),
+          "rt_temporal_accumulate_rectified")
 
 
 def denoise_history(fb_out, fb_in, max_x, max_y, d_hits, d_hist, params, d_work):

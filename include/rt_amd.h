@@ -703,6 +703,48 @@ int rt_temporal_accumulate(void* d_hist_out, const void* d_hist_in, const rt_hit
 int rt_temporal_accumulate_moving(void* d_hist_out, const void* d_hist_in, const rt_hit_record* d_hits, const rt_hit_record* d_hits_prev,
                                   const rt_camera* cam_prev, const float* d_geom_prev, const void* d_state, const rt_world* world,
                                   int max_x, int max_y, const rt_temporal_params* params, void* stream);
+/* History rectification: rt_temporal_accumulate (d_geom_prev == NULL) or rt_temporal_accumulate_moving (d_geom_prev given: that
+ * call's rule; 16-byte aligned, ignored when d_hist_in is NULL) with one more step — a history that THIS frame's neighbourhood
+ * contradicts sheds effective samples before it is merged (DESIGN.md §5.10 "History rectification").  Every argument, buffer, the
+ * single launch without allocation, synchronisation or atomics, and capture once the world is uploaded are those of the two calls.  The
+ * rule is theirs up to the point where a pixel has taken history (sg > 0): it has x_h = (hx, hy, hz), v_h, n_h and
+ * m = n_h < (float)max_history ? n_h : (float)max_history.  Then, each operation rounded once to binary32, no contraction, sums in the
+ * stated order (tests/temporal_rectify_model.py is the model, bit for bit):
+ *   the window:      q = p + (dx, dy), dx and dy in -radius .. radius, dy outer, both from -radius.  q is skipped, not weighted by 0,
+ *                    when it lies outside the frame, when it is EMPTY in this frame (rt_temporal_accumulate's "this frame" line), or when
+ *                    the bits of its guide's sphere differ from sphere_p.  The centre is always in the window.
+ *                    l_q = (x.r + x.g) + x.b of q's x_c = S_c / n.
+ *   first pass:      in window order cnt = cnt + 1.0f;  s1 = s1 + l_q;  then ml = s1 / cnt.
+ *   second pass:     in the same order ss = ss + (l_q - ml) * (l_q - ml);  then s2 = ss / (cnt - 1.0f).
+ *   the test:        only when gamma != 0 and cnt >= (float)min_count:  lh = (hx + hy) + hz;  dl = lh - ml;  e2 = dl * dl;
+ *                    lim = g2 * s2, g2 = gamma * gamma rounded once on the host;  if (e2 > lim) m = m * (lim / e2).  A NaN compares
+ *                    false and keeps m.  Nothing is clamped.
+ *   merging:         unchanged with this m:  a = n / (m + n);  x = x_h + a*(x_c - x_h);  v = ((1 - a)*(1 - a))*v_h + (a*a)*v_c;  neff = m + n.
+ * So: with gamma == 0 the call writes the bytes of rt_temporal_accumulate (d_geom_prev NULL) or of rt_temporal_accumulate_moving
+ * (given); a pixel that took no history is untouched by the rule; neff is never above what the unrectified call writes for the pixel
+ * (lim / e2 < 1 where it is applied); and x and v are a convex step from the unrectified values towards this frame's (a only grows).
+ * The history sheds weight and is not clamped, so the variance rt_denoise_history trusts stays the variance of what was averaged.
+ * RT_EINVAL for everything rt_temporal_accumulate refuses, a NULL rectify, whatever rt_temporal_rectify_check (host only) refuses —
+ * radius outside 1..2, min_count outside 2..(2*radius+1)^2, a gamma that is negative or not finite or whose square is not finite — and
+ * a misaligned non-NULL d_geom_prev; after all of those RT_ENOTSUP for USE_FP16 worlds.
+ * Defaults (RT_TEMPORAL_RECTIFY_DEFAULT_*): the setting with the smallest worst-case loss against each scenario's own optimum over
+ * static, orbiting and moving scenes (tools/temporal_study.py, tools/animate_study.py, profiles/r19/rectify.txt).
+ * Out of scope: HISTORY-AWARE BUDGETS keep the unrectified key (rt_temporal_inputs is a fixed POD); per-channel tests (one luminance
+ * test decides for the three channels); multi-GPU frames and parts; binary16 histories. */
+#define RT_TEMPORAL_RECTIFY_DEFAULT_RADIUS 1
+#define RT_TEMPORAL_RECTIFY_DEFAULT_MIN_COUNT 4
+#define RT_TEMPORAL_RECTIFY_DEFAULT_GAMMA 1.5f
+typedef struct rt_temporal_rectify {
+    int32_t radius;     /* 1..2: the window is the (2r+1)^2 pixels of THIS frame around the pixel */
+    int32_t min_count;  /* 2..(2r+1)^2: with fewer accepted window pixels the history is taken as it is */
+    float gamma;        /* allowed distance of the history from the window mean, in standard deviations of the window;
+                           finite, >= 0, gamma*gamma finite; 0 = off */
+} rt_temporal_rectify;
+int rt_temporal_rectify_check(const rt_temporal_rectify* r);                               /* host only: 0 or RT_EINVAL */
+int rt_temporal_accumulate_rectified(void* d_hist_out, const void* d_hist_in, const rt_hit_record* d_hits, const rt_hit_record* d_hits_prev,
+                                     const rt_camera* cam_prev, const float* d_geom_prev, const void* d_state, const rt_world* world,
+                                     int max_x, int max_y, const rt_temporal_params* params, const rt_temporal_rectify* rectify,
+                                     void* stream);
 /* rt_denoise_adaptive with its "per pixel" values taken from a history: x = hist.xyz, v = hist.w; a pixel is pass-through, and keeps
  * the bits of fb_in, when neff == 0 or a channel of x or v is not finite (or v < 0, which rt_temporal_accumulate never writes).  The
  * levels, fb_out == fb_in, buffers, alignment (d_hist 16-byte aligned too), capture and errors are those of rt_denoise_adaptive; d_hits

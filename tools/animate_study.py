@@ -7,7 +7,9 @@
    rel_error 0, RNG states carried on), the moved spheres +STEP in x per frame, library defaults.  RMSE of sqrt of the last history under
    the moving rule and under rt_temporal_accumulate's static rule against rt_render(REF_SPP) of the last frame's world, over the
    lambertian pixels on moved spheres whose last frame took history under the moving rule.  Two motions: every 7th small sphere, and
-   every small sphere (the field as a whole: what the test uses at 203x77, where a sphere is two pixels wide).
+   every small sphere (the field as a whole: what the test uses at 203x77, where a sphere is two pixels wide).  Under each row the same
+   pixels with rt_temporal_accumulate_rectified at its defaults (both rules), then the lambertian pixels on spheres that did NOT move
+   (the lighting lag) and every non-empty pixel, unrectified and rectified.
 2. Set-up time of one frame, both ways, at N = 10 000 (SPL 32) and N = 100 000 (SPL 320): this library's setters plus the device build
    (rt_world_get_geometry, rt_world_set_geometry, rt_world_set_camera, rt_build_octree_gpu, rt_free_octree of the old tree) against a
    world per frame (rt_world_create + rt_world_upload + rt_build_octree_gpu, and the two frees).  A host clock around work that ends in a
@@ -32,18 +34,15 @@ def small_spheres(spheres):
     return np.flatnonzero((spheres["material"] != -1) & (spheres["radius"] < 0.5) & (np.arange(len(spheres)) > 0))
 
 
-def quality(rt, torch, say, every):
+def frames_of(rt, torch, every):
+    """the scenario's frames on one resident world: per frame its state, guides, geometry and the geometry before the move"""
     W = rt.World(N, NX, NY)
     kind = W.spheres["material"].astype(np.int32)
     moved = small_spheres(W.spheres)[::every]
     d_moved = torch.from_numpy(moved).cuda()
     st = rt.alloc_rand_state(NX, NY)
     rt.render_init(NX, NY, st)
-    p = rt.temporal_params()
-    hm = [rt.alloc_temporal_history(NX, NY), rt.alloc_temporal_history(NX, NY)]
-    hs = [rt.alloc_temporal_history(NX, NY), rt.alloc_temporal_history(NX, NY)]
-    cam = W.get_camera()
-    prev, tree = None, None
+    frames, tree = [], None
     for f in range(FRAMES):
         d_geom_prev = W.get_geometry()
         if f:
@@ -56,27 +55,70 @@ def quality(rt, torch, say, every):
         fb, state, hits = rt.alloc_fb(NX, NY), rt.alloc_adaptive_state(NX, NY), rt.alloc_guides(NX, NY)
         rt.render_adaptive_begin(fb, NX, NY, rt.Adaptive(SPP, SPP, 4, 0.0, 0.0), W, st, state, tree)
         rt.render_guides(W, tree, NX, NY, hits)
-        rt.temporal_accumulate_moving(hm[f & 1], hm[(f + 1) & 1] if f else None, hits, prev, cam, d_geom_prev, state, W, NX, NY, p)
-        rt.temporal_accumulate(hs[f & 1], hs[(f + 1) & 1] if f else None, hits, prev, cam, state, W, NX, NY, p)
-        prev = hits
+        frames.append(dict(state=state, hits=hits, d_geom_prev=d_geom_prev, d_geom=W.get_geometry()))
+    return W, tree, kind, moved, frames
+
+
+def chain(rt, torch, W, frames, p, moving, rectify=None):
+    """the last frame's history (host) under the static or the moving rule; rectify: a TemporalRectify, or None for the plain calls"""
+    h = [rt.alloc_temporal_history(NX, NY), rt.alloc_temporal_history(NX, NY)]
+    cam = W.get_camera()
+    for f, fr in enumerate(frames):
+        W.set_geometry(fr["d_geom"])                     # the moving rule reads this frame's geometry from the world
+        out, last, prev = h[f & 1], h[(f + 1) & 1] if f else None, frames[f - 1]["hits"] if f else None
+        if rectify is not None:
+            rt.temporal_accumulate_rectified(out, last, fr["hits"], prev, cam, fr["state"], W, NX, NY, p, rectify,
+                                             d_geom_prev=fr["d_geom_prev"] if moving and f else None)
+        elif moving:
+            rt.temporal_accumulate_moving(out, last, fr["hits"], prev, cam, fr["d_geom_prev"], fr["state"], W, NX, NY, p)
+        else:
+            rt.temporal_accumulate(out, last, fr["hits"], prev, cam, fr["state"], W, NX, NY, p)
+    torch.cuda.synchronize()
+    return h[(len(frames) - 1) & 1].cpu().numpy()
+
+
+def quality(rt, torch, say, every, settings=()):
+    """the table row of one motion, the same pixels under the rectified calls at the library's defaults, and the lighting lag: the
+    lambertian pixels on spheres that did NOT move.  Returns {setting: RMSE over every non-empty pixel} of the moving rule for the
+    (radius, min_count, gamma) settings asked for; gamma 0 is the unrectified call"""
+    W, tree, kind, moved, frames = frames_of(rt, torch, every)
+    p = rt.temporal_params()
     ref, rs = rt.alloc_fb(NX, NY), rt.alloc_rand_state(NX, NY)
     rt.render_init(NX, NY, rs)
     rt.render(ref, NX, NY, REF_SPP, W, rs, tree)
     torch.cuda.synchronize()
     n = NX * NY
     ref = ref.cpu().numpy().reshape(-1, 3).astype(np.float64)
-    m, s = hm[(FRAMES - 1) & 1].cpu().numpy(), hs[(FRAMES - 1) & 1].cpu().numpy()
-    sphere = prev.cpu().numpy().view(rt.hit_record_dtype)["sphere"]
-    on_moved = np.isin(sphere, moved) & (kind[np.clip(sphere, 0, None)] == rt.MAT_LAMBERTIAN)
-    am, as_ = np.sqrt(m[:4 * n].reshape(n, 4)[:, :3].astype(np.float64)), np.sqrt(s[:4 * n].reshape(n, 4)[:, :3].astype(np.float64))
-    sel = on_moved & (m[4 * n:] > SPP) & np.isfinite(ref).all(1) & np.isfinite(am).all(1) & np.isfinite(as_).all(1)
+    m, s = chain(rt, torch, W, frames, p, True), chain(rt, torch, W, frames, p, False)
+    mr, sr = chain(rt, torch, W, frames, p, True, rt.temporal_rectify()), chain(rt, torch, W, frames, p, False, rt.temporal_rectify())
+    sphere = frames[-1]["hits"].cpu().numpy().view(rt.hit_record_dtype)["sphere"]
+    lamb = (sphere >= 0) & (kind[np.clip(sphere, 0, None)] == rt.MAT_LAMBERTIAN)
+    on_moved = np.isin(sphere, moved) & lamb
+    img = lambda h: np.sqrt(h[:4 * n].reshape(n, 4)[:, :3].astype(np.float64))
+    am, as_ = img(m), img(s)
+    fin = np.isfinite(ref).all(1) & np.isfinite(am).all(1) & np.isfinite(as_).all(1)
+    sel = on_moved & (m[4 * n:] > SPP) & fin
 
-    def e(img):
-        return float(np.sqrt(np.mean((img[sel] - ref[sel]) ** 2)))
-    say("%-28s %9d %9d %12.5f %12.5f %10.1f %10.1f" % ("every 7th small sphere" if every == 7 else "every small sphere", int(on_moved.sum()),
-                                                      int(sel.sum()), e(am), e(as_), float(m[4 * n:][sel].mean()), float(s[4 * n:][sel].mean())))
+    def e(a, mask):
+        return float(np.sqrt(np.mean((a[mask] - ref[mask]) ** 2)))
+    name = "every 7th small sphere" if every == 7 else "every small sphere"
+    say("%-28s %9d %9d %12.5f %12.5f %10.1f %10.1f" % (name, int(on_moved.sum()), int(sel.sum()), e(am, sel), e(as_, sel), float(m[4 * n:][sel].mean()),
+                                                      float(s[4 * n:][sel].mean())))
+    say("%-28s %9s %9s %12.5f %12.5f %10.1f %10.1f" % ("  rectified, defaults", "", "", e(img(mr), sel), e(img(sr), sel), float(mr[4 * n:][sel].mean()),
+                                                      float(sr[4 * n:][sel].mean())))
+    still = lamb & ~on_moved & (s[4 * n:] > SPP) & (m[4 * n:] > SPP) & fin
+    whole = (m[4 * n:] > 0) & fin
+    for label, mask in (("  lambertian, NOT moved", still), ("  every non-empty pixel", whole)):
+        say("%-28s %9s %9d %12.5f %12.5f %10.1f %10.1f   rectified %9.5f %9.5f  neff %5.1f %5.1f"
+            % (label, "", int(mask.sum()), e(am, mask), e(as_, mask), float(m[4 * n:][mask].mean()), float(s[4 * n:][mask].mean()), e(img(mr), mask),
+               e(img(sr), mask), float(mr[4 * n:][mask].mean()), float(sr[4 * n:][mask].mean())))
+    swept = {}
+    for radius, min_count, gamma in settings:
+        h = m if gamma == 0 else chain(rt, torch, W, frames, p, True, rt.temporal_rectify(radius=radius, min_count=min_count, gamma=gamma))
+        swept[(radius, min_count, gamma)] = e(img(h), whole)
     tree.close()
     W.close()
+    return swept
 
 
 def setup_times(rt, torch, say, n, spl):

@@ -1,6 +1,14 @@
 """Quality and cost of temporal accumulation (rt_temporal_accumulate, rt_denoise_history) on one GPU.
 
   python tools/temporal_study.py [OUT.txt]                        the quality tables and the parameter sweeps on C3, written to OUT.txt
+  python tools/temporal_study.py --rectify [OUT.txt]              history rectification (rt_temporal_accumulate_rectified): the sweep of
+                                                                  gamma, radius and min_count on five camera scenarios and the two moving
+                                                                  scenes of tools/animate_study.py, and the setting that loses least
+  python tools/temporal_study.py --rectify-kernels                k_temporal_accumulate_moving and k_temporal_accumulate_rectified side
+                                                                  by side, REPS + 1 times each on C3 and at 3840x2160: for rocprofv3
+  python tools/temporal_study.py --rectify-kernel-report DIR OUT  the kernel times of that run's trace, appended to OUT
+  python tools/temporal_study.py --rectify-pmc-report DIR OUT     the counters of --rectify-kernels runs under rocprofv3 --pmc (every
+                                                                  *counter_collection.csv below DIR), per kernel and frame size, appended to OUT
   python tools/temporal_study.py --kernels                        rt_temporal_accumulate + rt_denoise_history REPS + 1 times on C3 and on
                                                                   C5's world at 3840x2160: the run to put under rocprofv3 --kernel-trace --stats
   python tools/temporal_study.py --kernel-report DIR OUT          the kernel times of that run's trace, appended to OUT
@@ -61,13 +69,17 @@ class Path:
         torch.cuda.synchronize()
         base.close()
 
-    def history(self, rt, nx, ny, p):
-        """the history of the last frame: the chain over all frames with the parameters p"""
+    def history(self, rt, nx, ny, p, rectify=None):
+        """the history of the last frame: the chain over all frames with the parameters p (rectify: a TemporalRectify for the rectified call)"""
         bufs = [rt.alloc_temporal_history(nx, ny), rt.alloc_temporal_history(nx, ny)]
         for f, fr in enumerate(self.frames):
             prev = self.frames[f - 1] if f else None
-            rt.temporal_accumulate(bufs[f & 1], bufs[(f + 1) & 1] if f else None, fr["hits"], prev["hits"] if f else None, prev["cam"] if f else None,
-                                   fr["state"], fr["W"], nx, ny, p)
+            args = (bufs[f & 1], bufs[(f + 1) & 1] if f else None, fr["hits"], prev["hits"] if f else None, prev["cam"] if f else None,
+                    fr["state"], fr["W"], nx, ny, p)
+            if rectify is None:
+                rt.temporal_accumulate(*args)
+            else:
+                rt.temporal_accumulate_rectified(*args, rectify)
         return bufs[(len(self.frames) - 1) & 1]
 
     def close(self):
@@ -220,8 +232,204 @@ def kernel_report(d, path):
         fo.write(text)
 
 
+RECTIFY_GAMMA, RECTIFY_RADIUS, RECTIFY_MIN_COUNT = (0.5, 1.0, 1.5, 2.0, 3.0), (1, 2), (2, 4)
+RECTIFY_SCENARIOS = (("static camera", 0.0, 0), ("static camera, reuse_specular 1", 0.0, 1), ("orbit %g deg" % STEP, STEP, 0),
+                     ("orbit %g deg, reuse_specular 1" % STEP, STEP, 1), ("orbit 1 deg", 1.0, 0))
+
+
+def rectify_main():
+    """the sweep of rt_temporal_accumulate_rectified.  The figure of merit of every scenario is the RMSE of the unfiltered history (sqrt
+    of its mean, gamma frame) against the reference of the last frame over every pixel that is finite and not empty — the one figure
+    that exists for camera paths and moving scenes alike.  (0, 0, 0) is the unrectified call."""
+    import torch
+    import rt_amd as rt
+    import animate_study
+    torch.cuda.set_device(0)
+    path = next((a for a in sys.argv[1:] if not a.startswith("--")), None)
+    out = []
+
+    def say(line=""):
+        print(line, flush=True)
+        out.append(line)
+
+    settings = [(0, 0, 0.0)] + [(r, mc, g) for r in RECTIFY_RADIUS for mc in RECTIFY_MIN_COUNT for g in RECTIFY_GAMMA]
+    n = NX * NY
+    d = rt.TEMPORAL_RECTIFY_DEFAULTS
+    say("# tools/temporal_study.py --rectify: C3 scene %dx%d, N = %d, octree SPL %d, %d frames of %d spp, %s" % (NX, NY, N, SPL, FRAMES, SPP, torch.cuda.get_device_name(0)))
+    say("# defaults: radius %d, min_count %d, gamma %g; the temporal parameters at their defaults but for reuse_specular where stated"
+        % (d["radius"], d["min_count"], d["gamma"]))
+    say("# RMSE of sqrt(history) against rt_render(1024) at the last camera; all = every finite non-empty pixel, lamb = lambertian first hits")
+    table, paths = {}, {}
+    for label, step, spec in RECTIFY_SCENARIOS:
+        if step not in paths:
+            for P in paths.values():
+                P.close()
+            paths.clear()
+            P = paths[step] = Path(rt, torch, N, SPL, NX, NY, [f * step for f in range(FRAMES)], SPP)
+            last = P.frames[-1]
+            fb, st = rt.alloc_fb(NX, NY), rt.alloc_rand_state(NX, NY)
+            rt.render_init(NX, NY, st)
+            rt.render(fb, NX, NY, 1024, last["W"], st, last["O"])
+            torch.cuda.synchronize()
+            ref = fb.cpu().numpy().reshape(-1, 3).astype(np.float64)
+            sphere = last["hits"].cpu().numpy().view(rt.hit_record_dtype)["sphere"]
+            lamb = (sphere >= 0) & (P.kind[np.clip(sphere, 0, None)] == rt.MAT_LAMBERTIAN)
+        P = paths[step]
+        p = rt.temporal_params(reuse_specular=spec)
+        say()
+        say("## %s" % label)
+        say("%-34s %9s %9s %9s %9s %9s" % ("radius, min_count, gamma", "all", "lamb", "took", "neff", "neff<plain"))
+        plain = None
+        for r, mc, g in settings:
+            h = P.history(rt, NX, NY, p, None if g == 0 else rt.temporal_rectify(radius=r, min_count=mc, gamma=g))
+            torch.cuda.synchronize()
+            hh = h.cpu().numpy()
+            acc = np.sqrt(hh[:4 * n].reshape(n, 4)[:, :3].astype(np.float64))
+            neff = hh[4 * n:]
+            if plain is None:
+                plain = neff.copy()
+            ok = (neff > 0) & np.isfinite(ref).all(1) & np.isfinite(acc).all(1)
+            e = lambda m: float(np.sqrt(np.mean((acc[m] - ref[m]) ** 2)))
+            took = plain > SPP
+            table[(label, (r, mc, g))] = e(ok)
+            say("%-34s %9.5f %9.5f %8.1f%% %9.1f %8.1f%%" % ("unrectified" if g == 0 else "%d, %d, %g" % (r, mc, g), e(ok), e(ok & lamb), 100.0 * took.mean(),
+                                                            float(neff[took].mean()), 100.0 * float((neff[took] < plain[took]).mean())))
+        # the long history: max_history is the only brake of the unrectified call
+        for name, rect in (("max_history 2^30, unrectified", None), ("max_history 2^30, defaults", rt.temporal_rectify())):
+            hh = P.history(rt, NX, NY, rt.temporal_params(reuse_specular=spec, max_history=1 << 30), rect).cpu().numpy()
+            acc = np.sqrt(hh[:4 * n].reshape(n, 4)[:, :3].astype(np.float64))
+            ok = (hh[4 * n:] > 0) & np.isfinite(ref).all(1) & np.isfinite(acc).all(1)
+            say("%-34s %9.5f %9.5f %9s %9.1f" % (name, e(ok), e(ok & lamb), "", float(hh[4 * n:][took].mean())))
+    for P in paths.values():
+        P.close()
+    say()
+    say("## moving scenes (tools/animate_study.py: %dx%d, %d frames of %d spp, static camera, +%g in x per frame), moving rule"
+        % (animate_study.NX, animate_study.NY, animate_study.FRAMES, animate_study.SPP, animate_study.STEP))
+    say("%-28s %9s %9s %12s %12s %10s %10s" % ("moved", "pixels on", "compared", "moving rule", "static rule", "neff mov.", "neff st."))
+    for every in (1, 7):
+        label = "moving: every small sphere" if every == 1 else "moving: every 7th small sphere"
+        for key, val in animate_study.quality(rt, torch, say, every, settings).items():
+            table[(label, key)] = val
+    labels = []
+    for (label, _) in table:
+        if label not in labels:
+            labels.append(label)
+    say()
+    say("## every non-empty pixel, RMSE by scenario (columns in the order below) and setting")
+    for k, label in enumerate(labels):
+        say("#   %d: %s" % (k, label))
+    for key in settings:
+        say("%-16s " % ("unrectified" if key[2] == 0 else "%d, %d, %g" % key) + " ".join("%9.5f" % table[(label, key)] for label in labels))
+    say()
+    say("## one setting for all: the worst loss against each scenario's own optimum on this grid (the unrectified call is a setting too)")
+    own = {label: min(table[(label, key)] for key in settings) for label in labels}
+    loss = {key: max(table[(label, key)] / own[label] - 1.0 for label in labels) for key in settings}
+    for key in sorted(loss, key=loss.get):
+        worst = max(labels, key=lambda label: table[(label, key)] / own[label])
+        say("%-16s worst loss %5.1f %%  (%s)" % ("unrectified" if key[2] == 0 else "%d, %d, %g" % key, 100 * loss[key], worst))
+    if path:
+        os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
+        with open(path, "w") as f:
+            f.write("\n".join(out) + "\n")
+
+
+def rectify_kernels():
+    """two frames STEP degrees apart, then rt_temporal_accumulate_moving (nothing moved: the yardstick) and
+    rt_temporal_accumulate_rectified under the moving rule at radius 1 and 2, REPS + 1 times each in turn, on C3 and at 3840x2160"""
+    import torch
+    import rt_amd as rt
+    torch.cuda.set_device(0)
+    for n, spl, nx, ny in ((N, SPL, NX, NY), (100000, 320, 3840, 2160)):
+        P = Path(rt, torch, n, spl, nx, ny, [0.0, STEP], 4)
+        a, b = P.frames
+        h0, h1 = rt.alloc_temporal_history(nx, ny), rt.alloc_temporal_history(nx, ny)
+        p = rt.temporal_params()
+        geom = b["W"].get_geometry()
+        rt.temporal_accumulate(h0, None, a["hits"], None, None, a["state"], a["W"], nx, ny, p)
+        torch.cuda.synchronize()
+        for _ in range(REPS + 1):
+            rt.temporal_accumulate_moving(h1, h0, b["hits"], a["hits"], a["cam"], geom, b["state"], b["W"], nx, ny, p)
+            for radius in (1, 2):
+                rt.temporal_accumulate_rectified(h1, h0, b["hits"], a["hits"], a["cam"], b["state"], b["W"], nx, ny, p, rt.temporal_rectify(radius=radius),
+                                                 d_geom_prev=geom)
+            torch.cuda.synchronize()
+        print("%dx%d N=%d: %d x (moving, rectified r1, rectified r2)" % (nx, ny, n, REPS + 1), flush=True)
+        P.close()
+
+
+def rectify_kernel_report(d, path):
+    """median times of the three kernels of a --rectify-kernels run; the first call of each on each frame size is the warm-up"""
+    f = glob.glob(os.path.join(d, "**", "*kernel_trace.csv"), recursive=True)[0]
+    rows = list(csv.DictReader(open(f)))
+    rows.sort(key=lambda r: int(r["Start_Timestamp"]))
+    t = {"moving": [], "r1": [], "r2": []}
+    for r in rows:
+        name = r["Kernel_Name"]
+        dur = (int(r["End_Timestamp"]) - int(r["Start_Timestamp"])) / 1e3
+        if "k_temporal_accumulate_rectified" in name:
+            t["r2" if ("1, 2>" in name or "true, 2>" in name or "Lb1ELi2E" in name) else "r1"].append(dur)
+        elif "k_temporal_accumulate_moving" in name:
+            t["moving"].append(dur)
+    lines = ["", "## kernel times under rocprofv3 --kernel-trace --stats (tools/temporal_study.py --rectify-kernels), median of %d calls, us" % REPS,
+             "# one run: the three kernels alternate; k_temporal_accumulate_moving is the yardstick (nothing moved, same inputs, same history)",
+             "%-22s %30s %28s %8s %28s %8s" % ("frame", "k_temporal_accumulate_moving", "rectified<true, 1>", "ratio", "rectified<true, 2>", "ratio")]
+    for k, frame in enumerate(("C3 1200x800", "C5 world 3840x2160")):
+        med = {key: float(np.median(v[k * (REPS + 1) + 1:(k + 1) * (REPS + 1)])) for key, v in t.items()}
+        lines.append("%-22s %30.1f %28.1f %8.2f %28.1f %8.2f" % (frame, med["moving"], med["r1"], med["r1"] / med["moving"], med["r2"], med["r2"] / med["moving"]))
+    text = "\n".join(lines) + "\n"
+    print(text)
+    with open(path, "a") as fo:
+        fo.write(text)
+
+
+def rectify_pmc_report(d, path):
+    """per counter the mean over the timed dispatches (the first of each kernel on each frame size is the warm-up) of the three kernels"""
+    acc = {}
+    for f in sorted(glob.glob(os.path.join(d, "**", "*counter_collection.csv"), recursive=True)):
+        seen = {}
+        for r in csv.DictReader(open(f)):
+            name = r["Kernel_Name"]
+            if "k_temporal_accumulate_rectified" in name:
+                key = "r2" if ("true, 2>" in name or "Lb1ELi2E" in name) else "r1"
+            elif "k_temporal_accumulate_moving" in name:
+                key = "moving"
+            else:
+                continue
+            ids = seen.setdefault((key, r["Counter_Name"]), [])
+            if r["Dispatch_Id"] not in ids:
+                ids.append(r["Dispatch_Id"])
+            k = ids.index(r["Dispatch_Id"])
+            if k % (REPS + 1) == 0:
+                continue
+            slot = acc.setdefault((r["Counter_Name"], k // (REPS + 1), key), [0.0, set()])
+            slot[0] += float(r["Counter_Value"])
+            slot[1].add(r["Dispatch_Id"])
+    lines = ["", "## counters under rocprofv3 --pmc (runs of their own; tools/temporal_study.py --rectify-kernels), mean of %d dispatches" % REPS,
+             "%-32s %-20s %16s %16s %8s %16s %8s" % ("counter", "frame", "moving", "rectified r1", "ratio", "rectified r2", "ratio")]
+    for counter in sorted({k[0] for k in acc}):
+        for size, frame in enumerate(("C3 1200x800", "C5 world 3840x2160")):
+            v = {key: acc[(counter, size, key)][0] / max(1, len(acc[(counter, size, key)][1])) for key in ("moving", "r1", "r2") if (counter, size, key) in acc}
+            if len(v) == 3:
+                m = v["moving"] or float("nan")
+                lines.append("%-32s %-20s %16.0f %16.0f %8.2f %16.0f %8.2f" % (counter, frame, v["moving"], v["r1"], v["r1"] / m, v["r2"], v["r2"] / m))
+    text = "\n".join(lines) + "\n"
+    print(text)
+    with open(path, "a") as fo:
+        fo.write(text)
+
+
 if __name__ == "__main__":
-    if "--kernels" in sys.argv[1:]:
+    if "--rectify-pmc-report" in sys.argv[1:]:
+        i = sys.argv.index("--rectify-pmc-report")
+        rectify_pmc_report(sys.argv[i + 1], sys.argv[i + 2])
+    elif "--rectify" in sys.argv[1:]:
+        rectify_main()
+    elif "--rectify-kernels" in sys.argv[1:]:
+        rectify_kernels()
+    elif "--rectify-kernel-report" in sys.argv[1:]:
+        i = sys.argv.index("--rectify-kernel-report")
+        rectify_kernel_report(sys.argv[i + 1], sys.argv[i + 2])
+    elif "--kernels" in sys.argv[1:]:
         kernels()
     elif "--kernel-report" in sys.argv[1:]:
         i = sys.argv.index("--kernel-report")
