@@ -270,8 +270,8 @@ static int ctx_reserve_adaptive(rt_render_ctx& C, int64_t pixels, int rounds) {
     return group_reserve(C.a_rounds, rounds, rounds_group(C, rounds));
 }
 // ... and of the budget selection for states of up to `pixels` elements (rt_budget.hip)
-static int ctx_reserve_budget(rt_render_ctx& C, int64_t pixels, bool filtered = false) {
-    const size_t bytes = budget_ws_bytes(pixels, filtered);
+static int ctx_reserve_budget(rt_render_ctx& C) {
+    const size_t bytes = budget_ws_bytes();
     return group_reserve(C.b_bytes, (int64_t)bytes, budget_group(C, bytes));
 }
 static int ctx_release(rt_render_ctx& C) {
@@ -1247,88 +1247,93 @@ int rt_adaptive_budget_picks(const rt_budget* params, int round, int64_t* picks)
     *picks = budget_picks(params, round);
     return 0;
 }
-// The selection alone.  The key bits go to the second half of the context's lists, the caller's list receives the ids.
-int rt_adaptive_budget_select(rt_render_ctx* ctx, const void* d_state, int max_x, int max_y, rt_partition part, const rt_budget* params,
-                              int64_t picks, uint32_t* d_list, uint32_t* d_count, void* stream) {
-    FrameCall F; const rt_octree* none = nullptr;
-    const int rc = frame_begin(F, ctx, ctx && budget_params_ok(params) && picks >= 0 && picks <= (int64_t)0xffffffffll, d_state && d_list && d_count,
-                               max_x, max_y, part, nullptr, none, stream);
-    if (rc || !F.npx) return rc;
-    rt_render_ctx& C = *F.C;
-    RT_TRY(ctx_reserve_adaptive(C, F.npx, 1));
-    RT_TRY(ctx_reserve_budget(C, F.npx));
-    RT_TRY(ctx_wait_previous(C, F.st));
-    RT_TRY(launch_budget_select(adapt_state(const_cast<void*>(d_state), F.npx), F.npx, F.fr, params->batch, params->max_spp, params->floor,
-                                (unsigned int)std::min(picks, F.npx), C.a_list + F.npx, C.b_ws, d_list, d_count, F.st));
-    return ctx_mark_done(C, F.st);
-}
-// The same with the filter-aware key (whole frames only): every refusal comes before the context is looked at.
-int rt_adaptive_budget_select_filtered(rt_render_ctx* ctx, const void* d_state, const rt_hit_record* d_hits, int max_x, int max_y, const rt_budget* params,
-                                       const rt_denoise_var_params* filter, int64_t picks, uint32_t* d_list, uint32_t* d_count, float* d_keys, void* stream) {
-    FrameCall F; const rt_octree* none = nullptr;
-    const bool params_ok = ctx && budget_params_ok(params) && picks >= 0 && picks <= (int64_t)0xffffffffll && !rt_denoise_adaptive_check(max_x, max_y, filter);
-    const bool pointers_ok = d_state && d_list && d_count && d_hits && !((uintptr_t)d_hits & 15);       // (the guides are read as float4)
-    const int rc = frame_begin(F, ctx, params_ok, pointers_ok, max_x, max_y, kWhole, nullptr, none, stream);
-    if (rc || !F.npx) return rc;
-    rt_render_ctx& C = *F.C;
-    RT_TRY(ctx_reserve_adaptive(C, F.npx, 1));
-    RT_TRY(ctx_reserve_budget(C, F.npx, true));
-    RT_TRY(ctx_wait_previous(C, F.st));
-    RT_TRY(launch_budget_select_filtered(adapt_state(const_cast<void*>(d_state), F.npx), d_hits, max_x, max_y, *filter, params->batch, params->max_spp,
-                                         params->floor, (unsigned int)std::min(picks, F.npx), C.a_list + F.npx, d_keys, C.b_ws, d_list, d_count, F.st));
-    return ctx_mark_done(C, F.st);
-}
-// The same with the history-aware key (whole frames only; the world supplies kind[] and is uploaded if need be).
+// What a call has to hold for its key (BudgetKey, rt_launch.h): params_ok is refused before anything else is looked at, pointers_ok
+// after the frame's size (frame_begin).  A FILTERED or TEMPORAL key ranks whole frames only.
 static bool temporal_inputs_ok(const rt_temporal_inputs* in) {
     if (!in || !in->d_hits || ((uintptr_t)in->d_hits & 15) || ((uintptr_t)in->d_hist_in & 15)) return false;      // (read as float4)
     return !in->d_hist_in || (in->d_hits_prev && in->cam_prev && !((uintptr_t)in->d_hits_prev & 15));
 }
-int rt_adaptive_budget_select_temporal(rt_render_ctx* ctx, const void* d_state, const rt_world* world, int max_x, int max_y, const rt_budget* params,
-                                       const rt_temporal_inputs* in, const rt_temporal_params* temporal, int64_t picks, uint32_t* d_list,
-                                       uint32_t* d_count, float* d_keys, void* stream) {
+static bool budget_key_params_ok(const BudgetKey& key, int max_x, int max_y) {
+    if (key.rank == BudgetKey::FILTERED) return !rt_denoise_adaptive_check(max_x, max_y, key.filter);
+    if (key.rank == BudgetKey::TEMPORAL) return !rt_temporal_check(max_x, max_y, key.temporal);
+    return true;
+}
+static bool budget_key_pointers_ok(const BudgetKey& key) {
+    if (key.rank == BudgetKey::FILTERED) return key.hits && !((uintptr_t)key.hits & 15);                          // (the guides are read as float4)
+    if (key.rank == BudgetKey::TEMPORAL) return temporal_inputs_ok(key.in);
+    return true;
+}
+// One selection on the prepared context of a call whose key has passed both checks: the K elements with the largest keys into list,
+// their number into *count.  The key bits go to the second half of the context's lists.  world (TEMPORAL; uploaded): supplies kind[].
+static int budget_select_run(rt_render_ctx& C, const FrameCall& F, BudgetKey key, const rt_world* world, const void* d_state, const rt_budget* P,
+                             unsigned int K, uint32_t* list, uint32_t* count) {
+    if (key.rank == BudgetKey::TEMPORAL) { key.kind = world->z->dev.kind; key.n_kind = world->n; }
+    RT_TRY(launch_budget_select(key, d_state, F.npx, F.fr, P->batch, P->max_spp, P->floor, K, C.a_list + F.npx, C.b_ws, list, count, F.st));
+    return 0;
+}
+// The selection alone: the caller's list receives the ids.  Every refusal comes before the context is looked at.  kinds: the world of
+// a TEMPORAL key (uploaded if need be).
+static int budget_select_common(rt_render_ctx* ctx, const BudgetKey& key, const rt_world* kinds, const void* d_state, int max_x, int max_y,
+                                rt_partition part, const rt_budget* params, int64_t picks, uint32_t* d_list, uint32_t* d_count, void* stream) {
     FrameCall F; const rt_octree* none = nullptr;
-    const bool params_ok = ctx && world && budget_params_ok(params) && picks >= 0 && picks <= (int64_t)0xffffffffll && !rt_temporal_check(max_x, max_y, temporal);
-    const bool pointers_ok = d_state && d_list && d_count && temporal_inputs_ok(in);
-    const int rc = frame_begin(F, ctx, params_ok, pointers_ok, max_x, max_y, kWhole, nullptr, none, stream, world);
+    const bool params_ok = ctx && (kinds || key.rank != BudgetKey::TEMPORAL) && budget_params_ok(params) && picks >= 0 &&
+                           picks <= (int64_t)0xffffffffll && budget_key_params_ok(key, max_x, max_y);
+    const bool pointers_ok = d_state && d_list && d_count && budget_key_pointers_ok(key);
+    const int rc = frame_begin(F, ctx, params_ok, pointers_ok, max_x, max_y, part, nullptr, none, stream, kinds);
     if (rc || !F.npx) return rc;
     rt_render_ctx& C = *F.C;
     RT_TRY(ctx_reserve_adaptive(C, F.npx, 1));
-    RT_TRY(ctx_reserve_budget(C, F.npx));
+    RT_TRY(ctx_reserve_budget(C));
     RT_TRY(ctx_wait_previous(C, F.st));
-    RT_TRY(launch_budget_select_temporal(d_state, in->d_hist_in, in->d_hits, in->d_hits_prev, in->cam_prev, world->z->dev.kind, world->n, max_x, max_y,
-                                         *temporal, params->batch, params->max_spp, params->floor, (unsigned int)std::min(picks, F.npx), C.a_list + F.npx,
-                                         d_keys, C.b_ws, d_list, d_count, F.st));
+    RT_TRY(budget_select_run(C, F, key, kinds, d_state, params, (unsigned int)std::min(picks, F.npx), d_list, d_count));
     return ctx_mark_done(C, F.st);
 }
-// rt_render_adaptive_spend: `rounds` times — select K_r pixels, seed fb with their sums, `batch` samples for each through the resumed
-// k_render<*, 2, *>, finalise them.  Every round ends with every pixel finalised, so R rounds are R calls of one round.
+static BudgetKey budget_key_filtered(const rt_hit_record* d_hits, const rt_denoise_var_params* filter, float* d_keys = nullptr) {
+    BudgetKey key;
+    key.rank = BudgetKey::FILTERED; key.hits = d_hits; key.filter = filter; key.keys_out = d_keys;
+    return key;
+}
+static BudgetKey budget_key_temporal(const rt_temporal_inputs* in, const rt_temporal_params* temporal, float* d_keys = nullptr) {
+    BudgetKey key;
+    key.rank = BudgetKey::TEMPORAL; key.in = in; key.temporal = temporal; key.keys_out = d_keys;
+    return key;
+}
+int rt_adaptive_budget_select(rt_render_ctx* ctx, const void* d_state, int max_x, int max_y, rt_partition part, const rt_budget* params,
+                              int64_t picks, uint32_t* d_list, uint32_t* d_count, void* stream) {
+    return budget_select_common(ctx, BudgetKey(), nullptr, d_state, max_x, max_y, part, params, picks, d_list, d_count, stream);
+}
+// The same with the filter-aware key (whole frames only).
+int rt_adaptive_budget_select_filtered(rt_render_ctx* ctx, const void* d_state, const rt_hit_record* d_hits, int max_x, int max_y, const rt_budget* params,
+                                       const rt_denoise_var_params* filter, int64_t picks, uint32_t* d_list, uint32_t* d_count, float* d_keys, void* stream) {
+    return budget_select_common(ctx, budget_key_filtered(d_hits, filter, d_keys), nullptr, d_state, max_x, max_y, kWhole, params, picks, d_list, d_count, stream);
+}
+// The same with the history-aware key (whole frames only; the world supplies kind[] and is uploaded if need be).
+int rt_adaptive_budget_select_temporal(rt_render_ctx* ctx, const void* d_state, const rt_world* world, int max_x, int max_y, const rt_budget* params,
+                                       const rt_temporal_inputs* in, const rt_temporal_params* temporal, int64_t picks, uint32_t* d_list,
+                                       uint32_t* d_count, float* d_keys, void* stream) {
+    return budget_select_common(ctx, budget_key_temporal(in, temporal, d_keys), world, d_state, max_x, max_y, kWhole, params, picks, d_list, d_count, stream);
+}
+// rt_render_adaptive_spend: `rounds` times — select K_r pixels by `key`, seed fb with their sums, `batch` samples for each through the
+// resumed k_render<*, 2, *>, finalise them.  Every round ends with every pixel finalised, so R rounds are R calls of one round.
 static int render_adaptive_spend_common(rt_render_ctx* ctx, void* fb, int max_x, int max_y, const rt_budget* P, const rt_world* world,
                                         rt_rand_state* d_rand_state, const rt_octree* d_octree, int32_t* d_spp, void* d_state, rt_partition part,
-                                        uint32_t* d_picked, void* stream, bool filtered = false, const rt_denoise_var_params* filter = nullptr,
-                                        const rt_hit_record* d_hits = nullptr, bool history = false, const rt_temporal_inputs* tin = nullptr,
-                                        const rt_temporal_params* tpar = nullptr) {
+                                        uint32_t* d_picked, void* stream, const BudgetKey& key = BudgetKey()) {
     FrameCall F;
-    const bool params_ok = budget_params_ok(P) && world && !(filtered && rt_denoise_adaptive_check(max_x, max_y, filter)) &&
-                           !(history && rt_temporal_check(max_x, max_y, tpar));
-    const bool pointers_ok = fb && d_rand_state && d_state && !(filtered && (!d_hits || ((uintptr_t)d_hits & 15))) && !(history && !temporal_inputs_ok(tin));
+    const bool params_ok = budget_params_ok(P) && world && budget_key_params_ok(key, max_x, max_y);
+    const bool pointers_ok = fb && d_rand_state && d_state && budget_key_pointers_ok(key);
     const int rc = frame_begin(F, ctx, params_ok, pointers_ok, max_x, max_y, part, world, d_octree, stream);
     if (rc || !F.npx) return rc;
     rt_render_ctx& C = *F.C; const hipStream_t st = F.st; const int64_t npx = F.npx;
     const AdaptState S = adapt_state(d_state, npx);
     RenderArgs A = frame_args(fb, max_x, max_y, P->batch, world, d_rand_state, d_octree, part);
     RT_TRY(ctx_reserve_adaptive(C, npx, 1));
-    RT_TRY(ctx_reserve_budget(C, npx, filtered));
+    RT_TRY(ctx_reserve_budget(C));
     RT_TRY(ctx_wait_previous(C, st));
     A.ad_sl = S.sl; A.ad_q = S.q; A.ad_list = C.a_list; A.ad_count = C.a_count;      // (one count serves every round: the stream orders them)
     RT_TRY(ctx_timed_begin(C, st));
     for (int r = 0; r < P->rounds; ++r) {
         const unsigned int K = (unsigned int)std::min(budget_picks(P, r), npx);
-        if (filtered) RT_TRY(launch_budget_select_filtered(S, d_hits, max_x, max_y, *filter, P->batch, P->max_spp, P->floor, K, C.a_list + npx, nullptr,
-                                                           C.b_ws, C.a_list, C.a_count, st));
-        else if (history) RT_TRY(launch_budget_select_temporal(d_state, tin->d_hist_in, tin->d_hits, tin->d_hits_prev, tin->cam_prev, world->z->dev.kind,
-                                                               world->n, max_x, max_y, *tpar, P->batch, P->max_spp, P->floor, K, C.a_list + npx, nullptr,
-                                                               C.b_ws, C.a_list, C.a_count, st));
-        else RT_TRY(launch_budget_select(S, npx, F.fr, P->batch, P->max_spp, P->floor, K, C.a_list + npx, C.b_ws, C.a_list, C.a_count, st));
+        RT_TRY(budget_select_run(C, F, key, world, d_state, P, K, C.a_list, C.a_count));
         RT_TRY(launch_budget_seed((float*)fb, S, A.ad_list, A.ad_count, K, st));
         RT_TRY(resumed_round(C, A, F.tree, st));
         RT_TRY(launch_budget_final((float*)fb, S, A.ad_list, A.ad_count, K, d_spp, P->batch, d_picked ? d_picked + r : nullptr, st));
@@ -1352,14 +1357,14 @@ int rt_render_adaptive_spend_filtered(void* fb, int max_x, int max_y, const rt_b
                                       const rt_hit_record* d_hits, const rt_world* world, rt_rand_state* d_rand_state, const rt_octree* d_octree,
                                       int32_t* d_spp, void* d_state, uint32_t* d_picked, void* stream) {
     return render_adaptive_spend_common(nullptr, fb, max_x, max_y, params, world, d_rand_state, d_octree, d_spp, d_state, kWhole, d_picked,
-                                        stream, true, filter, d_hits);
+                                        stream, budget_key_filtered(d_hits, filter));
 }
 int rt_render_adaptive_spend_filtered_on(rt_render_ctx* ctx, void* fb, int max_x, int max_y, const rt_budget* params, const rt_denoise_var_params* filter,
                                          const rt_hit_record* d_hits, const rt_world* world, rt_rand_state* d_rand_state, const rt_octree* d_octree,
                                          int32_t* d_spp, void* d_state, uint32_t* d_picked, void* stream) {
     if (!ctx) return RT_EINVAL;
     return render_adaptive_spend_common(ctx, fb, max_x, max_y, params, world, d_rand_state, d_octree, d_spp, d_state, kWhole, d_picked,
-                                        stream, true, filter, d_hits);
+                                        stream, budget_key_filtered(d_hits, filter));
 }
 // ... with the history-aware key: the whole frame (a tile-major part has no neighbours to reproject into); the key is formed anew every
 // round from the current state and the unchanged history of the last frame
@@ -1367,14 +1372,14 @@ int rt_render_adaptive_spend_temporal(void* fb, int max_x, int max_y, const rt_b
                                       const rt_temporal_params* temporal, const rt_world* world, rt_rand_state* d_rand_state, const rt_octree* d_octree,
                                       int32_t* d_spp, void* d_state, uint32_t* d_picked, void* stream) {
     return render_adaptive_spend_common(nullptr, fb, max_x, max_y, params, world, d_rand_state, d_octree, d_spp, d_state, kWhole, d_picked,
-                                        stream, false, nullptr, nullptr, true, in, temporal);
+                                        stream, budget_key_temporal(in, temporal));
 }
 int rt_render_adaptive_spend_temporal_on(rt_render_ctx* ctx, void* fb, int max_x, int max_y, const rt_budget* params, const rt_temporal_inputs* in,
                                          const rt_temporal_params* temporal, const rt_world* world, rt_rand_state* d_rand_state,
                                          const rt_octree* d_octree, int32_t* d_spp, void* d_state, uint32_t* d_picked, void* stream) {
     if (!ctx) return RT_EINVAL;
     return render_adaptive_spend_common(ctx, fb, max_x, max_y, params, world, d_rand_state, d_octree, d_spp, d_state, kWhole, d_picked,
-                                        stream, false, nullptr, nullptr, true, in, temporal);
+                                        stream, budget_key_temporal(in, temporal));
 }
 
 // the kernel rt_render (mode 0) / rt_render_progressive (mode 1) launches for this world and tree — the library's own

@@ -85,10 +85,6 @@ hipError_t launch_denoise_var(float* fb_out, const float* fb_in, int max_x, int 
                               const rt_denoise_var_params& P, float4* work, hipStream_t st);
 hipError_t launch_denoise_var_levels(float* fb_out, int max_x, int max_y, const rt_hit_record* hits, const rt_denoise_var_params& P, float4* work,
                                      hipStream_t st);
-#ifdef RT_BUDGET_FILTER_UNFUSED
-hipError_t launch_denoise_var_level0(const float* fb_in, int max_x, int max_y, const rt_hit_record* hits, const void* state,
-                                     const rt_denoise_var_params& P, float4* work, hipStream_t st);
-#endif
 
 // ---- rt_temporal.hip
 hipError_t launch_temporal_accumulate(void* hist_out, const void* hist_in, const rt_hit_record* hits, const rt_hit_record* hits_prev,
@@ -112,16 +108,22 @@ hipError_t launch_temporal_accumulate_rectified(void* hist_out, const void* hist
                                                 const rt_temporal_rectify& Rc, hipStream_t st);
 
 // ---- rt_budget.hip
-size_t budget_ws_bytes(long long n, bool filtered);
-hipError_t launch_budget_select(const AdaptState& s, long long n, const AdaptFrame& fr, int batch, int max_spp, float floor_lum, unsigned int K,
-                                unsigned int* keys, unsigned int* ws, unsigned int* list, unsigned int* count, hipStream_t st);
-hipError_t launch_budget_select_filtered(const AdaptState& s, const rt_hit_record* hits, int max_x, int max_y, const rt_denoise_var_params& P, int batch,
-                                         int max_spp, float floor_lum, unsigned int K, unsigned int* keys, float* keys_out, unsigned int* ws,
-                                         unsigned int* list, unsigned int* count, hipStream_t st);
-hipError_t launch_budget_select_temporal(const void* state, const void* hist_in, const rt_hit_record* hits, const rt_hit_record* hits_prev,
-                                         const rt_camera* cam_prev, const int32_t* kind, int n_kind, int max_x, int max_y, const rt_temporal_params& P,
-                                         int batch, int max_spp, float floor_lum, unsigned int K, unsigned int* keys, float* keys_out, unsigned int* ws,
-                                         unsigned int* list, unsigned int* count, hipStream_t st);
+size_t budget_ws_bytes();
+// Which key ranks the pixels of a selection, with that key's inputs (checked by the caller, rt_api.hip):
+//   RAW       rt_adaptive_priority of the state's own (SL, Q, k); any part of a frame
+//   FILTERED  rt_adaptive_priority_filtered of level 0 of rt_denoise_adaptive(filter) on the state; whole row-major frames of at most
+//             RT_DENOISE_MAX_PIXELS pixels, hits: the frame's guides, 16-byte aligned
+//   TEMPORAL  rt_adaptive_priority_filtered of what rt_temporal_accumulate(in, temporal) would write; whole frames as FILTERED, the
+//             histories and guides of `in` 16-byte aligned (d_hist_in == nullptr: the first frame), kind[n_kind]: RT_MAT_* of the world list
+// keys_out (FILTERED, TEMPORAL; may be NULL): the key of every pixel before the eligibility mask.
+struct BudgetKey {
+    enum Rank { RAW, FILTERED, TEMPORAL } rank = RAW;
+    const rt_hit_record* hits = nullptr; const rt_denoise_var_params* filter = nullptr;
+    const rt_temporal_inputs* in = nullptr; const rt_temporal_params* temporal = nullptr; const int32_t* kind = nullptr; int n_kind = 0;
+    float* keys_out = nullptr;
+};
+hipError_t launch_budget_select(const BudgetKey& key, const void* state, long long n, const AdaptFrame& fr, int batch, int max_spp, float floor_lum,
+                                unsigned int K, unsigned int* keys, unsigned int* ws, unsigned int* list, unsigned int* count, hipStream_t st);
 hipError_t launch_budget_seed(float* fb, const AdaptState& s, const unsigned int* list, const unsigned int* count, unsigned int cap, hipStream_t st);
 hipError_t launch_budget_final(float* fb, const AdaptState& s, const unsigned int* list, const unsigned int* count, unsigned int cap, int32_t* spp, int batch,
                                uint32_t* picked, hipStream_t st);

@@ -9,6 +9,7 @@
 #include <hip/hip_runtime.h>
 #include "../../include/rt_amd.h"
 #include "rt_device.h"
+#include "rt_filter.h"
 
 #pragma clang fp contract(off)
 
@@ -66,19 +67,11 @@ struct TemporalFrame { float4 c, gp0, gp1; float nf, sl, q; int k, sp; bool empt
 
 __device__ __forceinline__ TemporalFrame temporal_frame(const TemporalArgs& T, int p) {
     TemporalFrame f;
-    const long long e = 3 * (long long)p;
-    // the "per pixel" line of rt_denoise_adaptive
-    f.k = T.S.k[p];
-    f.nf = (float)f.k;
-    f.c.x = T.S.rgb[e] / f.nf; f.c.y = T.S.rgb[e + 1] / f.nf; f.c.z = T.S.rgb[e + 2] / f.nf;
-    f.sl = T.S.sl[p];
-    f.q = T.S.q[p];
-    float d = f.nf * f.q - f.sl * f.sl;
-    d = d > 0.0f ? d : 0.0f;
-    f.c.w = d / ((f.nf * f.nf) * (f.nf - 1.0f));
+    const StateMoments m = state_moments(T.S, p);                  // the "per pixel" line of rt_denoise_adaptive
+    f.k = m.k; f.nf = m.nf; f.c = m.c; f.sl = m.sl; f.q = m.q;
     f.gp0 = T.g[2 * p]; f.gp1 = T.g[2 * p + 1];
     f.sp = __float_as_int(f.gp1.w);
-    f.empty = f.sp == -1 || f.k < 2 || !__builtin_isfinite(f.c.x) || !__builtin_isfinite(f.c.y) || !__builtin_isfinite(f.c.z) || !__builtin_isfinite(f.c.w);
+    f.empty = state_pass_through(m, f.sp);
     return f;
 }
 

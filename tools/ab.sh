@@ -6,7 +6,7 @@
 # The variants are timed in ROUNDS interleaved passes (clock / thermal drift hits all alike); prints per variant the
 # median and minimum kernel time and the median step time.  -p also runs the GPU parity suite against the LAST variant.
 # -s: time the budget selection instead (tools/adaptive_budget_study.py --select, which bench.py never runs): one table per variant,
-# with a checksum of the chosen sets (e.g. tools/ab.sh -s base budget_sort after tools/mkvariant.sh budget_sort -DRT_BUDGET_SORT).
+# with a checksum of the chosen sets (e.g. tools/ab.sh -s base probe after tools/mkvariant.sh probe -DSWITCH).
 cfg=c3; parity=0; rounds=3; selection=0
 while getopts "c:pr:s" o; do case $o in c) cfg=$OPTARG;; p) parity=1;; r) rounds=$OPTARG;; s) selection=1;; esac; done
 shift $((OPTIND - 1))

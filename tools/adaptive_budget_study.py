@@ -7,8 +7,8 @@
       minimum and maximum of REPS runs after a warm-up (host clock around the call and a device synchronise; the context's events).
   python tools/adaptive_budget_study.py --select [OUT.txt]
       the selection alone at the C3 and C5 frame sizes: host clock over CALLS back-to-back calls and one synchronise, minimum of REPS
-      after a warm-up, and a checksum of the chosen set.  Run it once per library (RT_AMD_LIB=.../variants/lib_budget_sort.so for the
-      -DRT_BUDGET_SORT build of tools/mkvariant.sh): equal checksums are the on-device cross-check, the times the A/B.
+      after a warm-up, and a checksum of the chosen set.  RT_AMD_LIB selects another build of the library (a parent commit's, a
+      tools/mkvariant.sh variant): equal checksums say both choose the same sets, the times are the A/B.
   rocprofv3 --kernel-trace --stats --output-format csv -d DIR -- python tools/adaptive_budget_study.py --kernels
   python tools/adaptive_budget_study.py --kernel-report DIR OUT.txt
       device times of one round: the selection kernels, seed and finalise, the round's render kernel, and k_adapt_refine_seed plus one

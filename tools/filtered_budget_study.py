@@ -9,14 +9,12 @@
       per-pixel sample counts of R and F at a mean of 32, with 4 rounds of batch 8 and with 12 rounds of batch 8.
   python tools/filtered_budget_study.py --select [OUT.txt]
       the filtered selection alone at the C3 and C5 frame sizes: host clock over CALLS back-to-back calls and one synchronise,
-      minimum of REPS after a warm-up, checksums of the key map and of the chosen set.  Run it once per library
-      (RT_AMD_LIB=.../variants/lib_budget_filter_unfused.so for the -DRT_BUDGET_FILTER_UNFUSED build of tools/mkvariant.sh): equal
-      checksums are the on-device cross-check of the fused kernel, the times the A/B.
+      minimum of REPS after a warm-up, checksums of the key map and of the chosen set.  RT_AMD_LIB selects another build of the
+      library (a parent commit's, a tools/mkvariant.sh variant): equal checksums say both rank alike, the times are the A/B.
   rocprofv3 --kernel-trace --stats --output-format csv -d DIR -- python tools/filtered_budget_study.py --kernels
   python tools/filtered_budget_study.py --kernel-report DIR OUT.txt
-      device times of the key kernels (fused: k_budget_keys_filtered; unfused: k_denoise_var_prepare, k_denoise_var_level,
-      k_budget_keys_from_level), of the rest of the selection, of k_budget_keys and of one raw and one filtered round's render
-      kernel; median of REPS calls after a warm-up.  Once per library as well.
+      device times of the key kernel (k_budget_keys_filtered), of the rest of the selection, of k_budget_keys and of one raw and one
+      filtered round's render kernel; median of REPS calls after a warm-up.  Once per library as well.
 """
 import csv
 import glob
@@ -218,7 +216,7 @@ def kernels():
     ctx.close()
 
 
-KEY_KERNELS = ("k_budget_keys_filtered", "k_denoise_var_prepare", "k_denoise_var_level", "k_budget_keys_from_level")
+KEY_KERNELS = ("k_budget_keys_filtered",)
 
 
 def kernel_report(d, path):
@@ -234,7 +232,7 @@ def kernel_report(d, path):
     groups, cur = [], None
     for nm, dur in ev:
         base = nm.split("<")[0]
-        if base in ("k_budget_keys", "k_budget_keys_filtered", "k_denoise_var_prepare") and (cur is None or cur["done"]):
+        if base in ("k_budget_keys", "k_budget_keys_filtered") and (cur is None or cur["done"]):
             cur = {"keys": {}, "rest": 0.0, "render": 0.0, "done": False}
             groups.append(cur)
         if cur is None:
