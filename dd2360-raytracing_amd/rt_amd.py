@@ -13,7 +13,7 @@ LIB_PATH = os.environ.get("RT_AMD_LIB", os.path.join(_HERE, "librt_amd.so"))   #
 
 FP32, FP16 = 0, 1
 MAT_NONE, MAT_LAMBERTIAN, MAT_METAL, MAT_DIELECTRIC = -1, 0, 1, 2
-OCTREE_MAX_NODES = 585
+OCTREE_MAX_NODES = 585        # rt_amd.h RT_OCTREE_MAX_NODES
 TRAVERSAL_REFERENCE, TRAVERSAL_FAST = 0, 1
 ARITH_IEEE, ARITH_CONTRACT = 0, 1
 IMAGE_P3, IMAGE_P6, IMAGE_PFM = 0, 1, 2
@@ -68,7 +68,7 @@ class DenoiseParams(C.Structure):
                 ("sigma_position", C.c_float), ("sigma_color", C.c_float)]
 
 DENOISE_INPUT_GAMMA, DENOISE_INPUT_SUM = 0, 1      # rt_amd.h RT_DENOISE_INPUT_*
-DENOISE_MAX_LEVELS = 8
+DENOISE_MAX_LEVELS = 8         # rt_amd.h RT_DENOISE_MAX_LEVELS
 DENOISE_MAX_PIXELS = 1 << 30   # rt_amd.h RT_DENOISE_MAX_PIXELS: the largest frame of render_guides / denoise
 DENOISE_WORK_BYTES = 32        # rt_amd.h RT_DENOISE_WORK_BYTES: the workspace per pixel (two float4 colour buffers)
 # rt_amd.h RT_DENOISE_DEFAULT_*: chosen on C3 at 16 spp for the lowest RMSE against 1024 spp (tools/denoise_study.py)
@@ -77,9 +77,7 @@ DENOISE_DEFAULTS = dict(levels=2, normal_pow_log2=4, sigma_position=0.01, sigma_
 
 def denoise_params(input=DENOISE_INPUT_GAMMA, samples=1, **kw):
     """a DenoiseParams with the library's defaults for whatever kw does not set"""
-    p = dict(DENOISE_DEFAULTS)
-    p.update(kw)
-    return DenoiseParams(input, samples, p["levels"], p["normal_pow_log2"], p["sigma_position"], p["sigma_color"])
+    return _params(DenoiseParams, DENOISE_DEFAULTS, kw, input, samples)
 
 
 class DenoiseVarParams(C.Structure):
@@ -95,9 +93,7 @@ DENOISE_VAR_DEFAULTS = dict(levels=1, normal_pow_log2=4, prefilter=1, sigma_posi
 
 def denoise_var_params(**kw):
     """a DenoiseVarParams with the library's defaults for whatever kw does not set"""
-    p = dict(DENOISE_VAR_DEFAULTS)
-    p.update(kw)
-    return DenoiseVarParams(p["levels"], p["normal_pow_log2"], p["prefilter"], p["sigma_position"], p["sigma_variance"])
+    return _params(DenoiseVarParams, DENOISE_VAR_DEFAULTS, kw)
 
 
 class TemporalParams(C.Structure):
@@ -113,9 +109,7 @@ TEMPORAL_DEFAULTS = dict(max_history=32, reuse_specular=0, position_tolerance=0.
 
 def temporal_params(**kw):
     """a TemporalParams with the library's defaults for whatever kw does not set"""
-    p = dict(TEMPORAL_DEFAULTS)
-    p.update(kw)
-    return TemporalParams(p["max_history"], p["reuse_specular"], p["position_tolerance"], p["normal_min_dot"])
+    return _params(TemporalParams, TEMPORAL_DEFAULTS, kw)
 
 
 class TemporalRectify(C.Structure):
@@ -130,9 +124,7 @@ TEMPORAL_RECTIFY_DEFAULTS = dict(radius=1, min_count=4, gamma=1.5)
 
 def temporal_rectify(**kw):
     """a TemporalRectify with the library's defaults for whatever kw does not set"""
-    p = dict(TEMPORAL_RECTIFY_DEFAULTS)
-    p.update(kw)
-    return TemporalRectify(p["radius"], p["min_count"], p["gamma"])
+    return _params(TemporalRectify, TEMPORAL_RECTIFY_DEFAULTS, kw)
 
 
 class TemporalInputs(C.Structure):
@@ -182,7 +174,7 @@ class FrameMetrics(C.Structure):
 assert C.sizeof(FrameMetrics) == 64 and C.sizeof(LevelsParams) == 16
 
 # every symbol include/rt_amd.h declares: (restype, argtypes)
-_vp, _i, _i64, _f = C.c_void_p, C.c_int, C.c_int64, C.c_float
+_vp, _i, _i64, _f, _P = C.c_void_p, C.c_int, C.c_int64, C.c_float, C.POINTER
 SYMBOLS = {
     "rt_abi_version": (_i, []),
     "rt_device_check": (_i, [_vp]),
@@ -221,20 +213,20 @@ SYMBOLS = {
     "rt_render_ctx_destroy": (_i, [_vp]),
     "rt_render_on": (_i, [_vp, _vp, _i, _i, _i, _vp, _vp, _vp, Partition, _vp]),
     "rt_render_progressive_on": (_i, [_vp, _vp, _i, _i, _i, _vp, _vp, _vp, Partition, _vp]),
-    "rt_render_adaptive": (_i, [_vp, _i, _i, C.POINTER(Adaptive), _vp, _vp, _vp, _vp, _vp]),
-    "rt_render_adaptive_on": (_i, [_vp, _vp, _i, _i, C.POINTER(Adaptive), _vp, _vp, _vp, _vp, _vp]),
-    "rt_render_adaptive_part": (_i, [_vp, _i, _i, C.POINTER(Adaptive), _vp, _vp, _vp, _vp, Partition, _vp]),
-    "rt_render_adaptive_part_on": (_i, [_vp, _vp, _i, _i, C.POINTER(Adaptive), _vp, _vp, _vp, _vp, Partition, _vp]),
-    "rt_render_adaptive_begin": (_i, [_vp, _i, _i, C.POINTER(Adaptive), _vp, _vp, _vp, _vp, _vp, Partition, _vp]),
-    "rt_render_adaptive_begin_on": (_i, [_vp, _vp, _i, _i, C.POINTER(Adaptive), _vp, _vp, _vp, _vp, _vp, Partition, _vp]),
-    "rt_render_adaptive_refine": (_i, [_vp, _i, _i, C.POINTER(Adaptive), C.POINTER(Adaptive), _vp, _vp, _vp, _vp, _vp, Partition, _vp]),
-    "rt_render_adaptive_refine_on": (_i, [_vp, _vp, _i, _i, C.POINTER(Adaptive), C.POINTER(Adaptive), _vp, _vp, _vp, _vp, _vp, Partition, _vp]),
+    "rt_render_adaptive": (_i, [_vp, _i, _i, _P(Adaptive), _vp, _vp, _vp, _vp, _vp]),
+    "rt_render_adaptive_on": (_i, [_vp, _vp, _i, _i, _P(Adaptive), _vp, _vp, _vp, _vp, _vp]),
+    "rt_render_adaptive_part": (_i, [_vp, _i, _i, _P(Adaptive), _vp, _vp, _vp, _vp, Partition, _vp]),
+    "rt_render_adaptive_part_on": (_i, [_vp, _vp, _i, _i, _P(Adaptive), _vp, _vp, _vp, _vp, Partition, _vp]),
+    "rt_render_adaptive_begin": (_i, [_vp, _i, _i, _P(Adaptive), _vp, _vp, _vp, _vp, _vp, Partition, _vp]),
+    "rt_render_adaptive_begin_on": (_i, [_vp, _vp, _i, _i, _P(Adaptive), _vp, _vp, _vp, _vp, _vp, Partition, _vp]),
+    "rt_render_adaptive_refine": (_i, [_vp, _i, _i, _P(Adaptive), _P(Adaptive), _vp, _vp, _vp, _vp, _vp, Partition, _vp]),
+    "rt_render_adaptive_refine_on": (_i, [_vp, _vp, _i, _i, _P(Adaptive), _P(Adaptive), _vp, _vp, _vp, _vp, _vp, Partition, _vp]),
     "rt_adaptive_priority": (_f, [_f, _f, _i, _f]),
-    "rt_adaptive_budget_check": (_i, [C.POINTER(Budget)]),
-    "rt_adaptive_budget_picks": (_i, [C.POINTER(Budget), _i, _vp]),
-    "rt_adaptive_budget_select": (_i, [_vp, _vp, _i, _i, Partition, C.POINTER(Budget), _i64, _vp, _vp, _vp]),
-    "rt_render_adaptive_spend": (_i, [_vp, _i, _i, C.POINTER(Budget), _vp, _vp, _vp, _vp, _vp, Partition, _vp, _vp]),
-    "rt_render_adaptive_spend_on": (_i, [_vp, _vp, _i, _i, C.POINTER(Budget), _vp, _vp, _vp, _vp, _vp, Partition, _vp, _vp]),
+    "rt_adaptive_budget_check": (_i, [_P(Budget)]),
+    "rt_adaptive_budget_picks": (_i, [_P(Budget), _i, _vp]),
+    "rt_adaptive_budget_select": (_i, [_vp, _vp, _i, _i, Partition, _P(Budget), _i64, _vp, _vp, _vp]),
+    "rt_render_adaptive_spend": (_i, [_vp, _i, _i, _P(Budget), _vp, _vp, _vp, _vp, _vp, Partition, _vp, _vp]),
+    "rt_render_adaptive_spend_on": (_i, [_vp, _vp, _i, _i, _P(Budget), _vp, _vp, _vp, _vp, _vp, Partition, _vp, _vp]),
     "rt_render_ctx_times": (_i, [_vp, _vp, _i, _vp]),
     "rt_render_ctx_counters": (_i, [_vp, _vp]),
     "rt_world_render_counters": (_i, [_vp, _vp]),
@@ -244,8 +236,8 @@ SYMBOLS = {
     "rt_world_render_schedule_reuse": (_i, [_vp, _vp, _vp]),
     "rt_render_ctx_schedule_feedback": (_i, [_vp, _vp, _vp, _i]),
     "rt_world_render_schedule_feedback": (_i, [_vp, _vp, _vp, _i]),
-    "rt_render_ctx_schedule_counts": (_i, [_vp, _vp, C.c_int64]),
-    "rt_world_render_schedule_counts": (_i, [_vp, _vp, C.c_int64]),
+    "rt_render_ctx_schedule_counts": (_i, [_vp, _vp, _i64]),
+    "rt_world_render_schedule_counts": (_i, [_vp, _vp, _i64]),
     "rt_render_kernel_name": (_i, [_vp, _vp, _i, _vp, _i]),
     "rt_multi_unique_id": (_i, [_vp]),
     "rt_multi_init": (_i, [_vp, _i, _i, _vp]),
@@ -254,7 +246,7 @@ SYMBOLS = {
     "rt_multi_destroy": (_i, [_vp]),
     "rt_multi_reserve": (_i, [_vp, _i, _i, _i, _i]),
     "rt_multi_render": (_i, [_vp, _vp, _i, _i, _i, _vp, _vp, _i, _i, _vp]),
-    "rt_multi_render_adaptive": (_i, [_vp, _vp, _i, _i, C.POINTER(Adaptive), _vp, _vp, _i, _i, _vp, _vp]),
+    "rt_multi_render_adaptive": (_i, [_vp, _vp, _i, _i, _P(Adaptive), _vp, _vp, _i, _i, _vp, _vp]),
     "rt_multi_last_render_ms": (_i, [_vp, _vp, _vp]),
     "rt_multi_selftest": (_i, [_vp, _vp, _vp, C.c_size_t, _vp]),
     "rt_assemble": (_i, [_vp, _vp, _i, _i, _i, _i, _vp]),
@@ -264,35 +256,31 @@ SYMBOLS = {
     "rt_multi_last_split": (_i, [_vp, _vp]),
     "rt_trace_rays": (_i, [_vp, _vp, _vp, _i64, _vp, _vp]),
     "rt_render_guides": (_i, [_vp, _vp, _i, _i, _vp, _vp]),
-    "rt_denoise": (_i, [_vp, _vp, _i, _i, _vp, C.POINTER(DenoiseParams), _vp, _vp]),
-    "rt_denoise_check": (_i, [_i, _i, C.POINTER(DenoiseParams)]),
-    "rt_denoise_adaptive": (_i, [_vp, _vp, _i, _i, _vp, _vp, C.POINTER(DenoiseVarParams), _vp, _vp]),
-    "rt_denoise_adaptive_check": (_i, [_i, _i, C.POINTER(DenoiseVarParams)]),
-    "rt_temporal_check": (_i, [_i, _i, C.POINTER(TemporalParams)]),
-    "rt_temporal_accumulate": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, C.POINTER(TemporalParams), _vp]),
-    "rt_temporal_accumulate_moving": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, C.POINTER(TemporalParams), _vp]),
-    "rt_temporal_rectify_check": (_i, [C.POINTER(TemporalRectify)]),
-    "rt_temporal_accumulate_rectified": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, C.POINTER(TemporalParams), C.POINTER(TemporalRectify),
-                                              _vp]),
-    "rt_denoise_history": (_i, [_vp, _vp, _i, _i, _vp, _vp, C.POINTER(DenoiseVarParams), _vp, _vp]),
+    "rt_denoise": (_i, [_vp, _vp, _i, _i, _vp, _P(DenoiseParams), _vp, _vp]),
+    "rt_denoise_check": (_i, [_i, _i, _P(DenoiseParams)]),
+    "rt_denoise_adaptive": (_i, [_vp, _vp, _i, _i, _vp, _vp, _P(DenoiseVarParams), _vp, _vp]),
+    "rt_denoise_adaptive_check": (_i, [_i, _i, _P(DenoiseVarParams)]),
+    "rt_temporal_check": (_i, [_i, _i, _P(TemporalParams)]),
+    "rt_temporal_accumulate": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _P(TemporalParams), _vp]),
+    "rt_temporal_accumulate_moving": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _P(TemporalParams), _vp]),
+    "rt_temporal_rectify_check": (_i, [_P(TemporalRectify)]),
+    "rt_temporal_accumulate_rectified": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _P(TemporalParams), _P(TemporalRectify), _vp]),
+    "rt_denoise_history": (_i, [_vp, _vp, _i, _i, _vp, _vp, _P(DenoiseVarParams), _vp, _vp]),
     "rt_adaptive_priority_filtered": (_f, [_f, _f, _f]),
-    "rt_adaptive_budget_select_filtered": (_i, [_vp, _vp, _vp, _i, _i, C.POINTER(Budget), C.POINTER(DenoiseVarParams), _i64, _vp, _vp, _vp, _vp]),
-    "rt_render_adaptive_spend_filtered": (_i, [_vp, _i, _i, C.POINTER(Budget), C.POINTER(DenoiseVarParams), _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
-    "rt_render_adaptive_spend_filtered_on": (_i, [_vp, _vp, _i, _i, C.POINTER(Budget), C.POINTER(DenoiseVarParams), _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
-    "rt_adaptive_budget_select_temporal": (_i, [_vp, _vp, _vp, _i, _i, C.POINTER(Budget), C.POINTER(TemporalInputs), C.POINTER(TemporalParams), _i64,
-                                                _vp, _vp, _vp, _vp]),
-    "rt_render_adaptive_spend_temporal": (_i, [_vp, _i, _i, C.POINTER(Budget), C.POINTER(TemporalInputs), C.POINTER(TemporalParams), _vp, _vp, _vp, _vp,
-                                               _vp, _vp, _vp]),
-    "rt_render_adaptive_spend_temporal_on": (_i, [_vp, _vp, _i, _i, C.POINTER(Budget), C.POINTER(TemporalInputs), C.POINTER(TemporalParams), _vp, _vp, _vp,
-                                                  _vp, _vp, _vp, _vp]),
-    "rt_frame_levels": (_i, [_vp, _vp, _i, _i, _i, C.POINTER(LevelsParams), _vp]),
-    "rt_frame_levels_check": (_i, [_i, _i, _i, C.POINTER(LevelsParams)]),
+    "rt_adaptive_budget_select_filtered": (_i, [_vp, _vp, _vp, _i, _i, _P(Budget), _P(DenoiseVarParams), _i64, _vp, _vp, _vp, _vp]),
+    "rt_render_adaptive_spend_filtered": (_i, [_vp, _i, _i, _P(Budget), _P(DenoiseVarParams), _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "rt_render_adaptive_spend_filtered_on": (_i, [_vp, _vp, _i, _i, _P(Budget), _P(DenoiseVarParams), _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "rt_adaptive_budget_select_temporal": (_i, [_vp, _vp, _vp, _i, _i, _P(Budget), _P(TemporalInputs), _P(TemporalParams), _i64, _vp, _vp, _vp, _vp]),
+    "rt_render_adaptive_spend_temporal": (_i, [_vp, _i, _i, _P(Budget), _P(TemporalInputs), _P(TemporalParams), _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "rt_render_adaptive_spend_temporal_on": (_i, [_vp, _vp, _i, _i, _P(Budget), _P(TemporalInputs), _P(TemporalParams), _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "rt_frame_levels": (_i, [_vp, _vp, _i, _i, _i, _P(LevelsParams), _vp]),
+    "rt_frame_levels_check": (_i, [_i, _i, _i, _P(LevelsParams)]),
     "rt_frame_levels_bytes": (_i64, [_i, _i, _i]),
     "rt_frame_compare_work_bytes": (_i64, [_i, _i]),
     "rt_frame_compare": (_i, [_vp, _i, _vp, _i, _i, _i, _vp, _vp, _vp, _vp]),
-    "rt_frame_psnr": (C.c_double, [C.POINTER(FrameMetrics)]),
-    "rt_frame_ssim": (C.c_double, [C.POINTER(FrameMetrics)]),
-    "rt_frame_rmse": (C.c_double, [C.POINTER(FrameMetrics)]),
+    "rt_frame_psnr": (C.c_double, [_P(FrameMetrics)]),
+    "rt_frame_ssim": (C.c_double, [_P(FrameMetrics)]),
+    "rt_frame_rmse": (C.c_double, [_P(FrameMetrics)]),
     "rt_write_ppm": (_i, [C.c_char_p, _i, _i, _vp, _i]),
     "rt_format_ppm": (_i64, [_i, _i, _vp, _i, _vp, _i64]),
     "rt_write_image": (_i, [C.c_char_p, _i, _i, _vp, _i, _i]),
@@ -334,13 +322,29 @@ def check(rc, what):
         raise RtError("%s failed: %d (%s)" % (what, rc, msg.decode() if msg else "?"))
 
 
+# ---- marshalling, written once ---------------------------------------------------------------------------------------
+def _call(name, *args):
+    """the symbol `name` with args; RtError, naming the symbol, unless it returns 0"""
+    check(getattr(lib(), name)(*args), name)
+
+
 def _np(a):
     return a.ctypes.data_as(C.c_void_p)
 
 
 def _dev(t):
-    """device pointer of a torch tensor (or a raw int)"""
-    return C.c_void_p(t if isinstance(t, int) else t.data_ptr())
+    """device pointer of a torch tensor (or a raw int); None stays None (NULL)"""
+    return None if t is None else C.c_void_p(t if isinstance(t, int) else t.data_ptr())
+
+
+def _h(obj):
+    """the handle of an optional World / Octree / RenderCtx; None stays None (NULL)"""
+    return None if obj is None else obj.h
+
+
+def _ref(p):
+    """byref of an optional parameter structure; None stays None (NULL)"""
+    return None if p is None else C.byref(p)
 
 
 def _stream():
@@ -348,143 +352,32 @@ def _stream():
     return C.c_void_p(torch.cuda.current_stream().cuda_stream)
 
 
-def render_kernel_name(world, octree=None, mode=0):
-    """the kernel rt_render (mode 0) / rt_render_progressive (mode 1) launches for this world and tree (the library's own rule)"""
-    buf = C.create_string_buffer(64)
-    check(lib().rt_render_kernel_name(world.h, octree.h if octree is not None else None, mode, buf, 64), "rt_render_kernel_name")
-    return buf.value.decode()
+def _on(stream):
+    """the caller's stream (a raw hipStream_t), or torch's current one"""
+    return _stream() if stream is None else C.c_void_p(stream)
 
 
-class RenderCtx:
-    """rt_render_ctx: per-launch state for frames rendered concurrently on one GPU (one context per stream)"""
+def _frame(name, ctx, stream, *args):
+    """a frame call: rt_X(args, stream) on the world's own context, or, with a RenderCtx, rt_X_on(ctx, args, stream)"""
+    if ctx is None:
+        _call(name, *args, _on(stream))
+    else:
+        _call(name + "_on", ctx.h, *args, _on(stream))
 
-    def __init__(self):
-        h = C.c_void_p()
-        check(lib().rt_render_ctx_create(C.byref(h)), "rt_render_ctx_create")
-        self.h = h
 
-    def reserve(self, max_x, max_y, part=None):
-        check(lib().rt_render_ctx_reserve(self.h, max_x, max_y, part or WHOLE), "rt_render_ctx_reserve")
-        return self
+def _params(cls, defaults, kw, *head):
+    """cls(*head, then the fields `defaults` names, in its order): the library's defaults for whatever kw does not set"""
+    p = dict(defaults, **kw)
+    return cls(*head, *(p[k] for k in defaults))
 
-    def render(self, fb, max_x, max_y, ns, world, d_rand_state, octree=None, part=None, stream=None):
-        check(lib().rt_render_on(self.h, _dev(fb), max_x, max_y, ns, world.h, _dev(d_rand_state), octree.h if octree is not None else None,
-                                 part or WHOLE, C.c_void_p(stream) if stream is not None else _stream()), "rt_render_on")
 
-    def render_adaptive(self, fb, max_x, max_y, params, world, d_rand_state, octree=None, d_spp=None, stream=None):
-        """rt_render_adaptive_on: params is an Adaptive; d_spp (optional) an int32 tensor of max_x * max_y"""
-        check(lib().rt_render_adaptive_on(self.h, _dev(fb), max_x, max_y, C.byref(params), world.h, _dev(d_rand_state),
-                                          octree.h if octree is not None else None, _dev(d_spp) if d_spp is not None else None,
-                                          C.c_void_p(stream) if stream is not None else _stream()), "rt_render_adaptive_on")
-
-    def render_adaptive_part(self, fb, max_x, max_y, params, world, d_rand_state, octree=None, d_spp=None, part=None, stream=None):
-        """rt_render_adaptive_part_on: buffers of rt_part_pixels(part) elements (d_spp: int32), tile-major unless part is the whole frame"""
-        check(lib().rt_render_adaptive_part_on(self.h, _dev(fb), max_x, max_y, C.byref(params), world.h, _dev(d_rand_state),
-                                               octree.h if octree is not None else None, _dev(d_spp) if d_spp is not None else None,
-                                               part or WHOLE, C.c_void_p(stream) if stream is not None else _stream()), "rt_render_adaptive_part_on")
-
-    def render_adaptive_begin(self, fb, max_x, max_y, params, world, d_rand_state, d_state, octree=None, d_spp=None, part=None, stream=None):
-        """rt_render_adaptive_begin_on: rt_render_adaptive_part_on that also fills d_state (alloc_adaptive_state) for later refinement"""
-        check(lib().rt_render_adaptive_begin_on(self.h, _dev(fb), max_x, max_y, C.byref(params), world.h, _dev(d_rand_state),
-                                                octree.h if octree is not None else None, _dev(d_spp) if d_spp is not None else None, _dev(d_state),
-                                                part or WHOLE, C.c_void_p(stream) if stream is not None else _stream()), "rt_render_adaptive_begin_on")
-
-    def render_adaptive_refine(self, fb, max_x, max_y, frm, to, world, d_rand_state, d_state, octree=None, d_spp=None, part=None, stream=None):
-        """rt_render_adaptive_refine_on: continue the frame that d_state holds at target `frm` (an Adaptive) to the target `to`"""
-        check(lib().rt_render_adaptive_refine_on(self.h, _dev(fb), max_x, max_y, C.byref(frm), C.byref(to), world.h, _dev(d_rand_state),
-                                                 octree.h if octree is not None else None, _dev(d_spp) if d_spp is not None else None, _dev(d_state),
-                                                 part or WHOLE, C.c_void_p(stream) if stream is not None else _stream()), "rt_render_adaptive_refine_on")
-
-    def render_adaptive_spend(self, fb, max_x, max_y, params, world, d_rand_state, d_state, octree=None, d_spp=None, part=None, d_picked=None,
-                              stream=None):
-        """rt_render_adaptive_spend_on: spend the Budget `params` on the frame that d_state holds; d_picked (optional): uint32 per round"""
-        check(lib().rt_render_adaptive_spend_on(self.h, _dev(fb), max_x, max_y, C.byref(params), world.h, _dev(d_rand_state),
-                                                octree.h if octree is not None else None, _dev(d_spp) if d_spp is not None else None, _dev(d_state),
-                                                part or WHOLE, _dev(d_picked) if d_picked is not None else None,
-                                                C.c_void_p(stream) if stream is not None else _stream()), "rt_render_adaptive_spend_on")
-
-    def adaptive_budget_select(self, d_state, max_x, max_y, params, picks, d_list, d_count, part=None, stream=None):
-        """rt_adaptive_budget_select: the ids of the `picks` pixels a round would choose into d_list (uint32), their number into d_count"""
-        check(lib().rt_adaptive_budget_select(self.h, _dev(d_state), max_x, max_y, part or WHOLE, C.byref(params), picks, _dev(d_list), _dev(d_count),
-                                              C.c_void_p(stream) if stream is not None else _stream()), "rt_adaptive_budget_select")
-
-    def render_adaptive_spend_filtered(self, fb, max_x, max_y, params, filter, d_hits, world, d_rand_state, d_state, octree=None, d_spp=None,
-                                       d_picked=None, stream=None):
-        """rt_render_adaptive_spend_filtered_on: the spend ranked by the error left after denoise_adaptive's first level (whole frames);
-        filter is the DenoiseVarParams the frame will be filtered with, d_hits the guides of render_guides"""
-        check(lib().rt_render_adaptive_spend_filtered_on(self.h, _dev(fb), max_x, max_y, C.byref(params), C.byref(filter), _dev(d_hits), world.h,
-                                                         _dev(d_rand_state), octree.h if octree is not None else None,
-                                                         _dev(d_spp) if d_spp is not None else None, _dev(d_state),
-                                                         _dev(d_picked) if d_picked is not None else None,
-                                                         C.c_void_p(stream) if stream is not None else _stream()), "rt_render_adaptive_spend_filtered_on")
-
-    def adaptive_budget_select_filtered(self, d_state, d_hits, max_x, max_y, params, filter, picks, d_list, d_count, d_keys=None, stream=None):
-        """rt_adaptive_budget_select_filtered: adaptive_budget_select with the filter-aware key; d_keys (optional, float32 per pixel)
-        receives every pixel's key before the eligibility mask"""
-        check(lib().rt_adaptive_budget_select_filtered(self.h, _dev(d_state), _dev(d_hits), max_x, max_y, C.byref(params), C.byref(filter), picks,
-                                                       _dev(d_list), _dev(d_count), _dev(d_keys) if d_keys is not None else None,
-                                                       C.c_void_p(stream) if stream is not None else _stream()), "rt_adaptive_budget_select_filtered")
-
-    def render_adaptive_spend_temporal(self, fb, max_x, max_y, params, inputs, temporal, world, d_rand_state, d_state, octree=None, d_spp=None,
-                                       d_picked=None, stream=None):
-        """rt_render_adaptive_spend_temporal_on: the spend ranked by the error left after temporal_accumulate's merge (whole frames);
-        inputs is a TemporalInputs (temporal_inputs()), temporal the TemporalParams the history is kept with"""
-        check(lib().rt_render_adaptive_spend_temporal_on(self.h, _dev(fb), max_x, max_y, C.byref(params), C.byref(inputs), C.byref(temporal), world.h,
-                                                         _dev(d_rand_state), octree.h if octree is not None else None,
-                                                         _dev(d_spp) if d_spp is not None else None, _dev(d_state),
-                                                         _dev(d_picked) if d_picked is not None else None,
-                                                         C.c_void_p(stream) if stream is not None else _stream()), "rt_render_adaptive_spend_temporal_on")
-
-    def adaptive_budget_select_temporal(self, d_state, world, max_x, max_y, params, inputs, temporal, picks, d_list, d_count, d_keys=None,
-                                        stream=None):
-        """rt_adaptive_budget_select_temporal: adaptive_budget_select with the history-aware key; d_keys (optional, float32 per pixel)
-        receives every pixel's key before the eligibility mask"""
-        check(lib().rt_adaptive_budget_select_temporal(self.h, _dev(d_state), world.h, max_x, max_y, C.byref(params), C.byref(inputs),
-                                                       C.byref(temporal), picks, _dev(d_list), _dev(d_count),
-                                                       _dev(d_keys) if d_keys is not None else None,
-                                                       C.c_void_p(stream) if stream is not None else _stream()), "rt_adaptive_budget_select_temporal")
-
-    def times(self):
-        out = np.zeros(64, np.float32)
-        n = C.c_int(0)
-        check(lib().rt_render_ctx_times(self.h, _np(out), 64, C.byref(n)), "rt_render_ctx_times")
-        return out[: n.value].tolist()
-
-    def counters(self):
-        """scheduling counters of the latest launch: slots handed out, thin waves left, long chains pre-classified, handles taken"""
-        out = np.zeros(4, np.uint32)
-        check(lib().rt_render_ctx_counters(self.h, _np(out)), "rt_render_ctx_counters")
-        return dict(zip(("slots", "thin_waves", "long_chains", "long_handles"), (int(v) for v in out)))
-
-    def schedule(self):
-        """the words that decided the latest launch's hand-out (rt_render_ctx_schedule): in-flight and pilot thresholds, tail mark
-        (first tail slot + 1), head count, head threshold, from-end flag, raw long / solo chain counts (before the use_long gate)"""
-        out = np.zeros(len(SCHEDULE_FIELDS), np.uint32)
-        check(lib().rt_render_ctx_schedule(self.h, _np(out), len(out)), "rt_render_ctx_schedule")
-        return dict(zip(SCHEDULE_FIELDS, (int(v) for v in out)))
-
-    def schedule_reuse(self):
-        """(reused, computed): launches that reused the context's kept schedule / scheduling passes issued, since it was created"""
-        a, b = C.c_uint64(0), C.c_uint64(0)
-        check(lib().rt_render_ctx_schedule_reuse(self.h, C.byref(a), C.byref(b)), "rt_render_ctx_schedule_reuse")
-        return a.value, b.value
-
-    def schedule_feedback(self):
-        """the measured pass of the context's record (rt_render_ctx_schedule_feedback): passes rebuilt from recorded counts since the
-        context was created ("refined"), whether the record holds counts / a rebuilt pass, the frame's largest count and the solo cap"""
-        a, out = C.c_uint64(0), np.zeros(len(FEEDBACK_FIELDS), np.uint32)
-        check(lib().rt_render_ctx_schedule_feedback(self.h, C.byref(a), _np(out), len(out)), "rt_render_ctx_schedule_feedback")
-        return dict(zip(("refined",) + FEEDBACK_FIELDS, [a.value] + [int(v) for v in out]))
-
-    def schedule_counts(self, n):
-        """the iteration counts the record's launch left, one uint16 per buffer element of that launch (n of them: rt_part_pixels)"""
-        out = np.zeros(int(n), np.uint16)
-        check(lib().rt_render_ctx_schedule_counts(self.h, _np(out), int(n)), "rt_render_ctx_schedule_counts")
-        return out
+class _Handle:
+    """owner of h, the opaque handle a subclass's create call filled: freed once, by the symbol the subclass names in _free"""
+    _free = None
 
     def close(self):
         if getattr(self, "h", None):
-            lib().rt_render_ctx_destroy(self.h)
+            getattr(lib(), self._free)(self.h)
             self.h = None
 
     def __del__(self):
@@ -494,15 +387,185 @@ class RenderCtx:
             pass
 
 
-SPLIT_RUNS, SPLIT_BALANCED, SPLIT_BALANCED_CACHED = 0, 1, 2      # rt_multi_set_split
+class _Scheduled(_Handle):
+    """a handle that reaches a render context's scheduling record — the context itself (_stem rt_render_ctx) or the world that owns one
+    (_stem rt_world_render): the six accessors, once"""
+    _stem = None
+
+    def _times(self):
+        out, n = np.zeros(64, np.float32), C.c_int(0)
+        _call(self._stem + "_times", self.h, _np(out), 64, C.byref(n))
+        return out[: n.value].tolist()
+
+    def _counters(self):
+        out = np.zeros(4, np.uint32)
+        _call(self._stem + "_counters", self.h, _np(out))
+        return dict(zip(("slots", "thin_waves", "long_chains", "long_handles"), (int(v) for v in out)))
+
+    def _schedule(self):
+        out = np.zeros(len(SCHEDULE_FIELDS), np.uint32)
+        _call(self._stem + "_schedule", self.h, _np(out), len(out))
+        return dict(zip(SCHEDULE_FIELDS, (int(v) for v in out)))
+
+    def schedule_reuse(self):
+        """(reused, computed): launches that reused the context's kept schedule / scheduling passes issued, since it was created"""
+        a, b = C.c_uint64(0), C.c_uint64(0)
+        _call(self._stem + "_schedule_reuse", self.h, C.byref(a), C.byref(b))
+        return a.value, b.value
+
+    def schedule_feedback(self):
+        """the measured pass of the context's record (rt_*_schedule_feedback): passes rebuilt from recorded counts since the context was
+        created ("refined"), whether the record holds counts / a rebuilt pass, the frame's largest count and the solo cap"""
+        a, out = C.c_uint64(0), np.zeros(len(FEEDBACK_FIELDS), np.uint32)
+        _call(self._stem + "_schedule_feedback", self.h, C.byref(a), _np(out), len(out))
+        return dict(zip(("refined",) + FEEDBACK_FIELDS, [a.value] + [int(v) for v in out]))
+
+    def schedule_counts(self, n):
+        """the iteration counts the record's launch left, one uint16 per buffer element of that launch (n of them: rt_part_pixels)"""
+        out = np.zeros(int(n), np.uint16)
+        _call(self._stem + "_schedule_counts", self.h, _np(out), int(n))
+        return out
+
+
+# the frame calls, each marshalled once; the free function (current stream, the world's context) and the RenderCtx method forward here
+# (`part or WHOLE` serves the methods' part=None; a free function given part=None, once a ctypes ArgumentError, now renders the whole frame)
+def _render(fb, max_x, max_y, ns, world, d_rand_state, octree, part, ctx=None, stream=None):
+    _frame("rt_render", ctx, stream, _dev(fb), max_x, max_y, ns, world.h, _dev(d_rand_state), _h(octree), part or WHOLE)
+
+
+def _render_adaptive(fb, max_x, max_y, params, world, d_rand_state, octree, d_spp, ctx=None, stream=None):
+    _frame("rt_render_adaptive", ctx, stream, _dev(fb), max_x, max_y, C.byref(params), world.h, _dev(d_rand_state), _h(octree), _dev(d_spp))
+
+
+def _render_adaptive_part(fb, max_x, max_y, params, world, d_rand_state, octree, d_spp, part, ctx=None, stream=None):
+    _frame("rt_render_adaptive_part", ctx, stream, _dev(fb), max_x, max_y, C.byref(params), world.h, _dev(d_rand_state), _h(octree), _dev(d_spp),
+           part or WHOLE)
+
+
+def _render_adaptive_begin(fb, max_x, max_y, params, world, d_rand_state, d_state, octree, d_spp, part, ctx=None, stream=None):
+    _frame("rt_render_adaptive_begin", ctx, stream, _dev(fb), max_x, max_y, C.byref(params), world.h, _dev(d_rand_state), _h(octree), _dev(d_spp),
+           _dev(d_state), part or WHOLE)
+
+
+def _render_adaptive_refine(fb, max_x, max_y, frm, to, world, d_rand_state, d_state, octree, d_spp, part, ctx=None, stream=None):
+    _frame("rt_render_adaptive_refine", ctx, stream, _dev(fb), max_x, max_y, C.byref(frm), C.byref(to), world.h, _dev(d_rand_state), _h(octree),
+           _dev(d_spp), _dev(d_state), part or WHOLE)
+
+
+def _render_adaptive_spend(fb, max_x, max_y, params, world, d_rand_state, d_state, octree, d_spp, part, d_picked, ctx=None, stream=None):
+    _frame("rt_render_adaptive_spend", ctx, stream, _dev(fb), max_x, max_y, C.byref(params), world.h, _dev(d_rand_state), _h(octree), _dev(d_spp),
+           _dev(d_state), part or WHOLE, _dev(d_picked))
+
+
+def _render_adaptive_spend_filtered(fb, max_x, max_y, params, filter, d_hits, world, d_rand_state, d_state, octree, d_spp, d_picked, ctx=None,
+                                    stream=None):
+    _frame("rt_render_adaptive_spend_filtered", ctx, stream, _dev(fb), max_x, max_y, C.byref(params), C.byref(filter), _dev(d_hits), world.h,
+           _dev(d_rand_state), _h(octree), _dev(d_spp), _dev(d_state), _dev(d_picked))
+
+
+def _render_adaptive_spend_temporal(fb, max_x, max_y, params, inputs, temporal, world, d_rand_state, d_state, octree, d_spp, d_picked, ctx=None,
+                                    stream=None):
+    _frame("rt_render_adaptive_spend_temporal", ctx, stream, _dev(fb), max_x, max_y, C.byref(params), C.byref(inputs), C.byref(temporal), world.h,
+           _dev(d_rand_state), _h(octree), _dev(d_spp), _dev(d_state), _dev(d_picked))
+
+
+def render_kernel_name(world, octree=None, mode=0):
+    """the kernel rt_render (mode 0) / rt_render_progressive (mode 1) launches for this world and tree (the library's own rule)"""
+    buf = C.create_string_buffer(64)
+    _call("rt_render_kernel_name", world.h, _h(octree), mode, buf, 64)
+    return buf.value.decode()
+
+
+class RenderCtx(_Scheduled):
+    """rt_render_ctx: per-launch state for frames rendered concurrently on one GPU (one context per stream)"""
+    _free, _stem = "rt_render_ctx_destroy", "rt_render_ctx"
+
+    def __init__(self):
+        h = C.c_void_p()
+        _call("rt_render_ctx_create", C.byref(h))
+        self.h = h
+
+    def reserve(self, max_x, max_y, part=None):
+        _call("rt_render_ctx_reserve", self.h, max_x, max_y, part or WHOLE)
+        return self
+
+    def render(self, fb, max_x, max_y, ns, world, d_rand_state, octree=None, part=None, stream=None):
+        _render(fb, max_x, max_y, ns, world, d_rand_state, octree, part, self, stream)
+
+    def render_adaptive(self, fb, max_x, max_y, params, world, d_rand_state, octree=None, d_spp=None, stream=None):
+        """rt_render_adaptive_on: params is an Adaptive; d_spp (optional) an int32 tensor of max_x * max_y"""
+        _render_adaptive(fb, max_x, max_y, params, world, d_rand_state, octree, d_spp, self, stream)
+
+    def render_adaptive_part(self, fb, max_x, max_y, params, world, d_rand_state, octree=None, d_spp=None, part=None, stream=None):
+        """rt_render_adaptive_part_on: buffers of rt_part_pixels(part) elements (d_spp: int32), tile-major unless part is the whole frame"""
+        _render_adaptive_part(fb, max_x, max_y, params, world, d_rand_state, octree, d_spp, part, self, stream)
+
+    def render_adaptive_begin(self, fb, max_x, max_y, params, world, d_rand_state, d_state, octree=None, d_spp=None, part=None, stream=None):
+        """rt_render_adaptive_begin_on: rt_render_adaptive_part_on that also fills d_state (alloc_adaptive_state) for later refinement"""
+        _render_adaptive_begin(fb, max_x, max_y, params, world, d_rand_state, d_state, octree, d_spp, part, self, stream)
+
+    def render_adaptive_refine(self, fb, max_x, max_y, frm, to, world, d_rand_state, d_state, octree=None, d_spp=None, part=None, stream=None):
+        """rt_render_adaptive_refine_on: continue the frame that d_state holds at target `frm` (an Adaptive) to the target `to`"""
+        _render_adaptive_refine(fb, max_x, max_y, frm, to, world, d_rand_state, d_state, octree, d_spp, part, self, stream)
+
+    def render_adaptive_spend(self, fb, max_x, max_y, params, world, d_rand_state, d_state, octree=None, d_spp=None, part=None, d_picked=None,
+                              stream=None):
+        """rt_render_adaptive_spend_on: spend the Budget `params` on the frame that d_state holds; d_picked (optional): uint32 per round"""
+        _render_adaptive_spend(fb, max_x, max_y, params, world, d_rand_state, d_state, octree, d_spp, part, d_picked, self, stream)
+
+    def adaptive_budget_select(self, d_state, max_x, max_y, params, picks, d_list, d_count, part=None, stream=None):
+        """rt_adaptive_budget_select: the ids of the `picks` pixels a round would choose into d_list (uint32), their number into d_count"""
+        _call("rt_adaptive_budget_select", self.h, _dev(d_state), max_x, max_y, part or WHOLE, C.byref(params), picks, _dev(d_list), _dev(d_count),
+              _on(stream))
+
+    def render_adaptive_spend_filtered(self, fb, max_x, max_y, params, filter, d_hits, world, d_rand_state, d_state, octree=None, d_spp=None,
+                                       d_picked=None, stream=None):
+        """rt_render_adaptive_spend_filtered_on: the spend ranked by the error left after denoise_adaptive's first level (whole frames);
+        filter is the DenoiseVarParams the frame will be filtered with, d_hits the guides of render_guides"""
+        _render_adaptive_spend_filtered(fb, max_x, max_y, params, filter, d_hits, world, d_rand_state, d_state, octree, d_spp, d_picked, self, stream)
+
+    def adaptive_budget_select_filtered(self, d_state, d_hits, max_x, max_y, params, filter, picks, d_list, d_count, d_keys=None, stream=None):
+        """rt_adaptive_budget_select_filtered: adaptive_budget_select with the filter-aware key; d_keys (optional, float32 per pixel)
+        receives every pixel's key before the eligibility mask"""
+        _call("rt_adaptive_budget_select_filtered", self.h, _dev(d_state), _dev(d_hits), max_x, max_y, C.byref(params), C.byref(filter), picks,
+              _dev(d_list), _dev(d_count), _dev(d_keys), _on(stream))
+
+    def render_adaptive_spend_temporal(self, fb, max_x, max_y, params, inputs, temporal, world, d_rand_state, d_state, octree=None, d_spp=None,
+                                       d_picked=None, stream=None):
+        """rt_render_adaptive_spend_temporal_on: the spend ranked by the error left after temporal_accumulate's merge (whole frames);
+        inputs is a TemporalInputs (temporal_inputs()), temporal the TemporalParams the history is kept with"""
+        _render_adaptive_spend_temporal(fb, max_x, max_y, params, inputs, temporal, world, d_rand_state, d_state, octree, d_spp, d_picked, self, stream)
+
+    def adaptive_budget_select_temporal(self, d_state, world, max_x, max_y, params, inputs, temporal, picks, d_list, d_count, d_keys=None,
+                                        stream=None):
+        """rt_adaptive_budget_select_temporal: adaptive_budget_select with the history-aware key; d_keys (optional, float32 per pixel)
+        receives every pixel's key before the eligibility mask"""
+        _call("rt_adaptive_budget_select_temporal", self.h, _dev(d_state), world.h, max_x, max_y, C.byref(params), C.byref(inputs), C.byref(temporal),
+              picks, _dev(d_list), _dev(d_count), _dev(d_keys), _on(stream))
+
+    def times(self):
+        """device times (ms) of the render kernel of the launches since the last query (HIP events on the launch stream)"""
+        return self._times()
+
+    def counters(self):
+        """scheduling counters of the latest launch: slots handed out, thin waves left, long chains pre-classified, handles taken"""
+        return self._counters()
+
+    def schedule(self):
+        """the words that decided the latest launch's hand-out (rt_render_ctx_schedule): in-flight and pilot thresholds, tail mark
+        (first tail slot + 1), head count, head threshold, from-end flag, raw long / solo chain counts (before the use_long gate)"""
+        return self._schedule()
+
+
+SPLIT_RUNS, SPLIT_BALANCED, SPLIT_BALANCED_CACHED = 0, 1, 2      # rt_amd.h RT_SPLIT_*: rt_multi_set_split
 GATHER_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_int, C.c_void_p)
-MULTI_ID_BYTES = 128
+MULTI_ID_BYTES = 128           # rt_amd.h RT_MULTI_ID_BYTES
 
 
 def multi_unique_id():
     """rank 0: the RCCL unique id (bytes) to hand to the other ranks"""
     buf = C.create_string_buffer(MULTI_ID_BYTES)
-    check(lib().rt_multi_unique_id(buf), "rt_multi_unique_id")
+    _call("rt_multi_unique_id", buf)
     return buf.raw
 
 
@@ -511,65 +574,53 @@ def multi_probe():
     return int(lib().rt_multi_probe())
 
 
-class Multi:
+class Multi(_Handle):
     """rt_multi: tile split over the ranks of a node + the single framebuffer exchange + rt_assemble on the root.
     unique_id (bytes) selects RCCL; gather (a Python callable with the rt_gather_fn arguments) a custom exchange."""
+    _free = "rt_multi_destroy"
 
     def __init__(self, rank, nranks, unique_id=None, gather=None):
         h = C.c_void_p()
         if gather is not None:
             self._cb = GATHER_FN(gather)                          # keep the thunk alive
-            check(lib().rt_multi_init_custom(C.byref(h), rank, nranks, C.cast(self._cb, C.c_void_p), None), "rt_multi_init_custom")
+            _call("rt_multi_init_custom", C.byref(h), rank, nranks, C.cast(self._cb, C.c_void_p), None)
         else:
             assert unique_id is not None and len(unique_id) == MULTI_ID_BYTES
             self._id = C.create_string_buffer(unique_id, MULTI_ID_BYTES)
-            check(lib().rt_multi_init(C.byref(h), rank, nranks, self._id), "rt_multi_init")
+            _call("rt_multi_init", C.byref(h), rank, nranks, self._id)
         self.h, self.rank, self.nranks = h, rank, nranks
         self.split_mode = SPLIT_RUNS                             # the library's default (rt_multi_set_split)
 
     def reserve(self, max_x, max_y, precision=FP32, root=0):
-        check(lib().rt_multi_reserve(self.h, max_x, max_y, precision, root), "rt_multi_reserve")
+        _call("rt_multi_reserve", self.h, max_x, max_y, precision, root)
         return self
 
     def render(self, fb_full, max_x, max_y, ns, world, octree=None, root=0, precision=None):
-        check(lib().rt_multi_render(self.h, _dev(fb_full) if fb_full is not None else None, max_x, max_y, ns, world.h,
-                                    octree.h if octree is not None else None, world.precision if precision is None else precision,
-                                    root, _stream()), "rt_multi_render")
+        _call("rt_multi_render", self.h, _dev(fb_full), max_x, max_y, ns, world.h, _h(octree), world.precision if precision is None else precision,
+              root, _stream())
 
     def render_adaptive(self, fb_full, max_x, max_y, params, world, octree=None, root=0, d_spp_full=None, precision=None):
         """rt_multi_render_adaptive (RT_SPLIT_RUNS only): the root gets the frame and, d_spp_full given (int32, max_x * max_y), the count map"""
-        check(lib().rt_multi_render_adaptive(self.h, _dev(fb_full) if fb_full is not None else None, max_x, max_y, C.byref(params), world.h,
-                                             octree.h if octree is not None else None, world.precision if precision is None else precision,
-                                             root, _dev(d_spp_full) if d_spp_full is not None else None, _stream()), "rt_multi_render_adaptive")
+        _call("rt_multi_render_adaptive", self.h, _dev(fb_full), max_x, max_y, C.byref(params), world.h, _h(octree),
+              world.precision if precision is None else precision, root, _dev(d_spp_full), _stream())
 
     def set_split(self, mode):
-        check(lib().rt_multi_set_split(self.h, mode), "rt_multi_set_split")
+        _call("rt_multi_set_split", self.h, mode)
         self.split_mode = mode
         return self
 
     def last_split(self):
         st = (C.c_int64 * (self.nranks + 1))()
-        check(lib().rt_multi_last_split(self.h, st), "rt_multi_last_split")
+        _call("rt_multi_last_split", self.h, st)
         return list(st)
 
     def last_render_ms(self):
         a, b = C.c_float(0), C.c_float(0)
-        check(lib().rt_multi_last_render_ms(self.h, C.byref(a), C.byref(b)), "rt_multi_last_render_ms")
+        _call("rt_multi_last_render_ms", self.h, C.byref(a), C.byref(b))
         return a.value, b.value
 
     def selftest(self, d_src, d_dst, nbytes):
-        check(lib().rt_multi_selftest(self.h, _dev(d_src), _dev(d_dst), nbytes, _stream()), "rt_multi_selftest")
-
-    def close(self):
-        if getattr(self, "h", None):
-            lib().rt_multi_destroy(self.h)
-            self.h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+        _call("rt_multi_selftest", self.h, _dev(d_src), _dev(d_dst), nbytes, _stream())
 
 
 def device_check():
@@ -580,16 +631,11 @@ def device_check():
 
 def split_balanced(world, octree, max_x, max_y, nparts, counts=False):
     """rt_split_balanced: starts[nparts + 1] of the bands of equal predicted cost (and, counts=True, the pilot's per-tile bounces, tests and columns)"""
-    import numpy as np
     tiles = ((max_x + 7) // 8) * ((max_y + 7) // 8)
     st = (C.c_int64 * (nparts + 1))()
-    b = np.zeros(tiles, np.int32) if counts else None
-    t = np.zeros(tiles, np.int32) if counts else None
-    c = np.zeros(tiles, np.int32) if counts else None
-    check(lib().rt_split_balanced(None, world.h, octree.h if octree is not None else None, max_x, max_y, nparts, st,
-                                  b.ctypes.data_as(C.c_void_p) if counts else None, t.ctypes.data_as(C.c_void_p) if counts else None,
-                                  c.ctypes.data_as(C.c_void_p) if counts else None, _stream()), "rt_split_balanced")
-    return (list(st), b, t, c) if counts else list(st)
+    btc = [np.zeros(tiles, np.int32) for _ in range(3)] if counts else [None] * 3
+    _call("rt_split_balanced", None, world.h, _h(octree), max_x, max_y, nparts, st, *(_np(a) if counts else None for a in btc), _stream())
+    return (list(st), *btc) if counts else list(st)
 
 
 def split_parts(starts):
@@ -601,61 +647,66 @@ def split_parts(starts):
 def assemble_split(fb_full, fb_parts, max_x, max_y, starts, part_stride_px, precision=FP32):
     n = len(starts) - 1
     st = (C.c_int64 * (n + 1))(*starts)
-    check(lib().rt_assemble_split(_dev(fb_full), _dev(fb_parts), max_x, max_y, n, st, part_stride_px, precision, _stream()), "rt_assemble_split")
+    _call("rt_assemble_split", _dev(fb_full), _dev(fb_parts), max_x, max_y, n, st, part_stride_px, precision, _stream())
 
 
-def part_pixels(max_x, max_y, part=WHOLE):
-    n = lib().rt_part_pixels(max_x, max_y, part)
+def _size(name, *args):
+    """a host-only size query: the count, RtError for the negative that marks an invalid argument"""
+    n = getattr(lib(), name)(*args)
     if n < 0:
-        raise RtError("rt_part_pixels: invalid argument")
+        raise RtError("%s: invalid argument" % name)
     return n
 
 
-class World:
+def part_pixels(max_x, max_y, part=WHOLE):
+    return _size("rt_part_pixels", max_x, max_y, part)
+
+
+class World(_Scheduled):
     """rand_init + create_world of main.cu:388-401 (host side), and the device scene they feed."""
+    _free, _stem = "rt_free_world", "rt_world_render"
 
     def __init__(self, num_spheres, nx, ny, sphere_radius=0.1, precision=FP32, spheres=None, camera=None):
-        L = lib()
         self.num_spheres, self.nx, self.ny, self.precision = num_spheres, nx, ny, precision
         self.rand_state = np.zeros(1, rand_state_dtype)
         if spheres is None:
             self.spheres = np.zeros(num_spheres, sphere_dtype)
             self.camera = np.zeros(1, camera_dtype)
             created = C.c_int(0)
-            check(L.rt_rand_init(_np(self.rand_state)), "rt_rand_init")
-            check(L.rt_create_world(_np(self.spheres), num_spheres, sphere_radius, _np(self.camera), nx, ny, _np(self.rand_state),
-                                    precision, C.byref(created)), "rt_create_world")
+            _call("rt_rand_init", _np(self.rand_state))
+            _call("rt_create_world", _np(self.spheres), num_spheres, sphere_radius, _np(self.camera), nx, ny, _np(self.rand_state), precision,
+                  C.byref(created))
             self.created = created.value
         else:
             self.spheres = np.ascontiguousarray(spheres, sphere_dtype)
             self.camera = np.ascontiguousarray(camera, camera_dtype).reshape(1)
             self.created = int((self.spheres["material"] != MAT_NONE).sum())
         h = C.c_void_p()
-        check(L.rt_world_create(_np(self.spheres), num_spheres, _np(self.camera), precision, C.byref(h)), "rt_world_create")
+        _call("rt_world_create", _np(self.spheres), num_spheres, _np(self.camera), precision, C.byref(h))
         self.h = h
 
     def upload(self):
-        check(lib().rt_world_upload(self.h), "rt_world_upload")
+        _call("rt_world_upload", self.h)
         return self
 
     def set_camera(self, cam):
         """rt_world_set_camera: the camera (a camera_dtype record) of every launch from now on; host only, launches already enqueued keep
         theirs"""
         cam = np.ascontiguousarray(cam, camera_dtype).reshape(1).copy()
-        check(lib().rt_world_set_camera(self.h, _np(cam)), "rt_world_set_camera")
+        _call("rt_world_set_camera", self.h, _np(cam))
         self.camera = cam
         return self
 
     def get_camera(self):
         """rt_world_camera: the camera the next launch will use, as a camera_dtype array of one record"""
         cam = np.zeros(1, camera_dtype)
-        check(lib().rt_world_camera(self.h, _np(cam)), "rt_world_camera")
+        _call("rt_world_camera", self.h, _np(cam))
         return cam
 
     def set_geometry(self, d_geom):
         """rt_world_set_geometry on the current stream: d_geom is a float32 device tensor of num_spheres x 4 (cx, cy, cz, radius) in
         world-list order.  Octrees built before the call describe the old geometry: build them again (Octree(world, spl, gpu=True))"""
-        check(lib().rt_world_set_geometry(self.h, _dev(d_geom), _stream()), "rt_world_set_geometry")
+        _call("rt_world_set_geometry", self.h, _dev(d_geom), _stream())
         self._spheres_stale = True
         return self
 
@@ -664,7 +715,7 @@ class World:
         if d_out is None:
             import torch
             d_out = torch.empty((self.num_spheres, 4), dtype=torch.float32, device="cuda")
-        check(lib().rt_world_get_geometry(self.h, _dev(d_out), _stream()), "rt_world_get_geometry")
+        _call("rt_world_get_geometry", self.h, _dev(d_out), _stream())
         return d_out
 
     def host_spheres(self):
@@ -678,111 +729,74 @@ class World:
 
     def set_list_traversal(self, mode):
         """TRAVERSAL_REFERENCE (every sphere in list order) or TRAVERSAL_FAST (default: the candidate grid) for renders without an octree"""
-        check(lib().rt_world_set_list_traversal(self.h, mode), "rt_world_set_list_traversal")
+        _call("rt_world_set_list_traversal", self.h, mode)
         return self
 
     def set_arith(self, mode):
         """ARITH_IEEE (default, the parity contract) or ARITH_CONTRACT (FMA contraction allowed: a tolerance mode)"""
-        check(lib().rt_world_set_arith(self.h, mode), "rt_world_set_arith")
+        _call("rt_world_set_arith", self.h, mode)
         return self
 
     def list_accel_info(self):
         e, g, h, n, l = C.c_int(0), C.c_int(0), C.c_float(0), C.c_int(0), C.c_int(0)
-        check(lib().rt_world_list_accel_info(self.h, C.byref(e), C.byref(g), C.byref(h), C.byref(n), C.byref(l)), "rt_world_list_accel_info")
+        _call("rt_world_list_accel_info", self.h, C.byref(e), C.byref(g), C.byref(h), C.byref(n), C.byref(l))
         return {"enabled": bool(e.value), "grid_dim": g.value, "cell_size": h.value, "grid_entries": n.value, "large_spheres": l.value}
 
     def render_times(self):
         """device times (ms) of the render kernel of the calls since the last query (HIP events on the launch stream)"""
-        out = np.zeros(64, np.float32)
-        n = C.c_int(0)
-        check(lib().rt_world_render_times(self.h, _np(out), 64, C.byref(n)), "rt_world_render_times")
-        return out[: n.value].tolist()
+        return self._times()
 
     def render_counters(self):
         """scheduling counters of the latest render() on this world (see RenderCtx.counters)"""
-        out = np.zeros(4, np.uint32)
-        check(lib().rt_world_render_counters(self.h, _np(out)), "rt_world_render_counters")
-        return dict(zip(("slots", "thin_waves", "long_chains", "long_handles"), (int(v) for v in out)))
+        return self._counters()
 
     def render_schedule(self):
         """the words that decided the hand-out of the latest render() on this world (see RenderCtx.schedule)"""
-        out = np.zeros(len(SCHEDULE_FIELDS), np.uint32)
-        check(lib().rt_world_render_schedule(self.h, _np(out), len(out)), "rt_world_render_schedule")
-        return dict(zip(SCHEDULE_FIELDS, (int(v) for v in out)))
-
-    def schedule_reuse(self):
-        """(reused, computed) of the context this world's render() calls use (see RenderCtx.schedule_reuse)"""
-        a, b = C.c_uint64(0), C.c_uint64(0)
-        check(lib().rt_world_render_schedule_reuse(self.h, C.byref(a), C.byref(b)), "rt_world_render_schedule_reuse")
-        return a.value, b.value
-
-    def schedule_feedback(self):
-        """the measured pass of the record of this world's own context (rt_world_render_schedule_feedback): passes rebuilt from recorded counts since the
-        world was created ("refined"), whether the record holds counts / a rebuilt pass, the frame's largest count and the solo cap"""
-        a, out = C.c_uint64(0), np.zeros(len(FEEDBACK_FIELDS), np.uint32)
-        check(lib().rt_world_render_schedule_feedback(self.h, C.byref(a), _np(out), len(out)), "rt_world_render_schedule_feedback")
-        return dict(zip(("refined",) + FEEDBACK_FIELDS, [a.value] + [int(v) for v in out]))
-
-    def schedule_counts(self, n):
-        """the iteration counts the record's launch left, one uint16 per buffer element of that launch (n of them: rt_part_pixels)"""
-        out = np.zeros(int(n), np.uint16)
-        check(lib().rt_world_render_schedule_counts(self.h, _np(out), int(n)), "rt_world_render_schedule_counts")
-        return out
-
-    def close(self):
-        if getattr(self, "h", None):
-            lib().rt_free_world(self.h)
-            self.h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+        return self._schedule()
 
 
-class Octree:
+class Octree(_Handle):
     """buildOctree (acceleration_structure.h:195) + upload (main.cu:413-417)."""
+    _free = "rt_free_octree"
 
     def __init__(self, world, spheres_per_leaf=30, gpu=False):
         """gpu=True: rt_build_octree_gpu (built on the device from the world's device copy, ready to render)"""
-        L = lib()
         self.world, self.spl = world, spheres_per_leaf
         h = C.c_void_p()
         if gpu:
-            check(L.rt_build_octree_gpu(world.h, spheres_per_leaf, C.byref(h), _stream()), "rt_build_octree_gpu")
+            _call("rt_build_octree_gpu", world.h, spheres_per_leaf, C.byref(h), _stream())
         else:
-            check(L.rt_build_octree(_np(world.host_spheres()), world.num_spheres, spheres_per_leaf, world.precision, C.byref(h)), "rt_build_octree")
+            _call("rt_build_octree", _np(world.host_spheres()), world.num_spheres, spheres_per_leaf, world.precision, C.byref(h))
         self.h = h
 
     def upload(self):
-        check(lib().rt_octree_upload(self.h), "rt_octree_upload")
+        _call("rt_octree_upload", self.h)
         return self
 
     def set_traversal(self, mode):
         """TRAVERSAL_REFERENCE (exact bucket scan) or TRAVERSAL_FAST (default, culling grid + fallback)"""
-        check(lib().rt_octree_set_traversal(self.h, mode), "rt_octree_set_traversal")
+        _call("rt_octree_set_traversal", self.h, mode)
         return self
 
     def device_array(self, which):
         """bytes of one device-resident array of the (uploaded) tree, see rt_octree_debug_array"""
         n = C.c_size_t(0)
-        check(lib().rt_octree_debug_array(self.h, which, None, 0, C.byref(n)), "rt_octree_debug_array")
+        _call("rt_octree_debug_array", self.h, which, None, 0, C.byref(n))
         buf = np.zeros(max(1, n.value), np.uint8)
-        check(lib().rt_octree_debug_array(self.h, which, _np(buf), n.value, C.byref(n)), "rt_octree_debug_array")
+        _call("rt_octree_debug_array", self.h, which, _np(buf), n.value, C.byref(n))
         return buf[: n.value]
 
     def accel_info(self):
         g, n, l = C.c_int(0), C.c_int(0), C.c_int(0)
         h = C.c_float(0)
-        check(lib().rt_octree_accel_info(self.h, C.byref(g), C.byref(h), C.byref(n), C.byref(l)), "rt_octree_accel_info")
+        _call("rt_octree_accel_info", self.h, C.byref(g), C.byref(h), C.byref(n), C.byref(l))
         return dict(grid_dim=g.value, cell_size=h.value, grid_entries=n.value, large_spheres=l.value)
 
     def info(self):
         v = [C.c_int(0) for _ in range(5)]
-        check(lib().rt_octree_info(self.h, *[C.byref(x) for x in v]), "rt_octree_info")
+        _call("rt_octree_info", self.h, *[C.byref(x) for x in v])
         fn, fe = C.c_int(0), C.c_int(0)
-        check(lib().rt_octree_flat_info(self.h, C.byref(fn), C.byref(fe)), "rt_octree_flat_info")
+        _call("rt_octree_flat_info", self.h, C.byref(fn), C.byref(fe))
         keys = ["node_count", "leaf_count", "spl", "dropped_full", "dropped_outside"]
         d = dict(zip(keys, [x.value for x in v]))
         d.update(flat_nodes=fn.value, flat_entries=fe.value)
@@ -790,32 +804,21 @@ class Octree:
 
     def nodes(self):
         out = np.zeros(OCTREE_MAX_NODES, octnode_dtype)
-        check(lib().rt_octree_nodes(self.h, _np(out)), "rt_octree_nodes")
+        _call("rt_octree_nodes", self.h, _np(out))
         return out
 
     def leaves(self):
         lc = self.info()["leaf_count"]
         counts = np.zeros(lc, np.int32)
         idx = np.zeros((lc, self.spl), np.int32)
-        check(lib().rt_octree_leaves(self.h, _np(counts), _np(idx)), "rt_octree_leaves")
+        _call("rt_octree_leaves", self.h, _np(counts), _np(idx))
         return counts, idx
-
-    def close(self):
-        if getattr(self, "h", None):
-            lib().rt_free_octree(self.h)
-            self.h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
 
 def camera_init(lookfrom, lookat, vup, vfov, aspect, aperture, focus_dist, precision=FP32):
     cam = np.zeros(1, camera_dtype)
     a = [np.asarray(x, np.float32) for x in (lookfrom, lookat, vup)]
-    check(lib().rt_camera_init(_np(cam), _np(a[0]), _np(a[1]), _np(a[2]), vfov, aspect, aperture, focus_dist, precision), "rt_camera_init")
+    _call("rt_camera_init", _np(cam), _np(a[0]), _np(a[1]), _np(a[2]), vfov, aspect, aperture, focus_dist, precision)
     return cam
 
 
@@ -831,29 +834,25 @@ def alloc_fb(max_x, max_y, part=WHOLE, precision=FP32, device="cuda"):
 
 
 def render_init(max_x, max_y, d_rand_state, part=WHOLE):
-    check(lib().rt_render_init(max_x, max_y, _dev(d_rand_state), part, _stream()), "rt_render_init")
+    _call("rt_render_init", max_x, max_y, _dev(d_rand_state), part, _stream())
 
 
 def render(fb, max_x, max_y, ns, world, d_rand_state, octree=None, part=WHOLE):
-    check(lib().rt_render(_dev(fb), max_x, max_y, ns, world.h, _dev(d_rand_state), octree.h if octree is not None else None, part, _stream()),
-          "rt_render")
+    _render(fb, max_x, max_y, ns, world, d_rand_state, octree, part)
 
 
 def render_progressive(fb, max_x, max_y, current_sample, world, d_rand_state, octree=None, part=WHOLE):
-    check(lib().rt_render_progressive(_dev(fb), max_x, max_y, current_sample, world.h, _dev(d_rand_state),
-                                      octree.h if octree is not None else None, part, _stream()), "rt_render_progressive")
+    _call("rt_render_progressive", _dev(fb), max_x, max_y, current_sample, world.h, _dev(d_rand_state), _h(octree), part, _stream())
 
 
 def render_adaptive(fb, max_x, max_y, params, world, d_rand_state, octree=None, d_spp=None):
     """rt_render_adaptive on the current stream: params is an Adaptive; d_spp (optional) an int32 tensor of max_x * max_y"""
-    check(lib().rt_render_adaptive(_dev(fb), max_x, max_y, C.byref(params), world.h, _dev(d_rand_state), octree.h if octree is not None else None,
-                                   _dev(d_spp) if d_spp is not None else None, _stream()), "rt_render_adaptive")
+    _render_adaptive(fb, max_x, max_y, params, world, d_rand_state, octree, d_spp)
 
 
 def render_adaptive_part(fb, max_x, max_y, params, world, d_rand_state, octree=None, d_spp=None, part=WHOLE):
     """rt_render_adaptive_part on the current stream: buffers of rt_part_pixels(part) elements (d_spp: int32), tile-major unless part is the whole frame"""
-    check(lib().rt_render_adaptive_part(_dev(fb), max_x, max_y, C.byref(params), world.h, _dev(d_rand_state), octree.h if octree is not None else None,
-                                        _dev(d_spp) if d_spp is not None else None, part, _stream()), "rt_render_adaptive_part")
+    _render_adaptive_part(fb, max_x, max_y, params, world, d_rand_state, octree, d_spp, part)
 
 
 def alloc_adaptive_state(max_x, max_y, part=WHOLE, device="cuda"):
@@ -864,16 +863,13 @@ def alloc_adaptive_state(max_x, max_y, part=WHOLE, device="cuda"):
 
 def render_adaptive_begin(fb, max_x, max_y, params, world, d_rand_state, d_state, octree=None, d_spp=None, part=WHOLE):
     """rt_render_adaptive_begin on the current stream: rt_render_adaptive_part that also fills d_state (alloc_adaptive_state)"""
-    check(lib().rt_render_adaptive_begin(_dev(fb), max_x, max_y, C.byref(params), world.h, _dev(d_rand_state), octree.h if octree is not None else None,
-                                         _dev(d_spp) if d_spp is not None else None, _dev(d_state), part, _stream()), "rt_render_adaptive_begin")
+    _render_adaptive_begin(fb, max_x, max_y, params, world, d_rand_state, d_state, octree, d_spp, part)
 
 
 def render_adaptive_refine(fb, max_x, max_y, frm, to, world, d_rand_state, d_state, octree=None, d_spp=None, part=WHOLE):
     """rt_render_adaptive_refine on the current stream: continue the frame that d_state holds at target `frm` to the target `to`;
     afterwards fb, d_spp, d_rand_state and d_state hold what render_adaptive_begin(to) would have left"""
-    check(lib().rt_render_adaptive_refine(_dev(fb), max_x, max_y, C.byref(frm), C.byref(to), world.h, _dev(d_rand_state),
-                                          octree.h if octree is not None else None, _dev(d_spp) if d_spp is not None else None, _dev(d_state),
-                                          part, _stream()), "rt_render_adaptive_refine")
+    _render_adaptive_refine(fb, max_x, max_y, frm, to, world, d_rand_state, d_state, octree, d_spp, part)
 
 
 def adaptive_priority(SL, Q, k, floor):
@@ -889,7 +885,7 @@ def adaptive_budget_check(params):
 def adaptive_budget_picks(params, round):
     """rt_adaptive_budget_picks: K_r, the picks of round `round`"""
     k = C.c_int64(0)
-    check(lib().rt_adaptive_budget_picks(C.byref(params), round, C.byref(k)), "rt_adaptive_budget_picks")
+    _call("rt_adaptive_budget_picks", C.byref(params), round, C.byref(k))
     return k.value
 
 
@@ -901,9 +897,7 @@ def adaptive_budget_select(ctx, d_state, max_x, max_y, params, picks, d_list, d_
 def render_adaptive_spend(fb, max_x, max_y, params, world, d_rand_state, d_state, octree=None, d_spp=None, part=WHOLE, d_picked=None):
     """rt_render_adaptive_spend on the current stream: spend the Budget `params` on the frame that d_state holds (render_adaptive_begin,
     _refine or an earlier spend left it); d_picked (optional): one uint32 per round, the round's pick count"""
-    check(lib().rt_render_adaptive_spend(_dev(fb), max_x, max_y, C.byref(params), world.h, _dev(d_rand_state), octree.h if octree is not None else None,
-                                         _dev(d_spp) if d_spp is not None else None, _dev(d_state), part,
-                                         _dev(d_picked) if d_picked is not None else None, _stream()), "rt_render_adaptive_spend")
+    _render_adaptive_spend(fb, max_x, max_y, params, world, d_rand_state, d_state, octree, d_spp, part, d_picked)
 
 
 def adaptive_priority_filtered(l, v, floor):
@@ -919,9 +913,7 @@ def adaptive_budget_select_filtered(ctx, d_state, d_hits, max_x, max_y, params, 
 def render_adaptive_spend_filtered(fb, max_x, max_y, params, filter, d_hits, world, d_rand_state, d_state, octree=None, d_spp=None, d_picked=None):
     """rt_render_adaptive_spend_filtered on the current stream: render_adaptive_spend with the pixels ranked by the error that is left
     after the first level of denoise_adaptive (filter: its DenoiseVarParams, d_hits: the guides); fb stays unfiltered"""
-    check(lib().rt_render_adaptive_spend_filtered(_dev(fb), max_x, max_y, C.byref(params), C.byref(filter), _dev(d_hits), world.h, _dev(d_rand_state),
-                                                  octree.h if octree is not None else None, _dev(d_spp) if d_spp is not None else None, _dev(d_state),
-                                                  _dev(d_picked) if d_picked is not None else None, _stream()), "rt_render_adaptive_spend_filtered")
+    _render_adaptive_spend_filtered(fb, max_x, max_y, params, filter, d_hits, world, d_rand_state, d_state, octree, d_spp, d_picked)
 
 
 def adaptive_budget_select_temporal(ctx, d_state, world, max_x, max_y, params, inputs, temporal, picks, d_list, d_count, d_keys=None):
@@ -933,18 +925,15 @@ def render_adaptive_spend_temporal(fb, max_x, max_y, params, inputs, temporal, w
     """rt_render_adaptive_spend_temporal on the current stream: render_adaptive_spend with the pixels ranked by the error that is left
     after temporal_accumulate merged them with the last frame's history (inputs: temporal_inputs(), temporal: its TemporalParams); fb
     stays unfiltered and the history is only read — run temporal_accumulate after the spend"""
-    check(lib().rt_render_adaptive_spend_temporal(_dev(fb), max_x, max_y, C.byref(params), C.byref(inputs), C.byref(temporal), world.h,
-                                                  _dev(d_rand_state), octree.h if octree is not None else None,
-                                                  _dev(d_spp) if d_spp is not None else None, _dev(d_state),
-                                                  _dev(d_picked) if d_picked is not None else None, _stream()), "rt_render_adaptive_spend_temporal")
+    _render_adaptive_spend_temporal(fb, max_x, max_y, params, inputs, temporal, world, d_rand_state, d_state, octree, d_spp, d_picked)
 
 
 def assemble(fb_full, fb_parts, max_x, max_y, nparts, precision=FP32):
-    check(lib().rt_assemble(_dev(fb_full), _dev(fb_parts), max_x, max_y, nparts, precision, _stream()), "rt_assemble")
+    _call("rt_assemble", _dev(fb_full), _dev(fb_parts), max_x, max_y, nparts, precision, _stream())
 
 
 def trace_rays(world, octree, d_rays, n, d_out):
-    check(lib().rt_trace_rays(world.h, octree.h if octree is not None else None, _dev(d_rays), n, _dev(d_out), _stream()), "rt_trace_rays")
+    _call("rt_trace_rays", world.h, _h(octree), _dev(d_rays), n, _dev(d_out), _stream())
 
 
 def alloc_guides(max_x, max_y, device="cuda"):
@@ -961,7 +950,7 @@ def alloc_denoise_work(max_x, max_y, device="cuda"):
 
 def render_guides(world, octree, max_x, max_y, d_hits):
     """rt_render_guides on the current stream: the first hit of every pixel's centre ray, row-major, into d_hits (alloc_guides)"""
-    check(lib().rt_render_guides(world.h, octree.h if octree is not None else None, max_x, max_y, _dev(d_hits), _stream()), "rt_render_guides")
+    _call("rt_render_guides", world.h, _h(octree), max_x, max_y, _dev(d_hits), _stream())
 
 
 def denoise_check(max_x, max_y, params):
@@ -971,7 +960,7 @@ def denoise_check(max_x, max_y, params):
 
 def denoise(fb_out, fb_in, max_x, max_y, d_hits, params, d_work):
     """rt_denoise on the current stream: params is a DenoiseParams (denoise_params()); fb_out may be fb_in"""
-    check(lib().rt_denoise(_dev(fb_out), _dev(fb_in), max_x, max_y, _dev(d_hits), C.byref(params), _dev(d_work), _stream()), "rt_denoise")
+    _call("rt_denoise", _dev(fb_out), _dev(fb_in), max_x, max_y, _dev(d_hits), C.byref(params), _dev(d_work), _stream())
 
 
 def denoise_adaptive_check(max_x, max_y, params):
@@ -982,8 +971,7 @@ def denoise_adaptive_check(max_x, max_y, params):
 def denoise_adaptive(fb_out, fb_in, max_x, max_y, d_hits, d_state, params, d_work):
     """rt_denoise_adaptive on the current stream: d_state is the whole-frame state render_adaptive_begin / _refine left, fb_in the frame
     of the same call, params a DenoiseVarParams (denoise_var_params()); fb_out may be fb_in"""
-    check(lib().rt_denoise_adaptive(_dev(fb_out), _dev(fb_in), max_x, max_y, _dev(d_hits), _dev(d_state), C.byref(params), _dev(d_work),
-                                    _stream()), "rt_denoise_adaptive")
+    _call("rt_denoise_adaptive", _dev(fb_out), _dev(fb_in), max_x, max_y, _dev(d_hits), _dev(d_state), C.byref(params), _dev(d_work), _stream())
 
 
 def alloc_temporal_history(max_x, max_y, device="cuda"):
@@ -998,31 +986,35 @@ def temporal_check(max_x, max_y, params):
     return lib().rt_temporal_check(max_x, max_y, C.byref(params)) == 0
 
 
+def _temporal_accumulate(name, d_hist_out, d_hist_in, d_hits, d_hits_prev, cam_prev, geom, d_state, world, max_x, max_y, *params):
+    """what the three temporal_accumulate* share: on the first frame (d_hist_in None) the history, the last frame's guides and its camera
+    all go as NULL, whatever was passed for them.  `geom` holds the d_geom_prev pointer of the forms that take one, and here the two
+    differ, on purpose left as they were: temporal_accumulate_moving also nulls d_geom_prev on the first frame,
+    temporal_accumulate_rectified sends it as given."""
+    first = d_hist_in is None
+    cam = None if first else _np(np.ascontiguousarray(cam_prev, camera_dtype).reshape(1))
+    _call(name, _dev(d_hist_out), None if first else _dev(d_hist_in), _dev(d_hits), None if first else _dev(d_hits_prev), cam, *geom, _dev(d_state),
+          world.h, max_x, max_y, *params, _stream())
+
+
 def temporal_accumulate(d_hist_out, d_hist_in, d_hits, d_hits_prev, cam_prev, d_state, world, max_x, max_y, params):
     """rt_temporal_accumulate on the current stream: this frame's history into d_hist_out from its state and guides and, unless
     d_hist_in is None (the first frame), the history, guides and camera (a camera_dtype array) of the last frame; params is a
     TemporalParams (temporal_params())"""
-    first = d_hist_in is None
-    cam = None if first else np.ascontiguousarray(cam_prev, camera_dtype).reshape(1)
-    check(lib().rt_temporal_accumulate(_dev(d_hist_out), None if first else _dev(d_hist_in), _dev(d_hits), None if first else _dev(d_hits_prev),
-                                       None if first else _np(cam), _dev(d_state), world.h, max_x, max_y, C.byref(params), _stream()),
-          "rt_temporal_accumulate")
+    _temporal_accumulate("rt_temporal_accumulate", d_hist_out, d_hist_in, d_hits, d_hits_prev, cam_prev, (), d_state, world, max_x, max_y,
+                         C.byref(params))
 
 
 def temporal_accumulate_moving(d_hist_out, d_hist_in, d_hits, d_hits_prev, cam_prev, d_geom_prev, d_state, world, max_x, max_y, params):
     """rt_temporal_accumulate_moving on the current stream: temporal_accumulate for a world whose spheres moved (World.set_geometry)
     since the frame that wrote d_hist_in; d_geom_prev is what World.get_geometry returned for that frame (None with d_hist_in None)"""
-    first = d_hist_in is None
-    cam = None if first else np.ascontiguousarray(cam_prev, camera_dtype).reshape(1)
-    check(lib().rt_temporal_accumulate_moving(_dev(d_hist_out), None if first else _dev(d_hist_in), _dev(d_hits),
-                                              None if first else _dev(d_hits_prev), None if first else _np(cam),
-                                              None if first or d_geom_prev is None else _dev(d_geom_prev), _dev(d_state), world.h, max_x, max_y,
-                                              C.byref(params), _stream()), "rt_temporal_accumulate_moving")
+    _temporal_accumulate("rt_temporal_accumulate_moving", d_hist_out, d_hist_in, d_hits, d_hits_prev, cam_prev,
+                         (None if d_hist_in is None else _dev(d_geom_prev),), d_state, world, max_x, max_y, C.byref(params))
 
 
 def temporal_rectify_check(rectify):
     """rt_temporal_rectify_check: True when temporal_accumulate_rectified accepts these rectification parameters (host only)"""
-    return lib().rt_temporal_rectify_check(C.byref(rectify) if rectify is not None else None) == 0
+    return lib().rt_temporal_rectify_check(_ref(rectify)) == 0
 
 
 def temporal_accumulate_rectified(d_hist_out, d_hist_in, d_hits, d_hits_prev, cam_prev, d_state, world, max_x, max_y, params, rectify,
@@ -1030,43 +1022,31 @@ def temporal_accumulate_rectified(d_hist_out, d_hist_in, d_hits, d_hits_prev, ca
     """rt_temporal_accumulate_rectified on the current stream: temporal_accumulate (d_geom_prev None) or temporal_accumulate_moving
     (d_geom_prev: what World.get_geometry returned for the frame that wrote d_hist_in) whose history sheds effective samples where this
     frame's neighbourhood contradicts it; rectify is a TemporalRectify (temporal_rectify())"""
-    first = d_hist_in is None
-    cam = None if first else np.ascontiguousarray(cam_prev, camera_dtype).reshape(1)
-    check(lib().rt_temporal_accumulate_rectified(_dev(d_hist_out), None if first else _dev(d_hist_in), _dev(d_hits),
-                                                 None if first else _dev(d_hits_prev), None if first else _np(cam),
-                                                 None if d_geom_prev is None else _dev(d_geom_prev), _dev(d_state), world.h, max_x, max_y,
-                                                 C.byref(params), C.byref(rectify) if rectify is not None else None, _stream()),
-          "rt_temporal_accumulate_rectified")
+    _temporal_accumulate("rt_temporal_accumulate_rectified", d_hist_out, d_hist_in, d_hits, d_hits_prev, cam_prev, (_dev(d_geom_prev),), d_state,
+                         world, max_x, max_y, C.byref(params), _ref(rectify))
 
 
 def denoise_history(fb_out, fb_in, max_x, max_y, d_hits, d_hist, params, d_work):
     """rt_denoise_history on the current stream: denoise_adaptive with the mean and variance of every pixel taken from the history
     d_hist (temporal_accumulate); fb_in supplies the pass-through pixels, fb_out may be fb_in"""
-    check(lib().rt_denoise_history(_dev(fb_out), _dev(fb_in), max_x, max_y, _dev(d_hits), _dev(d_hist), C.byref(params), _dev(d_work), _stream()),
-          "rt_denoise_history")
+    _call("rt_denoise_history", _dev(fb_out), _dev(fb_in), max_x, max_y, _dev(d_hits), _dev(d_hist), C.byref(params), _dev(d_work), _stream())
 
 
 def frame_levels_bytes(max_x, max_y, fmt=LEVELS_RGB8):
     """rt_frame_levels_bytes: the size of frame_levels' output"""
-    n = lib().rt_frame_levels_bytes(max_x, max_y, fmt)
-    if n < 0:
-        raise RtError("rt_frame_levels_bytes: invalid argument")
-    return n
+    return _size("rt_frame_levels_bytes", max_x, max_y, fmt)
 
 
 def frame_levels(d_out, fb, max_x, max_y, params, precision=FP32):
     """rt_frame_levels on the current stream: the frame as 8-bit levels into d_out (a uint8 tensor of frame_levels_bytes), params a
     LevelsParams"""
-    check(lib().rt_frame_levels(_dev(d_out), _dev(fb), max_x, max_y, precision, C.byref(params), _stream()), "rt_frame_levels")
+    _call("rt_frame_levels", _dev(d_out), _dev(fb), max_x, max_y, precision, C.byref(params), _stream())
 
 
 def alloc_compare_work(max_x, max_y, device="cuda"):
     """the workspace of frame_compare: rt_frame_compare_work_bytes bytes (one partial record per block)"""
     import torch
-    n = lib().rt_frame_compare_work_bytes(max_x, max_y)
-    if n < 0:
-        raise RtError("rt_frame_compare_work_bytes: invalid argument")
-    return torch.empty(n // 8, dtype=torch.float64, device=device)
+    return torch.empty(_size("rt_frame_compare_work_bytes", max_x, max_y) // 8, dtype=torch.float64, device=device)
 
 
 def frame_metrics(d_metrics):
@@ -1083,14 +1063,14 @@ def frame_compare(fb_a, fb_b, max_x, max_y, d_work, precision_a=FP32, precision_
     own = d_metrics is None
     if own:
         d_metrics = torch.empty(8, dtype=torch.int64, device=fb_a.device)
-    check(lib().rt_frame_compare(_dev(fb_a), precision_a, _dev(fb_b), precision_b, max_x, max_y, _dev(d_metrics),
-                                 _dev(d_ssim_map) if d_ssim_map is not None else None, _dev(d_work), _stream()), "rt_frame_compare")
+    _call("rt_frame_compare", _dev(fb_a), precision_a, _dev(fb_b), precision_b, max_x, max_y, _dev(d_metrics), _dev(d_ssim_map), _dev(d_work),
+          _stream())
     return frame_metrics(d_metrics) if own else None
 
 
 def write_image(path, fb_host, nx, ny, precision=FP32, fmt=IMAGE_P6):
     fb_host = np.ascontiguousarray(fb_host)
-    check(lib().rt_write_image(str(path).encode(), nx, ny, _np(fb_host), precision, fmt), "rt_write_image")
+    _call("rt_write_image", str(path).encode(), nx, ny, _np(fb_host), precision, fmt)
 
 
 def format_ppm(fb_host, nx, ny, precision=FP32):

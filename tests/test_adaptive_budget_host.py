@@ -3,15 +3,13 @@ rt_adaptive_priority equals the numpy model bit for bit, rt_adaptive_budget_pick
 refused rt_render_adaptive_spend / rt_adaptive_budget_select call returns before any device work — a world created on the host and
 placeholder device pointers are enough."""
 import ctypes as C
-import os
-import re
 
 import numpy as np
 import pytest
 
+import abi_header
 import adaptive_budget_model as M
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 FAKE = C.c_void_p(0x1000)          # never dereferenced: the calls below refuse before they touch a buffer
 NX, NY = 64, 40                    # 8 x 5 = 40 tiles
 WHOLE = (0, 1, 0, 0)
@@ -53,47 +51,12 @@ def w16(rt):
     W.close()
 
 
-def c_param_types(rt, decl):
-    """ctypes types of a C parameter list as the header spells it"""
-    out = []
-    for arg in decl.split(","):
-        arg = " ".join(re.sub(r"/\*.*?\*/", "", arg).split())
-        typ = arg.rsplit(" ", 1)[0] if not arg.endswith("*") else arg
-        if "rt_budget*" in typ:
-            out.append(C.POINTER(rt.Budget))
-        elif "*" in typ:
-            out.append(C.c_void_p)
-        elif typ == "int":
-            out.append(C.c_int)
-        elif typ == "int64_t":
-            out.append(C.c_int64)
-        elif typ == "float":
-            out.append(C.c_float)
-        elif typ == "rt_partition":
-            out.append(rt.Partition)
-        else:
-            raise AssertionError("unexpected parameter type %r" % typ)
-    return out
-
-
 def test_header_and_binding_agree(rt):
-    hdr = open(os.path.join(ROOT, "include", "rt_amd.h")).read()
-    for name in INT_CALLS:
-        m = re.search(r"\bint %s\((.*?)\);" % name, hdr, re.S)
-        assert m, name
-        restype, argtypes = rt.SYMBOLS[name]
-        assert restype is C.c_int and argtypes == c_param_types(rt, m.group(1)), name
-        assert hasattr(rt.lib(), name), name
-    m = re.search(r"\bfloat rt_adaptive_priority\((.*?)\);", hdr, re.S)
-    assert m and rt.SYMBOLS["rt_adaptive_priority"] == (C.c_float, c_param_types(rt, m.group(1)))
-    assert hasattr(rt.lib(), "rt_adaptive_priority")
-    # rt_budget as the header lays it out
-    m = re.search(r"typedef struct rt_budget \{(.*?)\} rt_budget;", hdr, re.S)
-    fields = re.findall(r"^\s*(int64_t|int32_t|float)\s+(\w+);", m.group(1), re.M)
-    ctype = {"int64_t": C.c_int64, "int32_t": C.c_int32, "float": C.c_float}
-    assert [(n, ctype[t]) for t, n in fields] == list(rt.Budget._fields_)
+    abi_header.check_bound(rt, INT_CALLS + ("rt_adaptive_priority",))
+    assert all(abi_header.PROTOTYPES[name][0] is C.c_int for name in INT_CALLS) and abi_header.PROTOTYPES["rt_adaptive_priority"][0] is C.c_float
+    abi_header.check_struct(rt.Budget, "rt_budget")           # rt_budget as the header lays it out
     assert C.sizeof(rt.Budget) == 24
-    assert re.search(r"#define RT_ABI_VERSION 6\b", hdr)
+    assert abi_header.DEFINES["RT_ABI_VERSION"] == 6
     assert rt.lib().rt_abi_version() == 6
     for name in ("Budget", "adaptive_priority", "adaptive_budget_check", "adaptive_budget_picks", "adaptive_budget_select",
                  "render_adaptive_spend"):

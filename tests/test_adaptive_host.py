@@ -1,12 +1,11 @@
 """CPU tests of rt_render_adaptive's argument checks (not gpu): every refused call returns before any device work, so a world
 created on the host and placeholder device pointers are enough.  The binding's rt_adaptive and the header's agree."""
 import ctypes as C
-import os
-import re
 
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+import abi_header
+
 FAKE = C.c_void_p(0x1000)          # never dereferenced: the calls below refuse before they touch a buffer
 NX, NY = 64, 40
 
@@ -77,13 +76,8 @@ def test_binary16_world_is_not_supported(rt, on):
 
 
 def test_binding_and_header_agree(rt):
-    hdr = open(os.path.join(ROOT, "include", "rt_amd.h")).read()
-    body = re.search(r"typedef struct rt_adaptive \{(.*?)\} rt_adaptive;", hdr, re.S).group(1)
-    fields = re.findall(r"^\s*(int32_t|float)\s+(\w+);", body, re.M)
-    ctype = {"int32_t": C.c_int32, "float": C.c_float}
-    assert [(n, ctype[t]) for t, n in fields] == list(rt.Adaptive._fields_)
+    abi_header.check_struct(rt.Adaptive, "rt_adaptive")
     assert C.sizeof(rt.Adaptive) == 20
-    for name in ("rt_render_adaptive", "rt_render_adaptive_on"):
-        assert re.search(r"\bint %s\(" % name, hdr), name
-        assert name in rt.SYMBOLS and hasattr(rt.lib(), name)
+    abi_header.check_bound(rt, ("rt_render_adaptive", "rt_render_adaptive_on"))
+    assert abi_header.PROTOTYPES["rt_render_adaptive"][0] is abi_header.PROTOTYPES["rt_render_adaptive_on"][0] is C.c_int
     assert rt.lib().rt_abi_version() == 6

@@ -2,12 +2,11 @@
 every refused call returns before any device work — a world created on the host and placeholder device pointers are enough.
 (A refused root without fb_full needs an rt_multi, which lives on a device: tests/test_gpu_multi_adaptive.py checks it.)"""
 import ctypes as C
-import os
-import re
 
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+import abi_header
+
 FAKE = C.c_void_p(0x1000)          # never dereferenced: the calls below refuse before they touch a buffer
 NX, NY = 64, 40                    # 8 x 5 = 40 tiles
 NEW = ("rt_render_adaptive_part", "rt_render_adaptive_part_on", "rt_multi_render_adaptive")
@@ -35,10 +34,8 @@ def world(rt):
 
 
 def test_new_symbols_are_declared_exported_and_bound(rt):
-    hdr = open(os.path.join(ROOT, "include", "rt_amd.h")).read()
-    for name in NEW:
-        assert re.search(r"\bint %s\(" % name, hdr), name
-        assert name in rt.SYMBOLS and hasattr(rt.lib(), name), name
+    abi_header.check_bound(rt, NEW)
+    assert all(abi_header.PROTOTYPES[name][0] is C.c_int for name in NEW)
     assert rt.lib().rt_abi_version() == 6
 
 

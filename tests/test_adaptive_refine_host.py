@@ -2,12 +2,11 @@
 the same signatures, and every refused call returns before any device work — a world created on the host and placeholder device
 pointers are enough.  A binary16 world answers RT_ENOTSUP only after the parameter checks, so it shows which pairs the rule accepts."""
 import ctypes as C
-import os
-import re
 
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+import abi_header
+
 FAKE = C.c_void_p(0x1000)          # never dereferenced: the calls below refuse before they touch a buffer
 NX, NY = 64, 40                    # 8 x 5 = 40 tiles
 NEW = ("rt_render_adaptive_begin", "rt_render_adaptive_begin_on", "rt_render_adaptive_refine", "rt_render_adaptive_refine_on")
@@ -51,34 +50,10 @@ def w16(rt):
     W.close()
 
 
-def c_param_types(rt, decl):
-    """ctypes types of a C parameter list as the header spells it"""
-    out = []
-    for arg in decl.split(","):
-        arg = " ".join(arg.split())
-        typ = arg.rsplit(" ", 1)[0] if not arg.endswith("*") else arg
-        if "rt_adaptive*" in typ:
-            out.append(C.POINTER(rt.Adaptive))
-        elif "*" in typ:
-            out.append(C.c_void_p)
-        elif typ == "int":
-            out.append(C.c_int)
-        elif typ == "rt_partition":
-            out.append(rt.Partition)
-        else:
-            raise AssertionError("unexpected parameter type %r" % typ)
-    return out
-
-
 def test_header_and_binding_agree(rt):
-    hdr = open(os.path.join(ROOT, "include", "rt_amd.h")).read()
-    for name in NEW:
-        m = re.search(r"\bint %s\((.*?)\);" % name, hdr, re.S)
-        assert m, name
-        restype, argtypes = rt.SYMBOLS[name]
-        assert restype is C.c_int and argtypes == c_param_types(rt, m.group(1)), name
-        assert hasattr(rt.lib(), name), name
-    assert re.search(r"#define RT_ADAPTIVE_STATE_BYTES 24\b", hdr)
+    abi_header.check_bound(rt, NEW)
+    assert all(abi_header.PROTOTYPES[name][0] is C.c_int for name in NEW)
+    assert abi_header.DEFINES["RT_ADAPTIVE_STATE_BYTES"] == 24
     assert rt.ADAPTIVE_STATE_BYTES == 24
     assert rt.lib().rt_abi_version() == 6
 

@@ -1,15 +1,13 @@
 """CPU tests of the animation entry points (not gpu): the camera of a world that is never uploaded, the new symbols in header, library
 and binding, and the numpy model of rt_temporal_accumulate_moving (tests/temporal_moving_model.py) on its hand-worked cases."""
 import ctypes as C
-import os
-import re
 
 import numpy as np
 import pytest
 
+import abi_header
 import temporal_moving_model as tmm
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NEW = ("rt_world_set_camera", "rt_world_camera", "rt_world_set_geometry", "rt_world_get_geometry", "rt_temporal_accumulate_moving")
 
 
@@ -45,18 +43,13 @@ def test_camera_round_trip_without_a_device(rt, precision):
 
 
 def test_header_library_and_binding_name_the_new_symbols(rt):
-    hdr = open(os.path.join(ROOT, "include", "rt_amd.h")).read()
-    declared = set(re.findall(r"^int (rt_[a-z0-9_]+)\(", hdr, re.M))
-    L = rt.lib()
-    for name in NEW:
-        assert name in declared, name
-        assert name in rt.SYMBOLS, name
-        assert hasattr(L, name), name
+    abi_header.check_bound(rt, NEW)
+    assert all(abi_header.PROTOTYPES[name][0] is C.c_int for name in NEW)
     assert len(rt.SYMBOLS["rt_temporal_accumulate_moving"][1]) == 12 and len(rt.SYMBOLS["rt_world_set_geometry"][1]) == 3
     for name in ("set_camera", "get_camera", "set_geometry", "get_geometry"):
         assert callable(getattr(rt.World, name)), name
     assert callable(rt.temporal_accumulate_moving)
-    assert L.rt_abi_version() == 6 and "#define RT_ABI_VERSION 6" in hdr
+    assert rt.lib().rt_abi_version() == 6 and abi_header.DEFINES["RT_ABI_VERSION"] == 6
 
 
 def test_the_moving_model_on_its_hand_worked_cases():

@@ -3,13 +3,11 @@ refused call returns its code before any device work — placeholder device poin
 RT_ENOTSUP from rt_render_guides only after the argument checks, which pins the frame-size limit of the guides; rt_denoise_check
 (the host-only size and parameter checks that rt_denoise runs) pins the filter's limit and shows which parameters are accepted."""
 import ctypes as C
-import os
-import re
 
-import numpy as np
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+import abi_header
+
 FAKE = C.c_void_p(0x1000)          # never dereferenced: the calls below refuse before they touch a buffer
 NX, NY = 64, 40
 EINVAL, ENOTSUP = -1, -4
@@ -30,33 +28,14 @@ def w16(rt):
 
 
 def test_header_and_binding_agree(rt):
-    hdr = open(os.path.join(ROOT, "include", "rt_amd.h")).read()
-    m = re.search(r"\bint rt_render_guides\((.*?)\);", hdr, re.S)
-    assert m and [a.split()[-1].lstrip("*") for a in m.group(1).split(",")] == ["world", "d_octree", "max_x", "max_y", "d_hits", "stream"]
-    assert rt.SYMBOLS["rt_render_guides"] == (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p])
-    m = re.search(r"\bint rt_denoise\((.*?)\);", hdr, re.S)
-    assert m and [a.split()[-1].lstrip("*") for a in m.group(1).split(",")] == ["fb_out", "fb_in", "max_x", "max_y", "d_hits", "params",
-                                                                                 "d_work", "stream"]
-    assert rt.SYMBOLS["rt_denoise"] == (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.POINTER(rt.DenoiseParams),
-                                                  C.c_void_p, C.c_void_p])
-    m = re.search(r"\bint rt_denoise_check\((.*?)\);", hdr, re.S)
-    assert m and [a.split()[-1].lstrip("*") for a in m.group(1).split(",")] == ["max_x", "max_y", "params"]
-    assert rt.SYMBOLS["rt_denoise_check"] == (C.c_int, [C.c_int, C.c_int, C.POINTER(rt.DenoiseParams)])
-    for name in ("rt_render_guides", "rt_denoise", "rt_denoise_check"):
-        assert hasattr(rt.lib(), name), name
-    # the struct, the constants and the defaults as the header defines them
-    body = re.search(r"typedef struct rt_denoise_params \{(.*?)\} rt_denoise_params;", hdr, re.S).group(1)
-    fields = re.findall(r"\b(int32_t|float)\s+(\w+);", body)
-    assert [(n, {"int32_t": C.c_int32, "float": C.c_float}[t]) for t, n in fields] == rt.DenoiseParams._fields_
-    consts = dict(re.findall(r"#define (RT_DENOISE_\w+) ([0-9.]+)f?\b", hdr))
-    assert int(consts["RT_DENOISE_INPUT_GAMMA"]) == rt.DENOISE_INPUT_GAMMA and int(consts["RT_DENOISE_INPUT_SUM"]) == rt.DENOISE_INPUT_SUM
-    assert int(consts["RT_DENOISE_MAX_LEVELS"]) == rt.DENOISE_MAX_LEVELS and int(consts["RT_DENOISE_WORK_BYTES"]) == rt.DENOISE_WORK_BYTES == 32
-    assert int(consts["RT_DENOISE_MAX_PIXELS"]) == rt.DENOISE_MAX_PIXELS == 1 << 30
-    d = rt.DENOISE_DEFAULTS
-    assert int(consts["RT_DENOISE_DEFAULT_LEVELS"]) == d["levels"]
-    assert int(consts["RT_DENOISE_DEFAULT_NORMAL_POW_LOG2"]) == d["normal_pow_log2"]
-    assert np.float32(consts["RT_DENOISE_DEFAULT_SIGMA_POSITION"]) == np.float32(d["sigma_position"])
-    assert np.float32(consts["RT_DENOISE_DEFAULT_SIGMA_COLOR"]) == np.float32(d["sigma_color"])
+    names = {"rt_render_guides": ["world", "d_octree", "max_x", "max_y", "d_hits", "stream"],
+             "rt_denoise": ["fb_out", "fb_in", "max_x", "max_y", "d_hits", "params", "d_work", "stream"],
+             "rt_denoise_check": ["max_x", "max_y", "params"]}
+    abi_header.check_bound(rt, names)
+    for name in names:
+        assert abi_header.PARAM_NAMES[name] == names[name] and abi_header.PROTOTYPES[name][0] is C.c_int, name
+    # the struct as the header defines it (its constants and defaults: tests/test_host_and_abi.py::test_constants_equal_the_header)
+    abi_header.check_struct(rt.DenoiseParams, "rt_denoise_params")
 
 
 def guides(rt, world, octree=None, nx=NX, ny=NY, hits=FAKE):

@@ -4,10 +4,10 @@ accepted; the frame limit sits at exactly RT_DENOISE_MAX_PIXELS; the numpy model
 restatement; and the ABI version is still 6 (the feature only adds symbols)."""
 import ctypes as C
 import os
-import re
 
 import numpy as np
 
+import abi_header
 import denoise_var_model
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -17,29 +17,15 @@ EINVAL = -1
 
 
 def test_header_and_binding_agree(rt):
-    hdr = open(os.path.join(ROOT, "include", "rt_amd.h")).read()
-    m = re.search(r"\bint rt_denoise_adaptive\((.*?)\);", hdr, re.S)
-    assert m and [a.split()[-1].lstrip("*") for a in m.group(1).split(",")] == ["fb_out", "fb_in", "max_x", "max_y", "d_hits", "d_state",
-                                                                                 "params", "d_work", "stream"]
-    assert rt.SYMBOLS["rt_denoise_adaptive"] == (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
-                                                           C.POINTER(rt.DenoiseVarParams), C.c_void_p, C.c_void_p])
-    m = re.search(r"\bint rt_denoise_adaptive_check\((.*?)\);", hdr, re.S)
-    assert m and [a.split()[-1].lstrip("*") for a in m.group(1).split(",")] == ["max_x", "max_y", "params"]
-    assert rt.SYMBOLS["rt_denoise_adaptive_check"] == (C.c_int, [C.c_int, C.c_int, C.POINTER(rt.DenoiseVarParams)])
-    for name in ("rt_denoise_adaptive", "rt_denoise_adaptive_check"):
-        assert hasattr(rt.lib(), name), name
-    body = re.search(r"typedef struct rt_denoise_var_params \{(.*?)\} rt_denoise_var_params;", hdr, re.S).group(1)
-    fields = re.findall(r"\b(int32_t|float)\s+(\w+);", body)
-    assert [(n, {"int32_t": C.c_int32, "float": C.c_float}[t]) for t, n in fields] == rt.DenoiseVarParams._fields_
-    consts = dict(re.findall(r"#define (RT_DENOISE_VAR_\w+) ([0-9.e-]+)f?\b", hdr))
-    assert np.float32(consts["RT_DENOISE_VAR_EPS"]) == np.float32(rt.DENOISE_VAR_EPS) == denoise_var_model.EPS
-    d = rt.DENOISE_VAR_DEFAULTS
-    assert int(consts["RT_DENOISE_VAR_DEFAULT_LEVELS"]) == d["levels"]
-    assert int(consts["RT_DENOISE_VAR_DEFAULT_NORMAL_POW_LOG2"]) == d["normal_pow_log2"]
-    assert int(consts["RT_DENOISE_VAR_DEFAULT_PREFILTER"]) == d["prefilter"]
-    assert np.float32(consts["RT_DENOISE_VAR_DEFAULT_SIGMA_POSITION"]) == np.float32(d["sigma_position"])
-    assert np.float32(consts["RT_DENOISE_VAR_DEFAULT_SIGMA_VARIANCE"]) == np.float32(d["sigma_variance"])
-    assert set(d) == {n for n, _ in rt.DenoiseVarParams._fields_}
+    names = {"rt_denoise_adaptive": ["fb_out", "fb_in", "max_x", "max_y", "d_hits", "d_state", "params", "d_work", "stream"],
+             "rt_denoise_adaptive_check": ["max_x", "max_y", "params"]}
+    abi_header.check_bound(rt, names)
+    for name in names:
+        assert abi_header.PARAM_NAMES[name] == names[name] and abi_header.PROTOTYPES[name][0] is C.c_int, name
+    abi_header.check_struct(rt.DenoiseVarParams, "rt_denoise_var_params")
+    # (the header's constants and defaults against the binding's: tests/test_host_and_abi.py::test_constants_equal_the_header)
+    assert np.float32(abi_header.DEFINES["RT_DENOISE_VAR_EPS"]) == denoise_var_model.EPS
+    assert set(rt.DENOISE_VAR_DEFAULTS) == {n for n, _ in rt.DenoiseVarParams._fields_}
 
 
 def test_abi_version_is_unchanged(rt):

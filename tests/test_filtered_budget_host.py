@@ -3,15 +3,13 @@ has not moved, tests/filtered_budget_model.py passes its self-check, rt_adaptive
 and every refused rt_adaptive_budget_select_filtered / rt_render_adaptive_spend_filtered call returns before any device work — a world
 created on the host and placeholder device pointers are enough."""
 import ctypes as C
-import os
-import re
 
 import numpy as np
 import pytest
 
+import abi_header
 import filtered_budget_model as M
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 FAKE = C.c_void_p(0x1000)          # 16-byte aligned, never dereferenced: the calls below refuse before they touch a buffer
 ODD = C.c_void_p(0x1008)           # not 16-byte aligned
 NX, NY = 64, 40
@@ -46,48 +44,17 @@ def world(rt):
     W.close()
 
 
-def c_param_types(rt, decl):
-    """ctypes types of a C parameter list as the header spells it"""
-    out = []
-    for arg in decl.split(","):
-        arg = " ".join(re.sub(r"/\*.*?\*/", "", arg).split())
-        typ = arg.rsplit(" ", 1)[0] if not arg.endswith("*") else arg
-        if "rt_budget*" in typ:
-            out.append(C.POINTER(rt.Budget))
-        elif "rt_denoise_var_params*" in typ:
-            out.append(C.POINTER(rt.DenoiseVarParams))
-        elif "*" in typ:
-            out.append(C.c_void_p)
-        elif typ == "int":
-            out.append(C.c_int)
-        elif typ == "int64_t":
-            out.append(C.c_int64)
-        elif typ == "float":
-            out.append(C.c_float)
-        else:
-            raise AssertionError("unexpected parameter type %r" % typ)
-    return out
-
-
 def test_header_and_binding_agree(rt):
-    hdr = open(os.path.join(ROOT, "include", "rt_amd.h")).read()
-    for name in INT_CALLS:
-        m = re.search(r"\bint %s\((.*?)\);" % name, hdr, re.S)
-        assert m, name
-        restype, argtypes = rt.SYMBOLS[name]
-        assert restype is C.c_int and argtypes == c_param_types(rt, m.group(1)), name
-        assert hasattr(rt.lib(), name), name
-    m = re.search(r"\bfloat rt_adaptive_priority_filtered\((.*?)\);", hdr, re.S)
-    assert m and rt.SYMBOLS["rt_adaptive_priority_filtered"] == (C.c_float, c_param_types(rt, m.group(1)))
-    assert hasattr(rt.lib(), "rt_adaptive_priority_filtered")
+    abi_header.check_bound(rt, INT_CALLS + ("rt_adaptive_priority_filtered",))
+    assert all(abi_header.PROTOTYPES[name][0] is C.c_int for name in INT_CALLS)
+    assert abi_header.PROTOTYPES["rt_adaptive_priority_filtered"][0] is C.c_float
     for name in ("adaptive_priority_filtered", "adaptive_budget_select_filtered", "render_adaptive_spend_filtered"):
         assert hasattr(rt, name), name
     assert hasattr(rt.RenderCtx, "render_adaptive_spend_filtered") and hasattr(rt.RenderCtx, "adaptive_budget_select_filtered")
 
 
 def test_abi_version_is_still_6(rt):
-    hdr = open(os.path.join(ROOT, "include", "rt_amd.h")).read()
-    assert re.search(r"#define RT_ABI_VERSION 6\b", hdr)
+    assert abi_header.DEFINES["RT_ABI_VERSION"] == 6
     assert rt.lib().rt_abi_version() == 6
 
 

@@ -1,12 +1,15 @@
 """CPU tests of the product's host side (not gpu): the C-ABI library loads and exports every symbol of
-include/rt_amd.h, and its host-only entry points (world generation, camera, octree build, PPM writer, partition
+include/rt_amd.h, the binding agrees with the whole header (every prototype's types, every mirrored structure, every constant it
+restates: tests/abi_header.py reads the header), and its host-only entry points (world generation, camera, octree build, PPM writer, partition
 arithmetic) agree bit for bit with the oracle.  No compute entry point is called here."""
+import ctypes as C
 import os
 import re
 
 import numpy as np
 import pytest
 
+import abi_header
 from oracle_lib import OracleScene, ppm_bytes
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -17,14 +20,55 @@ def u32(a):
 
 
 def test_abi_exports_every_declared_symbol(rt):
-    hdr = open(os.path.join(ROOT, "include", "rt_amd.h")).read()
-    declared = set(re.findall(r"\b(rt_[a-z0-9_]+)\s*\(", hdr))
-    assert declared, "no declarations parsed"
-    assert declared == set(rt.SYMBOLS), "binding and header disagree: %s" % (declared ^ set(rt.SYMBOLS))
-    L = rt.lib()
-    for name in declared:
-        assert hasattr(L, name), name
-    assert L.rt_abi_version() == 6
+    """the whole ABI, once: every prototype of the header is bound with the header's types and exported, and nothing else is bound"""
+    hdr = open(abi_header.HEADER).read()
+    assert len(abi_header.PROTOTYPES) == 108 and set(abi_header.PROTOTYPES) == set(re.findall(r"\b(rt_[a-z0-9_]+)\s*\(", hdr)), "a declaration was lost"
+    assert set(abi_header.PROTOTYPES) == set(rt.SYMBOLS), "binding and header disagree: %s" % (set(abi_header.PROTOTYPES) ^ set(rt.SYMBOLS))
+    abi_header.check_bound(rt, abi_header.PROTOTYPES)
+    assert rt.lib().rt_abi_version() == abi_header.DEFINES["RT_ABI_VERSION"] == 6
+
+
+def test_structures_mirror_the_header(rt):
+    """every ctypes.Structure of the binding: the header's fields in the header's order, and the size the C layout gives them; the
+    PODs that travel as numpy records: the header's size"""
+    mirrored = {c for c in vars(rt).values() if isinstance(c, type) and issubclass(c, C.Structure)}
+    assert mirrored == set(abi_header.MIRRORS.values()) and len(mirrored) == 10
+    for name, cls in abi_header.MIRRORS.items():
+        abi_header.check_struct(cls, name)
+    for name in ("rand_state", "sphere", "camera", "octnode", "hit_record"):
+        assert getattr(rt, name + "_dtype").itemsize == C.sizeof(abi_header.layout("rt_" + name)), name
+    assert C.sizeof(rt.FrameMetrics) == 64 and C.sizeof(rt.LevelsParams) == 16 and C.sizeof(rt.Partition) == 24
+
+
+# a constant of the binding is the header's #define without its RT_, except the two precisions; a dict of defaults: (the prefix of its
+# fields' defines, the structure it fills)
+RENAMED = {"FP32": "RT_PRECISION_FP32", "FP16": "RT_PRECISION_FP16"}
+DEFAULTS = {"DENOISE_DEFAULTS": ("RT_DENOISE_DEFAULT_", "DenoiseParams"), "DENOISE_VAR_DEFAULTS": ("RT_DENOISE_VAR_DEFAULT_", "DenoiseVarParams"),
+            "TEMPORAL_DEFAULTS": ("RT_TEMPORAL_DEFAULT_", "TemporalParams"), "TEMPORAL_RECTIFY_DEFAULTS": ("RT_TEMPORAL_RECTIFY_DEFAULT_", "TemporalRectify")}
+
+
+def test_constants_equal_the_header(rt):
+    """every constant the binding restates: ints equal, a float as the binary32 the header's f suffix makes of it"""
+    D = abi_header.DEFINES
+    pairs = dict(RENAMED, **{hdr[3:]: hdr for hdr in D if hasattr(rt, hdr[3:])})
+    assert len(pairs) >= 30 and {"PART_RUN", "ADAPTIVE_STATE_BYTES", "OCTREE_MAX_NODES", "DENOISE_MAX_PIXELS", "LEVELS_GRAY8"} <= set(pairs)
+    for py, (prefix, cls) in DEFAULTS.items():
+        v, fields = getattr(rt, py), [f for f, _ in getattr(rt, cls)._fields_]
+        assert list(v) == fields[len(fields) - len(v):], py                        # the defaults builder fills the structure's tail in this order
+        assert set(v) == {hdr[len(prefix):].lower() for hdr in D if hdr.startswith(prefix)}, py
+        pairs.update({(py, k): prefix + k.upper() for k in v})
+    for py, hdr in pairs.items():
+        v = getattr(rt, py) if isinstance(py, str) else getattr(rt, py[0])[py[1]]
+        assert type(v) is type(D[hdr]) and (v == D[hdr] or np.float32(v) == np.float32(D[hdr])), py
+    assert len(rt.SCHEDULE_FIELDS) == D["RT_SCHEDULE_WORDS"] and len(rt.FEEDBACK_FIELDS) == D["RT_FEEDBACK_WORDS"]
+    assert rt.DENOISE_MAX_PIXELS == 1 << 30 and rt.DENOISE_WORK_BYTES == 32 and rt.ADAPTIVE_STATE_BYTES == 24
+    # and nothing rt_amd.py marks as the header's went uncompared: "rt_amd.h RT_X", or "RT_X_*" for every define of that family
+    marked = set(re.findall(r"rt_amd\.h (RT_[A-Z0-9_]+)", open(rt.__file__).read()))
+    compared = set(pairs.values()) | {"RT_SCHEDULE_WORDS", "RT_FEEDBACK_WORDS"}
+    for m in marked:
+        family = [hdr for hdr in D if hdr.startswith(m)] if m.endswith("_") else [m]
+        assert family and set(family) <= compared, (m, set(family) - compared)
+    assert len(marked) >= 15
 
 
 def test_pod_sizes_match_reference_structs(rt):

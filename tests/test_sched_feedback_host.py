@@ -3,9 +3,11 @@ AddressSanitizer + UndefinedBehaviorSanitizer on the CPU (tests/host/sched_feedb
 one rebuild per record, every way the counts end (another key, a regrown or freed workspace, a capture, the two switches), a
 recording launch whose render kernel failed, and that a failed rebuild leaves no valid record.  Also: the new entry points are
 declared, exported and bound, and the knobs are in rt_tuning.h."""
+import ctypes as C
 import os
-import re
 import subprocess
+
+import abi_header
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "dd2360-raytracing_amd", "csrc")
@@ -24,14 +26,13 @@ def test_refinement_decision_under_asan_ubsan(tmp_path):
 
 
 def test_feedback_entry_points_are_declared_exported_and_bound(rt):
-    header = open(os.path.join(ROOT, "include", "rt_amd.h")).read()
-    assert "#define RT_FEEDBACK_WORDS 4" in header and len(rt.FEEDBACK_FIELDS) == 4
-    for name in ("rt_render_ctx_schedule_feedback", "rt_world_render_schedule_feedback"):
-        assert re.search(r"\bint %s\((rt_render_ctx|rt_world)\* \w+, uint64_t\* refined, uint32_t\* out, int n\);" % name, header), name
-        assert name in rt.SYMBOLS and hasattr(rt.lib(), name)
-    for name in ("rt_render_ctx_schedule_counts", "rt_world_render_schedule_counts"):
-        assert re.search(r"\bint %s\((rt_render_ctx|rt_world)\* \w+, uint16_t\* out, int64_t n\);" % name, header), name
-        assert name in rt.SYMBOLS and hasattr(rt.lib(), name)
+    assert abi_header.DEFINES["RT_FEEDBACK_WORDS"] == 4 and len(rt.FEEDBACK_FIELDS) == 4
+    for stem, handle in (("rt_render_ctx", "rt_render_ctx*"), ("rt_world_render", "rt_world*")):
+        for name, types, names in ((stem + "_schedule_feedback", ["uint64_t*", "uint32_t*", "int"], ["refined", "out", "n"]),
+                                   (stem + "_schedule_counts", ["uint16_t*", "int64_t"], ["out", "n"])):
+            assert abi_header.PARAM_C_TYPES[name] == [handle] + types and abi_header.PARAM_NAMES[name][1:] == names, name
+            assert abi_header.PROTOTYPES[name][0] is C.c_int
+            abi_header.check_bound(rt, [name])
     W = rt.World(22, 64, 40)
     try:
         f = W.schedule_feedback()                            # host state: no device needed before any launch

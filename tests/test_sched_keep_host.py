@@ -3,9 +3,12 @@ UndefinedBehaviorSanitizer on the CPU (tests/host/sched_keep_check.cpp): keys th
 is dropped or bypassed (a miss drops it before the pass is launched, a regrown or freed workspace, a stream capture and the context's
 life after it, the RT_SCHED_CACHE switch), and that a failed pass leaves no valid record.  Also: the header stays free of HIP, and the
 library's two reuse counters are declared, exported and bound."""
+import ctypes as C
 import os
 import re
 import subprocess
+
+import abi_header
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "dd2360-raytracing_amd", "csrc")
@@ -30,11 +33,11 @@ def test_the_header_includes_no_hip():
 
 
 def test_reuse_counters_are_declared_exported_and_bound(rt):
-    header = open(os.path.join(ROOT, "include", "rt_amd.h")).read()
-    assert "#define RT_ABI_VERSION 6" in header and rt.lib().rt_abi_version() == 6
-    for name in ("rt_render_ctx_schedule_reuse", "rt_world_render_schedule_reuse"):
-        assert re.search(r"\bint %s\((rt_render_ctx|rt_world)\* \w+, uint64_t\* reused, uint64_t\* computed\);" % name, header), name
-        assert name in rt.SYMBOLS and hasattr(rt.lib(), name)
+    assert abi_header.DEFINES["RT_ABI_VERSION"] == 6 and rt.lib().rt_abi_version() == 6
+    for name, handle in (("rt_render_ctx_schedule_reuse", "rt_render_ctx*"), ("rt_world_render_schedule_reuse", "rt_world*")):
+        assert abi_header.PARAM_C_TYPES[name] == [handle, "uint64_t*", "uint64_t*"] and abi_header.PARAM_NAMES[name][1:] == ["reused", "computed"], name
+        assert abi_header.PROTOTYPES[name][0] is C.c_int
+        abi_header.check_bound(rt, [name])
     W = rt.World(22, 64, 40)
     try:
         assert W.schedule_reuse() == (0, 0)                  # host counters: no device needed

@@ -5,17 +5,15 @@ are enough, and every case below holds at least one fault, so nothing here start
 case on the model alone: a history of 32 effective samples in the left half, none in the right half, and K = the size of the right
 half selects exactly the right half."""
 import ctypes as C
-import os
-import re
 
 import numpy as np
 import pytest
 
+import abi_header
 import adaptive_budget_model as B
 import temporal_budget_model as M
 import temporal_model as tm
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 FAKE = 0x1000                      # 16-byte aligned, never dereferenced: the calls below refuse before they touch a buffer
 ODD = 0x1008                       # not 16-byte aligned
 NX, NY = 64, 40
@@ -64,40 +62,11 @@ def test_model_self_check():
 
 
 # ---- header, library and binding ----------------------------------------------------------------------------------------------------
-def c_param_types(rt, decl):
-    """ctypes types of a C parameter list as the header spells it"""
-    out = []
-    for arg in decl.split(","):
-        arg = " ".join(re.sub(r"/\*.*?\*/", "", arg).split())
-        typ = arg.rsplit(" ", 1)[0] if not arg.endswith("*") else arg
-        if "rt_budget*" in typ:
-            out.append(C.POINTER(rt.Budget))
-        elif "rt_temporal_inputs*" in typ:
-            out.append(C.POINTER(rt.TemporalInputs))
-        elif "rt_temporal_params*" in typ:
-            out.append(C.POINTER(rt.TemporalParams))
-        elif "*" in typ:
-            out.append(C.c_void_p)
-        elif typ == "int":
-            out.append(C.c_int)
-        elif typ == "int64_t":
-            out.append(C.c_int64)
-        else:
-            raise AssertionError("unexpected parameter type %r" % typ)
-    return out
-
-
 def test_header_library_and_binding_agree(rt):
-    hdr = open(os.path.join(ROOT, "include", "rt_amd.h")).read()
-    for name in NEW_CALLS:
-        m = re.search(r"\bint %s\((.*?)\);" % name, hdr, re.S)
-        assert m, name
-        restype, argtypes = rt.SYMBOLS[name]
-        assert restype is C.c_int and argtypes == c_param_types(rt, m.group(1)), name
-        assert hasattr(rt.lib(), name), name
-    m = re.search(r"typedef struct rt_temporal_inputs \{(.*?)\} rt_temporal_inputs;", hdr, re.S)
-    fields = re.findall(r"\*\s*(\w+);", m.group(1))
-    assert fields == [f[0] for f in rt.TemporalInputs._fields_] == ["d_hist_in", "d_hits", "d_hits_prev", "cam_prev"]
+    abi_header.check_bound(rt, NEW_CALLS)
+    assert all(abi_header.PROTOTYPES[name][0] is C.c_int for name in NEW_CALLS)
+    abi_header.check_struct(rt.TemporalInputs, "rt_temporal_inputs")
+    assert [f[0] for f in rt.TemporalInputs._fields_] == ["d_hist_in", "d_hits", "d_hits_prev", "cam_prev"]
     assert C.sizeof(rt.TemporalInputs) == 4 * C.sizeof(C.c_void_p)
     for name in ("adaptive_budget_select_temporal", "render_adaptive_spend_temporal", "temporal_inputs"):
         assert hasattr(rt, name), name
@@ -105,8 +74,7 @@ def test_header_library_and_binding_agree(rt):
 
 
 def test_abi_version_is_still_6(rt):
-    hdr = open(os.path.join(ROOT, "include", "rt_amd.h")).read()
-    assert re.search(r"#define RT_ABI_VERSION 6\b", hdr)
+    assert abi_header.DEFINES["RT_ABI_VERSION"] == 6
     assert rt.lib().rt_abi_version() == 6
 
 

@@ -3,14 +3,12 @@ rt_temporal_check and rt_denoise_history are declared, exported and bound with t
 rt_temporal_check refuses every out-of-range field and accepts the defaults; every refused call returns RT_EINVAL before any device
 work (placeholder device pointers are enough); and the ABI version is still 6 (the feature only adds symbols)."""
 import ctypes as C
-import os
-import re
 
 import numpy as np
 
+import abi_header
 import temporal_model
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 FAKE, FAKE2 = C.c_void_p(0x100000), C.c_void_p(0x900000)      # never dereferenced: the calls below refuse before they touch a buffer
 NX, NY = 64, 40
 EINVAL, ENOTSUP = -1, -4
@@ -22,32 +20,18 @@ def test_the_model_follows_the_rule():
 
 
 def test_header_library_and_binding_agree(rt):
-    hdr = open(os.path.join(ROOT, "include", "rt_amd.h")).read()
     names = {"rt_temporal_check": ["max_x", "max_y", "params"],
              "rt_temporal_accumulate": ["d_hist_out", "d_hist_in", "d_hits", "d_hits_prev", "cam_prev", "d_state", "world", "max_x", "max_y",
                                         "params", "stream"],
              "rt_denoise_history": ["fb_out", "fb_in", "max_x", "max_y", "d_hits", "d_hist", "params", "d_work", "stream"]}
+    abi_header.check_bound(rt, NEW)
     for name in NEW:
-        m = re.search(r"\bint %s\((.*?)\);" % name, hdr, re.S)
-        assert m and [a.split()[-1].lstrip("*") for a in m.group(1).split(",")] == names[name], name
-        assert hasattr(rt.lib(), name), name
-        assert name in rt.SYMBOLS, name
-    vp, i = C.c_void_p, C.c_int
-    assert rt.SYMBOLS["rt_temporal_check"] == (i, [i, i, C.POINTER(rt.TemporalParams)])
-    assert rt.SYMBOLS["rt_temporal_accumulate"] == (i, [vp, vp, vp, vp, vp, vp, vp, i, i, C.POINTER(rt.TemporalParams), vp])
-    assert rt.SYMBOLS["rt_denoise_history"] == (i, [vp, vp, i, i, vp, vp, C.POINTER(rt.DenoiseVarParams), vp, vp])
-    body = re.search(r"typedef struct rt_temporal_params \{(.*?)\} rt_temporal_params;", hdr, re.S).group(1)
-    fields = re.findall(r"\b(int32_t|float)\s+(\w+);", body)
-    assert [(n, {"int32_t": C.c_int32, "float": C.c_float}[t]) for t, n in fields] == rt.TemporalParams._fields_
+        assert abi_header.PARAM_NAMES[name] == names[name] and abi_header.PROTOTYPES[name][0] is C.c_int, name
+    abi_header.check_struct(rt.TemporalParams, "rt_temporal_params")
     assert C.sizeof(rt.TemporalParams) == 16
-    consts = dict(re.findall(r"#define (RT_TEMPORAL_\w+) (-?[0-9.e-]+)f?\b", hdr))
-    assert int(consts["RT_TEMPORAL_HISTORY_BYTES"]) == rt.TEMPORAL_HISTORY_BYTES == 20
-    d = rt.TEMPORAL_DEFAULTS
-    assert int(consts["RT_TEMPORAL_DEFAULT_MAX_HISTORY"]) == d["max_history"]
-    assert int(consts["RT_TEMPORAL_DEFAULT_REUSE_SPECULAR"]) == d["reuse_specular"]
-    assert np.float32(consts["RT_TEMPORAL_DEFAULT_POSITION_TOLERANCE"]) == np.float32(d["position_tolerance"])
-    assert np.float32(consts["RT_TEMPORAL_DEFAULT_NORMAL_MIN_DOT"]) == np.float32(d["normal_min_dot"])
-    assert set(d) == {n for n, _ in rt.TemporalParams._fields_}
+    # (the header's constants and defaults against the binding's: tests/test_host_and_abi.py::test_constants_equal_the_header)
+    assert abi_header.DEFINES["RT_TEMPORAL_HISTORY_BYTES"] == rt.TEMPORAL_HISTORY_BYTES == 20
+    assert set(rt.TEMPORAL_DEFAULTS) == {n for n, _ in rt.TemporalParams._fields_}
     assert temporal_model.hit_record_dtype == rt.hit_record_dtype and temporal_model.camera_dtype == rt.camera_dtype
     for fn in ("temporal_params", "alloc_temporal_history", "temporal_check", "temporal_accumulate", "denoise_history"):
         assert callable(getattr(rt, fn)), fn

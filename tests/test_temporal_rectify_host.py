@@ -2,17 +2,15 @@
 its hand-worked cases and against both parent models, the new symbols in header, library and binding, rt_temporal_rectify_check, and
 the refusals of the entry point that come before any device call."""
 import ctypes as C
-import os
-import re
 
 import numpy as np
 import pytest
 
+import abi_header
 import temporal_rectify_model as trm
 
 tm, tmm = trm.tm, trm.tmm
 F = np.float32
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NEW = ("rt_temporal_rectify_check", "rt_temporal_accumulate_rectified")
 
 
@@ -86,24 +84,18 @@ def test_neff_never_rises_and_untaken_pixels_are_untouched(seed):
 
 
 def test_header_library_and_binding_name_the_new_symbols(rt):
-    hdr = open(os.path.join(ROOT, "include", "rt_amd.h")).read()
-    declared = set(re.findall(r"^int (rt_[a-z0-9_]+)\(", hdr, re.M))
-    L = rt.lib()
-    for name in NEW:
-        assert name in declared and name in rt.SYMBOLS and hasattr(L, name), name
-    i, vp = C.c_int, C.c_void_p
-    assert rt.SYMBOLS["rt_temporal_rectify_check"] == (i, [C.POINTER(rt.TemporalRectify)])
-    assert rt.SYMBOLS["rt_temporal_accumulate_rectified"] == (i, [vp] * 8 + [i, i, C.POINTER(rt.TemporalParams), C.POINTER(rt.TemporalRectify), vp])
+    abi_header.check_bound(rt, NEW)
+    assert all(abi_header.PROTOTYPES[name][0] is C.c_int for name in NEW)
+    abi_header.check_struct(rt.TemporalRectify, "rt_temporal_rectify")
     assert C.sizeof(rt.TemporalRectify) == 12
     for name in ("TemporalRectify", "temporal_rectify", "temporal_rectify_check", "temporal_accumulate_rectified"):
         assert hasattr(rt, name), name
     for key in ("RADIUS", "MIN_COUNT", "GAMMA"):
-        m = re.search(r"#define RT_TEMPORAL_RECTIFY_DEFAULT_%s (\S+)" % key, hdr)
-        assert m and float(m.group(1).rstrip("f")) == rt.TEMPORAL_RECTIFY_DEFAULTS[key.lower()], key
+        assert abi_header.DEFINES["RT_TEMPORAL_RECTIFY_DEFAULT_" + key] == rt.TEMPORAL_RECTIFY_DEFAULTS[key.lower()], key
     d = rt.temporal_rectify()
     assert (d.radius, d.min_count) == (rt.TEMPORAL_RECTIFY_DEFAULTS["radius"], rt.TEMPORAL_RECTIFY_DEFAULTS["min_count"])
     assert rt.temporal_rectify_check(d) and rt.temporal_rectify(gamma=0.0).gamma == 0.0
-    assert L.rt_abi_version() == 6 and "#define RT_ABI_VERSION 6" in hdr
+    assert rt.lib().rt_abi_version() == 6 and abi_header.DEFINES["RT_ABI_VERSION"] == 6
 
 
 BAD = [dict(radius=0), dict(radius=3), dict(min_count=1), dict(radius=1, min_count=10), dict(radius=2, min_count=26), dict(gamma=-1.0),
