@@ -1,7 +1,7 @@
 // main.cpp — host program of the MI355X render path; the counterpart of the reference's main() (main.cu:347-477).
 //
 // Same sequence, same stderr lines, same output modes (0 = PPM to stdout, 1 = none, 3 = output.ppm; mode 2, the
-// OpenGL viewer, is out of scope), same error convention (message + exit code 99), but every step goes through the
+// OpenGL viewer, is out of scope here: rt_sequence mode=progressive, host/sequence.cpp, is its headless counterpart), same error convention (message + exit code 99), but every step goes through the
 // C-ABI of include/rt_amd.h.  The reference's compile-time knobs become optional trailing arguments:
 //   rt_main [output_mode] [NUM_SPHERES] [nx] [ny] [ns] [USE_OCTREE 0|1] [SPHERES_PER_LEAF] [SPHERE_RADIUS] [USE_FP16 0|1] [BUILD_ON_GPU 0|1]
 // with the reference's values as defaults (main.cu:22-24, :348-350; acceleration_structure.h:15).  BUILD_ON_GPU 1 replaces
