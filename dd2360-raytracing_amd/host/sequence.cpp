@@ -4,8 +4,9 @@
 // of 3 bytes a pixel to the host.  mode=progressive is the reference's pass-by-pass viewer (main.cu:222-318, output mode 2) without
 // the window: one sample a pass, every `every`-th pass filtered, quantised and written.
 //
-// A second host program on top of include/rt_amd.h: every render step goes through the C-ABI, nothing is added to it.  The one kernel
-// here, k_animate, is the viewer's own: it writes a frame's geometry from the created list by the rule of rt_sequence_motion.hpp.
+// A second host program on top of include/rt_amd.h: every render step goes through the C-ABI, nothing is added to it.  The two kernels
+// here are the viewer's own: k_animate writes a frame's geometry from the created list by the rule of rt_sequence_motion.hpp, k_upscale
+// (upscale > 1) the shown frame from a smaller rendered one by the rule of rt_sequence_upscale.hpp.
 // Errors follow rt_main: a message on stderr and exit code 99.  Arguments are key=value tokens in any order; an unknown key, a
 // malformed value or a refused combination ends the program BEFORE rt_device_check, so no device is touched.
 //
@@ -24,8 +25,12 @@
 //   passes every    progressive: passes in all; every `every`-th pass and the last one are shown       (10 1)
 //   out             file prefix: <out>%04d.ppm, binary P6; out=none writes nothing                      (frame_ | pass_)
 //   timing          animation, 1: a table of the stages' device times and the wall time a frame, frame 0 left out (0)
+//   upscale         1: the frame is shown as it is rendered.  2..4: samples, history and filter run at nx x ny, the shown frame of
+//                   upscale*nx x upscale*ny pixels is rebuilt from it and first-hit guides of both sizes (rt_sequence_upscale.hpp,
+//                   kernel k_upscale); levels, copy and file have the shown size.  progressive: needs levels >= 1       (1)
 // Binary16 (fp16=1) is refused: the calls of the loop are fp32 only.
 #include <cmath>
+#include <cstddef>
 #include <cstdint>
 #include <cstdio>
 #include <cstdlib>
@@ -37,9 +42,12 @@
 #include <hip/hip_runtime.h>
 #include "../../include/rt_amd.h"
 #include "rt_sequence_motion.hpp"
+#include "rt_sequence_upscale.hpp"
 
 static_assert(RT_SEQ_MAT_NONE == RT_MAT_NONE, "rt_sequence_motion.hpp restates RT_MAT_NONE");
 static_assert(sizeof(rt_seq_geom) == 16, "a geometry record is 4 floats");
+static_assert(sizeof(rt_seq_hit) == sizeof(rt_hit_record) && sizeof(rt_seq_hit) == 32, "rt_sequence_upscale.hpp restates rt_hit_record");
+static_assert(offsetof(rt_seq_hit, sphere) == offsetof(rt_hit_record, sphere), "rt_sequence_upscale.hpp restates rt_hit_record");
 
 #define checkHipErrors(val) check_hip((int)(val), #val, __FILE__, __LINE__)
 static void check_hip(int result, char const* const func, const char* const file, int const line) {
@@ -56,6 +64,25 @@ __global__ __launch_bounds__(256) void k_animate(rt_seq_geom* out, const rt_seq_
     const int i = (int)blockIdx.x * 256 + (int)threadIdx.x;                  // (n < 2^31 - 256, checked with the arguments)
     if (i >= n) return;
     out[i] = rt_seq_move(base[i], (int)dir[i], f, move_step);
+}
+
+// The shown frame of s*nx x s*ny pixels from the low frame by the rule of rt_sequence_upscale.hpp: one lane a high pixel, 16x16 pixels
+// a block, the blocks of a row one after the other in a one-dimensional grid (a frame of few columns has more rows of blocks than a
+// grid's second dimension holds).  A lane reads one word of its own high guide, the sphere word and the 12 bytes of colour of up to four
+// low pixels — the lanes of a block share (16/s + 2)^2 of them, which the vector cache serves — and stores 12 bytes.  out holds
+// 3 * s*nx * s*ny floats and is none of the inputs; c, g hold the low frame, G the high guides.
+__global__ __launch_bounds__(256) void k_upscale(float* out, const float* c, const rt_seq_hit* g, const rt_seq_hit* G, int nx, int ny, int s,
+                                                 int blocks_x) {
+    const int NX = s * nx, NY = s * ny;                                      // (both within int, checked with the arguments)
+    const int by = (int)(blockIdx.x / (unsigned)blocks_x), bx = (int)(blockIdx.x - (unsigned)by * (unsigned)blocks_x);
+    const int I = bx * 16 + (int)threadIdx.x, J = by * 16 + (int)threadIdx.y;
+    if (I >= NX || J >= NY) return;
+    const size_t P = (size_t)J * (size_t)NX + (size_t)I;
+    float px[3];
+    (void)rt_seq_upscale_pixel(c, g, nx, ny, s, I, J, G[P].sphere, px);
+    out[P * 3] = px[0];
+    out[P * 3 + 1] = px[1];
+    out[P * 3 + 2] = px[2];
 }
 
 namespace {
@@ -76,7 +103,7 @@ struct Options {
     int levels = RT_DENOISE_VAR_DEFAULT_LEVELS;
     float sigma_variance = RT_DENOISE_VAR_DEFAULT_SIGMA_VARIANCE;
     int passes = 10, every = 1;
-    int timing = 0, fp16 = 0;
+    int timing = 0, fp16 = 0, upscale = 1;
     bool out_given = false;
 };
 
@@ -120,7 +147,7 @@ Options parse(int argc, char** argv) {
         KEY("reuse_specular", o.temporal.reuse_specular)
         KEY("rect_radius", o.rectify.radius) KEY("rect_min_count", o.rectify.min_count) KEY("gamma", o.rectify.gamma)
         KEY("levels", o.levels) KEY("sigma_variance", o.sigma_variance) KEY("passes", o.passes) KEY("every", o.every)
-        KEY("timing", o.timing) KEY("fp16", o.fp16)
+        KEY("timing", o.timing) KEY("fp16", o.fp16) KEY("upscale", o.upscale)
 #undef KEY
         refuse(key, "unknown key");
     }
@@ -136,6 +163,14 @@ void validate(Options& o) {
     if (o.nx < 1) refuse("nx", "needs a positive size");
     if (o.ny < 1) refuse("ny", "needs a positive size");
     if (o.spl < 1) refuse("spl", "needs at least one sphere a leaf");
+    if (o.upscale < 1 || o.upscale > RT_SEQ_UPSCALE_MAX) refuse("upscale", "needs 1 .. " + std::to_string(RT_SEQ_UPSCALE_MAX) + " (1 = the frame is shown as it is rendered)");
+    if (o.upscale > 1) {
+        if (o.nx > INT32_MAX / o.upscale || o.ny > INT32_MAX / o.upscale) refuse("upscale", "upscale * nx or upscale * ny is beyond int");
+        const rt_levels_params shown = {RT_DENOISE_INPUT_GAMMA, 1, RT_LEVELS_RGB8, 1};
+        if (rt_frame_levels_check(o.upscale * o.nx, o.upscale * o.ny, RT_PRECISION_FP32, &shown))
+            refuse("upscale", "rt_frame_levels_check refuses a shown frame of upscale * nx x upscale * ny pixels");
+        if (progressive && o.levels == 0) refuse("upscale", "the rule blends gamma values: progressive passes with levels=0 hold sample sums, needs levels >= 1");
+    }
     if (o.timing < 0 || o.timing > 1) refuse("timing", "is 0 or 1");
     if (!o.out_given) o.out = progressive ? "pass_" : "frame_";
     if (o.levels < 0 || o.levels > RT_DENOISE_MAX_LEVELS) refuse("levels", "needs 0 .. " + std::to_string(RT_DENOISE_MAX_LEVELS));
@@ -202,8 +237,20 @@ void write_p6(const std::string& prefix, int index, int nx, int ny, const unsign
     }
 }
 
-const char* const STAGES[] = {"animate + setters", "tree rebuild", "guides", "begin", "spend", "accumulate", "filter", "levels + copy"};
-enum { ANIMATE, TREE, GUIDES, BEGIN, SPEND, ACCUMULATE, FILTER, LEVELS, NSTAGES };
+// (the upscale stage and its line exist for upscale > 1 only)
+const char* const STAGES[] = {"animate + setters", "tree rebuild", "guides", "begin", "spend", "accumulate", "filter", "upscale", "levels + copy"};
+enum { ANIMATE, TREE, GUIDES, BEGIN, SPEND, ACCUMULATE, FILTER, UPSCALE, LEVELS, NSTAGES };
+
+// the high guides of the same world, tree and camera, then the shown frame from the low one (rt_sequence_upscale.hpp)
+void upscale_frame(float* d_up, const float* d_show, const rt_hit_record* d_hits, rt_hit_record* d_hits_up, const rt_world* world, const rt_octree* tree,
+                   int nx, int ny, int s, bool trace_guides, hipStream_t stream) {
+    const int NX = s * nx, NY = s * ny;
+    if (trace_guides) checkHipErrors(rt_render_guides(world, tree, NX, NY, d_hits_up, stream));
+    const unsigned blocks_x = (unsigned)((NX + 15) / 16), blocks_y = (unsigned)((NY + 15) / 16);   // at most 2^30 pixels: below 2^31 blocks
+    hipLaunchKernelGGL(k_upscale, dim3(blocks_x * blocks_y), dim3(16, 16), 0, stream, d_up, d_show, reinterpret_cast<const rt_seq_hit*>(d_hits),
+                       reinterpret_cast<const rt_seq_hit*>(d_hits_up), nx, ny, s, (int)blocks_x);
+    checkHipErrors(hipGetLastError());
+}
 
 struct Scene {
     std::vector<rt_sphere> list;
@@ -244,6 +291,8 @@ int run_animation(const Options& o) {
     const rt_denoise_var_params filter = {o.levels, RT_DENOISE_VAR_DEFAULT_NORMAL_POW_LOG2, RT_DENOISE_VAR_DEFAULT_PREFILTER,
                                           RT_DENOISE_VAR_DEFAULT_SIGMA_POSITION, o.sigma_variance};
     const rt_levels_params lp = {RT_DENOISE_INPUT_GAMMA, 1, RT_LEVELS_RGB8, 1};
+    const int s = o.upscale, NX = s * o.nx, NY = s * o.ny;                    // the shown frame; upscale=1: the rendered one
+    const size_t shown_px = (size_t)NX * NY;
 
     Scene S = create_scene(o);
     rt_world* const world = S.world;
@@ -257,7 +306,9 @@ int run_animation(const Options& o) {
     char* d_state = device_alloc<char>(px * RT_ADAPTIVE_STATE_BYTES);
     int32_t* d_spp = device_alloc<int32_t>(px);
     char* d_work = device_alloc<char>(px * RT_DENOISE_WORK_BYTES);
-    unsigned char* d_levels = device_alloc<unsigned char>(px * 3);
+    unsigned char* d_levels = device_alloc<unsigned char>(shown_px * 3);
+    float* d_up = s > 1 ? device_alloc<float>(shown_px * 3) : nullptr;
+    rt_hit_record* d_hits_up = s > 1 ? device_alloc<rt_hit_record>(shown_px) : nullptr;
     char* d_hist[2];
     rt_hit_record* d_hits[2];
     rt_seq_geom* d_geom[2];
@@ -270,7 +321,7 @@ int run_animation(const Options& o) {
     signed char* d_dir = device_alloc<signed char>(o.n);
     unsigned char* h_levels = nullptr;
     int32_t* h_spp = nullptr;
-    checkHipErrors(hipHostMalloc(reinterpret_cast<void**>(&h_levels), px * 3));
+    checkHipErrors(hipHostMalloc(reinterpret_cast<void**>(&h_levels), shown_px * 3));
     checkHipErrors(hipHostMalloc(reinterpret_cast<void**>(&h_spp), px * sizeof(int32_t)));
 
     // the motion mask, from the created list; the created geometry is the base of every frame and frame 0's own
@@ -340,10 +391,16 @@ int run_animation(const Options& o) {
         mark(FILTER, 0);
         if (o.levels > 0) checkHipErrors(rt_denoise_history(d_show, fb, o.nx, o.ny, d_hits[c], d_hist[c], &filter, d_work, stream));
         mark(FILTER, 1);
-        // 8. what leaves the device: 3 bytes a pixel (and the sample counts, for the report)
+        // 8. upscale > 1: the shown frame from the filtered low one and the guides of both sizes, traced anew every frame
+        if (s > 1) {
+            mark(UPSCALE, 0);
+            upscale_frame(d_up, d_show, d_hits[c], d_hits_up, world, tree, o.nx, o.ny, s, true, stream);
+            mark(UPSCALE, 1);
+        }
+        // 9. what leaves the device: 3 bytes a shown pixel (and the sample counts, for the report)
         mark(LEVELS, 0);
-        checkHipErrors(rt_frame_levels(d_levels, d_show, o.nx, o.ny, RT_PRECISION_FP32, &lp, stream));
-        checkHipErrors(hipMemcpyAsync(h_levels, d_levels, px * 3, hipMemcpyDeviceToHost, stream));
+        checkHipErrors(rt_frame_levels(d_levels, s > 1 ? d_up : d_show, NX, NY, RT_PRECISION_FP32, &lp, stream));
+        checkHipErrors(hipMemcpyAsync(h_levels, d_levels, shown_px * 3, hipMemcpyDeviceToHost, stream));
         mark(LEVELS, 1);
         checkHipErrors(hipMemcpyAsync(h_spp, d_spp, px * sizeof(int32_t), hipMemcpyDeviceToHost, stream));
         checkHipErrors(hipStreamSynchronize(stream));
@@ -351,14 +408,17 @@ int run_animation(const Options& o) {
 
         double total = 0.0;
         for (size_t p = 0; p < px; p++) total += h_spp[p];
-        std::cerr << "frame " << f << ": mean samples per pixel: " << total / (double)px << "\n";
-        if (o.out != "none") write_p6(o.out, f, o.nx, o.ny, h_levels);
+        std::cerr << "frame " << f << ": mean samples per pixel: " << total / (double)px;   // samples are taken at the low size only
+        if (s > 1) std::cerr << " (per low pixel, " << o.nx << "x" << o.ny << ")";
+        std::cerr << "\n";
+        if (o.out != "none") write_p6(o.out, f, NX, NY, h_levels);
         if (o.timing && f > 0) {
-            for (int s = 0; s < NSTAGES; s++) {
+            for (int st = 0; st < NSTAGES; st++) {
+                if (st == UPSCALE && s == 1) continue;
                 float ms = 0.f;
-                checkHipErrors(hipEventElapsedTime(&ms, ev[s][0], ev[s][1]));
-                sum_ms[s] += ms;
-                if (ms > max_ms[s]) max_ms[s] = ms;
+                checkHipErrors(hipEventElapsedTime(&ms, ev[st][0], ev[st][1]));
+                sum_ms[st] += ms;
+                if (ms > max_ms[st]) max_ms[st] = ms;
             }
             wall_sum += wall_ms;
             if (wall_ms > wall_max) wall_max = wall_ms;
@@ -371,12 +431,14 @@ int run_animation(const Options& o) {
         const int m = o.frames - 1;
         double stages = 0.0;
         char line[160];
-        snprintf(line, sizeof line, "timing: %dx%d, n=%d, frames 1..%d (frame 0 left out)\n", o.nx, o.ny, o.n, m);
+        if (s > 1) snprintf(line, sizeof line, "timing: %dx%d shown at %dx%d, n=%d, frames 1..%d (frame 0 left out)\n", o.nx, o.ny, NX, NY, o.n, m);
+        else snprintf(line, sizeof line, "timing: %dx%d, n=%d, frames 1..%d (frame 0 left out)\n", o.nx, o.ny, o.n, m);
         std::cerr << line;
-        for (int s = 0; s < NSTAGES; s++) {
-            snprintf(line, sizeof line, "timing: %-18s mean %9.3f ms  max %9.3f ms\n", STAGES[s], sum_ms[s] / m, max_ms[s]);
+        for (int st = 0; st < NSTAGES; st++) {
+            if (st == UPSCALE && s == 1) continue;
+            snprintf(line, sizeof line, "timing: %-18s mean %9.3f ms  max %9.3f ms\n", STAGES[st], sum_ms[st] / m, max_ms[st]);
             std::cerr << line;
-            stages += sum_ms[s] / m;
+            stages += sum_ms[st] / m;
         }
         snprintf(line, sizeof line, "timing: %-18s mean %9.3f ms\n", "sum of stages", stages);
         std::cerr << line;
@@ -394,6 +456,10 @@ int run_animation(const Options& o) {
     void* const device_buffers[] = {fb, d_rand, d_state, d_spp, d_work, d_levels, d_hist[0], d_hist[1], d_hits[0], d_hits[1], d_geom[0], d_geom[1], d_base, d_dir};
     for (void* p : device_buffers) checkHipErrors(hipFree(p));
     if (d_show != fb) checkHipErrors(hipFree(d_show));
+    if (s > 1) {
+        checkHipErrors(hipFree(d_up));
+        checkHipErrors(hipFree(d_hits_up));
+    }
     checkHipErrors(hipHostFree(h_levels));
     checkHipErrors(hipHostFree(h_spp));
     checkHipErrors(hipStreamDestroy(stream));
@@ -413,15 +479,20 @@ int run_progressive(const Options& o) {
     rt_rand_state* d_rand = device_alloc<rt_rand_state>(px);
     rt_hit_record* d_hits = device_alloc<rt_hit_record>(px);
     char* d_work = device_alloc<char>(px * RT_DENOISE_WORK_BYTES);
-    unsigned char* d_levels = device_alloc<unsigned char>(px * 3);
+    const int up = o.upscale, NX = up * o.nx, NY = up * o.ny;                // the shown frame; upscale=1: the rendered one
+    const size_t shown_px = (size_t)NX * NY;
+    unsigned char* d_levels = device_alloc<unsigned char>(shown_px * 3);
+    float* d_up = up > 1 ? device_alloc<float>(shown_px * 3) : nullptr;
+    rt_hit_record* d_hits_up = up > 1 ? device_alloc<rt_hit_record>(shown_px) : nullptr;
     unsigned char* h_levels = nullptr;
-    checkHipErrors(hipHostMalloc(reinterpret_cast<void**>(&h_levels), px * 3));
+    checkHipErrors(hipHostMalloc(reinterpret_cast<void**>(&h_levels), shown_px * 3));
 
     rt_octree* tree = nullptr;
     checkHipErrors(rt_build_octree_gpu(world, o.spl, &tree, stream));
     report_drops(tree);
     checkHipErrors(rt_render_init(o.nx, o.ny, d_rand, whole, stream));
     checkHipErrors(rt_render_guides(world, tree, o.nx, o.ny, d_hits, stream));   // once: nothing moves
+    if (up > 1) checkHipErrors(rt_render_guides(world, tree, NX, NY, d_hits_up, stream));   // the shown frame's, once as well
     for (int s = 1; s <= o.passes; s++) {
         checkHipErrors(rt_render_progressive(fb, o.nx, o.ny, s, world, d_rand, tree, whole, stream));
         if (s % o.every != 0 && s != o.passes) continue;
@@ -432,11 +503,12 @@ int run_progressive(const Options& o) {
             checkHipErrors(rt_denoise(d_show, fb, o.nx, o.ny, d_hits, &dp, d_work, stream));
             lp.input = RT_DENOISE_INPUT_GAMMA;                                   // the filter wrote the gamma frame
         }
-        checkHipErrors(rt_frame_levels(d_levels, d_show, o.nx, o.ny, RT_PRECISION_FP32, &lp, stream));
-        checkHipErrors(hipMemcpyAsync(h_levels, d_levels, px * 3, hipMemcpyDeviceToHost, stream));
+        if (up > 1) upscale_frame(d_up, d_show, d_hits, d_hits_up, world, tree, o.nx, o.ny, up, false, stream);   // (levels > 0: d_show is the gamma frame)
+        checkHipErrors(rt_frame_levels(d_levels, up > 1 ? d_up : d_show, NX, NY, RT_PRECISION_FP32, &lp, stream));
+        checkHipErrors(hipMemcpyAsync(h_levels, d_levels, shown_px * 3, hipMemcpyDeviceToHost, stream));
         checkHipErrors(hipStreamSynchronize(stream));
         std::cerr << "pass " << s << " shown\n";
-        if (o.out != "none") write_p6(o.out, s, o.nx, o.ny, h_levels);
+        if (o.out != "none") write_p6(o.out, s, NX, NY, h_levels);
     }
 
     checkHipErrors(hipStreamSynchronize(stream));
@@ -445,6 +517,10 @@ int run_progressive(const Options& o) {
     void* const device_buffers[] = {fb, d_rand, d_hits, d_work, d_levels};
     for (void* p : device_buffers) checkHipErrors(hipFree(p));
     if (d_show != fb) checkHipErrors(hipFree(d_show));
+    if (up > 1) {
+        checkHipErrors(hipFree(d_up));
+        checkHipErrors(hipFree(d_hits_up));
+    }
     checkHipErrors(hipHostFree(h_levels));
     checkHipErrors(hipStreamDestroy(stream));
     return 0;
@@ -457,7 +533,9 @@ int main(int argc, char** argv) {
     validate(o);
     const bool progressive = o.mode == "progressive";
     std::cerr << "rt_sequence: " << o.mode << ", " << o.nx << "x" << o.ny << ", " << o.n << " spheres of radius " << o.radius << ", "
-              << (progressive ? o.passes : o.frames) << (progressive ? " passes" : " frames") << "\n";
+              << (progressive ? o.passes : o.frames) << (progressive ? " passes" : " frames");
+    if (o.upscale > 1) std::cerr << ", shown at " << o.upscale * o.nx << "x" << o.upscale * o.ny;
+    std::cerr << "\n";
     checkHipErrors(rt_device_check(nullptr));
     const int rc = progressive ? run_progressive(o) : run_animation(o);
     (void)hipDeviceReset();
