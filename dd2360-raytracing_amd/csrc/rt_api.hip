@@ -854,7 +854,7 @@ static int begin_counters(rt_render_ctx& C, const RenderArgs& A, SchedAction act
 static bool feedback_gate(const RenderArgs& A, const rt_world* world, const rt_octree* d_octree, int ns) {
     const int min_ns = (int)tune_value("RT_FEEDBACK_MIN_NS", (float)RT_FEEDBACK_MIN_NS);
     const bool half = world->precision == RT_PRECISION_FP16;
-    return sched_feedback_gate(ns, min_ns < 16 ? 16 : min_ns, half ? 0 : render_variant_of(d_octree != nullptr, A.tree.acc), half);
+    return sched_feedback_gate(ns, min_ns < 16 ? 16 : min_ns, half ? kVariantList : render_variant(d_octree != nullptr, A.tree.acc), half);
 }
 static bool feedback_enabled() { return tune_value("RT_SCHED_FEEDBACK", (float)RT_SCHED_FEEDBACK) != 0.f; }
 // the scheduling pass of rt_render (ns >= 4): pilot, tile order and — from 16 samples — the long chains and the sorted tail.
@@ -1445,7 +1445,7 @@ int rt_split_balanced(rt_render_ctx* ctx, const rt_world* world, const rt_octree
     A.tree = tree_args(d_octree);
     const bool half = world->precision == RT_PRECISION_FP16;
     RT_TRY(hipMemsetAsync(C.d_work, 0, sizeof(int) * (size_t)tiles * 2, st));
-    if (half) RT_TRY(launch_pilot_h(A, d_octree != nullptr, C.d_cost, st));
+    if (half) RT_TRY(launch_pilot_h(A, d_octree != nullptr, C.d_cost, nullptr, st));
     else RT_TRY(launch_pilot(A, d_octree != nullptr, C.d_cost, nullptr, C.d_work, st));
     std::vector<int32_t> cost, work;
     try { cost.resize((size_t)tiles); work.resize((size_t)tiles * 2); } catch (const std::bad_alloc&) { return RT_ENOMEM; }

@@ -25,6 +25,8 @@
 // so their single rounding gives the two-step form's bits (rt_sampling.h: checked for all 2^32 draws).
 #include <hip/hip_runtime.h>
 #include <float.h>
+#include <cstdio>
+#include <type_traits>
 #include "rt_device.h"
 #include "rt_launch.h"
 #include "rt_tuning.h"
@@ -1743,17 +1745,27 @@ __global__ __launch_bounds__(256) void k_guides(RenderArgs A, long long n, rt_hi
 }
 
 // ---------------------------------------------------------------------------------------------------- launchers
-// LDS of a block of the tree kernels: the nodes, then one WalkLds per wave
-static size_t tree_lds_bytes(int n_nodes, bool pool = false) { return (size_t)n_nodes * sizeof(DevNode) + (pool ? 4 * sizeof(WalkLds) + kHotSlots * sizeof(float4) : 0); }
+// LDS of a block of a tree variant's kernels: the nodes, then — pooled walks — one WalkLds per wave and the hot spheres
+static size_t variant_lds_bytes(int n_nodes, int variant) {
+    return (size_t)n_nodes * sizeof(DevNode) + (variant_pooled(variant) ? 4 * sizeof(WalkLds) + kHotSlots * sizeof(float4) : 0);
+}
 
-// blocks the chip holds at once for one render kernel variant (occupancy query, cached); the persistent grid is never
-// larger than that, and never larger than the work
-template <class K> static unsigned resident_blocks(K kernel, size_t lds) {
-    int dev = 0, cus = 0, per_cu = 0;
-    if (hipGetDevice(&dev) != hipSuccess) return 1024u;
-    if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus <= 0) return 1024u;
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kernel, 256, lds) != hipSuccess || per_cu <= 0) per_cu = 4;
-    return (unsigned)(cus * per_cu);
+// blocks of the persistent grid of k_render<TREE, MODE, COOPG> for this launch: what the chip holds (resident_blocks), never more than the work
+template <bool TREE, int MODE, int COOPG>
+static unsigned grid_blocks(const RenderArgs& A, size_t lds) {
+    const unsigned need = (unsigned)((A.n_local_tiles + 3) / 4);
+    // the occupancy query costs as much host time as the launch: remembered per thread for the last (device, LDS size) —
+    // a progressive loop issues the same launch hundreds of times
+    thread_local int c_dev = -1; thread_local size_t c_lds = 0; thread_local unsigned c_cap = 0;
+    int dev = 0;
+    if (hipGetDevice(&dev) != hipSuccess) dev = -2;
+    if (dev != c_dev || lds != c_lds || c_cap == 0) { c_cap = resident_blocks((const void*)k_render<TREE, MODE, COOPG>, lds); c_dev = dev; c_lds = lds; }
+    return need < c_cap ? need : c_cap;
+}
+template <bool TREE, int MODE, int COOPG>
+static hipError_t launch_k_render(const RenderArgs& A, size_t lds, hipStream_t st) {
+    hipLaunchKernelGGL((k_render<TREE, MODE, COOPG>), dim3(grid_blocks<TREE, MODE, COOPG>(A, lds)), dim3(256), lds, st, A);
+    return hipGetLastError();
 }
 
 // The hitable_list instantiations live in their own translation unit (rt_kernels_list.hip = this file with RT_TU_LIST):
@@ -1761,12 +1773,7 @@ template <class K> static unsigned resident_blocks(K kernel, size_t lds) {
 // the two are compiled with different flags (Makefile).  The contract unit holds its own contracted k_render<false, 0|1, 1>.
 #ifdef RT_TU_HAS_LIST
 hipError_t launch_render_list(const RenderArgs& A, int mode, hipStream_t st) {
-    const unsigned need = (unsigned)((A.n_local_tiles + 3) / 4);
-    const unsigned cap = mode == 0 ? resident_blocks(k_render<false, 0, 1>, 0) : resident_blocks(k_render<false, 1, 1>, 0);
-    const unsigned blocks = need < cap ? need : cap;
-    if (mode == 0) hipLaunchKernelGGL((k_render<false, 0, 1>), dim3(blocks), dim3(256), 0, st, A);
-    else hipLaunchKernelGGL((k_render<false, 1, 1>), dim3(blocks), dim3(256), 0, st, A);
-    return hipGetLastError();
+    return mode == 0 ? launch_k_render<false, 0, 1>(A, 0, st) : launch_k_render<false, 1, 1>(A, 0, st);
 }
 #ifndef RT_TU_CONTRACT
 hipError_t launch_tile_cost_list(const RenderArgs& A, unsigned blocks, int* cost, unsigned char* pilot, hipStream_t st) {
@@ -1781,56 +1788,28 @@ hipError_t launch_guides_list(const RenderArgs& A, unsigned blocks, long long n,
     hipLaunchKernelGGL((k_guides<false>), dim3(blocks), dim3(256), 0, st, A, n, out);
     return hipGetLastError();
 }
-hipError_t launch_render_adaptive_list(const RenderArgs& A, hipStream_t st) {
-    const unsigned need = (unsigned)((A.n_local_tiles + 3) / 4);
-    const unsigned cap = resident_blocks(k_render<false, 2, 1>, 0);
-    hipLaunchKernelGGL((k_render<false, 2, 1>), dim3(need < cap ? need : cap), dim3(256), 0, st, A);
-    return hipGetLastError();
-}
+hipError_t launch_render_adaptive_list(const RenderArgs& A, hipStream_t st) { return launch_k_render<false, 2, 1>(A, 0, st); }
 #endif
 #endif
 
 #ifndef RT_TU_LIST
 // ---- the main unit and the contract unit: launch_render and what it needs
-// Which k_render instantiation a call launches — the ONE place that decides (launch_render and rt_render_kernel_name):
-// 0 = k_render<false,MODE,1> (list scan), 1 = k_render<true,MODE,1> (per-lane walk: trees without a candidate grid, reference
-// traversal), 4 = k_render<true,MODE,4> (sparse grids: walk_pool), 2 = k_render<true,MODE,2> (dense grids: walk_pool_dense) —
-// render (MODE 0) and render_progressive (MODE 1) walk the same way (rt_accel.h: coop_groups)
-static int render_variant(bool tree, int mode, const DevAccel& acc) {
-    (void)mode;
-    if (!tree) return 0;
-    if (acc.enabled) return acc.coop_groups >= 4 ? (acc.solo_chains ? 5 : 4) : 2;
-    return 1;
+// The ONE ladder from a tree variant chosen at run time (render_variant; never kVariantList) to the kernels' template argument:
+// f is called with a std::integral_constant<int, COOPG> and instantiates what it launches.
+template <class F> static auto with_walk(int variant, F&& f) {
+    if (variant == kVariantSolo) return f(std::integral_constant<int, kVariantSolo>{});
+    if (variant == kVariantSparse) return f(std::integral_constant<int, kVariantSparse>{});
+    if (variant == kVariantDense) return f(std::integral_constant<int, kVariantDense>{});
+    return f(std::integral_constant<int, kVariantTree>{});
 }
 
-// blocks of the persistent grid of k_render<true, MODE, COOPG> for this launch: what the chip holds, never more than the work
-template <int MODE, int COOPG>
-static unsigned tree_grid_blocks(const RenderArgs& A, size_t lds) {
-    const unsigned need = (unsigned)((A.n_local_tiles + 3) / 4);
-    // the occupancy query costs as much host time as the launch: remembered per thread for the last (device, LDS size) —
-    // a progressive loop issues the same launch hundreds of times
-    thread_local int c_dev = -1; thread_local size_t c_lds = 0; thread_local unsigned c_cap = 0;
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess) dev = -2;
-    if (dev != c_dev || lds != c_lds || c_cap == 0) { c_cap = resident_blocks(k_render<true, MODE, COOPG>, lds); c_dev = dev; c_lds = lds; }
-    const unsigned cap = c_cap;
-    return need < cap ? need : cap;
-}
-template <int MODE, int COOPG>
-static hipError_t launch_render_tree(const RenderArgs& A, size_t lds, hipStream_t st) {
-    hipLaunchKernelGGL((k_render<true, MODE, COOPG>), dim3(tree_grid_blocks<MODE, COOPG>(A, lds)), dim3(256), lds, st, A);
-    return hipGetLastError();
-}
-
+// (the mode ladder stays 0 | 1 here: the contract unit emits no k_render<*, 2, *>)
 hipError_t launch_render(const RenderArgs& A, bool tree, int mode, hipStream_t st) {
     if (A.n_local_tiles <= 0) return hipSuccess;
-    const int variant = render_variant(tree, mode, A.tree.acc);
-    if (variant == 0) return RT_TU_NAMESPACE::launch_render_list(A, mode, st);      // (qualified: the contract unit's own, not rt::'s that the argument's namespace offers too)
-    const size_t lds = tree_lds_bytes(A.tree.n_nodes, variant != 1);                       // (the variants with a pooled walk)
-    if (variant == 5) return mode == 0 ? launch_render_tree<0, 5>(A, lds, st) : launch_render_tree<1, 5>(A, lds, st);
-    if (variant == 4) return mode == 0 ? launch_render_tree<0, 4>(A, lds, st) : launch_render_tree<1, 4>(A, lds, st);
-    if (variant == 2) return mode == 0 ? launch_render_tree<0, 2>(A, lds, st) : launch_render_tree<1, 2>(A, lds, st);
-    return mode == 0 ? launch_render_tree<0, 1>(A, lds, st) : launch_render_tree<1, 1>(A, lds, st);
+    const int variant = render_variant(tree, A.tree.acc);
+    if (variant == kVariantList) return RT_TU_NAMESPACE::launch_render_list(A, mode, st);      // (qualified: the contract unit's own, not rt::'s that the argument's namespace offers too)
+    const size_t lds = variant_lds_bytes(A.tree.n_nodes, variant);
+    return with_walk(variant, [&](auto w) { return mode == 0 ? launch_k_render<true, 0, decltype(w)::value>(A, lds, st) : launch_k_render<true, 1, decltype(w)::value>(A, lds, st); });
 }
 #endif
 
@@ -1864,23 +1843,38 @@ hipError_t launch_render_init(rt_rand_state* rs, int max_x, int max_y, int part,
     return hipGetLastError();
 }
 
-const char* render_kernel_name(bool tree, int mode, const DevAccel& acc) {
-    switch (render_variant(tree, mode, acc)) {
-        case 0: return mode == 0 ? "k_render<false,0,1>" : "k_render<false,1,1>";
-        case 4: return mode == 0 ? "k_render<true,0,4>" : "k_render<true,1,4>";
-        case 5: return mode == 0 ? "k_render<true,0,5>" : "k_render<true,1,5>";
-        case 2: return mode == 0 ? "k_render<true,0,2>" : "k_render<true,1,2>";
-        default: return mode == 0 ? "k_render<true,0,1>" : "k_render<true,1,1>";
-    }
+// blocks the chip holds at once for one kernel of the render path in blocks of 256 (occupancy query; grid_blocks and
+// launch_render_h remember or repeat it): a persistent grid is never larger than that
+unsigned resident_blocks(const void* kernel, size_t lds) {
+    int dev = 0, cus = 0, per_cu = 0;
+    if (hipGetDevice(&dev) != hipSuccess) return 1024u;
+    if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus <= 0) return 1024u;
+    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kernel, 256, lds) != hipSuccess || per_cu <= 0) per_cu = 4;
+    return (unsigned)(cus * per_cu);
 }
 
-// tree_grid_blocks for a tree variant chosen at run time (the scheduling pass wants the grid's lanes before the launch)
-static unsigned render_grid_blocks(const RenderArgs& A, int variant, int mode) {
-    const size_t lds = tree_lds_bytes(A.tree.n_nodes, variant != 1);
-    if (variant == 5) return mode == 0 ? tree_grid_blocks<0, 5>(A, lds) : tree_grid_blocks<1, 5>(A, lds);
-    if (variant == 4) return mode == 0 ? tree_grid_blocks<0, 4>(A, lds) : tree_grid_blocks<1, 4>(A, lds);
-    if (variant == 2) return mode == 0 ? tree_grid_blocks<0, 2>(A, lds) : tree_grid_blocks<1, 2>(A, lds);
-    return mode == 0 ? tree_grid_blocks<0, 1>(A, lds) : tree_grid_blocks<1, 1>(A, lds);
+// Which walk a call launches — the ONE place that decides (rt_variant.h names the variants and says what each implies): trees with a
+// usable candidate grid take the pooled walk their grid's density asks for (rt_accel.h: coop_groups, solo_chains), every other tree
+// the per-lane walk.  rt_render, rt_render_progressive, rt_render_adaptive, the pilot, k_trace and k_guides all walk the same way.
+int render_variant(bool tree, const DevAccel& acc) {
+    if (!tree) return kVariantList;
+    if (acc.enabled) return acc.coop_groups >= 4 ? (acc.solo_chains ? kVariantSolo : kVariantSparse) : kVariantDense;
+    return kVariantTree;
+}
+
+// "k_render<TREE,MODE,COOPG>" as rocprofv3 prints it, from one format; the strings live as long as the library
+const char* render_kernel_name(bool tree, int mode, const DevAccel& acc) {
+    struct Names {
+        char s[2][kVariantSolo + 1][24];      // [mode][variant]
+        Names() { for (int m = 0; m < 2; ++m) for (int v = 0; v <= kVariantSolo; ++v) snprintf(s[m][v], sizeof s[m][v], "k_render<%s,%d,%d>", v == kVariantList ? "false" : "true", m, v == kVariantList ? 1 : v); }
+    };
+    static const Names names;
+    return names.s[mode == 0 ? 0 : 1][render_variant(tree, acc)];
+}
+
+// the lanes of rt_render's persistent grid on a tree variant (the scheduling pass wants them before the launch)
+static int render_grid_lanes(const RenderArgs& A, int variant) {
+    return 256 * (int)with_walk(variant, [&](auto w) { return grid_blocks<true, 0, decltype(w)::value>(A, variant_lds_bytes(A.tree.n_nodes, variant)); });
 }
 
 // the pilot pass alone: per tile the bounces (x 4) and — trees with a candidate grid — the grid entries its samples' walks pooled
@@ -1888,41 +1882,40 @@ hipError_t launch_pilot(const RenderArgs& A, bool tree, int* cost, unsigned char
     if (A.n_local_tiles <= 0) return hipSuccess;
     const long long per_block = 4 * (64 / (16 * RT_PILOT_SAMPLES));       // a wave covers 4 / RT_PILOT_SAMPLES tiles
     const unsigned blocks = (unsigned)((A.n_local_tiles + per_block - 1) / per_block);
+    const int variant = render_variant(tree, A.tree.acc);
+    if (variant == kVariantList) return launch_tile_cost_list(A, blocks, cost, pilot, st);
     // (the pilot paths walk the grid like the render kernel's waves do, through the wave's pool)
-    const int variant = render_variant(tree, 0, A.tree.acc);
-    if (variant == 5) hipLaunchKernelGGL((k_tile_cost<true, 5>), dim3(blocks), dim3(256), tree_lds_bytes(A.tree.n_nodes, true), st, A, cost, pilot, work);
-    else if (variant == 4) hipLaunchKernelGGL((k_tile_cost<true, 4>), dim3(blocks), dim3(256), tree_lds_bytes(A.tree.n_nodes, true), st, A, cost, pilot, work);
-    else if (variant == 2) hipLaunchKernelGGL((k_tile_cost<true, 2>), dim3(blocks), dim3(256), tree_lds_bytes(A.tree.n_nodes, true), st, A, cost, pilot, work);
-    else if (tree) hipLaunchKernelGGL((k_tile_cost<true, 1>), dim3(blocks), dim3(256), tree_lds_bytes(A.tree.n_nodes), st, A, cost, pilot, work);
-    else return launch_tile_cost_list(A, blocks, cost, pilot, st);
-    return hipGetLastError();
+    return with_walk(variant, [&](auto w) {
+        hipLaunchKernelGGL((k_tile_cost<true, decltype(w)::value>), dim3(blocks), dim3(256), variant_lds_bytes(A.tree.n_nodes, variant), st, A, cost, pilot, work);
+        return hipGetLastError();
+    });
 }
 
 hipError_t launch_tile_order(const RenderArgs& A, bool tree, int* cost, unsigned int* order, unsigned char* flags, unsigned int* long_list, hipStream_t st) {
     if (A.n_local_tiles <= 0) return hipSuccess;
     // flags: 64 bytes per local tile (one per pixel) followed by 16 per local tile (the pilot counts per 2x2 block) and 16 more (k_long_select)
     unsigned char* pilot = flags ? flags + (size_t)A.n_local_tiles * 64 : nullptr;
-    const int variant = render_variant(tree, 0, A.tree.acc);
+    const int variant = render_variant(tree, A.tree.acc);
+    const bool dense = variant_dense(variant);
     RenderArgs B = A;
-    B.n_lanes = tree ? (int)render_grid_blocks(A, variant, 0) * 256 : 0;      // (list scans keep the rate rule alone)
-    if (variant == 2 && A.f_inflight_dense > 0.f) B.f_inflight = A.f_inflight_dense;
-    B.head_sum = variant == 2 ? A.head_sum_dense : A.head_sum;
-    B.head_min_load = variant == 2 ? A.head_min_load : 0.f;
+    B.n_lanes = tree ? render_grid_lanes(A, variant) : 0;      // (list scans keep the rate rule alone)
+    if (dense && A.f_inflight_dense > 0.f) B.f_inflight = A.f_inflight_dense;
+    B.head_sum = dense ? A.head_sum_dense : A.head_sum;
+    B.head_min_load = dense ? A.head_min_load : 0.f;
     { const hipError_t e = launch_pilot(A, tree, cost, pilot, nullptr, st); if (e != hipSuccess) return e; }
     // (chains in waves of their own: the variant for very sparse grids)
-    return launch_select_and_order(B, cost, order, flags, long_list, st, 0, variant == 5 ? RT_PILOT_SOLO_SUM : 0x7fffffff);
+    return launch_select_and_order(B, cost, order, flags, long_list, st, 0, variant_solo_pilot(variant) ? RT_PILOT_SOLO_SUM : 0x7fffffff);
 }
 
-int render_variant_of(bool tree, const DevAccel& acc) { return render_variant(tree, 0, acc); }      // (for the host's gate: rt_sched_keep.h sched_feedback_gate)
-// the measured pass (rt_sched_keep.h "Feedback") of a launch on k_render<true,*,4> or <true,*,5>: launch_tile_order with the recorded
+// the measured pass (rt_sched_keep.h "Feedback") of a launch on a variant that records counts: launch_tile_order with the recorded
 // counts in the pilot's place.  extra: two words of the context ([0] the largest count, [1] the solo cap = waves / solo_cap_den).
 hipError_t launch_count_order(const RenderArgs& A, const unsigned short* iters, int* cost, unsigned int* order, unsigned char* flags, unsigned int* long_list,
                               float solo_frac, int solo_cap_den, unsigned int* extra, hipStream_t st) {
     if (A.n_local_tiles <= 0) return hipSuccess;
-    const int variant = render_variant(true, 0, A.tree.acc);
-    if ((variant != 4 && variant != 5) || !iters || !flags || !long_list) return hipErrorInvalidValue;
+    const int variant = render_variant(true, A.tree.acc);
+    if (!variant_records_counts(variant) || !iters || !flags || !long_list) return hipErrorInvalidValue;
     RenderArgs B = A;
-    B.n_lanes = (int)render_grid_blocks(A, variant, 0) * 256;
+    B.n_lanes = render_grid_lanes(A, variant);
     B.head_sum = A.head_sum; B.head_min_load = 0.f;
     { const hipError_t e = launch_count_cost(B, iters, cost, flags + (size_t)A.n_local_tiles * 64, st); if (e != hipSuccess) return e; }
     const CountedSelect cs{iters, solo_frac, solo_cap_den > 0 ? (unsigned int)(B.n_lanes / 64 / solo_cap_den) : 0u, extra};
@@ -1932,43 +1925,37 @@ hipError_t launch_count_order(const RenderArgs& A, const unsigned short* iters, 
 // one round of rt_render_adaptive: k_render<*, 2, *> of the variant rt_render would launch (the contracted arithmetic has no adaptive mode)
 hipError_t launch_render_adaptive(const RenderArgs& A, bool tree, hipStream_t st) {
     if (A.n_local_tiles <= 0) return hipSuccess;
-    const int variant = render_variant(tree, 0, A.tree.acc);
-    if (variant == 0) return launch_render_adaptive_list(A, st);
-    const size_t lds = tree_lds_bytes(A.tree.n_nodes, variant != 1);
-    if (variant == 5) return launch_render_tree<2, 5>(A, lds, st);
-    if (variant == 4) return launch_render_tree<2, 4>(A, lds, st);
-    if (variant == 2) return launch_render_tree<2, 2>(A, lds, st);
-    return launch_render_tree<2, 1>(A, lds, st);
+    const int variant = render_variant(tree, A.tree.acc);
+    if (variant == kVariantList) return launch_render_adaptive_list(A, st);
+    return with_walk(variant, [&](auto w) { return launch_k_render<true, 2, decltype(w)::value>(A, variant_lds_bytes(A.tree.n_nodes, variant), st); });
+}
+
+// What launch_trace and launch_guides share — n records, one lane each, in blocks of 256: list(blocks) launches the list scan's kernel,
+// walk(w, blocks, lds) the tree kernel of the walk the render kernel would use for this tree (sparse grids: the pooled walk), so that
+// per-ray parity checks cover it.
+template <class L, class W>
+static hipError_t launch_records(const DevTree& T, bool tree, long long n, L&& list, W&& walk) {
+    if (n <= 0) return hipSuccess;
+    const unsigned blocks = (unsigned)((n + 255) / 256);
+    if (!tree) return list(blocks);
+    const int variant = render_variant(true, T.acc);
+    return with_walk(variant, [&](auto w) { walk(w, blocks, variant_lds_bytes(T.n_nodes, variant)); return hipGetLastError(); });
 }
 
 hipError_t launch_trace(const DevScene& S, const DevTree& T, bool tree, const float* rays, long long n, rt_hit_record* out, hipStream_t st) {
-    if (n <= 0) return hipSuccess;
-    const unsigned blocks = (unsigned)((n + 255) / 256);
     RenderArgs A{};
     A.scene = S; A.tree = T;
-    if (!tree) return launch_trace_list(A, blocks, rays, n, out, st);
-    // the walk the render kernel would use for this tree (sparse grids: the pooled walk), so that per-ray parity checks cover it
-    if (render_variant(true, 0, T.acc) == 5) hipLaunchKernelGGL((k_trace<true, 5>), dim3(blocks), dim3(256), tree_lds_bytes(T.n_nodes, true), st, A, rays, n, out);
-    else if (render_variant(true, 0, T.acc) == 4) hipLaunchKernelGGL((k_trace<true, 4>), dim3(blocks), dim3(256), tree_lds_bytes(T.n_nodes, true), st, A, rays, n, out);
-    else if (render_variant(true, 0, T.acc) == 2) hipLaunchKernelGGL((k_trace<true, 2>), dim3(blocks), dim3(256), tree_lds_bytes(T.n_nodes, true), st, A, rays, n, out);
-    else hipLaunchKernelGGL((k_trace<true>), dim3(blocks), dim3(256), tree_lds_bytes(T.n_nodes), st, A, rays, n, out);
-    return hipGetLastError();
+    return launch_records(T, tree, n, [&](unsigned blocks) { return launch_trace_list(A, blocks, rays, n, out, st); },
+                          [&](auto w, unsigned blocks, size_t lds) { hipLaunchKernelGGL((k_trace<true, decltype(w)::value>), dim3(blocks), dim3(256), lds, st, A, rays, n, out); });
 }
 
 // the guides of a max_x x max_y frame (max_x * max_y < 2^31), launched as launch_trace launches k_trace: the same walk for every tree variant
 hipError_t launch_guides(const DevScene& S, const DevTree& T, bool tree, int max_x, int max_y, rt_hit_record* out, hipStream_t st) {
     const long long n = (long long)max_x * max_y;
-    if (n <= 0) return hipSuccess;
-    const unsigned blocks = (unsigned)((n + 255) / 256);
     RenderArgs A{};
     A.scene = S; A.tree = T; A.max_x = max_x; A.max_y = max_y;
-    if (!tree) return launch_guides_list(A, blocks, n, out, st);
-    const int variant = render_variant(true, 0, T.acc);
-    if (variant == 5) hipLaunchKernelGGL((k_guides<true, 5>), dim3(blocks), dim3(256), tree_lds_bytes(T.n_nodes, true), st, A, n, out);
-    else if (variant == 4) hipLaunchKernelGGL((k_guides<true, 4>), dim3(blocks), dim3(256), tree_lds_bytes(T.n_nodes, true), st, A, n, out);
-    else if (variant == 2) hipLaunchKernelGGL((k_guides<true, 2>), dim3(blocks), dim3(256), tree_lds_bytes(T.n_nodes, true), st, A, n, out);
-    else hipLaunchKernelGGL((k_guides<true>), dim3(blocks), dim3(256), tree_lds_bytes(T.n_nodes), st, A, n, out);
-    return hipGetLastError();
+    return launch_records(T, tree, n, [&](unsigned blocks) { return launch_guides_list(A, blocks, n, out, st); },
+                          [&](auto w, unsigned blocks, size_t lds) { hipLaunchKernelGGL((k_guides<true, decltype(w)::value>), dim3(blocks), dim3(256), lds, st, A, n, out); });
 }
 
 RT_STATS_READERS

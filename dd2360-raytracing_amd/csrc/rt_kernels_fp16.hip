@@ -9,6 +9,7 @@
 // binary32 bounds.  Scene data arrive as floats holding exact binary16 images.
 #include <hip/hip_runtime.h>
 #include <float.h>
+#include <type_traits>
 #include "rt_device.h"
 #include "rt_launch.h"
 #include "rt_real.h"
@@ -1052,13 +1053,8 @@ __global__ __launch_bounds__(256) void k_assemble_h(uint16_t* full, const uint16
 
 } // namespace h16
 
-static unsigned resident_blocks_h(const void* kernel, size_t lds) {
-    int dev = 0, cus = 0, per_cu = 0;
-    if (hipGetDevice(&dev) != hipSuccess) return 1024u;
-    if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus <= 0) return 1024u;
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kernel, 256, lds) != hipSuccess || per_cu <= 0) per_cu = 4;
-    return (unsigned)(cus * per_cu);
-}
+// the ONE ladder from the run-time `tree` to the kernels' TREE argument: f is called with std::true_type or std::false_type
+template <class F> static auto with_tree(bool tree, F&& f) { return tree ? f(std::true_type{}) : f(std::false_type{}); }
 
 const char* render_kernel_name_h(bool tree, int mode) {
     return tree ? (mode == 0 ? "k_render_h<true,0>" : "k_render_h<true,1>") : (mode == 0 ? "k_render_h<false,0>" : "k_render_h<false,1>");
@@ -1070,24 +1066,18 @@ static size_t h16_lds_bytes(bool tree, const DevTree& T) {
     return tree ? (size_t)T.n_nodes * (T.h16_np[0] > 0 ? (regular ? 2 : 1) * sizeof(float4) : sizeof(DevNode)) + (T.h16_np[0] > 0 ? h16::kPlaneLds4 * sizeof(float4) : 0) + 4 * sizeof(h16::WaveLds) : 0;
 }
 
-// the pilot pass alone (rt_split_balanced): per tile 4 x the bounces of its pilot samples
-hipError_t launch_pilot_h(const RenderArgs& A, bool tree, int* cost, hipStream_t st) {
+// the pilot pass: per tile 4 x the bounces of its pilot samples (pilot == nullptr: that alone, rt_split_balanced; else the counts per 2x2 block too)
+hipError_t launch_pilot_h(const RenderArgs& A, bool tree, int* cost, unsigned char* pilot, hipStream_t st) {
     if (A.n_local_tiles <= 0) return hipSuccess;
     const unsigned blocks = (unsigned)((A.n_local_tiles + 7) / 8);                 // a wave covers two tiles
-    const size_t lds = h16_lds_bytes(tree, A.tree);
-    if (tree) hipLaunchKernelGGL((h16::k_tile_cost_h<true>), dim3(blocks), dim3(256), lds, st, A, cost, (unsigned char*)nullptr);
-    else hipLaunchKernelGGL((h16::k_tile_cost_h<false>), dim3(blocks), dim3(256), lds, st, A, cost, (unsigned char*)nullptr);
+    with_tree(tree, [&](auto t) { hipLaunchKernelGGL((h16::k_tile_cost_h<decltype(t)::value>), dim3(blocks), dim3(256), h16_lds_bytes(tree, A.tree), st, A, cost, pilot); });
     return hipGetLastError();
 }
 
 // the scheduling pre-pass of a binary16 render: pilot pass in binary16, then the precision-independent selection and ordering (rt_schedule.hip)
 hipError_t launch_tile_order_h(const RenderArgs& A, bool tree, int* cost, unsigned int* order, unsigned char* flags, unsigned int* long_list, hipStream_t st) {
     if (A.n_local_tiles <= 0) return hipSuccess;
-    const unsigned blocks = (unsigned)((A.n_local_tiles + 7) / 8);                 // a wave covers two tiles
-    const size_t lds = h16_lds_bytes(tree, A.tree);
-    unsigned char* pilot = flags ? flags + (size_t)A.n_local_tiles * 64 : nullptr;
-    if (tree) hipLaunchKernelGGL((h16::k_tile_cost_h<true>), dim3(blocks), dim3(256), lds, st, A, cost, pilot);
-    else hipLaunchKernelGGL((h16::k_tile_cost_h<false>), dim3(blocks), dim3(256), lds, st, A, cost, pilot);
+    { const hipError_t e = launch_pilot_h(A, tree, cost, flags ? flags + (size_t)A.n_local_tiles * 64 : nullptr, st); if (e != hipSuccess) return e; }
     return launch_select_and_order(A, cost, order, flags, long_list, st, RT_H16_PILOT_LONG_SUM, 0x7fffffff);
 }
 
@@ -1095,9 +1085,8 @@ hipError_t launch_render_h(const RenderArgs& A, bool tree, int mode, hipStream_t
     if (A.n_local_tiles <= 0) return hipSuccess;
     const unsigned need = (unsigned)((A.n_local_tiles + 3) / 4);
     const size_t lds = h16_lds_bytes(tree, A.tree);
-    void (*k)(RenderArgs) = tree ? (mode == 0 ? h16::k_render_h<true, 0> : h16::k_render_h<true, 1>)
-                                 : (mode == 0 ? h16::k_render_h<false, 0> : h16::k_render_h<false, 1>);
-    const unsigned cap = resident_blocks_h((const void*)k, lds);
+    void (*k)(RenderArgs) = with_tree(tree, [&](auto t) { return mode == 0 ? h16::k_render_h<decltype(t)::value, 0> : h16::k_render_h<decltype(t)::value, 1>; });
+    const unsigned cap = resident_blocks((const void*)k, lds);
     const unsigned blocks = need < cap ? need : cap;
     hipLaunchKernelGGL(k, dim3(blocks), dim3(256), lds, st, A);
     return hipGetLastError();
@@ -1106,9 +1095,7 @@ hipError_t launch_render_h(const RenderArgs& A, bool tree, int mode, hipStream_t
 hipError_t launch_trace_h(const DevScene& S, const DevTree& T, bool tree, const float* rays, long long n, rt_hit_record* out, hipStream_t st) {
     if (n <= 0) return hipSuccess;
     const unsigned blocks = (unsigned)((n + 255) / 256);
-    const size_t lds = h16_lds_bytes(tree, T);
-    if (tree) hipLaunchKernelGGL((h16::k_trace_h<true>), dim3(blocks), dim3(256), lds, st, S, T, rays, n, out);
-    else hipLaunchKernelGGL((h16::k_trace_h<false>), dim3(blocks), dim3(256), lds, st, S, T, rays, n, out);
+    with_tree(tree, [&](auto t) { hipLaunchKernelGGL((h16::k_trace_h<decltype(t)::value>), dim3(blocks), dim3(256), h16_lds_bytes(tree, T), st, S, T, rays, n, out); });
     return hipGetLastError();
 }
 

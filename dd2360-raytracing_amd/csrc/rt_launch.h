@@ -4,6 +4,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include "rt_device.h"
+#include "rt_variant.h"
 
 namespace rt {
 
@@ -17,7 +18,8 @@ hipError_t launch_render(const RenderArgs& A, bool tree, int mode, hipStream_t s
 hipError_t launch_render_adaptive(const RenderArgs& A, bool tree, hipStream_t st);
 hipError_t launch_trace(const DevScene& S, const DevTree& T, bool tree, const float* rays, long long n, rt_hit_record* out, hipStream_t st);
 hipError_t launch_guides(const DevScene& S, const DevTree& T, bool tree, int max_x, int max_y, rt_hit_record* out, hipStream_t st);
-int render_variant_of(bool tree, const DevAccel& acc);
+int render_variant(bool tree, const DevAccel& acc);             // a kVariant* of rt_variant.h
+unsigned resident_blocks(const void* kernel, size_t lds);
 const char* render_kernel_name(bool tree, int mode, const DevAccel& acc);
 #ifdef RT_STATS
 hipError_t read_stats(unsigned long long* out, int reset);
@@ -65,7 +67,7 @@ hipError_t launch_assemble_spp(int32_t* full, const int32_t* parts, int max_x, i
 hipError_t launch_assemble_split(void* full, const void* parts, int max_x, int max_y, int nparts, const long long* starts, long long part_stride_px, bool half, hipStream_t st);
 
 // ---- rt_kernels_fp16.hip: the render path in binary16
-hipError_t launch_pilot_h(const RenderArgs& A, bool tree, int* cost, hipStream_t st);
+hipError_t launch_pilot_h(const RenderArgs& A, bool tree, int* cost, unsigned char* pilot, hipStream_t st);
 hipError_t launch_tile_order_h(const RenderArgs& A, bool tree, int* cost, unsigned int* order, unsigned char* flags, unsigned int* long_list, hipStream_t st);
 hipError_t launch_render_h(const RenderArgs& A, bool tree, int mode, hipStream_t st);
 hipError_t launch_trace_h(const DevScene& S, const DevTree& T, bool tree, const float* rays, long long n, rt_hit_record* out, hipStream_t st);

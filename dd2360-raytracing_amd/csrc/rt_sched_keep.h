@@ -7,6 +7,7 @@
 // HIP, so a stand-alone program exercises every transition on the CPU (tests/test_sched_keep_host.py).
 #pragma once
 #include <cstdint>
+#include "rt_variant.h"
 
 namespace rt {
 
@@ -84,10 +85,10 @@ inline void sched_keep_drop(SchedKeep& K) { sched_keep_forget(K); }
 // (kSchedCompute) therefore also records those counts, and the FIRST hit of that record runs the pass once more, from the counts instead
 // of the pilot's 18 one-sample paths per neighbourhood.  Later hits reuse the rebuilt pass like any other.  One rebuild per record.
 //
-// The gate — which launches take part at all: binary32, the sparse-grid kernels k_render<true,*,4> and <true,*,5> (the two whose launches
+// The gate — which launches take part at all: binary32, the variants that record counts (rt_variant.h: the sparse-grid kernels, the two whose launches
 // end when their longest pixel does), and at least `min_ns` samples (RT_FEEDBACK_MIN_NS): below that chains do not bound
 // a launch, and the hits of such launches keep the pilot's words.
-inline bool sched_feedback_gate(int ns, int min_ns, int render_variant, bool half) { return !half && ns >= min_ns && (render_variant == 4 || render_variant == 5); }
+inline bool sched_feedback_gate(int ns, int min_ns, int render_variant, bool half) { return !half && ns >= min_ns && variant_records_counts(render_variant); }
 // the launch of a kSchedCompute pass that passed the gate was given the count buffer, and its render kernel was launched successfully
 inline void sched_keep_counts(SchedKeep& K) { if (K.valid && !K.captured) K.has_counts = true; }
 // after sched_keep_decide returned kSchedReuse: is the rebuild due?  (enabled: RT_SCHED_FEEDBACK; gate: sched_feedback_gate of this launch)
