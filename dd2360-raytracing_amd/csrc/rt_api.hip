@@ -700,7 +700,7 @@ int rt_build_octree_gpu(const rt_world* world, int spheres_per_leaf, rt_octree**
         if (!O->z) { delete O; return RT_ENOMEM; }
         O->precision = world->precision;
         rc = gpubuild::build(O, (const float4*)world->z->d_geom, (const int32_t*)world->z->d_kind, world->n, spheres_per_leaf, (hipStream_t)stream);
-        if (rc == 0) { *out = O; return 0; }
+        if (rc == 0) { O->build_path = RT_BUILD_DEVICE; *out = O; return 0; }
         (void)rt_free_octree(O);
         if (rc != RT_ENOTSUP) return rc;
     }
@@ -715,8 +715,11 @@ int rt_build_octree_gpu(const rt_world* world, int spheres_per_leaf, rt_octree**
             s.material = world->h_kind[i]; s.albedo[0] = m.x; s.albedo[1] = m.y; s.albedo[2] = m.z; s.param = m.w;
         }
     } catch (const std::bad_alloc&) { return RT_ENOMEM; }
-    return rt_build_octree(list.data(), world->n, spheres_per_leaf, world->precision, out);
+    RT_TRY(rt_build_octree(list.data(), world->n, spheres_per_leaf, world->precision, out));
+    (*out)->build_path = RT_BUILD_HOST_DECLINED;
+    return 0;
 }
+int rt_octree_build_path(const rt_octree* O) { return O ? O->build_path : RT_EINVAL; }
 
 // ------------------------------------------------------------------------------------------------ the hot path
 int64_t rt_part_pixels(int max_x, int max_y, rt_partition part) {

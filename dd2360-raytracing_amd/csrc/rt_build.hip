@@ -644,6 +644,8 @@ int build(rt_octree* O, const float4* d_geom, const int32_t* d_kind, int n, int 
     unsigned long long* kx = B.take<unsigned long long>(std::max<size_t>(nx, 1)); unsigned long long* kz = B.take<unsigned long long>(std::max<size_t>(nz, 1));
     if (B.used > B.size) return RT_ENOMEM;
     unsigned long long* kxs = pairs_a; unsigned long long* kzs = pairs_b;                       // sorted keys in the workspace (the pairs are done with)
+    // No input reaches this: a grid sphere has R' <= Rlim = 1.5 h, so its columns floor((x - R' - g0) / h - 1e-4) .. floor((x + R' - g0) / h + 1e-4)
+    // span 2 R' / h + 2e-4 <= 3.0002 and number at most floor(3.0002) + 2 = 5 (k_classify, as rt_accel.h's build_accel): nx, nz <= 5 n < cap.
     if (nx > cap || nz > cap) return RT_ENOTSUP;
     RT_TRY(hipMemsetAsync(cellbits, 0, 64 * (size_t)std::max(1, bit_rows), st));
     RT_TRY(hipMemsetAsync(large_brick, 0, 32 * (size_t)std::max(1, n_large), st));

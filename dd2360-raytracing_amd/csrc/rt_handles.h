@@ -129,6 +129,7 @@ struct rt_octree {
     std::vector<DevNode> h_nodes; std::vector<float4> h_ent_hot; std::vector<int32_t> h_ent_id;
     AccelHost accel;
     int traversal = RT_TRAVERSAL_FAST;
+    int build_path = RT_BUILD_HOST;            // rt_octree_build_path: set where rt_build_octree_gpu decides (the list grid's tree is a host build)
     struct Lazy {
         bool uploaded = false;
         DevTree dev{};

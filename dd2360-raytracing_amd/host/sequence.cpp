@@ -369,6 +369,8 @@ int run_animation(const Options& o) {
             tree = nullptr;
             checkHipErrors(rt_build_octree_gpu(world, o.spl, &tree, stream));
             report_drops(tree);
+            if (o.timing && rt_octree_build_path(tree) != RT_BUILD_DEVICE)
+                std::cerr << "timing: frame " << f << ": the device build declined this geometry, the tree was built on the host\n";
         }
         mark(TREE, 1);
         // 3. - 7. guides, samples, history, filter

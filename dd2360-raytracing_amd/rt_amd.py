@@ -15,6 +15,7 @@ FP32, FP16 = 0, 1
 MAT_NONE, MAT_LAMBERTIAN, MAT_METAL, MAT_DIELECTRIC = -1, 0, 1, 2
 OCTREE_MAX_NODES = 585        # rt_amd.h RT_OCTREE_MAX_NODES
 TRAVERSAL_REFERENCE, TRAVERSAL_FAST = 0, 1
+BUILD_HOST, BUILD_DEVICE, BUILD_HOST_DECLINED = 0, 1, 2      # rt_amd.h RT_BUILD_*: what Octree.build_path() returns
 ARITH_IEEE, ARITH_CONTRACT = 0, 1
 IMAGE_P3, IMAGE_P6, IMAGE_PFM = 0, 1, 2
 
@@ -192,6 +193,7 @@ SYMBOLS = {
     "rt_build_octree": (_i, [_vp, _i, _i, _i, _vp]),
     "rt_octree_upload": (_i, [_vp]),
     "rt_build_octree_gpu": (_i, [_vp, _i, _vp, _vp]),
+    "rt_octree_build_path": (_i, [_vp]),
     "rt_octree_debug_array": (_i, [_vp, _i, _vp, C.c_size_t, _vp]),
     "rt_free_octree": (_i, [_vp]),
     "rt_octree_info": (_i, [_vp, _vp, _vp, _vp, _vp, _vp]),
@@ -772,6 +774,10 @@ class Octree(_Handle):
     def upload(self):
         _call("rt_octree_upload", self.h)
         return self
+
+    def build_path(self):
+        """rt_octree_build_path: BUILD_HOST, BUILD_DEVICE or BUILD_HOST_DECLINED (gpu=True, but the device build declined the input)"""
+        return _size("rt_octree_build_path", self.h)
 
     def set_traversal(self, mode):
         """TRAVERSAL_REFERENCE (exact bucket scan) or TRAVERSAL_FAST (default, culling grid + fallback)"""

@@ -199,6 +199,14 @@ int rt_octree_upload(rt_octree* octree);   /* the cudaMalloc + cudaMemcpy of mai
  * 1.9 ms instead of 25.6 ms of host build + 3 ms of upload (MI355X box).  USE_FP16 worlds: the tree in binary16 arithmetic, the pair
  * layout and plane table of the binary16 kernels, no candidate grid — again what rt_build_octree + rt_octree_upload give. */
 int rt_build_octree_gpu(const rt_world* world, int spheres_per_leaf, rt_octree** out, void* stream);
+/* Which build a tree came from (read-only; RT_EINVAL for NULL).  rt_build_octree_gpu declines an input whose (level-3 cell, sphere)
+ * pairs outnumber its workspace of 16 * num_spheres + 65536 — many spheres that each span many cells — and then builds the same tree
+ * on the host from the world's list (after rt_world_set_geometry: one synchronising download first): RT_BUILD_HOST_DECLINED, a
+ * rebuild of tens of milliseconds where the device takes one. */
+#define RT_BUILD_HOST 0            /* rt_build_octree */
+#define RT_BUILD_DEVICE 1          /* rt_build_octree_gpu, on the device */
+#define RT_BUILD_HOST_DECLINED 2   /* rt_build_octree_gpu, on the host after the device build declined */
+int rt_octree_build_path(const rt_octree* octree);
 /* one device-resident array of a tree, copied to the host (parity checks of the two builds; binary16 trees: 0-2 only): 0 traversal nodes, 1 bucket
  * entries (c, r^2), 2 entry -> sphere, 3/4 large spheres + bricks, 5 strip bin starts (columns x fine bins; the x copy, then the z copy), 6/7 strip entries + bricks, 8/9 membership
  * lists, 10 cell -> node, 11/12 membership bitmaps.  *bytes = size of the array; copied when cap suffices. */

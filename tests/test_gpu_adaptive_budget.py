@@ -73,6 +73,7 @@ class Frame:
         picked = self.torch.full((rounds,), SENTINEL, dtype=self.torch.int32, device="cuda")
         B = self.rt.Budget(samples, rounds, batch, max_spp, floor)
         if self.ctx is not None:
+            self.torch.cuda.synchronize()                    # (the fill above runs on the current stream, the spend on the context's)
             self.ctx.render_adaptive_spend(self.fb, self.nx, self.ny, B, W, self.st, self.state, O, self.spp, self.part, picked, stream=self.stream)
         else:
             self.rt.render_adaptive_spend(self.fb, self.nx, self.ny, B, W, self.st, self.state, O, self.spp, self.part, picked)

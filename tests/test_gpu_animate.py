@@ -8,8 +8,8 @@ i % 3 == 1 is translated by (0.3, 0.15, -0.2), i % 3 == 2 has its radius times 1
 to (50, 50, 50), outside the tree's box; for USE_FP16 worlds every value is rounded to binary16 first.
 
 The host staging copy (h_geom) has two readers: the world's list grid, which the list-path cases and rt_world_list_accel_info cover
-at N = 500, and the host fallback of rt_build_octree_gpu, which no input of test size reaches (the device build declines only when
-its workspace overflows).  The wrapper's own host build (Octree(world, gpu=False)) reads the binding's copy of the list, which
+at N = 500, and the host fallback of rt_build_octree_gpu, which the device build's workspace limit leads to: the worlds here stay
+below it, tests/test_gpu_build_limits.py::test_fallback_after_a_move moves a resident world of 161 spheres across it.  The wrapper's own host build (Octree(world, gpu=False)) reads the binding's copy of the list, which
 World.set_geometry marks stale in the same way: test_host_build_after_a_move."""
 import numpy as np
 import pytest

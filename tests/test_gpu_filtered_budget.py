@@ -180,6 +180,7 @@ class Frame(T.Frame):
         picked = self.torch.full((rounds,), SENTINEL, dtype=self.torch.int32, device="cuda")
         Bd = self.rt.Budget(samples, rounds, batch, max_spp, floor)
         if self.ctx is not None:
+            self.torch.cuda.synchronize()                    # (the fill above runs on the current stream, the spend on the context's)
             self.ctx.render_adaptive_spend_filtered(self.fb, self.nx, self.ny, Bd, p, sc.d_hits, sc.W, self.st, self.state, sc.O, self.spp, picked,
                                                     stream=self.stream)
         else:

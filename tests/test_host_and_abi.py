@@ -22,7 +22,7 @@ def u32(a):
 def test_abi_exports_every_declared_symbol(rt):
     """the whole ABI, once: every prototype of the header is bound with the header's types and exported, and nothing else is bound"""
     hdr = open(abi_header.HEADER).read()
-    assert len(abi_header.PROTOTYPES) == 108 and set(abi_header.PROTOTYPES) == set(re.findall(r"\b(rt_[a-z0-9_]+)\s*\(", hdr)), "a declaration was lost"
+    assert len(abi_header.PROTOTYPES) == 109 and set(abi_header.PROTOTYPES) == set(re.findall(r"\b(rt_[a-z0-9_]+)\s*\(", hdr)), "a declaration was lost"
     assert set(abi_header.PROTOTYPES) == set(rt.SYMBOLS), "binding and header disagree: %s" % (set(abi_header.PROTOTYPES) ^ set(rt.SYMBOLS))
     abi_header.check_bound(rt, abi_header.PROTOTYPES)
     assert rt.lib().rt_abi_version() == abi_header.DEFINES["RT_ABI_VERSION"] == 6
