@@ -2,8 +2,6 @@
 operation per line, the eligibility mask, the picks of a round, and the selection as a plain sort."""
 import numpy as np
 
-RUN = 64                           # rt_amd.h RT_PART_RUN
-
 
 def priority(SL, Q, k, floor):
     """rt_adaptive_priority for arrays (or scalars): float32 in, float32 out, one rounding per operation"""
@@ -34,23 +32,6 @@ def picks(samples, rounds, batch, r):
     """K_r: integer divisions (Python ints, never negative here, so // is C's /)"""
     q = samples // batch
     return q * (r + 1) // rounds - q * r // rounds
-
-
-def inside(nx, ny, part, n):
-    """for every element of a part's buffer: whether it lies inside the frame; part = (part, nparts, tile_begin, tile_end)"""
-    p, nparts, tb, te = part
-    e = np.arange(n, dtype=np.int64)
-    lt = e // 64
-    if te > tb:
-        tile = tb + lt
-    elif nparts == 1:
-        return np.ones(n, bool)
-    else:
-        tile = ((lt // RUN) * nparts + p) * RUN + lt % RUN
-    tiles_x = (nx + 7) // 8
-    i = (tile % tiles_x) * 8 + (e % 64) % 8
-    j = (tile // tiles_x) * 8 + (e % 64) // 8
-    return (i < nx) & (j < ny)
 
 
 def eligible(SL, Q, k, batch, max_spp, floor, in_frame):

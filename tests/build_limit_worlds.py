@@ -160,10 +160,10 @@ def oracle(rt, name, fp16, spl, nx=NX, ny=NY):
 
 # ---------------------------------------------------------------------------------------------------- rays
 def rays(fp16):
-    """N_RAYS rays: test_gpu_parity.random_rays (origins in the box - inside every shell -, at the camera, far away, around the box),
+    """N_RAYS rays: world_cases.random_rays (origins in the box - inside every shell -, at the camera, far away, around the box),
     the last N_AIMED of them replaced by rays from 12 to 40 (binary16: 12 to 16) away from (0, 1, 0) - outside every shell - aimed at a
     point of the root box; binary16 numbers for a binary16 world"""
-    from test_gpu_parity import random_rays
+    from world_cases import random_rays
     r = random_rays(N_RAYS, 4100)
     rng = np.random.default_rng(4200)
     d = rng.normal(size=(N_AIMED, 3))

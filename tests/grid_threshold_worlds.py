@@ -1,5 +1,5 @@
 """Worlds and rays AT the thresholds of the candidate grid (csrc/rt_accel.h, csrc/rt_build.hip, closest_tree), which create_world scenes
-and test_gpu_parity.random_world never come near: radii a few float steps either side of the radius at which a sphere leaves the grid
+and world_cases.random_world never come near: radii a few float steps either side of the radius at which a sphere leaves the grid
 (R' = Rlim), centres a few float steps either side of the centre bound 17.5, column ranges and fine bins either side of a floor(),
 hittable counts 63 / 64, large counts 64 / 65 and 0 / 8 / 9, the clamps of the cell size, in-tree counts either side of the dense
 rule and of the solo rule; ray origins a few float steps either side of the near zone's sphere |o - (0,1,0)| = 24, aimed at grazing
@@ -26,7 +26,7 @@ import numpy as np
 
 import material_edge_worlds as mw
 import oracle_lib
-from test_gpu_strips import lattice_rays
+from world_cases import lattice_rays
 
 F = np.float32
 NX, NY = 64, 40
@@ -594,7 +594,7 @@ def precondition_rays(n, seed):
 
 
 def lattice_rays_for(m, sp, n, seed):
-    """test_gpu_strips.lattice_rays on the model's grid: g0, G and h of the world's own grid - a list's grid reaches past the root box -
+    """world_cases.lattice_rays on the model's grid: g0, G and h of the world's own grid - a list's grid reaches past the root box -
     (no grid: 64 columns over the root box)"""
     on = m["enabled"] and m["G"] > 0
     info = dict(grid_dim=m["G"], cell_size=m["h"]) if on else dict(grid_dim=64, cell_size=2.0 * ROOT_HALF / 64)
@@ -614,7 +614,7 @@ def preferred_targets(name, variant=None):
 
 def ray_families(name, variant, sp, m, n):
     """the four ray sets of a world, by name"""
-    from test_gpu_parity import random_rays
+    from world_cases import random_rays
     return {"zone": zone_rays(sp, n, 7100, preferred_targets(name, variant)), "precondition": precondition_rays(n, 7200),
             "lattice": lattice_rays_for(m, sp, n, 7300), "random": random_rays(n, 7400)}
 

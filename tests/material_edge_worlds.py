@@ -1,4 +1,4 @@
-"""Worlds for the branches of the shading code that create_world and test_gpu_parity.random_world never reach: several refractive
+"""Worlds for the branches of the shading code that create_world and world_cases.random_world never reach: several refractive
 indices in one world (below, at and above 1; 0, negative, inf and NaN), negative radii (hollow glass shells, inward-facing rooms the
 camera cannot see out of), albedo 0 and 1e30, fuzz exactly 0 and 1, a radius of 0 and of NaN, a lens radius of 0, slot 0 as a ghost
 and as the room itself.
@@ -258,10 +258,10 @@ def gpu_world(rt, sp, cam, nx, ny, precision=0):
 
 # ---------------------------------------------------------------------------------------------------- rays
 def edge_rays(sp, n, seed):
-    """n rays for the hit-record tests: test_gpu_parity.random_rays rescaled to the field (half its width); a quarter of the origins
+    """n rays for the hit-record tests: world_cases.random_rays rescaled to the field (half its width); a quarter of the origins
     inside negative-radius spheres or in the glass between a shell and its outer sphere (inside the dielectrics where the world has no
     negative radius); 2 % aimed exactly through the centre of a radius-0 sphere, origin, direction and centre all representable."""
-    from test_gpu_parity import random_rays
+    from world_cases import random_rays
     rng = np.random.default_rng(seed)
     rays = random_rays(n, seed)
     rays[:, [0, 2, 3, 5]] *= F(0.5)

@@ -3,6 +3,7 @@
 tests rebuild (tests/test_reference_fixtures_host.py, tests/test_gpu_reference_fixtures.py).  A helper module: no tests here.
 
 A "side" is anything with trace(rays, mode) and scatter(sphere, rays, recs, states): ref_lib.RefWorld or oracle_lib.OracleScene."""
+import hashlib
 import types
 
 import numpy as np
@@ -10,8 +11,7 @@ import numpy as np
 import material_edge_worlds as mw
 import oracle_lib
 from denoise_model import guide_rays
-from test_gpu_parity import random_rays, random_world
-from test_gpu_strips import lattice_rays
+from world_cases import lattice_rays, random_rays, random_world
 
 F = np.float32
 NX, NY = 64, 40
@@ -25,17 +25,6 @@ EDGE = {"%s%s" % (n, "_" + v if v else ""): (n, v) for n, v in mw.WORLDS}
 NAMES = list(CREATED) + list(RANDOM) + list(EDGE)
 # more trees: buckets of 3 and 4 that overflow
 SMALL_BUCKETS = [("created_10000", 3), ("random_3", 4), ("random_2", 3), ("created_10000", 4)]
-
-
-def bits(a):
-    return np.ascontiguousarray(a, F).view(np.uint32)
-
-
-def same(got, ref):
-    """bit-equal; NaN where the reference has NaN (test_gpu_reference_edges.same)"""
-    got, ref = np.asarray(got, F), np.asarray(ref, F)
-    nan = np.isnan(ref)
-    return got.shape == ref.shape and np.array_equal(bits(got)[~nan], bits(ref)[~nan]) and bool(np.isnan(got[nan]).all())
 
 
 def half(a):
@@ -67,6 +56,24 @@ def world(name, fp16=False):
         if fp16:
             geom, mat, cam = half(geom), half(mat), half(cam)
     return geom, mat, kind, cam, spl
+
+
+def tag(name, fp16):
+    return "%s_%s" % (name, "fp16" if fp16 else "fp32")
+
+
+def sha(*arrays):
+    h = hashlib.sha256()
+    for a in arrays:
+        h.update(np.ascontiguousarray(a).tobytes())
+    return np.frombuffer(h.digest(), np.uint8)
+
+
+def world_of(gold, name, fp16):
+    """the world, checked against the digest taken when the fixtures were recorded"""
+    w = world(name, fp16)
+    assert np.array_equal(sha(*w[:4]), gold["hits"][tag(name, fp16) + "_world_sha"]), "the world builder of %s changed: re-record the fixtures" % name
+    return w
 
 
 def as_spheres(geom, mat, kind):

@@ -8,12 +8,9 @@ Test infrastructure only: self_check() holds the model to hand-worked cases (pyt
 import numpy as np
 
 import temporal_model as tm
+from bitcmp import f32_bits
 
 F = tm.F
-
-
-def bits(a):
-    return np.ascontiguousarray(a, F).view(np.uint32)
 
 
 def moved_points(hits, geom, geom_prev):
@@ -25,8 +22,8 @@ def moved_points(hits, geom, geom_prev):
     known = (s >= 0) & (s < len(geom))
     sc = np.clip(s, 0, len(geom) - 1)
     c1, c0 = geom[sc], geom_prev[sc]
-    moved = known & (bits(c0[:, :3]) != bits(c1[:, :3])).any(axis=1)
-    resized = known & (bits(c0[:, 3]) != bits(c1[:, 3]))
+    moved = known & (f32_bits(c0[:, :3]) != f32_bits(c1[:, :3])).any(axis=1)
+    resized = known & (f32_bits(c0[:, 3]) != f32_bits(c1[:, 3]))
     P = np.asarray(hits["p"], F)
     with np.errstate(all="ignore"):
         back = (P - c1[:, :3]) + c0[:, :3]
@@ -176,7 +173,7 @@ def self_check():
     prev7["sphere"] = 7
     spec = dict(args, reuse_specular=1)
     Pb, known, moved, resized = moved_points(hits, g1, g0)
-    assert not known.any() and not moved.any() and not resized.any() and np.array_equal(bits(Pb), bits(hits["p"]))
+    assert not known.any() and not moved.any() and not resized.any() and np.array_equal(f32_bits(Pb), f32_bits(hits["p"]))
     assert np.array_equal(accumulate_moving(hist, hits, prev7, cam, g1, g0, state, **spec), tm.accumulate(hist, hits, prev7, cam, state, **spec))
     assert np.array_equal(accumulate_moving(hist, hits, prev7, cam, g1, g0, state, **args), first)       # not lambertian: not asked
     hits["sphere"] = -1

@@ -9,6 +9,7 @@ import pytest
 
 import abi_header
 import filtered_budget_model as M
+from bitcmp import f32_bits
 
 FAKE = C.c_void_p(0x1000)          # 16-byte aligned, never dereferenced: the calls below refuse before they touch a buffer
 ODD = C.c_void_p(0x1008)           # not 16-byte aligned
@@ -63,10 +64,6 @@ def test_model_self_check():
 
 
 # ---- the key -----------------------------------------------------------------------------------------------------------------
-def bits(a):
-    return np.ascontiguousarray(a, np.float32).view(np.uint32)
-
-
 def test_priority_filtered_equals_the_model(rt):
     tiny = float(np.float32(1e-45))                                   # the smallest denormal
     vals = [0.0, -0.0, tiny, 1e-40, 1.1754944e-38, 1e-20, 0.02, 0.3, 1.0, 1.5, 3.0e19, 3.0e38, INF, NAN, -1.0, -INF]
@@ -76,8 +73,8 @@ def test_priority_filtered_equals_the_model(rt):
     L = rt.lib()
     got = np.array([L.rt_adaptive_priority_filtered(C.c_float(l[i]), C.c_float(v[i]), C.c_float(f[i])) for i in range(len(l))], np.float32)
     ref = M.priority_filtered(l, v, f)
-    assert np.array_equal(bits(got), bits(ref))
-    assert not np.isnan(got).any() and (bits(got) < 0x80000000).all()         # never NaN, never negative (not even -0)
+    assert np.array_equal(f32_bits(got), f32_bits(ref))
+    assert not np.isnan(got).any() and (f32_bits(got) < 0x80000000).all()         # never NaN, never negative (not even -0)
     assert np.isinf(got).any() and (got == 0).any() and len(np.unique(got)) > 30       # the table is not degenerate
     # random pairs in the range a frame produces
     rng = np.random.default_rng(20240611)
@@ -85,7 +82,7 @@ def test_priority_filtered_equals_the_model(rt):
     v = (rng.uniform(0.0, 1.0, 4000) ** 4).astype(np.float32)
     f = rng.choice(np.array([0.0, 0.02, 1.0], np.float32), 4000)
     got = np.array([rt.adaptive_priority_filtered(l[i], v[i], f[i]) for i in range(4000)], np.float32)
-    assert np.array_equal(bits(got), bits(M.priority_filtered(l, v, f)))
+    assert np.array_equal(f32_bits(got), f32_bits(M.priority_filtered(l, v, f)))
 
 
 def test_priority_filtered_edge_values(rt):

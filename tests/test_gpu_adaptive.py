@@ -10,6 +10,9 @@ import subprocess
 import numpy as np
 import pytest
 
+from adaptive_frames import adaptive_frame, pick_rel_error, progressive_samples, stop_rule_model
+from bitcmp import raw_bits
+from gpu_frames import frame_rows, render_frame
 from oracle_lib import OracleScene
 
 pytestmark = pytest.mark.gpu
@@ -22,86 +25,6 @@ MIN, BATCH, MAX = 4, 4, 32
 FLOOR = 0.02
 
 
-def u32(a):
-    return np.ascontiguousarray(a).view(np.uint32)
-
-
-def model(samples, rel_error, floor, lo, step, hi):
-    """the stop rule on per-sample colours samples[s, pixel, 3] (float32): (spp, fb) of every pixel"""
-    npx = samples.shape[1]
-    S = np.zeros((npx, 3), F)
-    SL = np.zeros(npx, F)
-    Q = np.zeros(npx, F)
-    spp = np.zeros(npx, np.int32)
-    fb = np.zeros((npx, 3), F)
-    rel, fl = F(rel_error), F(floor)
-    for k in range(1, hi + 1):
-        c = samples[k - 1]
-        S = S + c
-        l = (c[:, 0] + c[:, 1]) + c[:, 2]
-        SL = SL + l
-        Q = Q + l * l
-        if k < lo or (k - lo) % step:
-            continue
-        n = F(k)
-        d = n * Q - SL * SL
-        m = np.where(SL > n * fl, SL, n * fl)
-        t = rel * rel
-        with np.errstate(invalid="ignore", over="ignore"):
-            conv = (d <= (t * (n - F(1))) * (m * m)) if rel > 0 else np.zeros(npx, bool)
-        stop = (spp == 0) & (conv | (k == hi))
-        kk = F(1.0 / float(F(k)))
-        fb[stop] = np.sqrt(S[stop] * kk)
-        spp[stop] = k
-    return spp, fb
-
-
-def progressive_samples(rt, torch, W, O, nx, ny, count):
-    """per-sample colours [count, pixels, 3] and the RNG state after every pass [count, pixels, 12], from one-sample passes"""
-    st = rt.alloc_rand_state(nx, ny)
-    fb = rt.alloc_fb(nx, ny)
-    rt.render_init(nx, ny, st)
-    cols, states = [], []
-    for _ in range(count):
-        rt.render_progressive(fb, nx, ny, 1, W, st, O)
-        cols.append(fb.clone())
-        states.append(st.clone())
-    torch.cuda.synchronize()
-    return (np.stack([c.cpu().numpy().reshape(-1, 3) for c in cols]),
-            np.stack([s.cpu().numpy().view(np.uint32).reshape(-1, 12) for s in states]))
-
-
-def adaptive(rt, torch, W, O, nx, ny, params, ctx=None, stream=None):
-    st = rt.alloc_rand_state(nx, ny)
-    fb = rt.alloc_fb(nx, ny)
-    spp = torch.full((nx * ny,), -1, dtype=torch.int32, device="cuda")
-    rt.render_init(nx, ny, st)
-    if ctx is None:
-        rt.render_adaptive(fb, nx, ny, params, W, st, O, spp)
-    else:
-        ctx.render_adaptive(fb, nx, ny, params, W, st, O, spp, stream=stream)
-    torch.cuda.synchronize()
-    return spp.cpu().numpy(), fb.cpu().numpy().reshape(-1, 3), st.cpu().numpy().view(np.uint32).reshape(-1, 12)
-
-
-def uniform(rt, torch, W, O, nx, ny, ns):
-    st = rt.alloc_rand_state(nx, ny)
-    fb = rt.alloc_fb(nx, ny)
-    rt.render_init(nx, ny, st)
-    rt.render(fb, nx, ny, ns, W, st, O)
-    torch.cuda.synchronize()
-    return fb.cpu().numpy().reshape(-1, 3), st.cpu().numpy().view(np.uint32).reshape(-1, 12)
-
-
-def pick_rel_error(samples, lo, step, hi, floor):
-    """the first target of a sweep whose frame mixes >= 3 distinct counts, early stops and capped pixels"""
-    for rel in (0.02, 0.03, 0.05, 0.07, 0.1, 0.15, 0.2, 0.3, 0.5):
-        spp, _ = model(samples, rel, floor, lo, step, hi)
-        if len(np.unique(spp)) >= 3 and (spp < hi).any() and (spp == hi).any():
-            return rel
-    raise AssertionError("no rel_error in the sweep gives a mixed frame")
-
-
 @pytest.fixture(scope="module")
 def small(rt, cuda):
     """test 1's scene, its per-sample colours and states, the chosen target and the adaptive frame"""
@@ -111,7 +34,7 @@ def small(rt, cuda):
     samples, states = progressive_samples(rt, torch, W, O, NX, NY, MAX)
     rel = pick_rel_error(samples, MIN, BATCH, MAX, FLOOR)
     P = rt.Adaptive(MIN, MAX, BATCH, rel, FLOOR)
-    got = adaptive(rt, torch, W, O, NX, NY, P)
+    got = adaptive_frame(rt, torch, W, O, NX, NY, P)
     yield dict(W=W, O=O, samples=samples, states=states, rel=rel, P=P, got=got)
     O.close()
     W.close()
@@ -119,12 +42,12 @@ def small(rt, cuda):
 
 def test_frame_equals_an_independent_model_of_the_rule(small):
     spp, fb, st = small["got"]
-    m_spp, m_fb = model(small["samples"], small["rel"], FLOOR, MIN, BATCH, MAX)
+    m_spp, m_fb = stop_rule_model(small["samples"], small["rel"], FLOOR, MIN, BATCH, MAX)
     ks = np.unique(spp)
     assert len(ks) >= 3 and (spp < MAX).any() and (spp == MAX).any(), ks
     assert set(ks.tolist()) <= set(range(MIN, MAX + 1, BATCH))
     assert np.array_equal(spp, m_spp)
-    assert np.array_equal(u32(fb), u32(m_fb))
+    assert np.array_equal(raw_bits(fb), raw_bits(m_fb))
     # the written-back state of a pixel that stopped at k is the state after its k-th one-sample pass
     want = small["states"][spp - 1, np.arange(spp.size)]
     assert np.array_equal(st, want)
@@ -133,9 +56,9 @@ def test_frame_equals_an_independent_model_of_the_rule(small):
 def test_frame_is_a_truncation_of_the_uniform_render(rt, cuda, small):
     spp, fb, st = small["got"]
     for k in np.unique(spp):
-        ufb, ust = uniform(rt, cuda, small["W"], small["O"], NX, NY, int(k))
+        ufb, ust = frame_rows(*render_frame(rt, cuda, small["W"], small["O"], NX, NY, int(k)))
         at = spp == k
-        assert np.array_equal(u32(fb[at]), u32(ufb[at])), k
+        assert np.array_equal(raw_bits(fb[at]), raw_bits(ufb[at])), k
         assert np.array_equal(st[at], ust[at]), k
 
 
@@ -148,10 +71,10 @@ def test_frame_matches_the_oracle(small):
         S.render_progressive(fb, 1, states, nthreads=8)
         samples.append(fb.reshape(-1, 3).copy())
     samples = np.stack(samples)
-    m_spp, m_fb = model(samples, small["rel"], FLOOR, MIN, BATCH, MAX)
+    m_spp, m_fb = stop_rule_model(samples, small["rel"], FLOOR, MIN, BATCH, MAX)
     spp, got, _ = small["got"]
     assert np.array_equal(spp, m_spp)
-    assert np.array_equal(u32(got), u32(m_fb))
+    assert np.array_equal(raw_bits(got), raw_bits(m_fb))
 
 
 # ---- limits at the C3 size --------------------------------------------------------------------------------------------
@@ -166,18 +89,18 @@ def c3(rt, cuda):
 
 def test_c3_zero_target_equals_the_uniform_render(rt, cuda, c3):
     W, O = c3
-    spp, fb, st = adaptive(rt, cuda, W, O, 1200, 800, rt.Adaptive(16, 64, 16, 0.0, 0.0))
-    ufb, ust = uniform(rt, cuda, W, O, 1200, 800, 64)
+    spp, fb, st = adaptive_frame(rt, cuda, W, O, 1200, 800, rt.Adaptive(16, 64, 16, 0.0, 0.0))
+    ufb, ust = frame_rows(*render_frame(rt, cuda, W, O, 1200, 800, 64))
     assert (spp == 64).all()
-    assert np.array_equal(u32(fb), u32(ufb)) and np.array_equal(st, ust)
+    assert np.array_equal(raw_bits(fb), raw_bits(ufb)) and np.array_equal(st, ust)
 
 
 def test_c3_huge_target_stops_everywhere_after_round_0(rt, cuda, c3):
     W, O = c3
-    spp, fb, st = adaptive(rt, cuda, W, O, 1200, 800, rt.Adaptive(16, 64, 16, 1.0e6, 1.0e-3))
-    ufb, ust = uniform(rt, cuda, W, O, 1200, 800, 16)
+    spp, fb, st = adaptive_frame(rt, cuda, W, O, 1200, 800, rt.Adaptive(16, 64, 16, 1.0e6, 1.0e-3))
+    ufb, ust = frame_rows(*render_frame(rt, cuda, W, O, 1200, 800, 16))
     assert (spp == 16).all()
-    assert np.array_equal(u32(fb), u32(ufb)) and np.array_equal(st, ust)
+    assert np.array_equal(raw_bits(fb), raw_bits(ufb)) and np.array_equal(st, ust)
 
 
 # ---- the other paths --------------------------------------------------------------------------------------------------
@@ -203,15 +126,15 @@ def test_other_paths_truncate_the_uniform_render(rt, cuda, name):
     assert kernel is None or rt.render_kernel_name(W, O) == kernel
     lo, step, hi = 16, 8, 40                       # round 0 with the long-chain pass, three resumed rounds
     for rel in (0.05, 0.1, 0.2, 0.4):
-        spp, fb, st = adaptive(rt, cuda, W, O, nx, ny, rt.Adaptive(lo, hi, step, rel, FLOOR))
+        spp, fb, st = adaptive_frame(rt, cuda, W, O, nx, ny, rt.Adaptive(lo, hi, step, rel, FLOOR))
         if len(np.unique(spp)) >= 3:
             break
     ks = np.unique(spp)
     assert len(ks) >= 3, ks
     for k in ks:
-        ufb, ust = uniform(rt, cuda, W, O, nx, ny, int(k))
+        ufb, ust = frame_rows(*render_frame(rt, cuda, W, O, nx, ny, int(k)))
         at = spp == k
-        assert np.array_equal(u32(fb[at]), u32(ufb[at])), (name, k)
+        assert np.array_equal(raw_bits(fb[at]), raw_bits(ufb[at])), (name, k)
         assert np.array_equal(st[at], ust[at]), (name, k)
     if O is not None:
         O.close()
@@ -222,10 +145,10 @@ def test_other_paths_truncate_the_uniform_render(rt, cuda, name):
 def test_context_reuse_and_two_streams(rt, cuda, small):
     torch = cuda
     W, O, P = small["W"], small["O"], small["P"]
-    a = uniform(rt, torch, W, O, NX, NY, 24)
-    spp0, fb0, st0 = adaptive(rt, torch, W, O, NX, NY, P)
-    b = uniform(rt, torch, W, O, NX, NY, 24)
-    assert np.array_equal(u32(a[0]), u32(b[0])) and np.array_equal(a[1], b[1])
+    a = frame_rows(*render_frame(rt, torch, W, O, NX, NY, 24))
+    spp0, fb0, st0 = adaptive_frame(rt, torch, W, O, NX, NY, P)
+    b = frame_rows(*render_frame(rt, torch, W, O, NX, NY, 24))
+    assert np.array_equal(raw_bits(a[0]), raw_bits(b[0])) and np.array_equal(a[1], b[1])
     # two contexts on two streams, launched back to back, equal the single-stream frame
     ctxs = [rt.RenderCtx(), rt.RenderCtx()]
     streams = [torch.cuda.Stream(), torch.cuda.Stream()]
@@ -240,7 +163,7 @@ def test_context_reuse_and_two_streams(rt, cuda, small):
     torch.cuda.synchronize()
     for st, fb, spp in bufs:
         assert np.array_equal(spp.cpu().numpy(), spp0)
-        assert np.array_equal(u32(fb.cpu().numpy().reshape(-1, 3)), u32(fb0))
+        assert np.array_equal(raw_bits(fb.cpu().numpy().reshape(-1, 3)), raw_bits(fb0))
         assert np.array_equal(st.cpu().numpy().view(np.uint32).reshape(-1, 12), st0)
     for c in ctxs:
         c.close()
@@ -257,7 +180,7 @@ def test_rt_main_writes_the_adaptive_frame(rt, cuda, tmp_path):
     assert "Rendering a %dx%d image with %d samples per pixel in 8x8 blocks." % (nx, ny, ns) in err and "Adaptive sampling: " in err
     W = rt.World(500, nx, ny)
     O = rt.Octree(W, 30)
-    spp, fb, _ = adaptive(rt, cuda, W, O, nx, ny, rt.Adaptive(lo, ns, step, rel, FLOOR))
+    spp, fb, _ = adaptive_frame(rt, cuda, W, O, nx, ny, rt.Adaptive(lo, ns, step, rel, FLOOR))
     assert (tmp_path / "output.ppm").read_bytes() == rt.format_ppm(fb, nx, ny)
     assert "mean samples per pixel: " in err
     O.close()

@@ -10,154 +10,14 @@ import pytest
 
 import adaptive_budget_model as M
 import denoise_var_model
+from adaptive_frames import BATCH, check_exact, check_round, FLOOR, Frame, inside_frame, make_state, MAX_SPP, model_pick, Scene, SENTINEL, state_parts
+from bitcmp import assert_same_snapshots, raw_bits
 
 pytestmark = pytest.mark.gpu
 
 NX, NY = 203, 77                   # 26 x 10 = 260 tiles: ragged right and top edges
 N, SPL = 10000, 32
-FLOOR = 0.02
-SENTINEL = 0x7FC0DEAD              # a NaN pattern nothing renders
-STATE_FILL = 0xA5                  # every byte of a fresh state (padding elements keep it)
 LOOSE = (4, 64, 4, 0.2, FLOOR)     # (min_spp, max_spp, batch, rel_error, floor): pixels stop at many different counts
-BATCH, MAX_SPP = 4, 64
-
-
-def u32(a):
-    return np.ascontiguousarray(a).view(np.uint32)
-
-
-def tup(P):
-    return (P.part, P.nparts, P.tile_begin, P.tile_end)
-
-
-def state_parts(s, n):
-    """the state's structure of arrays: S_rgb [n, 3], SL [n], Q [n] (float32), k [n] (int32)"""
-    f = s.view(np.float32)
-    return f[:3 * n].reshape(n, 3), f[3 * n:4 * n], f[4 * n:5 * n], s.view(np.int32)[5 * n:6 * n]
-
-
-def make_state(S, SL, Q, k):
-    n = len(k)
-    out = np.empty(6 * n, np.float32)
-    out[:3 * n] = np.asarray(S, np.float32).reshape(-1)
-    out[3 * n:4 * n] = SL
-    out[4 * n:5 * n] = Q
-    out[5 * n:].view(np.int32)[:] = k
-    return out.view(np.uint8)
-
-
-class Frame:
-    """the buffers of one part: fb and d_spp pre-filled with SENTINEL, RNG states from rt_render_init(part), a fresh state"""
-
-    def __init__(self, rt, torch, nx, ny, part, ctx=None, stream=None):
-        self.rt, self.torch, self.nx, self.ny, self.part, self.ctx, self.stream = rt, torch, nx, ny, part, ctx, stream
-        n = self.n = rt.part_pixels(nx, ny, part)
-        self.fb = torch.full((n * 3,), SENTINEL, dtype=torch.int32, device="cuda").view(torch.float32)
-        self.spp = torch.full((n,), SENTINEL, dtype=torch.int32, device="cuda")
-        self.st = rt.alloc_rand_state(nx, ny, part)
-        rt.render_init(nx, ny, self.st, part)
-        self.state = torch.full((n * rt.ADAPTIVE_STATE_BYTES,), STATE_FILL, dtype=torch.uint8, device="cuda")
-        self.inside = M.inside(nx, ny, tup(part), n)
-        torch.cuda.synchronize()
-
-    def begin(self, W, O, P):
-        if self.ctx is not None:
-            self.ctx.render_adaptive_begin(self.fb, self.nx, self.ny, self.rt.Adaptive(*P), W, self.st, self.state, O, self.spp, self.part,
-                                           stream=self.stream)
-        else:
-            self.rt.render_adaptive_begin(self.fb, self.nx, self.ny, self.rt.Adaptive(*P), W, self.st, self.state, O, self.spp, self.part)
-        return self
-
-    def spend(self, W, O, samples, rounds, batch=BATCH, max_spp=MAX_SPP, floor=FLOOR):
-        """one rt_render_adaptive_spend; returns d_picked read back"""
-        picked = self.torch.full((rounds,), SENTINEL, dtype=self.torch.int32, device="cuda")
-        B = self.rt.Budget(samples, rounds, batch, max_spp, floor)
-        if self.ctx is not None:
-            self.torch.cuda.synchronize()                    # (the fill above runs on the current stream, the spend on the context's)
-            self.ctx.render_adaptive_spend(self.fb, self.nx, self.ny, B, W, self.st, self.state, O, self.spp, self.part, picked, stream=self.stream)
-        else:
-            self.rt.render_adaptive_spend(self.fb, self.nx, self.ny, B, W, self.st, self.state, O, self.spp, self.part, picked)
-        self.torch.cuda.synchronize()
-        return picked.cpu().numpy().view(np.uint32)
-
-    def snap(self):
-        self.torch.cuda.synchronize()
-        return dict(fb=u32(self.fb.cpu().numpy()).reshape(-1, 3), spp=self.spp.cpu().numpy(),
-                    st=self.st.cpu().numpy().view(np.uint32).reshape(-1, 12), state=self.state.cpu().numpy().copy())
-
-
-def same(a, b, what=""):
-    for k in a:
-        assert np.array_equal(a[k], b[k]), (what, k)
-
-
-def model_pick(snap, n, inside, K, batch=BATCH, max_spp=MAX_SPP, floor=FLOOR):
-    """the model's choice for the state of a snapshot: (sorted ids, eligible mask, key bits)"""
-    S, SL, Q, k = state_parts(snap["state"], n)
-    kk = np.where(inside, k, 0)                              # (padding holds the fill pattern: any k, never eligible)
-    return M.select(SL, Q, kk, batch, max_spp, floor, inside, K)
-
-
-class Scene:
-    """a world and tree, and for every k the frame begin((k, k, 1, 0, floor)) leaves on fresh buffers of a part (the reference of a
-    pixel that has taken exactly k samples)"""
-
-    def __init__(self, rt, torch, n, spl, nx, ny, trav=None):
-        self.rt, self.torch, self.nx, self.ny = rt, torch, nx, ny
-        self.W = rt.World(n, nx, ny)
-        self.O = rt.Octree(self.W, spl) if spl else None
-        if trav is not None:
-            (self.O.set_traversal if self.O is not None else self.W.set_list_traversal)(trav)
-        self.refs = {}
-
-    def at_k(self, part, k, floor=FLOOR):
-        key = (tup(part), int(k), floor)
-        if key not in self.refs:
-            self.refs[key] = Frame(self.rt, self.torch, self.nx, self.ny, part).begin(self.W, self.O, (int(k), int(k), 1, 0.0, floor)).snap()
-        return self.refs[key]
-
-    def close(self):
-        if self.O is not None:
-            self.O.close()
-        self.W.close()
-
-
-def check_round(sc, F, before, after, picked, K, batch=BATCH, max_spp=MAX_SPP, floor=FLOOR):
-    """one round from `before` to `after` against the model: the chosen set through the counts, untouched pixels, every pixel at its k"""
-    n, inside = F.n, F.inside
-    chosen, ok, kb = model_pick(before, n, inside, K, batch, max_spp, floor)
-    assert int(picked) == len(chosen) == min(K, int(ok.sum()))
-    k0 = state_parts(before["state"], n)[3]
-    S1, SL1, Q1, k1 = state_parts(after["state"], n)
-    want = k0.copy()
-    want[chosen] += batch
-    assert np.array_equal(k1[inside], want[inside])
-    assert np.array_equal(after["spp"][inside], want[inside])
-    # every untouched element — the padding included — keeps all its bits
-    hit = np.zeros(n, bool)
-    hit[chosen] = True
-    S0, SL0, Q0, _ = state_parts(before["state"], n)
-    for a, b in ((before["fb"], after["fb"]), (before["st"], after["st"]), (before["spp"], after["spp"]), (u32(S0), u32(S1)),
-                 (u32(SL0), u32(SL1)), (u32(Q0), u32(Q1)), (k0, k1)):
-        assert np.array_equal(a[~hit], b[~hit])
-    assert (after["spp"][~inside] == SENTINEL).all() and (after["fb"][~inside] == SENTINEL).all()
-    assert (after["state"].view(np.uint32).reshape(6, n)[3:, ~inside] == 0xA5A5A5A5).all() and (u32(S1)[~inside] == 0xA5A5A5A5).all()
-    check_exact(sc, F, after)
-    return chosen, ok
-
-
-def check_exact(sc, F, snap, floor=FLOOR):
-    """for every distinct k of the frame: fb, the RNG state and the state's sums at the pixels with that k are the k-sample frame's"""
-    n, inside = F.n, F.inside
-    S, SL, Q, k = state_parts(snap["state"], n)
-    for kv in np.unique(k[inside]):
-        ref = sc.at_k(F.part, kv, floor)
-        at = inside & (k == kv)
-        rS, rSL, rQ, rk = state_parts(ref["state"], n)
-        assert (rk[inside] == kv).all()
-        assert np.array_equal(snap["fb"][at], ref["fb"][at]), kv
-        assert np.array_equal(snap["st"][at], ref["st"][at]), kv
-        assert np.array_equal(u32(S[at]), u32(rS[at])) and np.array_equal(u32(SL[at]), u32(rSL[at])) and np.array_equal(u32(Q[at]), u32(rQ[at])), kv
 
 
 @pytest.fixture(scope="module")
@@ -252,7 +112,7 @@ SELECT_PARTS = {"whole": (0, 1, 0, 0), "range_lo": (0, 2, 0, 130), "range_hi": (
 def run_select(rt, torch, ctx, name, part):
     P = rt.Partition(*part)
     n = rt.part_pixels(NX, NY, P)
-    inside = M.inside(NX, NY, part, n)
+    inside = inside_frame(NX, NY, part, n)
     SL, Q, k, K, straddles = build_case(name, n, inside)
     if not inside.all():
         # the padding would win every round if the selection looked at it: the largest finite key, eligible k
@@ -297,14 +157,14 @@ def test_selection_on_written_states(rt, cuda, ctx, name):
 @pytest.mark.parametrize("name", ["three_groups", "mixed_k", "K_above_eligible"])
 def test_selection_never_lists_padding(rt, cuda, ctx, name, part):
     n = rt.part_pixels(NX, NY, rt.Partition(*SELECT_PARTS[part]))
-    assert not M.inside(NX, NY, SELECT_PARTS[part], n).all()              # ragged: the part has padding
+    assert not inside_frame(NX, NY, SELECT_PARTS[part], n).all()              # ragged: the part has padding
     assert run_select(rt, cuda, ctx, name, SELECT_PARTS[part]) > 0
 
 
 def test_selection_model_is_what_the_host_export_computes(rt):
     """the model's key is rt_adaptive_priority's, on the values the cases use"""
     for SL, Q, k in ((4.0, 4.0, 8), (4.0, 3.0, 8), (4.0, 2.5, 8), (4.0, np.inf, 8), (np.nan, 3.0, 8), (4.0, 2.0, 8), (4.0, 1.0e30, 8)):
-        assert u32(rt.adaptive_priority(SL, Q, k, FLOOR))[()] == u32(M.priority(SL, Q, k, FLOOR))[()]
+        assert raw_bits(rt.adaptive_priority(SL, Q, k, FLOOR))[()] == raw_bits(M.priority(SL, Q, k, FLOOR))[()]
 
 
 # ---- 2. one round on a rendered frame ------------------------------------------------------------------------------------------
@@ -343,7 +203,7 @@ def test_rounds_compose(rt, cuda, scene):
         check_round(sc, B, before, B.snap(), p[0], K)        # the model predicts every single round from the state read back
         singles.append(int(p[0]))
     assert list(picked) == singles == Ks
-    same(A.snap(), B.snap())
+    assert_same_snapshots(A.snap(), B.snap())
 
 
 # ---- 4. paths and parts -----------------------------------------------------------------------------------------------------------
@@ -384,7 +244,7 @@ def test_context_on_a_side_stream(rt, cuda, scene):
     F, before, after = one_round(rt, torch, scene, rt.WHOLE, ctx=c, stream=s.cuda_stream)
     assert len(c.times()) == 2                               # begin and the spend
     G, _, ref = one_round(rt, torch, scene, rt.WHOLE)
-    same(after, ref)
+    assert_same_snapshots(after, ref)
     c.close()
 
 
@@ -394,10 +254,10 @@ def test_zero_samples_change_nothing(rt, cuda, scene):
     before = F.snap()
     picked = F.spend(scene.W, scene.O, 0, 2)
     assert list(picked) == [0, 0]
-    same(F.snap(), before)
+    assert_same_snapshots(F.snap(), before)
     picked = F.spend(scene.W, scene.O, BATCH - 1, 1)         # less than one batch: q = 0
     assert list(picked) == [0]
-    same(F.snap(), before)
+    assert_same_snapshots(F.snap(), before)
 
 
 def test_budget_larger_than_the_frame_can_take(rt, cuda, scene):
@@ -421,7 +281,7 @@ def test_budget_larger_than_the_frame_can_take(rt, cuda, scene):
     assert list(picked) == singles
     assert singles[0] > singles[-1]                          # pixels became ineligible on the way
     final = A.snap()
-    same(final, B.snap())
+    assert_same_snapshots(final, B.snap())
     k1 = state_parts(final["state"], A.n)[3]
     grew = k1 > k0
     assert grew.any() and (k1[grew] <= cap).all() and (k1[~grew] == k0[~grew]).all()
@@ -453,8 +313,8 @@ def test_denoiser_accepts_the_state(rt, cuda, scene):
     ref = denoise_var_model.denoise_adaptive(F.fb.cpu().numpy(), hits, F.state.cpu().numpy(), NX, NY, p.levels, p.normal_pow_log2,
                                              p.prefilter, p.sigma_position, p.sigma_variance)
     got = out.cpu().numpy()
-    assert np.array_equal(u32(got), u32(np.asarray(ref, np.float32).reshape(-1)))
-    assert not np.array_equal(u32(got), u32(F.fb.cpu().numpy()))
+    assert np.array_equal(raw_bits(got), raw_bits(np.asarray(ref, np.float32).reshape(-1)))
+    assert not np.array_equal(raw_bits(got), raw_bits(F.fb.cpu().numpy()))
 
 
 # ---- 7. C3 -----------------------------------------------------------------------------------------------------------------------
@@ -477,7 +337,7 @@ def test_c3_spend(rt, cuda):
         assert int(p[0]) == len(chosen) == int(picked[r])
         assert np.array_equal(B.snap()["spp"], want)
     final = A.snap()
-    same(final, B.snap())
+    assert_same_snapshots(final, B.snap())
     check_exact(sc, A, final)
     assert len(np.unique(final["spp"])) >= 3
     sc.close()

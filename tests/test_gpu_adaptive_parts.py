@@ -8,6 +8,9 @@ what rt_render_init(part) wrote)."""
 import numpy as np
 import pytest
 
+from adaptive_frames import adaptive_frame, part_layout, part_tuple
+from bitcmp import raw_bits
+
 pytestmark = pytest.mark.gpu
 
 NX, NY = 203, 77                   # 26 x 10 = 260 tiles: ragged right and top edges; 5 runs of 64 tiles, the last one of 4
@@ -15,42 +18,6 @@ N, SPL = 10000, 32
 MIN, BATCH, MAX = 4, 4, 32
 FLOOR = 0.02
 SENTINEL = 0x7FC0DEAD              # a NaN pattern nothing renders
-RUN = 64
-
-
-def u32(a):
-    return np.ascontiguousarray(a).view(np.uint32)
-
-
-def part_tile(lt, part, nparts, begin, end):
-    """global tile of a part's local tile (rt_amd.h: runs of RT_PART_RUN dealt round-robin, or a range)"""
-    if end > begin:
-        return begin + lt
-    if nparts == 1:
-        return lt
-    return ((lt // RUN) * nparts + part) * RUN + lt % RUN
-
-
-def layout(rt, nx, ny, P):
-    """for every element of a part buffer: its row-major pixel index and whether it lies inside the frame"""
-    n = rt.part_pixels(nx, ny, P)
-    e = np.arange(n, dtype=np.int64)
-    tile = part_tile(e // 64, P.part, P.nparts, P.tile_begin, P.tile_end)
-    tiles_x = (nx + 7) // 8
-    i = (tile % tiles_x) * 8 + (e % 64) % 8
-    j = (tile // tiles_x) * 8 + (e % 64) // 8
-    inside = (i < nx) & (j < ny)
-    return np.where(inside, j * nx + i, 0), inside
-
-
-def whole(rt, torch, W, O, nx, ny, params):
-    st = rt.alloc_rand_state(nx, ny)
-    fb = rt.alloc_fb(nx, ny)
-    spp = torch.full((nx * ny,), -1, dtype=torch.int32, device="cuda")
-    rt.render_init(nx, ny, st)
-    rt.render_adaptive(fb, nx, ny, params, W, st, O, spp)
-    torch.cuda.synchronize()
-    return spp.cpu().numpy(), fb.cpu().numpy().reshape(-1, 3), st.cpu().numpy().view(np.uint32).reshape(-1, 12)
 
 
 def part_render(rt, torch, W, O, nx, ny, params, P, ctx=None, stream=None):
@@ -74,10 +41,10 @@ def check_part(rt, ref, nx, ny, P, got):
     """a part's counts and states against the whole frame through the layout; padding untouched"""
     r_spp, r_fb, r_st = ref
     fb, spp, st, st0 = got
-    pix, inside = layout(rt, nx, ny, P)
-    f = u32(fb.cpu().numpy()).reshape(-1, 3)
+    pix, inside = part_layout(nx, ny, part_tuple(P), rt.part_pixels(nx, ny, P))
+    f = raw_bits(fb.cpu().numpy()).reshape(-1, 3)
     assert np.array_equal(spp[inside], r_spp[pix[inside]]), P
-    assert np.array_equal(f[inside], u32(r_fb)[pix[inside]]), P
+    assert np.array_equal(f[inside], raw_bits(r_fb)[pix[inside]]), P
     assert np.array_equal(st[inside], r_st[pix[inside]]), P
     assert (spp[~inside] == SENTINEL).all() and (f[~inside] == SENTINEL).all(), P
     assert np.array_equal(st[~inside], st0[~inside]), P
@@ -98,14 +65,14 @@ def runs_case(rt, torch, W, O, nx, ny, params, nparts, ref):
     full = rt.alloc_fb(nx, ny)
     rt.assemble(full, staged, nx, ny, nparts)
     torch.cuda.synchronize()
-    assert np.array_equal(u32(full.cpu().numpy()).reshape(-1, 3), u32(ref[1])), nparts
+    assert np.array_equal(raw_bits(full.cpu().numpy()).reshape(-1, 3), raw_bits(ref[1])), nparts
 
 
 def pick_rel_error(rt, torch, W, O, nx, ny, lo, step, hi):
     """the first target of a sweep whose frame mixes >= 3 distinct counts, early stops and capped pixels"""
     for rel in (0.02, 0.03, 0.05, 0.07, 0.1, 0.15, 0.2, 0.3, 0.5):
         P = rt.Adaptive(lo, hi, step, rel, FLOOR)
-        ref = whole(rt, torch, W, O, nx, ny, P)
+        ref = adaptive_frame(rt, torch, W, O, nx, ny, P)
         spp = ref[0]
         if len(np.unique(spp)) >= 3 and (spp < hi).any() and (spp == hi).any():
             return P, ref
@@ -141,7 +108,7 @@ def test_range_parts_equal_the_whole_frame(rt, cuda, scene, starts):
     full = rt.alloc_fb(NX, NY)
     rt.assemble_split(full, staged, NX, NY, starts, stride)
     torch.cuda.synchronize()
-    assert np.array_equal(u32(full.cpu().numpy()).reshape(-1, 3), u32(scene["ref"][1]))
+    assert np.array_equal(raw_bits(full.cpu().numpy()).reshape(-1, 3), raw_bits(scene["ref"][1]))
 
 
 def test_more_parts_than_tiles(rt, cuda, scene):
@@ -169,7 +136,7 @@ def test_one_part_is_the_whole_frame(rt, cuda, scene):
     torch.cuda.synchronize()
     r_spp, r_fb, r_st = scene["ref"]
     assert np.array_equal(spp.cpu().numpy(), r_spp)
-    assert np.array_equal(u32(fb.cpu().numpy()).reshape(-1, 3), u32(r_fb))
+    assert np.array_equal(raw_bits(fb.cpu().numpy()).reshape(-1, 3), raw_bits(r_fb))
     assert np.array_equal(st.cpu().numpy().view(np.uint32).reshape(-1, 12), r_st)
 
 

@@ -15,7 +15,7 @@ import numpy as np
 import pytest
 
 import material_edge_worlds as mw
-from test_gpu_parity import random_rays
+from world_cases import random_rays
 
 pytestmark = pytest.mark.gpu
 NX, NY, NS = 43, 21, 4

@@ -4,28 +4,10 @@ device-resident array, and the frames rendered through both."""
 import numpy as np
 import pytest
 
-from test_gpu_parity import random_world
+from tree_compare import compare
+from world_cases import random_world
 
 pytestmark = pytest.mark.gpu
-
-ARRAYS = ["nodes", "ent_hot", "ent_id", "large_hot", "large_brick", "cs", "hot", "brick", "memb_start", "memb_cell", "cellnode", "bits_index", "cellbits"]
-
-
-def compare(rt, W, spl):
-    H = rt.Octree(W, spl).upload()
-    G = rt.Octree(W, spl, gpu=True)
-    assert H.info() == G.info()
-    assert H.accel_info() == G.accel_info()
-    assert np.array_equal(H.nodes().view(np.uint8), G.nodes().view(np.uint8))                  # OctNode[585], reference numbering
-    hc, hi = H.leaves(); gc, gi = G.leaves()
-    assert np.array_equal(hc, gc) and np.array_equal(hi, gi)                                   # OctLeaf contents, reference numbering
-    for k, name in enumerate(ARRAYS):
-        a, b = H.device_array(k), G.device_array(k)
-        assert a.size == b.size, name
-        if name == "large_hot" and a.size == 0:
-            continue
-        assert np.array_equal(a, b), name
-    return H, G
 
 
 @pytest.mark.parametrize("n,spl", [(22, 30), (500, 30), (8000, 30), (10000, 32), (100000, 320), (2000, 3), (5, 30)])

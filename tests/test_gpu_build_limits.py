@@ -2,7 +2,7 @@
 tests/build_limit_worlds.py; tests/test_build_limit_worlds_host.py shows on the CPU that `at_cap` has exactly cap = 16 n + 65536
 (level-3 cell, sphere) pairs and `over_cap` one more.  Every case states the build its tree must have come from
 (rt_octree_build_path) and every comparison is bit equality: trees against the host build Octree(W, spl) through
-test_gpu_build.compare (infos, nodes, leaves, the 13 device arrays; binary16: arrays 0-2), frames (43 x 21, 4 spp, create_world's
+tree_compare.compare (infos, nodes, leaves, the 13 device arrays; binary16: arrays 0-2), frames (43 x 21, 4 spp, create_world's
 camera, framebuffer and written-back RNG states) and 4096 hit records against OracleScene(custom=...).
 
   a. at_cap: the device builds - 4097 leaves at SPHERES_PER_LEAF 17, drops in every cell at 16, a large list of 133 spheres whose
@@ -24,8 +24,8 @@ import pytest
 
 import build_limit_worlds as bw
 import reference_cases as rc
-from test_gpu_build import compare
-from test_gpu_grid_thresholds import compare_empty
+from bitcmp import same_nan_as_ref
+from tree_compare import compare, compare_empty
 
 pytestmark = pytest.mark.gpu
 NX, NY, NS = bw.NX, bw.NY, bw.NS
@@ -53,7 +53,7 @@ def oracle_records(rt, name, fp16, spl):
 
 # ---------------------------------------------------------------------------------------------------- helpers
 def compare16(rt, W, spl):
-    """test_gpu_build.compare for a binary16 world (as test_device_build_of_binary16_trees): infos, nodes, leaves, arrays 0-2"""
+    """tree_compare.compare for a binary16 world (as test_device_build_of_binary16_trees): infos, nodes, leaves, arrays 0-2"""
     H = rt.Octree(W, spl).upload()
     G = rt.Octree(W, spl, gpu=True)
     assert H.info() == G.info()
@@ -101,7 +101,7 @@ def assert_frame(got, want, fp16, what):
         assert np.array_equal(fb.view(np.uint16)[~nan], ref.astype(np.float16).view(np.uint16)[~nan]), what
         assert np.isnan(fb[nan]).all(), what
     else:
-        assert rc.same(fb, ref), what
+        assert same_nan_as_ref(fb, ref), what
     assert np.array_equal(st[:, :6], ref_st[:, :6]), what
 
 
@@ -118,7 +118,7 @@ def assert_frames_and_rays(rt, torch, W, O, name, fp16, spl):
         got = d_out.cpu().numpy().view(rt.hit_record_dtype)
         assert np.array_equal(got["sphere"], ref["sphere"]), ("rays", trav)
         for f in ("t", "p", "normal"):
-            assert rc.same(got[f], ref[f]), ("rays", trav, f)
+            assert same_nan_as_ref(got[f], ref[f]), ("rays", trav, f)
 
 
 # ---------------------------------------------------------------------------------------------------- a. at the limit

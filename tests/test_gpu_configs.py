@@ -13,13 +13,10 @@ import threading
 import numpy as np
 import pytest
 
+from bitcmp import f32_bits
 from oracle_lib import OracleScene, ppm_bytes
 
 pytestmark = pytest.mark.gpu
-
-
-def bits(a):
-    return np.ascontiguousarray(a, np.float32).view(np.uint32)
 
 
 def oracle_rows(S, ns, rows):
@@ -64,7 +61,7 @@ def test_c2_real_workload_list_path_against_the_oracle(rt, cuda):
     rows = (2, 120, 250, 316, 317, 431, 640, 798)
     ref = oracle_rows(S, ns, rows)
     for r in rows:
-        assert np.array_equal(bits(got[r]), bits(ref[r][0][0])), "row %d differs" % r
+        assert np.array_equal(f32_bits(got[r]), f32_bits(ref[r][0][0])), "row %d differs" % r
         assert np.array_equal(st_host[r][:, :6], ref[r][1][:, :6]), "RNG state of row %d differs" % r
     W.set_list_traversal(rt.TRAVERSAL_REFERENCE)
     fb2, st2 = render(rt, torch, W, None, nx, ny, ns)
@@ -121,7 +118,7 @@ def test_c5_real_workload_8_part_split_against_the_oracle(rt, cuda):
     st_host = st.cpu().numpy().view(np.uint32).reshape(ny, nx, 12)
     bg.join()
     for r in rows:
-        assert np.array_equal(bits(got[r]), bits(ref[r][0][0])), "row %d differs" % r
+        assert np.array_equal(f32_bits(got[r]), f32_bits(ref[r][0][0])), "row %d differs" % r
         assert np.array_equal(st_host[r][:, :6], ref[r][1][:, :6]), "RNG state of row %d differs" % r
 
 
@@ -150,7 +147,7 @@ def test_image_writers_from_a_device_frame(rt, cuda, tmp_path):
     raw = pfm.read_bytes()
     head = b"PF\n%d %d\n-1.0\n" % (nx, ny)
     assert raw.startswith(head)
-    assert np.array_equal(np.frombuffer(raw[len(head):], "<u4"), bits(ref).ravel())
+    assert np.array_equal(np.frombuffer(raw[len(head):], "<u4"), f32_bits(ref).ravel())
     # binary16 frame: the same three writers on the float images of the halves
     W16 = rt.World(n, nx, ny, precision=rt.FP16)
     O16 = rt.Octree(W16, spl)
@@ -186,13 +183,13 @@ def test_c3_full_size_progressive_64_passes(rt, cuda):
     assert torch.equal(st.view(torch.uint8), st_whole.view(torch.uint8))              # RNG continuation over 64 launches = one launch of 64
     acc = fb.cpu().numpy().reshape(ny, nx, 3)
     shown = np.sqrt(acc * np.float32(1.0 / 64.0))                                     # exact scale, correctly rounded sqrt
-    assert np.array_equal(bits(shown), bits(whole.cpu().numpy().reshape(ny, nx, 3)))
+    assert np.array_equal(f32_bits(shown), f32_bits(whole.cpu().numpy().reshape(ny, nx, 3)))
     S = OracleScene(n, nx, ny, use_octree=True, spl=spl)
     rows = (3, 250, 316, 317, 600, 797)
     ref = oracle_rows(S, ns, rows)
     st_host = st.cpu().numpy().view(np.uint32).reshape(-1, 12)
     for r in rows:
-        assert np.array_equal(bits(shown[r]), bits(ref[r][0][0])), "row %d differs" % r
+        assert np.array_equal(f32_bits(shown[r]), f32_bits(ref[r][0][0])), "row %d differs" % r
         assert np.array_equal(st_host[r * nx:(r + 1) * nx, :6], ref[r][1][:, :6]), "RNG states of row %d differ" % r
     O.set_traversal(rt.TRAVERSAL_REFERENCE)                                           # the literal traverseTree scan, per-lane kernel
     assert rt.render_kernel_name(W, O, 1) == "k_render<true,1,1>"

@@ -8,23 +8,14 @@ import numpy as np
 import pytest
 
 import denoise_model
+from bitcmp import f32_bits, same_any_nan
 from oracle_lib import OracleScene
+from tree_compare import traced
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NX, NY = 203, 77                   # ragged: neither a multiple of the 16x16 filter tile nor of the 8x8 render tile
 N, SPL = 10000, 32
-
-
-def u32(a):
-    return np.ascontiguousarray(a, np.float32).view(np.uint32)
-
-
-def same(a, b):
-    """bit equality, except that any two NaNs are equal (sqrtf of a NaN need not keep its payload)"""
-    a, b = np.asarray(a, np.float32), np.asarray(b, np.float32)
-    na, nb = np.isnan(a), np.isnan(b)
-    return bool(np.array_equal(na, nb) and np.array_equal(u32(a[~na]), u32(b[~nb])))
 
 
 def gpu_guides(rt, torch, W, O, nx, ny):
@@ -34,18 +25,10 @@ def gpu_guides(rt, torch, W, O, nx, ny):
     return d, d.cpu().numpy().view(rt.hit_record_dtype)
 
 
-def traced(rt, torch, W, O, rays):
-    d_rays = torch.from_numpy(rays).cuda()
-    d_out = torch.zeros(rays.shape[0] * 32, dtype=torch.uint8, device="cuda")
-    rt.trace_rays(W, O, d_rays, rays.shape[0], d_out)
-    torch.cuda.synchronize()
-    return d_out.cpu().numpy().view(rt.hit_record_dtype)
-
-
 def assert_records_equal(got, ref):
     assert np.array_equal(got["sphere"], ref["sphere"])
     for f in ("t", "p", "normal"):
-        assert np.array_equal(u32(got[f]), u32(ref[f])), f
+        assert np.array_equal(f32_bits(got[f]), f32_bits(ref[f])), f
 
 
 def rendered(rt, torch, W, O, nx, ny, ns):
@@ -148,7 +131,7 @@ def test_denoise_matches_the_model(rt, cuda, scene, mode, kw):
     fb = scene[mode]
     got = run(rt, torch, fb, scene["d_hits"], NX, NY, p)
     ref = model(rt, fb.cpu().numpy(), scene["hits"], NX, NY, p)
-    assert np.array_equal(u32(got), u32(ref))
+    assert np.array_equal(f32_bits(got), f32_bits(ref))
     assert np.isfinite(got).all()
     if mode == "gamma":
         assert not np.array_equal(got, fb.cpu().numpy())                           # the filter did something
@@ -161,7 +144,7 @@ def test_denoise_in_place(rt, cuda, scene, mode):
     ref = run(rt, torch, scene[mode], scene["d_hits"], NX, NY, p)
     buf = scene[mode].clone()
     got = run(rt, torch, buf, scene["d_hits"], NX, NY, p, out=buf)
-    assert np.array_equal(u32(got), u32(ref))
+    assert np.array_equal(f32_bits(got), f32_bits(ref))
 
 
 @pytest.mark.parametrize("mode", ["gamma", "sum"])
@@ -183,15 +166,15 @@ def test_pass_through_pixels(rt, cuda, scene, mode):
     p = rt.denoise_params(rt.DENOISE_INPUT_SUM if mode == "sum" else rt.DENOISE_INPUT_GAMMA, 8, levels=5)
     got = run(rt, torch, fb, scene["d_hits"], NX, NY, p)
     ref = model(rt, host.reshape(-1), scene["hits"], NX, NY, p)
-    assert same(got, ref)
+    assert same_any_nan(got, ref)
     g3 = got.reshape(-1, 3)
     if mode == "gamma":
         keep = sky.copy()
         keep[bad] = True
-        assert np.array_equal(u32(g3[keep]), u32(host[keep]))                    # the exact input bits
-        assert np.array_equal(u32(g3), u32(ref.reshape(-1, 3)))
+        assert np.array_equal(f32_bits(g3[keep]), f32_bits(host[keep]))                    # the exact input bits
+        assert np.array_equal(f32_bits(g3), f32_bits(ref.reshape(-1, 3)))
     else:
-        assert same(g3[sky], np.sqrt(host[sky] / np.float32(8)))
+        assert same_any_nan(g3[sky], np.sqrt(host[sky] / np.float32(8)))
     fine = np.ones(NX * NY, bool)
     fine[bad] = False
     assert np.isfinite(g3[fine]).all()                                              # nothing leaked into a neighbour
@@ -208,7 +191,7 @@ def test_tiny_frames(rt, cuda, nx, ny):
     assert_records_equal(hits, traced(rt, torch, W, O, rays))
     for p in (rt.denoise_params(levels=3), rt.denoise_params(rt.DENOISE_INPUT_SUM, 3, levels=8)):
         got = run(rt, torch, fb, d_hits, nx, ny, p)
-        assert same(got, model(rt, fb.cpu().numpy(), hits, nx, ny, p))
+        assert same_any_nan(got, model(rt, fb.cpu().numpy(), hits, nx, ny, p))
     O.close()
     W.close()
 
@@ -227,7 +210,7 @@ def test_denoise_captured_in_a_graph(rt, cuda, scene):
         out.zero_()
         g.replay()
         torch.cuda.synchronize()
-        assert np.array_equal(u32(out.cpu().numpy()), u32(ref))
+        assert np.array_equal(f32_bits(out.cpu().numpy()), f32_bits(ref))
 
 
 def test_denoised_16spp_is_closer_to_1024spp(rt, cuda):

@@ -9,23 +9,13 @@ import numpy as np
 import pytest
 
 import denoise_var_model
+from bitcmp import f32_bits, same_any_nan
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NX, NY = 203, 77                   # ragged: neither a multiple of the 16x16 filter tile nor of the 8x8 render tile
 N, SPL = 10000, 32
 ADAPT = (4, 64, 4, 0.1, 0.02)      # (min_spp, max_spp, batch, rel_error, floor): pixels stop at many different counts
-
-
-def u32(a):
-    return np.ascontiguousarray(a, np.float32).view(np.uint32)
-
-
-def same(a, b):
-    """bit equality, except that any two NaNs are equal (sqrtf of a NaN need not keep its payload)"""
-    a, b = np.asarray(a, np.float32), np.asarray(b, np.float32)
-    na, nb = np.isnan(a), np.isnan(b)
-    return bool(np.array_equal(na, nb) and np.array_equal(u32(a[~na]), u32(b[~nb])))
 
 
 def gpu_guides(rt, torch, W, O, nx, ny):
@@ -72,7 +62,7 @@ def model(fb, hits, state, nx, ny, p):
 def check_against_model(rt, torch, F, d_hits, hits, nx, ny, p):
     got = run(rt, torch, F.fb, d_hits, F.state, nx, ny, p)
     ref = model(F.fb.cpu().numpy(), hits, F.state.cpu().numpy(), nx, ny, p)
-    assert np.array_equal(u32(got), u32(ref))
+    assert np.array_equal(f32_bits(got), f32_bits(ref))
     return got
 
 
@@ -150,7 +140,7 @@ def test_equals_rt_denoise_on_a_uniform_state(rt, cuda, scene, levels):
     got = run(rt, torch, F.fb, scene["d_hits"], F.state, NX, NY, new).reshape(-1, 3)
     filtered = scene["hits"]["sphere"] != -1
     assert np.isfinite(got[filtered]).all() and filtered.sum() > n // 2
-    assert np.array_equal(u32(got[filtered]), u32(ref[filtered]))
+    assert np.array_equal(f32_bits(got[filtered]), f32_bits(ref[filtered]))
 
 
 # ---- 4. a refinement chain leaves the state of begin(to) -------------------------------------------------------------------------
@@ -165,8 +155,8 @@ def test_refined_state_filters_like_begin(rt, cuda, scene):
     B = Frame(rt, torch, W, O, NX, NY, to)
     a = run(rt, torch, A.fb, scene["d_hits"], A.state, NX, NY, p)
     b = run(rt, torch, B.fb, scene["d_hits"], B.state, NX, NY, p)
-    assert np.array_equal(u32(a), u32(b))
-    assert not np.array_equal(u32(a), u32(first))
+    assert np.array_equal(f32_bits(a), f32_bits(b))
+    assert not np.array_equal(f32_bits(a), f32_bits(first))
 
 
 # ---- 5. in place, pass-through, tiny frames, a graph ---------------------------------------------------------------------------------
@@ -177,7 +167,7 @@ def test_in_place(rt, cuda, scene):
     ref = run(rt, torch, F.fb, scene["d_hits"], F.state, NX, NY, p)
     buf = F.fb.clone()
     got = run(rt, torch, buf, scene["d_hits"], F.state, NX, NY, p, out=buf)
-    assert np.array_equal(u32(got), u32(ref))
+    assert np.array_equal(f32_bits(got), f32_bits(ref))
 
 
 def test_pass_through_pixels(rt, cuda, scene):
@@ -208,10 +198,10 @@ def test_pass_through_pixels(rt, cuda, scene):
     p = rt.denoise_var_params(levels=5)
     got = run(rt, torch, fb, scene["d_hits"], d_state, NX, NY, p)
     ref = model(host.reshape(-1), scene["hits"], state, NX, NY, p)
-    assert np.array_equal(u32(got), u32(ref))
+    assert np.array_equal(f32_bits(got), f32_bits(ref))
     g3 = got.reshape(-1, 3)
-    assert np.array_equal(u32(g3[keep]), u32(host[keep]))                        # the exact input bits
-    assert not np.array_equal(u32(g3[bad[35:40]]), u32(host[bad[35:40]]))        # filtered: its variance is 0, not missing
+    assert np.array_equal(f32_bits(g3[keep]), f32_bits(host[keep]))                        # the exact input bits
+    assert not np.array_equal(f32_bits(g3[bad[35:40]]), f32_bits(host[bad[35:40]]))        # filtered: its variance is 0, not missing
     assert np.isfinite(g3[~sky]).all()                                            # nothing leaked into a neighbour
 
 
@@ -224,7 +214,7 @@ def test_tiny_frames(rt, cuda, nx, ny):
     d_hits, hits = gpu_guides(rt, torch, W, O, nx, ny)
     for p in (rt.denoise_var_params(levels=3), rt.denoise_var_params(levels=8, prefilter=0)):
         got = run(rt, torch, F.fb, d_hits, F.state, nx, ny, p)
-        assert same(got, model(F.fb.cpu().numpy(), hits, F.state.cpu().numpy(), nx, ny, p))
+        assert same_any_nan(got, model(F.fb.cpu().numpy(), hits, F.state.cpu().numpy(), nx, ny, p))
     O.close()
     W.close()
 
@@ -244,7 +234,7 @@ def test_captured_in_a_graph(rt, cuda, scene):
         out.zero_()
         g.replay()
         torch.cuda.synchronize()
-        assert np.array_equal(u32(out.cpu().numpy()), u32(ref))
+        assert np.array_equal(f32_bits(out.cpu().numpy()), f32_bits(ref))
 
 
 # ---- 6. the host program -----------------------------------------------------------------------------------------------------------

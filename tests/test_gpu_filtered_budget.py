@@ -5,7 +5,7 @@ The key kernel is held to tests/filtered_budget_model.py — level 0 of rt_denoi
 line, the set by a plain sort — on states and guides the test writes (ragged against the 16x16 filter tile and the span of the
 selection's blocks, with sky, NaN, Inf, k = 1, a clamped d and a zero variance), on a flat patch where the cut falls between equal
 keys, on all-sky guides, on tiny frames and on a frame with more tiles than blocks.  A spend is checked as tests/
-test_gpu_adaptive_budget.py checks the raw one, whose frames, scenes and per-pixel exactness check this file borrows."""
+test_gpu_adaptive_budget.py checks the raw one, with the frames, scenes and per-pixel exactness check of tests/adaptive_frames.py."""
 import ctypes as C
 
 import numpy as np
@@ -14,18 +14,14 @@ import pytest
 import adaptive_budget_model as B
 import denoise_var_model as V
 import filtered_budget_model as M
-import test_gpu_adaptive_budget as T
-from test_gpu_adaptive_budget import SENTINEL, same, state_parts, u32
+from adaptive_frames import BATCH, check_exact, check_round, check_round_filtered, filt_of, FLOOR, Frame, MAX_SPP, model_pick, Scene, SENTINEL
+from bitcmp import assert_same_snapshots
 
 pytestmark = pytest.mark.gpu
 
-NX, NY = T.NX, T.NY                # 203 x 77: 13 x 5 filter tiles, ragged on both edges; 15631 pixels = 15 full selection spans and a rest
-FLOOR, BATCH, MAX_SPP = T.FLOOR, T.BATCH, T.MAX_SPP
+NX, NY = 203, 77                   # 203 x 77: 13 x 5 filter tiles, ragged on both edges; 15631 pixels = 15 full selection spans and a rest
+N, SPL = 10000, 32
 LOOSE = (4, 64, 4, 0.1, FLOOR)
-
-
-def filt_of(p):
-    return (p.normal_pow_log2, p.prefilter, p.sigma_position, p.sigma_variance)
 
 
 def upload_hits(torch, hits):
@@ -70,11 +66,7 @@ def ctx(rt, cuda):
 
 @pytest.fixture(scope="module")
 def scene(rt, cuda):
-    sc = T.Scene(rt, cuda, T.N, T.SPL, NX, NY)
-    sc.d_hits = rt.alloc_guides(NX, NY)
-    rt.render_guides(sc.W, sc.O, NX, NY, sc.d_hits)
-    cuda.cuda.synchronize()
-    sc.hits = sc.d_hits.cpu().numpy().view(rt.hit_record_dtype)
+    sc = Scene(rt, cuda, N, SPL, NX, NY).with_guides()
     yield sc
     sc.close()
 
@@ -155,7 +147,7 @@ def test_tiny_frames(rt, cuda, ctx, nx, ny):
     torch = cuda
     W = rt.World(500, nx, ny)
     O = rt.Octree(W, 30)
-    F = T.Frame(rt, torch, nx, ny, rt.WHOLE).begin(W, O, (4, 32, 4, 0.1, FLOOR))
+    F = Frame(rt, torch, nx, ny, rt.WHOLE).begin(W, O, (4, 32, 4, 0.1, FLOOR))
     d_hits = rt.alloc_guides(nx, ny)
     rt.render_guides(W, O, nx, ny, d_hits)
     torch.cuda.synchronize()
@@ -175,37 +167,6 @@ def test_more_tiles_than_blocks(rt, cuda, ctx):
 
 
 # ---- 6. a rendered frame: rounds compose, every round is the model's, every pixel is exact ------------------------------------------
-class Frame(T.Frame):
-    def spend_filtered(self, sc, p, samples, rounds, batch=BATCH, max_spp=MAX_SPP, floor=FLOOR):
-        picked = self.torch.full((rounds,), SENTINEL, dtype=self.torch.int32, device="cuda")
-        Bd = self.rt.Budget(samples, rounds, batch, max_spp, floor)
-        if self.ctx is not None:
-            self.torch.cuda.synchronize()                    # (the fill above runs on the current stream, the spend on the context's)
-            self.ctx.render_adaptive_spend_filtered(self.fb, self.nx, self.ny, Bd, p, sc.d_hits, sc.W, self.st, self.state, sc.O, self.spp, picked,
-                                                    stream=self.stream)
-        else:
-            self.rt.render_adaptive_spend_filtered(self.fb, self.nx, self.ny, Bd, p, sc.d_hits, sc.W, self.st, self.state, sc.O, self.spp, picked)
-        self.torch.cuda.synchronize()
-        return picked.cpu().numpy().view(np.uint32)
-
-
-def check_round(sc, F, before, after, picked, K, p, batch=BATCH, max_spp=MAX_SPP):
-    """one filtered round from `before` to `after`: the model's set on the snapshot, untouched pixels keep every bit"""
-    n = F.n
-    chosen, ok, _ = M.select(sc.hits, before["state"], F.nx, F.ny, batch, max_spp, FLOOR, K, filt_of(p))
-    assert int(picked) == len(chosen) == min(K, int(ok.sum()))
-    S0, SL0, Q0, k0 = state_parts(before["state"], n)
-    S1, SL1, Q1, k1 = state_parts(after["state"], n)
-    want = k0.copy()
-    want[chosen] += batch
-    assert np.array_equal(k1, want) and np.array_equal(after["spp"], want)
-    hit = np.zeros(n, bool)
-    hit[chosen] = True
-    for a, b in ((before["fb"], after["fb"]), (before["st"], after["st"]), (u32(S0), u32(S1)), (u32(SL0), u32(SL1)), (u32(Q0), u32(Q1))):
-        assert np.array_equal(a[~hit], b[~hit])
-    return chosen
-
-
 def rounds_compose(rt, torch, sc, p, ctx=None, stream=None):
     A = Frame(rt, torch, sc.nx, sc.ny, rt.WHOLE, ctx, stream).begin(sc.W, sc.O, LOOSE)
     Bf = Frame(rt, torch, sc.nx, sc.ny, rt.WHOLE).begin(sc.W, sc.O, LOOSE)
@@ -219,12 +180,12 @@ def rounds_compose(rt, torch, sc, p, ctx=None, stream=None):
     for K in Ks:
         before = Bf.snap()
         pk = Bf.spend_filtered(sc, p, K * BATCH, 1)
-        check_round(sc, Bf, before, Bf.snap(), pk[0], K, p)
+        check_round_filtered(sc, Bf, before, Bf.snap(), pk[0], K, p)
         singles.append(int(pk[0]))
     assert list(picked) == singles and sum(singles) > q // 2      # (check_round held every count to min(K_r, eligible))
     final = A.snap()
-    same(final, Bf.snap())
-    T.check_exact(sc, A, final)
+    assert_same_snapshots(final, Bf.snap())
+    check_exact(sc, A, final)
     assert len(np.unique(final["spp"])) >= 3
     return A, final
 
@@ -237,18 +198,14 @@ def test_rendered_frame_rounds_compose(rt, cuda, scene):
     snap = F.snap()
     K = F.n // 6
     f_set = M.select(scene.hits, snap["state"], NX, NY, BATCH, MAX_SPP, FLOOR, K, filt_of(p))[0]
-    r_set = T.model_pick(snap, F.n, F.inside, K)[0]
+    r_set = model_pick(snap, F.n, F.inside, K)[0]
     assert len(f_set) == len(r_set) == K and not np.array_equal(f_set, r_set)
 
 
 # ---- 7. other paths and mixing ---------------------------------------------------------------------------------------------------
 def test_list_path(rt, cuda):
-    sc = T.Scene(rt, cuda, 500, None, 131, 71, 0)
+    sc = Scene(rt, cuda, 500, None, 131, 71, 0).with_guides()
     assert rt.render_kernel_name(sc.W, sc.O) == "k_render<false,0,1>"
-    sc.d_hits = rt.alloc_guides(131, 71)
-    rt.render_guides(sc.W, sc.O, 131, 71, sc.d_hits)
-    cuda.cuda.synchronize()
-    sc.hits = sc.d_hits.cpu().numpy().view(rt.hit_record_dtype)
     rounds_compose(rt, cuda, sc, rt.denoise_var_params())
     sc.close()
 
@@ -269,12 +226,12 @@ def test_raw_spend_then_filtered_spend(rt, cuda, scene):
     before = F.snap()
     pk = F.spend(sc.W, sc.O, 3000 * BATCH, 1)
     mid = F.snap()
-    T.check_round(sc, F, before, mid, pk[0], 3000)
+    check_round(sc, F, before, mid, pk[0], 3000)
     pk = F.spend_filtered(sc, p, 2500 * BATCH, 1)
     after = F.snap()
-    check_round(sc, F, mid, after, pk[0], 2500, p)
+    check_round_filtered(sc, F, mid, after, pk[0], 2500, p)
     pk = F.spend(sc.W, sc.O, 1000 * BATCH, 1)                # ... and back
-    T.check_round(sc, F, after, F.snap(), pk[0], 1000)
+    check_round(sc, F, after, F.snap(), pk[0], 1000)
 
 
 # ---- 8. errors on the device -----------------------------------------------------------------------------------------------------
@@ -282,14 +239,14 @@ def test_binary16_and_contracted_worlds_are_refused(rt, cuda, scene):
     torch = cuda
     F = Frame(rt, torch, NX, NY, rt.WHOLE)
     p, Bd = rt.denoise_var_params(), rt.Budget(4000, 1, BATCH, MAX_SPP, FLOOR)
-    w16 = rt.World(T.N, NX, NY, precision=rt.FP16)
-    wc = rt.World(T.N, NX, NY)
+    w16 = rt.World(N, NX, NY, precision=rt.FP16)
+    wc = rt.World(N, NX, NY)
     wc.set_arith(rt.ARITH_CONTRACT)
     before = F.snap()
     for W in (w16, wc):
         with pytest.raises(rt.RtError, match="-4"):
             rt.render_adaptive_spend_filtered(F.fb, NX, NY, Bd, p, scene.d_hits, W, F.st, F.state, None, F.spp)
-    same(F.snap(), before)
+    assert_same_snapshots(F.snap(), before)
     w16.close()
     wc.close()
 
@@ -315,7 +272,7 @@ def test_refused_during_a_capture(rt, cuda, scene, ctx):
     assert rc_spend == -1 and rc_select == -1
     g.replay()
     torch.cuda.synchronize()
-    same(F.snap(), before)
+    assert_same_snapshots(F.snap(), before)
     assert float(marker.sum()) == 4.0 and int(cnt.cpu().numpy()[0]) == 0
 
 
@@ -327,9 +284,7 @@ def test_c3_filtered_budget_against_uniform(rt, cuda):
     torch = cuda
     nx, ny = 1200, 800
     n = nx * ny
-    sc = T.Scene(rt, torch, 10000, 32, nx, ny)
-    sc.d_hits = rt.alloc_guides(nx, ny)
-    rt.render_guides(sc.W, sc.O, nx, ny, sc.d_hits)
+    sc = Scene(rt, torch, 10000, 32, nx, ny).with_guides()
     st, fb = rt.alloc_rand_state(nx, ny), rt.alloc_fb(nx, ny)
     rt.render_init(nx, ny, st)
     rt.render(fb, nx, ny, 1024, sc.W, st, sc.O)

@@ -2,7 +2,7 @@
 through rt_trace_rays (fast and reference traversal), rt_build_octree_gpu, rt_render_guides, rt_render and rt_render_progressive.
 
 Every comparison is bit equality with the CPU oracle's hitable_list::hit / hitTree and render, "NaN where the oracle has NaN"
-(reference_cases.same); no ray and no pixel is left out.  tests/test_grid_threshold_worlds_host.py shows on the CPU that every world
+(bitcmp.same_nan_as_ref); no ray and no pixel is left out.  tests/test_grid_threshold_worlds_host.py shows on the CPU that every world
 reaches the threshold it is named for, that the host build files it as the float64 model does, and that the rays fall to both sides
 of every precondition of the walk and graze.  Here:
   * hit records: origins on the near zone's boundary aimed at grazing spheres at the centre bound on the far side (|o - c| up to
@@ -21,8 +21,9 @@ import denoise_model
 import grid_threshold_worlds as gw
 import material_edge_worlds as mw
 import reference_cases as rc
-from test_gpu_build import compare
-from test_gpu_parity import gpu_render
+from bitcmp import same_nan_as_ref
+from gpu_frames import render_frame, states_of
+from tree_compare import assert_records, compare, compare_empty, traced
 
 pytestmark = pytest.mark.gpu
 
@@ -46,10 +47,6 @@ def kernel(name, variant, mode, k=0):
     return "k_render<%s,%d,%d>" % ("false" if (mode == "list" and v == 1) else "true", k, v)
 
 
-def states_of(st):
-    return st.cpu().numpy().view(np.uint32).reshape(-1, 12)
-
-
 def make(rt, name, variant, mode, spl, cam="own"):
     sp, c = gw.world(name, variant, NX, NY, cam)
     W = mw.gpu_world(rt, sp, c, NX, NY)
@@ -69,20 +66,6 @@ def oracle_records(name, variant, mode, spl):
             a.setflags(write=False)
         out[fam] = (rays, ref)
     return out
-
-
-def traced(rt, torch, W, O, rays):
-    d_rays = torch.from_numpy(np.array(rays)).cuda()
-    d_out = torch.zeros(len(rays) * 32, dtype=torch.uint8, device="cuda")
-    rt.trace_rays(W, O, d_rays, len(rays), d_out)
-    torch.cuda.synchronize()
-    return d_out.cpu().numpy().view(rt.hit_record_dtype)
-
-
-def assert_records(got, ref, label):
-    assert np.array_equal(got["sphere"], ref["sphere"]), label
-    for f in ("t", "p", "normal"):
-        assert rc.same(got[f], ref[f]), (label, f)
 
 
 def test_every_case_has_its_variant_stated_and_all_are_reached():
@@ -109,26 +92,6 @@ def test_hit_records(rt, cuda, name, variant, mode, spl):
 
 
 # ---------------------------------------------------------------------------------------------------- device build
-def compare_empty(rt, W, spl):
-    """test_gpu_build.compare for a tree that stores no sphere: there is no grid, and the contents of the grid arrays are unspecified
-    (no kernel reads them while enabled == 0; the device build leaves them unset).  The comparison covers the infos, the
-    reference-layout nodes and leaves, the traversal nodes and the (empty) entry arrays, and the sizes rt_octree_debug_array states for
-    the grid arrays of either build"""
-    H = rt.Octree(W, spl).upload()
-    G = rt.Octree(W, spl, gpu=True)
-    assert H.info() == G.info() and H.info()["flat_entries"] == 0
-    assert H.accel_info() == G.accel_info() == dict(grid_dim=0, cell_size=0.0, grid_entries=0, large_spheres=0)
-    assert np.array_equal(H.nodes().view(np.uint8), G.nodes().view(np.uint8))
-    hc, hi = H.leaves(); gc, gi = G.leaves()
-    assert np.array_equal(hc, gc) and np.array_equal(hi, gi) and not hc.any()
-    for k in range(3):
-        a, b = H.device_array(k), G.device_array(k)
-        assert a.size == b.size and np.array_equal(a, b), k
-    for k in range(3, 13):
-        assert H.device_array(k).size == G.device_array(k).size, k
-    return H, G
-
-
 @pytest.mark.parametrize("name,variant,mode,spl", TREES, ids=[i for i, c in zip(IDS, gw.CASES) if c[2] == "tree"])
 def test_device_build_equals_host_build(rt, cuda, name, variant, mode, spl):
     """all 13 device arrays, nodes, leaves and infos of rt_build_octree_gpu equal the host build's, and both are the model's grid"""
@@ -177,9 +140,9 @@ def test_guides_and_frames(rt, cuda, name, variant, mode, spl, cam):
     ref = gw.oracle(sp, c, mode == "tree", spl).trace(rays, mode=2 if mode == "tree" else 1)
     assert_records(d.cpu().numpy().view(rt.hit_record_dtype), ref, "guides")
     assert (ref["sphere"] >= 0).sum() > NX * NY // 4
-    fb, st = gpu_render(rt, torch, W, O, NX, NY, NS)
+    fb, st = render_frame(rt, torch, W, O, NX, NY, NS)
     want, want_st = oracle_frame(name, variant, mode, spl, cam, NS)
-    assert rc.same(fb.cpu().numpy().reshape(NY, NX, 3), want)
+    assert same_nan_as_ref(fb.cpu().numpy().reshape(NY, NX, 3), want)
     assert np.array_equal(states_of(st)[:, :6], want_st[:, :6])
 
 
@@ -188,9 +151,9 @@ def test_frame_with_the_long_chain_pass(rt, cuda):
     torch = cuda
     ns = 16
     sp, c, W, O = make(rt, "rlim", None, "tree", 30)
-    fb, st = gpu_render(rt, torch, W, O, NX, NY, ns)
+    fb, st = render_frame(rt, torch, W, O, NX, NY, ns)
     want, want_st = oracle_frame("rlim", None, "tree", 30, "own", ns)
-    assert rc.same(fb.cpu().numpy().reshape(NY, NX, 3), want)
+    assert same_nan_as_ref(fb.cpu().numpy().reshape(NY, NX, 3), want)
     assert np.array_equal(states_of(st)[:, :6], want_st[:, :6])
 
 
@@ -205,12 +168,12 @@ def test_parts_and_progressive_passes(rt, cuda, name, variant, mode, spl):
     per = rt.part_pixels(NX, NY, rt.Partition(0, nparts))
     parts = torch.zeros(nparts * per * 3, dtype=torch.float32, device="cuda")
     for p in range(nparts):
-        fb, _ = gpu_render(rt, torch, W, O, NX, NY, NS, rt.Partition(p, nparts))
+        fb, _ = render_frame(rt, torch, W, O, NX, NY, NS, rt.Partition(p, nparts))
         parts[p * per * 3: p * per * 3 + fb.numel()] = fb
     full = torch.zeros(NX * NY * 3, dtype=torch.float32, device="cuda")
     rt.assemble(full, parts, NX, NY, nparts)
     torch.cuda.synchronize()
-    assert rc.same(full.cpu().numpy().reshape(NY, NX, 3), want)
+    assert same_nan_as_ref(full.cpu().numpy().reshape(NY, NX, 3), want)
     S = gw.oracle(sp, c, mode == "tree", spl)
     st = rt.alloc_rand_state(NX, NY); fb = rt.alloc_fb(NX, NY)
     rt.render_init(NX, NY, st)
@@ -220,5 +183,5 @@ def test_parts_and_progressive_passes(rt, cuda, name, variant, mode, spl):
         rt.render_progressive(fb, NX, NY, k, W, st, O)
         S.render_progressive(ref, k, ref_st, nthreads=8)
         torch.cuda.synchronize()
-        assert rc.same(fb.cpu().numpy().reshape(NY, NX, 3), ref), k
+        assert same_nan_as_ref(fb.cpu().numpy().reshape(NY, NX, 3), ref), k
         assert np.array_equal(states_of(st)[:, :6], ref_st[:, :6]), k

@@ -3,7 +3,7 @@ accelerator builds, on the worlds of tests/material_edge_worlds.py — several r
 table of world_upload), ref_idx below 1, 0, negative, inf and NaN, negative radii (shells, rooms no path leaves: every pixel a long
 chain that ends at the depth limit), albedo 0 and 1e30, fuzz 0 and 1, radius 0 / NaN / inf, lens radius 0, slot 0 a ghost or the room.
 
-Every comparison is bit equality with the CPU oracle; a NaN compares as "NaN where the oracle has NaN" (same, test_gpu_reference_edges).
+Every comparison is bit equality with the CPU oracle; a NaN compares as "NaN where the oracle has NaN" (bitcmp.same_nan_as_ref).
 tests/test_material_edge_worlds_host.py shows on the oracle alone that each world reaches the branch it is named for.
 
 Two statements of the issue this file was written for are restated, because the code (rightly) does otherwise:
@@ -16,30 +16,16 @@ import numpy as np
 import pytest
 
 import material_edge_worlds as mw
-from test_gpu_adaptive import adaptive, model, pick_rel_error, progressive_samples
-from test_gpu_build import compare
-from test_gpu_parity import f32_to_half_bits, gpu_render, half_bits
-from test_gpu_reference_edges import same
+from adaptive_frames import adaptive_frame, pick_rel_error, progressive_samples, stop_rule_model
+from bitcmp import f32_bits, same_nan_as_ref
+from gpu_frames import render_frame, states_of
+from tree_compare import compare
+from world_cases import f32_to_half_bits, half_bits
 
 pytestmark = pytest.mark.gpu
 
 NX, NY, NS, SPL = 64, 40, 16, 30
 FLOOR = 0.02
-
-
-def bits(a):
-    return np.ascontiguousarray(a, np.float32).view(np.uint32)
-
-
-def same_bits(got, ref):
-    """bit-equal; NaN where the oracle has NaN"""
-    got, ref = np.asarray(got, np.float32), np.asarray(ref, np.float32)
-    nan = np.isnan(ref)
-    return np.array_equal(bits(got)[~nan], bits(ref)[~nan]) and np.isnan(got[nan]).all()
-
-
-def states_of(st):
-    return st.cpu().numpy().view(np.uint32).reshape(-1, 12)
 
 
 def make(rt, name, variant=None, nx=NX, ny=NY, tree=False):
@@ -65,7 +51,7 @@ def oracle_frame(name, variant, tree, nx=NX, ny=NY, ns=NS, sp=None, key=None):
 
 def test_the_closed_form_camera_is_the_librarys(rt):
     for nx, ny, aperture in ((NX, NY, None), (61, 35, None), (NX, NY, 0.0), (131, 99, None)):
-        assert np.array_equal(bits(mw.camera_floats(nx, ny, aperture)), bits(mw.library_camera(rt, nx, ny, aperture)))
+        assert np.array_equal(f32_bits(mw.camera_floats(nx, ny, aperture)), f32_bits(mw.library_camera(rt, nx, ny, aperture)))
 
 
 @pytest.mark.parametrize("name,variant", mw.WORLDS)
@@ -106,9 +92,9 @@ def test_hit_records(rt, cuda, name, variant):
         torch.cuda.synchronize()
         got = d_out.cpu().numpy().view(rt.hit_record_dtype)
         assert np.array_equal(got["sphere"], ref["sphere"]), label
-        assert same_bits(got["t"], ref["t"]), label
-        assert same_bits(got["p"], ref["p"]), label
-        assert same_bits(got["normal"], ref["normal"]), label
+        assert same_nan_as_ref(got["t"], ref["t"]), label
+        assert same_nan_as_ref(got["p"], ref["p"]), label
+        assert same_nan_as_ref(got["normal"], ref["normal"]), label
 
 
 # ---------------------------------------------------------------------------------------------------- builds
@@ -157,12 +143,12 @@ FRAMES += [("shells", None, False, 61, 35), ("shells", None, True, 61, 35), ("wh
 def test_frames_fp32(rt, cuda, name, variant, tree, nx, ny):
     """16 spp (the long-chain pass is on), fast traversal: framebuffer and the first 6 words of every RNG state equal the oracle's"""
     _, _, W, O = make(rt, name, variant, nx, ny, tree)
-    fb, st = gpu_render(rt, cuda, W, O, nx, ny, NS)
+    fb, st = render_frame(rt, cuda, W, O, nx, ny, NS)
     ref, ref_st = oracle_frame(name, variant, tree, nx, ny)
-    assert same(fb.cpu().numpy().reshape(ny, nx, 3), ref)
+    assert same_nan_as_ref(fb.cpu().numpy().reshape(ny, nx, 3), ref)
     assert np.array_equal(states_of(st)[:, :6], ref_st[:, :6])
     if name == "white_room":
-        assert (bits(ref) == 0).all()                             # a black frame: the states pin every draw of every bounce
+        assert (f32_bits(ref) == 0).all()                             # a black frame: the states pin every draw of every bounce
 
 
 @pytest.mark.parametrize("name,nx,ny,ns,tree", [("glass_indices", NX, NY, NS, True), ("shells", NX, NY, NS, True), ("tir_room", NX, NY, NS, True),
@@ -197,21 +183,21 @@ def test_two_worlds_that_differ_only_in_their_indices(rt, cuda, tree):
     sp, cam = mw.world("glass_indices", NX, NY, rt=rt)
     twin = mw.with_index(sp, 1.5)
     refs = [oracle_frame("glass_indices", None, tree), oracle_frame("glass_indices", None, tree, sp=twin, key="index 1.5")]
-    assert (bits(refs[0][0]) != bits(refs[1][0])).any(axis=2).mean() >= 0.05
+    assert (f32_bits(refs[0][0]) != f32_bits(refs[1][0])).any(axis=2).mean() >= 0.05
 
     def check(fb, st, which):
         torch.cuda.synchronize()
-        assert same(fb.cpu().numpy().reshape(NY, NX, 3), refs[which][0]), which
+        assert same_nan_as_ref(fb.cpu().numpy().reshape(NY, NX, 3), refs[which][0]), which
         assert np.array_equal(states_of(st)[:, :6], refs[which][1][:, :6]), which
 
     A = mw.gpu_world(rt, sp, cam, NX, NY)
     OA = rt.Octree(A, SPL) if tree else None
-    check(*gpu_render(rt, torch, A, OA, NX, NY, NS), 0)
+    check(*render_frame(rt, torch, A, OA, NX, NY, NS), 0)
     B = mw.gpu_world(rt, twin, cam, NX, NY)
     OB = rt.Octree(B, SPL) if tree else None
     for _ in range(2):
-        check(*gpu_render(rt, torch, B, OB, NX, NY, NS), 1)
-        check(*gpu_render(rt, torch, A, OA, NX, NY, NS), 0)
+        check(*render_frame(rt, torch, B, OB, NX, NY, NS), 1)
+        check(*render_frame(rt, torch, A, OA, NX, NY, NS), 0)
     ctx = rt.RenderCtx()
     for which, (W, O) in enumerate([(A, OA), (B, OB)] * 2):
         # fresh handles for every frame of the shared context
@@ -240,7 +226,7 @@ def test_progressive_passes(rt, cuda, name, tree):
         rt.render_progressive(fb, NX, NY, k, W, st, O)
         S.render_progressive(ref, k, ref_st, nthreads=8)
         torch.cuda.synchronize()
-        assert same(fb.cpu().numpy().reshape(NY, NX, 3), ref), k
+        assert same_nan_as_ref(fb.cpu().numpy().reshape(NY, NX, 3), ref), k
         assert np.array_equal(states_of(st)[:, :6], ref_st[:, :6]), k
     if name == "extremes":
         assert np.isnan(ref).any() and np.isinf(ref).any()
@@ -258,13 +244,13 @@ def test_frames_made_of_long_chains(rt, cuda, name, ns):
     assembled, the bits are the oracle's (at 64 spp for 8 rows of it), and no thin wave is left counted afterwards."""
     torch = cuda
     sp, cam, W, O = make(rt, name, None, LX, LY, tree=True)
-    whole, st = gpu_render(rt, torch, W, O, LX, LY, ns)
+    whole, st = render_frame(rt, torch, W, O, LX, LY, ns)
     assert W.render_counters()["thin_waves"] == 0                 # rt_world_render_counters [1]
     nparts = 3
     per = rt.part_pixels(LX, LY, rt.Partition(0, nparts))
     parts = torch.zeros(nparts * per * 3, dtype=torch.float32, device="cuda")
     for p in range(nparts):
-        fb, _ = gpu_render(rt, torch, W, O, LX, LY, ns, rt.Partition(p, nparts))
+        fb, _ = render_frame(rt, torch, W, O, LX, LY, ns, rt.Partition(p, nparts))
         assert W.render_counters()["thin_waves"] == 0
         parts[p * per * 3: p * per * 3 + fb.numel()] = fb
     full = torch.zeros(LX * LY * 3, dtype=torch.float32, device="cuda")
@@ -278,7 +264,7 @@ def test_frames_made_of_long_chains(rt, cuda, name, ns):
         S = mw.oracle(sp, cam, LX, LY, tree=True, spl=SPL)
         blocks = [(r0, rows) + S.render(ns, row0=r0, rows=rows, nthreads=rows) for r0, rows in ROW_BLOCKS]
     for r0, rows, ref, ref_st in blocks:
-        assert same(got[r0:r0 + rows], ref) and same(got_parts[r0:r0 + rows], ref), r0
+        assert same_nan_as_ref(got[r0:r0 + rows], ref) and same_nan_as_ref(got_parts[r0:r0 + rows], ref), r0
         assert np.array_equal(got_st[r0:r0 + rows].reshape(-1, 12)[:, :6], ref_st[:, :6]), r0
 
 
@@ -294,10 +280,10 @@ def test_adaptive_with_nan_samples(rt, cuda, variant, tree):
     samples, states = progressive_samples(rt, torch, W, O, NX, NY, hi)
     with np.errstate(all="ignore"):
         rel = pick_rel_error(samples, lo, step, hi, FLOOR)
-        m_spp, m_fb = model(samples, rel, FLOOR, lo, step, hi)
-    spp, fb, st = adaptive(rt, torch, W, O, NX, NY, rt.Adaptive(lo, hi, step, rel, FLOOR))
+        m_spp, m_fb = stop_rule_model(samples, rel, FLOOR, lo, step, hi)
+    spp, fb, st = adaptive_frame(rt, torch, W, O, NX, NY, rt.Adaptive(lo, hi, step, rel, FLOOR))
     assert np.array_equal(spp, m_spp)
-    assert same(fb, m_fb)
+    assert same_nan_as_ref(fb, m_fb)
     assert np.array_equal(st, states[spp - 1, np.arange(spp.size)])
     nan_at = np.isnan(samples).any(axis=2)                                        # [sample, pixel]
     took_nan = (nan_at & (np.arange(1, hi + 1)[:, None] <= spp[None, :])).any(axis=0)
@@ -310,5 +296,5 @@ def test_adaptive_with_nan_samples(rt, cuda, variant, tree):
         ok = np.isfinite(samples)
         mean = np.where(ok, samples, 0.0).sum(axis=0) / np.maximum(ok.sum(axis=0), 1)
         patched = np.where(np.isnan(samples), mean[None], samples).astype(np.float32)
-        p_spp, _ = model(patched, rel, FLOOR, lo, step, hi)
+        p_spp, _ = stop_rule_model(patched, rel, FLOOR, lo, step, hi)
     assert (p_spp[took_nan] < hi).sum() >= 1

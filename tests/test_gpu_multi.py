@@ -9,18 +9,10 @@ import sys
 import numpy as np
 import pytest
 
+from gpu_frames import render_frame
+
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-
-
-def whole_frame(rt, torch, W, O, nx, ny, ns, precision=None):
-    precision = rt.FP32 if precision is None else precision
-    st = rt.alloc_rand_state(nx, ny)
-    fb = rt.alloc_fb(nx, ny, precision=precision)
-    rt.render_init(nx, ny, st)
-    rt.render(fb, nx, ny, ns, W, st, O)
-    torch.cuda.synchronize()
-    return fb, st
 
 
 def test_multi_render_one_rank_over_rccl(rt, cuda):
@@ -34,7 +26,7 @@ def test_multi_render_one_rank_over_rccl(rt, cuda):
     full = torch.zeros(nx * ny * 3, dtype=torch.float32, device="cuda")
     M.render(full, nx, ny, ns, W, O)
     torch.cuda.synchronize()
-    fb, _ = whole_frame(rt, torch, W, O, nx, ny, ns)
+    fb, _ = render_frame(rt, torch, W, O, nx, ny, ns)
     assert torch.equal(full.view(torch.int32), fb.view(torch.int32))
     call_ms, kernel_ms = M.last_render_ms()
     assert 0 < kernel_ms <= call_ms

@@ -5,47 +5,12 @@ import hashlib
 import numpy as np
 import pytest
 
+from bitcmp import f32_bits
+from gpu_frames import render_frame
 from oracle_lib import OracleScene, ppm_bytes
+from world_cases import f32_to_half_bits, half_bits, random_rays, random_world
 
 pytestmark = pytest.mark.gpu
-
-
-def bits(a):
-    return np.ascontiguousarray(a, np.float32).view(np.uint32)
-
-
-def gpu_render(rt, torch, W, O, nx, ny, ns, part=None):
-    part = part or rt.WHOLE
-    st = rt.alloc_rand_state(nx, ny, part)
-    fb = rt.alloc_fb(nx, ny, part)
-    rt.render_init(nx, ny, st, part)
-    rt.render(fb, nx, ny, ns, W, st, O, part)
-    torch.cuda.synchronize()
-    return fb, st
-
-
-def random_rays(n, seed):
-    """rays that exercise the scene: origins around/inside the sphere field, at the camera, far away on the ground;
-    directions random, some axis-aligned (zero components -> inf/NaN slab arithmetic)."""
-    rng = np.random.default_rng(seed)
-    o = np.empty((n, 3), np.float32)
-    d = rng.normal(size=(n, 3)).astype(np.float32)
-    k = n // 4
-    o[:k] = rng.uniform([-11, 0, -11], [11, 2, 11], (k, 3))
-    o[k:2 * k] = np.array([13, 2, 3], np.float32) + rng.normal(scale=0.05, size=(k, 3))
-    tgt = rng.uniform([-11, 0, -11], [11, 0.3, 11], (k, 3))
-    d[k:2 * k] = tgt - o[k:2 * k]
-    o[2 * k:3 * k] = rng.uniform([-300, 0, -300], [300, 40, 300], (k, 3))
-    tgt = rng.uniform([-11, 0, -11], [11, 1, 11], (k, 3))
-    d[2 * k:3 * k] = tgt - o[2 * k:3 * k]
-    o[3 * k:] = rng.uniform([-12, -0.5, -12], [12, 3, 12], (n - 3 * k, 3))
-    # axis-aligned / zero-component directions
-    z = rng.integers(0, n, n // 50)
-    d[z, rng.integers(0, 3, z.size)] = 0.0
-    z = rng.integers(0, n, n // 100)
-    d[z] = 0.0
-    d[z, rng.integers(0, 3, z.size)] = rng.choice([-1.0, 1.0], z.size)
-    return np.ascontiguousarray(np.concatenate([o, d], 1), np.float32)
 
 
 @pytest.mark.parametrize("n,spl", [(22, 30), (500, 30), (10000, 32)])
@@ -71,9 +36,9 @@ def test_trace_hit_records(rt, cuda, n, spl, tree):
     ref = OracleScene(n, 1200, 800, use_octree=tree, spl=spl).trace(rays, mode=2 if tree else 1)
     assert np.array_equal(got["sphere"], ref["sphere"])
     assert ref["hit"].sum() > nrays // 20
-    assert np.array_equal(bits(got["t"]), bits(ref["t"]))
-    assert np.array_equal(bits(got["p"]), bits(ref["p"]))
-    assert np.array_equal(bits(got["normal"]), bits(ref["normal"]))
+    assert np.array_equal(f32_bits(got["t"]), f32_bits(ref["t"]))
+    assert np.array_equal(f32_bits(got["p"]), f32_bits(ref["p"]))
+    assert np.array_equal(f32_bits(got["normal"]), f32_bits(ref["normal"]))
 
 
 def test_trace_hit_records_on_a_dense_grid(rt, cuda):
@@ -97,9 +62,9 @@ def test_trace_hit_records_on_a_dense_grid(rt, cuda):
     ref = OracleScene(n, 3840, 2160, use_octree=True, spl=spl).trace(rays, mode=2)
     for got in outs:
         assert np.array_equal(got["sphere"], ref["sphere"])
-        assert np.array_equal(bits(got["t"]), bits(ref["t"]))
-        assert np.array_equal(bits(got["p"]), bits(ref["p"]))
-        assert np.array_equal(bits(got["normal"]), bits(ref["normal"]))
+        assert np.array_equal(f32_bits(got["t"]), f32_bits(ref["t"]))
+        assert np.array_equal(f32_bits(got["p"]), f32_bits(ref["p"]))
+        assert np.array_equal(f32_bits(got["normal"]), f32_bits(ref["normal"]))
     assert ref["hit"].sum() > nrays // 20
 
 
@@ -114,11 +79,11 @@ def test_render_small_frames(rt, cuda, n, nx, ny, ns, tree, spl):
     torch = cuda
     W = rt.World(n, nx, ny)
     O = rt.Octree(W, spl) if tree else None
-    fb, st = gpu_render(rt, torch, W, O, nx, ny, ns)
+    fb, st = render_frame(rt, torch, W, O, nx, ny, ns)
     S = OracleScene(n, nx, ny, use_octree=tree, spl=spl)
     ref, ref_st = S.render(ns, nthreads=8)
     got = fb.cpu().numpy().reshape(ny, nx, 3)
-    assert np.array_equal(bits(got), bits(ref))
+    assert np.array_equal(f32_bits(got), f32_bits(ref))
     got_st = st.cpu().numpy().view(np.uint32).reshape(-1, 12)
     assert np.array_equal(got_st[:, :6], ref_st[:, :6])
 
@@ -169,7 +134,7 @@ def test_c1_ppm_md5(rt, cuda):
     torch = cuda
     nx, ny, ns = 400, 225, 4
     W = rt.World(22, nx, ny)
-    fb, _ = gpu_render(rt, torch, W, None, nx, ny, ns)
+    fb, _ = render_frame(rt, torch, W, None, nx, ny, ns)
     got = fb.cpu().numpy().reshape(ny, nx, 3)
     ppm = rt.format_ppm(got, nx, ny)
     assert hashlib.md5(ppm).hexdigest() == "bb5ebdd40d476c6a48e7de6a3af3e3ed"
@@ -196,12 +161,12 @@ def test_partition_assemble_equals_whole(rt, cuda, nparts):
     nx, ny, ns, n = 700, 330, 3, 500
     W = rt.World(n, nx, ny)
     O = rt.Octree(W, 30)
-    whole, _ = gpu_render(rt, torch, W, O, nx, ny, ns)
+    whole, _ = render_frame(rt, torch, W, O, nx, ny, ns)
     per = rt.part_pixels(nx, ny, rt.Partition(0, nparts))
     parts = torch.zeros(nparts * per * 3, dtype=torch.float32, device="cuda")
     for p in range(nparts):
         part = rt.Partition(p, nparts)
-        fb, _ = gpu_render(rt, torch, W, O, nx, ny, ns, part)
+        fb, _ = render_frame(rt, torch, W, O, nx, ny, ns, part)
         parts[p * per * 3: p * per * 3 + fb.numel()] = fb
     full = torch.zeros(nx * ny * 3, dtype=torch.float32, device="cuda")
     rt.assemble(full, parts, nx, ny, nparts)
@@ -225,14 +190,14 @@ def test_long_chain_selection_on_ragged_and_partitioned_frames(rt, cuda, nparts)
     n_long = 0
     for p in range(nparts):
         part = rt.Partition(p, nparts)
-        fb, st = gpu_render(rt, torch, W, O, nx, ny, ns, part)
+        fb, st = render_frame(rt, torch, W, O, nx, ny, ns, part)
         c = W.render_counters()
         assert c["thin_waves"] == 0
         assert c["long_handles"] >= c["long_chains"]              # every pre-classified chain was taken (handles past the end find the list empty)
         n_long += c["long_chains"]
         if nparts == 1:
             got = fb.cpu().numpy().reshape(ny, nx, 3)
-            assert np.array_equal(bits(got), bits(ref))
+            assert np.array_equal(f32_bits(got), f32_bits(ref))
             assert np.array_equal(st.cpu().numpy().view(np.uint32).reshape(-1, 12)[:, :6], ref_st[:, :6])
         else:
             parts[p * per * 3: p * per * 3 + fb.numel()] = fb
@@ -240,7 +205,7 @@ def test_long_chain_selection_on_ragged_and_partitioned_frames(rt, cuda, nparts)
         full = torch.zeros(nx * ny * 3, dtype=torch.float32, device="cuda")
         rt.assemble(full, parts, nx, ny, nparts)
         torch.cuda.synchronize()
-        assert np.array_equal(bits(full.cpu().numpy().reshape(ny, nx, 3)), bits(ref))
+        assert np.array_equal(f32_bits(full.cpu().numpy().reshape(ny, nx, 3)), f32_bits(ref))
     assert 0 < n_long <= nx * ny // 64, n_long
 
 
@@ -260,7 +225,7 @@ def test_render_progressive(rt, cuda):
         rt.render_progressive(fb, nx, ny, k, W, st, O)
         S.render_progressive(ref, k, ref_st, nthreads=8)
     torch.cuda.synchronize()
-    assert np.array_equal(bits(fb.cpu().numpy().reshape(ny, nx, 3)), bits(ref))
+    assert np.array_equal(f32_bits(fb.cpu().numpy().reshape(ny, nx, 3)), f32_bits(ref))
     assert np.array_equal(st.cpu().numpy().view(np.uint32).reshape(-1, 12)[:, :6], ref_st[:, :6])
 
 
@@ -273,11 +238,11 @@ def test_full_size_properties_c3(rt, cuda):
     nx, ny, ns, n, spl = 1200, 800, 64, 10000, 32
     W = rt.World(n, nx, ny)
     O = rt.Octree(W, spl)
-    fb, st = gpu_render(rt, torch, W, O, nx, ny, ns)
-    fb2, _ = gpu_render(rt, torch, W, O, nx, ny, ns)
+    fb, st = render_frame(rt, torch, W, O, nx, ny, ns)
+    fb2, _ = render_frame(rt, torch, W, O, nx, ny, ns)
     assert torch.equal(fb.view(torch.int32), fb2.view(torch.int32))
     O.set_traversal(rt.TRAVERSAL_REFERENCE)                    # the exact bucket scan gives the same 61 M samples
-    fb3, st3 = gpu_render(rt, torch, W, O, nx, ny, ns)
+    fb3, st3 = render_frame(rt, torch, W, O, nx, ny, ns)
     O.set_traversal(rt.TRAVERSAL_FAST)
     assert torch.equal(fb.view(torch.int32), fb3.view(torch.int32)) and torch.equal(st, st3)
     got = fb.cpu().numpy().reshape(ny, nx, 3)
@@ -290,7 +255,7 @@ def test_full_size_properties_c3(rt, cuda):
     # thin-wave / cooperative-walk machinery of the render kernel
     for row in (3, 100, 250, 316, 317, 431, 600, 797):
         ref, _ = S.render(ns, row0=row, rows=1, nthreads=4)
-        assert np.array_equal(bits(got[row]), bits(ref[0])), "row %d differs" % row
+        assert np.array_equal(f32_bits(got[row]), f32_bits(ref[0])), "row %d differs" % row
     st_host = st.cpu().numpy().view(np.uint32).reshape(-1, 12)
     _, st_ref = S.render(ns, row0=316, rows=2, nthreads=4)
     assert np.array_equal(st_host[316 * nx: 318 * nx, :6], st_ref[:, :6])          # RNG state written back (main.cu:110)
@@ -298,7 +263,7 @@ def test_full_size_properties_c3(rt, cuda):
     per = rt.part_pixels(nx, ny, rt.Partition(0, nparts))
     parts = torch.zeros(nparts * per * 3, dtype=torch.float32, device="cuda")
     for p in range(nparts):
-        f, _ = gpu_render(rt, torch, W, O, nx, ny, ns, rt.Partition(p, nparts))
+        f, _ = render_frame(rt, torch, W, O, nx, ny, ns, rt.Partition(p, nparts))
         parts[p * per * 3: p * per * 3 + f.numel()] = f
     full = torch.zeros(nx * ny * 3, dtype=torch.float32, device="cuda")
     rt.assemble(full, parts, nx, ny, nparts)
@@ -312,14 +277,14 @@ def test_list_equals_octree_c2_scene(rt, cuda):
     nx, ny, ns, n = 1200, 800, 8, 500
     W = rt.World(n, nx, ny)
     O = rt.Octree(W, 30)
-    a, _ = gpu_render(rt, torch, W, None, nx, ny, ns)
-    b, _ = gpu_render(rt, torch, W, O, nx, ny, ns)
+    a, _ = render_frame(rt, torch, W, None, nx, ny, ns)
+    b, _ = render_frame(rt, torch, W, O, nx, ny, ns)
     assert torch.equal(a.view(torch.int32), b.view(torch.int32))
     # the list path again, every sphere in list order instead of the candidate grid: the same frame and RNG states
     W.set_list_traversal(rt.TRAVERSAL_REFERENCE)
-    c, st_c = gpu_render(rt, torch, W, None, nx, ny, ns)
+    c, st_c = render_frame(rt, torch, W, None, nx, ny, ns)
     W.set_list_traversal(rt.TRAVERSAL_FAST)
-    d, st_d = gpu_render(rt, torch, W, None, nx, ny, ns)
+    d, st_d = render_frame(rt, torch, W, None, nx, ny, ns)
     assert torch.equal(a.view(torch.int32), c.view(torch.int32)) and torch.equal(c.view(torch.int32), d.view(torch.int32))
     assert torch.equal(st_c.view(torch.uint8), st_d.view(torch.uint8))
 
@@ -329,14 +294,6 @@ def test_list_equals_octree_c2_scene(rt, cuda):
 # real_t operator = float op + one rounding to binary16), so the test bar is 0 ulp — bit-exact binary16 channels.
 # Against a real CUDA build of the reference no bit-exactness can be claimed (hsin/hcos/__hdiv are approximations
 # there); the documented expectation is >= 99 % of channels within +-1/255.
-def half_bits(t):
-    return t.cpu().numpy().view(np.uint16)
-
-
-def f32_to_half_bits(a):
-    return np.ascontiguousarray(a, np.float32).astype(np.float16).view(np.uint16)
-
-
 @pytest.mark.parametrize("n,nx,ny,ns,tree,spl", [
     (500, 48, 32, 2, False, 30), (500, 61, 35, 3, True, 30), (9805, 48, 32, 2, True, 32), (22, 64, 36, 4, True, 30),
 ])
@@ -373,8 +330,8 @@ def test_fp16_trace_hit_records(rt, cuda, tree):
     ref = OracleScene(n, 1200, 800, fp16=True, use_octree=tree, spl=spl).trace(rays, mode=2 if tree else 1)
     assert np.array_equal(got["sphere"], ref["sphere"])
     assert ref["hit"].sum() > nrays // 50
-    assert np.array_equal(bits(got["t"]), bits(ref["t"]))
-    assert np.array_equal(bits(got["normal"]), bits(ref["normal"]))
+    assert np.array_equal(f32_bits(got["t"]), f32_bits(ref["t"]))
+    assert np.array_equal(f32_bits(got["normal"]), f32_bits(ref["normal"]))
 
 
 def test_fp16_rays_that_pass_every_node_of_the_tree(rt, cuda):
@@ -405,7 +362,7 @@ def test_fp16_rays_that_pass_every_node_of_the_tree(rt, cuda):
     got = d_out.cpu().numpy().view(rt.hit_record_dtype)
     ref = OracleScene(n, 1200, 800, fp16=True, use_octree=True, spl=spl).trace(rays, mode=2)
     assert np.array_equal(got["sphere"], ref["sphere"])
-    assert np.array_equal(bits(got["t"]), bits(ref["t"])) and np.array_equal(bits(got["normal"]), bits(ref["normal"]))
+    assert np.array_equal(f32_bits(got["t"]), f32_bits(ref["t"])) and np.array_equal(f32_bits(got["normal"]), f32_bits(ref["normal"]))
     assert ref["hit"][512 + 4352:].sum() > 1000                         # the ordinary rays of the launch do hit
 
 
@@ -509,7 +466,7 @@ def test_fp16_c4_properties_and_psnr(rt, cuda):
         assert np.array_equal(got[row][~nan], f32_to_half_bits(ref[0])[~nan]), "row %d" % row
     W32 = rt.World(n, nx, ny)
     O32 = rt.Octree(W32, spl)
-    a, _ = gpu_render(rt, torch, W32, O32, nx, ny, ns)
+    a, _ = render_frame(rt, torch, W32, O32, nx, ny, ns)
     a = np.clip(np.nan_to_num(a.cpu().numpy()), 0, 1)
     b = np.clip(np.nan_to_num(outs[0].float().cpu().numpy()), 0, 1)
     psnr = 10 * np.log10(1.0 / float(np.mean((a - b) ** 2)))
@@ -517,35 +474,6 @@ def test_fp16_c4_properties_and_psnr(rt, cuda):
 
 
 # ---------------------------------------------------------------------------------------------------- arbitrary worlds
-def random_world(rt, seed, n, nx, ny, big=6, air=0.3, outside=0.05, ghosts=0.03):
-    """a caller-built world (not create_world): spheres of many sizes, in the air, overlapping, some outside the
-    octree's root box (dropped with the reference's 'not in range' message), some ghost slots, every material"""
-    rng = np.random.default_rng(seed)
-    sp = np.zeros(n, rt.sphere_dtype)
-    sp["center"][:, 0] = rng.uniform(-10.5, 10.5, n)
-    sp["center"][:, 2] = rng.uniform(-10.5, 10.5, n)
-    sp["radius"] = rng.choice([0.03, 0.05, 0.1, 0.1, 0.1, 0.15, 0.2, 0.3], n)
-    sp["center"][:, 1] = sp["radius"]
-    up = rng.random(n) < air
-    sp["center"][up, 1] = rng.uniform(0.0, 1.9, up.sum())
-    bigs = rng.choice(np.arange(1, n), big, replace=False)
-    sp["radius"][bigs] = rng.uniform(0.6, 1.4, big)
-    sp["center"][bigs, 1] = rng.uniform(0.2, 1.2, big)
-    out = rng.random(n) < outside
-    sp["center"][out, 0] = rng.uniform(11.5, 14.0, out.sum())
-    sp["material"] = rng.choice([rt.MAT_LAMBERTIAN, rt.MAT_LAMBERTIAN, rt.MAT_METAL, rt.MAT_DIELECTRIC], n)
-    sp["albedo"] = rng.uniform(0.05, 1.0, (n, 3))
-    sp["param"] = np.where(sp["material"] == rt.MAT_METAL, rng.uniform(0, 1, n), np.where(sp["material"] == rt.MAT_DIELECTRIC, 1.5, 0.0))
-    g = rng.random(n) < ghosts
-    g[0] = False
-    sp["material"][g] = rt.MAT_NONE
-    sp["center"][g] = 0; sp["radius"][g] = 0; sp["albedo"][g] = 0; sp["param"][g] = 0
-    sp[0] = ((0.0, -1000.0, -1.0), 1000.0, rt.MAT_LAMBERTIAN, (0.5, 0.5, 0.5), 0.0)      # ground stays slot 0 (hitTree tests it first)
-    cam = rt.camera_init((rng.uniform(8, 14), rng.uniform(1, 4), rng.uniform(-4, 4)), (0, 0.3, 0), (0, 1, 0), 35.0,
-                         np.float32(nx) / np.float32(ny), 0.05, 10.0)
-    return sp, cam
-
-
 def oracle_of(sp, cam, n, nx, ny, tree, spl):
     geom = np.concatenate([sp["center"], sp["radius"][:, None]], 1)
     mat = np.concatenate([sp["albedo"], sp["param"][:, None]], 1)
@@ -578,12 +506,12 @@ def test_arbitrary_world_hit_records_and_frames(rt, cuda, seed, n, spl):
         torch.cuda.synchronize()
         got = d_out.cpu().numpy().view(rt.hit_record_dtype)
         assert np.array_equal(got["sphere"], ref["sphere"]), name
-        assert np.array_equal(bits(got["t"]), bits(ref["t"])), name
-        assert np.array_equal(bits(got["normal"]), bits(ref["normal"])), name
+        assert np.array_equal(f32_bits(got["t"]), f32_bits(ref["t"])), name
+        assert np.array_equal(f32_bits(got["normal"]), f32_bits(ref["normal"])), name
     O.set_traversal(rt.TRAVERSAL_FAST)
-    fb, st = gpu_render(rt, torch, W, O, nx, ny, ns)
+    fb, st = render_frame(rt, torch, W, O, nx, ny, ns)
     ref, ref_st = S_tree.render(ns, nthreads=8)
-    assert np.array_equal(bits(fb.cpu().numpy().reshape(ny, nx, 3)), bits(ref))
+    assert np.array_equal(f32_bits(fb.cpu().numpy().reshape(ny, nx, 3)), f32_bits(ref))
     assert np.array_equal(st.cpu().numpy().view(np.uint32).reshape(-1, 12)[:, :6], ref_st[:, :6])
 
 
@@ -627,15 +555,15 @@ def test_reference_default_configuration(rt, cuda):
     W = rt.World(n, nx, ny)
     O = rt.Octree(W, spl)
     assert O.info()["dropped_full"] == 0 and W.created == 8000
-    fb, st = gpu_render(rt, torch, W, O, nx, ny, ns)
+    fb, st = render_frame(rt, torch, W, O, nx, ny, ns)
     O.set_traversal(rt.TRAVERSAL_REFERENCE)
-    fb2, st2 = gpu_render(rt, torch, W, O, nx, ny, ns)
+    fb2, st2 = render_frame(rt, torch, W, O, nx, ny, ns)
     assert torch.equal(fb.view(torch.int32), fb2.view(torch.int32)) and torch.equal(st, st2)
     got = fb.cpu().numpy().reshape(ny, nx, 3)
     S = OracleScene(n, nx, ny, use_octree=True, spl=spl)
     for row in (0, 127, 402, 640, 799):
         ref, _ = S.render(ns, row0=row, rows=1, nthreads=1)
-        assert np.array_equal(bits(got[row]), bits(ref[0])), "row %d" % row
+        assert np.array_equal(f32_bits(got[row]), f32_bits(ref[0])), "row %d" % row
 
 
 @pytest.mark.gpu
@@ -672,7 +600,7 @@ def test_calls_captured_in_a_hip_graph(rt, cuda):
     assert torch.equal(a.view(torch.int32), b.view(torch.int32)) and torch.equal(sa, sb)
 
     for ns in (8, 16):
-        fb0, st0 = gpu_render(rt, torch, W, O, nx, ny, ns)             # also the warm-up of this frame size
+        fb0, st0 = render_frame(rt, torch, W, O, nx, ny, ns)             # also the warm-up of this frame size
         st = rt.alloc_rand_state(nx, ny); fb = rt.alloc_fb(nx, ny)
         g = torch.cuda.CUDAGraph()
         with torch.cuda.graph(g):
@@ -684,7 +612,7 @@ def test_calls_captured_in_a_hip_graph(rt, cuda):
             assert torch.equal(fb.view(torch.int32), fb0.view(torch.int32)) and torch.equal(st, st0)
 
     # without an octree (the list through the candidate grid, built and uploaded by the first such call — the direct render here)
-    fb0, st0 = gpu_render(rt, torch, W, None, nx, ny, 8)
+    fb0, st0 = render_frame(rt, torch, W, None, nx, ny, 8)
     st = rt.alloc_rand_state(nx, ny); fb = rt.alloc_fb(nx, ny)
     g = torch.cuda.CUDAGraph()
     with torch.cuda.graph(g):
@@ -722,16 +650,16 @@ def test_c5_geometry_rows_against_the_oracle(rt, cuda):
     W = rt.World(n, nx, ny)
     O = rt.Octree(W, spl)
     assert O.info()["dropped_full"] == 0
-    fb, st = gpu_render(rt, torch, W, O, nx, ny, ns)
+    fb, st = render_frame(rt, torch, W, O, nx, ny, ns)
     O.set_traversal(rt.TRAVERSAL_REFERENCE)
-    fb2, st2 = gpu_render(rt, torch, W, O, nx, ny, ns)
+    fb2, st2 = render_frame(rt, torch, W, O, nx, ny, ns)
     O.set_traversal(rt.TRAVERSAL_FAST)
     assert torch.equal(fb.view(torch.int32), fb2.view(torch.int32)) and torch.equal(st, st2)
     got = fb.cpu().numpy().reshape(ny, nx, 3)
     S = OracleScene(n, nx, ny, use_octree=True, spl=spl)
     for row in (40, 700, 1100, 2100):
         ref, _ = S.render(ns, row0=row, rows=1, nthreads=8)
-        assert np.array_equal(bits(got[row]), bits(ref[0])), "row %d differs" % row
+        assert np.array_equal(f32_bits(got[row]), f32_bits(ref[0])), "row %d differs" % row
 
 
 def to_half_image(a):
@@ -767,8 +695,8 @@ def test_fp16_arbitrary_world_hit_records_and_frames(rt, cuda, seed, n, spl):
         got = d_out.cpu().numpy().view(rt.hit_record_dtype)
         ref = S.trace(rays, mode=2 if tree else 1)
         assert np.array_equal(got["sphere"], ref["sphere"]), tree
-        assert np.array_equal(bits(got["t"]), bits(ref["t"])), tree
-        assert np.array_equal(bits(got["normal"]), bits(ref["normal"])), tree
+        assert np.array_equal(f32_bits(got["t"]), f32_bits(ref["t"])), tree
+        assert np.array_equal(f32_bits(got["normal"]), f32_bits(ref["normal"])), tree
     st = rt.alloc_rand_state(nx, ny); fb = rt.alloc_fb(nx, ny, precision=rt.FP16)
     rt.render_init(nx, ny, st); rt.render(fb, nx, ny, ns, W, st, O)
     torch.cuda.synchronize()

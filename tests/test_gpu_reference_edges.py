@@ -11,29 +11,11 @@
 import numpy as np
 import pytest
 
+from bitcmp import f32_bits, same_nan_as_ref
+from gpu_frames import frame_image, render_frame
 from oracle_lib import OracleScene
 
 pytestmark = pytest.mark.gpu
-
-
-def bits(a):
-    return np.ascontiguousarray(a, np.float32).view(np.uint32)
-
-
-def gpu_frame(rt, torch, W, O, nx, ny, ns):
-    st = rt.alloc_rand_state(nx, ny)
-    fb = rt.alloc_fb(nx, ny)
-    rt.render_init(nx, ny, st)
-    rt.render(fb, nx, ny, ns, W, st, O)
-    torch.cuda.synchronize()
-    return fb.cpu().numpy().reshape(ny, nx, 3)
-
-
-def same(a, b):
-    """bit-equal, NaN pixels (the reference's dielectric produces them) equal to NaN pixels"""
-    a, b = np.asarray(a, np.float32), np.asarray(b, np.float32)
-    nan = np.isnan(b)
-    return np.array_equal(bits(a)[~nan], bits(b)[~nan]) and np.isnan(a[nan]).all()
 
 
 def test_list_and_octree_disagree_in_one_pixel_exactly_as_the_reference_paths_do(rt, cuda):
@@ -42,9 +24,9 @@ def test_list_and_octree_disagree_in_one_pixel_exactly_as_the_reference_paths_do
     W = rt.World(n, nx, ny)
     O = rt.Octree(W, spl)
     assert O.info()["dropped_full"] == 0 and O.info()["dropped_outside"] == 0          # nothing is missing from the tree: the paths differ by traversal alone
-    f_list = gpu_frame(rt, torch, W, None, nx, ny, ns)
-    f_tree = gpu_frame(rt, torch, W, O, nx, ny, ns)
-    differ = np.argwhere((bits(f_list) != bits(f_tree)).any(axis=2) & ~(np.isnan(f_list).any(axis=2) & np.isnan(f_tree).any(axis=2)))
+    f_list = frame_image(render_frame(rt, torch, W, None, nx, ny, ns)[0], nx, ny)
+    f_tree = frame_image(render_frame(rt, torch, W, O, nx, ny, ns)[0], nx, ny)
+    differ = np.argwhere((f32_bits(f_list) != f32_bits(f_tree)).any(axis=2) & ~(np.isnan(f_list).any(axis=2) & np.isnan(f_tree).any(axis=2)))
     assert [tuple(int(v) for v in d) for d in differ] == [(450, 671)], differ             # (row j, column i): pixel (671, 450), j counted from the bottom row
     # the two reference paths on the CPU: the rows around that pixel, and a few others
     rows = (0, 200, 449, 450, 451, 799)
@@ -54,21 +36,21 @@ def test_list_and_octree_disagree_in_one_pixel_exactly_as_the_reference_paths_do
     for r in rows:
         o_list = o_lists[r] = S_list.render(ns, row0=r, rows=1, nthreads=1)[0][0]
         o_tree = S_tree.render(ns, row0=r, rows=1, nthreads=1)[0][0]
-        assert same(f_list[r], o_list), "list row %d differs from the oracle's hitable_list path" % r
-        assert same(f_tree[r], o_tree), "octree row %d differs from the oracle's hitTree path" % r
-        d = np.flatnonzero((bits(o_list) != bits(o_tree)).any(axis=1) & ~np.isnan(o_list).any(axis=1))
+        assert same_nan_as_ref(f_list[r], o_list), "list row %d differs from the oracle's hitable_list path" % r
+        assert same_nan_as_ref(f_tree[r], o_tree), "octree row %d differs from the oracle's hitTree path" % r
+        d = np.flatnonzero((f32_bits(o_list) != f32_bits(o_tree)).any(axis=1) & ~np.isnan(o_list).any(axis=1))
         assert list(d) == ([671] if r == 450 else []), (r, d)
     # the values the harness recorded: list (0.4648, 0.5031, 0.4974), octree (0.4479, 0.4836, 0.5074)
     assert np.allclose(f_list[450, 671], (0.4648, 0.5031, 0.4974), atol=5e-5) and np.allclose(f_tree[450, 671], (0.4479, 0.4836, 0.5074), atol=5e-5)
     # the plain list-order scan and the literal tree traversal give the same two frames as the default (grid) paths
     W.set_list_traversal(rt.TRAVERSAL_REFERENCE)
-    f_list_ref = gpu_frame(rt, torch, W, None, nx, ny, ns)
-    assert same(f_list_ref, f_list), "the list-order scan differs from the default list path"
+    f_list_ref = frame_image(render_frame(rt, torch, W, None, nx, ny, ns)[0], nx, ny)
+    assert same_nan_as_ref(f_list_ref, f_list), "the list-order scan differs from the default list path"
     for r in (449, 450, 451):
-        assert same(f_list_ref[r], o_lists[r]), "list-order scan row %d differs from the oracle's hitable_list path" % r
+        assert same_nan_as_ref(f_list_ref[r], o_lists[r]), "list-order scan row %d differs from the oracle's hitable_list path" % r
     O.set_traversal(rt.TRAVERSAL_REFERENCE)
-    f_tree_ref = gpu_frame(rt, torch, W, O, nx, ny, ns)
-    assert same(f_tree_ref, f_tree)
+    f_tree_ref = frame_image(render_frame(rt, torch, W, O, nx, ny, ns)[0], nx, ny)
+    assert same_nan_as_ref(f_tree_ref, f_tree)
 
 
 def test_render_through_a_tree_with_full_buckets_equals_the_oracle(rt, cuda):
@@ -81,17 +63,17 @@ def test_render_through_a_tree_with_full_buckets_equals_the_oracle(rt, cuda):
     S = OracleScene(n, nx, ny, use_octree=True, spl=spl)
     assert S.info()["dropped_full"] == 834
     want = S.render(ns, nthreads=8)[0]
-    fast = gpu_frame(rt, torch, W, O, nx, ny, ns)
-    assert same(fast, want), "fast traversal through overflowing buckets differs from the oracle"
+    fast = frame_image(render_frame(rt, torch, W, O, nx, ny, ns)[0], nx, ny)
+    assert same_nan_as_ref(fast, want), "fast traversal through overflowing buckets differs from the oracle"
     O.set_traversal(rt.TRAVERSAL_REFERENCE)
-    assert same(gpu_frame(rt, torch, W, O, nx, ny, ns), want), "reference traversal through overflowing buckets differs from the oracle"
+    assert same_nan_as_ref(frame_image(render_frame(rt, torch, W, O, nx, ny, ns)[0], nx, ny), want), "reference traversal through overflowing buckets differs from the oracle"
     # the device-built tree drops the same insertions and renders the same frame
     Og = rt.Octree(W, spl, gpu=True)
     assert Og.info()["dropped_full"] == 834
-    assert same(gpu_frame(rt, torch, W, Og, nx, ny, ns), want)
+    assert same_nan_as_ref(frame_image(render_frame(rt, torch, W, Og, nx, ny, ns)[0], nx, ny), want)
     # the dropped spheres are invisible through the tree and visible in the list: the frames differ in many pixels
-    f_list = gpu_frame(rt, torch, W, None, nx, ny, ns)
-    assert ((bits(f_list) != bits(fast)).any(axis=2)).sum() > 100
+    f_list = frame_image(render_frame(rt, torch, W, None, nx, ny, ns)[0], nx, ny)
+    assert ((f32_bits(f_list) != f32_bits(fast)).any(axis=2)).sum() > 100
     # binary16 (USE_FP16): same tree shape rules, bit-exact against the fp16 oracle
     Wh = rt.World(n, nx, ny, precision=rt.FP16)
     Oh = rt.Octree(Wh, spl)

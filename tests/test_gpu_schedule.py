@@ -17,6 +17,7 @@ import sys
 import numpy as np
 import pytest
 
+from gpu_frames import render_frame
 from oracle_lib import OracleScene
 from sched_worker import SCENES
 
@@ -275,16 +276,6 @@ def test_every_knob_setting_renders_the_oracle_frame(rt, cuda, oracle, tmp_path,
 
 
 # ---- geometry edges, default knobs, in this process -----------------------------------------------------------------
-def gpu_render(rt, torch, W, O, nx, ny, ns, part=None):
-    part = part or rt.WHOLE
-    st = rt.alloc_rand_state(nx, ny, part)
-    fb = rt.alloc_fb(nx, ny, part)
-    rt.render_init(nx, ny, st, part)
-    rt.render(fb, nx, ny, ns, W, st, O, part)
-    torch.cuda.synchronize()
-    return fb, st
-
-
 @pytest.mark.parametrize("n,spl", [(500, 30), (10000, 32)])
 @pytest.mark.parametrize("nx,ny", [(7, 5), (8, 300), (300, 8)])
 def test_frames_of_one_tile_row_or_column_equal_the_oracle(rt, cuda, n, spl, nx, ny):
@@ -292,7 +283,7 @@ def test_frames_of_one_tile_row_or_column_equal_the_oracle(rt, cuda, n, spl, nx,
     torch = cuda
     W = rt.World(n, nx, ny)
     O = rt.Octree(W, spl)
-    fb, st = gpu_render(rt, torch, W, O, nx, ny, 16)
+    fb, st = render_frame(rt, torch, W, O, nx, ny, 16)
     s = W.render_schedule()
     assert s["tail_mark"] == 1 and s["head_thr"] == 1, s            # fewer than 64 tiles: the tail (handed out first) is the whole frame
     assert s["inflight_thr"] > 0 and s["static_thr"] > 0, s
@@ -309,7 +300,7 @@ def test_part_without_tiles_writes_nothing(rt, cuda):
     nx, ny, n = 7, 5, 500
     W = rt.World(n, nx, ny)
     O = rt.Octree(W, 30)
-    gpu_render(rt, torch, W, O, nx, ny, 16)
+    render_frame(rt, torch, W, O, nx, ny, 16)
     before = (W.render_schedule(), W.render_counters())
     P = rt.Partition(1, 2)
     assert rt.part_pixels(nx, ny, P) == 0

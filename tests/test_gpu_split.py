@@ -4,17 +4,9 @@ non-empty, and rt_assemble_split restores the row-major frame from the bands' co
 import numpy as np
 import pytest
 
+from gpu_frames import render_frame
+
 pytestmark = pytest.mark.gpu
-
-
-def whole_frame(rt, torch, W, O, nx, ny, ns, precision=None):
-    precision = rt.FP32 if precision is None else precision
-    st = rt.alloc_rand_state(nx, ny)
-    fb = rt.alloc_fb(nx, ny, precision=precision)
-    rt.render_init(nx, ny, st)
-    rt.render(fb, nx, ny, ns, W, st, O)
-    torch.cuda.synchronize()
-    return fb, st
 
 
 @pytest.mark.parametrize("nx,ny,ns,n,spl,nparts,fp16", [
@@ -35,7 +27,7 @@ def test_balanced_bands_render_the_bits_of_the_whole_frame(rt, cuda, nx, ny, ns,
     assert b.min() >= 0 and b.sum() >= 32 * (tiles - ((nx + 7) // 8) - ((ny + 7) // 8))     # every pilot sample has at least one bounce
     if spl and not fp16:
         assert t.sum() > 0 and c.sum() >= b.sum()                                # trees with a candidate grid: tests counted, a loop pass per bounce at least
-    full, st_full = whole_frame(rt, torch, W, O, nx, ny, ns, precision)
+    full, st_full = render_frame(rt, torch, W, O, nx, ny, ns, precision=precision)
     parts = rt.split_parts(starts)
     per = max(rt.part_pixels(nx, ny, p) for p in parts)
     dt = torch.float16 if fp16 else torch.float32
@@ -76,7 +68,7 @@ def test_split_arguments_and_single_band(rt, cuda):
     st = rt.split_balanced(W, None, nx, ny, tiles)                                # exactly one tile each
     assert st == list(range(tiles + 1))
     # a range as the only part of a "split into one": compact layout, the same pixels as the whole frame
-    full, _ = whole_frame(rt, torch, W, None, nx, ny, 4)
+    full, _ = render_frame(rt, torch, W, None, nx, ny, 4)
     part = rt.Partition(0, 1, 0, tiles)
     s2 = rt.alloc_rand_state(nx, ny, part); fb = rt.alloc_fb(nx, ny, part)
     rt.render_init(nx, ny, s2, part); rt.render(fb, nx, ny, 4, W, s2, None, part)

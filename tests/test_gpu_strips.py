@@ -6,50 +6,11 @@ centre, shows here as a missing or farther hit.  Random ray
 import numpy as np
 import pytest
 
+from bitcmp import f32_bits
 from oracle_lib import OracleScene
+from world_cases import lattice_rays
 
 pytestmark = pytest.mark.gpu
-
-
-def bits(a):
-    return np.ascontiguousarray(a, np.float32).view(np.uint32)
-
-
-def lattice_rays(info, centers, radii, n, seed, g0=None):
-    """g0: the grid's origin where it is not the root box's (a list whose grid follows its spheres further out)"""
-    rng = np.random.default_rng(seed)
-    G, h = info["grid_dim"], float(info["cell_size"])
-    if g0 is None:
-        g0 = -(11.0 + 5.0 * h)                                # build_accel: half = root half-width + 2 Rlim + 2 h, Rlim = 1.5 h
-    F = 8
-    o = np.zeros((n, 3), np.float64)
-    d = np.zeros((n, 3), np.float64)
-    # origins: x and z on column edges / fine-bin edges / an ulp off them, y anywhere in and around the spheres' slab
-    i = rng.integers(0, G * F + 1, (n, 2))
-    on_col = rng.random((n, 2)) < 0.5
-    i = np.where(on_col, (i // F) * F, i)
-    o[:, 0] = g0 + i[:, 0] * (h / F)
-    o[:, 2] = g0 + i[:, 1] * (h / F)
-    o[:, 1] = rng.choice([0.0, 1e-4, 0.1, 0.2, 0.2, 0.4, 0.4001, 0.7, 2.0], n)
-    # a third of the origins at a sphere's centre or on its surface along an axis
-    k = n // 3
-    pick = rng.integers(1, len(radii), k)
-    o[:k] = centers[pick]
-    on_surface = rng.random(k) < 0.6
-    axis = rng.integers(0, 3, k)
-    sign = rng.choice([-1.0, 1.0], k)
-    o[np.arange(k)[on_surface], axis[on_surface]] += (sign * radii[pick])[on_surface]
-    # directions
-    kind = rng.integers(0, 8, n)
-    ang = rng.uniform(0, 2 * np.pi, n)
-    d[:, 0] = np.cos(ang); d[:, 2] = np.sin(ang); d[:, 1] = rng.normal(scale=0.2, size=n)
-    m = kind == 0; d[m, 2] = rng.choice([1e-30, -1e-30, 1e-12, -1e-7], m.sum()); d[m, 0] = rng.choice([-1.0, 1.0], m.sum())     # along x, all but flat in z
-    m = kind == 1; d[m, 0] = rng.choice([1e-30, -1e-30, 1e-12, -1e-7], m.sum()); d[m, 2] = rng.choice([-1.0, 1.0], m.sum())     # along z
-    m = kind == 2; d[m, 0] = rng.choice([-1.0, 1.0], m.sum()); d[m, 2] = d[m, 0] * rng.choice([-1.0, 1.0], m.sum())               # |dx| == |dz|: the major axis' tie
-    m = kind == 3; d[m, 1] = rng.choice([1e-30, -1e-30, 1e-9, -1e-6, 1e-3], m.sum())                                               # all but horizontal
-    m = kind == 4; d[m, 0] *= 1e-6; d[m, 2] *= 1e-6; d[m, 1] = rng.choice([-1.0, 1.0], m.sum())                                    # all but vertical
-    m = kind == 5; d[m] *= rng.choice([1e-9, 1e-4, 1e4, 1e9], m.sum())[:, None]                                                    # |d|^2 at and beyond the walk's preconditions
-    return np.ascontiguousarray(np.concatenate([o, d], 1), np.float32)
 
 
 def trace(rt, torch, W, O, rays):
@@ -82,6 +43,6 @@ def test_rays_on_the_strips_lattice(rt, cuda, n, spl, frame):
     assert ref["hit"].sum() > nrays // 10
     for got in outs:
         assert np.array_equal(got["sphere"], ref["sphere"])
-        assert np.array_equal(bits(got["t"]), bits(ref["t"]))
-        assert np.array_equal(bits(got["p"]), bits(ref["p"]))
-        assert np.array_equal(bits(got["normal"]), bits(ref["normal"]))
+        assert np.array_equal(f32_bits(got["t"]), f32_bits(ref["t"]))
+        assert np.array_equal(f32_bits(got["p"]), f32_bits(ref["p"]))
+        assert np.array_equal(f32_bits(got["normal"]), f32_bits(ref["normal"]))

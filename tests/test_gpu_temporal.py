@@ -1,5 +1,5 @@
 """GPU tests of temporal accumulation (-m gpu): rt_temporal_accumulate and rt_denoise_history.  Every comparison is bit equality through
-same() of tests/test_gpu_denoise_var.py, except the quality check: the kernel against the numpy float32 model of
+same_any_nan() of tests/test_gpu_denoise_var.py, except the quality check: the kernel against the numpy float32 model of
 tests/temporal_model.py over chains of three frames on camera paths and on fabricated guides and histories; the new prepare against
 rt_denoise_adaptive on a first frame; tiny frames; a captured graph, in place, the refusals; and the RMSE against 512 spp.
 
@@ -9,86 +9,18 @@ asserts are taken at position_tolerance 1: at this resolution one pixel spans 0.
 distance of 13) more than 0.04 t from its neighbour, so the library's default tolerance of 0.03 t, chosen at 1200x800, accepts too few
 taps of a MOVED frame here (the model alone: 33 % of the lambertian pixels take history at 1 degree, against 81 % at tolerance 1, where
 14 % take it at 60 degrees)."""
-import math
-
 import numpy as np
 import pytest
 
 import temporal_model as tm
-from test_gpu_denoise_var import same      # bit equality, except that any two NaNs are equal
+from bitcmp import same_any_nan
+from temporal_paths import gpu_chain, model_chain, Path, PATHS
+from world_cases import orbit_camera
 
 pytestmark = pytest.mark.gpu
 NX, NY = 203, 77                   # ragged: neither a multiple of the 16x16 tile nor of the 8x8 render tile
 N, SPL = 10000, 32
 ADAPT = (4, 64, 4, 0.1, 0.02)      # (min_spp, max_spp, batch, rel_error, floor): pixels stop at many different counts
-PATHS = dict(static=0.0, orbit=1.0, jump=60.0)          # degrees per frame
-
-
-def orbit_camera(rt, deg, nx, ny):
-    """create_world's camera (lookfrom (13, 2, 3), 30 degrees, aperture 0.1, focus 10) with lookfrom turned about the y axis"""
-    th = math.radians(deg)
-    lookfrom = (13 * math.cos(th) + 3 * math.sin(th), 2.0, -13 * math.sin(th) + 3 * math.cos(th))
-    return rt.camera_init(lookfrom, (0, 0, 0), (0, 1, 0), 30.0, nx / ny, 0.1, 10.0)
-
-
-class Path:
-    """frames of one world on a camera path: frame f is rendered by a world of its own (same spheres, camera f) with the RNG states carried
-    on; each leaves its state, gamma frame and guides on the device and on the host"""
-
-    def __init__(self, rt, torch, n_spheres, spl, nx, ny, degs, adapt):
-        self.rt, self.torch, self.nx, self.ny = rt, torch, nx, ny
-        base = rt.World(n_spheres, nx, ny)
-        self.kind = base.spheres["material"].astype(np.int32)
-        st = rt.alloc_rand_state(nx, ny)
-        rt.render_init(nx, ny, st)
-        self.worlds, self.trees, self.frames = {}, {}, []
-        for f, deg in enumerate(degs):
-            if deg not in self.worlds:
-                cam = orbit_camera(rt, deg, nx, ny)
-                if deg == 0.0:
-                    assert np.array_equal(cam.view(np.uint8), base.camera.view(np.uint8))
-                self.worlds[deg] = rt.World(n_spheres, nx, ny, spheres=base.spheres, camera=cam)
-                self.trees[deg] = rt.Octree(self.worlds[deg], spl)
-            W, O = self.worlds[deg], self.trees[deg]
-            fb, state, d_hits = rt.alloc_fb(nx, ny), rt.alloc_adaptive_state(nx, ny), rt.alloc_guides(nx, ny)
-            rt.render_adaptive_begin(fb, nx, ny, rt.Adaptive(*adapt[f % len(adapt)]), W, st, state, O)
-            rt.render_guides(W, O, nx, ny, d_hits)
-            torch.cuda.synchronize()
-            self.frames.append(dict(W=W, O=O, cam=W.camera.copy(), fb=fb, state=state, d_hits=d_hits, h_state=state.cpu().numpy(),
-                                    hits=d_hits.cpu().numpy().view(rt.hit_record_dtype)))
-        base.close()
-
-    def close(self):
-        for O in self.trees.values():
-            O.close()
-        for W in self.worlds.values():
-            W.close()
-
-
-def gpu_chain(rt, torch, P, p, upto=None):
-    """the histories of the path's frames on the GPU, each fed with the last: device tensors"""
-    out = []
-    for f, fr in enumerate(P.frames[:upto]):
-        h = rt.alloc_temporal_history(P.nx, P.ny)
-        h.fill_(7.0)                                                             # every pixel must be written
-        prev = P.frames[f - 1] if f else None
-        rt.temporal_accumulate(h, out[-1] if f else None, fr["d_hits"], prev["d_hits"] if f else None, prev["cam"] if f else None, fr["state"],
-                               fr["W"], P.nx, P.ny, p)
-        out.append(h)
-    torch.cuda.synchronize()
-    return out
-
-
-def model_chain(P, p, upto=None):
-    """the same chain in the model, each fed with the model's last, and the counts of every frame"""
-    out, counts = [], []
-    for f, fr in enumerate(P.frames[:upto]):
-        prev = P.frames[f - 1] if f else None
-        c = {}
-        out.append(tm.accumulate(out[-1] if f else None, fr["hits"], prev["hits"] if f else None, prev["cam"] if f else None, fr["h_state"], P.kind,
-                                 P.nx, P.ny, p.max_history, p.reuse_specular, p.position_tolerance, p.normal_min_dot, counts=c))
-        counts.append(c)
-    return out, counts
 
 
 @pytest.fixture(scope="module")
@@ -119,10 +51,10 @@ def test_matches_the_model_over_a_chain(rt, cuda, paths, path, kw):
     got = gpu_chain(rt, torch, P, p)
     ref, counts = model_chain(P, p)
     for f in range(3):
-        assert same(got[f].cpu().numpy(), ref[f]), (path, kw, f)
+        assert same_any_nan(got[f].cpu().numpy(), ref[f]), (path, kw, f)
     assert counts[0]["nonempty"] > NX * NY // 2 and counts[0]["took"] == 0
     if p.max_history == 0:
-        assert same(ref[2], tm.accumulate(None, P.frames[2]["hits"], None, None, P.frames[2]["h_state"], P.kind, NX, NY, 0, 0, 1.0, 0.0))
+        assert same_any_nan(ref[2], tm.accumulate(None, P.frames[2]["hits"], None, None, P.frames[2]["h_state"], P.kind, NX, NY, 0, 0, 1.0, 0.0))
     elif path == "static":
         assert counts[2]["took_lambertian"] >= 0.99 * counts[2]["lambertian"] > 0    # a landing point is its own pixel centre
     if not p.reuse_specular:
@@ -225,7 +157,7 @@ def test_every_skip_cause_on_fabricated_buffers(rt, cuda, kw):
     out.fill_(7.0)
     rt.temporal_accumulate(out, dev["hist"], dev["hits"], dev["prev"], fab["cam"], dev["state"], W, nx, ny, p)
     torch.cuda.synchronize()
-    assert same(out.cpu().numpy(), ref)
+    assert same_any_nan(out.cpu().numpy(), ref)
     W.close()
 
 
@@ -241,7 +173,7 @@ def test_first_frame_filters_like_denoise_adaptive(rt, cuda, paths, levels):
     rt.denoise_adaptive(ref, fr["fb"], NX, NY, fr["d_hits"], fr["state"], p, work)
     rt.denoise_history(got, fr["fb"], NX, NY, fr["d_hits"], hist, p, work)
     torch.cuda.synchronize()
-    assert same(got.cpu().numpy(), ref.cpu().numpy())
+    assert same_any_nan(got.cpu().numpy(), ref.cpu().numpy())
     assert not np.array_equal(got.cpu().numpy(), fr["fb"].cpu().numpy())           # the filter did something
 
 
@@ -254,7 +186,7 @@ def test_tiny_frames(rt, cuda, nx, ny):
         got = gpu_chain(rt, torch, P, p)
         ref, _ = model_chain(P, p)
         for f in range(3):
-            assert same(got[f].cpu().numpy(), ref[f]), (nx, ny, f)
+            assert same_any_nan(got[f].cpu().numpy(), ref[f]), (nx, ny, f)
     fr = P.frames[0]
     hist = gpu_chain(rt, torch, P, rt.temporal_params(), upto=1)[0]
     ref, got = torch.full_like(fr["fb"], 7.0), torch.full_like(fr["fb"], 9.0)
@@ -262,7 +194,7 @@ def test_tiny_frames(rt, cuda, nx, ny):
     rt.denoise_adaptive(ref, fr["fb"], nx, ny, fr["d_hits"], fr["state"], rt.denoise_var_params(levels=3), work)
     rt.denoise_history(got, fr["fb"], nx, ny, fr["d_hits"], hist, rt.denoise_var_params(levels=3), work)
     torch.cuda.synchronize()
-    assert same(got.cpu().numpy(), ref.cpu().numpy())
+    assert same_any_nan(got.cpu().numpy(), ref.cpu().numpy())
     P.close()
 
 
@@ -288,8 +220,8 @@ def test_captured_in_a_graph(rt, cuda, paths):
         out.zero_()
         g.replay()
         torch.cuda.synchronize()
-        assert same(hist.cpu().numpy(), h[2].cpu().numpy())
-        assert same(out.cpu().numpy(), ref.cpu().numpy())
+        assert same_any_nan(hist.cpu().numpy(), h[2].cpu().numpy())
+        assert same_any_nan(out.cpu().numpy(), ref.cpu().numpy())
 
 
 def test_in_place(rt, cuda, paths):
@@ -304,7 +236,7 @@ def test_in_place(rt, cuda, paths):
     buf = fr["fb"].clone()
     rt.denoise_history(buf, buf, NX, NY, fr["d_hits"], h, dp, work)
     torch.cuda.synchronize()
-    assert same(buf.cpu().numpy(), ref.cpu().numpy())
+    assert same_any_nan(buf.cpu().numpy(), ref.cpu().numpy())
     assert not np.array_equal(buf.cpu().numpy(), fr["fb"].cpu().numpy())
 
 

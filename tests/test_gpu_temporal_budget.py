@@ -6,7 +6,8 @@ sort — on the second and third frame of the camera paths of tests/test_gpu_tem
 on a first frame, on all-sky guides, on a frame whose cut falls between equal keys, on tiny frames, on a frame with more tiles than
 blocks and on the fabricated left / right case of tests/test_temporal_budget_host.py.  The last frame's history that the model is fed
 is the one rt_temporal_accumulate wrote on the device (tests/test_gpu_temporal.py holds that kernel to the model).  A spend is checked
-as tests/test_gpu_adaptive_budget.py checks the raw one, whose frames, scenes and per-pixel exactness check this file borrows."""
+as tests/test_gpu_adaptive_budget.py checks the raw one, with the frames, scenes and per-pixel exactness check of tests/adaptive_frames.py;
+the camera paths and their chains of histories are tests/temporal_paths.py's."""
 import ctypes as C
 
 import numpy as np
@@ -17,16 +18,16 @@ import denoise_var_model as V
 import filtered_budget_model as FM
 import temporal_budget_model as M
 import temporal_model as tm
-import test_gpu_adaptive_budget as T
-import test_gpu_filtered_budget as TF
-import test_gpu_temporal as TT
-from test_gpu_adaptive_budget import SENTINEL, state_parts, u32
-from test_gpu_denoise_var import same      # bit equality, except that any two NaNs are equal
+from adaptive_frames import (BATCH, FLOOR, MAX_SPP, SENTINEL, Frame, Scene, check_exact, check_round, check_round_filtered, check_round_temporal,
+                             model_pick, state_parts)
+from bitcmp import assert_same_snapshots, raw_bits, same_any_nan
+from temporal_paths import gpu_chain, Path, PATHS
 
 pytestmark = pytest.mark.gpu
 
-NX, NY = TT.NX, TT.NY              # 203 x 77: 13 x 5 tiles of 16 x 16, ragged on both edges; 15 full selection spans and a rest
-FLOOR, BATCH, MAX_SPP = T.FLOOR, T.BATCH, T.MAX_SPP
+NX, NY = 203, 77                   # 203 x 77: 13 x 5 tiles of 16 x 16, ragged on both edges; 15 full selection spans and a rest
+N, SPL = 10000, 32
+LOOSE = (4, 64, 4, 0.1, FLOOR)     # the frame a spend continues (tests/test_gpu_filtered_budget.py's)
 ADAPT = (4, 64, 4, 0.1, 0.02)      # (min_spp, max_spp, batch, rel_error, floor): pixels stop at many different counts
 SMALL = (23, 11)
 PARAMS = [dict(), dict(position_tolerance=1.0), dict(max_history=0), dict(max_history=8), dict(reuse_specular=1), dict(normal_min_dot=0.99)]
@@ -70,7 +71,7 @@ def check_select(rt, torch, ctx, W, kind, nx, ny, p, Ks, hist, hits, prev_hits, 
     for K in (Ks(elig) if callable(Ks) else Ks):
         chosen = FM.pick(ok, kb, K)
         got, keys = gpu_select(rt, torch, ctx, dev["state"], W, nx, ny, tin, p, K)
-        assert same(keys, key), (nx, ny, K, int((keys.view(np.uint32) != kb).sum()))
+        assert same_any_nan(keys, key), (nx, ny, K, int((keys.view(np.uint32) != kb).sum()))
         assert len(got) == min(K, elig) and np.array_equal(got, chosen), (nx, ny, K)
     for name, b in zip(("hist", "state"), before):                  # both are only read
         assert b is None or np.array_equal(dev[name].cpu().numpy(), b), name
@@ -93,8 +94,8 @@ def paths(rt, cuda):
     """three frames on each camera path of tests/test_gpu_temporal.py: at 203x77 its world (10 000 spheres), at 23x11 500 spheres"""
     M.self_check()                                 # the model follows the rule before the kernel is held to the model
     made = {}
-    for size, (n_spheres, spl) in (((NX, NY), (TT.N, TT.SPL)), (SMALL, (500, 30))):
-        made[size] = {name: TT.Path(rt, cuda, n_spheres, spl, size[0], size[1], [0.0, step, 2 * step], [ADAPT]) for name, step in TT.PATHS.items()}
+    for size, (n_spheres, spl) in (((NX, NY), (N, SPL)), (SMALL, (500, 30))):
+        made[size] = {name: Path(rt, cuda, n_spheres, spl, size[0], size[1], [0.0, step, 2 * step], [ADAPT]) for name, step in PATHS.items()}
     yield made
     for group in made.values():
         for P in group.values():
@@ -104,13 +105,13 @@ def paths(rt, cuda):
 # ---- 1. kernel == model on the second and third frame of the camera paths ------------------------------------------------------------
 @pytest.mark.parametrize("size", [SMALL, (NX, NY)], ids=["23x11", "203x77"])
 @pytest.mark.parametrize("kw", PARAMS, ids=[",".join("%s=%s" % kv for kv in c.items()) or "defaults" for c in PARAMS])
-@pytest.mark.parametrize("path", list(TT.PATHS))
+@pytest.mark.parametrize("path", list(PATHS))
 def test_keys_and_set_match_the_model(rt, cuda, ctx, paths, path, kw, size):
     torch = cuda
     nx, ny = size
     P = paths[size][path]
     p = rt.temporal_params(**kw)
-    hist = TT.gpu_chain(rt, torch, P, p, upto=2)                                   # the histories of frames 0 and 1
+    hist = gpu_chain(rt, torch, P, p, upto=2)                                   # the histories of frames 0 and 1
     took = 0
     for f in (1, 2):
         fr, prev = P.frames[f], P.frames[f - 1]
@@ -142,9 +143,9 @@ def test_first_frame_keys_are_the_filtered_rule_on_this_frame(rt, cuda, ctx, pat
     with np.errstate(all="ignore"):
         l = (xc[:, 0] + xc[:, 1]) + xc[:, 2]
     want = np.where(empty, B.priority(SL, Q, k, FLOOR), FM.priority_filtered(l, vc, FLOOR))
-    assert 0 < empty.sum() < n and same(keys, want)
+    assert 0 < empty.sum() < n and same_any_nan(keys, want)
     raw = B.priority(SL, Q, k, FLOOR)
-    assert not np.array_equal(u32(want[~empty]), u32(raw[~empty]))                # the same quantity, not the same bits
+    assert not np.array_equal(raw_bits(want[~empty]), raw_bits(raw[~empty]))                # the same quantity, not the same bits
     assert np.allclose(want[~empty], raw[~empty], rtol=1e-5, atol=0)
     check_select(rt, torch, ctx, fr["W"], P.kind, NX, NY, p, four_Ks(n), None, fr["hits"], None, None, fr["h_state"],
                  dev=dict(hist=None, hits=fr["d_hits"], prev=None, state=fr["state"]))
@@ -228,9 +229,9 @@ def test_cut_between_equal_keys(rt, cuda, ctx):
 @pytest.mark.parametrize("nx,ny", [(1, 1), (1, 37), (41, 1), (17, 2)])
 def test_tiny_frames(rt, cuda, ctx, nx, ny):
     torch = cuda
-    P = TT.Path(rt, torch, 500, 30, nx, ny, [0.0, 0.0, 1.0], [(4, 32, 4, 0.1, FLOOR)])
+    P = Path(rt, torch, 500, 30, nx, ny, [0.0, 0.0, 1.0], [(4, 32, 4, 0.1, FLOOR)])
     for p in (rt.temporal_params(position_tolerance=1.0), rt.temporal_params(reuse_specular=1, max_history=8)):
-        hist = TT.gpu_chain(rt, torch, P, p, upto=2)
+        hist = gpu_chain(rt, torch, P, p, upto=2)
         for f in (1, 2):
             fr, prev = P.frames[f], P.frames[f - 1]
             check_select(rt, torch, ctx, fr["W"], P.kind, nx, ny, p, lambda elig: (0, 1, max(elig // 3, 1), elig + 5), hist[f - 1].cpu().numpy(),
@@ -243,9 +244,9 @@ def test_more_tiles_than_blocks(rt, cuda, ctx):
     torch = cuda
     nx, ny = 530, 500                                          # 34 x 32 = 1088 tiles of 16 x 16: a block takes two
     assert ((nx + 15) // 16) * ((ny + 15) // 16) > 1024
-    P = TT.Path(rt, torch, 500, 30, nx, ny, [0.0, 0.2], [ADAPT])
+    P = Path(rt, torch, 500, 30, nx, ny, [0.0, 0.2], [ADAPT])
     p = rt.temporal_params()
-    hist = TT.gpu_chain(rt, torch, P, p, upto=1)[0]
+    hist = gpu_chain(rt, torch, P, p, upto=1)[0]
     fr, prev = P.frames[1], P.frames[0]
     c = {}
     h = hist.cpu().numpy()
@@ -258,32 +259,14 @@ def test_more_tiles_than_blocks(rt, cuda, ctx):
 
 
 # ---- 7. the spend on a rendered frame ------------------------------------------------------------------------------------------------
-class Frame(TF.Frame):
-    def spend_temporal(self, sc, samples, rounds, batch=BATCH, max_spp=MAX_SPP, floor=FLOOR):
-        picked = self.torch.full((rounds,), SENTINEL, dtype=self.torch.int32, device="cuda")
-        Bd = self.rt.Budget(samples, rounds, batch, max_spp, floor)
-        if self.ctx is not None:
-            self.torch.cuda.synchronize()                    # (the fill above runs on the current stream, the spend on the context's)
-            self.ctx.render_adaptive_spend_temporal(self.fb, self.nx, self.ny, Bd, sc.tin, sc.tp, sc.W, self.st, self.state, sc.O, self.spp, picked,
-                                                    stream=self.stream)
-        else:
-            self.rt.render_adaptive_spend_temporal(self.fb, self.nx, self.ny, Bd, sc.tin, sc.tp, sc.W, self.st, self.state, sc.O, self.spp, picked)
-        self.torch.cuda.synchronize()
-        return picked.cpu().numpy().view(np.uint32)
-
-
 def temporal_scene(rt, torch, n_spheres, spl, nx, ny, trav=None):
-    """T.Scene (this frame: create_world's camera) with its guides, and the last frame: the same spheres seen from one degree further
+    """Scene (this frame: create_world's camera) with its guides, and the last frame: the same spheres seen from one degree further
     round the orbit, its guides, camera and first-frame history.  position_tolerance 1: the docstring of tests/test_gpu_temporal.py says why."""
-    sc = T.Scene(rt, torch, n_spheres, spl, nx, ny, trav)
-    sc.d_hits = rt.alloc_guides(nx, ny)
-    rt.render_guides(sc.W, sc.O, nx, ny, sc.d_hits)
-    torch.cuda.synchronize()
-    sc.hits = sc.d_hits.cpu().numpy().view(rt.hit_record_dtype)
-    sc.last = TT.Path(rt, torch, n_spheres, 30 if spl is None else spl, nx, ny, [1.0], [ADAPT])
+    sc = Scene(rt, torch, n_spheres, spl, nx, ny, trav).with_guides()
+    sc.last = Path(rt, torch, n_spheres, 30 if spl is None else spl, nx, ny, [1.0], [ADAPT])
     assert np.array_equal(sc.last.kind, sc.W.spheres["material"].astype(np.int32))
     sc.tp = rt.temporal_params(position_tolerance=1.0)
-    sc.d_hist = TT.gpu_chain(rt, torch, sc.last, sc.tp)[0]
+    sc.d_hist = gpu_chain(rt, torch, sc.last, sc.tp)[0]
     sc.hist = sc.d_hist.cpu().numpy().copy()
     prev = sc.last.frames[0]
     sc.tin = rt.temporal_inputs(sc.d_hits, sc.d_hist, prev["d_hits"], prev["cam"])
@@ -299,38 +282,19 @@ def close_scene(sc):
 
 @pytest.fixture(scope="module")
 def scene(rt, cuda):
-    sc = temporal_scene(rt, cuda, T.N, T.SPL, NX, NY)
+    sc = temporal_scene(rt, cuda, N, SPL, NX, NY)
     c = {}
     prev = sc.last.frames[0]
-    F = Frame(rt, cuda, NX, NY, rt.WHOLE).begin(sc.W, sc.O, TF.LOOSE)
+    F = Frame(rt, cuda, NX, NY, rt.WHOLE).begin(sc.W, sc.O, LOOSE)
     M.frame_keys(sc.hist, sc.hits, prev["hits"], prev["cam"], F.snap()["state"], sc.last.kind, NX, NY, FLOOR, *tup(sc.tp), counts=c)
     assert c["took"] > NX * NY // 10 and c["asked"] > c["took"]                     # the history enters the ranking of this scene, and is refused
     yield sc
     close_scene(sc)
 
 
-def check_round(sc, F, before, after, picked, K, batch=BATCH, max_spp=MAX_SPP):
-    """one history-aware round from `before` to `after`: the model's set on the snapshot, untouched pixels keep every bit, every pixel
-    holds what its k samples give (T.check_exact)"""
-    n = F.n
-    chosen, ok, _ = sc.model_select(before["state"], K, batch, max_spp)
-    assert int(picked) == len(chosen) == min(K, int(ok.sum()))
-    S0, SL0, Q0, k0 = state_parts(before["state"], n)
-    S1, SL1, Q1, k1 = state_parts(after["state"], n)
-    want = k0.copy()
-    want[chosen] += batch
-    assert np.array_equal(k1, want) and np.array_equal(after["spp"], want)
-    hit = np.zeros(n, bool)
-    hit[chosen] = True
-    for a, b in ((before["fb"], after["fb"]), (before["st"], after["st"]), (u32(S0), u32(S1)), (u32(SL0), u32(SL1)), (u32(Q0), u32(Q1))):
-        assert np.array_equal(a[~hit], b[~hit])
-    T.check_exact(sc, F, after)
-    return chosen
-
-
 def rounds_compose(rt, torch, sc, ctx=None, stream=None):
-    A = Frame(rt, torch, sc.nx, sc.ny, rt.WHOLE, ctx, stream).begin(sc.W, sc.O, TF.LOOSE)
-    Bf = Frame(rt, torch, sc.nx, sc.ny, rt.WHOLE).begin(sc.W, sc.O, TF.LOOSE)
+    A = Frame(rt, torch, sc.nx, sc.ny, rt.WHOLE, ctx, stream).begin(sc.W, sc.O, LOOSE)
+    Bf = Frame(rt, torch, sc.nx, sc.ny, rt.WHOLE).begin(sc.W, sc.O, LOOSE)
     n = A.n
     q = n // 4 + 1
     samples, rounds = BATCH * q + 3, 3                       # three rounds of batch 4
@@ -341,12 +305,12 @@ def rounds_compose(rt, torch, sc, ctx=None, stream=None):
     for K in Ks:
         before = Bf.snap()
         pk = Bf.spend_temporal(sc, K * BATCH, 1)
-        check_round(sc, Bf, before, Bf.snap(), pk[0], K)
+        check_round_temporal(sc, Bf, before, Bf.snap(), pk[0], K)
         singles.append(int(pk[0]))
     assert list(picked) == singles and sum(singles) > q // 2
     final = A.snap()
-    T.same(final, Bf.snap())
-    T.check_exact(sc, A, final)
+    assert_same_snapshots(final, Bf.snap())
+    check_exact(sc, A, final)
     assert len(np.unique(final["spp"])) >= 3
     assert np.array_equal(sc.d_hist.cpu().numpy(), sc.hist)  # d_hist_in is only read
     return A, final
@@ -355,11 +319,11 @@ def rounds_compose(rt, torch, sc, ctx=None, stream=None):
 def test_rendered_frame_rounds_compose(rt, cuda, scene):
     rounds_compose(rt, cuda, scene)
     # the history-aware key is another ordering than the raw one on this frame: the first round's sets differ
-    F = Frame(rt, cuda, NX, NY, rt.WHOLE).begin(scene.W, scene.O, TF.LOOSE)
+    F = Frame(rt, cuda, NX, NY, rt.WHOLE).begin(scene.W, scene.O, LOOSE)
     snap = F.snap()
     K = F.n // 6
     h_set = scene.model_select(snap["state"], K)[0]
-    r_set = T.model_pick(snap, F.n, F.inside, K)[0]
+    r_set = model_pick(snap, F.n, F.inside, K)[0]
     assert len(h_set) == len(r_set) == K and not np.array_equal(h_set, r_set)
 
 
@@ -382,20 +346,20 @@ def test_context_on_a_side_stream(rt, cuda, scene):
 
 def test_raw_then_temporal_then_filtered_spend(rt, cuda, scene):
     sc, fp = scene, rt.denoise_var_params()
-    F = Frame(rt, cuda, NX, NY, rt.WHOLE).begin(sc.W, sc.O, TF.LOOSE)
+    F = Frame(rt, cuda, NX, NY, rt.WHOLE).begin(sc.W, sc.O, LOOSE)
     before = F.snap()
     pk = F.spend(sc.W, sc.O, 3000 * BATCH, 1)
     mid = F.snap()
-    T.check_round(sc, F, before, mid, pk[0], 3000)
+    check_round(sc, F, before, mid, pk[0], 3000)
     pk = F.spend_temporal(sc, 2500 * BATCH, 1)
     after = F.snap()
-    check_round(sc, F, mid, after, pk[0], 2500)
+    check_round_temporal(sc, F, mid, after, pk[0], 2500)
     pk = F.spend_filtered(sc, fp, 1000 * BATCH, 1)
     last = F.snap()
-    TF.check_round(sc, F, after, last, pk[0], 1000, fp)
-    T.check_exact(sc, F, last)
+    check_round_filtered(sc, F, after, last, pk[0], 1000, fp)
+    check_exact(sc, F, last)
     pk = F.spend_temporal(sc, 500 * BATCH, 1)                # ... and back
-    check_round(sc, F, last, F.snap(), pk[0], 500)
+    check_round_temporal(sc, F, last, F.snap(), pk[0], 500)
     assert np.array_equal(sc.d_hist.cpu().numpy(), sc.hist)
 
 
@@ -403,7 +367,7 @@ def test_accumulate_around_a_round_differs_only_in_chosen_pixels(rt, cuda, scene
     torch, sc = cuda, scene
     n = NX * NY
     prev = sc.last.frames[0]
-    F = Frame(rt, torch, NX, NY, rt.WHOLE).begin(sc.W, sc.O, TF.LOOSE)
+    F = Frame(rt, torch, NX, NY, rt.WHOLE).begin(sc.W, sc.O, LOOSE)
 
     def accumulate():
         h = rt.alloc_temporal_history(NX, NY)
@@ -416,12 +380,12 @@ def test_accumulate_around_a_round_differs_only_in_chosen_pixels(rt, cuda, scene
     before = F.snap()
     K = 3000
     pk = F.spend_temporal(sc, K * BATCH, 1)
-    chosen = check_round(sc, F, before, F.snap(), pk[0], K)
+    chosen = check_round_temporal(sc, F, before, F.snap(), pk[0], K)
     xv1, neff1 = accumulate()
     hit = np.zeros(n, bool)
     hit[chosen] = True
     assert len(chosen) == K
-    assert np.array_equal(u32(xv0[~hit]), u32(xv1[~hit])) and np.array_equal(u32(neff0[~hit]), u32(neff1[~hit]))
+    assert np.array_equal(raw_bits(xv0[~hit]), raw_bits(xv1[~hit])) and np.array_equal(raw_bits(neff0[~hit]), raw_bits(neff1[~hit]))
     live = hit & (neff0 > 0)
     assert live.any() and (neff1[live] > neff0[live]).all()                        # m + (n + batch) against m + n
     assert np.array_equal(sc.d_hist.cpu().numpy(), sc.hist)
@@ -430,10 +394,10 @@ def test_accumulate_around_a_round_differs_only_in_chosen_pixels(rt, cuda, scene
 # ---- 8. errors on the device -----------------------------------------------------------------------------------------------------
 def test_binary16_and_contracted_worlds(rt, cuda, scene, ctx):
     torch, sc = cuda, scene
-    F = Frame(rt, torch, NX, NY, rt.WHOLE).begin(sc.W, sc.O, TF.LOOSE)
+    F = Frame(rt, torch, NX, NY, rt.WHOLE).begin(sc.W, sc.O, LOOSE)
     Bd = rt.Budget(4000, 1, BATCH, MAX_SPP, FLOOR)
-    w16 = rt.World(T.N, NX, NY, precision=rt.FP16)
-    wc = rt.World(T.N, NX, NY)
+    w16 = rt.World(N, NX, NY, precision=rt.FP16)
+    wc = rt.World(N, NX, NY)
     wc.set_arith(rt.ARITH_CONTRACT)
     before = F.snap()
     for W in (w16, wc):
@@ -444,7 +408,7 @@ def test_binary16_and_contracted_worlds(rt, cuda, scene, ctx):
     with pytest.raises(rt.RtError, match="-4"):
         rt.adaptive_budget_select_temporal(ctx, F.state, w16, NX, NY, Bd, sc.tin, sc.tp, 1000, lst, cnt)
     torch.cuda.synchronize()
-    T.same(F.snap(), before)
+    assert_same_snapshots(F.snap(), before)
     assert int(cnt.cpu().numpy()[0]) == SENTINEL
     # the selection renders nothing: a contracted world supplies kind[] like any other
     want, _ = gpu_select(rt, torch, ctx, F.state, sc.W, NX, NY, sc.tin, sc.tp, 1000, want_keys=False)
@@ -456,7 +420,7 @@ def test_binary16_and_contracted_worlds(rt, cuda, scene, ctx):
 
 def test_refused_during_a_capture(rt, cuda, scene, ctx):
     torch, sc = cuda, scene
-    F = Frame(rt, torch, NX, NY, rt.WHOLE).begin(sc.W, sc.O, TF.LOOSE)
+    F = Frame(rt, torch, NX, NY, rt.WHOLE).begin(sc.W, sc.O, LOOSE)
     Bd = rt.Budget(4000, 1, BATCH, MAX_SPP, FLOOR)
     F.spend_temporal(sc, 4000, 1)                            # warm: the workspaces exist, so only the capture can be the reason
     lst = torch.zeros(1064, dtype=torch.int32, device="cuda")
@@ -476,5 +440,5 @@ def test_refused_during_a_capture(rt, cuda, scene, ctx):
     assert rc_spend == -1 and rc_select == -1
     g.replay()
     torch.cuda.synchronize()
-    T.same(F.snap(), before)
+    assert_same_snapshots(F.snap(), before)
     assert float(marker.sum()) == 4.0 and int(cnt.cpu().numpy()[0]) == 0

@@ -1,4 +1,4 @@
-"""GPU tests of rt_temporal_accumulate_moving (-m gpu).  Every comparison is bit equality through same() of tests/test_gpu_denoise_var.py,
+"""GPU tests of rt_temporal_accumulate_moving (-m gpu).  Every comparison is bit equality through same_any_nan() of tests/test_gpu_denoise_var.py,
 except the quality check: the kernel against the numpy model of tests/temporal_moving_model.py over a chain of three frames of ONE
 world whose spheres move and whose camera stands or orbits, the two identities of the rule against rt_temporal_accumulate on the GPU,
 tiny frames, a captured graph, the refusals, and the RMSE against 512 spp.
@@ -12,8 +12,8 @@ import pytest
 
 import temporal_model as tm
 import temporal_moving_model as tmm
-from test_gpu_denoise_var import same      # bit equality, except that any two NaNs are equal
-from test_gpu_temporal import orbit_camera
+from bitcmp import same_any_nan
+from temporal_paths import Animation
 
 pytestmark = pytest.mark.gpu
 NX, NY = 203, 77
@@ -21,61 +21,6 @@ N, SPL = 10000, 32
 ADAPT = (4, 64, 4, 0.1, 0.02)
 PATHS = dict(static=0.0, orbit=1.0)            # degrees per frame
 F = np.float32
-STEP = F(0.5)
-
-
-def motion_sets(spheres, every=7):
-    """the small spheres that move (every `every`-th) and, disjoint from them for every > 3, those that change radius"""
-    small = np.flatnonzero((spheres["material"] != -1) & (spheres["radius"] < 0.5) & (np.arange(len(spheres)) > 0))
-    return small[::every], small[3::7]
-
-
-class Animation:
-    """frames of ONE world: before frame f > 0 the geometry is read back (what the next accumulate takes as d_geom_prev), the moved set
-    is translated and the second set resized, the camera is set and the tree is built again on the device; every frame leaves its
-    state, gamma frame, guides, camera and geometry on the device and on the host"""
-
-    def __init__(self, rt, torch, n_spheres, spl, nx, ny, degs, adapt, resize=True, every=7):
-        self.rt, self.torch, self.nx, self.ny, self.spl = rt, torch, nx, ny, spl
-        self.W = W = rt.World(n_spheres, nx, ny)
-        self.kind = W.spheres["material"].astype(np.int32)
-        self.moved, self.resized = motion_sets(W.spheres, every)
-        assert len(self.moved) >= 1 and not (resize and set(self.moved) & set(self.resized))
-        st = rt.alloc_rand_state(nx, ny)
-        rt.render_init(nx, ny, st)
-        self.frames, self.tree = [], None
-        for f, deg in enumerate(degs):
-            if f:
-                nxt = W.get_geometry()
-                nxt[torch.from_numpy(self.moved).cuda(), 0] += float(STEP)
-                if resize:
-                    nxt[torch.from_numpy(self.resized).cuda(), 3] *= 1.25
-                W.set_geometry(nxt)
-                W.set_camera(orbit_camera(rt, deg, nx, ny))
-            self.rebuild()
-            fb, state, d_hits = rt.alloc_fb(nx, ny), rt.alloc_adaptive_state(nx, ny), rt.alloc_guides(nx, ny)
-            rt.render_adaptive_begin(fb, nx, ny, rt.Adaptive(*adapt), W, st, state, self.tree)
-            rt.render_guides(W, self.tree, nx, ny, d_hits)
-            d_geom = W.get_geometry()
-            torch.cuda.synchronize()
-            self.frames.append(dict(cam=W.get_camera(), fb=fb, state=state, d_hits=d_hits, d_geom=d_geom, h_state=state.cpu().numpy(),
-                                    hits=d_hits.cpu().numpy().view(rt.hit_record_dtype), geom=d_geom.cpu().numpy()))
-
-    def rebuild(self):
-        if self.tree is not None:
-            self.tree.close()
-        self.tree = self.rt.Octree(self.W, self.spl, gpu=True)
-
-    def at(self, f):
-        """the world with the geometry and camera of frame f again (the moving accumulate reads this frame's geometry from the world)"""
-        self.W.set_geometry(self.frames[f]["d_geom"])
-        self.W.set_camera(self.frames[f]["cam"])
-        return self.frames[f]
-
-    def close(self):
-        if self.tree is not None:
-            self.tree.close()
-        self.W.close()
 
 
 def gpu_chain(rt, torch, A, p, upto=None):
@@ -130,7 +75,7 @@ def test_matches_the_model_over_a_chain(rt, cuda, anims, path, kw):
     got = gpu_chain(rt, cuda, A, p)
     ref, counts = model_chain(A, p)
     for f in range(3):
-        assert same(got[f].cpu().numpy(), ref[f]), (path, kw, f)
+        assert same_any_nan(got[f].cpu().numpy(), ref[f]), (path, kw, f)
     assert counts[0]["nonempty"] > NX * NY // 2 and counts[0]["took"] == 0
     if p.max_history == 0:
         assert all(c["took"] == 0 for c in counts)
@@ -160,7 +105,7 @@ def test_both_identities_on_the_gpu(rt, cuda, anims):
         rt.temporal_accumulate_moving(a, h[1], fr["d_hits"], pv["d_hits"], pv["cam"], fr["d_geom"], fr["state"], A.W, NX, NY, p)
         rt.temporal_accumulate(b, h[1], fr["d_hits"], pv["d_hits"], pv["cam"], fr["state"], A.W, NX, NY, p)
         torch.cuda.synchronize()
-        assert same(a.cpu().numpy(), b.cpu().numpy()), name
+        assert same_any_nan(a.cpu().numpy(), b.cpu().numpy()), name
         # moved: the static call on guides whose p fields hold P', wherever the radius was kept
         patched = tmm.patched_guides(fr["hits"], fr["geom"], pv["geom"])
         assert not np.array_equal(patched["p"], fr["hits"]["p"])
@@ -171,8 +116,8 @@ def test_both_identities_on_the_gpu(rt, cuda, anims):
         assert 0 < (~keep).sum() < keep.sum()
         xa, na = tm.history_parts(h[2].cpu().numpy(), NX * NY)
         xb, nb = tm.history_parts(b.cpu().numpy(), NX * NY)
-        assert same(xa[keep], xb[keep]) and same(na[keep], nb[keep]), name
-        assert not same(xa[~keep], xb[~keep])
+        assert same_any_nan(xa[keep], xb[keep]) and same_any_nan(na[keep], nb[keep]), name
+        assert not same_any_nan(xa[~keep], xb[~keep])
 
 
 @pytest.mark.parametrize("nx,ny", [(1, 1), (3, 2), (16, 17)])
@@ -182,7 +127,7 @@ def test_tiny_frames(rt, cuda, nx, ny):
         got = gpu_chain(rt, cuda, A, p)
         ref, _ = model_chain(A, p)
         for f in range(3):
-            assert same(got[f].cpu().numpy(), ref[f]), (nx, ny, f)
+            assert same_any_nan(got[f].cpu().numpy(), ref[f]), (nx, ny, f)
     A.close()
 
 
@@ -199,7 +144,7 @@ def test_captured_in_a_graph(rt, cuda, anims):
     hist.fill_(3.0)
     g.replay()
     torch.cuda.synchronize()
-    assert same(hist.cpu().numpy(), h[2].cpu().numpy())
+    assert same_any_nan(hist.cpu().numpy(), h[2].cpu().numpy())
 
 
 def test_refusals(rt, cuda, anims):

@@ -1,4 +1,4 @@
-"""GPU tests of rt_temporal_accumulate_rectified (-m gpu).  Every comparison is bit equality through same() of
+"""GPU tests of rt_temporal_accumulate_rectified (-m gpu).  Every comparison is bit equality through same_any_nan() of
 tests/test_gpu_denoise_var.py, except the quality check: the kernel against the numpy model of tests/temporal_rectify_model.py over
 chains of three frames of ONE world whose spheres move and whose camera stands or orbits — under the static rule (d_geom_prev NULL) and
 under the moving rule (given), at radius 1 and 2, at a biting gamma and at the default —, frames smaller than the window's apron, both
@@ -12,8 +12,8 @@ import pytest
 
 import temporal_model as tm
 import temporal_rectify_model as trm
-from test_gpu_denoise_var import same      # bit equality, except that any two NaNs are equal
-from test_gpu_temporal_moving import Animation
+from bitcmp import same_any_nan
+from temporal_paths import Animation
 
 pytestmark = pytest.mark.gpu
 NX, NY = 203, 77
@@ -82,7 +82,7 @@ def test_matches_the_model_over_a_chain(rt, cuda, anims, path, radius, gamma, mo
     got = gpu_chain(rt, cuda, A, p, r, moving)
     ref, counts = model_chain(A, p, r, moving)
     for f in range(3):
-        assert same(got[f].cpu().numpy(), ref[f]), (path, radius, gamma, moving, f)
+        assert same_any_nan(got[f].cpu().numpy(), ref[f]), (path, radius, gamma, moving, f)
     assert counts[0]["nonempty"] > NX * NY // 2 and counts[0]["took"] == 0 and counts[2]["took"] > 1000
     if gamma is not None:
         assert counts[2]["rectified"] > 100
@@ -117,7 +117,7 @@ def test_tiny_and_edge_frames_at_radius_2(rt, cuda, nx, ny):
             got = gpu_chain(rt, cuda, A, p, r, moving)
             ref, _ = model_chain(A, p, r, moving)
             for f in range(3):
-                assert same(got[f].cpu().numpy(), ref[f]), (nx, ny, r.gamma, moving, f)
+                assert same_any_nan(got[f].cpu().numpy(), ref[f]), (nx, ny, r.gamma, moving, f)
     A.close()
 
 
@@ -134,19 +134,19 @@ def test_gamma_zero_is_the_two_existing_calls(rt, cuda, anims, radius):
         rt.temporal_accumulate_rectified(a, first, fr["d_hits"], pv["d_hits"], pv["cam"], fr["state"], A.W, NX, NY, p, off)
         rt.temporal_accumulate(b, first, fr["d_hits"], pv["d_hits"], pv["cam"], fr["state"], A.W, NX, NY, p)
         torch.cuda.synchronize()
-        assert same(a.cpu().numpy(), b.cpu().numpy()), name
+        assert same_any_nan(a.cpu().numpy(), b.cpu().numpy()), name
         ref = b.cpu().numpy()
         a.fill_(5.0)
         rt.temporal_accumulate_rectified(a, first, fr["d_hits"], pv["d_hits"], pv["cam"], fr["state"], A.W, NX, NY, p, off, d_geom_prev=pv["d_geom"])
         rt.temporal_accumulate_moving(b, first, fr["d_hits"], pv["d_hits"], pv["cam"], pv["d_geom"], fr["state"], A.W, NX, NY, p)
         torch.cuda.synchronize()
-        assert same(a.cpu().numpy(), b.cpu().numpy()), name
-        assert not same(ref, b.cpu().numpy())                                        # the two rules differ on these frames
+        assert same_any_nan(a.cpu().numpy(), b.cpu().numpy()), name
+        assert not same_any_nan(ref, b.cpu().numpy())                                        # the two rules differ on these frames
         b.fill_(9.0)
         rt.temporal_accumulate(b, None, fr["d_hits"], None, None, fr["state"], A.W, NX, NY, p)
         rt.temporal_accumulate_rectified(a, None, fr["d_hits"], None, None, fr["state"], A.W, NX, NY, p, rt.temporal_rectify(radius=radius))
         torch.cuda.synchronize()
-        assert same(a.cpu().numpy(), b.cpu().numpy()), name                          # a first frame takes no history: nothing to rectify
+        assert same_any_nan(a.cpu().numpy(), b.cpu().numpy()), name                          # a first frame takes no history: nothing to rectify
 
 
 # ---- 4. the hand-worked cases ---------------------------------------------------------------------------------------------------------
@@ -172,7 +172,7 @@ def test_hand_worked_cases_on_the_gpu(rt, cuda, case):
         torch.cuda.synchronize()
         got = out.cpu().numpy()
         trm.check_case(case, got)
-        assert same(got, ref), case["name"]
+        assert same_any_nan(got, ref), case["name"]
     W.close()
 
 
@@ -192,7 +192,7 @@ def test_captured_in_a_graph(rt, cuda, anims, moving):
     hist.fill_(3.0)
     g.replay()
     torch.cuda.synchronize()
-    assert same(hist.cpu().numpy(), h[2].cpu().numpy())
+    assert same_any_nan(hist.cpu().numpy(), h[2].cpu().numpy())
 
 
 # ---- 6. refusals -----------------------------------------------------------------------------------------------------------------------

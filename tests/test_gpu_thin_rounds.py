@@ -21,9 +21,10 @@ import pytest
 import grid_threshold_worlds as gw
 import material_edge_worlds as mw
 import reference_cases as rc
+from bitcmp import same_nan_as_ref
+from gpu_frames import render_frame, states_of
 from oracle_lib import OracleScene
-from test_gpu_grid_thresholds import assert_records, traced
-from test_gpu_parity import gpu_render
+from tree_compare import assert_records, traced
 
 pytestmark = pytest.mark.gpu
 
@@ -231,17 +232,13 @@ def oracle_frames():
     return whole, whole_st, passes
 
 
-def states_of(st):
-    return st.cpu().numpy().view(np.uint32).reshape(-1, 12)
-
-
 def test_frame_whole_and_progressive(rt, cuda):
     torch = cuda
     W = rt.World(10000, NX, NY)
     O = rt.Octree(W, 32)
     whole, whole_st, passes = oracle_frames()
-    fb, st = gpu_render(rt, torch, W, O, NX, NY, NS)
-    assert rc.same(fb.cpu().numpy().reshape(NY, NX, 3), whole)
+    fb, st = render_frame(rt, torch, W, O, NX, NY, NS)
+    assert same_nan_as_ref(fb.cpu().numpy().reshape(NY, NX, 3), whole)
     assert np.array_equal(states_of(st)[:, :6], whole_st[:, :6])
     st = rt.alloc_rand_state(NX, NY); fb = rt.alloc_fb(NX, NY)
     rt.render_init(NX, NY, st)
@@ -249,7 +246,7 @@ def test_frame_whole_and_progressive(rt, cuda):
         rt.render_progressive(fb, NX, NY, k, W, st, O)
         if k in passes:
             torch.cuda.synchronize()
-            assert rc.same(fb.cpu().numpy().reshape(NY, NX, 3), passes[k][0]), k
+            assert same_nan_as_ref(fb.cpu().numpy().reshape(NY, NX, 3), passes[k][0]), k
             assert np.array_equal(states_of(st)[:, :6], passes[k][1][:, :6]), k
 
 

@@ -20,6 +20,7 @@ import pytest
 import grid_threshold_worlds as gw
 import ref_lib
 import reference_cases as rc
+from bitcmp import same_nan_as_ref
 
 N_RAYS = 24000
 IDS = ["%s%s-%s" % (n, "_" + v if v else "", mode) for n, v, mode, _ in gw.CASES]
@@ -66,8 +67,8 @@ def test_the_builders_are_deterministic():
 
 
 def test_lattice_rays_default_origin_is_unchanged():
-    """the optional g0 of test_gpu_strips.lattice_rays: leaving it out, or passing the root-box formula, gives the same bytes"""
-    from test_gpu_strips import lattice_rays
+    """the optional g0 of world_cases.lattice_rays: leaving it out, or passing the root-box formula, gives the same bytes"""
+    from world_cases import lattice_rays
     sp = gw.world("rlim")[0]
     c, r = sp["center"].astype(np.float64), sp["radius"].astype(np.float64)
     info = dict(grid_dim=104, cell_size=0.2347186952829361)
@@ -297,4 +298,4 @@ def test_oracle_records_are_the_reference_builds(name, variant, mode, spl):
         assert (got["sphere"] != -2).all(), fam                   # no ghost slot's record in binary32
         assert np.array_equal(got["hit"], ref["hit"]) and np.array_equal(got["sphere"], ref["sphere"]), fam
         for f in ("t", "p", "normal"):
-            assert rc.same(got[f], ref[f]), (fam, f)
+            assert same_nan_as_ref(got[f], ref[f]), (fam, f)

@@ -10,13 +10,10 @@ import numpy as np
 import pytest
 
 import abi_header
+from bitcmp import raw_bits
 from oracle_lib import OracleScene, ppm_bytes
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-
-
-def u32(a):
-    return np.ascontiguousarray(a).view(np.uint32)
 
 
 def test_abi_exports_every_declared_symbol(rt):
@@ -117,16 +114,16 @@ def test_world_camera_octree_match_oracle(rt, precision, n, spl):
     S = OracleScene(n, 1200, 800, fp16=bool(precision), use_octree=True, spl=spl)
     geom, mat, kind = S.spheres()
     sp = W.spheres
-    assert np.array_equal(u32(sp["center"]), u32(geom[:, :3])) and np.array_equal(u32(sp["radius"]), u32(geom[:, 3]))
+    assert np.array_equal(raw_bits(sp["center"]), raw_bits(geom[:, :3])) and np.array_equal(raw_bits(sp["radius"]), raw_bits(geom[:, 3]))
     assert np.array_equal(sp["material"], kind)
-    assert np.array_equal(u32(sp["albedo"]), u32(mat[:, :3])) and np.array_equal(u32(sp["param"]), u32(mat[:, 3]))
+    assert np.array_equal(raw_bits(sp["albedo"]), raw_bits(mat[:, :3])) and np.array_equal(raw_bits(sp["param"]), raw_bits(mat[:, 3]))
     assert W.created == S.info()["real"]
-    assert np.array_equal(u32(W.camera).ravel(), u32(S.camera()))
-    assert np.array_equal(u32(W.rand_state).ravel()[:6], S.world_rng()[:6])        # *rand_state = local_rand_state
+    assert np.array_equal(raw_bits(W.camera).ravel(), raw_bits(S.camera()))
+    assert np.array_equal(raw_bits(W.rand_state).ravel()[:6], S.world_rng()[:6])        # *rand_state = local_rand_state
     t = S.octree()
     nodes = O.nodes()
     counts, idx = O.leaves()
-    assert np.array_equal(nodes["level"], t["level"]) and np.array_equal(u32(nodes["aabb"]), u32(t["box"]))
+    assert np.array_equal(nodes["level"], t["level"]) and np.array_equal(raw_bits(nodes["aabb"]), raw_bits(t["box"]))
     assert np.array_equal(nodes["children"], t["children"])
     assert np.array_equal(counts, t["counts"]) and np.array_equal(idx, t["indices"])
     info, oinfo = O.info(), S.info()
@@ -152,7 +149,7 @@ def test_part_without_tiles_is_a_no_op(rt):
 def test_camera_init_matches_create_world(rt):
     W = rt.World(22, 1200, 800)
     cam = rt.camera_init((13, 2, 3), (0, 0, 0), (0, 1, 0), 30.0, np.float32(1200) / np.float32(800), np.float32(0.1), 10.0)
-    assert np.array_equal(u32(cam), u32(W.camera))
+    assert np.array_equal(raw_bits(cam), raw_bits(W.camera))
 
 
 def test_ppm_writer_matches_oracle(rt, tmp_path):

@@ -14,12 +14,9 @@ import numpy as np
 import pytest
 
 import material_edge_worlds as mw
+from bitcmp import f32_bits
 
 NX, NY, NS = 64, 40, 16
-
-
-def bits(a):
-    return np.ascontiguousarray(a, np.float32).view(np.uint32)
 
 
 def render(name, variant=None, tree=False, sp=None):
@@ -29,7 +26,7 @@ def render(name, variant=None, tree=False, sp=None):
 
 
 def differing(a, b):
-    return float((bits(a) != bits(b)).any(axis=2).mean())
+    return float((f32_bits(a) != f32_bits(b)).any(axis=2).mean())
 
 
 def test_the_builders_are_deterministic_and_large_enough_for_the_candidate_grid():
@@ -67,7 +64,7 @@ def test_white_room_is_black_and_every_path_runs_to_the_depth_limit(tree):
     fb, rays = render("white_room", tree=tree)
     print("white_room tree=%d: %.2f rays per sample, %d black pixels" % (tree, rays, (fb == 0).all(axis=2).sum()))
     assert rays >= 40
-    assert (bits(fb) == 0).all()
+    assert (f32_bits(fb) == 0).all()
 
 
 def test_mirror_room_paths_run_to_the_depth_limit():

@@ -1,7 +1,7 @@
 """The CPU oracle (oracle/rt_oracle.hpp) against a CPU build of the REFERENCE's own headers (`make -C oracle ref`: oracle/ref_capi.cpp
 over the nine unmodified headers, in fp32 and in USE_FP16, one library per SPHERES_PER_LEAF).  Not marked gpu.
 
-Every comparison is bit equality; a NaN compares as "NaN where the reference has NaN" (test_gpu_reference_edges.same).  No tolerance
+Every comparison is bit equality; a NaN compares as "NaN where the reference has NaN" (bitcmp.same_nan_as_ref).  No tolerance
 appears anywhere.  Worlds: create_world at N = 22, 500 and 10000, three random_world worlds, the nine of material_edge_worlds.WORLDS
 (tests/reference_cases.py), each in both precisions.  Compared: buildOctree (every node, leaf, count and drop counter), hit records
 through hitable_list::hit and hitTree, one-bounce material::scatter along lockstep paths (hit record, return value, attenuation,
@@ -32,6 +32,7 @@ import material_edge_worlds as mw
 import oracle_lib
 import ref_lib
 import reference_cases as rc
+from bitcmp import f32_bits, same_nan_as_ref
 
 F = np.float32
 
@@ -69,7 +70,7 @@ def test_the_stand_in_rng_gives_the_recorded_known_answers():
     for _ in range(4):
         d, st = ref_lib.curand_uniform(st)
         u.append(d)
-    u = rc.bits(np.array(u))
+    u = f32_bits(np.array(u))
     assert u[:, 0].tolist() == [0x3e48b09e, 0x3ee873b3, 0x3eb7ce17, 0x3f39620a]
     assert u[:, 1].tolist() == [0x3eb57405, 0x3f5a9bd8, 0x3ecb5bc7, 0x3f78538f]
 
@@ -84,7 +85,7 @@ def compare_trees(name, fp16, spl):
     words = 0
     for k in ("level", "box", "children", "counts", "indices"):
         assert t[k].shape == o[k].shape and t[k].dtype == o[k].dtype, k
-        assert rc.same(t[k], o[k]) if k == "box" else np.array_equal(t[k], o[k]), k
+        assert same_nan_as_ref(t[k], o[k]) if k == "box" else np.array_equal(t[k], o[k]), k
         words += t[k].size
     print("%s %s spl %d: %d octree words, %d nodes, %d leaves, dropped %d full / %d outside" % (
         name, "fp16" if fp16 else "fp32", ref.spl, words, info["node_count"], info["leaf_count"], info["dropped_full"], info["dropped_outside"]))
@@ -123,7 +124,7 @@ def test_hit_records(name, fp16):
         assert (a["sphere"] != -2).all(), "the reference hit a ghost slot"
         assert np.array_equal(a["hit"], b["hit"]) and np.array_equal(a["sphere"], b["sphere"]), mode
         for k in ("t", "p", "normal"):
-            assert rc.same(b[k], a[k]), (mode, k)
+            assert same_nan_as_ref(b[k], a[k]), (mode, k)
         print("%s %s %s: %d hit records compared, %d hits" % (name, "fp16" if fp16 else "fp32", ("", "list", "tree")[mode], len(rays), a["hit"].sum()))
         assert a["hit"].sum() > len(rays) // 50
 
@@ -163,7 +164,7 @@ def test_lockstep_paths(name, fp16):
     for _ in range(2):
         st0 = ref_lib.curand_uniform(st0, fp16)[1]
     orays, ost = oracle_lib.get_ray(cam, s, t, st0, fp16=fp16)
-    assert rc.same(orays, rays) and np.array_equal(ost, st)
+    assert same_nan_as_ref(orays, rays) and np.array_equal(ost, st)
     if fp16 and name not in rc.EDGE and name != "random_3":      # (random_3's camera happens to stand close: its camera paths do bounce)
         # binary16 from create_world's and random_world's far cameras: b * b overflows and nearly every camera ray misses everything
         # (SURVEY fact 8).  So that scatter is compared there too, as many paths again start on the world's ray set, inside the field
@@ -182,12 +183,12 @@ def test_lockstep_paths(name, fp16):
             count("ghost_records_" + mode, (~real).sum())
             assert np.array_equal(a["hit"][real], b["hit"][real]) and np.array_equal(a["sphere"][real], b["sphere"][real]), (depth, mode)
             for k in ("t", "p", "normal"):
-                assert rc.same(b[k][real], a[k][real]), (depth, mode, k)
+                assert same_nan_as_ref(b[k][real], a[k][real]), (depth, mode, k)
         ret, att, sc, sta = out
         oret, oatt, osc, osta = oout
         ok = ~x["excluded"]
         assert np.array_equal(ret, oret), depth
-        assert rc.same(oatt, att) and rc.same(osc[:, :3], sc[:, :3]) and rc.same(osc[ok, 3:], sc[ok, 3:]), depth
+        assert same_nan_as_ref(oatt, att) and same_nan_as_ref(osc[:, :3], sc[:, :3]) and same_nan_as_ref(osc[ok, 3:], sc[ok, 3:]), depth
         assert np.array_equal(osta, sta), depth
         # witnesses, from the reference's side
         sph, kd = x["sphere"], kind[x["sphere"]]
@@ -232,11 +233,11 @@ def test_camera_constructor_fp32(nx, ny, aperture):
     c = mw.CAMERA
     args = (c["lookfrom"], c["lookat"], c["vup"], c["vfov"], float(F(nx) / F(ny)), c["aperture"] if aperture is None else aperture, c["focus"])
     ref = ref_lib.camera(*args)
-    assert np.array_equal(rc.bits(oracle_lib.make_camera(*args)), rc.bits(ref))
-    assert np.array_equal(rc.bits(mw.camera_floats(nx, ny, aperture)), rc.bits(ref))
+    assert np.array_equal(f32_bits(oracle_lib.make_camera(*args)), f32_bits(ref))
+    assert np.array_equal(f32_bits(mw.camera_floats(nx, ny, aperture)), f32_bits(ref))
     args = ((13, 2, 3), (0, 0, 0), (0, 1, 0), 30.0, float(F(nx) / F(ny)), 0.1, 10.0)
-    assert np.array_equal(rc.bits(oracle_lib.make_camera(*args)), rc.bits(ref_lib.camera(*args)))
-    assert np.array_equal(rc.bits(oracle_lib.OracleScene(22, nx, ny).camera()), rc.bits(ref_lib.camera(*args)))
+    assert np.array_equal(f32_bits(oracle_lib.make_camera(*args)), f32_bits(ref_lib.camera(*args)))
+    assert np.array_equal(f32_bits(oracle_lib.OracleScene(22, nx, ny).camera()), f32_bits(ref_lib.camera(*args)))
 
 
 @pytest.mark.parametrize("fp16", [False, True])
@@ -251,5 +252,5 @@ def test_get_ray(fp16):
             cam, s, t = rc.half(cam), rc.half(s), rc.half(t)
         a, sa = ref_lib.get_ray(cam, s, t, st, fp16)
         b, sb = oracle_lib.get_ray(cam, s, t, st, fp16)
-        assert rc.same(b, a) and np.array_equal(sa, sb)
+        assert same_nan_as_ref(b, a) and np.array_equal(sa, sb)
         assert (sa != st).any()

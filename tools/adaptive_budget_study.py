@@ -14,14 +14,14 @@
       device times of one round: the selection kernels, seed and finalise, the round's render kernel, and k_adapt_refine_seed plus one
       k_adapt_refine_check of a refinement on the same frame (the closest existing per-round bookkeeping); median of REPS calls.
 """
-import csv
-import glob
 import os
 import sys
 import time
 import zlib
 
 import numpy as np
+
+from kernel_trace import read_trace, short_name
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "dd2360-raytracing_amd"))
@@ -208,10 +208,7 @@ def kernels():
 
 
 def kernel_report(d, path):
-    f = glob.glob(os.path.join(d, "**", "*kernel_trace.csv"), recursive=True)[0]
-    rows = list(csv.DictReader(open(f)))
-    rows.sort(key=lambda r: int(r["Start_Timestamp"]))
-    ev = [(r["Kernel_Name"].split("(")[0].replace("rt::", "").replace("void ", ""), (int(r["End_Timestamp"]) - int(r["Start_Timestamp"])) / 1e3) for r in rows]
+    ev = [(short_name(name), dur) for name, dur in read_trace(d)]
     say, close = writer(path)
     say()
     say("## one round under rocprofv3 --kernel-trace --stats (tools/adaptive_budget_study.py --kernels): a quarter of the frame, batch 8;")

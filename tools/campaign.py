@@ -6,7 +6,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "dd2360-raytracing_amd")); sys.path.insert(0, os.path.join(ROOT, "tests"))
 import numpy as np, torch
 import rt_amd as rt
-from test_gpu_parity import random_rays, random_world
+from world_cases import random_rays, random_world
 
 bad = 0
 t0 = time.time()

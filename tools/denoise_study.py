@@ -12,8 +12,6 @@ the pixels that are finite in the reference, the raw and the denoised frame (the
 negative number, material.h:95); SSIM is tools/image_metrics.py's (the reference notebook's, on 8-bit greyscale).  Times: host clock
 around a device synchronise, median of REPS runs after a warm-up.
 """
-import csv
-import glob
 import os
 import sys
 import time
@@ -23,6 +21,8 @@ import numpy as np
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "dd2360-raytracing_amd"))
 sys.path.insert(0, os.path.join(ROOT, "tools"))
+
+from kernel_trace import read_trace, short_name      # noqa: E402
 
 NX, NY, N, SPL = 1200, 800, 10000, 32
 REPS = 7
@@ -159,15 +159,10 @@ def kernels():
 def kernel_report(d, path):
     """per-kernel times from the kernel trace of a --kernels run: launches are grouped into calls (k_guides, prepare, then a level
     kernel per level) in trace order; the first call of each frame is the warm-up"""
-    f = glob.glob(os.path.join(d, "**", "*kernel_trace.csv"), recursive=True)[0]
-    rows = list(csv.DictReader(open(f)))
-    rows.sort(key=lambda r: int(r["Start_Timestamp"]))
     calls, cur = [], None
-    for r in rows:
-        name = r["Kernel_Name"]
-        dur = (int(r["End_Timestamp"]) - int(r["Start_Timestamp"])) / 1e3
+    for name, dur in read_trace(d):
         if name.startswith("void rt::k_guides") or name.startswith("rt::k_guides") or "k_guides" in name.split("(")[0]:
-            cur = [("guides " + name.split("(")[0].replace("void ", "").replace("rt::", ""), dur)]
+            cur = [("guides " + short_name(name), dur)]
             calls.append(cur)
         elif cur is not None and ("k_denoise" in name.split("(")[0]):
             cur.append(("prepare" if "prepare" in name else "level %d" % (len(cur) - 2), dur))

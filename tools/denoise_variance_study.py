@@ -12,12 +12,12 @@ pixels that are finite in the reference, the raw and both filtered frames.  A un
 min_spp = max_spp = n (rel_error 0): bit for bit rt_render(n), plus the state.  The adaptive frame is that of DESIGN.md §5.9:
 8 / 8 / 128, rel_error 0.10, floor 0.02.
 """
-import csv
-import glob
 import os
 import sys
 
 import numpy as np
+
+from kernel_trace import read_trace
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "dd2360-raytracing_amd"))
@@ -155,13 +155,9 @@ def kernels():
 def kernel_report(d, path, label):
     """per-level times of both filters from the kernel trace of a --kernels run: a prepare kernel opens a call, the level kernels
     that follow are its levels in order; the first call of each filter on each frame is the warm-up"""
-    f = glob.glob(os.path.join(d, "**", "*kernel_trace.csv"), recursive=True)[0]
-    rows = list(csv.DictReader(open(f)))
-    rows.sort(key=lambda r: int(r["Start_Timestamp"]))
     calls, cur = [], None
-    for r in rows:
-        name = r["Kernel_Name"].split("(")[0]
-        dur = (int(r["End_Timestamp"]) - int(r["Start_Timestamp"])) / 1e3
+    for name, dur in read_trace(d):
+        name = name.split("(")[0]
         if "k_denoise" not in name:
             continue
         if "prepare" in name:

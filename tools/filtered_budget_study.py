@@ -16,14 +16,14 @@
       device times of the key kernel (k_budget_keys_filtered), of the rest of the selection, of k_budget_keys and of one raw and one
       filtered round's render kernel; median of REPS calls after a warm-up.  Once per library as well.
 """
-import csv
-import glob
 import os
 import sys
 import time
 import zlib
 
 import numpy as np
+
+from kernel_trace import read_trace, short_name
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "dd2360-raytracing_amd"))
@@ -220,10 +220,7 @@ KEY_KERNELS = ("k_budget_keys_filtered",)
 
 
 def kernel_report(d, path):
-    f = glob.glob(os.path.join(d, "**", "*kernel_trace.csv"), recursive=True)[0]
-    rows = list(csv.DictReader(open(f)))
-    rows.sort(key=lambda r: int(r["Start_Timestamp"]))
-    ev = [(r["Kernel_Name"].split("(")[0].replace("rt::", "").replace("void ", ""), (int(r["End_Timestamp"]) - int(r["Start_Timestamp"])) / 1e3) for r in rows]
+    ev = [(short_name(name), dur) for name, dur in read_trace(d)]
     say, close = writer(path)
     say()
     say("## %s under rocprofv3 --kernel-trace --stats (tools/filtered_budget_study.py --kernels): K a quarter of the frame, batch 8;" % os.path.basename(d.rstrip("/")))

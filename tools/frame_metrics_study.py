@@ -10,8 +10,6 @@ C3 is 1200x800, N = 10 000, octree SPL 32: rt_render(1024) against 16 spp, raw a
 world (N = 100 000, SPL 320) at 3840x2160, 64 spp against 8 spp.  The host route is what every study tool does today: copy both float
 frames to the host, tools/image_metrics.compare_frames (numpy / scipy) and the studies' RMSE over the pixels finite in both frames.
 """
-import csv
-import glob
 import os
 import sys
 import time
@@ -21,6 +19,8 @@ import numpy as np
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "dd2360-raytracing_amd"))
 sys.path.insert(0, os.path.join(ROOT, "tools"))
+
+from kernel_trace import read_trace      # noqa: E402
 
 REPS = 7
 FRAMES = (("C3 1200x800", 10000, 32, 1200, 800, 1024, 16), ("C5 world 3840x2160", 100000, 320, 3840, 2160, 64, 8))
@@ -156,10 +156,7 @@ def kernels():
 def kernel_report(d, path):
     """median kernel times from the trace of a --kernels run: per frame size, the calls come in the order kernels() issues them and the
     first repetition is the warm-up"""
-    f = glob.glob(os.path.join(d, "**", "*kernel_trace.csv"), recursive=True)[0]
-    rows = [r for r in csv.DictReader(open(f)) if "k_frame" in r["Kernel_Name"]]
-    rows.sort(key=lambda r: int(r["Start_Timestamp"]))
-    dur = [((int(r["End_Timestamp"]) - int(r["Start_Timestamp"])) / 1e3, r["Kernel_Name"]) for r in rows]
+    dur = [(us, name) for name, us in read_trace(d) if "k_frame" in name]
     per = 5 * (REPS + 1)                                       # compare, final, compare, final, levels
     lines = ["", "## kernel times under rocprofv3 --kernel-trace --stats (tools/frame_metrics_study.py --kernels), median of %d calls, us" % REPS,
              "%-22s %24s %24s %24s %16s" % ("frame", "k_frame_compare + map", "k_frame_compare", "k_frame_compare_final", "k_frame_levels")]

@@ -17,8 +17,6 @@ Every frame spends the same mean of SPP samples a pixel, three ways:
   history   the same by rt_render_adaptive_spend_temporal (the error left after the merge with the last frame's history)
 and each way keeps its own chain of histories: rt_temporal_accumulate (defaults) after the spend.
 """
-import csv
-import glob
 import os
 import sys
 
@@ -28,6 +26,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "dd2360-raytracing_amd"))
 sys.path.insert(0, os.path.join(ROOT, "tools"))
 
+from kernel_trace import durations, read_trace                                             # noqa: E402
 from temporal_study import FRAMES, N, NX, NY, REPS, SPL, SPP, STEP, Path, orbit_camera      # noqa: E402
 
 LOW = 8
@@ -199,17 +198,8 @@ def kernels():
 def kernel_report(d, path):
     """times of k_budget_keys_temporal beside k_temporal_accumulate (the calls with a history) from the kernel trace of a --kernels run:
     median, minimum and maximum of REPS calls; the first call of each kernel on each frame size is the warm-up"""
-    f = glob.glob(os.path.join(d, "**", "*kernel_trace.csv"), recursive=True)[0]
-    rows = list(csv.DictReader(open(f)))
-    rows.sort(key=lambda r: int(r["Start_Timestamp"]))
-    acc, key = [], []
-    for r in rows:
-        name = r["Kernel_Name"]
-        dur = (int(r["End_Timestamp"]) - int(r["Start_Timestamp"])) / 1e3
-        if "k_temporal_accumulate" in name:
-            acc.append(dur)
-        elif "k_budget_keys_temporal" in name:
-            key.append(dur)
+    ev = read_trace(d)
+    acc, key = durations(ev, "k_temporal_accumulate"), durations(ev, "k_budget_keys_temporal")
     lines = ["", "## kernel times under rocprofv3 --kernel-trace --stats (tools/temporal_budget_study.py --kernels), %d calls each, us" % REPS,
              "# k_budget_keys_temporal has to move %d bytes a pixel (state 24, guides 32 + 32, history 20 read, key 4 written); k_temporal_accumulate 128" % BYTES_PER_PIXEL,
              "%-22s %38s %10s %38s" % ("frame", "k_budget_keys_temporal med (min .. max)", "GB/s", "k_temporal_accumulate med (min .. max)")]

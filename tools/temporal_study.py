@@ -21,7 +21,6 @@ and in all four frames compared, once over all of them and once over those whose
 """
 import csv
 import glob
-import math
 import os
 import sys
 
@@ -29,7 +28,10 @@ import numpy as np
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "dd2360-raytracing_amd"))
-sys.path.insert(0, os.path.join(ROOT, "tests"))                  # temporal_model.reproject: how far the image moves
+sys.path.insert(0, os.path.join(ROOT, "tests"))                  # temporal_model.reproject: how far the image moves; world_cases
+
+from kernel_trace import durations, is_instance, read_trace      # noqa: E402
+from world_cases import orbit_camera                             # noqa: E402  (the tests' camera path, the same orbit)
 
 NX, NY, N, SPL = 1200, 800, 10000, 32
 FRAMES, STEP, SPP = 8, 0.2, 16
@@ -40,12 +42,6 @@ JOINT_HISTORY, JOINT_TOLERANCE = (8, 16, 24, 32, 48, 64), (0.01, 0.03, 0.1)     
 # bytes k_temporal_accumulate has to move per pixel: the state (24), this frame's guide (32) and history (20 written), and of the last
 # frame one guide (32) and one history (20) — the four gathers of neighbouring pixels overlap, each byte of the last frame is needed once
 BYTES_PER_PIXEL = 24 + 32 + 20 + 32 + 20
-
-
-def orbit_camera(rt, deg, nx, ny):
-    th = math.radians(deg)
-    lookfrom = (13 * math.cos(th) + 3 * math.sin(th), 2.0, -13 * math.sin(th) + 3 * math.cos(th))
-    return rt.camera_init(lookfrom, (0, 0, 0), (0, 1, 0), 30.0, nx / ny, 0.1, 10.0)
 
 
 class Path:
@@ -205,17 +201,8 @@ def kernels():
 def kernel_report(d, path):
     """median times of k_temporal_accumulate (the calls with a history) and of k_denoise_var_level<true,1> from the kernel trace of a
     --kernels run; the first call on each frame size is the warm-up"""
-    f = glob.glob(os.path.join(d, "**", "*kernel_trace.csv"), recursive=True)[0]
-    rows = list(csv.DictReader(open(f)))
-    rows.sort(key=lambda r: int(r["Start_Timestamp"]))
-    acc, lev = [], []
-    for r in rows:
-        name = r["Kernel_Name"]
-        dur = (int(r["End_Timestamp"]) - int(r["Start_Timestamp"])) / 1e3
-        if "k_temporal_accumulate" in name:
-            acc.append(dur)
-        elif "k_denoise_var_level<true, 1>" in name or "k_denoise_var_level<true,1>" in name or "k_denoise_var_levelILb1ELi1E" in name:
-            lev.append(dur)
+    ev = read_trace(d)
+    acc, lev = durations(ev, "k_temporal_accumulate"), durations(ev, "k_denoise_var_level", True, 1)
     per = REPS + 2                                     # per frame size: the first frame's call, the warm-up and REPS timed calls
     lines = ["", "## kernel times under rocprofv3 --kernel-trace --stats (tools/temporal_study.py --kernels), median of %d calls, us" % REPS,
              "# k_temporal_accumulate has to move %d bytes a pixel (state 24, guides 32 + 32, history 20 read + 20 written)" % BYTES_PER_PIXEL,
@@ -359,15 +346,10 @@ def rectify_kernels():
 
 def rectify_kernel_report(d, path):
     """median times of the three kernels of a --rectify-kernels run; the first call of each on each frame size is the warm-up"""
-    f = glob.glob(os.path.join(d, "**", "*kernel_trace.csv"), recursive=True)[0]
-    rows = list(csv.DictReader(open(f)))
-    rows.sort(key=lambda r: int(r["Start_Timestamp"]))
     t = {"moving": [], "r1": [], "r2": []}
-    for r in rows:
-        name = r["Kernel_Name"]
-        dur = (int(r["End_Timestamp"]) - int(r["Start_Timestamp"])) / 1e3
+    for name, dur in read_trace(d):
         if "k_temporal_accumulate_rectified" in name:
-            t["r2" if ("1, 2>" in name or "true, 2>" in name or "Lb1ELi2E" in name) else "r1"].append(dur)
+            t["r2" if is_instance(name, "k_temporal_accumulate_rectified", True, 2) else "r1"].append(dur)
         elif "k_temporal_accumulate_moving" in name:
             t["moving"].append(dur)
     lines = ["", "## kernel times under rocprofv3 --kernel-trace --stats (tools/temporal_study.py --rectify-kernels), median of %d calls, us" % REPS,
@@ -390,7 +372,7 @@ def rectify_pmc_report(d, path):
         for r in csv.DictReader(open(f)):
             name = r["Kernel_Name"]
             if "k_temporal_accumulate_rectified" in name:
-                key = "r2" if ("true, 2>" in name or "Lb1ELi2E" in name) else "r1"
+                key = "r2" if is_instance(name, "k_temporal_accumulate_rectified", True, 2) else "r1"
             elif "k_temporal_accumulate_moving" in name:
                 key = "moving"
             else:
