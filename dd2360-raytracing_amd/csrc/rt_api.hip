@@ -1406,9 +1406,8 @@ int rt_render_kernel_name(const rt_world* world, const rt_octree* d_octree, int 
 
 int rt_assemble(void* fb_full, const void* fb_parts, int max_x, int max_y, int nparts, int precision, void* stream) {
     if (!fb_full || !fb_parts || max_x <= 0 || max_y <= 0 || nparts < 1) return RT_EINVAL;
-    if (precision == RT_PRECISION_FP16) return (int)launch_assemble_h(fb_full, fb_parts, max_x, max_y, nparts, (hipStream_t)stream);
-    if (precision != RT_PRECISION_FP32) return RT_EINVAL;
-    return (int)launch_assemble((float*)fb_full, (const float*)fb_parts, max_x, max_y, nparts, (hipStream_t)stream);
+    if (precision != RT_PRECISION_FP32 && precision != RT_PRECISION_FP16) return RT_EINVAL;
+    return (int)launch_gather(precision == RT_PRECISION_FP16 ? kGatherF16x3 : kGatherF32x3, fb_full, fb_parts, max_x, max_y, nparts, nullptr, 0, (hipStream_t)stream);
 }
 
 int rt_assemble_split(void* fb_full, const void* fb_parts, int max_x, int max_y, int nparts, const int64_t* starts, int64_t part_stride_px, int precision, void* stream) {
@@ -1418,7 +1417,7 @@ int rt_assemble_split(void* fb_full, const void* fb_parts, int max_x, int max_y,
     if (starts[0] != 0 || starts[nparts] != tiles) return RT_EINVAL;
     long long st64[rt::kMaxSplitParts + 1];
     for (int p = 0; p <= nparts; ++p) { if (p && starts[p] < starts[p - 1]) return RT_EINVAL; if (p && (starts[p] - starts[p - 1]) * 64 > part_stride_px && nparts > 1) return RT_EINVAL; st64[p] = starts[p]; }
-    return (int)launch_assemble_split(fb_full, fb_parts, max_x, max_y, nparts, st64, part_stride_px, precision == RT_PRECISION_FP16, (hipStream_t)stream);
+    return (int)launch_gather(precision == RT_PRECISION_FP16 ? kGatherF16x3 : kGatherF32x3, fb_full, fb_parts, max_x, max_y, nparts, st64, part_stride_px, (hipStream_t)stream);
 }
 
 // rt_split_balanced: the pilot pass over the whole frame, the counts to the host, the cuts in integer arithmetic

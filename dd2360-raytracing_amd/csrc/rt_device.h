@@ -101,7 +101,7 @@ inline DenoiseVarLevel denoise_var_level(const rt_denoise_var_params& P, int l) 
     return L;
 }
 constexpr int kMaxSplitParts = 64;
-struct SplitStarts { long long s[kMaxSplitParts + 1]; };      // first tile of every band of a balanced split, and the tile count (k_assemble_split)
+struct SplitStarts { long long s[kMaxSplitParts + 1]; };      // first tile of every band of a balanced split, and the tile count (k_gather by bands, rt_assemble.hip)
 
 // One node of the traversal copy of the Octree, in depth-first pre-order (children in index order, the visit
 // order of traverseTree, acceleration_structure.h:276-304).  48 bytes = 3 x 16 B so a lane fetches it with

@@ -1037,20 +1037,6 @@ __global__ __launch_bounds__(256) void k_trace_h(DevScene S, DevTree T, const fl
     out[gid] = h;
 }
 
-__global__ __launch_bounds__(256) void k_assemble_h(uint16_t* full, const uint16_t* parts, int max_x, int max_y, int tiles_x, int nparts, long long part_stride_px, long long n_tiles) {
-    const int lane = threadIdx.x & 63;
-    const long long tile = (long long)blockIdx.x * 4 + (threadIdx.x >> 6);
-    if (tile >= n_tiles) return;
-    const int tx = (int)(tile % tiles_x), ty = (int)(tile / tiles_x);
-    const int i = tx * 8 + (lane & 7), j = ty * 8 + (lane >> 3);
-    if (i >= max_x || j >= max_y) return;
-    int owner; long long local_tile;
-    part_owner(tile, nparts, owner, local_tile);
-    const long long src = owner * part_stride_px + local_tile * 64 + lane;
-    const long long dst = (long long)j * max_x + i;
-    full[dst * 3 + 0] = parts[src * 3 + 0]; full[dst * 3 + 1] = parts[src * 3 + 1]; full[dst * 3 + 2] = parts[src * 3 + 2];
-}
-
 } // namespace h16
 
 // the ONE ladder from the run-time `tree` to the kernels' TREE argument: f is called with std::true_type or std::false_type
@@ -1107,14 +1093,5 @@ hipError_t read_h16_stats(unsigned long long* out, int reset) {
     return e;
 }
 #endif
-
-hipError_t launch_assemble_h(void* full, const void* parts, int max_x, int max_y, int nparts, hipStream_t st) {
-    const int tiles_x = (max_x + 7) / 8, tiles_y = (max_y + 7) / 8;
-    const long long tiles = (long long)tiles_x * tiles_y;
-    const long long per_part = part_local_tiles(tiles, 0, nparts) * 64;
-    const unsigned blocks = (unsigned)((tiles + 3) / 4);
-    hipLaunchKernelGGL(h16::k_assemble_h, dim3(blocks), dim3(256), 0, st, (uint16_t*)full, (const uint16_t*)parts, max_x, max_y, tiles_x, nparts, per_part, tiles);
-    return hipGetLastError();
-}
 
 } // namespace rt

@@ -62,16 +62,16 @@ hipError_t launch_adapt_refine_check(float* fb, const AdaptState& s, const unsig
 hipError_t launch_adapt_zero(unsigned int* p, int n, hipStream_t st);
 
 // ---- rt_assemble.hip: part buffers gathered into the row-major frame
-hipError_t launch_assemble(float* full, const float* parts, int max_x, int max_y, int nparts, hipStream_t st);
-hipError_t launch_assemble_spp(int32_t* full, const int32_t* parts, int max_x, int max_y, int nparts, hipStream_t st);
-hipError_t launch_assemble_split(void* full, const void* parts, int max_x, int max_y, int nparts, const long long* starts, long long part_stride_px, bool half, hipStream_t st);
+// (what an element is: 3 floats, 3 halves, one int32; starts == nullptr: parts in runs, each padded to part 0's size — else the
+// starts[nparts + 1] of a balanced split's bands, band p's buffer part_stride_px elements behind band p - 1's)
+enum GatherElem { kGatherF32x3, kGatherF16x3, kGatherI32x1 };
+hipError_t launch_gather(GatherElem elem, void* full, const void* parts, int max_x, int max_y, int nparts, const long long* starts, long long part_stride_px, hipStream_t st);
 
 // ---- rt_kernels_fp16.hip: the render path in binary16
 hipError_t launch_pilot_h(const RenderArgs& A, bool tree, int* cost, unsigned char* pilot, hipStream_t st);
 hipError_t launch_tile_order_h(const RenderArgs& A, bool tree, int* cost, unsigned int* order, unsigned char* flags, unsigned int* long_list, hipStream_t st);
 hipError_t launch_render_h(const RenderArgs& A, bool tree, int mode, hipStream_t st);
 hipError_t launch_trace_h(const DevScene& S, const DevTree& T, bool tree, const float* rays, long long n, rt_hit_record* out, hipStream_t st);
-hipError_t launch_assemble_h(void* full, const void* parts, int max_x, int max_y, int nparts, hipStream_t st);
 const char* render_kernel_name_h(bool tree, int mode);
 #ifdef RT_H16_STATS
 hipError_t read_h16_stats(unsigned long long* out, int reset);

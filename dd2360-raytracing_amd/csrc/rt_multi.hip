@@ -1,11 +1,11 @@
 // rt_multi.hip — one frame over the GPUs of a node: rt_multi_render (include/rt_amd.h).
 //
 // No reference counterpart (the reference is single-GPU); the launch surface it extends is main.cu:422-427.  One process per
-// GPU.  The frame's 8x8 tiles (the reference's block shape, main.cu:351-352) are split over the ranks — by default into horizontal
-// bands of equal predicted cost (rt_split_balanced: every rank runs the same pilot pass over the whole frame and cuts it the same
-// way, no communication; a GPU's rays then meet the same part of the scene, as in the undivided frame), or dealt round-robin in
-// runs of RT_PART_RUN consecutive tiles (RT_SPLIT_RUNS); pixels are independent (the per-pixel RNG is keyed by the
-// absolute pixel_index, main.cu:93), so every split gives the bits of the single-GPU frame.  Each rank renders its tiles
+// GPU.  The frame's 8x8 tiles (the reference's block shape, main.cu:351-352) are split over the ranks — by default dealt round-robin
+// in runs of RT_PART_RUN consecutive tiles (RT_SPLIT_RUNS), or, opt-in (rt_multi_set_split), cut into horizontal bands of equal
+// predicted cost (rt_split_balanced: every rank runs the same pilot pass over the whole frame and cuts it the same way, no
+// communication; a GPU's rays then meet the same part of the scene, as in the undivided frame); pixels are independent (the per-pixel
+// RNG is keyed by the absolute pixel_index, main.cu:93), so every split gives the bits of the single-GPU frame.  Each rank renders its tiles
 // into a compact tile-major buffer (rt_partition) and ONE exchange brings the buffers to the root: with RCCL a single
 // ncclGroupStart / ncclRecv x (nranks-1) | ncclSend / ncclGroupEnd straight out of the render buffer and straight into the
 // root's staging slots (the root renders into its own slot: no copy anywhere), on the caller's stream; then rt_assemble
@@ -63,6 +63,16 @@ Rccl& rccl() {                                        // bound once per process,
 #define RT_TRY(expr) do { hipError_t e_ = (expr); if (e_ != hipSuccess) return (int)e_; } while (0)
 #define RT_NCCL(expr) do { if ((expr) != 0) return RT_ECOMM; } while (0)
 
+// A frame moves one or two lanes of data to the root: the colours (3 floats or halves per element) and, for an adaptive frame, the
+// sample counts (one int32 per element).  In every order — buffers, gather callbacks, RCCL calls — colours come first.
+enum { kColour = 0, kCounts = 1, kLanes = 2 };
+struct Lane { void* d_local = nullptr; int64_t local_bytes = 0; void* d_parts = nullptr; int64_t parts_bytes = 0; };
+struct LaneFormat { size_t bytes; int dtype; size_t words; };      // bytes per element; RCCL datatype and how many of it an element is
+LaneFormat lane_format(int k, int precision) {
+    if (k == kCounts) return {sizeof(int32_t), kNcclInt32, 1};
+    return precision == RT_PRECISION_FP16 ? LaneFormat{6, kNcclFloat16, 3} : LaneFormat{12, kNcclFloat32, 3};
+}
+
 }  // namespace
 
 
@@ -71,13 +81,9 @@ struct rt_multi {
     NcclComm comm = nullptr;
     rt_gather_fn gather = nullptr; void* user = nullptr;
     rt_render_ctx* ctx = nullptr;
-    // this rank's RNG states (compact, tile-major), its frame part when it is not the root, the root's staging slots
+    // this rank's RNG states (compact, tile-major); per lane its part when it is not the root, the root's staging slots
     void* d_rand = nullptr; int64_t rand_bytes = 0;
-    void* d_local = nullptr; int64_t local_bytes = 0;
-    void* d_parts = nullptr; int64_t parts_bytes = 0;
-    // rt_multi_render_adaptive: this rank's sample counts when it is not the root, the root's staging slots for them (one int32 per pixel)
-    void* d_spp_local = nullptr; int64_t spp_local_bytes = 0;
-    void* d_spp_parts = nullptr; int64_t spp_parts_bytes = 0;
+    Lane lane[kLanes];
     hipEvent_t ev0 = nullptr, ev1 = nullptr; bool timed = false;
     // how the frame is divided (rt_multi_set_split) and the bands of the last balanced split, with what they were computed for
     int split_mode = RT_SPLIT_RUNS;
@@ -87,7 +93,10 @@ struct rt_multi {
 // one buffer with its size, grown on its own demand
 static int grow(void** p, int64_t* have, size_t need) { return group_reserve(*have, (int64_t)need, DevGroup().add(p, need)); }
 static DevGroup multi_group(rt_multi* M) {
-    return DevGroup().add(&M->d_rand, 0).add(&M->d_local, 0).add(&M->d_parts, 0).add(&M->d_spp_local, 0).add(&M->d_spp_parts, 0);
+    DevGroup g;
+    g.add(&M->d_rand, 0);
+    for (Lane& L : M->lane) g.add(&L.d_local, 0).add(&L.d_parts, 0);
+    return g;
 }
 
 static int multi_new(rt_multi** out, int rank, int nranks) {
@@ -170,12 +179,16 @@ int rt_multi_last_split(rt_multi* M, int64_t* starts) {
     return 0;
 }
 
-// this rank's buffers for a part of n_mine pixels, the root's staging slots of `per` pixels each
+// lane k's buffers for a part of n_mine elements of `bytes` bytes: on the root the staging slots of `per` elements each, elsewhere the send buffer
+static int lane_buffers(rt_multi* M, int k, int64_t n_mine, int64_t per, size_t bytes, int root) {
+    Lane& L = M->lane[k];
+    if (M->rank == root) return grow(&L.d_parts, &L.parts_bytes, (size_t)per * bytes * (size_t)M->nranks);
+    return grow(&L.d_local, &L.local_bytes, (size_t)(n_mine > 0 ? n_mine : 1) * bytes);
+}
+// this rank's RNG states and colour lane for a part of n_mine pixels
 static int multi_buffers(rt_multi* M, int64_t n_mine, int64_t per, size_t px, int root) {
-    int rc = grow(&M->d_rand, &M->rand_bytes, (size_t)(n_mine > 0 ? n_mine : 1) * sizeof(rt_rand_state));
-    if (!rc && M->rank == root) rc = grow(&M->d_parts, &M->parts_bytes, (size_t)per * px * (size_t)M->nranks);
-    if (!rc && M->rank != root) rc = grow(&M->d_local, &M->local_bytes, (size_t)(n_mine > 0 ? n_mine : 1) * px);
-    return rc;
+    const int rc = grow(&M->d_rand, &M->rand_bytes, (size_t)(n_mine > 0 ? n_mine : 1) * sizeof(rt_rand_state));
+    return rc ? rc : lane_buffers(M, kColour, n_mine, per, px, root);
 }
 
 // buffers for frames of this size (rt_multi_render grows them on demand; call this once before timing or graph capture).
@@ -184,7 +197,7 @@ static int multi_buffers(rt_multi* M, int64_t n_mine, int64_t per, size_t px, in
 int rt_multi_reserve(rt_multi* M, int max_x, int max_y, int precision, int root) {
     if (!M || max_x <= 0 || max_y <= 0 || root < 0 || root >= M->nranks) return RT_EINVAL;
     if (precision != RT_PRECISION_FP32 && precision != RT_PRECISION_FP16) return RT_EINVAL;
-    const size_t px = precision == RT_PRECISION_FP16 ? 6 : 12;
+    const size_t px = lane_format(kColour, precision).bytes;
     const rt_partition mine = {M->rank, M->nranks, 0, 0}, first = {0, M->nranks, 0, 0};
     int64_t n_mine = rt_part_pixels(max_x, max_y, mine), per = rt_part_pixels(max_x, max_y, first);
     const bool balanced = M->split_mode != RT_SPLIT_RUNS && M->nranks > 1;
@@ -194,21 +207,38 @@ int rt_multi_reserve(rt_multi* M, int max_x, int max_y, int precision, int root)
     return rc;
 }
 
-int rt_multi_render(rt_multi* M, void* fb_full, int max_x, int max_y, int ns, const rt_world* world, const rt_octree* d_octree, int precision, int root, void* stream) {
-    if (!M || !world || max_x <= 0 || max_y <= 0 || ns <= 0 || root < 0 || root >= M->nranks) return RT_EINVAL;
-    if (M->rank == root && !fb_full) return RT_EINVAL;
-    // the buffers, the RCCL datatype and rt_assemble are sized by `precision`, the render kernel by the world's: they must agree
-    // (an fp32 world rendered into binary16-sized buffers would write out of bounds)
-    if (precision != world->precision) return RT_EINVAL;
-    const hipStream_t st = (hipStream_t)stream;
-    const size_t px = precision == RT_PRECISION_FP16 ? 6 : 12;
+// One frame on its way to the root: what the entry point was asked for, and what frame_begin decides.
+struct Frame {
+    int max_x, max_y, precision, root, nlanes;
+    void* out[kLanes];                 // the caller's row-major buffers (fb_full, d_spp_full)
+    rt_partition mine; bool balanced;  // this rank's part; bands of a balanced split or runs
+    int64_t per;                       // elements between the staging slots of two ranks (the largest part)
+    void* local[kLanes];               // where this rank renders lane k
+};
+// elements of rank r's part
+static int64_t frame_elems(const rt_multi* M, const Frame& F, int r) {
+    return rt_part_pixels(F.max_x, F.max_y, rt_partition{r, M->nranks, F.balanced ? M->starts[r] : 0, F.balanced ? M->starts[r + 1] : 0});
+}
+// where this rank renders lane k: a single rank's "part" is the whole frame in the reference's row-major layout (rt_partition,
+// nparts == 1), straight into the caller's buffer; the root renders straight into its slot of the staging buffer, the others into
+// their send buffer
+static void* lane_staging(const rt_multi* M, const Frame& F, int k) {
+    if (M->nranks == 1) return F.out[k];
+    const Lane& L = M->lane[k];
+    return M->rank == F.root ? (void*)((char*)L.d_parts + (size_t)F.per * lane_format(k, F.precision).bytes * (size_t)F.root) : L.d_local;
+}
+
+// the split, this rank's buffers and staging, its RNG states initialised: everything before the entry point's render call
+static int frame_begin(rt_multi* M, Frame& F, const rt_world* world, const rt_octree* d_octree, void* stream) {
+    const int max_x = F.max_x, max_y = F.max_y;
+    const size_t px = lane_format(kColour, F.precision).bytes;
     const int64_t tiles = (int64_t)((max_x + 7) / 8) * ((max_y + 7) / 8);
-    const bool balanced = M->split_mode != RT_SPLIT_RUNS && M->nranks > 1 && tiles >= M->nranks;
+    F.balanced = M->split_mode != RT_SPLIT_RUNS && M->nranks > 1 && tiles >= M->nranks;
+    F.mine = rt_partition{M->rank, M->nranks, 0, 0};
+    F.per = 0;
     int rc = 0;
-    rt_partition mine = {M->rank, M->nranks, 0, 0};
-    int64_t per = 0;
-    RT_TRY(hipEventRecord(M->ev0, st));                                   // (this rank's share of the frame starts with the split)
-    if (balanced) {
+    RT_TRY(hipEventRecord(M->ev0, (hipStream_t)stream));                  // (this rank's share of the frame starts with the split)
+    if (F.balanced) {
         // every rank cuts the frame the same way: the same pilot pass, the same integer arithmetic (rt_split_balanced)
         const uint64_t key[4] = {world->serial, d_octree ? d_octree->serial : 0, ((uint64_t)(uint32_t)max_x << 32) | (uint32_t)max_y,
                                  ((uint64_t)(uint32_t)M->nranks << 32) | (uint32_t)(d_octree ? d_octree->traversal : 0)};
@@ -217,52 +247,86 @@ int rt_multi_render(rt_multi* M, void* fb_full, int max_x, int max_y, int ns, co
             if ((rc = rt_split_balanced(M->ctx, world, d_octree, max_x, max_y, M->nranks, M->starts, nullptr, nullptr, nullptr, stream))) return rc;
             memcpy(M->split_key, key, sizeof(key)); M->have_split = true;
         }
-        mine.tile_begin = M->starts[M->rank]; mine.tile_end = M->starts[M->rank + 1];
-        for (int r = 0; r < M->nranks; ++r) per = std::max<int64_t>(per, (M->starts[r + 1] - M->starts[r]) * 64);
-        if ((rc = multi_buffers(M, (mine.tile_end - mine.tile_begin) * 64, per, px, root))) return rc;
+        F.mine.tile_begin = M->starts[M->rank]; F.mine.tile_end = M->starts[M->rank + 1];
+        for (int r = 0; r < M->nranks; ++r) F.per = std::max<int64_t>(F.per, (M->starts[r + 1] - M->starts[r]) * 64);
+        if ((rc = multi_buffers(M, (F.mine.tile_end - F.mine.tile_begin) * 64, F.per, px, F.root))) return rc;
     } else {
         M->have_split = false;
-        if ((rc = rt_multi_reserve(M, max_x, max_y, precision, root))) return rc;
-        per = rt_part_pixels(max_x, max_y, rt_partition{0, M->nranks, 0, 0});
+        if ((rc = rt_multi_reserve(M, max_x, max_y, F.precision, F.root))) return rc;
+        F.per = rt_part_pixels(max_x, max_y, rt_partition{0, M->nranks, 0, 0});
     }
-    const size_t stride = (size_t)per * px;
-    // the root renders straight into its slot of the staging buffer, the others into their send buffer; a single rank's
-    // "part" is the whole frame in the reference's row-major layout (rt_partition, nparts == 1): straight into fb_full
-    void* local = M->nranks == 1 ? fb_full : M->rank == root ? (void*)((char*)M->d_parts + stride * (size_t)root) : M->d_local;
-    if ((rc = rt_render_init(max_x, max_y, (rt_rand_state*)M->d_rand, mine, stream))) return rc;
-    if ((rc = rt_render_on(M->ctx, local, max_x, max_y, ns, world, (rt_rand_state*)M->d_rand, d_octree, mine, stream))) return rc;
-    RT_TRY(hipEventRecord(M->ev1, st));
-    M->timed = true;
-    if (M->nranks > 1) {
-        const size_t mine_bytes = (size_t)rt_part_pixels(max_x, max_y, mine) * px;
-        if (M->gather) {
-            if ((rc = M->gather(M->user, local, mine_bytes, M->rank == root ? M->d_parts : nullptr, stride, root, stream))) return rc > 0 ? RT_ECOMM : rc;
-        } else {
-            Rccl& R = rccl();
-            const int dtype = precision == RT_PRECISION_FP16 ? kNcclFloat16 : kNcclFloat32;
-            RT_NCCL(R.GroupStart());                              // the single framebuffer exchange
-            if (M->rank == root) {
-                for (int r = 0; r < M->nranks; ++r) {
-                    if (r == root) continue;
-                    const rt_partition pr = {r, M->nranks, balanced ? M->starts[r] : 0, balanced ? M->starts[r + 1] : 0};
-                    const size_t count = (size_t)rt_part_pixels(max_x, max_y, pr) * 3;
-                    if (count && R.Recv((char*)M->d_parts + stride * (size_t)r, count, dtype, r, M->comm, st) != 0) { (void)R.GroupEnd(); return RT_ECOMM; }
-                }
-            } else if (mine_bytes) {
-                if (R.Send(local, mine_bytes / (px / 3), dtype, root, M->comm, st) != 0) { (void)R.GroupEnd(); return RT_ECOMM; }
+    // (the further lanes have buffers only where there is an exchange)
+    for (int k = kColour + 1; k < F.nlanes && M->nranks > 1; ++k)
+        if ((rc = lane_buffers(M, k, rt_part_pixels(max_x, max_y, F.mine), F.per, lane_format(k, F.precision).bytes, F.root))) return rc;
+    for (int k = 0; k < F.nlanes; ++k) F.local[k] = lane_staging(M, F, k);
+    return rt_render_init(max_x, max_y, (rt_rand_state*)M->d_rand, F.mine, stream);
+}
+
+// What goes to the root, in which order.  A custom gather: one call per lane, by every rank, one with nothing to send included.  RCCL:
+// the single exchange of the frame, one group — the root receives from its peers in ascending rank, per peer lane by lane, straight
+// into the staging slots; a peer sends lane by lane straight out of its render buffers; a rank without elements is left out.
+static int frame_exchange(rt_multi* M, const Frame& F, hipStream_t st) {
+    const bool root = M->rank == F.root;
+    const size_t n_mine = (size_t)frame_elems(M, F, M->rank);
+    if (M->gather) {
+        for (int k = 0; k < F.nlanes; ++k) {
+            const size_t b = lane_format(k, F.precision).bytes;
+            const int rc = M->gather(M->user, F.local[k], n_mine * b, root ? M->lane[k].d_parts : nullptr, (size_t)F.per * b, F.root, (void*)st);
+            if (rc) return rc > 0 ? RT_ECOMM : rc;
+        }
+        return 0;
+    }
+    Rccl& R = rccl();
+    RT_NCCL(R.GroupStart());
+    int bad = 0;
+    if (root) {
+        for (int r = 0; r < M->nranks && !bad; ++r) {
+            const size_t n = r == F.root ? 0 : (size_t)frame_elems(M, F, r);
+            for (int k = 0; k < F.nlanes && n && !bad; ++k) {
+                const LaneFormat f = lane_format(k, F.precision);
+                bad = R.Recv((char*)M->lane[k].d_parts + (size_t)F.per * f.bytes * (size_t)r, n * f.words, f.dtype, r, M->comm, st);
             }
-            RT_NCCL(R.GroupEnd());
+        }
+    } else if (n_mine) {
+        for (int k = 0; k < F.nlanes && !bad; ++k) {
+            const LaneFormat f = lane_format(k, F.precision);
+            bad = R.Send(F.local[k], n_mine * f.words, f.dtype, F.root, M->comm, st);
         }
     }
-    if (M->rank == root && M->nranks > 1)
-        rc = balanced ? rt_assemble_split(fb_full, M->d_parts, max_x, max_y, M->nranks, M->starts, per, precision, stream)
-                      : rt_assemble(fb_full, M->d_parts, max_x, max_y, M->nranks, precision, stream);
+    if (bad) { (void)R.GroupEnd(); return RT_ECOMM; }
+    RT_NCCL(R.GroupEnd());
+    return 0;
+}
+
+// everything after the entry point's render call: the exchange, and on the root the row-major frame (and count map) from the staging slots
+static int frame_end(rt_multi* M, const Frame& F, void* stream) {
+    const hipStream_t st = (hipStream_t)stream;
+    RT_TRY(hipEventRecord(M->ev1, st));
+    M->timed = true;
+    if (M->nranks == 1) return 0;
+    int rc = frame_exchange(M, F, st);
+    if (rc || M->rank != F.root) return rc;
+    rc = F.balanced ? rt_assemble_split(F.out[kColour], M->lane[kColour].d_parts, F.max_x, F.max_y, M->nranks, M->starts, F.per, F.precision, stream)
+                    : rt_assemble(F.out[kColour], M->lane[kColour].d_parts, F.max_x, F.max_y, M->nranks, F.precision, stream);
+    if (!rc && F.nlanes > kCounts && F.out[kCounts])
+        rc = (int)rt::launch_gather(rt::kGatherI32x1, F.out[kCounts], M->lane[kCounts].d_parts, F.max_x, F.max_y, M->nranks, nullptr, 0, st);
     return rc;
 }
 
+int rt_multi_render(rt_multi* M, void* fb_full, int max_x, int max_y, int ns, const rt_world* world, const rt_octree* d_octree, int precision, int root, void* stream) {
+    if (!M || !world || max_x <= 0 || max_y <= 0 || ns <= 0 || root < 0 || root >= M->nranks) return RT_EINVAL;
+    if (M->rank == root && !fb_full) return RT_EINVAL;
+    // the buffers, the RCCL datatype and rt_assemble are sized by `precision`, the render kernel by the world's: they must agree
+    // (an fp32 world rendered into binary16-sized buffers would write out of bounds)
+    if (precision != world->precision) return RT_EINVAL;
+    Frame F = {max_x, max_y, precision, root, 1, {fb_full, nullptr}};
+    int rc = frame_begin(M, F, world, d_octree, stream);
+    if (!rc) rc = rt_render_on(M->ctx, F.local[kColour], max_x, max_y, ns, world, (rt_rand_state*)M->d_rand, d_octree, F.mine, stream);
+    return rc ? rc : frame_end(M, F, stream);
+}
+
 // rt_multi_render with adaptive sampling, runs only: every rank runs render_init + rt_render_adaptive_part_on on its runs, then the
-// colour parts and the sample-count parts go to the root — RCCL: both in one group (4-byte words for the counts); a custom gather:
-// two calls, colours first — where rt_assemble and its one-channel twin write the row-major frame and map.
+// colour parts and the sample-count parts go to the root as the frame's two lanes.
 int rt_multi_render_adaptive(rt_multi* M, void* fb_full, int max_x, int max_y, const rt_adaptive* params, const rt_world* world, const rt_octree* d_octree,
                              int precision, int root, int32_t* d_spp_full, void* stream) {
     if (!M || !world || max_x <= 0 || max_y <= 0 || root < 0 || root >= M->nranks || !adaptive_params_ok(params)) return RT_EINVAL;
@@ -271,50 +335,10 @@ int rt_multi_render_adaptive(rt_multi* M, void* fb_full, int max_x, int max_y, c
     if (world->precision == RT_PRECISION_FP16 || world->arith == RT_ARITH_CONTRACT) return RT_ENOTSUP;
     // balanced bands are cut on a uniform-cost pilot pass: they say nothing about where adaptive sampling spends its samples
     if (M->split_mode != RT_SPLIT_RUNS) return RT_ENOTSUP;
-    const hipStream_t st = (hipStream_t)stream;
-    const size_t px = 12, spx = sizeof(int32_t);
-    int rc = 0;
-    const rt_partition mine = {M->rank, M->nranks, 0, 0};
-    RT_TRY(hipEventRecord(M->ev0, st));
-    M->have_split = false;
-    if ((rc = rt_multi_reserve(M, max_x, max_y, precision, root))) return rc;
-    const int64_t per = rt_part_pixels(max_x, max_y, rt_partition{0, M->nranks, 0, 0});
-    const int64_t n_mine = rt_part_pixels(max_x, max_y, mine);
-    if (M->nranks > 1 && M->rank == root && (rc = grow(&M->d_spp_parts, &M->spp_parts_bytes, (size_t)per * spx * (size_t)M->nranks))) return rc;
-    if (M->nranks > 1 && M->rank != root && (rc = grow(&M->d_spp_local, &M->spp_local_bytes, (size_t)(n_mine > 0 ? n_mine : 1) * spx))) return rc;
-    const size_t stride = (size_t)per * px, spp_stride = (size_t)per * spx;
-    // as rt_multi_render: the root renders into its staging slots, a single rank straight into fb_full / d_spp_full
-    void* local = M->nranks == 1 ? fb_full : M->rank == root ? (void*)((char*)M->d_parts + stride * (size_t)root) : M->d_local;
-    int32_t* spp = M->nranks == 1 ? d_spp_full : M->rank == root ? (int32_t*)((char*)M->d_spp_parts + spp_stride * (size_t)root) : (int32_t*)M->d_spp_local;
-    if ((rc = rt_render_init(max_x, max_y, (rt_rand_state*)M->d_rand, mine, stream))) return rc;
-    if ((rc = rt_render_adaptive_part_on(M->ctx, local, max_x, max_y, params, world, (rt_rand_state*)M->d_rand, d_octree, spp, mine, stream))) return rc;
-    RT_TRY(hipEventRecord(M->ev1, st));
-    M->timed = true;
-    if (M->nranks == 1) return 0;
-    const size_t mine_bytes = (size_t)n_mine * px, mine_spp_bytes = (size_t)n_mine * spx;
-    if (M->gather) {
-        if ((rc = M->gather(M->user, local, mine_bytes, M->rank == root ? M->d_parts : nullptr, stride, root, stream))) return rc > 0 ? RT_ECOMM : rc;
-        if ((rc = M->gather(M->user, spp, mine_spp_bytes, M->rank == root ? M->d_spp_parts : nullptr, spp_stride, root, stream))) return rc > 0 ? RT_ECOMM : rc;
-    } else {
-        Rccl& R = rccl();
-        RT_NCCL(R.GroupStart());                                  // both exchanges in one group
-        if (M->rank == root) {
-            for (int r = 0; r < M->nranks; ++r) {
-                if (r == root) continue;
-                const size_t count = (size_t)rt_part_pixels(max_x, max_y, rt_partition{r, M->nranks, 0, 0});
-                if (count && (R.Recv((char*)M->d_parts + stride * (size_t)r, count * 3, kNcclFloat32, r, M->comm, st) != 0 ||
-                              R.Recv((char*)M->d_spp_parts + spp_stride * (size_t)r, count, kNcclInt32, r, M->comm, st) != 0)) { (void)R.GroupEnd(); return RT_ECOMM; }
-            }
-        } else if (n_mine) {
-            if (R.Send(local, (size_t)n_mine * 3, kNcclFloat32, root, M->comm, st) != 0 ||
-                R.Send(spp, (size_t)n_mine, kNcclInt32, root, M->comm, st) != 0) { (void)R.GroupEnd(); return RT_ECOMM; }
-        }
-        RT_NCCL(R.GroupEnd());
-    }
-    if (M->rank != root) return 0;
-    if ((rc = rt_assemble(fb_full, M->d_parts, max_x, max_y, M->nranks, precision, stream))) return rc;
-    if (d_spp_full) RT_TRY(rt::launch_assemble_spp(d_spp_full, (const int32_t*)M->d_spp_parts, max_x, max_y, M->nranks, st));
-    return 0;
+    Frame F = {max_x, max_y, precision, root, 2, {fb_full, d_spp_full}};
+    int rc = frame_begin(M, F, world, d_octree, stream);
+    if (!rc) rc = rt_render_adaptive_part_on(M->ctx, F.local[kColour], max_x, max_y, params, world, (rt_rand_state*)M->d_rand, d_octree, (int32_t*)F.local[kCounts], F.mine, stream);
+    return rc ? rc : frame_end(M, F, stream);
 }
 
 // device time of this rank's own share of the last rt_multi_render (render_init + render, before the exchange), and of

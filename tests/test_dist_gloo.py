@@ -53,7 +53,7 @@ def local_pixel_ids(nx, ny, part, nparts, padded):
 
 
 def assemble_numpy(parts, nx, ny, nparts, per):
-    """numpy restatement of k_assemble (tests only)"""
+    """numpy restatement of k_gather for parts in runs (csrc/rt_assemble.hip; tests only)"""
     tx, ty = (nx + 7) // 8, (ny + 7) // 8
     full = np.full(nx * ny, -7, np.int64)
     for t in range(tx * ty):

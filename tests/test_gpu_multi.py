@@ -2,14 +2,13 @@
 one rank, RCCL bound at run time moving device memory (self send/recv), N ranks as N fresh child processes on GPU 0 through
 the custom-gather form (RCCL refuses two ranks on one device), and render contexts on concurrent streams."""
 import os
-import socket
 import subprocess
 import sys
 
-import numpy as np
 import pytest
 
 from gpu_frames import render_frame
+from rank_runner import run_ranks
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -39,36 +38,20 @@ def test_multi_render_one_rank_over_rccl(rt, cuda):
 
 
 @pytest.mark.parametrize("world,nx,ny,ns,n,spl,fp16,split", [
-    (2, 400, 232, 16, 10000, 32, 0, 1),      # octree, long-chain classification on; bands of equal predicted cost (the default split)
+    (2, 400, 232, 16, 10000, 32, 0, 1),      # octree, long-chain classification on; bands of equal predicted cost (RT_SPLIT_BALANCED, opt-in)
     (3, 203, 117, 4, 500, 0, 0, 1),          # ragged frame, three ranks, hitable_list path
     (2, 200, 120, 4, 500, 30, 1, 1),         # USE_FP16
-    (2, 400, 232, 16, 10000, 32, 0, 0),      # the same three through runs of RT_PART_RUN tiles dealt round-robin (RT_SPLIT_RUNS)
+    (2, 400, 232, 16, 10000, 32, 0, 0),      # the same three through runs of RT_PART_RUN tiles dealt round-robin (RT_SPLIT_RUNS, the default split)
     (3, 203, 117, 4, 500, 0, 0, 0),
     (2, 200, 120, 4, 500, 30, 1, 0),
     (3, 400, 232, 16, 10000, 32, 0, 2),      # the split kept from the first frame to the second (RT_SPLIT_BALANCED_CACHED)
+    (3, 64, 40, 4, 500, 30, 0, 0),           # 40 tiles, less than one run of RT_PART_RUN: rank 0 holds every tile, ranks 1 and 2 none —
+    (3, 64, 40, 4, 500, 30, 1, 0),           # they still join the exchange, with nothing to send; both precisions
 ])
 def test_multi_render_child_processes_on_one_gpu(rt, cuda, world, nx, ny, ns, n, spl, fp16, split):
     """N fresh child processes, one rank each, all on GPU 0: the real rt_multi_render (split, render, staging slots,
     rt_assemble / rt_assemble_split) with a gloo exchange; rank 0 checks the assembled frame against a single-process render bit for bit."""
-    s = socket.socket()
-    s.bind(("127.0.0.1", 0))
-    port = s.getsockname()[1]
-    s.close()
-    script = os.path.join(ROOT, "tests", "multi_worker.py")
-    args = [str(v) for v in (world, port, nx, ny, ns, n, spl, fp16)]
-    procs = [subprocess.Popen([sys.executable, script, str(r)] + args + [str(split)], stdout=subprocess.PIPE, stderr=subprocess.PIPE) for r in range(world)]
-    outs = []
-    try:
-        for p in procs:
-            o, e = p.communicate(timeout=300)
-            outs.append((p.returncode, o.decode(), e.decode()))
-    finally:
-        for p in procs:
-            if p.poll() is None:
-                p.kill()
-    for rc, o, e in outs:
-        assert rc == 0, (rc, o[-2000:], e[-2000:])
-    assert "EQUALS" in outs[0][1]
+    assert "EQUALS" in run_ranks("plain", world, nx, ny, ns, n, spl, fp16, split)
 
 
 def test_multi_render_rejects_a_precision_that_is_not_the_worlds(rt, cuda):

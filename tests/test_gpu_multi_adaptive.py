@@ -1,49 +1,26 @@
 """rt_multi_render_adaptive on the one GPU of the test box (-m gpu): N ranks as N fresh child processes on GPU 0 through the
-custom-gather form (tests/multi_adaptive_worker.py; RCCL refuses two ranks on one device), one rank over RCCL, and the refusals.
+custom-gather form (tests/multi_worker.py adaptive; RCCL refuses two ranks on one device), one rank over RCCL, and the refusals.
 Every comparison is bit equality with the single-process rt_render_adaptive."""
 import ctypes as C
-import os
 import re
-import socket
-import subprocess
-import sys
 
 import pytest
 
+from rank_runner import run_ranks
+
 pytestmark = pytest.mark.gpu
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-
-
-def free_port():
-    s = socket.socket()
-    s.bind(("127.0.0.1", 0))
-    port = s.getsockname()[1]
-    s.close()
-    return port
 
 
 @pytest.mark.parametrize("world,nx,ny,n,spl,lo,hi,step,rel", [
     (2, 203, 117, 10000, 32, 4, 32, 4, 0.1),     # ragged frame: 26 x 15 tiles, 7 runs — part 0 holds 4, part 1 holds 3 (the last of 6 tiles)
     (3, 203, 77, 500, 0, 16, 40, 8, 0.1),        # three ranks, hitable_list path, round 0 with the long-chain pass
     (8, 640, 200, 500, 30, 4, 24, 4, 0.1),       # 2000 tiles = 31.25 runs: 3 rounds of 8 runs and an incomplete fourth; 8 GPU processes
+    (3, 64, 40, 500, 30, 4, 12, 4, 0.1),         # 40 tiles, less than one run: ranks 1 and 2 hold nothing and still make both gather calls
 ])
 def test_multi_adaptive_child_processes_on_one_gpu(rt, cuda, world, nx, ny, n, spl, lo, hi, step, rel):
-    script = os.path.join(ROOT, "tests", "multi_adaptive_worker.py")
-    args = [str(v) for v in (world, free_port(), nx, ny, n, spl, lo, hi, step, rel, 0.02)]
-    procs = [subprocess.Popen([sys.executable, script, str(r)] + args, stdout=subprocess.PIPE, stderr=subprocess.PIPE) for r in range(world)]
-    outs = []
-    try:
-        for p in procs:
-            o, e = p.communicate(timeout=300)
-            outs.append((p.returncode, o.decode(), e.decode()))
-    finally:
-        for p in procs:
-            if p.poll() is None:
-                p.kill()
-    for rc, o, e in outs:
-        assert rc == 0, (rc, o[-2000:], e[-2000:])
-    m = re.search(r"frame and counts EQUAL the single-process frame \(counts \[(.*)\]\)", outs[0][1])
-    assert m, outs[0][1]
+    out = run_ranks("adaptive", world, nx, ny, n, spl, lo, hi, step, rel, 0.02)
+    m = re.search(r"frame and counts EQUAL the single-process frame \(counts \[(.*)\]\)", out)
+    assert m, out
     assert len(m.group(1).split(",")) >= 2, m.group(1)          # a mixed frame: the count map says something
 
 
