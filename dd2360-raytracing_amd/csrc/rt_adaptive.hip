@@ -28,7 +28,7 @@ __device__ __forceinline__ void adapt_append(bool active, unsigned int pid, unsi
         unsigned int base = 0;
         if ((threadIdx.x & 63) == 0) base = atomicAdd(count_out, (unsigned int)__popcll(mask));
         base = __shfl(base, 0);
-        const unsigned int rank = __builtin_amdgcn_mbcnt_hi((unsigned)(mask >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)mask, 0u));
+        const unsigned int rank = rank_below(mask);
         if (active) list_out[base + rank] = pid;
     }
 }

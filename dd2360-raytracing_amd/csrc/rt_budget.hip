@@ -57,9 +57,6 @@ __device__ __forceinline__ void budget_hist_add(bool valid, unsigned int digit, 
     }
     if (valid) atomicAdd(&sh_hist[digit], 1u);
 }
-__device__ __forceinline__ unsigned int budget_lane_rank(unsigned long long m) {          // set bits of m below this lane
-    return __builtin_amdgcn_mbcnt_hi((unsigned)(m >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)m, 0u));
-}
 // for thread t of the block's 256: the sum of v over the threads >= t (sh: 4 words)
 __device__ __forceinline__ unsigned int budget_suffix_sum(unsigned int v, unsigned int* sh) {
     const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
@@ -235,7 +232,7 @@ __global__ __launch_bounds__(256) void k_budget_compact(const unsigned int* __re
             const unsigned long long m = __ballot(tie);
             if ((threadIdx.x & 63) == 0) sh[w] = (unsigned int)__popcll(m);
             __syncthreads();
-            unsigned int rank = run + budget_lane_rank(m);
+            unsigned int rank = run + rank_below(m);
             for (int ww = 0; ww < w; ++ww) rank += sh[ww];
             run += (sh[0] + sh[1]) + (sh[2] + sh[3]);
             pick = pick || (tie && rank < need);
@@ -243,7 +240,7 @@ __global__ __launch_bounds__(256) void k_budget_compact(const unsigned int* __re
         const unsigned long long mp = __ballot(pick);
         if ((threadIdx.x & 63) == 0) sh[4 + w] = (unsigned int)__popcll(mp);
         __syncthreads();
-        unsigned int pos = at + budget_lane_rank(mp);
+        unsigned int pos = at + rank_below(mp);
         for (int ww = 0; ww < w; ++ww) pos += sh[4 + ww];
         at += (sh[4] + sh[5]) + (sh[6] + sh[7]);
         if (pick && pos < K) list[pos] = (unsigned int)t;     // (the set never exceeds K: the list's capacity is not left to that proof)

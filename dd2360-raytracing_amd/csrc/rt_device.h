@@ -1,5 +1,5 @@
 // rt_device.h — device-side data layout shared by the kernels (rt_kernels.hip and its neighbours) and the uploader (rt_api.hip),
-// and the few device helpers that more than one kernel file uses (the partition's tile mapping, adapt_in_frame, wave_excl_scan).
+// and the few device helpers that more than one kernel file uses (the partition's tile mapping, adapt_in_frame, rank_below, wave_excl_scan).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -182,6 +182,11 @@ struct DevTree {
     int32_t h16_np[3];
     DevAccel acc;
 };
+
+// how many of a ballot's lanes lie below this one: a voting lane's rank among the voters, the slot it takes when they append to a list
+static __device__ __forceinline__ unsigned rank_below(unsigned long long m) {
+    return __builtin_amdgcn_mbcnt_hi((unsigned)(m >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)m, 0u));
+}
 
 // exclusive prefix sum over the 64 lanes of a wave (the grid walk's pool, the tail sort's bins): row_shr 1/2/4/8 (a row of 16), then
 // row_bcast 15 and 31 — six DPP adds, no LDS

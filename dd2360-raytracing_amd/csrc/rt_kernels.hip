@@ -12,7 +12,9 @@
 //     ended starts its next sample at once instead of idling until the slowest path of the wave finishes;
 //   * octree on: candidates come from an exact culling grid (rt_accel.h), the reference's traversal is the fallback; a wave's
 //     sphere tests are pooled and dealt out evenly over its 64 lanes — walk_pool on sparse grids (two columns per ray and round),
-//     walk_pool_dense on dense ones (one column, four entries per lane and pass, the owner's best hit re-read every pass);
+//     walk_pool_dense on dense ones (one column, four entries per lane and pass, the owner's best hit re-read every pass); the
+//     steps the two share (a column's entry range, the owner's ray record, a round's preamble and pick-up, the pre-filter's margin)
+//     and the pieces of sphere::hit that several places need (sphere_bc, sphere_offer_t, hit_eligible) are functions of their own;
 //     waves holding long pixel chains stop refilling ("thin");
 //   * no virtual calls, no device heap, no recursion: materials are a tag + 4 floats, the octree is a pre-order
 //     node array with skip links staged in LDS, bucket contents are pre-gathered (centre, r^2) float4 streams;
@@ -91,13 +93,16 @@ struct RayF { V3 o, d; };
 RT_DEV float pow5(float x) { const double v = (double)x; const double v2 = v * v; return (float)((v2 * v2) * v); }
 
 // ---------------------------------------------------------------------------------------------------- sphere::hit
+// sphere.h:18-21 for a sphere as (centre, r^2): b = oc.d and c = oc.oc - r^2
+RT_DEV float2 sphere_bc(const RayF& r, const float4 s) {
+    const float ocx = r.o.x - s.x, ocy = r.o.y - s.y, ocz = r.o.z - s.z;
+    return make_float2(ocx * r.d.x + ocy * r.d.y + ocz * r.d.z, (ocx * ocx + ocy * ocy + ocz * ocz) - s.w);
+}
 // One candidate test against (cx,cy,cz,r2).  closest is closest_so_far; on acceptance it is lowered and `best`
 // records which entry won.  Operation order of sphere.h:18-41 with a = d.d hoisted by the caller.
 RT_DEV void sphere_test(const RayF& r, float a, float cx, float cy, float cz, float r2, int id, float& closest, int& best) {
-    const float ocx = r.o.x - cx, ocy = r.o.y - cy, ocz = r.o.z - cz;
-    const float b = ocx * r.d.x + ocy * r.d.y + ocz * r.d.z;
-    const float c = (ocx * ocx + ocy * ocy + ocz * ocz) - r2;
-    const float disc = b * b - a * c;
+    const float2 bc = sphere_bc(r, make_float4(cx, cy, cz, r2));
+    const float b = bc.x, disc = b * b - a * bc.y;
     if (disc > 0.0f) {
         const float sq = sqrtf(disc);
         float t = (-b - sq) / a;
@@ -174,22 +179,19 @@ RT_DEV int bcast(int v, int l) { return __builtin_amdgcn_readlane(v, l); }
 // sphere::hit reduced to "which t would this sphere offer": the near root if it is > t_min, else the far root if that
 // is > t_min, else none (+inf).  The reference accepts exactly when that value is < closest_so_far (the far root is
 // never below the near root, so a rejected near root in range cannot be followed by an accepted far root).
-RT_DEV float sphere_candidate(const RayF& r, float a, const float4 s) {
-    const float ocx = r.o.x - s.x, ocy = r.o.y - s.y, ocz = r.o.z - s.z;
-    const float b = ocx * r.d.x + ocy * r.d.y + ocz * r.d.z;
-    const float c = (ocx * ocx + ocy * ocy + ocz * ocz) - s.w;
-    const float disc = b * b - a * c;
+// sphere_offer_t forms the roots (sphere.h:24-43; sq = sqrtf(disc), disc > 0) for whoever holds b and disc already: the queued
+// candidates of the pooled walks, the large spheres; sphere_candidate is the whole test.
+RT_DEV float sphere_offer_t(float a, float b, float sq) {
     float cand = __builtin_inff();
-    if (disc > 0.0f) {
-        const float sq = sqrtf(disc);
-        const float t1 = (-b - sq) / a;
-        if (t1 > 0.001f) cand = t1;
-        else {
-            const float t2 = (-b + sq) / a;
-            if (t2 > 0.001f) cand = t2;
-        }
-    }
+    const float t1 = (-b - sq) / a;
+    if (t1 > 0.001f) cand = t1;
+    else { const float t2 = (-b + sq) / a; if (t2 > 0.001f) cand = t2; }
     return cand;
+}
+RT_DEV float sphere_candidate(const RayF& r, float a, const float4 s) {
+    const float2 bc = sphere_bc(r, s);
+    const float b = bc.x, disc = b * b - a * bc.y;
+    return disc > 0.0f ? sphere_offer_t(a, b, sqrtf(disc)) : __builtin_inff();
 }
 
 // hitable_list::hit over the hittable spheres in list order.
@@ -367,25 +369,32 @@ RT_DEV bool in_brick(const RayF& r, float cand, const float4 blo, const float4 b
     return ux > blo.x && ux < bhi.x && uy > blo.y && uy < bhi.y && uz > blo.z && uz < bhi.z;
 }
 
-// blo/bhi: the candidate's DevAccel::brick pair (brick bounds, world-list index, single storing node or -1)
+// blo/bhi, here and below: the candidate's DevAccel::brick pair (brick bounds, world-list index, single storing node or -1)
+// The eligibility ladder of a hit at `cand`: inside the brick; else — hit point near an outer face of the brick, or no brick (a bucket was
+// full) — the reference's own slab test of the single storing node, or of the nodes `eligible` goes through.  COUNT: `offer` counts the
+// single node's test in the diagnostic builds (ST_ELIG, ST_ELIG_NODES, WP_OFFER_RAYBOX), the pooled walks' candidates never did.
+template <bool COUNT>
+RT_DEV bool hit_eligible(const float4* s_nodes, const RayF& r, float cand, const float4 blo, const float4 bhi STAT_ARG) {
+    bool ok = in_brick(r, cand, blo, bhi);
+    if (!ok) {
+        const int node1 = __float_as_int(bhi.w);
+        if (node1 >= 0) {
+            if (COUNT) { STAT(st, ST_ELIG, 1); STAT(st, ST_ELIG_NODES, 1); WPASS(WP_OFFER_RAYBOX); }
+            const float4 n0 = s_nodes[node1 * 3 + 0];
+            const float4 n1 = s_nodes[node1 * 3 + 1];
+            ok = ray_box(r, n0.x, n0.y, n0.z, n0.w, n1.x, n1.y);
+        } else {
+            ok = eligible(s_nodes, r, cand, __float_as_int(blo.w) STAT_PASS);
+        }
+    }
+    return ok;
+}
+// a large sphere's offer to its own ray
 RT_DEV void offer(const DevTree& T, const float4* s_nodes, const RayF& r, float cand, const float4 blo, const float4 bhi, float& best_t, int& best, bool& tie STAT_ARG) {
     STAT(st, ST_OFFERS, 1);
     const int id = __float_as_int(blo.w);
     if (cand < best_t) {
-        bool ok = in_brick(r, cand, blo, bhi);
-        if (!ok) {
-            // hit point near an outer face of the brick, or no brick (a bucket was full): the reference's own slab test
-            const int node1 = __float_as_int(bhi.w);
-            if (node1 >= 0) {
-                STAT(st, ST_ELIG, 1); STAT(st, ST_ELIG_NODES, 1); WPASS(WP_OFFER_RAYBOX);
-                const float4 n0 = s_nodes[node1 * 3 + 0];
-                const float4 n1 = s_nodes[node1 * 3 + 1];
-                ok = ray_box(r, n0.x, n0.y, n0.z, n0.w, n1.x, n1.y);
-            } else {
-                ok = eligible(s_nodes, r, cand, id STAT_PASS);
-            }
-        }
-        if (ok) { best_t = cand; best = id; }
+        if (hit_eligible<true>(s_nodes, r, cand, blo, bhi STAT_PASS)) { best_t = cand; best = id; }
     } else if (cand == best_t && id != best && best > 0) {
         tie = true;                      // two different tree spheres at the same float t: visit order decides -> reference scan
     }
@@ -480,7 +489,58 @@ static_assert(sizeof(unsigned) * kWalkPool >= sizeof(uint4) * 2 * kThinWalkers &
 struct PoolSpan { unsigned cur, end, seg_end, base, sg; int owner; RayF q; float a, abt, atm; };      // a lane's walk through one span of the pool
 RT_DEV void walk_sync() { __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront"); __builtin_amdgcn_wave_barrier(); }
 
-// one queued candidate: sphere.h:24-43's offer, eligibility as in `offer`, merged into the owner's key
+// The steps that the two pooled walks share, each written once.  Where a walk still spells one of them out (the thin round's column
+// range; walk_pool_dense's owner record, span search and discriminant; the candidate queue of both), every form of the helper that
+// was tried changed kernel text there, and text is what these kernels are held to (HISTORY.md, round 26).
+// A column's bins (rt_accel.h): Gf fine bins of width 1 / F cells, entries keyed by their centre — the query grows by q_c.
+struct ColBins { const int32_t* __restrict__ cs; int Gf; float fF, fGf, fGfm, q_c; };
+// The entry range [e0, e1) of column i of a walk (om_c, on_c, slope, coff: Walk); left as it is where the line misses the column's bins.
+RT_DEV void column_entries(const ColBins& B, float om_c, float on_c, float slope, int coff, int i, int& e0, int& e1) {
+    const float u0 = on_c + ((float)i - om_c) * slope, u1 = u0 + slope;                          // the line at the column's two edges
+    const float lo = (fminf(u0, u1) - B.q_c) * B.fF, hi = (fmaxf(u0, u1) + B.q_c) * B.fF;      // in fine bins (F is a power of two)
+    if (hi >= 0.0f && lo < B.fGf) {
+        const int k0 = (int)fmaxf(lo, 0.0f), k1 = (int)fminf(hi, B.fGfm);
+        const unsigned cbase = (unsigned)(coff + i * B.Gf);
+        e0 = B.cs[cbase + (unsigned)k0]; e1 = B.cs[cbase + (unsigned)k1 + 1u];
+    }
+}
+
+// The pooled walks' square-root-free pre-filter (App. A.5), for an entry with disc > 0.  b: the entry's; abt = a * best_t and atm = a * t_min, each
+// with its margin towards "keep" (the owner's L.ray record, f_abt; a * (0.001f * 0.9999f - 1e-6f)).  Lm > 0 with Lm^2 > disc: the near root lies
+// beyond the best hit; M > 0 with M^2 > disc: the far root lies behind t_min.  The two cannot both be positive (Lm > 0 needs b + kb < -abt,
+// M > 0 needs b - kb > -atm, and abt > atm), so the caller makes one test of the larger: the entry is dropped if P > 0 && P * P > disc * 1.0003f.
+// (the margins are fused here — one rounding less than the analysis allows for).  The value, not the verdict, is returned: a helper that
+// returns the comparison moves the caller's loads behind its branch (HISTORY.md, round 26).
+RT_DEV float entry_margin(float b, float abt, float atm) {
+    const float ab = fabsf(b);
+    const float Lm = __builtin_fmaf(ab, -1e-4f, -b) - abt, M = __builtin_fmaf(ab, -1e-4f, b) + atm;
+    return fmaxf(Lm, M);
+}
+
+// An owner's ray as its L.ray record holds it, for whoever tests its spheres: origin, direction, a = |d|^2 and abt (entry_margin) as of the round's start.
+// (I: int or unsigned as the caller holds the owner — converting the index changes the kernels' text.  walk_pool_dense reads the record itself: there even this form does.)
+template <typename I>
+RT_DEV void owner_ray(const WalkLds& L, I owner, RayF& q, float& a, float& abt) {
+    const float4 r0 = L.ray[2 * owner], r1 = L.ray[2 * owner + 1];
+    q.o = {r0.x, r0.y, r0.z}; q.d = {r0.w, r1.x, r1.y}; a = r1.z; abt = r1.w;
+}
+RT_DEV float margin_atm(float a) { return a * (0.001f * 0.9999f - 1e-6f); }      // entry_margin's atm: a * t_min, lowered
+RT_DEV float margin_abt(float a, float best_t) { return __builtin_fmaf(a * best_t, 1.0001f, 1e-6f * a); }      // ... and its abt: a * best_t, raised
+// A round begins: this lane's state for whoever tests its spheres (the ray's second half with abt as of now, the best hit as a key), the tie flags cleared ...
+RT_DEV void round_begin(WalkLds& L, int lane, const RayF& r, float a, float best_t, int best) {
+    L.ray[2 * lane + 1] = make_float4(r.d.y, r.d.z, a, margin_abt(a, best_t));
+    L.key[lane] = ((unsigned long long)__float_as_uint(best_t) << 32) | (unsigned)best;
+    if (lane == 0) { L.tie_lo = 0u; L.tie_hi = 0u; }
+}
+// ... and ends, after the fence behind its last candidate: every owner picks up its key and its tie bit
+RT_DEV void round_pickup(const WalkLds& L, int lane, float& best_t, int& best, bool& tie) {
+    const unsigned long long k = L.key[lane];
+    best_t = __uint_as_float((unsigned)(k >> 32)); best = (int)(unsigned)k;
+    const unsigned tmask = lane < 32 ? L.tie_lo : L.tie_hi;
+    if ((tmask >> (lane & 31)) & 1u) tie = true;
+}
+
+// one queued candidate: the exact roots' offer (sphere_offer_t), eligibility as in `offer`, merged into the owner's key
 // (q, a: the owner's ray and |d|^2 — a direct round holds them in registers, the queue's candidates fetch them from L.ray)
 RT_DEV void pool_candidate_b(const DevTree& T, const float4* s_nodes, WalkLds& L, const uint4 c, const RayF& q, const float a, const float4 blo, const float4 bhi STAT_ARG) {
     const int owner = (int)c.w;
@@ -488,25 +548,13 @@ RT_DEV void pool_candidate_b(const DevTree& T, const float4* s_nodes, WalkLds& L
     const unsigned long long k0 = L.key[owner];
     const float best_t = __uint_as_float((unsigned)(k0 >> 32));
     const int best = (int)(unsigned)k0;
-    const float sq = sqrtf(disc);
-    float cand = __builtin_inff();
-    const float t1 = (-b - sq) / a;
-    if (t1 > 0.001f) cand = t1;
-    else { const float t2 = (-b + sq) / a; if (t2 > 0.001f) cand = t2; }
+    const float cand = sphere_offer_t(a, b, sqrtf(disc));
     if (!(cand <= best_t)) return;
     const int id = __float_as_int(blo.w);
     STAT(st, ST_OFFERS, 1);
     bool tie = false;
     if (cand < best_t) {
-        bool ok = in_brick(q, cand, blo, bhi);
-        if (!ok) {
-            const int node1 = __float_as_int(bhi.w);
-            if (node1 >= 0) {
-                const float4 n0 = s_nodes[node1 * 3 + 0], n1 = s_nodes[node1 * 3 + 1];
-                ok = ray_box(q, n0.x, n0.y, n0.z, n0.w, n1.x, n1.y);
-            } else ok = eligible(s_nodes, q, cand, id STAT_PASS);
-        }
-        if (ok) {
+        if (hit_eligible<false>(s_nodes, q, cand, blo, bhi STAT_PASS)) {
             const unsigned long long old = atomicMin(&L.key[owner], ((unsigned long long)__float_as_uint(cand) << 32) | (unsigned)id);
             // an equal t from another tree sphere (index > 0: the ground wins its ties in the reference too): the visit order decides
             tie = (unsigned)(old >> 32) == __float_as_uint(cand) && (int)(unsigned)old != id && (int)(unsigned)old > 0;
@@ -520,9 +568,9 @@ RT_DEV void pool_candidate(const DevTree& T, const float4* s_nodes, WalkLds& L, 
     // cannot win has fetched it for nothing, a chain alone in its wave has one dependent round trip less per candidate)
     const int e = (int)c.z;
     const float4 blo = T.acc.brick[2 * e], bhi = T.acc.brick[2 * e + 1];
-    const float4 r0 = L.ray[2 * c.w], r1 = L.ray[2 * c.w + 1];
-    RayF q; q.o = {r0.x, r0.y, r0.z}; q.d = {r0.w, r1.x, r1.y};
-    pool_candidate_b(T, s_nodes, L, c, q, r1.z, blo, bhi STAT_PASS);
+    RayF q; float a, abt;
+    owner_ray(L, c.w, q, a, abt);
+    pool_candidate_b(T, s_nodes, L, c, q, a, blo, bhi STAT_PASS);
 }
 
 RT_DEV void pool_drain(const DevTree& T, const float4* s_nodes, WalkLds& L, int lane, unsigned& qn STAT_ARG) {
@@ -543,23 +591,19 @@ RT_DEV void walk_pool(const DevTree& T, const float4* s_nodes, WalkLds& L, const
     const int32_t* __restrict__ cs = A.cs;
     const float4* __restrict__ hot = A.hot;
     const int lane = threadIdx.x & 63;
-    // a column's bins (rt_accel.h): Gf fine bins of width 1 / F cells, entries keyed by their centre — the query grows by q_c
     const int Gf = A.Gf;
     const float fF = (float)A.F, fGf = (float)Gf, fGfm = fGf - 0.5f, q_c = A.rq_c;
+    const ColBins B = {cs, Gf, fF, fGf, fGfm, q_c};
     const int step = W.fwd ? 1 : -1;
-    const float f_atm = a * (0.001f * 0.9999f - 1e-6f);
     bool walking = W.walking && W.i != W.iend;
     const int nw0 = __popcll(__ballot(walking));
     const bool thin_round = RT_POOL_THIN_ROUND && nw0 <= kThinWalkers;      // (walkers only leave: every round of this call has at most 16)
     L.ray[2 * lane] = make_float4(r.o.x, r.o.y, r.o.z, r.d.x);
     while (true) {
-        // ---- this lane's state for whoever tests its spheres; pool and flags cleared
-        L.ray[2 * lane + 1] = make_float4(r.d.y, r.d.z, a, __builtin_fmaf(a * best_t, 1.0001f, 1e-6f * a));
-        L.key[lane] = ((unsigned long long)__float_as_uint(best_t) << 32) | (unsigned)best;
-        if (lane == 0) { L.tie_lo = 0u; L.tie_hi = 0u; }
+        round_begin(L, lane, r, a, best_t, best);
         const unsigned long long wmask = __ballot(walking);
         if (thin_round && walking) {
-            const unsigned rank = __builtin_amdgcn_mbcnt_hi((unsigned)(wmask >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)wmask, 0u));
+            const unsigned rank = rank_below(wmask);
             uint4* rec = (uint4*)L.pref;
             rec[2 * rank] = make_uint4((unsigned)lane, (unsigned)W.i, (unsigned)step, (unsigned)W.iend);
             rec[2 * rank + 1] = make_uint4(__float_as_uint(W.om_c), __float_as_uint(W.on_c), __float_as_uint(W.slope), (unsigned)W.coff);
@@ -581,6 +625,7 @@ RT_DEV void walk_pool(const DevTree& T, const float4* s_nodes, WalkLds& L, const
                 const int wstep = (int)ra.z;
                 if (c < ((int)ra.w - (int)ra.y) * wstep) {           // (columns left: a column at or beyond the end is empty)
                     const int wi = (int)ra.y + c * wstep;
+                    // (column_entries' steps on the record's values, spelled out)
                     const float w_om = __uint_as_float(rb.x), w_on = __uint_as_float(rb.y), w_slope = __uint_as_float(rb.z);
                     const float u0 = w_on + ((float)wi - w_om) * w_slope, u1 = u0 + w_slope;          // the line at the column's two edges
                     const float lo = (fminf(u0, u1) - q_c) * fF, hi = (fmaxf(u0, u1) + q_c) * fF;      // in fine bins (F is a power of two)
@@ -596,7 +641,7 @@ RT_DEV void walk_pool(const DevTree& T, const float4* s_nodes, WalkLds& L, const
             int qs = (int)cnt;
             qs += __builtin_amdgcn_update_dpp(0, qs, 0xB1, 0xf, 0xf, false);     // quad_perm:[1,0,3,2]
             qs += __builtin_amdgcn_update_dpp(0, qs, 0x4E, 0xf, 0xf, false);     // quad_perm:[2,3,0,1]
-            const unsigned rank = __builtin_amdgcn_mbcnt_hi((unsigned)(wmask >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)wmask, 0u));
+            const unsigned rank = rank_below(wmask);
             const int mywork = __builtin_amdgcn_ds_bpermute((int)((rank & 15u) << 4), qs);            // from lane 4 x rank
             if (walking) {
                 const int taken = min(kThinCols, (W.iend - W.i) * step);
@@ -619,18 +664,14 @@ RT_DEV void walk_pool(const DevTree& T, const float4* s_nodes, WalkLds& L, const
                     STAT(st, ST_A_ITERS_WAVE, 1);
                     unsigned he = 0u; int owner = 0;
                     if (act) { const uint2 sl = slot[lane]; he = sl.x; owner = (int)sl.y; }
-                    const float4 r0 = L.ray[2 * owner], r1 = L.ray[2 * owner + 1];
+                    RayF q; float qa, abt;
+                    owner_ray(L, owner, q, qa, abt);
                     const float4 s4 = hot[he], blo = A.brick[2 * he], bhi = A.brick[2 * he + 1];
-                    RayF q; q.o = {r0.x, r0.y, r0.z}; q.d = {r0.w, r1.x, r1.y};
-                    const float qa = r1.z, abt = r1.w, atm = qa * (0.001f * 0.9999f - 1e-6f);
+                    const float atm = margin_atm(qa);
                     STAT(st, ST_TESTS, act ? 1 : 0); STAT(st, ST_A_LANE_STEPS, act ? 1 : 0);
-                    const float ocx = q.o.x - s4.x, ocy = q.o.y - s4.y, ocz = q.o.z - s4.z;
-                    const float b = ocx * q.d.x + ocy * q.d.y + ocz * q.d.z;
-                    const float cc = (ocx * ocx + ocy * ocy + ocz * ocz) - s4.w;
-                    const float disc = b * b - qa * cc;
-                    const float ab = fabsf(b);
-                    const float Lm = __builtin_fmaf(ab, -1e-4f, -b) - abt, M = __builtin_fmaf(ab, -1e-4f, b) + atm;
-                    const float P = fmaxf(Lm, M);
+                    const float2 bc = sphere_bc(q, s4);
+                    const float b = bc.x, disc = b * b - qa * bc.y;
+                    const float P = entry_margin(b, abt, atm);
                     if (act && disc > 0.0f && !(P > 0.0f && P * P > disc * 1.0003f)) {
                         STAT(st, ST_DISCPOS, 1);
                         pool_candidate_b(T, s_nodes, L, make_uint4(__float_as_uint(b), __float_as_uint(disc), he, (unsigned)owner), q, qa, blo, bhi STAT_PASS);
@@ -642,7 +683,7 @@ RT_DEV void walk_pool(const DevTree& T, const float4* s_nodes, WalkLds& L, const
                 // `pref` are read: phase 2 below may overwrite them after the fence)
                 const bool has = cnt != 0u;
                 const unsigned long long m = __ballot(has);
-                if (has) L.seg[__builtin_amdgcn_mbcnt_hi((unsigned)(m >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)m, 0u))] = make_uint2((unsigned)f0, cnt | (L.pref[8 * wk] << 26));
+                if (has) L.seg[rank_below(m)] = make_uint2((unsigned)f0, cnt | (L.pref[8 * wk] << 26));
                 n_seg = (unsigned)__popcll(m);
                 walk_sync();
             }
@@ -657,13 +698,7 @@ RT_DEV void walk_pool(const DevTree& T, const float4* s_nodes, WalkLds& L, const
             e0[c] = 0; e1[c] = 0;
             if (c < cols_now && walking && W.i != W.iend) {
                 STAT(st, ST_COLS, 1);
-                const float u0 = W.on_c + ((float)W.i - W.om_c) * W.slope, u1 = u0 + W.slope;      // the line at the column's two edges
-                const float lo = (fminf(u0, u1) - q_c) * fF, hi = (fmaxf(u0, u1) + q_c) * fF;      // in fine bins (F is a power of two)
-                if (hi >= 0.0f && lo < fGf) {
-                    const int k0 = (int)fmaxf(lo, 0.0f), k1 = (int)fminf(hi, fGfm);
-                    const unsigned cbase = (unsigned)(W.coff + W.i * Gf);
-                    e0[c] = cs[cbase + (unsigned)k0]; e1[c] = cs[cbase + (unsigned)k1 + 1u];
-                }
+                column_entries(B, W.om_c, W.on_c, W.slope, W.coff, W.i, e0[c], e1[c]);
                 W.i += step; ++W.cols;
             }
         }
@@ -673,7 +708,7 @@ RT_DEV void walk_pool(const DevTree& T, const float4* s_nodes, WalkLds& L, const
             const bool has = e1[c] > e0[c];
             const unsigned long long m = __ballot(has);
             if (has) {
-                const unsigned slot = n_seg + __builtin_amdgcn_mbcnt_hi((unsigned)(m >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)m, 0u));
+                const unsigned slot = n_seg + rank_below(m);
                 L.seg[slot] = make_uint2((unsigned)e0[c], (unsigned)(e1[c] - e0[c]) | ((unsigned)lane << 26));
                 W.work += (unsigned)(e1[c] - e0[c]);
             }
@@ -740,19 +775,14 @@ RT_DEV void walk_pool(const DevTree& T, const float4* s_nodes, WalkLds& L, const
                     const unsigned p0 = L.pref[S.sg];
                     he = sd.x - p0 + S.cur;
                     S.owner = (int)(sd.y >> 26);
-                    const float4 r0 = L.ray[2 * S.owner], r1 = L.ray[2 * S.owner + 1];
-                    S.q.o = {r0.x, r0.y, r0.z}; S.q.d = {r0.w, r1.x, r1.y}; S.a = r1.z; S.abt = r1.w;
-                    S.atm = S.a * (0.001f * 0.9999f - 1e-6f);
+                    owner_ray(L, S.owner, S.q, S.a, S.abt);
+                    S.atm = margin_atm(S.a);
                 }
                 const float4 s4 = hot[he], blo = A.brick[2 * he], bhi = A.brick[2 * he + 1];
                 STAT(st, ST_TESTS, act ? 1 : 0); STAT(st, ST_A_LANE_STEPS, act ? 1 : 0);
-                const float ocx = S.q.o.x - s4.x, ocy = S.q.o.y - s4.y, ocz = S.q.o.z - s4.z;
-                const float b = ocx * S.q.d.x + ocy * S.q.d.y + ocz * S.q.d.z;
-                const float c = (ocx * ocx + ocy * ocy + ocz * ocz) - s4.w;
-                const float disc = b * b - S.a * c;
-                const float ab = fabsf(b);
-                const float Lm = __builtin_fmaf(ab, -1e-4f, -b) - S.abt, M = __builtin_fmaf(ab, -1e-4f, b) + S.atm;
-                const float P = fmaxf(Lm, M);
+                const float2 bc = sphere_bc(S.q, s4);
+                const float b = bc.x, disc = b * b - S.a * bc.y;
+                const float P = entry_margin(b, S.abt, S.atm);
                 if (act && disc > 0.0f && !(P > 0.0f && P * P > disc * 1.0003f)) {
                     STAT(st, ST_DISCPOS, 1);
                     pool_candidate_b(T, s_nodes, L, make_uint4(__float_as_uint(b), __float_as_uint(disc), he, (unsigned)S.owner), S.q, S.a, blo, bhi STAT_PASS);
@@ -778,9 +808,8 @@ RT_DEV void walk_pool(const DevTree& T, const float4* s_nodes, WalkLds& L, const
                         const int ow = (int)(sd.y >> 26);
                         if (ow != S.owner) {
                             S.owner = ow;
-                            const float4 r0 = L.ray[2 * ow], r1 = L.ray[2 * ow + 1];
-                            S.q.o = {r0.x, r0.y, r0.z}; S.q.d = {r0.w, r1.x, r1.y}; S.a = r1.z; S.abt = r1.w;
-                            S.atm = S.a * (0.001f * 0.9999f - 1e-6f);
+                            owner_ray(L, ow, S.q, S.a, S.abt);
+                            S.atm = margin_atm(S.a);
                         }
                     }
                     he[j] = act[j] ? S.base + S.cur : 0u;
@@ -792,14 +821,9 @@ RT_DEV void walk_pool(const DevTree& T, const float4* s_nodes, WalkLds& L, const
                 for (int j = 0; j < RT_POOL_SPANS; ++j) {
                     const PoolSpan& S = sp[j];
                     STAT(st, ST_TESTS, act[j] ? 1 : 0); STAT(st, ST_A_LANE_STEPS, act[j] ? 1 : 0);
-                    const float ocx = S.q.o.x - s4[j].x, ocy = S.q.o.y - s4[j].y, ocz = S.q.o.z - s4[j].z;
-                    const float b = ocx * S.q.d.x + ocy * S.q.d.y + ocz * S.q.d.z;
-                    const float c = (ocx * ocx + ocy * ocy + ocz * ocz) - s4[j].w;
-                    const float disc = b * b - S.a * c;
-                    // App. A.5: near root beyond the best hit (Lm) / far root behind t_min (M); never both positive: one test of the larger
-                    const float ab = fabsf(b);
-                    const float Lm = __builtin_fmaf(ab, -1e-4f, -b) - S.abt, M = __builtin_fmaf(ab, -1e-4f, b) + S.atm;
-                    const float P = fmaxf(Lm, M);
+                    const float2 bc = sphere_bc(S.q, s4[j]);
+                    const float b = bc.x, disc = b * b - S.a * bc.y;
+                    const float P = entry_margin(b, S.abt, S.atm);
                     hold[j] = act[j] && disc > 0.0f && !(P > 0.0f && P * P > disc * 1.0003f);
                     hb[j] = b; hd[j] = disc;
                     anyhold = anyhold || hold[j];
@@ -810,7 +834,7 @@ RT_DEV void walk_pool(const DevTree& T, const float4* s_nodes, WalkLds& L, const
                     for (int j = 0; j < RT_POOL_SPANS; ++j) {
                         const unsigned long long hm = __ballot(hold[j]);
                         if (hm != 0ull) {
-                            const unsigned slot = qn + __builtin_amdgcn_mbcnt_hi((unsigned)(hm >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)hm, 0u));
+                            const unsigned slot = qn + rank_below(hm);
                             if (hold[j]) {
                                 STAT(st, ST_DISCPOS, 1);
                                 const uint4 ce = make_uint4(__float_as_uint(hb[j]), __float_as_uint(hd[j]), he[j], (unsigned)sp[j].owner);
@@ -824,14 +848,9 @@ RT_DEV void walk_pool(const DevTree& T, const float4* s_nodes, WalkLds& L, const
                 if (qn >= 64u) pool_drain(T, s_nodes, L, lane, qn STAT_PASS);
             }
             pool_drain(T, s_nodes, L, lane, qn STAT_PASS);
-            (void)f_atm;
         }
         if (picked) {
-            // ---- every owner picks up its result
-            const unsigned long long k = L.key[lane];
-            best_t = __uint_as_float((unsigned)(k >> 32)); best = (int)(unsigned)k;
-            const unsigned tmask = lane < 32 ? L.tie_lo : L.tie_hi;
-            if ((tmask >> (lane & 31)) & 1u) tie = true;
+            round_pickup(L, lane, best_t, best, tie);
         }
         if (walking && best >= 0) walk_clip(W, A, best_t);
         walking = walking && W.i != W.iend;
@@ -856,33 +875,26 @@ RT_DEV void walk_pool_dense(const DevTree& T, const float4* s_nodes, WalkLds& L,
     const int lane = threadIdx.x & 63;
     const int Gf = A.Gf;
     const float fF = (float)A.F, fGf = (float)Gf, fGfm = fGf - 0.5f, q_c = A.rq_c;
+    const ColBins B = {cs, Gf, fF, fGf, fGfm, q_c};
     const int step = W.fwd ? 1 : -1;
     bool walking = W.walking && W.i != W.iend;
     const int nw0 = __popcll(__ballot(walking));
     L.ray[2 * lane] = make_float4(r.o.x, r.o.y, r.o.z, r.d.x);
     while (true) {
-        L.ray[2 * lane + 1] = make_float4(r.d.y, r.d.z, a, __builtin_fmaf(a * best_t, 1.0001f, 1e-6f * a));
-        L.key[lane] = ((unsigned long long)__float_as_uint(best_t) << 32) | (unsigned)best;
-        if (lane == 0) { L.tie_lo = 0u; L.tie_hi = 0u; }
+        round_begin(L, lane, r, a, best_t, best);
         walk_sync();
         // ---- phase 1: the entry range of the next column of every walking lane
         int e0 = 0, e1 = 0;
         if (walking && W.i != W.iend) {
             STAT(st, ST_COLS, 1);
-            const float u0 = W.on_c + ((float)W.i - W.om_c) * W.slope, u1 = u0 + W.slope;
-            const float lo = (fminf(u0, u1) - q_c) * fF, hi = (fmaxf(u0, u1) + q_c) * fF;
-            if (hi >= 0.0f && lo < fGf) {
-                const int k0 = (int)fmaxf(lo, 0.0f), k1 = (int)fminf(hi, fGfm);
-                const unsigned cbase = (unsigned)(W.coff + W.i * Gf);
-                e0 = cs[cbase + (unsigned)k0]; e1 = cs[cbase + (unsigned)k1 + 1u];
-            }
+            column_entries(B, W.om_c, W.on_c, W.slope, W.coff, W.i, e0, e1);
             W.i += step; ++W.cols;
         }
         const bool has = e1 > e0;
         const unsigned long long m = __ballot(has);
         const unsigned n_seg = (unsigned)__popcll(m);
         if (has) {
-            const unsigned slot = __builtin_amdgcn_mbcnt_hi((unsigned)(m >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)m, 0u));
+            const unsigned slot = rank_below(m);
             L.seg[slot] = make_uint2((unsigned)e0, (unsigned)(e1 - e0) | ((unsigned)lane << 26));
             W.work += (unsigned)(e1 - e0);
         }
@@ -923,7 +935,7 @@ RT_DEV void walk_pool_dense(const DevTree& T, const float4* s_nodes, WalkLds& L,
                     S.seg_end = p0 + (sd.y & 0x3ffffffu);
                     S.base = sd.x - p0;
                     S.owner = (int)(sd.y >> 26);
-                    const float4 r0 = L.ray[2 * S.owner], r1 = L.ray[2 * S.owner + 1];
+                    const float4 r0 = L.ray[2 * S.owner], r1 = L.ray[2 * S.owner + 1];          // (owner_ray without abt, which every pass forms anew below)
                     S.q.o = {r0.x, r0.y, r0.z}; S.q.d = {r0.w, r1.x, r1.y}; S.a = r1.z;
                     S.atm = S.a * (0.001f * 0.9999f - 1e-6f);
                 }
@@ -935,7 +947,7 @@ RT_DEV void walk_pool_dense(const DevTree& T, const float4* s_nodes, WalkLds& L,
                 for (int k = 0; k < PB; ++k) s4[k] = hp[k];                           // (padded arrays: reading past a range is harmless, holding is not)
                 // the owner's best hit as of now
                 const float bt_now = __uint_as_float((unsigned)(L.key[S.owner] >> 32));
-                S.abt = __builtin_fmaf(S.a * bt_now, 1.0001f, 1e-6f * S.a);
+                S.abt = margin_abt(S.a, bt_now);
                 if (act) { STAT(st, ST_TESTS, nb); STAT(st, ST_A_LANE_STEPS, 1); }
                 bool hold[PB]; float hb[PB], hd[PB];
                 bool anyhold = false;
@@ -945,12 +957,7 @@ RT_DEV void walk_pool_dense(const DevTree& T, const float4* s_nodes, WalkLds& L,
                     const float b = ocx * S.q.d.x + ocy * S.q.d.y + ocz * S.q.d.z;
                     const float c = (ocx * ocx + ocy * ocy + ocz * ocz) - s4[k].w;
                     const float disc = b * b - S.a * c;
-                    // App. A.5: "near root beyond the best hit" (Lm) and "far root behind t_min" (M).  The two cannot both be
-                    // positive (Lm > 0 needs b + kb < -abt, M > 0 needs b - kb > -atm, and abt > atm): one test of the larger.
-                    // (the margins are fused here — one rounding less than the analysis allows for)
-                    const float ab = fabsf(b);
-                    const float Lm = __builtin_fmaf(ab, -1e-4f, -b) - S.abt, M = __builtin_fmaf(ab, -1e-4f, b) + S.atm;
-                    const float P = fmaxf(Lm, M);
+                    const float P = entry_margin(b, S.abt, S.atm);
                     hold[k] = (unsigned)k < nb && disc > 0.0f && !(P > 0.0f && P * P > disc * 1.0003f);
                     hb[k] = b; hd[k] = disc;
                     anyhold = anyhold || hold[k];
@@ -960,7 +967,7 @@ RT_DEV void walk_pool_dense(const DevTree& T, const float4* s_nodes, WalkLds& L,
                     for (int k = 0; k < PB; ++k) {
                         const unsigned long long hm = __ballot(hold[k]);
                         if (hm != 0ull) {
-                            const unsigned slot = qn + __builtin_amdgcn_mbcnt_hi((unsigned)(hm >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)hm, 0u));
+                            const unsigned slot = qn + rank_below(hm);
                             if (hold[k]) {
                                 STAT(st, ST_DISCPOS, 1);
                                 const uint4 ce = make_uint4(__float_as_uint(hb[k]), __float_as_uint(hd[k]), he0 + (unsigned)k, (unsigned)S.owner);
@@ -975,10 +982,7 @@ RT_DEV void walk_pool_dense(const DevTree& T, const float4* s_nodes, WalkLds& L,
                 if (qn >= (unsigned)RT_DENSE_DRAIN) pool_drain(T, s_nodes, L, lane, qn STAT_PASS);
             }
             pool_drain(T, s_nodes, L, lane, qn STAT_PASS);
-            const unsigned long long k = L.key[lane];
-            best_t = __uint_as_float((unsigned)(k >> 32)); best = (int)(unsigned)k;
-            const unsigned tmask = lane < 32 ? L.tie_lo : L.tie_hi;
-            if ((tmask >> (lane & 31)) & 1u) tie = true;
+            round_pickup(L, lane, best_t, best, tie);
         }
         if (walking && best >= 0) walk_clip(W, A, best_t);
         walking = walking && W.i != W.iend;
@@ -1059,10 +1063,8 @@ RT_DEV void closest_tree(const DevScene& S, const DevTree& T, const float4* s_no
                 const float4* hs = hot_spheres(s_nodes, T.n_nodes);
                 const float4 sp = k < kHotLarge ? hs[1 + k] : T.acc.large_hot[k];
                 WPASS(WP_LARGE_K);
-                const float ocx = r.o.x - sp.x, ocy = r.o.y - sp.y, ocz = r.o.z - sp.z;
-                const float b = ocx * r.d.x + ocy * r.d.y + ocz * r.d.z;
-                const float c = (ocx * ocx + ocy * ocy + ocz * ocz) - sp.w;
-                const float disc = b * b - a * c;
+                const float2 bc = sphere_bc(r, sp);
+                const float b = bc.x, disc = b * b - a * bc.y;
                 if (disc > 0.0f) {
                     const float sqa = __builtin_amdgcn_sqrtf(disc);
                     const float m = 1e-4f * ((fabsf(b) + sqa) * ra) + 1e-6f;
@@ -1070,11 +1072,7 @@ RT_DEV void closest_tree(const DevScene& S, const DevTree& T, const float4* s_no
                     const bool beyond = (-b - sqa) * ra - m > closest;
                     if (!behind && !beyond) {
                         WPASS(WP_LARGE_EXACT);
-                        const float sq = sqrtf(disc);
-                        float cand = __builtin_inff();
-                        const float t1 = (-b - sq) / a;
-                        if (t1 > 0.001f) cand = t1;
-                        else { const float t2 = (-b + sq) / a; if (t2 > 0.001f) cand = t2; }
+                        const float cand = sphere_offer_t(a, b, sqrtf(disc));
                         offer(T, s_nodes, r, cand, k < kHotLarge ? hs[1 + kHotLarge + 2 * k] : T.acc.large_brick[2 * k], k < kHotLarge ? hs[2 + kHotLarge + 2 * k] : T.acc.large_brick[2 * k + 1], closest, best, ts.tie STAT_PASS);
                     }
                 }
@@ -1442,8 +1440,7 @@ __global__ __launch_bounds__(256, RT_RENDER_WAVES) void k_render(RenderArgs A) {
         }
     };
     RT_STATS_ONLY(
-    Stats st; for (int q = 0; q < ST_N; ++q) st.c[q] = 0;
-    for (int q = 0; q < 8; ++q) st.cyc[q] = 0;
+    Stats st; stats_clear(st);
     const unsigned long long tK0 = TICK(), rK0 = __builtin_amdgcn_s_memrealtime();
     unsigned int dbg_thin_iters = 0, dbg_long = 0;
     unsigned long long th[4] = {0, 0, 0, 0};
@@ -1486,7 +1483,7 @@ __global__ __launch_bounds__(256, RT_RENDER_WAVES) void k_render(RenderArgs A) {
                 if (mneed != 0ull) {
                     const long long n = (long long)__popcll(mneed);
                     const long long left = pool_end - pool_next;                 // what the current chunk still holds
-                    const long long rank = (long long)__builtin_amdgcn_mbcnt_hi((unsigned)(mneed >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)mneed, 0u));
+                    const long long rank = (long long)rank_below(mneed);
                     long long fresh = 0;
                     if (n > left) {                                               // one more chunk for the wave (lane 0 asks)
                         unsigned int b = 0;
@@ -1643,10 +1640,7 @@ __global__ __launch_bounds__(256) void k_tile_cost(RenderArgs A, int* __restrict
     bool live = inside;
     if (live) r = primary_ray(A.scene.cam, i, j, A.max_x, A.max_y, ps);
     int bounces = 0;
-    RT_STATS_ONLY(
-    Stats st; for (int q = 0; q < ST_N; ++q) st.c[q] = 0;
-    for (int q = 0; q < 8; ++q) st.cyc[q] = 0;
-    )
+    RT_STATS_ONLY(Stats st; stats_clear(st);)
     float closest = FLT_MAX; int best = -1;
     TreeState ts; tree_state_init(ts);
     int lane_iters = 0;          // passes of this loop the path was alive for: its bounces plus the passes a long walk stayed pending (quorum) — the lane-time it costs
@@ -1689,10 +1683,7 @@ RT_DEV void trace_record(const RenderArgs& A, const float4* s_nodes, const RayF&
     const DevScene& S = A.scene; const DevTree& T = A.tree;
     const float a = dot3(r.d, r.d);
     float closest = FLT_MAX; int best = -1;
-    RT_STATS_ONLY(
-    Stats st; for (int q = 0; q < ST_N; ++q) st.c[q] = 0;
-    for (int q = 0; q < 8; ++q) st.cyc[q] = 0;
-    )
+    RT_STATS_ONLY(Stats st; stats_clear(st);)
     if (TREE) {
         TreeState ts; tree_state_init(ts);
         bool act = live;

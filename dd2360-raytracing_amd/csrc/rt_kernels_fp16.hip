@@ -332,7 +332,7 @@ RT_DEV void push_pass(WaveLds& L, const __amdgpu_buffer_rsrc_t ent, int lane, ui
             acc &= acc - 1u;
             const int pr = p & 15, hi = p >> 4;               // pair of the pass, half of the pair
             const uint32_t idx1 = (pair0 + (unsigned)(pr * STRIDE)) * 2u + 1u + (unsigned)hi;       // (this lane's pairs of the pass are STRIDE apart)
-            const unsigned slot = qn + __builtin_amdgcn_mbcnt_hi((unsigned)(m >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)m, 0u));
+            const unsigned slot = qn + rank_below(m);
             L.u.p2.cq[slot] = (idx1 << 6) | (uint32_t)owner;
         }
         qn += n;

@@ -27,6 +27,10 @@ __device__ unsigned long long g_wave_dbg[8192 * 4];   // per wave: end time (100
 // when a third and two thirds of the samples were done, then the last two at the pixel's end (tools/chain_pace.py)
 __device__ unsigned int g_chain_dbg[(1 << 20) * 8];
 struct Stats { unsigned int c[ST_N]; unsigned long long cyc[8]; };
+static __device__ __forceinline__ void stats_clear(Stats& st) {      // a kernel's counter block starts at zero
+    for (int q = 0; q < ST_N; ++q) st.c[q] = 0;
+    for (int q = 0; q < 8; ++q) st.cyc[q] = 0;
+}
 #ifdef RT_STATS_LIGHT
 #define STAT(st, k, v) ((void)0)
 #define TRSTAT_ROUND(lane, n_seg, total) ((void)0)
