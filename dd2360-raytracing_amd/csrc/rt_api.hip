@@ -450,7 +450,7 @@ int rt_build_octree(const rt_sphere* list, int num_hitables, int spheres_per_lea
         flatten(*O->host, list, precision, 0, O->h_nodes, O->h_ent_hot, O->h_ent_id);
         O->n_nodes = (int)O->h_nodes.size(); O->n_entries = (int)O->h_ent_id.size();
         build_accel(O->accel, O->h_nodes, O->h_ent_id, O->h_ent_hot, num_hitables);
-        O->n_world = num_hitables; O->bit_rows = (int)(O->accel.cellbits.size() / 16);
+        O->n_world = num_hitables; O->bit_rows = (int)(O->accel.cellbits.size() / 16); O->spl = spheres_per_leaf;
         if (precision != RT_PRECISION_FP32) O->accel.p.enabled = 0;      // the error bounds behind the grid are binary32 bounds
     } catch (const std::bad_alloc&) { rt_free_octree(O); return RT_ENOMEM; }
     *out = O;
@@ -514,7 +514,8 @@ static void h16_plane_table(H16Layout& L) {
 }
 // The tree's device buffers in upload order, each with the host array it is a copy of: a binary32 tree's own flattened arrays, a
 // binary16 tree's pair layout `h16` (a group that is only freed needs none).  A tree built on the device (rt_build.hip) owns d_arena
-// and d_acc[7] alone — its other pointers are null here, Z.dev points into the arena — and is never uploaded.
+// d_acc[7] and the workspace d_ws it keeps for rt_octree_rebuild_gpu — its other pointers are null here, Z.dev points into the arena —
+// and is never uploaded.
 static DevGroup octree_group(const rt_octree* O, const H16Layout* h16 = nullptr) {
     rt_octree::Lazy& Z = *O->z;
     const AccelHost& A = O->accel;
@@ -524,7 +525,7 @@ static DevGroup octree_group(const rt_octree* O, const H16Layout* h16 = nullptr)
     g.add_copy(&Z.d_acc[0], A.large_hot).add_copy(&Z.d_acc[1], A.large_brick).add_copy(&Z.d_acc[2], A.cs).add_copy(&Z.d_acc[3], A.hot)
      .add_copy(&Z.d_acc[4], A.brick).add_copy(&Z.d_acc[5], A.memb_start).add_copy(&Z.d_acc[6], A.memb_cell).add_copy(&Z.d_acc[8], A.cellnode)
      .add_copy(&Z.d_acc[9], A.bits_index).add_copy(&Z.d_acc[10], A.cellbits);
-    return g.add(&Z.d_acc[7], 0).add(&Z.d_arena, 0);
+    return g.add(&Z.d_acc[7], 0).add(&Z.d_arena, 0).add(&Z.d_ws, 0);
 }
 static int octree_upload(const rt_octree* O) {
     rt_octree::Lazy& Z = *O->z;
@@ -688,22 +689,7 @@ int rt_octree_debug_array(const rt_octree* O, int which, void* out, size_t cap, 
 
 // buildOctree + traversal copy + candidate grid on the device, from the world's device-resident sphere list (rt_build.hip).
 // Inputs the device build declines are built on the host from the world's own copy of the list.
-int rt_build_octree_gpu(const rt_world* world, int spheres_per_leaf, rt_octree** out, void* stream) {
-    if (!world || !out || spheres_per_leaf <= 0) return RT_EINVAL;
-    *out = nullptr;
-    {
-        int rc = world_upload(world);
-        if (rc) return rc;
-        rt_octree* O = new (std::nothrow) rt_octree();
-        if (!O) return RT_ENOMEM;
-        O->z = new (std::nothrow) rt_octree::Lazy();
-        if (!O->z) { delete O; return RT_ENOMEM; }
-        O->precision = world->precision;
-        rc = gpubuild::build(O, (const float4*)world->z->d_geom, (const int32_t*)world->z->d_kind, world->n, spheres_per_leaf, (hipStream_t)stream);
-        if (rc == 0) { O->build_path = RT_BUILD_DEVICE; *out = O; return 0; }
-        (void)rt_free_octree(O);
-        if (rc != RT_ENOTSUP) return rc;
-    }
+static int build_octree_of_world_on_host(const rt_world* world, int spheres_per_leaf, rt_octree** out) {
     RT_TRY(world_host_geometry(world));
     std::vector<rt_sphere> list;
     try {
@@ -717,6 +703,84 @@ int rt_build_octree_gpu(const rt_world* world, int spheres_per_leaf, rt_octree**
     } catch (const std::bad_alloc&) { return RT_ENOMEM; }
     RT_TRY(rt_build_octree(list.data(), world->n, spheres_per_leaf, world->precision, out));
     (*out)->build_path = RT_BUILD_HOST_DECLINED;
+    return 0;
+}
+int rt_build_octree_gpu(const rt_world* world, int spheres_per_leaf, rt_octree** out, void* stream) {
+    if (!world || !out || spheres_per_leaf <= 0) return RT_EINVAL;
+    *out = nullptr;
+    int rc = world_upload(world);
+    if (rc) return rc;
+    rt_octree* O = new (std::nothrow) rt_octree();
+    if (!O) return RT_ENOMEM;
+    O->z = new (std::nothrow) rt_octree::Lazy();
+    if (!O->z) { delete O; return RT_ENOMEM; }
+    O->precision = world->precision;
+    rc = gpubuild::build(O, (const float4*)world->z->d_geom, (const int32_t*)world->z->d_kind, world->n, spheres_per_leaf, (hipStream_t)stream, false, nullptr);
+    if (rc == 0) { O->build_path = RT_BUILD_DEVICE; *out = O; return 0; }
+    (void)rt_free_octree(O);
+    if (rc != RT_ENOTSUP) return rc;
+    return build_octree_of_world_on_host(world, spheres_per_leaf, out);
+}
+
+// The tree of the world's current geometry in the handle of an earlier rt_build_octree_gpu (include/rt_amd_rebuild.h).  The device part and what
+// it keeps: gpubuild::rebuild.  Here: the refusals, what a handle whose last build was the host's has to give up first, and the host
+// build moved into the handle when the device declines.
+static int octree_drop_host_build(rt_octree* O) {          // the staging arrays and their uploads; the handle is an empty device-build handle afterwards
+    rt_octree::Lazy& Z = *O->z;
+    const int rc = group_free(octree_group(O));
+    delete O->host; O->host = nullptr;
+    std::vector<DevNode>().swap(O->h_nodes); std::vector<float4>().swap(O->h_ent_hot); std::vector<int32_t>().swap(O->h_ent_id);
+    O->accel = AccelHost();
+    Z.dev = DevTree{}; Z.uploaded = false;
+    return rc;
+}
+static void octree_render_nothing(rt_octree* O) {          // after a failed rebuild: no node, no grid, nothing to inspect; freeable
+    rt_octree::Lazy& Z = *O->z;
+    Z.dev = DevTree{}; Z.uploaded = true;
+    Z.d_ref_nodes = nullptr; Z.d_leaf_count = nullptr; Z.d_leaf_indices = nullptr;
+    O->n_nodes = 0; O->n_entries = 0; O->bit_rows = 1;
+    O->accel.p = DevAccel{}; O->accel.n_entries = 0; O->accel.n_entries_z = 0;
+}
+int rt_octree_rebuild_gpu(rt_octree* O, const rt_world* world, void* stream) {
+    if (!O || !world || !O->z) return RT_EINVAL;
+    if (O->build_path == RT_BUILD_HOST || world->n != O->n_world || world->precision != O->precision || O->spl <= 0) return RT_EINVAL;
+    RT_TRY(world_upload(world));
+    rt_octree::Lazy& Z = *O->z;
+    // from here on the handle is another tree: whatever is keyed on it misses once, as after free and build
+    O->serial = rt_next_serial();
+    delete Z.host_view; Z.host_view = nullptr;
+    int rc = O->host ? octree_drop_host_build(O) : 0;
+    bool regrown = false;
+    if (!rc) rc = gpubuild::rebuild(O, (const float4*)world->z->d_geom, (const int32_t*)world->z->d_kind, world->n, O->spl, (hipStream_t)stream, &regrown);
+    if (rc == 0) {
+        O->build_path = RT_BUILD_DEVICE;
+        Z.rebuilds++; if (regrown) Z.regrown++;
+        return 0;
+    }
+    octree_render_nothing(O);
+    if (rc != RT_ENOTSUP) return rc;
+    // the device build declined: the host build of rt_build_octree_gpu, moved into this handle; the device pieces go
+    rt_octree* T = nullptr;
+    RT_TRY(build_octree_of_world_on_host(world, O->spl, &T));
+    rc = group_free(octree_group(O));
+    Z.ws_bytes = Z.a_bytes = Z.b_bytes = 0; Z.len_pairs = Z.len_leaf = 0; Z.last_pairs = 0;
+    Z.ref_node_count = Z.ref_leaf_count = Z.ref_dropped_full = Z.ref_dropped_outside = Z.ref_spl = 0;
+    O->host = T->host; T->host = nullptr;
+    O->h_nodes.swap(T->h_nodes); O->h_ent_hot.swap(T->h_ent_hot); O->h_ent_id.swap(T->h_ent_id);
+    O->accel = std::move(T->accel);
+    O->n_nodes = T->n_nodes; O->n_entries = T->n_entries; O->n_world = T->n_world; O->bit_rows = T->bit_rows;
+    (void)rt_free_octree(T);
+    Z.dev = DevTree{}; Z.uploaded = false;                             // uploaded by the first launch that uses it, as any host build
+    O->build_path = RT_BUILD_HOST_DECLINED;
+    if (rc) { octree_render_nothing(O); return rc; }
+    Z.rebuilds++;
+    return 0;
+}
+int rt_octree_rebuild_info(const rt_octree* O, uint64_t* rebuilds, uint64_t* regrown, uint64_t* host_syncs_last) {
+    if (!O || !O->z) return RT_EINVAL;
+    if (rebuilds) *rebuilds = O->z->rebuilds;
+    if (regrown) *regrown = O->z->regrown;
+    if (host_syncs_last) *host_syncs_last = O->z->syncs_last;
     return 0;
 }
 int rt_octree_build_path(const rt_octree* O) { return O ? O->build_path : RT_EINVAL; }

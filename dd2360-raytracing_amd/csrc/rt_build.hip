@@ -12,8 +12,9 @@
 //     rest is dropped with the reference's "leaf nodes are full" message, :135); bucket b of the cell is created by the member
 //     number b x SPL, so buckets sorted by (creating sphere, pre-order rank of the cell) are leaves[1..leafCount-1] in order.
 // Everything else (pre-order traversal copy, bucket entries, memberships, bricks, the (x,z) candidate grid in two copies) is
-// per-sphere or per-cell work plus radix sorts (rocPRIM).  The host supplies a handful of scalars on the way (four small
-// read-backs): sizes of the arrays to allocate, the grid's cell size from the median radius.
+// per-sphere or per-cell work plus radix sorts (rocPRIM).  The host supplies a handful of scalars on the way (small read-backs):
+// sizes of the arrays to allocate, the grid's cell size from the median radius.  The workspace and the tree's two allocations stay in
+// the handle, and rt_octree_rebuild_gpu() builds into them again with the size read-backs gone ("memory kept in the handle" below).
 //
 // Binary16 trees (USE_FP16): the same reference layout in real_t = binary16 arithmetic, then the pair layout and plane table the
 // binary16 kernels read, and no candidate grid.
@@ -41,6 +42,10 @@ struct Counters {
     unsigned median_bits, bit_rows, n_large, reg_total;
     unsigned long long ylo, yhi, rmax;       // order-preserving encodings of doubles (min, max, max)
     unsigned long long reg_cells;            // cells the grid spheres' inflated squares overlap, summed (build_accel's density measure)
+    // a rebuild (rt_octree_rebuild_gpu) lays its arrays out for lengths the host chose BEFORE it knows the counts: the kernel that finds a
+    // count above its array's length sets this word, every later kernel of the run returns at once when it is set, and the host sees it at
+    // its next read-back.  No kernel indexes by a count that has not been checked against the length.
+    unsigned abort, pad_;
 };
 
 // a double as an unsigned integer with the same order
@@ -82,15 +87,18 @@ __global__ __launch_bounds__(256) void k_pairs(const float4* __restrict__ geom, 
                 atomicMin(&first[f3], (unsigned)i);
                 const unsigned slot = atomicAdd(&C->n_pairs, 1u);
                 if (slot < cap) pairs[slot] = ((unsigned long long)f3 << 32) | (unsigned)i;
-                else C->pair_overflow = 1u;
+                else { C->pair_overflow = 1u; C->abort = 1u; }
             }
         }
     }
 }
 
-// pairs sorted by (cell, sphere): where each cell's members start and end
-__global__ __launch_bounds__(256) void k_segments(const unsigned long long* __restrict__ sorted, unsigned n_pairs, unsigned* seg_start, unsigned* seg_end) {
+// pairs sorted by (cell, sphere): where each cell's members start and end.  COUNTED: launched over the array's length, the number of pairs
+// read from the counters (the keys behind it are the fill, which sorts last)
+template <bool COUNTED>
+__global__ __launch_bounds__(256) void k_segments(const unsigned long long* __restrict__ sorted, unsigned n_pairs, const Counters* C, unsigned* seg_start, unsigned* seg_end) {
     const unsigned p = blockIdx.x * 256 + threadIdx.x;
+    if (COUNTED) { if (C->abort) return; n_pairs = C->n_pairs; }        // (no abort: n_pairs <= the length k_pairs checked every slot against)
     if (p >= n_pairs) return;
     const unsigned fr = (unsigned)(sorted[p] >> 32);
     if (p == 0 || (unsigned)(sorted[p - 1] >> 32) != fr) seg_start[fr] = p;
@@ -99,7 +107,8 @@ __global__ __launch_bounds__(256) void k_segments(const unsigned long long* __re
 
 // node and leaf numbers in the reference's creation order (one block)
 __global__ __launch_bounds__(1024) void k_number(const unsigned* __restrict__ first, const unsigned* __restrict__ seg_start, const unsigned* __restrict__ seg_end,
-                                                 const unsigned long long* __restrict__ sorted, int spl, int* node_id, int* dev_index, int* accepted, int* leaf_of, Counters* C) {
+                                                 const unsigned long long* __restrict__ sorted, int spl, unsigned leaf_cap, int* node_id, int* dev_index, int* accepted, int* leaf_of, Counters* C) {
+    if (C->abort) return;                        // (the whole block: the word is written below only behind the last barrier)
     __shared__ unsigned long long s_key[kFullNodes];
     __shared__ unsigned long long s_bkey[4096];
     __shared__ unsigned short s_bfr[4096];
@@ -146,13 +155,17 @@ __global__ __launch_bounds__(1024) void k_number(const unsigned* __restrict__ fi
         for (int x = 0; x < total; ++x) rank += s_bkey[x] < s_bkey[q] ? 1 : 0;
         leaf_of[(int)s_bfr[q] * 8 + (int)s_bb[q]] = 1 + rank;        // leaf 0 is never used (leafCount starts at 1, :59)
     }
-    if (t == 0) { C->node_count = s_nodes; C->leaf_count = 1u + (unsigned)total; C->dropped_full = s_drop; }
+    if (t == 0) {
+        C->node_count = s_nodes; C->leaf_count = 1u + (unsigned)total; C->dropped_full = s_drop;
+        if (1u + (unsigned)total > leaf_cap) C->abort = 1u;           // more buckets than the leaf arrays are laid out for
+    }
 }
 
 // OctLeaf contents, and how many of a cell's accepted members can be hit at all (ghost slots cannot)
 __global__ __launch_bounds__(64) void k_leaves(const unsigned* __restrict__ seg_start, const int* __restrict__ accepted, const int* __restrict__ leaf_of,
                                                const unsigned long long* __restrict__ sorted, const int32_t* __restrict__ kind, int spl,
-                                               int32_t* leaf_count, int32_t* leaf_indices, int* hit_cnt) {
+                                               int32_t* leaf_count, int32_t* leaf_indices, int* hit_cnt, const Counters* C) {
+    if (C->abort) return;
     const int fr = blockIdx.x, lane = threadIdx.x;
     const int acc = accepted[fr];
     if (acc <= 0) { if (lane == 0) hit_cnt[fr] = 0; return; }
@@ -173,7 +186,8 @@ __global__ __launch_bounds__(64) void k_leaves(const unsigned* __restrict__ seg_
 // OctNode array in the reference's numbering, and the pre-order traversal copy with skip links (one block)
 __global__ __launch_bounds__(1024) void k_nodes(const float (*__restrict__ box)[6], const int* __restrict__ node_id, const int* __restrict__ dev_index, const int* __restrict__ accepted,
                                                 const int* __restrict__ leaf_of, const int* __restrict__ hit_cnt, int spl, rt_octnode* ref_nodes, DevNode* dnodes,
-                                                int* ent_first, int32_t* devcell, int32_t* cellnode, int* dev_to_fr, Counters* C) {
+                                                int* ent_first, int32_t* devcell, int32_t* cellnode, int* dev_to_fr, unsigned ent_cap, Counters* C) {
+    if (C->abort) return;                        // (the whole block: the word is written below only behind the barrier)
     __shared__ int s_ex[kFullNodes + 1];         // existing nodes before fr
     __shared__ int s_ef[kFullNodes + 1];         // hittable entries before fr
     const int t = threadIdx.x;
@@ -185,6 +199,7 @@ __global__ __launch_bounds__(1024) void k_nodes(const float (*__restrict__ box)[
     }
     for (int c = t; c < 512; c += 1024) cellnode[c] = -1;
     __syncthreads();
+    if (t == 0 && (unsigned)s_ef[kFullNodes] > ent_cap) C->abort = 1u;      // more entries than k_entries' arrays are laid out for
     for (int fr = t; fr < kFullNodes; fr += 1024) {
         ent_first[fr] = s_ef[fr];
         const int id = node_id[fr];
@@ -214,7 +229,8 @@ __global__ __launch_bounds__(1024) void k_nodes(const float (*__restrict__ box)[
 template <class R>
 __global__ __launch_bounds__(64) void k_entries(const unsigned* __restrict__ seg_start, const int* __restrict__ accepted, const int* __restrict__ dev_index, const int* __restrict__ ent_first,
                                                 const unsigned long long* __restrict__ sorted, const float4* __restrict__ geom, const int32_t* __restrict__ kind,
-                                                float4* ent_hot, int32_t* ent_id, unsigned long long* pair2, float4* hot_of) {
+                                                float4* ent_hot, int32_t* ent_id, unsigned long long* pair2, float4* hot_of, const Counters* C) {
+    if (C->abort) return;
     const int fr = blockIdx.x, lane = threadIdx.x;
     const int acc = accepted[fr];
     if (acc <= 0) return;
@@ -243,8 +259,10 @@ __global__ __launch_bounds__(64) void k_entries(const unsigned* __restrict__ seg
 // The binary16 kernels read the bucket entries as PAIRS (rt_kernels_fp16.hip; the layout rt_octree_upload derives on the host):
 // node first/count in pairs, an odd count padded with a NaN sphere, the entry -> sphere table following the pairs, and per node
 // the six indices of its box planes in the tree's plane table (x planes 0..8, y 9..17, z 18..26: the root box halved 3 times).
-__global__ void k_pair_offsets(DevNode* dnodes, int n_nodes, const int* __restrict__ dev_to_fr, int* pair_first, Counters* C) {
-    if (threadIdx.x != 0 || blockIdx.x != 0) return;
+// n_nodes < 0 (both kernels): the node count is read from the counters, k_pair_fill is launched over all kFullNodes
+__global__ void k_pair_offsets(DevNode* dnodes, int n_nodes, const int* __restrict__ dev_to_fr, int* pair_first, unsigned pair_cap, Counters* C) {
+    if (threadIdx.x != 0 || blockIdx.x != 0 || C->abort) return;
+    if (n_nodes < 0) n_nodes = (int)C->node_count;
     int run = 0;
     for (int k = 0; k < n_nodes; ++k) {
         pair_first[k] = run;
@@ -261,10 +279,14 @@ __global__ void k_pair_offsets(DevNode* dnodes, int n_nodes, const int* __restri
         dnodes[k].pad[0] = (int32_t)w;
     }
     C->reg_total = (unsigned)(2 * run);                               // entry slots of the pair layout (n_entries stays the entry count)
+    if ((unsigned)run > pair_cap) C->abort = 1u;
 }
 __global__ __launch_bounds__(64) void k_pair_fill(DevNode* dnodes, const int* __restrict__ pair_first, const float4* __restrict__ ent_hot, const int32_t* __restrict__ ent_id,
-                                                  uint4* pairs, int32_t* pid) {
+                                                  uint4* pairs, int32_t* pid, int n_nodes, const Counters* C) {
+    if (C->abort) return;
+    if (n_nodes < 0) n_nodes = (int)C->node_count;
     const int k = blockIdx.x, lane = threadIdx.x;
+    if (k >= n_nodes) return;
     const int first = dnodes[k].first, cnt = dnodes[k].count, pf = pair_first[k];
     auto hb = [](float v) { return (uint32_t)half_t(v).bits; };
     for (int e = 2 * lane; e < cnt; e += 128) {
@@ -283,8 +305,11 @@ __global__ __launch_bounds__(64) void k_pair_fill(DevNode* dnodes, const int* __
 }
 
 // ---------------------------------------------------------------------------------------------- candidate grid (rt_accel.h)
-__global__ __launch_bounds__(256) void k_memb(const unsigned long long* __restrict__ sorted2, int n_entries, int n_world, int32_t* memb_cell, int32_t* memb_start) {
+// COUNTED: launched over the arrays' length, the number of entries read from the counters (as k_segments)
+template <bool COUNTED>
+__global__ __launch_bounds__(256) void k_memb(const unsigned long long* __restrict__ sorted2, int n_entries, const Counters* C, int n_world, int32_t* memb_cell, int32_t* memb_start) {
     const int p = blockIdx.x * 256 + threadIdx.x;
+    if (COUNTED) { if (C->abort) return; n_entries = (int)C->n_entries; }      // (no abort: n_entries <= the length k_nodes checked it against)
     if (p >= n_entries) return;
     const int s = (int)(sorted2[p] >> 32);
     memb_cell[p] = (int32_t)(unsigned)sorted2[p];
@@ -296,7 +321,7 @@ __global__ __launch_bounds__(256) void k_memb(const unsigned long long* __restri
 __global__ __launch_bounds__(256) void k_bricks(int n_world, const int32_t* __restrict__ memb_start, const int32_t* __restrict__ memb_cell, const int32_t* __restrict__ devcell,
                                                 const float4* __restrict__ hot_of, float4* sb_lo, float4* sb_hi, int* multi, unsigned* r2bits, Counters* C) {
     const int s = blockIdx.x * 256 + threadIdx.x;
-    if (s >= n_world) return;
+    if (s >= n_world || C->abort) return;
     const int mb = memb_start[s], me = memb_start[s + 1];
     int lo[3] = {8, 8, 8}, hi[3] = {-1, -1, -1};
     bool ok = me > mb;
@@ -320,6 +345,14 @@ __global__ __launch_bounds__(256) void k_bricks(int n_world, const int32_t* __re
     const bool in_tree = me > mb;
     r2bits[s] = in_tree ? __float_as_uint(hot_of[s].w) : kNone;       // (r^2 >= 0: the bits order like the values)
     if (in_tree) atomicAdd(&C->in_tree, 1u);
+}
+
+// what the host decides the grid from, fetched into the counters so that ONE copy brings it back: radii[size / 2] of the sorted radii
+// (build_accel's median) and the rows of the membership bitmaps (one lane)
+__global__ void k_median(const unsigned* __restrict__ r2_sorted, const int* __restrict__ multi, const int* __restrict__ row_of, int n_world, Counters* C) {
+    if (threadIdx.x != 0 || blockIdx.x != 0 || C->abort) return;
+    C->median_bits = r2_sorted[C->in_tree / 2];                       // (in_tree <= n_world, and n_world >= 1)
+    C->bit_rows = (unsigned)(row_of[n_world - 1] + multi[n_world - 1]);
 }
 
 __global__ __launch_bounds__(256) void k_bitrows(int n_world, const int32_t* __restrict__ memb_start, const int32_t* __restrict__ memb_cell, const int32_t* __restrict__ devcell,
@@ -452,22 +485,59 @@ template <class R> static const float (*device_boxes(int* rc))[6] {   // the 585
     return d_box[dev];
 }
 
-// Builds into O (a fresh handle whose Lazy block is empty).  geom/kind: the world's device copies.  Returns RT_ENOTSUP when the
-// device build cannot take this input (the caller then builds on the host).
-int build(rt_octree* O, const float4* d_geom, const int32_t* d_kind, int n, int spl, hipStream_t st) {
+// ---- memory kept in the handle
+// A device build leaves three pieces in the handle (rt_handles.h): the workspace, the first arena (reference layout, traversal copy,
+// entries, memberships) and the second (the grid), each with its bytes.  build() below takes every piece from a Mem, which is where the
+// bytes come from: a piece the handle holds and that suffices is used as it is — neither hipMalloc nor hipFree — and one that is
+// missing or too small is allocated, at exactly the bytes asked (a fresh build) or with a quarter more (a rebuild's grid, whose size
+// the host knows only in mid-run).  Offsets inside a piece may differ from run to run: every pointer reaches the kernels by value.
+struct Mem {
+    bool slack = false;        // allocate a quarter more than asked
+    bool enlarged = false;     // a piece the handle held was too small
+    int get(void** slot, size_t* have, size_t need) {
+        if (*slot && *have >= need) return 0;
+        if (*slot) { enlarged = true; void* old = *slot; *slot = nullptr; *have = 0; RT_TRY(hipFree(old)); }      // (hipFree waits for the device)
+        const size_t bytes = slack ? need + need / 4 : need;
+        RT_TRY(hipMalloc(slot, bytes));
+        *have = bytes;
+        return 0;
+    }
+};
+constexpr int kOutgrown = 0x7ffffff0;                 // build(): a count exceeded the length its array was laid out for (rebuild() enlarges and runs again)
+constexpr size_t kMaxLeaves = 4097;                   // 512 cells x 8 buckets, and leaf 0
+
+static size_t pair_capacity(int n) { return (size_t)16 * n + 65536; }      // (cell, sphere) pairs the workspace holds; more -> host build
+static size_t first_arena_bytes(int n, int spl, bool fp16, size_t ent_cap, size_t leaf_cap, size_t node_cap) {
+    return sizeof(rt_octnode) * RT_OCTREE_MAX_NODES + sizeof(int32_t) * leaf_cap * (1 + (size_t)spl) + sizeof(DevNode) * node_cap
+         + ent_cap * (16 + 4 + 4 + 8 + 8) + (size_t)n * (4 + 4 + 4) + 512 * 4 + node_cap * 4 + 64 * 256
+         + (fp16 ? (ent_cap / 2 + node_cap + 1) * (16 + 8) + node_cap * 8 + 27 * 4 + 8 * 256 : 0);
+}
+static size_t with_a_quarter(size_t count, size_t at_least) { return std::max(count + count / 4, count + at_least); }
+
+// Builds into O.  geom/kind: the world's device copies.  Returns RT_ENOTSUP when the device build cannot take this input (the caller
+// then builds on the host).
+// counted == false, a fresh build: the host reads every count back before the step that needs it as a size (stops (1), (2), (3)).
+// counted == true, a rebuild (O holds the pieces of an earlier build): the arrays of the first arena and the two sorts behind them run
+// at the lengths Z.len_pairs / Z.len_leaf, which the host knows, the counts stay in Counters on the device, and stops (1) - (3) are
+// gone; kOutgrown when a count exceeded its length (Z.last_pairs then holds the pairs counted).  What the host genuinely decides
+// stays a read-back in both: the grid's cell size (4), the registration totals (5); and the final wait.
+int build(rt_octree* O, const float4* d_geom, const int32_t* d_kind, int n, int spl, hipStream_t st, bool counted, bool* grid_enlarged) {
     int rc = 0;
     const bool fp16 = O->precision == RT_PRECISION_FP16;
     const float (*d_box)[6] = fp16 ? device_boxes<half_t>(&rc) : device_boxes<float>(&rc);
     if (!d_box) return rc;
     rt_octree::Lazy& Z = *O->z;
-    // ---- workspace: everything whose size is known from n (freed at the end)
-    const size_t cap = (size_t)16 * n + 65536;                         // (cell, sphere) pairs; more -> host build
+    Z.syncs_last = 0;
+    auto wait = [&]() { ++Z.syncs_last; return hipStreamSynchronize(st); };       // every host-blocking wait of a build goes through here
+    Mem M;
+    O->spl = spl; O->n_world = n; O->bit_rows = 1;
+    { DevAccel off{}; O->accel.p = off; O->accel.n_entries = 0; O->accel.n_entries_z = 0; }
+    // ---- workspace: everything whose size is known from n
+    const size_t cap = pair_capacity(n);
     const size_t sort_tmp = (size_t)64 << 20;
     const size_t ws_bytes = cap * 16 + (size_t)n * (16 * 4 + 4 * 8 + 16 + 16) + sort_tmp + ((size_t)1 << 20);
-    void* ws_mem = nullptr;
-    RT_TRY(hipMalloc(&ws_mem, ws_bytes));
-    struct Guard { void* p; ~Guard() { if (p) (void)hipFree(p); } } guard{ws_mem};
-    Arena W; W.base = (char*)ws_mem; W.size = ws_bytes;
+    if ((rc = M.get(&Z.d_ws, &Z.ws_bytes, ws_bytes))) return rc;
+    Arena W; W.base = (char*)Z.d_ws; W.size = Z.ws_bytes;
     Counters* C = W.take<Counters>(1);
     unsigned* first = W.take<unsigned>(kFullNodes);
     unsigned* seg_start = W.take<unsigned>(kFullNodes);
@@ -490,57 +560,75 @@ int build(rt_octree* O, const float4* d_geom, const int32_t* d_kind, int n, int 
     RT_TRY(hipMemsetAsync(leaf_of, 0, sizeof(int) * kFullNodes * 8, st));
     RT_TRY(hipMemsetAsync(hot_of, 0, sizeof(float4) * (size_t)n, st));
     // ---- the reference-layout tree
+    // counted: the pairs are sorted at the length of their array, behind the pairs the greatest key (a pair's cell is below 1024 and the
+    // sort reads 10 bits of it: the sorted prefix is the same keys in the same order)
+    const size_t pair_len = counted ? std::min(Z.len_pairs, cap) : cap;
+    if (counted) RT_TRY(hipMemsetAsync(pairs_a, 0xff, sizeof(unsigned long long) * pair_len, st));
     if (n > 1) {
-        if (fp16) hipLaunchKernelGGL(k_pairs<half_t>, dim3(blocks_for((size_t)n - 1)), dim3(256), 0, st, d_geom, n, d_box, first, pairs_a, (unsigned)cap, C);
-        else hipLaunchKernelGGL(k_pairs<float>, dim3(blocks_for((size_t)n - 1)), dim3(256), 0, st, d_geom, n, d_box, first, pairs_a, (unsigned)cap, C);
+        if (fp16) hipLaunchKernelGGL(k_pairs<half_t>, dim3(blocks_for((size_t)n - 1)), dim3(256), 0, st, d_geom, n, d_box, first, pairs_a, (unsigned)pair_len, C);
+        else hipLaunchKernelGGL(k_pairs<float>, dim3(blocks_for((size_t)n - 1)), dim3(256), 0, st, d_geom, n, d_box, first, pairs_a, (unsigned)pair_len, C);
     }
-    RT_TRY(hipMemcpyAsync(&hc, C, sizeof(hc), hipMemcpyDeviceToHost, st));
-    RT_TRY(hipStreamSynchronize(st));                                   // (1) how many pairs to sort
-    if (hc.pair_overflow) return RT_ENOTSUP;
-    const unsigned n_pairs = hc.n_pairs;
-    if (n_pairs) {
-        if ((rc = sort_keys(pairs_a, pairs_b, n_pairs, 0, 32 + 10, tmp, sort_tmp, st))) return rc;
-        hipLaunchKernelGGL(k_segments, dim3(blocks_for(n_pairs)), dim3(256), 0, st, (const unsigned long long*)pairs_b, n_pairs, seg_start, seg_end);
+    unsigned n_pairs = 0;
+    if (!counted) {
+        RT_TRY(hipMemcpyAsync(&hc, C, sizeof(hc), hipMemcpyDeviceToHost, st));
+        RT_TRY(wait());                                                 // (1) how many pairs to sort
+        if (hc.pair_overflow) return RT_ENOTSUP;
+        n_pairs = Z.last_pairs = hc.n_pairs;
     }
-    // reference-layout arrays at their worst-case size (4097 leaves): part of the final allocation, sized below; until then in the workspace
+    const size_t sort_len = counted ? pair_len : n_pairs;
+    if (sort_len) {
+        if ((rc = sort_keys(pairs_a, pairs_b, sort_len, 0, 32 + 10, tmp, sort_tmp, st))) return rc;
+        if (counted) hipLaunchKernelGGL(k_segments<true>, dim3(blocks_for(sort_len)), dim3(256), 0, st, (const unsigned long long*)pairs_b, 0u, (const Counters*)C, seg_start, seg_end);
+        else hipLaunchKernelGGL(k_segments<false>, dim3(blocks_for(sort_len)), dim3(256), 0, st, (const unsigned long long*)pairs_b, n_pairs, (const Counters*)C, seg_start, seg_end);
+    }
+    // the leaf arrays' length: a fresh build sizes them by the count it reads back, which never exceeds the most a tree can have
+    const size_t leaf_len = counted ? std::min(Z.len_leaf, kMaxLeaves) : kMaxLeaves;
     hipLaunchKernelGGL(k_number, dim3(1), dim3(1024), 0, st, (const unsigned*)first, (const unsigned*)seg_start, (const unsigned*)seg_end, (const unsigned long long*)pairs_b, spl,
-                       node_id, dev_index, accepted, leaf_of, C);
-    RT_TRY(hipMemcpyAsync(&hc, C, sizeof(hc), hipMemcpyDeviceToHost, st));
-    RT_TRY(hipStreamSynchronize(st));                                   // (2) nodeCount, leafCount: sizes of the tree's arrays
-    const int node_count = (int)hc.node_count, leaf_count = (int)hc.leaf_count;
+                       (unsigned)leaf_len, node_id, dev_index, accepted, leaf_of, C);
+    int node_count = 0, leaf_count = 0;
+    if (!counted) {
+        RT_TRY(hipMemcpyAsync(&hc, C, sizeof(hc), hipMemcpyDeviceToHost, st));
+        RT_TRY(wait());                                                 // (2) nodeCount, leafCount: sizes of the tree's arrays
+        node_count = (int)hc.node_count; leaf_count = (int)hc.leaf_count;
+    }
     // ---- first part of the tree's own allocation: reference layout + traversal copy (entries bounded by the pairs)
-    const size_t ent_cap = n_pairs ? n_pairs : 1;
-    size_t a_bytes = sizeof(rt_octnode) * RT_OCTREE_MAX_NODES + sizeof(int32_t) * (size_t)leaf_count * (1 + (size_t)spl) + sizeof(DevNode) * (size_t)node_count
-                   + ent_cap * (16 + 4 + 4 + 8 + 8) + (size_t)n * (4 + 4 + 4) + 512 * 4 + (size_t)node_count * 4 + 64 * 256
-                   + (fp16 ? (ent_cap / 2 + (size_t)node_count + 1) * (16 + 8) + (size_t)node_count * 8 + 27 * 4 + 8 * 256 : 0);
-    void* a_mem = nullptr;
-    RT_TRY(hipMalloc(&a_mem, a_bytes));
-    Z.d_arena = a_mem;                                                  // owned by the handle from here on (rt_free_octree)
-    Arena A; A.base = (char*)a_mem; A.size = a_bytes;
+    const size_t ent_cap = sort_len ? sort_len : 1;
+    const size_t leaf_cap = counted ? leaf_len : (size_t)leaf_count, node_cap = counted ? (size_t)kFullNodes : (size_t)node_count;
+    if ((rc = M.get(&Z.d_arena, &Z.a_bytes, first_arena_bytes(n, spl, fp16, ent_cap, leaf_cap, node_cap)))) return rc;      // owned by the handle (rt_free_octree)
+    Arena A; A.base = (char*)Z.d_arena; A.size = Z.a_bytes;
     rt_octnode* ref_nodes = A.take<rt_octnode>(RT_OCTREE_MAX_NODES);
-    int32_t* leaf_cnt = A.take<int32_t>(leaf_count); int32_t* leaf_idx = A.take<int32_t>((size_t)leaf_count * spl);
-    DevNode* dnodes = A.take<DevNode>(node_count);
+    int32_t* leaf_cnt = A.take<int32_t>(leaf_cap); int32_t* leaf_idx = A.take<int32_t>(leaf_cap * spl);
+    DevNode* dnodes = A.take<DevNode>(node_cap);
     float4* ent_hot = A.take<float4>(ent_cap); int32_t* ent_id = A.take<int32_t>(ent_cap);
     int32_t* memb_cell = A.take<int32_t>(ent_cap); int32_t* memb_start = A.take<int32_t>((size_t)n + 1);
-    int32_t* bits_index = A.take<int32_t>(n); int32_t* cellnode = A.take<int32_t>(512); int32_t* devcell = A.take<int32_t>(node_count);
+    int32_t* bits_index = A.take<int32_t>(n); int32_t* cellnode = A.take<int32_t>(512); int32_t* devcell = A.take<int32_t>(node_cap);
     unsigned long long* pair2a = A.take<unsigned long long>(ent_cap); unsigned long long* pair2b = A.take<unsigned long long>(ent_cap);
-    int* dev_to_fr = A.take<int>(node_count);
-    const size_t pair_cap = ent_cap / 2 + (size_t)node_count + 1;       // binary16 only: every node may add a padding half-pair
+    int* dev_to_fr = A.take<int>(node_cap);
+    const size_t pair_cap = ent_cap / 2 + node_cap + 1;                 // binary16 only: every node may add a padding half-pair
     uint4* h_pairs = fp16 ? A.take<uint4>(pair_cap) : nullptr; int32_t* h_pid = fp16 ? A.take<int32_t>(2 * pair_cap) : nullptr;
-    int* pair_first = fp16 ? A.take<int>(node_count) : nullptr; float* d_planes = fp16 ? A.take<float>(27) : nullptr;
+    int* pair_first = fp16 ? A.take<int>(node_cap) : nullptr; float* d_planes = fp16 ? A.take<float>(27) : nullptr;
     if (A.used > A.size) return RT_ENOMEM;
     RT_TRY(hipMemsetAsync(ref_nodes, 0, sizeof(rt_octnode) * RT_OCTREE_MAX_NODES, st));
-    RT_TRY(hipMemsetAsync(leaf_cnt, 0, sizeof(int32_t) * (size_t)leaf_count, st));
-    RT_TRY(hipMemsetAsync(leaf_idx, 0, sizeof(int32_t) * (size_t)leaf_count * spl, st));
+    RT_TRY(hipMemsetAsync(leaf_cnt, 0, sizeof(int32_t) * leaf_cap, st));
+    RT_TRY(hipMemsetAsync(leaf_idx, 0, sizeof(int32_t) * leaf_cap * spl, st));
     RT_TRY(hipMemsetAsync(memb_start, 0, sizeof(int32_t) * ((size_t)n + 1), st));
+    if (counted && !fp16) RT_TRY(hipMemsetAsync(pair2a, 0xff, sizeof(unsigned long long) * ent_cap, st));      // the greatest key behind k_entries' (a sphere index is below n)
     hipLaunchKernelGGL(k_leaves, dim3(kFullNodes), dim3(64), 0, st, (const unsigned*)seg_start, (const int*)accepted, (const int*)leaf_of, (const unsigned long long*)pairs_b, d_kind, spl,
-                       leaf_cnt, leaf_idx, hit_cnt);
+                       leaf_cnt, leaf_idx, hit_cnt, (const Counters*)C);
     hipLaunchKernelGGL(k_nodes, dim3(1), dim3(1024), 0, st, d_box, (const int*)node_id, (const int*)dev_index, (const int*)accepted, (const int*)leaf_of, (const int*)hit_cnt, spl,
-                       ref_nodes, dnodes, ent_first, devcell, cellnode, dev_to_fr, C);
+                       ref_nodes, dnodes, ent_first, devcell, cellnode, dev_to_fr, (unsigned)ent_cap, C);
     if (fp16) hipLaunchKernelGGL(k_entries<half_t>, dim3(kFullNodes), dim3(64), 0, st, (const unsigned*)seg_start, (const int*)accepted, (const int*)dev_index, (const int*)ent_first,
-                                 (const unsigned long long*)pairs_b, d_geom, d_kind, ent_hot, ent_id, pair2a, hot_of);
+                                 (const unsigned long long*)pairs_b, d_geom, d_kind, ent_hot, ent_id, pair2a, hot_of, (const Counters*)C);
     else hipLaunchKernelGGL(k_entries<float>, dim3(kFullNodes), dim3(64), 0, st, (const unsigned*)seg_start, (const int*)accepted, (const int*)dev_index, (const int*)ent_first,
-                            (const unsigned long long*)pairs_b, d_geom, d_kind, ent_hot, ent_id, pair2a, hot_of);
+                            (const unsigned long long*)pairs_b, d_geom, d_kind, ent_hot, ent_id, pair2a, hot_of, (const Counters*)C);
+    // a counted run's first read-back: the counts as they are now known, or that one of them outgrew its array
+    auto counts_arrived = [&]() {
+        Z.last_pairs = hc.n_pairs;
+        if (hc.pair_overflow && hc.n_pairs > cap) return (int)RT_ENOTSUP;
+        if (hc.abort) return kOutgrown;
+        node_count = (int)hc.node_count; leaf_count = (int)hc.leaf_count;
+        return 0;
+    };
     if (fp16) {
         // the binary16 kernels' layout: pairs, pair-based node ranges, plane table; no candidate grid (its error bounds are binary32 bounds)
         float h_box[kFullNodes][6];
@@ -555,44 +643,53 @@ int build(rt_octree* O, const float4* d_geom, const int32_t* d_kind, int n, int 
             planes[9 * axis + 8] = h_box[0][3 + axis];
         }
         RT_TRY(hipMemcpyAsync(d_planes, planes, sizeof(planes), hipMemcpyHostToDevice, st));
-        hipLaunchKernelGGL(k_pair_offsets, dim3(1), dim3(64), 0, st, dnodes, node_count, (const int*)dev_to_fr, pair_first, C);
-        hipLaunchKernelGGL(k_pair_fill, dim3(node_count), dim3(64), 0, st, dnodes, (const int*)pair_first, (const float4*)ent_hot, (const int32_t*)ent_id, h_pairs, h_pid);
+        hipLaunchKernelGGL(k_pair_offsets, dim3(1), dim3(64), 0, st, dnodes, counted ? -1 : node_count, (const int*)dev_to_fr, pair_first, (unsigned)pair_cap, C);
+        hipLaunchKernelGGL(k_pair_fill, dim3(counted ? kFullNodes : node_count), dim3(64), 0, st, dnodes, (const int*)pair_first, (const float4*)ent_hot, (const int32_t*)ent_id, h_pairs, h_pid,
+                           counted ? -1 : node_count, (const Counters*)C);
         RT_TRY(hipMemcpyAsync(&hc, C, sizeof(hc), hipMemcpyDeviceToHost, st));
-        RT_TRY(hipStreamSynchronize(st));
+        RT_TRY(wait());
         RT_TRY(hipGetLastError());
+        if ((rc = counts_arrived())) return rc;
         if (hc.reg_total >= 2u << 23) return RT_ENOTSUP;               // as the host build: a pair index must fit the kernels' segment words
-        O->n_nodes = node_count; O->n_entries = (int)hc.n_entries; O->n_world = n;
+        O->n_nodes = node_count; O->n_entries = (int)hc.n_entries;
         Z.dev.n_nodes = node_count; Z.dev.n_entries = (int)hc.reg_total;
         Z.dev.nodes4 = (const float4*)dnodes; Z.dev.ent_hot = (const float4*)h_pairs; Z.dev.ent_id = h_pid;
         Z.dev.h16_planes = d_planes; Z.dev.h16_np[0] = Z.dev.h16_np[1] = Z.dev.h16_np[2] = 9;
         Z.d_ref_nodes = ref_nodes; Z.d_leaf_count = leaf_cnt; Z.d_leaf_indices = leaf_idx;
         Z.ref_node_count = node_count; Z.ref_leaf_count = leaf_count; Z.ref_dropped_full = (int)hc.dropped_full; Z.ref_dropped_outside = (int)hc.dropped_outside; Z.ref_spl = spl;
-        DevAccel off{}; O->accel.p = off; O->accel.n_entries = 0; Z.dev.acc = off;
+        DevAccel off{}; Z.dev.acc = off;
         Z.uploaded = true;
         return 0;
     }
-    RT_TRY(hipMemcpyAsync(&hc, C, sizeof(hc), hipMemcpyDeviceToHost, st));
-    RT_TRY(hipStreamSynchronize(st));                                   // (3) number of bucket entries
-    const int n_entries = (int)hc.n_entries;
+    int n_entries = 0;
+    if (!counted) {
+        RT_TRY(hipMemcpyAsync(&hc, C, sizeof(hc), hipMemcpyDeviceToHost, st));
+        RT_TRY(wait());                                                 // (3) number of bucket entries
+        n_entries = (int)hc.n_entries;
+    }
     // ---- memberships, bricks, bitmaps, median radius
-    if (n_entries) {
-        if ((rc = sort_keys(pair2a, pair2b, (size_t)n_entries, 0, 32 + bits_for((unsigned long long)n), tmp, sort_tmp, st))) return rc;
-        hipLaunchKernelGGL(k_memb, dim3(blocks_for((size_t)n_entries)), dim3(256), 0, st, (const unsigned long long*)pair2b, n_entries, n, memb_cell, memb_start);
+    const size_t memb_len = counted ? ent_cap : (size_t)n_entries;
+    if (memb_len) {
+        if ((rc = sort_keys(pair2a, pair2b, memb_len, 0, 32 + bits_for((unsigned long long)n), tmp, sort_tmp, st))) return rc;
+        if (counted) hipLaunchKernelGGL(k_memb<true>, dim3(blocks_for(memb_len)), dim3(256), 0, st, (const unsigned long long*)pair2b, 0, (const Counters*)C, n, memb_cell, memb_start);
+        else hipLaunchKernelGGL(k_memb<false>, dim3(blocks_for(memb_len)), dim3(256), 0, st, (const unsigned long long*)pair2b, n_entries, (const Counters*)C, n, memb_cell, memb_start);
     }
     hipLaunchKernelGGL(k_bricks, dim3(blocks_for((size_t)n)), dim3(256), 0, st, n, (const int32_t*)memb_start, (const int32_t*)memb_cell, (const int32_t*)devcell, (const float4*)hot_of,
                        sb_lo, sb_hi, multi, r2a, C);
     if ((rc = excl_scan(multi, row_of, (size_t)n, tmp, sort_tmp, st))) return rc;
     if ((rc = sort_keys(r2a, r2b, (size_t)n, 0, 32, tmp, sort_tmp, st))) return rc;
+    hipLaunchKernelGGL(k_median, dim3(1), dim3(64), 0, st, (const unsigned*)r2b, (const int*)multi, (const int*)row_of, n, C);
     RT_TRY(hipMemcpyAsync(&hc, C, sizeof(hc), hipMemcpyDeviceToHost, st));
-    int last_multi = 0, last_row = 0;
-    RT_TRY(hipMemcpyAsync(&last_multi, multi + (n - 1), sizeof(int), hipMemcpyDeviceToHost, st));
-    RT_TRY(hipMemcpyAsync(&last_row, row_of + (n - 1), sizeof(int), hipMemcpyDeviceToHost, st));
-    RT_TRY(hipStreamSynchronize(st));                                   // (4a) tree spheres, bitmap rows
+    RT_TRY(wait());                                                     // (4) tree spheres, bitmap rows, the median radius
+    if (counted) {
+        if ((rc = counts_arrived())) return rc;
+        n_entries = (int)hc.n_entries;
+    }
     const unsigned in_tree = hc.in_tree;
-    const int bit_rows = last_row + last_multi;
+    const int bit_rows = (int)hc.bit_rows;
     AccelHost& AH = O->accel;
     DevAccel p{};
-    O->n_nodes = node_count; O->n_entries = n_entries; O->n_world = n; O->bit_rows = std::max(1, bit_rows);
+    O->n_nodes = node_count; O->n_entries = n_entries; O->bit_rows = std::max(1, bit_rows);
     Z.dev.n_nodes = node_count; Z.dev.n_entries = n_entries;
     Z.dev.nodes4 = (const float4*)dnodes; Z.dev.ent_hot = ent_hot; Z.dev.ent_id = ent_id;
     Z.d_ref_nodes = ref_nodes; Z.d_leaf_count = leaf_cnt; Z.d_leaf_indices = leaf_idx;
@@ -602,9 +699,7 @@ int build(rt_octree* O, const float4* d_geom, const int32_t* d_kind, int n, int 
         AH.p = p; AH.n_entries = 0; Z.dev.acc = p; Z.uploaded = true;
         return 0;
     }
-    unsigned median_bits = 0;
-    RT_TRY(hipMemcpy(&median_bits, r2b + in_tree / 2, sizeof(unsigned), hipMemcpyDeviceToHost));     // (4b) radii[size / 2] of the sorted radii
-    float med_r2; memcpy(&med_r2, &median_bits, 4);
+    float med_r2; memcpy(&med_r2, &hc.median_bits, 4);
     // ---- cell size and extent, as build_accel (rt_accel.h step 2)
     const double rmed = std::sqrt((double)med_r2);
     double h = 2.0 * accel_Rp(rmed * rmed);
@@ -627,16 +722,16 @@ int build(rt_octree* O, const float4* d_geom, const int32_t* d_kind, int n, int 
     RT_TRY(hipMemcpyAsync(&tail[4], nreg_z + (n - 1), sizeof(int), hipMemcpyDeviceToHost, st));
     RT_TRY(hipMemcpyAsync(&tail[5], off_z + (n - 1), sizeof(int), hipMemcpyDeviceToHost, st));
     RT_TRY(hipMemcpyAsync(&hc, C, sizeof(hc), hipMemcpyDeviceToHost, st));
-    RT_TRY(hipStreamSynchronize(st));                                   // (5) registrations, large spheres, y-slab
+    RT_TRY(wait());                                                     // (5) registrations, large spheres, y-slab
     const int n_large = tail[0] + tail[1];
     const size_t nx = (size_t)tail[2] + (size_t)tail[3], nz = (size_t)tail[4] + (size_t)tail[5], total = nx + nz;
     const size_t ncell = (size_t)G * G, nbin = (size_t)G * Gf;
     // ---- second part of the tree's allocation: the grid
     const size_t b_bytes = (total + 16) * (16 + 32) + 2 * (nbin + 1) * 4 + (size_t)std::max(1, n_large) * (16 + 32) + (size_t)std::max(1, bit_rows) * 64 + (std::max<size_t>(nx, 1) + std::max<size_t>(nz, 1)) * 8 + 32 * 256;
-    void* b_mem = nullptr;
-    RT_TRY(hipMalloc(&b_mem, b_bytes));
-    Z.d_acc[7] = b_mem;                                                 // freed with the other accel buffers
-    Arena B; B.base = (char*)b_mem; B.size = b_bytes;
+    M.slack = counted; M.enlarged = false;                              // (a rebuild that has to enlarge the grid's piece leaves room for the next)
+    if ((rc = M.get(&Z.d_acc[7], &Z.b_bytes, b_bytes))) return rc;      // freed with the other accel buffers
+    if (grid_enlarged) *grid_enlarged = M.enlarged;
+    Arena B; B.base = (char*)Z.d_acc[7]; B.size = Z.b_bytes;
     float4* g_hot = B.take<float4>(total + 16); float4* g_brick = B.take<float4>(2 * total + 32);
     int32_t* cs = B.take<int32_t>(2 * (nbin + 1));
     float4* large_hot = B.take<float4>(std::max(1, n_large)); float4* large_brick = B.take<float4>(2 * (size_t)std::max(1, n_large));
@@ -662,7 +757,7 @@ int build(rt_octree* O, const float4* d_geom, const int32_t* d_kind, int n, int 
     if (n_large) hipLaunchKernelGGL(k_large, dim3(blocks_for((size_t)n)), dim3(256), 0, st, n, (const int*)is_large, (const int*)large_off, (const float4*)hot_of,
                                     (const float4*)sb_lo, (const float4*)sb_hi, large_hot, large_brick);
     RT_TRY(hipGetLastError());
-    RT_TRY(hipStreamSynchronize(st));                                   // the workspace is freed on return
+    RT_TRY(wait());                                                     // ready to render when the call returns
     // ---- parameters, as build_accel
     p.large_hot = large_hot; p.large_brick = large_brick; p.cs = cs; p.hot = g_hot; p.brick = g_brick;
     p.zoff = (int32_t)(nbin + 1);
@@ -680,6 +775,36 @@ int build(rt_octree* O, const float4* d_geom, const int32_t* d_kind, int n, int 
     Z.dev.acc = p;
     Z.uploaded = true;
     return 0;
+}
+
+// rt_octree_rebuild_gpu's device part: build() once more into the pieces O holds.  The first rebuild of a fresh build lays the first arena
+// out for the last build's pairs and leaf buckets plus a quarter and gives the grid's piece the same slack; after that a run with
+// capacities that suffice allocates and frees nothing.  A run that finds a count above its length (kOutgrown) is run once more, from
+// the start, with lengths that cannot fail: the pairs it counted plus a quarter, bucket entries bounded by the pairs, leaf buckets
+// bounded by the pairs and by the most a tree can have.  *regrown: a piece was too small, or the run had to be repeated.
+int rebuild(rt_octree* O, const float4* d_geom, const int32_t* d_kind, int n, int spl, hipStream_t st, bool* regrown) {
+    rt_octree::Lazy& Z = *O->z;
+    *regrown = false;
+    if (!Z.d_ws) return build(O, d_geom, d_kind, n, spl, st, false, nullptr);      // nothing kept (the last build was the host's): as a fresh build
+    const size_t cap = pair_capacity(n);
+    if (!Z.len_pairs) {
+        Z.len_pairs = std::min(cap, with_a_quarter(Z.last_pairs, 64));
+        Z.len_leaf = std::min(kMaxLeaves, with_a_quarter((size_t)std::max(1, Z.ref_leaf_count), 8));
+        if (Z.d_acc[7]) { Mem M; const int rc = M.get(&Z.d_acc[7], &Z.b_bytes, Z.b_bytes + Z.b_bytes / 4); if (rc) return rc; }
+    }
+    bool grid_enlarged = false;
+    int rc = build(O, d_geom, d_kind, n, spl, st, true, &grid_enlarged);
+    if (rc == kOutgrown) {
+        const uint64_t syncs = Z.syncs_last;
+        Z.len_pairs = std::min(cap, with_a_quarter(Z.last_pairs, 64));
+        Z.len_leaf = std::min(kMaxLeaves, Z.len_pairs + 1);
+        *regrown = true;
+        rc = build(O, d_geom, d_kind, n, spl, st, true, &grid_enlarged);
+        Z.syncs_last += syncs;
+        if (rc == kOutgrown) rc = RT_ENOMEM;                           // the same geometry within bounds that hold for any: a bug, not a retry
+    }
+    if (grid_enlarged) *regrown = true;
+    return rc;
 }
 
 }  // namespace gpubuild

@@ -21,12 +21,12 @@ struct rt_octree;
 // Whatever grows, uploads or frees device buffers goes through the three functions below.
 struct DevBuf { void** at; size_t bytes; const void* src; size_t src_bytes; };      // bytes == 0: freed with the group, allocated elsewhere
 struct DevGroup {
-    int n = 0; DevBuf b[16];          // (16: the largest group, a tree's)
-    DevGroup& add(void* at, size_t bytes) { assert(n < 16); b[n++] = DevBuf{(void**)at, bytes, nullptr, 0}; return *this; }      // at: the address of the (typed) pointer
+    int n = 0; DevBuf b[17];          // (17: the largest group, a tree's)
+    DevGroup& add(void* at, size_t bytes) { assert(n < 17); b[n++] = DevBuf{(void**)at, bytes, nullptr, 0}; return *this; }      // at: the address of the (typed) pointer
     // a copy of a host vector; an empty one still gets a buffer (of one element), so no kernel argument is ever null
     template <class V> DevGroup& add_copy(void* at, const V& v) {
         const size_t sz = sizeof(typename V::value_type);
-        assert(n < 16);
+        assert(n < 17);
         b[n++] = DevBuf{(void**)at, (v.empty() ? 1 : v.size()) * sz, v.empty() ? nullptr : v.data(), v.size() * sz};
         return *this;
     }
@@ -141,10 +141,20 @@ struct rt_octree {
         const rt_octnode* d_ref_nodes = nullptr; const int32_t* d_leaf_count = nullptr; const int32_t* d_leaf_indices = nullptr;
         int ref_node_count = 0, ref_leaf_count = 0, ref_dropped_full = 0, ref_dropped_outside = 0, ref_spl = 0;
         Octree* host_view = nullptr;            // ... downloaded here when an inspection call first asks for it
+        // what the device build keeps for rt_octree_rebuild_gpu (rt_build.hip "memory kept in the handle"): its workspace, the bytes of
+        // the workspace and of the two allocations above (d_arena, d_acc[7]), and the lengths the count-dependent arrays of d_arena are
+        // laid out for — (cell, sphere) pairs (bucket entries are bounded by them) and leaf buckets.  len_pairs == 0: the arena holds a
+        // fresh build's exact sizes; the first rebuild lays it out anew with a quarter of slack.
+        void* d_ws = nullptr;
+        size_t ws_bytes = 0, a_bytes = 0, b_bytes = 0;
+        size_t len_pairs = 0, len_leaf = 0;
+        unsigned last_pairs = 0;                // the pairs the last device build counted
+        uint64_t rebuilds = 0, regrown = 0, syncs_last = 0;      // rt_octree_rebuild_info
     };
     Lazy* z = nullptr;
     int n_nodes = 0, n_entries = 0;
     int n_world = 0, bit_rows = 1;          // world list size, rows of the membership bitmaps (>= 1)
+    int spl = 0;                            // SPHERES_PER_LEAF the tree was built with (rt_octree_rebuild_gpu builds with it again)
 };
 
 

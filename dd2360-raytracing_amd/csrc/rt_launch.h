@@ -78,7 +78,10 @@ hipError_t read_h16_stats(unsigned long long* out, int reset);
 #endif
 
 // ---- rt_build.hip
-namespace gpubuild { int build(rt_octree* O, const float4* d_geom, const int32_t* d_kind, int n, int spl, hipStream_t st); }
+namespace gpubuild {
+int build(rt_octree* O, const float4* d_geom, const int32_t* d_kind, int n, int spl, hipStream_t st, bool counted, bool* grid_enlarged);
+int rebuild(rt_octree* O, const float4* d_geom, const int32_t* d_kind, int n, int spl, hipStream_t st, bool* regrown);
+}
 
 // ---- rt_denoise.hip
 hipError_t launch_denoise(float* fb_out, const float* fb_in, int max_x, int max_y, const rt_hit_record* hits, const rt_denoise_params& P,

@@ -24,6 +24,10 @@
 //   levels sigma_variance   rt_denoise_var_params (progressive: the levels of rt_denoise); levels=0 shows the unfiltered fb
 //   passes every    progressive: passes in all; every `every`-th pass and the last one are shown       (10 1)
 //   out             file prefix: <out>%04d.ppm, binary P6; out=none writes nothing                      (frame_ | pass_)
+//   tree            animation: build = every frame of moved spheres synchronises, frees the tree and calls rt_build_octree_gpu;
+//                   rebuild = frame 0 builds, every later one calls rt_octree_rebuild_gpu on the same handle: no free, and no
+//                   synchronisation before the stage (the rebuild is ordered on the loop's stream, where every reader of the old
+//                   tree was enqueued).  The frames are the same byte for byte                         (build)
 //   timing          animation, 1: a table of the stages' device times and the wall time a frame, frame 0 left out (0)
 //   upscale         1: the frame is shown as it is rendered.  2..4: samples, history and filter run at nx x ny, the shown frame of
 //                   upscale*nx x upscale*ny pixels is rebuilt from it and first-hit guides of both sizes (rt_sequence_upscale.hpp,
@@ -88,7 +92,7 @@ __global__ __launch_bounds__(256) void k_upscale(float* out, const float* c, con
 namespace {
 
 struct Options {
-    std::string mode = "animation", out;
+    std::string mode = "animation", out, tree = "build";
     int n = 500, nx = 64, ny = 40, spl = 30, frames = 4;
     float radius = 0.1f;
     int min_spp = 4, max_spp = 8, batch = 4;
@@ -139,6 +143,7 @@ Options parse(int argc, char** argv) {
 #define KEY(name, field) if (key == name) { parse_value(key, v, &(field)); continue; }
         if (key == "mode") { o.mode = v; continue; }
         if (key == "out") { o.out = v; o.out_given = true; continue; }
+        if (key == "tree") { o.tree = v; continue; }
         KEY("n", o.n) KEY("nx", o.nx) KEY("ny", o.ny) KEY("spl", o.spl) KEY("radius", o.radius) KEY("frames", o.frames)
         KEY("min_spp", o.min_spp) KEY("max_spp", o.max_spp) KEY("batch", o.batch) KEY("rel_error", o.rel_error) KEY("floor", o.floor)
         KEY("budget", o.budget) KEY("rounds", o.rounds) KEY("budget_max_spp", o.budget_max_spp)
@@ -158,6 +163,8 @@ Options parse(int argc, char** argv) {
 void validate(Options& o) {
     const bool progressive = o.mode == "progressive";
     if (!progressive && o.mode != "animation") refuse("mode", "'" + o.mode + "' is neither animation nor progressive");
+    if (o.tree != "build" && o.tree != "rebuild") refuse("tree", "'" + o.tree + "' is neither build nor rebuild");
+    if (progressive && o.tree != "build") refuse("tree", "nothing moves in mode=progressive: the tree is built once");
     if (o.fp16 != 0) refuse("fp16", "binary16 is not offered: the calls of the loop are fp32 only");
     if (o.n < 1 || o.n >= INT32_MAX - 256) refuse("n", "needs 1 .. 2^31 - 257 spheres");
     if (o.nx < 1) refuse("nx", "needs a positive size");
@@ -364,10 +371,14 @@ int run_animation(const Options& o) {
         // 2. the tree of this geometry; the old one may still be read by the last frame's launches
         mark(TREE, 0);
         if (f == 0 || spheres_move) {
-            checkHipErrors(hipStreamSynchronize(stream));
-            checkHipErrors(rt_free_octree(tree));
-            tree = nullptr;
-            checkHipErrors(rt_build_octree_gpu(world, o.spl, &tree, stream));
+            if (f > 0 && o.tree == "rebuild") {
+                checkHipErrors(rt_octree_rebuild_gpu(tree, world, stream));     // every launch that reads the old tree is on this stream
+            } else {
+                checkHipErrors(hipStreamSynchronize(stream));
+                checkHipErrors(rt_free_octree(tree));
+                tree = nullptr;
+                checkHipErrors(rt_build_octree_gpu(world, o.spl, &tree, stream));
+            }
             report_drops(tree);
             if (o.timing && rt_octree_build_path(tree) != RT_BUILD_DEVICE)
                 std::cerr << "timing: frame " << f << ": the device build declined this geometry, the tree was built on the host\n";

@@ -291,6 +291,13 @@ SYMBOLS = {
 _LIB = None
 
 
+# every symbol include/rt_amd_rebuild.h declares (the header rt_amd.h includes at its end): (restype, argtypes)
+SYMBOLS_REBUILD = {
+    "rt_octree_rebuild_gpu": (_i, [_vp, _vp, _vp]),
+    "rt_octree_rebuild_info": (_i, [_vp, _vp, _vp, _vp]),
+}
+
+
 def lib():
     """Load librt_amd.so.  Raises RtError when it is missing or does not export the whole ABI (no fallback)."""
     global _LIB
@@ -308,7 +315,7 @@ def lib():
             L = C.CDLL(LIB_PATH)
         except OSError as e:
             raise RtError("cannot load %s: %s" % (LIB_PATH, e))
-        for name, (res, args) in SYMBOLS.items():
+        for name, (res, args) in list(SYMBOLS.items()) + list(SYMBOLS_REBUILD.items()):
             try:
                 fn = getattr(L, name)
             except AttributeError:
@@ -707,7 +714,8 @@ class World(_Scheduled):
 
     def set_geometry(self, d_geom):
         """rt_world_set_geometry on the current stream: d_geom is a float32 device tensor of num_spheres x 4 (cx, cy, cz, radius) in
-        world-list order.  Octrees built before the call describe the old geometry: build them again (Octree(world, spl, gpu=True))"""
+        world-list order.  Octrees built before the call describe the old geometry: build them again (Octree(world, spl, gpu=True), or
+        octree.rebuild() in place)"""
         _call("rt_world_set_geometry", self.h, _dev(d_geom), _stream())
         self._spheres_stale = True
         return self
@@ -778,6 +786,19 @@ class Octree(_Handle):
     def build_path(self):
         """rt_octree_build_path: BUILD_HOST, BUILD_DEVICE or BUILD_HOST_DECLINED (gpu=True, but the device build declined the input)"""
         return _size("rt_octree_build_path", self.h)
+
+    def rebuild(self, world=None):
+        """rt_octree_rebuild_gpu on the current stream: the tree of the world's current device geometry (after set_geometry) in this
+        handle, which a gpu=True build made; everything observable equals a fresh Octree(world, spl, gpu=True)"""
+        _call("rt_octree_rebuild_gpu", self.h, _h(self.world if world is None else world), _stream())
+        return self
+
+    def rebuild_info(self):
+        """rt_octree_rebuild_info: rebuilds that succeeded, how many of them had to enlarge the kept memory or run twice, and the
+        host-blocking waits of the last one"""
+        v = [C.c_uint64(0) for _ in range(3)]
+        _call("rt_octree_rebuild_info", self.h, *[C.byref(x) for x in v])
+        return dict(zip(("rebuilds", "regrown", "host_syncs_last"), (x.value for x in v)))
 
     def set_traversal(self, mode):
         """TRAVERSAL_REFERENCE (exact bucket scan) or TRAVERSAL_FAST (default, culling grid + fallback)"""

@@ -177,7 +177,8 @@ int rt_world_list_accel_info(const rt_world* world, int* enabled, int* grid_dim,
  *   - the world's list grid (rt_world_set_list_traversal): freed; the next launch without an octree builds another ON THE HOST.  The
  *     list path of a moved world pays that build per move: the animated path is the octree path, rt_build_octree_gpu per frame;
  *   - octrees built from the world before the call: they describe the old geometry, and rendering through one is undefined, as through
- *     the tree of another world.  Free them and call rt_build_octree_gpu(world, ...) again;
+ *     the tree of another world.  Free them and call rt_build_octree_gpu(world, ...) again, or rebuild one in place with
+ *     rt_octree_rebuild_gpu, see rt_amd_rebuild.h;
  *   - kept schedules, progressive tile orders and cached splits miss once, as after rt_world_set_camera.
  * rt_world_get_geometry copies the same layout out, device to device, asynchronously on `stream` (uploads the world if need be): a
  * viewer keeps last frame's geometry with it for rt_temporal_accumulate_moving.  RT_EINVAL for NULL or a misaligned d_geom. */
@@ -207,6 +208,8 @@ int rt_build_octree_gpu(const rt_world* world, int spheres_per_leaf, rt_octree**
 #define RT_BUILD_DEVICE 1          /* rt_build_octree_gpu, on the device */
 #define RT_BUILD_HOST_DECLINED 2   /* rt_build_octree_gpu, on the host after the device build declined */
 int rt_octree_build_path(const rt_octree* octree);
+/* Rebuilding such a tree in place for a moved world, frame after frame (rt_octree_rebuild_gpu and rt_octree_rebuild_info), is declared
+ * in rt_amd_rebuild.h, which this header includes at its end. */
 /* one device-resident array of a tree, copied to the host (parity checks of the two builds; binary16 trees: 0-2 only): 0 traversal nodes, 1 bucket
  * entries (c, r^2), 2 entry -> sphere, 3/4 large spheres + bricks, 5 strip bin starts (columns x fine bins; the x copy, then the z copy), 6/7 strip entries + bricks, 8/9 membership
  * lists, 10 cell -> node, 11/12 membership bitmaps.  *bytes = size of the array; copied when cap suffices. */
@@ -932,4 +935,5 @@ int rt_write_image(const char* path, int nx, int ny, const void* fb, int precisi
 #ifdef __cplusplus
 }
 #endif
+#include "rt_amd_rebuild.h"   /* part of this ABI: the declarations that follow the ones above, in a file of their own */
 #endif /* RT_AMD_H */
