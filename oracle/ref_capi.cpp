@@ -4,7 +4,7 @@
 //
 // Everything numeric below happens inside the reference's functions: the constructors sphere / lambertian / metal / dielectric /
 // camera, buildOctree, hitable_list::hit, hitTree, material::scatter, camera::get_ray.  This file only moves floats in and out.
-// Nothing of main.cu is restated (no color, render or create_world): main.cu needs nvcc and is not built.
+// Nothing of main.cu is restated (no color, render or create_world); its own text is built by ref_main_capi.cpp.
 // The build defines USE_FP16 or not, and puts a generated copy of acceleration_structure.h, in which only the SPHERES_PER_LEAF
 // line differs, first on the include path (that header has a hard #define).
 //

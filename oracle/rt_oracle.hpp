@@ -5,12 +5,14 @@
 // and bench.py's cpu_baseline leg as the checker / baseline.  Nothing in the
 // product path (dd2360-raytracing_amd/) may include, link or call this.
 //
-// PARITY STATUS: pinned to a CPU build of the reference's own headers, unpinned against a CUDA build.  The reference ships no
-// tests, golden images or known-answer vectors, and main.cu needs nvcc.  Its headers compile unmodified as host C++ behind the
-// stand-ins of oracle/ref_shim/ (`make ref`, oracle/ref_capi.cpp): tests/test_reference_pins_host.py holds buildOctree, both
-// closest-hit searches, one-bounce scatter, get_ray and the fp32 camera constructor of this file to that build bit for bit, and
-// tests/golden/reference_*.npz keep its recorded results.  What that build does not reach — cuRAND's constants, device libm,
-// FMA contraction, fp16 device intrinsics, the loops of main.cu (color, render, create_world below) — rests on
+// PARITY STATUS: pinned to a CPU build of the reference's own text, unpinned against a CUDA build.  The reference ships no
+// tests, golden images or known-answer vectors, and main() needs nvcc.  Its headers, and main.cu above `int main(`, compile
+// unmodified as host C++ behind the stand-ins of oracle/ref_shim/ (`make ref`, oracle/ref_capi.cpp, oracle/ref_main_capi.cpp):
+// tests/test_reference_pins_host.py holds buildOctree, both closest-hit searches, one-bounce scatter, get_ray and the fp32 camera
+// constructor of this file to that build bit for bit, tests/test_reference_main_host.py holds create_world, render_init, render,
+// render_progressive, color and the PPM writer below to it, and tests/golden/reference_*.npz keep its recorded results.  What that
+// build does not reach — cuRAND's constants, device libm, FMA contraction, fp16 device intrinsics (so the device branch of the
+// binary16 camera), main()'s own host sequence and the window loop — rests on
 //   (i)  reading the reference sources (every function cites file:line), and
 //   (ii) the probe values recorded in SURVEY.md §8c / App. A (XORWOW KATs, world counts, octree node/leaf counts, camera
 //        half_height bits, C1 PPM md5), which tests/test_oracle_pins.py checks.
@@ -146,7 +148,7 @@ static inline float uniform(Xorwow& s) {
 }
 
 // draw counter (diagnostics for world generation; SURVEY §8c pins)
-struct Counters { uint64_t rays = 0, sphere_tests = 0, slab_tests = 0, bucket_visits = 0, draws = 0, samples = 0; };
+struct Counters { uint64_t rays = 0, sphere_tests = 0, slab_tests = 0, bucket_visits = 0, draws = 0, samples = 0, scatters[3] = {0, 0, 0}; };   // scatters: calls of material::scatter by kind
 
 // ---------------------------------------------------------------- vec3 / ray  (vec3.h, ray.h)
 template <class R> struct V3 { R e[3]; };
@@ -521,6 +523,7 @@ template <class R> static V3<R> color(const World<R>& W, Ray<R> cur, Xorwow& s, 
         Hit<R> rec;
         if (closest_hit(W, cur, rec, C)) {
             Ray<R> sc; V3<R> a;
+            if (C && W.list[rec.sphere].kind >= 0 && W.list[rec.sphere].kind < 3) C->scatters[W.list[rec.sphere].kind]++;
             if (scatter(W.list[rec.sphere], cur, rec, a, sc, s)) { att = mulv(att, a); cur = sc; }
             else return black;
         } else {

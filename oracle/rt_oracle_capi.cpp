@@ -228,6 +228,23 @@ void orc_render(orc_scene* s, float* fb, int max_x, int max_y, int ns, void* sta
     });
 }
 
+// what render() of the rows [row0, row0 + rows) from fresh render_init states walks through; the frame is thrown away.
+// out (3 x u64): the calls of material::scatter on a lambertian, a metal, a dielectric.  A check on a test's inputs, not a result.
+void orc_count_scatters(orc_scene* s, int max_x, int max_y, int ns, int row0, int rows, uint64_t* out) {
+    with_world(s, [&](auto& W) {
+        using R = decltype(W.cam.lens_radius);
+        Counters c;
+        for (int j = row0; j < row0 + rows; ++j)
+            for (int i = 0; i < max_x; ++i) {
+                Xorwow st;
+                xorwow_init(st, 1984ull + (uint64_t)(j * max_x + i));
+                render_pixel<R>(W, i, j, max_x, max_y, ns, st, &c);
+            }
+        for (int k = 0; k < 3; ++k) out[k] = c.scatters[k];
+        return 0;
+    });
+}
+
 // render_progressive (main.cu:119-142): one sample; fb = col if current_sample == 1 else fb += col (real_t adds).
 void orc_render_progressive(orc_scene* s, float* fb, int max_x, int max_y, int current_sample, void* states, int nthreads) {
     with_world(s, [&](auto& W) {

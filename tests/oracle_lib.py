@@ -43,6 +43,7 @@ def lib():
         L.orc_make_camera.argtypes = [C.c_int, C.c_void_p, C.c_void_p]
         L.orc_render_init.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p]
         L.orc_render.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p]
+        L.orc_count_scatters.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p]
         L.orc_render_progressive.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int]
         L.orc_ppm.restype = C.c_int64
         L.orc_ppm.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int64]
@@ -165,6 +166,12 @@ class OracleScene:
             keys = ["rays", "sphere_tests", "slab_tests", "bucket_visits", "draws", "samples"]
             return fb, states, dict(zip(keys, cnt.tolist()))
         return fb, states
+
+    def count_scatters(self, ns, row0=0, rows=None):
+        """the calls of material::scatter, by kind, that render(ns) of those rows makes from fresh states: a check on a test's inputs"""
+        out = np.zeros(3, np.uint64)
+        self.L.orc_count_scatters(self.h, self.nx, self.ny, ns, row0, self.ny if rows is None else rows, _p(out))
+        return dict(zip(("lambertian", "metal", "dielectric"), out.tolist()))
 
     def render_progressive(self, fb, current_sample, states, nthreads=1):
         self.L.orc_render_progressive(self.h, _p(fb), self.nx, self.ny, current_sample, _p(states), nthreads)

@@ -1,4 +1,8 @@
-"""ctypes binding of the libraries that `make -C oracle ref` builds from the REFERENCE's own headers (oracle/ref_capi.cpp, oracle/_ref/).
+"""ctypes binding of the libraries that `make -C oracle ref` builds from the REFERENCE's own text (oracle/_ref/): libref_* from its nine
+headers (oracle/ref_capi.cpp) and libmain_* from main.cu's text above `int main(` (oracle/ref_main_capi.cpp: create_world, render_init,
+render, render_progressive, output_to_stream), one main library per case of MAIN_RENDER and MAIN_WORLD.
+
+Not reached by either: main() itself and the window loop, whose <<<>>> launches do not parse as C++.
 
 Test infrastructure only.  The libraries exist where the reference's sources were at build time; on a clean checkout without them
 `status()` says so and the live comparisons skip — the recorded fixtures under tests/golden/ (make_reference_golden.py) still hold."""
@@ -13,6 +17,15 @@ from oracle_lib import ORACLE_DIR
 REF_DIR = os.path.join(ORACLE_DIR, "_ref")
 SPLS = (3, 4, 30, 32, 40, 64)
 _LIBS = {}
+# the main cases of oracle/Makefile: (fp16, NUM_SPHERES, SPHERE_RADIUS as written, USE_OCTREE, SPHERES_PER_LEAF or "own": the header's)
+MAIN_RENDER = tuple((f, n, "0.1", o, s) for f, n, o, s in (
+    (False, 8000, True, "own"), (False, 1000, True, 30), (False, 1000, False, 30), (False, 5, True, 30), (False, 5, False, 30),
+    (False, 22, True, 30), (False, 22, False, 30), (False, 500, True, 30), (False, 500, False, 30), (False, 10000, True, 32),
+    (False, 2000, True, 3), (True, 22, True, 30), (True, 22, False, 30), (True, 500, True, 30), (True, 500, False, 30)))
+MAIN_WORLD = ((False, 500, "0.2", True, 30), (True, 5, "0.1", True, 30), (True, 8000, "0.1", True, "own"), (True, 10000, "0.1", True, 32),
+              (True, 500, "0.2", True, 30))
+OWN_SPL = 30                         # acceleration_structure.h:15 as shipped; build_info reports it
+_MAIN = {}
 
 
 def source_dir():
@@ -27,9 +40,15 @@ def lib_path(fp16, spl):
     return os.path.join(REF_DIR, "libref_%s_spl%d.so" % ("fp16" if fp16 else "fp32", spl))
 
 
+def main_path(case, opt=2):
+    fp16, n, radius, octree, spl = case
+    return os.path.join(REF_DIR, "libmain_%s_n%d_r%s_oct%d_spl%s_O%d.so" % ("fp16" if fp16 else "fp32", n, radius, int(octree), spl, opt))
+
+
 def status():
     """'ok', 'absent' (neither libraries nor sources: nothing to compare with) or 'unbuilt' (sources without all libraries: an error)"""
     have = [os.path.exists(lib_path(f, s)) for f in (False, True) for s in SPLS]
+    have += [os.path.exists(main_path(c)) for c in MAIN_RENDER + MAIN_WORLD] + [os.path.exists(main_path(c, 0)) for c in MAIN_RENDER]
     if all(have):
         return "ok"
     if not any(have) and not os.path.isdir(REF_DIR) and not os.path.exists(os.path.join(source_dir(), "acceleration_structure.h")):
@@ -159,3 +178,123 @@ def curand_uniform(states, fp16=False):
     out = np.zeros(st.shape[0], np.float32)
     lib(fp16).ref_curand_uniform(st.shape[0], _p(st), _p(out))
     return out, st
+
+
+def main_case(n, fp16=False, octree=True, spl=30, radius="0.1"):
+    """the case of MAIN_RENDER / MAIN_WORLD with these parameters; there is exactly one"""
+    got = [c for c in MAIN_RENDER + MAIN_WORLD if c[:4] == (bool(fp16), n, radius, bool(octree)) and (c[4] == spl or (c[4] == "own" and spl == OWN_SPL))]
+    assert len(got) == 1, (n, fp16, octree, spl, radius, got)
+    return got[0]
+
+
+def main_lib(case, opt=2):
+    key = (case, opt)
+    if key not in _MAIN:
+        L = C.CDLL(main_path(case, opt))
+        L.refmain_build_info.argtypes = [C.c_void_p, C.c_void_p]
+        L.refmain_create.restype = C.c_void_p
+        L.refmain_create.argtypes = [C.c_int, C.c_int]
+        L.refmain_destroy.argtypes = [C.c_void_p]
+        L.refmain_spheres.argtypes = [C.c_void_p] * 4
+        L.refmain_world_rng.argtypes = [C.c_void_p] * 2
+        L.refmain_camera.argtypes = [C.c_void_p] * 2
+        L.refmain_set_camera.argtypes = [C.c_void_p] * 2
+        L.refmain_build_octree.argtypes = [C.c_void_p] * 2
+        L.refmain_render_init.argtypes = [C.c_int] * 4 + [C.c_void_p]
+        L.refmain_render.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]
+        L.refmain_render_progressive.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]
+        L.refmain_ppm.restype = C.c_int64
+        L.refmain_ppm.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int64]
+        info, radius = np.zeros(5, np.int32), np.zeros(1, np.float32)
+        L.refmain_build_info(_p(info), _p(radius))
+        fp16, n, r, octree, spl = case
+        assert info.tolist() == [int(fp16), n, int(octree), OWN_SPL if spl == "own" else spl, 48] and radius[0] == np.float32(r), (case, info, radius)
+        _MAIN[key] = L
+    return _MAIN[key]
+
+
+class RefMain:
+    """rand_init + create_world of the reference's main.cu for an nx x ny frame, and its render kernels run pixel by pixel.
+    Same method names and array shapes as OracleScene where both have the call."""
+
+    def __init__(self, case, nx, ny, opt=2):
+        self.L, self.case, self.nx, self.ny = main_lib(case, opt), case, nx, ny
+        self.fp16, self.n, _, self.use_octree, _ = case
+        self.h = C.c_void_p(self.L.refmain_create(nx, ny))
+        self._info = None
+        if self.use_octree:
+            self.build_octree()
+
+    def close(self):
+        if self.h:
+            self.L.refmain_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def spheres(self):
+        geom, mat, kind = np.zeros((self.n, 4), np.float32), np.zeros((self.n, 4), np.float32), np.zeros(self.n, np.int32)
+        self.L.refmain_spheres(self.h, _p(geom), _p(mat), _p(kind))
+        return geom, mat, kind
+
+    def world_rng(self):
+        out = np.zeros(12, np.uint32)
+        self.L.refmain_world_rng(self.h, _p(out))
+        return out
+
+    def camera(self):
+        out = np.zeros(22, np.float32)
+        self.L.refmain_camera(self.h, _p(out))
+        return out
+
+    def set_camera(self, cam):
+        cam = np.ascontiguousarray(cam, np.float32).ravel()
+        assert cam.size == 22
+        self.L.refmain_set_camera(self.h, _p(cam))
+        return self
+
+    def build_octree(self):
+        """buildOctree on create_world's list: node_count, leaf_count, dropped_full, dropped_outside"""
+        if self._info is None:
+            out = np.zeros(4, np.int64)
+            self.L.refmain_build_octree(self.h, _p(out))
+            self._info = dict(zip(("node_count", "leaf_count", "dropped_full", "dropped_outside"), out.tolist()))
+        return dict(self._info)
+
+    def render_init(self, row0=0, rows=None):
+        rows = self.ny if rows is None else rows
+        st = np.zeros((rows * self.nx, 12), np.uint32)
+        self.L.refmain_render_init(self.nx, self.ny, row0, rows, _p(st))
+        return st
+
+    def render(self, ns, states=None, row0=0, rows=None):
+        """(frame rows x nx x 3, states after, ghost rows x nx); states None: render_init's.  ghost: the pixels where the reference
+        reached a slot that create_world left unwritten and has no result (ref_main_capi.cpp): they take no part in a comparison"""
+        rows = self.ny if rows is None else rows
+        states = self.render_init(row0, rows) if states is None else np.array(states, np.uint32).reshape(rows * self.nx, 12)
+        fb, ghost = np.zeros((rows, self.nx, 3), np.float32), np.zeros((rows, self.nx), np.uint8)
+        self.L.refmain_render(self.h, _p(fb), ns, row0, rows, _p(states), _p(ghost))
+        return fb, states, ghost.astype(bool)
+
+    def render_progressive(self, fb, current_sample, states, ghost):
+        """one pass over the whole frame: fb (ny x nx x 3 float32), states and ghost (ny x nx uint8, as render's) are advanced in place"""
+        assert fb.dtype == np.float32 and fb.shape == (self.ny, self.nx, 3) and fb.flags.c_contiguous
+        assert states.dtype == np.uint32 and states.shape == (self.ny * self.nx, 12) and states.flags.c_contiguous
+        assert ghost.dtype == np.uint8 and ghost.shape == (self.ny, self.nx) and ghost.flags.c_contiguous
+        self.L.refmain_render_progressive(self.h, _p(fb), current_sample, 0, self.ny, _p(states), _p(ghost))
+        return fb
+
+
+def main_ppm(fb, fp16=False):
+    """output_to_stream of the reference on an ny x nx x 3 frame, as bytes (any built main library of that precision serves)"""
+    fb = np.ascontiguousarray(fb, np.float32)
+    ny, nx = fb.shape[:2]
+    L = main_lib(main_case(22, fp16))
+    n = L.refmain_ppm(_p(fb), nx, ny, None, 0)
+    buf = C.create_string_buffer(n)
+    L.refmain_ppm(_p(fb), nx, ny, buf, n)
+    return buf.raw[:n]

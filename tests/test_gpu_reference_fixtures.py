@@ -3,7 +3,7 @@ reference_octrees.npz were recorded from a CPU build of the reference's headers 
 k_trace (fast and reference traversal, list and tree), k_trace_h (binary16) and k_guides against the hit records; the device-built
 octree (rt_build_octree_gpu, nodes and leaves in the reference's numbering) against the octree digests.  All nine worlds of
 material_edge_worlds.WORLDS and one random_world world.  Bit equality, "NaN where the reference has NaN" (bitcmp.same_nan_as_ref).
-Reads nothing outside tests/golden/.  Frames stay compared with the oracle (the built reference has no render loop)."""
+Reads nothing outside tests/golden/.  Frames of the reference's own render loops: tests/test_gpu_reference_frames.py."""
 import os
 
 import numpy as np

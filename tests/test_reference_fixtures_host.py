@@ -2,7 +2,10 @@
 a CPU build of the reference's headers) against the CPU oracle and the host code.  Not marked gpu, and it never skips: this is the pin
 that stays where the reference itself is absent.  Bit equality, "NaN where the reference has NaN" (bitcmp.same_nan_as_ref).
 
-The last test re-records from the live libraries, where oracle/_ref/ is built, and holds the files to what they give now."""
+reference_frames.npz holds whole frames of main.cu's own render loops (tests/reference_frames.py, recorded from the main libraries
+of oracle/ref_main_capi.cpp): the oracle's render / render_progressive / create_world and the host code's rt_create_world are held to it.
+
+The last tests re-record from the live libraries, where oracle/_ref/ is built, and hold the files to what they give now."""
 import os
 
 import numpy as np
@@ -11,7 +14,8 @@ import pytest
 import oracle_lib
 import ref_lib
 import reference_cases as rc
-from bitcmp import same_nan_as_ref
+import reference_frames as rf
+from bitcmp import f32_bits, same_nan_as_ref
 
 GOLD = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
 PRECISIONS = [False, True]
@@ -20,6 +24,11 @@ PRECISIONS = [False, True]
 @pytest.fixture(scope="module")
 def gold():
     return {f: np.load(os.path.join(GOLD, "reference_%s.npz" % f)) for f in ("hits", "bounces", "octrees")}
+
+
+@pytest.fixture(scope="module")
+def frames():
+    return np.load(os.path.join(GOLD, "reference_frames.npz"))
 
 
 def tree_cases():
@@ -106,6 +115,63 @@ def test_the_fixtures_are_small_and_cover_every_world(gold):
         for fp16 in PRECISIONS:
             assert rc.tag(name, fp16) + "_tree_t" in gold["hits"] and rc.tag(name, fp16) + "_ret" in gold["bounces"]
     assert len([k for k in gold["octrees"].files if k.endswith("_sha")]) == 2 * len(tree_cases())
+
+
+# ---------------------------------------------------------------------------------------------------- frames of main.cu's own loops
+def test_the_frame_fixtures_are_small_and_cover_every_case(frames):
+    assert os.path.getsize(os.path.join(GOLD, "reference_frames.npz")) <= os.path.getsize(os.path.join(GOLD, "frames.npz"))
+    assert sorted(frames.files) == sorted(c.name + "_" + f for c in rf.CASES for f in ("frame", "states_sha", "list_sha", "camera", "params", "ghost"))
+    for c in rf.CASES:
+        assert np.array_equal(frames[c.name + "_params"], rf.params_of(c)), c.name
+        shape = (c.passes, c.ny, c.nx, 3) if c.passes else (len(rf.rows_of(c)), c.nx, 3)
+        assert frames[c.name + "_frame"].shape == shape and frames[c.name + "_frame"].dtype == (np.float16 if c.fp16 else np.float32)
+        g = frames[c.name + "_ghost"]
+        assert g.dtype == bool and g.shape == shape[-3:-1] and g.sum() * 100 < g.size and (c.fp16 or not g.any())
+    assert {(c.fp16, c.octree) for c in rf.RENDER} == {(False, False), (False, True), (True, False), (True, True)}
+
+
+@pytest.mark.parametrize("case", rf.CASES, ids=lambda c: c.name)
+def test_oracle_frames(frames, case):
+    """create_world's list and camera, the frame (the sum after each progressive pass) and the RNG states afterwards"""
+    S = rf.oracle_scene(case)
+    assert np.array_equal(rf.list_digest(*S.spheres()), frames[case.name + "_list_sha"])
+    assert np.array_equal(f32_bits(S.camera()), f32_bits(frames[case.name + "_camera"]))
+    got, g = rf.run(S, case), frames[case.name + "_ghost"]
+    want = frames[case.name + "_frame"].astype(np.float32)
+    assert same_nan_as_ref(got["frame"][..., ~g, :], want[..., ~g, :])
+    assert np.array_equal(rf.state_digest(got["states"], g), frames[case.name + "_states_sha"])
+
+
+@pytest.mark.parametrize("case", rf.CASES, ids=lambda c: c.name)
+def test_host_code_create_world(rt, frames, case):
+    """rt_rand_init + rt_create_world (host/rt_scene.hpp), the world the product renders: the reference's list, the camera rendered with"""
+    W = rt.World(case.n, case.nx, case.ny, precision=rt.FP16 if case.fp16 else rt.FP32)
+    assert np.array_equal(rf.list_digest_of_world(W), frames[case.name + "_list_sha"])
+    assert np.array_equal(f32_bits(W.camera.view(np.float32)), f32_bits(frames[case.name + "_camera"]))
+
+
+@pytest.mark.parametrize("case", rf.CASES, ids=lambda c: c.name)
+def test_a_case_reaches_all_three_materials(case):
+    """a check on the cases themselves: the oracle's walk through each calls material::scatter on a lambertian, a metal and a
+    dielectric.  (How often, against the camera rays it starts, is the recorder's to assert: golden/make_reference_golden.py.)"""
+    rays, scatters = rf.oracle_content(case)
+    print("%s: %d camera rays, scatter calls %s" % (case.name, rays, scatters))
+    assert rays == len(rf.rows_of(case)) * case.nx * case.ns * max(case.passes, 1)
+    assert all(scatters[m] > 0 for m in ("lambertian", "metal", "dielectric"))
+
+
+def test_the_live_main_libraries_still_give_the_frames(frames):
+    if ref_lib.status() == "absent":
+        pytest.skip("neither oracle/_ref/ nor the reference's sources are here")
+    assert ref_lib.status() == "ok", "the reference's sources are here but oracle/_ref/ is incomplete: run `make -C oracle ref`"
+    import sys
+    sys.path.insert(0, GOLD)
+    import make_reference_golden as mk
+    d = mk.record_frames(both_builds=False)
+    assert sorted(d) == sorted(frames.files)
+    for k, v in d.items():
+        a, b = np.asarray(v), frames[k]
+        assert a.dtype == b.dtype and a.shape == b.shape and a.tobytes() == b.tobytes(), k
 
 
 def test_the_live_libraries_still_give_the_fixtures(gold):

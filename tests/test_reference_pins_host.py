@@ -21,7 +21,7 @@ Left out, with reasons:
     ghost records are therefore reported by the driver (sphere -2), left out of the comparison of that ray and path, and counted:
     0 in binary32 on every world, and in binary16 under 1 % of the records (a radius-0 sphere catches directions within about
     2^-5 of its own, 2.4e-4 of the sphere of directions, and no world has more than a dozen ghosts in view).
-  * the loops of main.cu (color, render, create_world) are not built; they rest on the C1 md5 of test_oracle_pins.py as before.
+  * the loops of main.cu (color, render, create_world): tests/test_reference_main_host.py, over a build of main.cu's own text.
 
 The live tests skip only where neither oracle/_ref/ nor the reference's sources exist (a clean checkout elsewhere: the fixtures of
 tests/test_reference_fixtures_host.py stand in); sources without libraries are a failure."""
