@@ -6,21 +6,13 @@
 #include <hip/hip_runtime.h>
 #include "rt_device.h"
 #include "rt_launch.h"
+#include "rt_adapt_rule.h"
 
 #pragma clang fp contract(off)
 
 namespace rt {
 
-// The stop rule of include/rt_amd.h after k samples, one IEEE binary32 rounding per operation: rel_error > 0 and
-// k*Q - S*S <= (rel_error^2 * (k-1)) * max(S, k*floor)^2 (S, Q: sums of the samples' luminance and of its squares).  Every check calls it.
-__device__ __forceinline__ bool adapt_rule(float S, float Q, int k, float rel_error, float floor_lum) {
-    const float nk = (float)k;
-    const float d = nk * Q - S * S;
-    const float nf = nk * floor_lum;
-    const float m = S > nf ? S : nf;
-    const float tt = rel_error * rel_error;
-    return rel_error > 0.f && d <= (tt * (nk - 1.f)) * (m * m);       // NaN anywhere: false, the pixel runs on
-}
+// (the stop rule every check calls, adapt_rule: rt_adapt_rule.h — k_render<*, 3, *> applies the same function inside the render kernel)
 // the wave's active lanes append their pixel to list_out, one atomic per wave — the order never changes a pixel
 __device__ __forceinline__ void adapt_append(bool active, unsigned int pid, unsigned int* list_out, unsigned int* count_out) {
     const unsigned long long mask = __ballot(active);

@@ -1242,6 +1242,42 @@ int rt_render_adaptive_part_on(rt_render_ctx* ctx, void* fb, int max_x, int max_
     return render_adaptive_common(ctx, fb, max_x, max_y, params, world, d_rand_state, d_octree, d_spp, part, stream);
 }
 
+// ---- the adaptive frame in one launch (DESIGN.md §5.9 "Fused"; include/rt_amd_fused.h) ------------------------------------------
+// render_adaptive_common without its rounds: the family's prologue (the same refusals in the same order), round 0's scheduling pass
+// under round 0's key (ns = min_spp: begin and this call share the context's record), then ONE k_render<*, 3, *> with ns = max_spp
+// that applies the rule itself.  No list, no check, no adaptive workspace; d_state == NULL: the sums never leave the registers.
+static int render_adaptive_fused_common(rt_render_ctx* ctx, void* fb, int max_x, int max_y, const rt_adaptive* P, const rt_world* world,
+                                        rt_rand_state* d_rand_state, const rt_octree* d_octree, int32_t* d_spp, void* d_state, rt_partition part,
+                                        void* stream) {
+    FrameCall F;
+    const int rc = frame_begin(F, ctx, adaptive_params_ok(P) && world, fb && d_rand_state, max_x, max_y, part, world, d_octree, stream);
+    if (rc || !F.npx) return rc;
+    rt_render_ctx& C = *F.C; const hipStream_t st = F.st;
+    RenderArgs A = frame_args(fb, max_x, max_y, P->min_spp, world, d_rand_state, d_octree, part);
+    const bool sched = P->min_spp >= 4;
+    if (sched) RT_TRY(ctx_reserve(C, A.n_local_tiles));
+    RT_TRY(ctx_wait_previous(C, st));
+    RT_TRY(scheduled_round(C, A, world, d_octree, P->min_spp, sched, false, st));
+    // (the pass was made for min_spp samples a pixel: the kernel compares its in-flight threshold with a chain predicted for as many)
+    A.ns = P->max_spp;
+    fused_args_set(A, FusedArgs{P->min_spp, P->batch, P->rel_error, P->floor, d_state, d_spp});
+    RT_TRY(ctx_timed_begin(C, st));
+    RT_TRY(launch_render_fused(A, F.tree, st));
+    C.last_queue = A.queue;
+    RT_TRY(ctx_timed_end(C, st));
+    return ctx_mark_done(C, st);
+}
+int rt_render_adaptive_fused(void* fb, int max_x, int max_y, const rt_adaptive* params, const rt_world* world, rt_rand_state* d_rand_state,
+                             const rt_octree* d_octree, int32_t* d_spp, void* d_state, rt_partition part, void* stream) {
+    return render_adaptive_fused_common(nullptr, fb, max_x, max_y, params, world, d_rand_state, d_octree, d_spp, d_state, part, stream);
+}
+int rt_render_adaptive_fused_on(rt_render_ctx* ctx, void* fb, int max_x, int max_y, const rt_adaptive* params, const rt_world* world,
+                                rt_rand_state* d_rand_state, const rt_octree* d_octree, int32_t* d_spp, void* d_state, rt_partition part,
+                                void* stream) {
+    if (!ctx) return RT_EINVAL;
+    return render_adaptive_fused_common(ctx, fb, max_x, max_y, params, world, d_rand_state, d_octree, d_spp, d_state, part, stream);
+}
+
 // ---- refinement of an adaptive frame (DESIGN.md §5.9 "Refinement") ----------------------------------------------------
 // rt_render_adaptive_begin is render_adaptive_common with the caller's state.  rt_render_adaptive_refine continues from that state: a
 // seed pass decides, from each pixel's k and sums, which pixels `to` stops where they are (finalised again) and lists the others, then
@@ -1449,11 +1485,12 @@ int rt_render_adaptive_spend_temporal_on(rt_render_ctx* ctx, void* fb, int max_x
                                         stream, budget_key_temporal(in, temporal));
 }
 
-// the kernel rt_render (mode 0) / rt_render_progressive (mode 1) launches for this world and tree — the library's own
+// the kernel rt_render (mode 0) / rt_render_progressive (mode 1) / rt_render_adaptive_fused (mode 3; binary32 only) launches for this world and tree — the library's own
 // selection rule, for profiles and bench lines (rocprofv3 shows the same name)
 int rt_render_kernel_name(const rt_world* world, const rt_octree* d_octree, int mode, char* out, int cap) {
-    if (!world || !out || cap <= 0 || (mode != 0 && mode != 1)) return RT_EINVAL;
+    if (!world || !out || cap <= 0 || (mode != 0 && mode != 1 && mode != 3)) return RT_EINVAL;
     if (d_octree && d_octree->precision != world->precision) return RT_EINVAL;
+    if (mode == 3 && world->precision == RT_PRECISION_FP16) return RT_ENOTSUP;
     if (!d_octree) d_octree = list_tree_of(world);
     const bool tree = d_octree != nullptr;
     std::string name;

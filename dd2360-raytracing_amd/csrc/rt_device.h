@@ -3,6 +3,8 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <stddef.h>
+#include <string.h>
 #include "../../include/rt_amd.h"
 
 namespace rt {
@@ -232,6 +234,7 @@ struct RenderArgs {
     // adaptive rounds (k_render<*, 2, *>, rt_render_adaptive): the lane leaves the running sums behind — fb = S_rgb, ad_sl = sum of the
     // samples' luminance, ad_q = sum of its squares — instead of the final colour.  ad_list == NULL: round 0, the whole frame through
     // the scheduled hand-out, from zero; otherwise the pixels (row-major indices) still active, *ad_count of them, resumed from the sums.
+    // (a fused frame, k_render<*, 3, *>, has no rounds: these four words carry its FusedArgs instead, below)
     const unsigned int* ad_list;
     const unsigned int* ad_count;
     float* ad_sl;
@@ -240,5 +243,18 @@ struct RenderArgs {
     // 65535, stored by MODE 0 of k_render<true,*,4> and <true,*,5> where it ends a pixel; NULL = not recorded (every other launch)
     unsigned short* iters_out;
 };
+// The fused adaptive frame (k_render<*, 3, *>, rt_render_adaptive_fused; RenderArgs::ns = max_spp): the stop rule's parameters, which
+// the lane itself applies after min_spp, min_spp + batch, ... samples, and where a pixel's end goes — its colour to fb, its count to
+// spp (NULL: not wanted) and, state != NULL, S_rgb, SL, Q and k to the caller's refinement state, adapt_state(state, elements of the
+// part).  A fused launch has no rounds and reads none of ad_list, ad_count, ad_sl, ad_q: its arguments travel in those 32 bytes, so
+// RenderArgs keeps its size and its declaration.  (Appended fields move whatever lies behind the struct in the argument segment of
+// every kernel that takes one, the hidden arguments included, and with them a scalar load's offset in those kernels' text; a union
+// over the four words changed the order of MODE 2's loads and stores: HISTORY.md, round 28.)
+struct FusedArgs { int32_t min_spp, batch; float rel_error, floor; void* state; int32_t* spp; };
+static_assert(sizeof(FusedArgs) == 32 && offsetof(RenderArgs, ad_q) + sizeof(float*) - offsetof(RenderArgs, ad_list) == sizeof(FusedArgs),
+              "FusedArgs fills the four words of the rounds");
+static_assert(sizeof(RenderArgs) == 568, "RenderArgs keeps its size: what lies behind it in a kernel's argument segment keeps its offset");
+inline void fused_args_set(RenderArgs& A, const FusedArgs& F) { memcpy((void*)&A.ad_list, &F, sizeof F); }
+__device__ __forceinline__ FusedArgs fused_args(const RenderArgs& A) { FusedArgs F; __builtin_memcpy(&F, (const void*)&A.ad_list, sizeof F); return F; }
 
 } // namespace rt

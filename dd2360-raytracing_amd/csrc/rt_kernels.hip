@@ -33,6 +33,7 @@
 #include "rt_launch.h"
 #include "rt_tuning.h"
 #include "rt_sampling.h"
+#include "rt_adapt_rule.h"
 
 // This file is compiled three times (Makefile).  All three see the device code — what traces a ray, k_render and the other kernel
 // templates, of which a unit emits only what its launchers instantiate; the launchers at the end of the file are dealt out:
@@ -1234,6 +1235,10 @@ RT_DEV V3 sky(const RayF& r, const V3& att) {
 // MODE 0: render (ns samples, /ns, sqrt).  MODE 1: render_progressive (one sample, accumulate).  MODE 2: one round of
 // rt_render_adaptive — ns samples more per pixel, the running sums left behind instead of the colour (RenderArgs::ad_*); every
 // line that only MODE 2 needs sits behind `if constexpr`, so the MODE 0 / 1 instantiations compile to what they were.
+// MODE 3: the whole adaptive frame in one launch (rt_render_adaptive_fused) — a pixel starts as in MODE 2's round 0 and runs up to
+// ns = max_spp samples; after min_spp, min_spp + batch, ... samples (the rounds' checkpoints) the lane itself applies adapt_rule to its
+// running sums, and where the pixel ends it writes what the rounds' check kernels write (FusedArgs, rt_device.h).  A pixel is a truncation
+// of its own RNG stream, so which launch structure truncates it changes no bit.  Behind `if constexpr` as MODE 2's lines are.
 //
 // Persistent waves: the grid is sized to what the chip holds at once.  Pixel slots are numbered tile-major
 // (slot = local_tile*64 + ly*8 + lx, the 8x8 block shape of the reference); every lane starts on slot
@@ -1275,7 +1280,7 @@ __global__ __launch_bounds__(256, RT_RENDER_WAVES) void k_render(RenderArgs A) {
     Rng s = {0, 0, 0, 0, 0, 0};
     V3 col = {0.0f, 0.0f, 0.0f};
     V3 att = {1.0f, 1.0f, 1.0f};
-    float sum_l = 0.0f, sum_q = 0.0f;   // MODE 2: the pixel's running luminance sum and sum of squares
+    float sum_l = 0.0f, sum_q = 0.0f;   // MODE 2, 3: the pixel's running luminance sum and sum of squares
     RayF r; r.o = {0.f, 0.f, 0.f}; r.d = {0.f, 1.f, 0.f};
     int sample = 0, depth = 0;
     bool live = false;
@@ -1368,6 +1373,7 @@ __global__ __launch_bounds__(256, RT_RENDER_WAVES) void k_render(RenderArgs A) {
             const rt_rand_state* st = A.rand_state + idx;
             s.d = st->d; s.v0 = st->v[0]; s.v1 = st->v[1]; s.v2 = st->v[2]; s.v3 = st->v[3]; s.v4 = st->v[4];
             col = {0.0f, 0.0f, 0.0f}; att = {1.0f, 1.0f, 1.0f}; sample = 0; depth = 0;
+            if constexpr (MODE == 3) { sum_l = 0.0f; sum_q = 0.0f; }
             if constexpr (MODE == 2) {
                 sum_l = 0.0f; sum_q = 0.0f;
                 if (A.ad_list) {
@@ -1410,7 +1416,7 @@ __global__ __launch_bounds__(256, RT_RENDER_WAVES) void k_render(RenderArgs A) {
         const rt_rand_state* st = A.rand_state + idx;
         s.d = st->d; s.v0 = st->v[0]; s.v1 = st->v[1]; s.v2 = st->v[2]; s.v3 = st->v[3]; s.v4 = st->v[4];
         col = {0.0f, 0.0f, 0.0f}; att = {1.0f, 1.0f, 1.0f}; sample = 0; depth = 0;
-        if constexpr (MODE == 2) { sum_l = 0.0f; sum_q = 0.0f; }     // (long chains are listed in round 0 only)
+        if constexpr (MODE == 2 || MODE == 3) { sum_l = 0.0f; sum_q = 0.0f; }     // (long chains are listed in round 0 only)
         r = primary_ray(A.scene.cam, i, j, A.max_x, A.max_y, s);
         return true;
     };
@@ -1423,6 +1429,18 @@ __global__ __launch_bounds__(256, RT_RENDER_WAVES) void k_render(RenderArgs A) {
         if constexpr (MODE == 2) {
             fb[0] = col.x; fb[1] = col.y; fb[2] = col.z;                 // S_rgb: the check kernel divides and takes the root
             A.ad_sl[idx] = sum_l; A.ad_q[idx] = sum_q;
+        } else if constexpr (MODE == 3) {
+            // what k_adapt_check / k_adapt_check_keep (rt_adaptive.hip) leave for a pixel that stops after `sample` samples
+            const float kk = (float)(1.0 / (double)(float)sample);
+            const FusedArgs F = fused_args(A);
+            if (F.state) {
+                const AdaptState K = adapt_state(F.state, part_whole(A.nparts, A.tile_begin, A.tile_end) ? (long long)A.max_x * A.max_y : A.n_local_tiles * 64);
+                float* S = K.rgb + idx * 3;
+                S[0] = col.x; S[1] = col.y; S[2] = col.z;
+                K.sl[idx] = sum_l; K.q[idx] = sum_q; K.k[idx] = sample;
+            }
+            fb[0] = sqrtf(col.x * kk); fb[1] = sqrtf(col.y * kk); fb[2] = sqrtf(col.z * kk);
+            if (F.spp) F.spp[idx] = sample;
         } else if (MODE == 0) {
             const float k = (float)(1.0 / (double)(float)A.ns);          // vec3::operator/=(real_t): 1.0/t in double (vec3.h:137)
             col.x *= k; col.y *= k; col.z *= k;
@@ -1526,7 +1544,7 @@ __global__ __launch_bounds__(256, RT_RENDER_WAVES) void k_render(RenderArgs A) {
         if (live && !(TREE && ts.pending)) {
             ++iters;
             bool done;                                     // this sample's path has ended
-            float lum = 0.0f;                              // MODE 2: (c.x + c.y) + c.z of the sample (0 for an absorbed path)
+            float lum = 0.0f;                              // MODE 2, 3: (c.x + c.y) + c.z of the sample (0 for an absorbed path)
             if (best >= 0) {
                 const bool cont = scatter(cold_args()->scene, best, closest, r, att, s);
                 ++depth;
@@ -1534,14 +1552,20 @@ __global__ __launch_bounds__(256, RT_RENDER_WAVES) void k_render(RenderArgs A) {
             } else {
                 const V3 c = sky(r, att);
                 col.x += c.x; col.y += c.y; col.z += c.z;
-                if constexpr (MODE == 2) lum = (c.x + c.y) + c.z;
+                if constexpr (MODE == 2 || MODE == 3) lum = (c.x + c.y) + c.z;
                 done = true;
             }
             if (done) {
-                if constexpr (MODE == 2) { sum_l += lum; sum_q += lum * lum; }
+                if constexpr (MODE == 2 || MODE == 3) { sum_l += lum; sum_q += lum * lum; }
                 (void)lum;
                 ++sample; depth = 0; att = {1.0f, 1.0f, 1.0f};
-                if (sample < ns) {
+                bool more = sample < ns;
+                if constexpr (MODE == 3) {
+                    const FusedArgs F = fused_args(*cold_args());
+                    if (more && sample >= F.min_spp && (unsigned int)(sample - F.min_spp) % (unsigned int)F.batch == 0u)
+                        more = !adapt_rule(sum_l, sum_q, sample, F.rel_error, F.floor);
+                }
+                if (more) {
                     RT_STATS_ONLY(
                     if (MODE == 0 && idx < (1ll << 20) && (sample == ns / 3 || sample == 2 * (ns / 3))) {
                         unsigned int* cd = g_chain_dbg + idx * 8 + (sample == ns / 3 ? 0 : 3);
@@ -1555,8 +1579,11 @@ __global__ __launch_bounds__(256, RT_RENDER_WAVES) void k_render(RenderArgs A) {
                     bool now_long = false;
                     if ((sample & (RT_LONG_CHECK - 1)) == 0 && sample + 8 <= ns) {
                         const unsigned int long_thr = MODE != 1 ? cold_args()->queue[kQueueThr] : 0u;
+                        // (MODE 3: the pass that set the threshold predicted a launch of min_spp samples a pixel — the chain is predicted for as many)
+                        unsigned int thr_ns = (unsigned int)ns;
+                        if constexpr (MODE == 3) thr_ns = (unsigned int)fused_args(*cold_args()).min_spp;
                         now_long = iters >= (unsigned int)((COOPG == 2 ? RT_LONG_RATE_DENSE : RT_LONG_RATE) * sample) ||
-                                   (long_thr != 0u && (unsigned long long)iters * (unsigned int)ns >= (unsigned long long)long_thr * (unsigned int)sample);
+                                   (long_thr != 0u && (unsigned long long)iters * thr_ns >= (unsigned long long)long_thr * (unsigned int)sample);
                     }
                     if (now_long) {
                         RT_STATS_ONLY(
@@ -1780,6 +1807,7 @@ hipError_t launch_guides_list(const RenderArgs& A, unsigned blocks, long long n,
     return hipGetLastError();
 }
 hipError_t launch_render_adaptive_list(const RenderArgs& A, hipStream_t st) { return launch_k_render<false, 2, 1>(A, 0, st); }
+hipError_t launch_render_fused_list(const RenderArgs& A, hipStream_t st) { return launch_k_render<false, 3, 1>(A, 0, st); }
 #endif
 #endif
 
@@ -1856,11 +1884,11 @@ int render_variant(bool tree, const DevAccel& acc) {
 // "k_render<TREE,MODE,COOPG>" as rocprofv3 prints it, from one format; the strings live as long as the library
 const char* render_kernel_name(bool tree, int mode, const DevAccel& acc) {
     struct Names {
-        char s[2][kVariantSolo + 1][24];      // [mode][variant]
-        Names() { for (int m = 0; m < 2; ++m) for (int v = 0; v <= kVariantSolo; ++v) snprintf(s[m][v], sizeof s[m][v], "k_render<%s,%d,%d>", v == kVariantList ? "false" : "true", m, v == kVariantList ? 1 : v); }
+        char s[4][kVariantSolo + 1][24];      // [mode][variant]
+        Names() { for (int m = 0; m < 4; ++m) for (int v = 0; v <= kVariantSolo; ++v) snprintf(s[m][v], sizeof s[m][v], "k_render<%s,%d,%d>", v == kVariantList ? "false" : "true", m, v == kVariantList ? 1 : v); }
     };
     static const Names names;
-    return names.s[mode == 0 ? 0 : 1][render_variant(tree, acc)];
+    return names.s[mode >= 0 && mode < 4 ? mode : 1][render_variant(tree, acc)];
 }
 
 // the lanes of rt_render's persistent grid on a tree variant (the scheduling pass wants them before the launch)
@@ -1919,6 +1947,14 @@ hipError_t launch_render_adaptive(const RenderArgs& A, bool tree, hipStream_t st
     const int variant = render_variant(tree, A.tree.acc);
     if (variant == kVariantList) return launch_render_adaptive_list(A, st);
     return with_walk(variant, [&](auto w) { return launch_k_render<true, 2, decltype(w)::value>(A, variant_lds_bytes(A.tree.n_nodes, variant), st); });
+}
+
+// rt_render_adaptive_fused: k_render<*, 3, *> of the same variant, once for the whole frame (A.ns = max_spp; FusedArgs: the rule and where a pixel's end goes)
+hipError_t launch_render_fused(const RenderArgs& A, bool tree, hipStream_t st) {
+    if (A.n_local_tiles <= 0) return hipSuccess;
+    const int variant = render_variant(tree, A.tree.acc);
+    if (variant == kVariantList) return launch_render_fused_list(A, st);
+    return with_walk(variant, [&](auto w) { return launch_k_render<true, 3, decltype(w)::value>(A, variant_lds_bytes(A.tree.n_nodes, variant), st); });
 }
 
 // What launch_trace and launch_guides share — n records, one lane each, in blocks of 256: list(blocks) launches the list scan's kernel,

@@ -87,6 +87,7 @@ struct rt_multi {
     hipEvent_t ev0 = nullptr, ev1 = nullptr; bool timed = false;
     // how the frame is divided (rt_multi_set_split) and the bands of the last balanced split, with what they were computed for
     int split_mode = RT_SPLIT_RUNS;
+    bool adaptive_fused = false;         // rt_multi_set_adaptive_fused: a rank's adaptive part in one launch (rt_render_adaptive_fused_on)
     int64_t starts[rt::kMaxSplitParts + 1] = {0}; bool have_split = false; uint64_t split_key[4] = {0, 0, 0, 0};
 };
 
@@ -171,6 +172,11 @@ int rt_multi_destroy(rt_multi* M) {
 int rt_multi_set_split(rt_multi* M, int mode) {
     if (!M || mode < RT_SPLIT_RUNS || mode > RT_SPLIT_BALANCED_CACHED) return RT_EINVAL;
     M->split_mode = mode; M->have_split = false;
+    return 0;
+}
+int rt_multi_set_adaptive_fused(rt_multi* M, int on) {
+    if (!M || (on != 0 && on != 1)) return RT_EINVAL;
+    M->adaptive_fused = on == 1;
     return 0;
 }
 int rt_multi_last_split(rt_multi* M, int64_t* starts) {
@@ -325,7 +331,8 @@ int rt_multi_render(rt_multi* M, void* fb_full, int max_x, int max_y, int ns, co
     return rc ? rc : frame_end(M, F, stream);
 }
 
-// rt_multi_render with adaptive sampling, runs only: every rank runs render_init + rt_render_adaptive_part_on on its runs, then the
+// rt_multi_render with adaptive sampling, runs only: every rank runs render_init + rt_render_adaptive_part_on (or, after
+// rt_multi_set_adaptive_fused(1), rt_render_adaptive_fused_on) on its runs, then the
 // colour parts and the sample-count parts go to the root as the frame's two lanes.
 int rt_multi_render_adaptive(rt_multi* M, void* fb_full, int max_x, int max_y, const rt_adaptive* params, const rt_world* world, const rt_octree* d_octree,
                              int precision, int root, int32_t* d_spp_full, void* stream) {
@@ -337,7 +344,9 @@ int rt_multi_render_adaptive(rt_multi* M, void* fb_full, int max_x, int max_y, c
     if (M->split_mode != RT_SPLIT_RUNS) return RT_ENOTSUP;
     Frame F = {max_x, max_y, precision, root, 2, {fb_full, d_spp_full}};
     int rc = frame_begin(M, F, world, d_octree, stream);
-    if (!rc) rc = rt_render_adaptive_part_on(M->ctx, F.local[kColour], max_x, max_y, params, world, (rt_rand_state*)M->d_rand, d_octree, (int32_t*)F.local[kCounts], F.mine, stream);
+    // (the part's bits are the same either way: include/rt_amd_fused.h)
+    if (!rc) rc = M->adaptive_fused ? rt_render_adaptive_fused_on(M->ctx, F.local[kColour], max_x, max_y, params, world, (rt_rand_state*)M->d_rand, d_octree, (int32_t*)F.local[kCounts], nullptr, F.mine, stream)
+                                    : rt_render_adaptive_part_on(M->ctx, F.local[kColour], max_x, max_y, params, world, (rt_rand_state*)M->d_rand, d_octree, (int32_t*)F.local[kCounts], F.mine, stream);
     return rc ? rc : frame_end(M, F, stream);
 }
 

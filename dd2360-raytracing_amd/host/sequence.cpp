@@ -14,6 +14,9 @@
 //   n nx ny spl radius   NUM_SPHERES, frame size, SPHERES_PER_LEAF, SPHERE_RADIUS of rt_main            (500 64 40 30 0.1)
 //   frames          animation: number of frames, >= 1                                                  (4)
 //   min_spp max_spp batch rel_error floor   the rt_adaptive of every frame                             (4 8 4 0 0)
+//   adaptive        animation: rounds = rt_render_adaptive_begin (round 0, then a launch and a check a batch); fused = the same frame
+//                   and state from rt_render_adaptive_fused, one launch with the stop rule inside.  The frames are the same byte
+//                   for byte; the `begin` line of timing=1 shows the difference                        (rounds)
 //   budget rounds   extra samples a frame = budget * nx * ny, spent by rt_render_adaptive_spend_temporal in `rounds` rounds of
 //                   `batch` samples a pick; budget=0: no spend                                         (0 1)
 //   budget_max_spp  the spend's cap on a pixel's samples; 0 = max_spp + rounds * batch, which refuses no pick (0)
@@ -92,7 +95,7 @@ __global__ __launch_bounds__(256) void k_upscale(float* out, const float* c, con
 namespace {
 
 struct Options {
-    std::string mode = "animation", out, tree = "build";
+    std::string mode = "animation", out, tree = "build", adaptive = "rounds";
     int n = 500, nx = 64, ny = 40, spl = 30, frames = 4;
     float radius = 0.1f;
     int min_spp = 4, max_spp = 8, batch = 4;
@@ -144,6 +147,7 @@ Options parse(int argc, char** argv) {
         if (key == "mode") { o.mode = v; continue; }
         if (key == "out") { o.out = v; o.out_given = true; continue; }
         if (key == "tree") { o.tree = v; continue; }
+        if (key == "adaptive") { o.adaptive = v; continue; }
         KEY("n", o.n) KEY("nx", o.nx) KEY("ny", o.ny) KEY("spl", o.spl) KEY("radius", o.radius) KEY("frames", o.frames)
         KEY("min_spp", o.min_spp) KEY("max_spp", o.max_spp) KEY("batch", o.batch) KEY("rel_error", o.rel_error) KEY("floor", o.floor)
         KEY("budget", o.budget) KEY("rounds", o.rounds) KEY("budget_max_spp", o.budget_max_spp)
@@ -164,6 +168,8 @@ void validate(Options& o) {
     const bool progressive = o.mode == "progressive";
     if (!progressive && o.mode != "animation") refuse("mode", "'" + o.mode + "' is neither animation nor progressive");
     if (o.tree != "build" && o.tree != "rebuild") refuse("tree", "'" + o.tree + "' is neither build nor rebuild");
+    if (o.adaptive != "rounds" && o.adaptive != "fused") refuse("adaptive", "'" + o.adaptive + "' is neither rounds nor fused");
+    if (progressive && o.adaptive != "rounds") refuse("adaptive", "mode=progressive takes one sample a pass: no adaptive frame");
     if (progressive && o.tree != "build") refuse("tree", "nothing moves in mode=progressive: the tree is built once");
     if (o.fp16 != 0) refuse("fp16", "binary16 is not offered: the calls of the loop are fp32 only");
     if (o.n < 1 || o.n >= INT32_MAX - 256) refuse("n", "needs 1 .. 2^31 - 257 spheres");
@@ -389,7 +395,8 @@ int run_animation(const Options& o) {
         checkHipErrors(rt_render_guides(world, tree, o.nx, o.ny, d_hits[c], stream));
         mark(GUIDES, 1);
         mark(BEGIN, 0);
-        checkHipErrors(rt_render_adaptive_begin(fb, o.nx, o.ny, &adaptive, world, d_rand, tree, d_spp, d_state, whole, stream));
+        if (o.adaptive == "fused") checkHipErrors(rt_render_adaptive_fused(fb, o.nx, o.ny, &adaptive, world, d_rand, tree, d_spp, d_state, whole, stream));
+        else checkHipErrors(rt_render_adaptive_begin(fb, o.nx, o.ny, &adaptive, world, d_rand, tree, d_spp, d_state, whole, stream));
         mark(BEGIN, 1);
         mark(SPEND, 0);
         if (o.budget > 0) {

@@ -297,6 +297,13 @@ SYMBOLS_REBUILD = {
     "rt_octree_rebuild_info": (_i, [_vp, _vp, _vp, _vp]),
 }
 
+# every symbol include/rt_amd_fused.h declares (the other header rt_amd.h includes at its end): (restype, argtypes)
+SYMBOLS_FUSED = {
+    "rt_render_adaptive_fused": (_i, [_vp, _i, _i, _P(Adaptive), _vp, _vp, _vp, _vp, _vp, Partition, _vp]),
+    "rt_render_adaptive_fused_on": (_i, [_vp, _vp, _i, _i, _P(Adaptive), _vp, _vp, _vp, _vp, _vp, Partition, _vp]),
+    "rt_multi_set_adaptive_fused": (_i, [_vp, _i]),
+}
+
 
 def lib():
     """Load librt_amd.so.  Raises RtError when it is missing or does not export the whole ABI (no fallback)."""
@@ -315,7 +322,7 @@ def lib():
             L = C.CDLL(LIB_PATH)
         except OSError as e:
             raise RtError("cannot load %s: %s" % (LIB_PATH, e))
-        for name, (res, args) in list(SYMBOLS.items()) + list(SYMBOLS_REBUILD.items()):
+        for name, (res, args) in list(SYMBOLS.items()) + list(SYMBOLS_REBUILD.items()) + list(SYMBOLS_FUSED.items()):
             try:
                 fn = getattr(L, name)
             except AttributeError:
@@ -456,6 +463,11 @@ def _render_adaptive_begin(fb, max_x, max_y, params, world, d_rand_state, d_stat
            _dev(d_state), part or WHOLE)
 
 
+def _render_adaptive_fused(fb, max_x, max_y, params, world, d_rand_state, d_state, octree, d_spp, part, ctx=None, stream=None):
+    _frame("rt_render_adaptive_fused", ctx, stream, _dev(fb), max_x, max_y, C.byref(params), world.h, _dev(d_rand_state), _h(octree), _dev(d_spp),
+           _dev(d_state), part or WHOLE)
+
+
 def _render_adaptive_refine(fb, max_x, max_y, frm, to, world, d_rand_state, d_state, octree, d_spp, part, ctx=None, stream=None):
     _frame("rt_render_adaptive_refine", ctx, stream, _dev(fb), max_x, max_y, C.byref(frm), C.byref(to), world.h, _dev(d_rand_state), _h(octree),
            _dev(d_spp), _dev(d_state), part or WHOLE)
@@ -479,7 +491,8 @@ def _render_adaptive_spend_temporal(fb, max_x, max_y, params, inputs, temporal, 
 
 
 def render_kernel_name(world, octree=None, mode=0):
-    """the kernel rt_render (mode 0) / rt_render_progressive (mode 1) launches for this world and tree (the library's own rule)"""
+    """the kernel rt_render (mode 0) / rt_render_progressive (mode 1) / rt_render_adaptive_fused (mode 3) launches for this world and tree
+    (the library's own rule)"""
     buf = C.create_string_buffer(64)
     _call("rt_render_kernel_name", world.h, _h(octree), mode, buf, 64)
     return buf.value.decode()
@@ -512,6 +525,10 @@ class RenderCtx(_Scheduled):
     def render_adaptive_begin(self, fb, max_x, max_y, params, world, d_rand_state, d_state, octree=None, d_spp=None, part=None, stream=None):
         """rt_render_adaptive_begin_on: rt_render_adaptive_part_on that also fills d_state (alloc_adaptive_state) for later refinement"""
         _render_adaptive_begin(fb, max_x, max_y, params, world, d_rand_state, d_state, octree, d_spp, part, self, stream)
+
+    def render_adaptive_fused(self, fb, max_x, max_y, params, world, d_rand_state, d_state=None, octree=None, d_spp=None, part=None, stream=None):
+        """rt_render_adaptive_fused_on: render_adaptive_begin's frame and state (d_state None: render_adaptive_part's frame) in one launch"""
+        _render_adaptive_fused(fb, max_x, max_y, params, world, d_rand_state, d_state, octree, d_spp, part, self, stream)
 
     def render_adaptive_refine(self, fb, max_x, max_y, frm, to, world, d_rand_state, d_state, octree=None, d_spp=None, part=None, stream=None):
         """rt_render_adaptive_refine_on: continue the frame that d_state holds at target `frm` (an Adaptive) to the target `to`"""
@@ -616,6 +633,11 @@ class Multi(_Handle):
     def set_split(self, mode):
         _call("rt_multi_set_split", self.h, mode)
         self.split_mode = mode
+        return self
+
+    def set_adaptive_fused(self, on):
+        """rt_multi_set_adaptive_fused: 1 = render_adaptive renders each rank's part in one launch (the same bits), 0 = in rounds"""
+        _call("rt_multi_set_adaptive_fused", self.h, int(on))
         return self
 
     def last_split(self):
@@ -891,6 +913,12 @@ def alloc_adaptive_state(max_x, max_y, part=WHOLE, device="cuda"):
 def render_adaptive_begin(fb, max_x, max_y, params, world, d_rand_state, d_state, octree=None, d_spp=None, part=WHOLE):
     """rt_render_adaptive_begin on the current stream: rt_render_adaptive_part that also fills d_state (alloc_adaptive_state)"""
     _render_adaptive_begin(fb, max_x, max_y, params, world, d_rand_state, d_state, octree, d_spp, part)
+
+
+def render_adaptive_fused(fb, max_x, max_y, params, world, d_rand_state, d_state=None, octree=None, d_spp=None, part=WHOLE):
+    """rt_render_adaptive_fused on the current stream: what render_adaptive_begin leaves (d_state None: what render_adaptive_part
+    leaves), from one scheduling pass and one render launch - the stop rule runs inside the kernel"""
+    _render_adaptive_fused(fb, max_x, max_y, params, world, d_rand_state, d_state, octree, d_spp, part)
 
 
 def render_adaptive_refine(fb, max_x, max_y, frm, to, world, d_rand_state, d_state, octree=None, d_spp=None, part=WHOLE):

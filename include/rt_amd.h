@@ -936,4 +936,5 @@ int rt_write_image(const char* path, int nx, int ny, const void* fb, int precisi
 }
 #endif
 #include "rt_amd_rebuild.h"   /* part of this ABI: the declarations that follow the ones above, in a file of their own */
+#include "rt_amd_fused.h"     /* ... and the adaptive frame in one launch */
 #endif /* RT_AMD_H */
