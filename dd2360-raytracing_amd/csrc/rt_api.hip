@@ -1329,6 +1329,44 @@ int rt_render_adaptive_refine_on(rt_render_ctx* ctx, void* fb, int max_x, int ma
     return render_adaptive_refine_common(ctx, fb, max_x, max_y, from, to, world, d_rand_state, d_octree, d_spp, d_state, part, stream);
 }
 
+// ---- a refinement in one render launch (DESIGN.md §5.9 "Fused refinement"; include/rt_amd_refine_fused.h) -----------------------
+// render_adaptive_refine_common without its rounds: the same prologue (the same refusals in the same order) and the same seed pass,
+// then ONE k_render<*, 4, *> over the seed's list with ns = to->max_spp: a listed pixel resumes from the state and applies the rule
+// itself at the rounds' checkpoints.  One list and one count, the word npx behind the list's start (rt_device.h); no check kernel.
+static int render_adaptive_refine_fused_common(rt_render_ctx* ctx, void* fb, int max_x, int max_y, const rt_adaptive* from, const rt_adaptive* to,
+                                               const rt_world* world, rt_rand_state* d_rand_state, const rt_octree* d_octree, int32_t* d_spp,
+                                               void* d_state, rt_partition part, void* stream) {
+    FrameCall F;
+    const int rc = frame_begin(F, ctx, adaptive_refines(from, to) && world, fb && d_rand_state && d_state, max_x, max_y, part, world, d_octree, stream);
+    if (rc || !F.npx) return rc;
+    rt_render_ctx& C = *F.C; const hipStream_t st = F.st; const int64_t npx = F.npx;
+    const AdaptState S = adapt_state(d_state, npx);
+    RenderArgs A = frame_args(fb, max_x, max_y, to->max_spp, world, d_rand_state, d_octree, part);
+    RT_TRY(ctx_reserve_adaptive(C, npx, 1));
+    RT_TRY(ctx_wait_previous(C, st));
+    unsigned int* list = C.a_list; unsigned int* count = C.a_list + npx;
+    fused_args_set(A, FusedArgs{to->min_spp, to->batch, to->rel_error, to->floor, d_state, d_spp});
+    refine_fused_list_set(A, list);
+    RT_TRY(launch_adapt_zero(count, 1, st));
+    RT_TRY(ctx_timed_begin(C, st));
+    RT_TRY(launch_adapt_refine_seed((float*)fb, S, npx, list, count, d_spp, to->max_spp, to->rel_error, to->floor, F.fr, st));
+    A.queue = next_slot(C);
+    RT_TRY(launch_zero_counters(A.queue, (int)kQueueStride, st));
+    RT_TRY(launch_render_refine_fused(A, F.tree, st));
+    C.last_queue = A.queue;
+    RT_TRY(ctx_timed_end(C, st));
+    return ctx_mark_done(C, st);
+}
+int rt_render_adaptive_refine_fused(void* fb, int max_x, int max_y, const rt_adaptive* from, const rt_adaptive* to, const rt_world* world,
+                                    rt_rand_state* d_rand_state, const rt_octree* d_octree, int32_t* d_spp, void* d_state, rt_partition part, void* stream) {
+    return render_adaptive_refine_fused_common(nullptr, fb, max_x, max_y, from, to, world, d_rand_state, d_octree, d_spp, d_state, part, stream);
+}
+int rt_render_adaptive_refine_fused_on(rt_render_ctx* ctx, void* fb, int max_x, int max_y, const rt_adaptive* from, const rt_adaptive* to, const rt_world* world,
+                                       rt_rand_state* d_rand_state, const rt_octree* d_octree, int32_t* d_spp, void* d_state, rt_partition part, void* stream) {
+    if (!ctx) return RT_EINVAL;
+    return render_adaptive_refine_fused_common(ctx, fb, max_x, max_y, from, to, world, d_rand_state, d_octree, d_spp, d_state, part, stream);
+}
+
 // ---- adaptive sample budgets (DESIGN.md §5.9 "Budgets") ----------------------------------------------------------------
 float rt_adaptive_priority(float SL, float Q, int k, float floor) { return adapt_priority(SL, Q, k, floor); }
 float rt_adaptive_priority_filtered(float l, float v, float floor) { return adapt_priority_filtered(l, v, floor); }
@@ -1485,12 +1523,13 @@ int rt_render_adaptive_spend_temporal_on(rt_render_ctx* ctx, void* fb, int max_x
                                         stream, budget_key_temporal(in, temporal));
 }
 
-// the kernel rt_render (mode 0) / rt_render_progressive (mode 1) / rt_render_adaptive_fused (mode 3; binary32 only) launches for this world and tree — the library's own
+// the kernel rt_render (mode 0) / rt_render_progressive (mode 1) / rt_render_adaptive_fused (mode 3; binary32 only) /
+// rt_render_adaptive_refine_fused (mode 4; binary32 only) launches for this world and tree — the library's own
 // selection rule, for profiles and bench lines (rocprofv3 shows the same name)
 int rt_render_kernel_name(const rt_world* world, const rt_octree* d_octree, int mode, char* out, int cap) {
-    if (!world || !out || cap <= 0 || (mode != 0 && mode != 1 && mode != 3)) return RT_EINVAL;
+    if (!world || !out || cap <= 0 || (mode != 0 && mode != 1 && mode != 3 && mode != 4)) return RT_EINVAL;
     if (d_octree && d_octree->precision != world->precision) return RT_EINVAL;
-    if (mode == 3 && world->precision == RT_PRECISION_FP16) return RT_ENOTSUP;
+    if ((mode == 3 || mode == 4) && world->precision == RT_PRECISION_FP16) return RT_ENOTSUP;
     if (!d_octree) d_octree = list_tree_of(world);
     const bool tree = d_octree != nullptr;
     std::string name;

@@ -256,5 +256,16 @@ static_assert(sizeof(FusedArgs) == 32 && offsetof(RenderArgs, ad_q) + sizeof(flo
 static_assert(sizeof(RenderArgs) == 568, "RenderArgs keeps its size: what lies behind it in a kernel's argument segment keeps its offset");
 inline void fused_args_set(RenderArgs& A, const FusedArgs& F) { memcpy((void*)&A.ad_list, &F, sizeof F); }
 __device__ __forceinline__ FusedArgs fused_args(const RenderArgs& A) { FusedArgs F; __builtin_memcpy(&F, (const void*)&A.ad_list, sizeof F); return F; }
+// The fused refinement (k_render<*, 4, *>, rt_render_adaptive_refine_fused; RenderArgs::ns = to.max_spp): a launch over the list that
+// k_adapt_refine_seed leaves, every listed pixel resumed from the caller's state (never NULL here) and run on under the same rule.  Its
+// FusedArgs travel where MODE 3's do (min_spp is carried and not read: a resumed pixel's checkpoints count from its own k); the list
+// needs one pointer more.  It travels in iters_out, which only MODE 0 reads (a list launch has no measured pass), and its count is the
+// word `elements of the part` behind the list's start — the first word of the second of the two lists the adaptive workspace holds,
+// which a fused refinement never fills.  The kernel forms that offset from its own arguments, as it does for adapt_state.
+static_assert(sizeof(unsigned short*) == sizeof(const unsigned int*) &&
+              (offsetof(RenderArgs, iters_out) >= offsetof(RenderArgs, ad_list) + sizeof(FusedArgs) || offsetof(RenderArgs, iters_out) + sizeof(unsigned short*) <= offsetof(RenderArgs, ad_list)),
+              "the refinement's list travels in iters_out, outside the words of FusedArgs");
+inline void refine_fused_list_set(RenderArgs& A, const unsigned int* list) { memcpy((void*)&A.iters_out, &list, sizeof list); }
+__device__ __forceinline__ const unsigned int* refine_fused_list(const RenderArgs& A) { const unsigned int* l; __builtin_memcpy(&l, (const void*)&A.iters_out, sizeof l); return l; }
 
 } // namespace rt

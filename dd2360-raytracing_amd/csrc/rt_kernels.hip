@@ -1239,6 +1239,9 @@ RT_DEV V3 sky(const RayF& r, const V3& att) {
 // ns = max_spp samples; after min_spp, min_spp + batch, ... samples (the rounds' checkpoints) the lane itself applies adapt_rule to its
 // running sums, and where the pixel ends it writes what the rounds' check kernels write (FusedArgs, rt_device.h).  A pixel is a truncation
 // of its own RNG stream, so which launch structure truncates it changes no bit.  Behind `if constexpr` as MODE 2's lines are.
+// MODE 4: a refinement in one launch (rt_render_adaptive_refine_fused) — MODE 3 launched over the list k_adapt_refine_seed leaves, as a
+// resumed MODE 2 round is: a listed pixel starts where the caller's state stands (k0 samples, its sums, its RNG state), runs up to
+// ns = to.max_spp and asks the rule after k0 + batch, k0 + 2 batch, ... samples, the checkpoints of the resumed rounds.  Behind `if constexpr`.
 //
 // Persistent waves: the grid is sized to what the chip holds at once.  Pixel slots are numbered tile-major
 // (slot = local_tile*64 + ly*8 + lx, the 8x8 block shape of the reference); every lane starts on slot
@@ -1258,7 +1261,9 @@ __global__ __launch_bounds__(256, RT_RENDER_WAVES) void k_render(RenderArgs A) {
     extern __shared__ float4 s_nodes[];
     if (TREE) stage_tree_fp32<COOPG != 1>(A.scene, A.tree, s_nodes);
     const int lane = threadIdx.x & 63;
-    const long long n_slots = (MODE == 2 && A.ad_list) ? (long long)*A.ad_count : A.n_local_tiles * 64;
+    // (MODE 4: the list's count lies `elements of the part` words behind its start, rt_device.h)
+    const long long n_elems = part_whole(A.nparts, A.tile_begin, A.tile_end) ? (long long)A.max_x * A.max_y : A.n_local_tiles * 64;
+    const long long n_slots = MODE == 4 ? (long long)refine_fused_list(A)[n_elems] : (MODE == 2 && A.ad_list) ? (long long)*A.ad_count : A.n_local_tiles * 64;
     const int ns = (MODE != 1) ? A.ns : 1;
 
     const long long n_waves = (long long)gridDim.x * 4;
@@ -1283,6 +1288,7 @@ __global__ __launch_bounds__(256, RT_RENDER_WAVES) void k_render(RenderArgs A) {
     float sum_l = 0.0f, sum_q = 0.0f;   // MODE 2, 3: the pixel's running luminance sum and sum of squares
     RayF r; r.o = {0.f, 0.f, 0.f}; r.d = {0.f, 1.f, 0.f};
     int sample = 0, depth = 0;
+    int k0 = 0;                         // MODE 4: the samples the pixel had when this launch took it up
     bool live = false;
     RT_STATS_ONLY(
     unsigned int pix_iters = 0, pix_alone = 0;
@@ -1311,6 +1317,18 @@ __global__ __launch_bounds__(256, RT_RENDER_WAVES) void k_render(RenderArgs A) {
 #endif
         iters = 0; is_long = false; is_med = false;
         while (slot < n_slots) {
+            if constexpr (MODE == 4) {                             // the seed's list, decoded as a resumed round's is (below)
+                const unsigned int pid = refine_fused_list(A)[slot];
+                idx = (long long)pid;
+                if (part_whole(A.nparts, A.tile_begin, A.tile_end)) { i = (int)(pid % (unsigned int)A.max_x); j = (int)(pid / (unsigned int)A.max_x); }
+                else {
+                    const long long tile = part_tile((long long)(pid >> 6), A.part, A.nparts, A.tile_begin, A.tile_end);
+                    const int tx = (int)(tile % A.tiles_x), ty = (int)(tile / A.tiles_x);
+                    i = tx * 8 + (int)(pid & 7u); j = ty * 8 + (int)((pid >> 3) & 7u);
+                }
+                live = true;
+                break;
+            }
             if constexpr (MODE == 2) {
                 if (A.ad_list) {                                   // a resumed round: the list of the pixels still active, in any order
                     // (entries are buffer indices: row-major for the whole frame, local_tile * 64 + l in a part — decoded as the tile hand-out does)
@@ -1374,6 +1392,12 @@ __global__ __launch_bounds__(256, RT_RENDER_WAVES) void k_render(RenderArgs A) {
             s.d = st->d; s.v0 = st->v[0]; s.v1 = st->v[1]; s.v2 = st->v[2]; s.v3 = st->v[3]; s.v4 = st->v[4];
             col = {0.0f, 0.0f, 0.0f}; att = {1.0f, 1.0f, 1.0f}; sample = 0; depth = 0;
             if constexpr (MODE == 3) { sum_l = 0.0f; sum_q = 0.0f; }
+            if constexpr (MODE == 4) {                             // where the state stands: k0 is one of the rounds' checkpoints, below max_spp
+                const AdaptState K = adapt_state(fused_args(A).state, n_elems);
+                const float* S = K.rgb + idx * 3;
+                k0 = K.k[idx]; sample = k0;
+                col.x = S[0]; col.y = S[1]; col.z = S[2]; sum_l = K.sl[idx]; sum_q = K.q[idx];
+            }
             if constexpr (MODE == 2) {
                 sum_l = 0.0f; sum_q = 0.0f;
                 if (A.ad_list) {
@@ -1416,7 +1440,7 @@ __global__ __launch_bounds__(256, RT_RENDER_WAVES) void k_render(RenderArgs A) {
         const rt_rand_state* st = A.rand_state + idx;
         s.d = st->d; s.v0 = st->v[0]; s.v1 = st->v[1]; s.v2 = st->v[2]; s.v3 = st->v[3]; s.v4 = st->v[4];
         col = {0.0f, 0.0f, 0.0f}; att = {1.0f, 1.0f, 1.0f}; sample = 0; depth = 0;
-        if constexpr (MODE == 2 || MODE == 3) { sum_l = 0.0f; sum_q = 0.0f; }     // (long chains are listed in round 0 only)
+        if constexpr (MODE == 2 || MODE == 3 || MODE == 4) { sum_l = 0.0f; sum_q = 0.0f; }     // (long chains are listed in round 0 only: never reached in MODE 4)
         r = primary_ray(A.scene.cam, i, j, A.max_x, A.max_y, s);
         return true;
     };
@@ -1429,8 +1453,9 @@ __global__ __launch_bounds__(256, RT_RENDER_WAVES) void k_render(RenderArgs A) {
         if constexpr (MODE == 2) {
             fb[0] = col.x; fb[1] = col.y; fb[2] = col.z;                 // S_rgb: the check kernel divides and takes the root
             A.ad_sl[idx] = sum_l; A.ad_q[idx] = sum_q;
-        } else if constexpr (MODE == 3) {
+        } else if constexpr (MODE == 3 || MODE == 4) {
             // what k_adapt_check / k_adapt_check_keep (rt_adaptive.hip) leave for a pixel that stops after `sample` samples
+            // (MODE 4: what k_adapt_refine_check leaves; the state is never NULL there)
             const float kk = (float)(1.0 / (double)(float)sample);
             const FusedArgs F = fused_args(A);
             if (F.state) {
@@ -1544,7 +1569,7 @@ __global__ __launch_bounds__(256, RT_RENDER_WAVES) void k_render(RenderArgs A) {
         if (live && !(TREE && ts.pending)) {
             ++iters;
             bool done;                                     // this sample's path has ended
-            float lum = 0.0f;                              // MODE 2, 3: (c.x + c.y) + c.z of the sample (0 for an absorbed path)
+            float lum = 0.0f;                              // MODE 2, 3, 4: (c.x + c.y) + c.z of the sample (0 for an absorbed path)
             if (best >= 0) {
                 const bool cont = scatter(cold_args()->scene, best, closest, r, att, s);
                 ++depth;
@@ -1552,17 +1577,22 @@ __global__ __launch_bounds__(256, RT_RENDER_WAVES) void k_render(RenderArgs A) {
             } else {
                 const V3 c = sky(r, att);
                 col.x += c.x; col.y += c.y; col.z += c.z;
-                if constexpr (MODE == 2 || MODE == 3) lum = (c.x + c.y) + c.z;
+                if constexpr (MODE == 2 || MODE == 3 || MODE == 4) lum = (c.x + c.y) + c.z;
                 done = true;
             }
             if (done) {
-                if constexpr (MODE == 2 || MODE == 3) { sum_l += lum; sum_q += lum * lum; }
+                if constexpr (MODE == 2 || MODE == 3 || MODE == 4) { sum_l += lum; sum_q += lum * lum; }
                 (void)lum;
                 ++sample; depth = 0; att = {1.0f, 1.0f, 1.0f};
                 bool more = sample < ns;
                 if constexpr (MODE == 3) {
                     const FusedArgs F = fused_args(*cold_args());
                     if (more && sample >= F.min_spp && (unsigned int)(sample - F.min_spp) % (unsigned int)F.batch == 0u)
+                        more = !adapt_rule(sum_l, sum_q, sample, F.rel_error, F.floor);
+                }
+                if constexpr (MODE == 4) {
+                    const FusedArgs F = fused_args(*cold_args());
+                    if (more && (unsigned int)(sample - k0) % (unsigned int)F.batch == 0u)
                         more = !adapt_rule(sum_l, sum_q, sample, F.rel_error, F.floor);
                 }
                 if (more) {
@@ -1577,13 +1607,15 @@ __global__ __launch_bounds__(256, RT_RENDER_WAVES) void k_render(RenderArgs A) {
                     // ... long from RT_LONG_RATE bounces per sample on, or — k_tile_order — when the chain this rate predicts (rate x ns) is a sizeable
                     // part of what ONE lane works through in this launch (queue[kQueueThr]; 0 when no scheduling pass ran)
                     bool now_long = false;
-                    if ((sample & (RT_LONG_CHECK - 1)) == 0 && sample + 8 <= ns) {
+                    // (MODE 4: a resumed pixel's iters count this launch's bounces, so the rates are taken over this launch's samples)
+                    const int taken = MODE == 4 ? sample - k0 : sample;
+                    if ((taken & (RT_LONG_CHECK - 1)) == 0 && sample + 8 <= ns) {
                         const unsigned int long_thr = MODE != 1 ? cold_args()->queue[kQueueThr] : 0u;
                         // (MODE 3: the pass that set the threshold predicted a launch of min_spp samples a pixel — the chain is predicted for as many)
                         unsigned int thr_ns = (unsigned int)ns;
                         if constexpr (MODE == 3) thr_ns = (unsigned int)fused_args(*cold_args()).min_spp;
-                        now_long = iters >= (unsigned int)((COOPG == 2 ? RT_LONG_RATE_DENSE : RT_LONG_RATE) * sample) ||
-                                   (long_thr != 0u && (unsigned long long)iters * thr_ns >= (unsigned long long)long_thr * (unsigned int)sample);
+                        now_long = iters >= (unsigned int)((COOPG == 2 ? RT_LONG_RATE_DENSE : RT_LONG_RATE) * taken) ||
+                                   (long_thr != 0u && (unsigned long long)iters * thr_ns >= (unsigned long long)long_thr * (unsigned int)taken);
                     }
                     if (now_long) {
                         RT_STATS_ONLY(
@@ -1591,7 +1623,7 @@ __global__ __launch_bounds__(256, RT_RENDER_WAVES) void k_render(RenderArgs A) {
                         )
                         is_long = true;
                     }
-                    else if (RT_MED_RATE > 0 && (sample & 7) == 0 && iters >= (unsigned int)(RT_MED_RATE * sample)) is_med = true;
+                    else if (RT_MED_RATE > 0 && (taken & 7) == 0 && iters >= (unsigned int)(RT_MED_RATE * taken)) is_med = true;
                 } else {
                     WPASS(WP_ENDPIX);
                     end_pixel();
@@ -1808,6 +1840,7 @@ hipError_t launch_guides_list(const RenderArgs& A, unsigned blocks, long long n,
 }
 hipError_t launch_render_adaptive_list(const RenderArgs& A, hipStream_t st) { return launch_k_render<false, 2, 1>(A, 0, st); }
 hipError_t launch_render_fused_list(const RenderArgs& A, hipStream_t st) { return launch_k_render<false, 3, 1>(A, 0, st); }
+hipError_t launch_render_refine_fused_list(const RenderArgs& A, hipStream_t st) { return launch_k_render<false, 4, 1>(A, 0, st); }
 #endif
 #endif
 
@@ -1884,11 +1917,11 @@ int render_variant(bool tree, const DevAccel& acc) {
 // "k_render<TREE,MODE,COOPG>" as rocprofv3 prints it, from one format; the strings live as long as the library
 const char* render_kernel_name(bool tree, int mode, const DevAccel& acc) {
     struct Names {
-        char s[4][kVariantSolo + 1][24];      // [mode][variant]
-        Names() { for (int m = 0; m < 4; ++m) for (int v = 0; v <= kVariantSolo; ++v) snprintf(s[m][v], sizeof s[m][v], "k_render<%s,%d,%d>", v == kVariantList ? "false" : "true", m, v == kVariantList ? 1 : v); }
+        char s[5][kVariantSolo + 1][24];      // [mode][variant]
+        Names() { for (int m = 0; m < 5; ++m) for (int v = 0; v <= kVariantSolo; ++v) snprintf(s[m][v], sizeof s[m][v], "k_render<%s,%d,%d>", v == kVariantList ? "false" : "true", m, v == kVariantList ? 1 : v); }
     };
     static const Names names;
-    return names.s[mode >= 0 && mode < 4 ? mode : 1][render_variant(tree, acc)];
+    return names.s[mode >= 0 && mode < 5 ? mode : 1][render_variant(tree, acc)];
 }
 
 // the lanes of rt_render's persistent grid on a tree variant (the scheduling pass wants them before the launch)
@@ -1955,6 +1988,14 @@ hipError_t launch_render_fused(const RenderArgs& A, bool tree, hipStream_t st) {
     const int variant = render_variant(tree, A.tree.acc);
     if (variant == kVariantList) return launch_render_fused_list(A, st);
     return with_walk(variant, [&](auto w) { return launch_k_render<true, 3, decltype(w)::value>(A, variant_lds_bytes(A.tree.n_nodes, variant), st); });
+}
+
+// rt_render_adaptive_refine_fused: k_render<*, 4, *> of the same variant, once over the seed's list (A.ns = to.max_spp; the list travels in A.iters_out, rt_device.h)
+hipError_t launch_render_refine_fused(const RenderArgs& A, bool tree, hipStream_t st) {
+    if (A.n_local_tiles <= 0) return hipSuccess;
+    const int variant = render_variant(tree, A.tree.acc);
+    if (variant == kVariantList) return launch_render_refine_fused_list(A, st);
+    return with_walk(variant, [&](auto w) { return launch_k_render<true, 4, decltype(w)::value>(A, variant_lds_bytes(A.tree.n_nodes, variant), st); });
 }
 
 // What launch_trace and launch_guides share — n records, one lane each, in blocks of 256: list(blocks) launches the list scan's kernel,

@@ -17,6 +17,7 @@ hipError_t launch_count_order(const RenderArgs& A, const unsigned short* iters, 
 hipError_t launch_render(const RenderArgs& A, bool tree, int mode, hipStream_t st);
 hipError_t launch_render_adaptive(const RenderArgs& A, bool tree, hipStream_t st);
 hipError_t launch_render_fused(const RenderArgs& A, bool tree, hipStream_t st);
+hipError_t launch_render_refine_fused(const RenderArgs& A, bool tree, hipStream_t st);
 hipError_t launch_trace(const DevScene& S, const DevTree& T, bool tree, const float* rays, long long n, rt_hit_record* out, hipStream_t st);
 hipError_t launch_guides(const DevScene& S, const DevTree& T, bool tree, int max_x, int max_y, rt_hit_record* out, hipStream_t st);
 int render_variant(bool tree, const DevAccel& acc);             // a kVariant* of rt_variant.h
@@ -36,6 +37,7 @@ hipError_t launch_trace_list(const RenderArgs& A, unsigned blocks, const float* 
 hipError_t launch_guides_list(const RenderArgs& A, unsigned blocks, long long n, rt_hit_record* out, hipStream_t st);
 hipError_t launch_render_adaptive_list(const RenderArgs& A, hipStream_t st);
 hipError_t launch_render_fused_list(const RenderArgs& A, hipStream_t st);
+hipError_t launch_render_refine_fused_list(const RenderArgs& A, hipStream_t st);
 // ---- rt_kernels_contract.hip: k_render with FMA contraction allowed (rt_world_set_arith(RT_ARITH_CONTRACT)); nothing else is contracted
 namespace fmac { hipError_t launch_render(const RenderArgs& A, bool tree, int mode, hipStream_t st); }
 

@@ -304,6 +304,12 @@ SYMBOLS_FUSED = {
     "rt_multi_set_adaptive_fused": (_i, [_vp, _i]),
 }
 
+# every symbol include/rt_amd_refine_fused.h declares (the header rt_amd.h includes last): (restype, argtypes)
+SYMBOLS_REFINE_FUSED = {
+    "rt_render_adaptive_refine_fused": (_i, [_vp, _i, _i, _P(Adaptive), _P(Adaptive), _vp, _vp, _vp, _vp, _vp, Partition, _vp]),
+    "rt_render_adaptive_refine_fused_on": (_i, [_vp, _vp, _i, _i, _P(Adaptive), _P(Adaptive), _vp, _vp, _vp, _vp, _vp, Partition, _vp]),
+}
+
 
 def lib():
     """Load librt_amd.so.  Raises RtError when it is missing or does not export the whole ABI (no fallback)."""
@@ -322,7 +328,7 @@ def lib():
             L = C.CDLL(LIB_PATH)
         except OSError as e:
             raise RtError("cannot load %s: %s" % (LIB_PATH, e))
-        for name, (res, args) in list(SYMBOLS.items()) + list(SYMBOLS_REBUILD.items()) + list(SYMBOLS_FUSED.items()):
+        for name, (res, args) in list(SYMBOLS.items()) + list(SYMBOLS_REBUILD.items()) + list(SYMBOLS_FUSED.items()) + list(SYMBOLS_REFINE_FUSED.items()):
             try:
                 fn = getattr(L, name)
             except AttributeError:
@@ -473,6 +479,11 @@ def _render_adaptive_refine(fb, max_x, max_y, frm, to, world, d_rand_state, d_st
            _dev(d_spp), _dev(d_state), part or WHOLE)
 
 
+def _render_adaptive_refine_fused(fb, max_x, max_y, frm, to, world, d_rand_state, d_state, octree, d_spp, part, ctx=None, stream=None):
+    _frame("rt_render_adaptive_refine_fused", ctx, stream, _dev(fb), max_x, max_y, C.byref(frm), C.byref(to), world.h, _dev(d_rand_state),
+           _h(octree), _dev(d_spp), _dev(d_state), part or WHOLE)
+
+
 def _render_adaptive_spend(fb, max_x, max_y, params, world, d_rand_state, d_state, octree, d_spp, part, d_picked, ctx=None, stream=None):
     _frame("rt_render_adaptive_spend", ctx, stream, _dev(fb), max_x, max_y, C.byref(params), world.h, _dev(d_rand_state), _h(octree), _dev(d_spp),
            _dev(d_state), part or WHOLE, _dev(d_picked))
@@ -491,8 +502,8 @@ def _render_adaptive_spend_temporal(fb, max_x, max_y, params, inputs, temporal, 
 
 
 def render_kernel_name(world, octree=None, mode=0):
-    """the kernel rt_render (mode 0) / rt_render_progressive (mode 1) / rt_render_adaptive_fused (mode 3) launches for this world and tree
-    (the library's own rule)"""
+    """the kernel rt_render (mode 0) / rt_render_progressive (mode 1) / rt_render_adaptive_fused (mode 3) /
+    rt_render_adaptive_refine_fused (mode 4) launches for this world and tree (the library's own rule)"""
     buf = C.create_string_buffer(64)
     _call("rt_render_kernel_name", world.h, _h(octree), mode, buf, 64)
     return buf.value.decode()
@@ -533,6 +544,10 @@ class RenderCtx(_Scheduled):
     def render_adaptive_refine(self, fb, max_x, max_y, frm, to, world, d_rand_state, d_state, octree=None, d_spp=None, part=None, stream=None):
         """rt_render_adaptive_refine_on: continue the frame that d_state holds at target `frm` (an Adaptive) to the target `to`"""
         _render_adaptive_refine(fb, max_x, max_y, frm, to, world, d_rand_state, d_state, octree, d_spp, part, self, stream)
+
+    def render_adaptive_refine_fused(self, fb, max_x, max_y, frm, to, world, d_rand_state, d_state, octree=None, d_spp=None, part=None, stream=None):
+        """rt_render_adaptive_refine_fused_on: render_adaptive_refine's result from the seed pass and one render launch"""
+        _render_adaptive_refine_fused(fb, max_x, max_y, frm, to, world, d_rand_state, d_state, octree, d_spp, part, self, stream)
 
     def render_adaptive_spend(self, fb, max_x, max_y, params, world, d_rand_state, d_state, octree=None, d_spp=None, part=None, d_picked=None,
                               stream=None):
@@ -925,6 +940,12 @@ def render_adaptive_refine(fb, max_x, max_y, frm, to, world, d_rand_state, d_sta
     """rt_render_adaptive_refine on the current stream: continue the frame that d_state holds at target `frm` to the target `to`;
     afterwards fb, d_spp, d_rand_state and d_state hold what render_adaptive_begin(to) would have left"""
     _render_adaptive_refine(fb, max_x, max_y, frm, to, world, d_rand_state, d_state, octree, d_spp, part)
+
+
+def render_adaptive_refine_fused(fb, max_x, max_y, frm, to, world, d_rand_state, d_state, octree=None, d_spp=None, part=WHOLE):
+    """rt_render_adaptive_refine_fused on the current stream: what render_adaptive_refine leaves, from its seed pass and one render
+    launch - every listed pixel resumes from the state and the stop rule runs inside the kernel"""
+    _render_adaptive_refine_fused(fb, max_x, max_y, frm, to, world, d_rand_state, d_state, octree, d_spp, part)
 
 
 def adaptive_priority(SL, Q, k, floor):

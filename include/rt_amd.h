@@ -325,7 +325,7 @@ int rt_render_adaptive_part_on(rt_render_ctx* ctx, void* fb, int max_x, int max_
  * (DESIGN.md §5.9 "Refinement": the rule of `to` then stops no pixel earlier than the rule of `from`).  Other errors as for
  * rt_render_adaptive_part, and RT_EINVAL for a NULL d_state.  Asynchronous on `stream`, no host synchronisation, never captured; the
  * _on forms take a context of the caller's.  A state from another frame, world, tree or part is undefined behaviour, as a progressive
- * pass on a foreign fb is. */
+ * pass on a foreign fb is.  (rt_render_adaptive_refine_fused, rt_amd_refine_fused.h: the same refinement in one render launch.) */
 #define RT_ADAPTIVE_STATE_BYTES 24   /* per buffer element of the caller's refinement state */
 int rt_render_adaptive_begin(void* fb, int max_x, int max_y, const rt_adaptive* params, const rt_world* world, rt_rand_state* d_rand_state,
                              const rt_octree* d_octree, int32_t* d_spp, void* d_state, rt_partition part, void* stream);
@@ -937,4 +937,5 @@ int rt_write_image(const char* path, int nx, int ny, const void* fb, int precisi
 #endif
 #include "rt_amd_rebuild.h"   /* part of this ABI: the declarations that follow the ones above, in a file of their own */
 #include "rt_amd_fused.h"     /* ... and the adaptive frame in one launch */
+#include "rt_amd_refine_fused.h"   /* ... and its refinement in one launch */
 #endif /* RT_AMD_H */
