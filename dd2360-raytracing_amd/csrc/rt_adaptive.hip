@@ -41,10 +41,10 @@ __device__ __forceinline__ void adapt_check(float* __restrict__ fb, const float*
     bool active = false;
     unsigned int pid = 0;
     bool inside = true;
-    if (!list_in && t < n && !part_whole(fr.nparts, fr.tile_begin, fr.tile_end)) {          // (adapt_in_frame of rt_device.h, spelt out: with the call in its place
-        const long long tile = part_tile(t >> 6, fr.part, fr.nparts, fr.tile_begin, fr.tile_end);      // hipcc emits other instruction text for k_adapt_check and k_adapt_check_keep — tried in round 19)
+    if (!list_in && t < n && !frame_whole(fr)) {                                         // (adapt_in_frame of rt_device.h, restated: with the call in its place hipcc emits
+        const long long tile = part_tile(t >> 6, fr.part, fr.nparts, fr.tile_begin, fr.tile_end);      // other instruction text for k_adapt_check and k_adapt_check_keep — rounds 19 and 30)
         const int tx = (int)(tile % fr.tiles_x), ty = (int)(tile / fr.tiles_x);
-        inside = tx * 8 + (int)(t & 7) < fr.max_x && ty * 8 + (int)((t >> 3) & 7) < fr.max_y;
+        inside = tile_px(tx, (int)(t & 7)) < fr.max_x && tile_px(ty, (int)((t >> 3) & 7)) < fr.max_y;
     }
     if (t < n && inside) {
         pid = list_in ? list_in[t] : (unsigned int)t;
@@ -89,7 +89,7 @@ __global__ __launch_bounds__(256) void k_adapt_refine_seed(float* __restrict__ f
     const long long t = (long long)blockIdx.x * 256 + threadIdx.x;
     bool active = false;
     const unsigned int pid = (unsigned int)t;
-    if (t < n_all && (part_whole(fr.nparts, fr.tile_begin, fr.tile_end) || adapt_in_frame(t, fr))) {
+    if (t < n_all && (frame_whole(fr) || adapt_in_frame(t, fr))) {
         const int k = s.k[pid];
         const float* S = s.rgb + (size_t)pid * 3;
         float* f = fb + (size_t)pid * 3;

@@ -33,8 +33,8 @@ __global__ __launch_bounds__(256) void k_gather(T* full, const T* parts, int max
     const int lane = threadIdx.x & 63;
     const long long tile = (long long)blockIdx.x * 4 + (threadIdx.x >> 6);
     if (tile >= own.tiles(nparts)) return;
-    const int tx = (int)(tile % tiles_x), ty = (int)(tile / tiles_x);
-    const int i = tx * 8 + (lane & 7), j = ty * 8 + (lane >> 3);
+    int tx, ty; tile_xy(tile, tiles_x, tx, ty);
+    const int i = tile_px(tx, lane & 7), j = tile_px(ty, lane >> 3);
     if (i >= max_x || j >= max_y) return;
     int owner; long long local_tile;
     own(tile, nparts, owner, local_tile);

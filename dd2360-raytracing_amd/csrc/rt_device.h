@@ -1,5 +1,5 @@
 // rt_device.h — device-side data layout shared by the kernels (rt_kernels.hip and its neighbours) and the uploader (rt_api.hip),
-// and the few device helpers that more than one kernel file uses (the partition's tile mapping, adapt_in_frame, rank_below, wave_excl_scan).
+// and the few device helpers that more than one kernel file uses (the partition's tile mapping, the pixel hand-out, rank_below, wave_excl_scan).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -16,7 +16,6 @@ constexpr double kRootHalfXZ = 11.0;            // the box spans [-kRootHalfXZ, 
 constexpr double kCellXZ = 2.0 * kRootHalfXZ / 8.0, kCellY = 0.25;
 constexpr float kRootHalfXZf = (float)kRootHalfXZ, kInvCellXZf = 1.0f / 2.75f, kInvCellYf = 4.0f;
 static_assert(kCellXZ == 2.75 && 1.0 / kCellY == 4.0, "level-3 cells of the reference's root box");
-
 
 // The tile split of a frame over parts (rt_amd.h, rt_partition).  Two forms: a contiguous range [begin, end) of the row-major tile
 // numbering (end > begin: rt_split_balanced cuts the frame into such bands of equal predicted cost), or — begin == end == 0 — runs of
@@ -51,12 +50,52 @@ __host__ __device__ inline bool part_has(long long tile, int part, int nparts, l
 }
 // the frame and the part an adaptive check runs over (k_adapt_check: which elements of a compact part buffer are padding)
 struct AdaptFrame { int max_x, max_y, tiles_x, part, nparts; long long tile_begin, tile_end; };
+// ---- The pixel hand-out: which pixel (i, j) and which buffer element a part's (local tile, position in the tile) or a list entry is,
+// and in which order the render kernels' slots go through them.  Written here once; every kernel that decodes goes through it.
+// `P` names the frame and the part by its fields max_x, max_y, tiles_x, part, nparts, tile_begin, tile_end: a RenderArgs or an AdaptFrame.
+// Buffers: row-major (j * max_x + i) for the undivided frame, compact tile-major (local_tile * 64 + ly * 8 + lx) in a part.  (The statements' order in these helpers is the kernels' instruction text: HISTORY.md, round 30.)
+template <class P> __device__ __forceinline__ bool frame_whole(const P& p) { return part_whole(p.nparts, p.tile_begin, p.tile_end); }
+// tile -> its column and row of tiles; a tile column (row) and a position 0..7 in it -> pixel column (row)
+__device__ __forceinline__ void tile_xy(long long tile, int tiles_x, int& tx, int& ty) { tx = (int)(tile % tiles_x); ty = (int)(tile / tiles_x); }
+template <class P> __device__ __forceinline__ void local_tile_xy(const P& p, long long local_tile, int& tx, int& ty) { const long long tile = part_tile(local_tile, p.part, p.nparts, p.tile_begin, p.tile_end); tile_xy(tile, p.tiles_x, tx, ty); }
+__device__ __forceinline__ int tile_px(int t, int l) { return t * 8 + l; }
+template <class P> __device__ __forceinline__ void local_pixel(const P& p, long long local_tile, int l, int& i, int& j) { int tx, ty; local_tile_xy(p, local_tile, tx, ty); i = tile_px(tx, l & 7); j = tile_px(ty, l >> 3); }   // the tile decode: (local tile, position l = ly * 8 + lx in it) -> pixel
+// the list-entry decode: entries are buffer elements (the adaptive lists, rt_adaptive.hip) -> pixel
+// (the part's branch is local_pixel of (pid >> 6, pid & 63), spelt out: through the call k_render<*,2,*> and <*,4,*> come out as other text)
+template <class P> __device__ __forceinline__ void listed_pixel(const P& p, unsigned int pid, int& i, int& j) {
+    if (frame_whole(p)) { i = (int)(pid % (unsigned int)p.max_x); j = (int)(pid / (unsigned int)p.max_x); return; }
+    const long long tile = part_tile((long long)(pid >> 6), p.part, p.nparts, p.tile_begin, p.tile_end);
+    const int tx = (int)(tile % p.tiles_x), ty = (int)(tile / p.tiles_x);
+    i = tile_px(tx, (int)(pid & 7u)); j = tile_px(ty, (int)((pid >> 3) & 7u));
+}
+// the buffer element of pixel (i, j), which is position l of the part's local tile — or element `compact` of its buffer, `whole` held by the caller
+template <class P> __device__ __forceinline__ long long pixel_elem(const P& p, int i, int j, long long local_tile, int l) { return frame_whole(p) ? (long long)j * p.max_x + i : local_tile * 64 + l; }
+template <class P> __device__ __forceinline__ long long pixel_elem(const P& p, bool whole, int i, int j, long long compact) { return whole ? (long long)j * p.max_x + i : compact; }
+template <class P> __device__ __forceinline__ long long part_elems(const P& p) { return frame_whole(p) ? (long long)p.max_x * p.max_y : p.n_local_tiles * 64; }   // elements of this part's buffers (rt_part_pixels on the host)
 // element t of a part's compact tile-major buffer lies inside the frame (the elements of edge tiles outside it are padding)
 __device__ __forceinline__ bool adapt_in_frame(long long t, const AdaptFrame& fr) {
     const long long tile = part_tile(t >> 6, fr.part, fr.nparts, fr.tile_begin, fr.tile_end);
-    const int tx = (int)(tile % fr.tiles_x), ty = (int)(tile / fr.tiles_x);
-    return tx * 8 + (int)(t & 7) < fr.max_x && ty * 8 + (int)((t >> 3) & 7) < fr.max_y;
+    const int tx = (int)(tile % fr.tiles_x), ty = (int)(tile / fr.tiles_x);       // (tile_xy, spelt out: as a call it changes the text of k_budget_keys and k_adapt_refine_seed)
+    return tile_px(tx, (int)(t & 7)) < fr.max_x && tile_px(ty, (int)((t >> 3) & 7)) < fr.max_y;
 }
+// The interleaved slots: consecutive slots are the same pixel position of kIl different tiles (in hand-out order), so the 64 pixels of a
+// tile go to 64 different lanes; the last block holds the tiles that are left.  Slot ms -> position in the hand-out order, and l.
+// (k_render<true,3,1> takes two other registers with this call in any of twelve forms — HISTORY.md, round 30 — so k_render restates it.)
+template <int kIl> __device__ __forceinline__ long long slot_rank(long long ms, long long n_local_tiles, int& l) {
+    const long long blk = ms / (64 * kIl);
+    const long long tiles_in_blk = (n_local_tiles - blk * kIl) < kIl ? (n_local_tiles - blk * kIl) : kIl;
+    const long long within = ms % (64 * kIl);
+    const long long rank = blk * kIl + within % tiles_in_blk;
+    l = (int)(within / tiles_in_blk); return rank;
+}
+// The long list is in the pilot's order, the pixels of a 2x2 block and the blocks of a tile next to each other, and neighbours are chains of like length: a stride
+// (a prime that does not divide the count, so a permutation) puts them into different waves, each left alone once the shorter ones ended.  Entry of the h-th chain handed out:
+__device__ __forceinline__ unsigned int long_list_at(unsigned int h, unsigned int n_long) { const unsigned int stride = n_long % 257u ? 257u : (n_long % 263u ? 263u : 269u); return (unsigned int)(((unsigned long long)h * stride) % n_long); }
+// a pixel's generator (XORWOW's six words; rt_rand_state's Box-Muller fields are never used): the register copy every render unit keeps, loaded and stored
+struct Rng { uint32_t d, v0, v1, v2, v3, v4; };
+template <class RNG> __device__ __forceinline__ void rng_load(RNG& s, const rt_rand_state* st) { s.d = st->d; s.v0 = st->v[0]; s.v1 = st->v[1]; s.v2 = st->v[2]; s.v3 = st->v[3]; s.v4 = st->v[4]; }
+template <class RNG> __device__ __forceinline__ void rng_store(rt_rand_state* st, const RNG& s) { st->d = s.d; st->v[0] = s.v0; st->v[1] = s.v1; st->v[2] = s.v2; st->v[3] = s.v3; st->v[4] = s.v4; }
+
 // the caller's refinement state of rt_render_adaptive_begin / _refine, structure of arrays over the n buffer elements:
 // S_rgb[3n] (interleaved like fb), SL[n], Q[n], k[n] (int32) — RT_ADAPTIVE_STATE_BYTES = 24 per element
 struct AdaptState { float* rgb; float* sl; float* q; int32_t* k; };

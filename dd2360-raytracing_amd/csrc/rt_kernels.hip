@@ -67,8 +67,6 @@ namespace RT_TU_NAMESPACE {
 
 #include "rt_stats.h"      // the diagnostic build's counters (-DRT_STATS): STAT / WPASS / RT_STATS_ONLY — nothing in a product build
 
-struct Rng { uint32_t d, v0, v1, v2, v3, v4; };
-
 // curand (XORWOW) + curand_uniform: x * 2^-32 + 2^-33 — the product is exact, so one fused rounding gives the reference's bits (rt_sampling.h)
 RT_DEV float rng_uniform(Rng& s) {
     const uint32_t t = s.v0 ^ (s.v0 >> 2);
@@ -1232,16 +1230,14 @@ RT_DEV V3 sky(const RayF& r, const V3& att) {
 }
 
 // ---------------------------------------------------------------------------------------------------- kernels
-// MODE 0: render (ns samples, /ns, sqrt).  MODE 1: render_progressive (one sample, accumulate).  MODE 2: one round of
-// rt_render_adaptive — ns samples more per pixel, the running sums left behind instead of the colour (RenderArgs::ad_*); every
-// line that only MODE 2 needs sits behind `if constexpr`, so the MODE 0 / 1 instantiations compile to what they were.
-// MODE 3: the whole adaptive frame in one launch (rt_render_adaptive_fused) — a pixel starts as in MODE 2's round 0 and runs up to
-// ns = max_spp samples; after min_spp, min_spp + batch, ... samples (the rounds' checkpoints) the lane itself applies adapt_rule to its
-// running sums, and where the pixel ends it writes what the rounds' check kernels write (FusedArgs, rt_device.h).  A pixel is a truncation
-// of its own RNG stream, so which launch structure truncates it changes no bit.  Behind `if constexpr` as MODE 2's lines are.
-// MODE 4: a refinement in one launch (rt_render_adaptive_refine_fused) — MODE 3 launched over the list k_adapt_refine_seed leaves, as a
-// resumed MODE 2 round is: a listed pixel starts where the caller's state stands (k0 samples, its sums, its RNG state), runs up to
-// ns = to.max_spp and asks the rule after k0 + batch, k0 + 2 batch, ... samples, the checkpoints of the resumed rounds.  Behind `if constexpr`.
+// MODE | entry point                      | a pixel runs                                    | and leaves                        | RenderMode<MODE>
+//  0   | rt_render                        | ns samples                                      | its colour: / ns, sqrt            | averages, schedules
+//  1   | rt_render_progressive            | one sample, slots taken in chunks of 64 a wave  | the sample, accumulated           | chunked
+//  2   | rt_render_adaptive, one round    | ns samples more (ad_list: the active, resumed)  | its sums S_rgb, SL, Q (ad_*)      | schedules, sums, listed
+//  3   | rt_render_adaptive_fused         | up to ns = max_spp, adapt_rule after min_spp, min_spp + batch, ... | what the rounds' check kernels write (FusedArgs) | schedules, sums, rule_in_lane
+//  4   | rt_render_adaptive_refine_fused  | k_adapt_refine_seed's list, each from the caller's state (k0 samples), rule after k0 + batch, ... | as MODE 3 | ... and listed, resumes
+// A pixel is a truncation of its own RNG stream, so which launch structure truncates it changes no bit.  Every line that one mode alone
+// needs sits behind `if constexpr` of a RenderMode flag (below), so the other instantiations compile to what they were.
 //
 // Persistent waves: the grid is sized to what the chip holds at once.  Pixel slots are numbered tile-major
 // (slot = local_tile*64 + ly*8 + lx, the 8x8 block shape of the reference); every lane starts on slot
@@ -1254,17 +1250,27 @@ RT_DEV V3 sky(const RayF& r, const V3& att) {
 // Therefore: slots are interleaved over blocks of 64 tiles (the 64 pixels of a tile go to 64 different lanes/waves: long
 // pixels cluster); a lane whose pixel shows >= RT_LONG_RATE bounces per sample (checked every RT_LONG_CHECK samples) marks it long;
 // a wave holding a long pixel stops refilling its other lanes ("thin" wave, raised issue priority) until that pixel is
-// finished, then resumes.  A global counter caps the
-// number of thin waves at a quarter of the grid, so a scene made of long pixels only keeps its throughput.
+// finished, then resumes.  A global counter caps the number of thin waves at a quarter of the grid, so a scene made of long pixels only keeps its throughput.
+// What a MODE is, named once (the table above): every test of the mode in k_render reads one of these.
+template <int MODE> struct RenderMode {
+    static constexpr bool averages = MODE == 0;                  // ends a pixel with its colour: / ns, sqrt
+    static constexpr bool chunked = MODE == 1;                   // one sample a launch, accumulated; slots taken in chunks of 64 a wave
+    static constexpr bool schedules = MODE != 1;                 // reads what the scheduling pass leaves (tail list, long-chain threshold, solo chains)
+    static constexpr bool sums = MODE >= 2;                      // keeps the luminance sums sum_l, sum_q beside the colour sum
+    static constexpr bool listed = MODE == 2 || MODE == 4;       // may run over a list of pixels, each resumed from its sums
+    static constexpr bool rule_in_lane = MODE == 3 || MODE == 4; // the lane applies adapt_rule at the checkpoints and ends the pixel (FusedArgs)
+    static constexpr bool resumes = MODE == 4;                   // always over a list (refine_fused_list), from the caller's state: checkpoints count from k0
+};
 template <bool TREE, int MODE, int COOPG>
 __global__ __launch_bounds__(256, RT_RENDER_WAVES) void k_render(RenderArgs A) {
+    using M = RenderMode<MODE>;
     extern __shared__ float4 s_nodes[];
     if (TREE) stage_tree_fp32<COOPG != 1>(A.scene, A.tree, s_nodes);
     const int lane = threadIdx.x & 63;
     // (MODE 4: the list's count lies `elements of the part` words behind its start, rt_device.h)
-    const long long n_elems = part_whole(A.nparts, A.tile_begin, A.tile_end) ? (long long)A.max_x * A.max_y : A.n_local_tiles * 64;
-    const long long n_slots = MODE == 4 ? (long long)refine_fused_list(A)[n_elems] : (MODE == 2 && A.ad_list) ? (long long)*A.ad_count : A.n_local_tiles * 64;
-    const int ns = (MODE != 1) ? A.ns : 1;
+    const long long n_elems = part_elems(A);
+    const long long n_slots = M::resumes ? (long long)refine_fused_list(A)[n_elems] : (M::listed && A.ad_list) ? (long long)*A.ad_count : A.n_local_tiles * 64;
+    const int ns = M::chunked ? 1 : A.ns;
 
     const long long n_waves = (long long)gridDim.x * 4;
     long long slot = 0;
@@ -1300,7 +1306,7 @@ __global__ __launch_bounds__(256, RT_RENDER_WAVES) void k_render(RenderArgs A) {
     // requests per C3 pass, one atomic per wave and iteration on one address — 0.3 ms of a 1.0 ms pass.  There a wave owns its first
     // kProgOwn slots outright (the counter's values start behind all waves' own slots) and then takes the rest in chunks of 64, at
     // the one place of the main loop where the wave is convergent (`refill_progressive`).
-    constexpr bool kChunked = MODE == 1;
+    constexpr bool kChunked = M::chunked;
     constexpr long long kProgOwn = RT_PROG_OWN;
     const long long first_free = (kChunked && kProgOwn > 0 && n_waves * kProgOwn <= n_slots) ? n_waves * kProgOwn : 0;
     long long pool_next = 0, pool_end = 0;              // wave-uniform: this wave's current chunk [pool_next, pool_end)
@@ -1317,31 +1323,13 @@ __global__ __launch_bounds__(256, RT_RENDER_WAVES) void k_render(RenderArgs A) {
 #endif
         iters = 0; is_long = false; is_med = false;
         while (slot < n_slots) {
-            if constexpr (MODE == 4) {                             // the seed's list, decoded as a resumed round's is (below)
-                const unsigned int pid = refine_fused_list(A)[slot];
-                idx = (long long)pid;
-                if (part_whole(A.nparts, A.tile_begin, A.tile_end)) { i = (int)(pid % (unsigned int)A.max_x); j = (int)(pid / (unsigned int)A.max_x); }
-                else {
-                    const long long tile = part_tile((long long)(pid >> 6), A.part, A.nparts, A.tile_begin, A.tile_end);
-                    const int tx = (int)(tile % A.tiles_x), ty = (int)(tile / A.tiles_x);
-                    i = tx * 8 + (int)(pid & 7u); j = ty * 8 + (int)((pid >> 3) & 7u);
-                }
-                live = true;
-                break;
-            }
-            if constexpr (MODE == 2) {
-                if (A.ad_list) {                                   // a resumed round: the list of the pixels still active, in any order
-                    // (entries are buffer indices: row-major for the whole frame, local_tile * 64 + l in a part — decoded as the tile hand-out does)
-                    const unsigned int pid = A.ad_list[slot];
-                    idx = (long long)pid;
-                    if (part_whole(A.nparts, A.tile_begin, A.tile_end)) { i = (int)(pid % (unsigned int)A.max_x); j = (int)(pid / (unsigned int)A.max_x); }
-                    else {
-                        const long long tile = part_tile((long long)(pid >> 6), A.part, A.nparts, A.tile_begin, A.tile_end);
-                        const int tx = (int)(tile % A.tiles_x), ty = (int)(tile / A.tiles_x);
-                        i = tx * 8 + (int)(pid & 7u); j = ty * 8 + (int)((pid >> 3) & 7u);
-                    }
-                    live = true;
-                    break;
+            if constexpr (M::listed) {
+                // a resumed round: the list of the pixels still active, in any order (MODE 4: the seed's list, always there)
+                const unsigned int* list = M::resumes ? refine_fused_list(A) : A.ad_list;
+                if (M::resumes || list) {
+                    const unsigned int pid = list[slot];
+                    idx = (long long)pid; listed_pixel(A, pid, i, j);
+                    live = true; break;
                 }
             }
             // Slots are interleaved over blocks of 64 tiles (in hand-out order): consecutive slots are the same pixel
@@ -1351,7 +1339,7 @@ __global__ __launch_bounds__(256, RT_RENDER_WAVES) void k_render(RenderArgs A) {
             long long local_tile; int l;
             // On sparse grids that list is handed out FIRST (its first `head` entries, k_tail_scatter: all of it but the blocks outside the
             // frame), then the tiles, most expensive class first: C3 13.9 -> 13.2 ms, C2 10.4 -> 9.3 (rt_tuning.h RT_HEAD_SUM_SPARSE).
-            const long long tail0 = (MODE != 1 && A.tail_list) ? (long long)A.queue[kQueueThr + 2] : 0;
+            const long long tail0 = (M::schedules && A.tail_list) ? (long long)A.queue[kQueueThr + 2] : 0;
             const long long head = tail0 > 0 ? (long long)A.queue[kQueueThr + 3] : 0;
             if (tail0 > 0 && (slot < head || slot >= tail0 - 1 + head)) {
                 // (head taken from the list's cheap END — queue[kQueueThr + 5] — : the sky first, the rest of the list, most expensive first, last)
@@ -1361,6 +1349,7 @@ __global__ __launch_bounds__(256, RT_RENDER_WAVES) void k_render(RenderArgs A) {
                 const unsigned int pid = A.tail_list[k];
                 local_tile = (long long)(pid >> 6); l = (int)(pid & 63u);
             } else {
+                // (slot_rank of rt_device.h, restated: with the call k_render<true,3,1> takes two other registers)
                 constexpr int kIl = COOPG == 2 ? RT_INTERLEAVE_DENSE : (COOPG == 5 ? RT_INTERLEAVE_SOLO : RT_INTERLEAVE);   // tiles whose pixels interleave (consecutive slots: one pixel position of kIl tiles)
                 // (k_tile_order starts the tail on a multiple of 64 tiles: a block of kIl tiles that straddled it would skip some pixels and render others twice)
                 static_assert(kIl > 0 && 64 % kIl == 0, "RT_INTERLEAVE, RT_INTERLEAVE_DENSE and RT_INTERLEAVE_SOLO must divide 64 (the tail starts on a multiple of 64 tiles)");
@@ -1372,12 +1361,10 @@ __global__ __launch_bounds__(256, RT_RENDER_WAVES) void k_render(RenderArgs A) {
                 l = (int)(within / tiles_in_blk);
                 local_tile = A.order ? (long long)A.order[rank] : rank;
             }
-            const long long tile = part_tile(local_tile, A.part, A.nparts, A.tile_begin, A.tile_end);
-            const int tx = (int)(tile % A.tiles_x), ty = (int)(tile / A.tiles_x);
-            i = tx * 8 + (l & 7); j = ty * 8 + (l >> 3);
+            local_pixel(A, local_tile, l, i, j);
             const bool taken = use_long && A.long_flag[local_tile * 64 + l];      // long chains are handed out separately
             if (i < A.max_x && j < A.max_y && !taken) {
-                idx = part_whole(A.nparts, A.tile_begin, A.tile_end) ? (long long)j * A.max_x + i : local_tile * 64 + l;
+                idx = frame_whole(A) ? (long long)j * A.max_x + i : local_tile * 64 + l;      // (pixel_elem of rt_device.h, restated: the call changes k_render<*,1,*>'s registers)
                 live = true;
                 RT_STATS_ONLY(
                 pix_t0 = __builtin_amdgcn_s_memrealtime();
@@ -1388,18 +1375,16 @@ __global__ __launch_bounds__(256, RT_RENDER_WAVES) void k_render(RenderArgs A) {
         }
         if (!live) retired = true;
         if (live) {
-            const rt_rand_state* st = A.rand_state + idx;
-            s.d = st->d; s.v0 = st->v[0]; s.v1 = st->v[1]; s.v2 = st->v[2]; s.v3 = st->v[3]; s.v4 = st->v[4];
+            rng_load(s, A.rand_state + idx);
             col = {0.0f, 0.0f, 0.0f}; att = {1.0f, 1.0f, 1.0f}; sample = 0; depth = 0;
-            if constexpr (MODE == 3) { sum_l = 0.0f; sum_q = 0.0f; }
-            if constexpr (MODE == 4) {                             // where the state stands: k0 is one of the rounds' checkpoints, below max_spp
+            if constexpr (M::sums && !M::resumes) { sum_l = 0.0f; sum_q = 0.0f; }
+            if constexpr (M::resumes) {                           // where the state stands: k0 is one of the rounds' checkpoints, below max_spp
                 const AdaptState K = adapt_state(fused_args(A).state, n_elems);
                 const float* S = K.rgb + idx * 3;
                 k0 = K.k[idx]; sample = k0;
                 col.x = S[0]; col.y = S[1]; col.z = S[2]; sum_l = K.sl[idx]; sum_q = K.q[idx];
             }
-            if constexpr (MODE == 2) {
-                sum_l = 0.0f; sum_q = 0.0f;
+            if constexpr (M::listed && !M::resumes) {
                 if (A.ad_list) {
                     const float* f = (const float*)A.fb + idx * 3;
                     col.x = f[0]; col.y = f[1]; col.z = f[2]; sum_l = A.ad_sl[idx]; sum_q = A.ad_q[idx];
@@ -1424,49 +1409,44 @@ __global__ __launch_bounds__(256, RT_RENDER_WAVES) void k_render(RenderArgs A) {
             // the list is in the pilot's order, the four pixels of a 2x2 block and the blocks of a tile next to each other — and
             // neighbours are chains of like length: a stride (a prime that does not divide the count, so a permutation) puts
             // them into different waves, where each is left alone with its wave once the shorter ones have ended
-            const unsigned int stride = n_long % 257u ? 257u : (n_long % 263u ? 263u : 269u);
-            pid = (long long)A.long_list[(unsigned int)(((unsigned long long)h * stride) % n_long)];
+            pid = (long long)A.long_list[long_list_at(h, n_long)];
         }
         const long long local_tile = pid >> 6;
         const int l = (int)(pid & 63);
-        const long long tile = part_tile(local_tile, A.part, A.nparts, A.tile_begin, A.tile_end);
-        const int tx = (int)(tile % A.tiles_x), ty = (int)(tile / A.tiles_x);
-        i = tx * 8 + (l & 7); j = ty * 8 + (l >> 3);
-        idx = part_whole(A.nparts, A.tile_begin, A.tile_end) ? (long long)j * A.max_x + i : pid;
+        local_pixel(A, local_tile, l, i, j);
+        idx = frame_whole(A) ? (long long)j * A.max_x + i : pid;                                   // (pixel_elem, restated as above)
         live = true; iters = 0; is_long = true;
         RT_STATS_ONLY(
         pix_t0 = __builtin_amdgcn_s_memrealtime();
         )
-        const rt_rand_state* st = A.rand_state + idx;
-        s.d = st->d; s.v0 = st->v[0]; s.v1 = st->v[1]; s.v2 = st->v[2]; s.v3 = st->v[3]; s.v4 = st->v[4];
+        rng_load(s, A.rand_state + idx);          // (begin_pixel's start, restated: one start_pixel for both changes every k_render's text in seven forms — HISTORY.md, round 30)
         col = {0.0f, 0.0f, 0.0f}; att = {1.0f, 1.0f, 1.0f}; sample = 0; depth = 0;
-        if constexpr (MODE == 2 || MODE == 3 || MODE == 4) { sum_l = 0.0f; sum_q = 0.0f; }     // (long chains are listed in round 0 only: never reached in MODE 4)
+        if constexpr (M::sums) { sum_l = 0.0f; sum_q = 0.0f; }     // (long chains are listed in round 0 only: never reached by a pixel that resumes)
         r = primary_ray(A.scene.cam, i, j, A.max_x, A.max_y, s);
         return true;
     };
     // rand_state[pixel_index] = local_rand_state; fb[pixel_index] = ...  (main.cu:110-115 / :133-141)
     auto end_pixel = [&]() {
         const RenderArgs& A = *cold_args();
-        rt_rand_state* st_out = A.rand_state + idx;
-        st_out->d = s.d; st_out->v[0] = s.v0; st_out->v[1] = s.v1; st_out->v[2] = s.v2; st_out->v[3] = s.v3; st_out->v[4] = s.v4;
+        rng_store(A.rand_state + idx, s);
         float* fb = (float*)A.fb + idx * 3;
-        if constexpr (MODE == 2) {
+        if constexpr (M::sums && !M::rule_in_lane) {
             fb[0] = col.x; fb[1] = col.y; fb[2] = col.z;                 // S_rgb: the check kernel divides and takes the root
             A.ad_sl[idx] = sum_l; A.ad_q[idx] = sum_q;
-        } else if constexpr (MODE == 3 || MODE == 4) {
+        } else if constexpr (M::rule_in_lane) {
             // what k_adapt_check / k_adapt_check_keep (rt_adaptive.hip) leave for a pixel that stops after `sample` samples
             // (MODE 4: what k_adapt_refine_check leaves; the state is never NULL there)
             const float kk = (float)(1.0 / (double)(float)sample);
             const FusedArgs F = fused_args(A);
             if (F.state) {
-                const AdaptState K = adapt_state(F.state, part_whole(A.nparts, A.tile_begin, A.tile_end) ? (long long)A.max_x * A.max_y : A.n_local_tiles * 64);
+                const AdaptState K = adapt_state(F.state, part_elems(A));
                 float* S = K.rgb + idx * 3;
                 S[0] = col.x; S[1] = col.y; S[2] = col.z;
                 K.sl[idx] = sum_l; K.q[idx] = sum_q; K.k[idx] = sample;
             }
             fb[0] = sqrtf(col.x * kk); fb[1] = sqrtf(col.y * kk); fb[2] = sqrtf(col.z * kk);
             if (F.spp) F.spp[idx] = sample;
-        } else if (MODE == 0) {
+        } else if (M::averages) {
             const float k = (float)(1.0 / (double)(float)A.ns);          // vec3::operator/=(real_t): 1.0/t in double (vec3.h:137)
             col.x *= k; col.y *= k; col.z *= k;
             fb[0] = sqrtf(col.x); fb[1] = sqrtf(col.y); fb[2] = sqrtf(col.z);
@@ -1492,7 +1472,7 @@ __global__ __launch_bounds__(256, RT_RENDER_WAVES) void k_render(RenderArgs A) {
     // start: pre-classified long chains first, RT_LONG_PER_WAVE per wave, in waves that are thin from the beginning
     // (the pre-classified chains alone in their waves: very sparse grids, whose pilot names them, and — <true,0,4> and <true,2,4>, which
     // share a context's record — sparse grids once a measured pass has: a pilot-made pass leaves n_solo = 0 there)
-    constexpr bool kSolo = TREE && (COOPG == 5 || (COOPG == 4 && MODE != 1));
+    constexpr bool kSolo = TREE && (COOPG == 5 || (COOPG == 4 && M::schedules));
     if (kSolo && n_solo != 0u && lane == 0 && begin_long_pixel(true)) solo = true;
     if (__ballot(live) == 0ull && lane < RT_LONG_PER_WAVE) begin_long_pixel(false);
     if (__ballot(live) != 0ull) { thin = true; __builtin_amdgcn_s_setprio(3); }
@@ -1577,27 +1557,23 @@ __global__ __launch_bounds__(256, RT_RENDER_WAVES) void k_render(RenderArgs A) {
             } else {
                 const V3 c = sky(r, att);
                 col.x += c.x; col.y += c.y; col.z += c.z;
-                if constexpr (MODE == 2 || MODE == 3 || MODE == 4) lum = (c.x + c.y) + c.z;
+                if constexpr (M::sums) lum = (c.x + c.y) + c.z;
                 done = true;
             }
             if (done) {
-                if constexpr (MODE == 2 || MODE == 3 || MODE == 4) { sum_l += lum; sum_q += lum * lum; }
+                if constexpr (M::sums) { sum_l += lum; sum_q += lum * lum; }
                 (void)lum;
                 ++sample; depth = 0; att = {1.0f, 1.0f, 1.0f};
                 bool more = sample < ns;
-                if constexpr (MODE == 3) {
+                if constexpr (M::rule_in_lane) {                   // the checkpoints: base, base + batch, ... — base = min_spp, or k0 for a resumed pixel (never below it)
                     const FusedArgs F = fused_args(*cold_args());
-                    if (more && sample >= F.min_spp && (unsigned int)(sample - F.min_spp) % (unsigned int)F.batch == 0u)
-                        more = !adapt_rule(sum_l, sum_q, sample, F.rel_error, F.floor);
-                }
-                if constexpr (MODE == 4) {
-                    const FusedArgs F = fused_args(*cold_args());
-                    if (more && (unsigned int)(sample - k0) % (unsigned int)F.batch == 0u)
+                    const int base = M::resumes ? k0 : F.min_spp;
+                    if (more && (M::resumes || sample >= base) && (unsigned int)(sample - base) % (unsigned int)F.batch == 0u)
                         more = !adapt_rule(sum_l, sum_q, sample, F.rel_error, F.floor);
                 }
                 if (more) {
                     RT_STATS_ONLY(
-                    if (MODE == 0 && idx < (1ll << 20) && (sample == ns / 3 || sample == 2 * (ns / 3))) {
+                    if (M::averages && idx < (1ll << 20) && (sample == ns / 3 || sample == 2 * (ns / 3))) {
                         unsigned int* cd = g_chain_dbg + idx * 8 + (sample == ns / 3 ? 0 : 3);
                         cd[0] = (unsigned int)__builtin_amdgcn_s_memrealtime(); cd[1] = pix_iters; cd[2] = pix_alone;
                     }
@@ -1608,12 +1584,12 @@ __global__ __launch_bounds__(256, RT_RENDER_WAVES) void k_render(RenderArgs A) {
                     // part of what ONE lane works through in this launch (queue[kQueueThr]; 0 when no scheduling pass ran)
                     bool now_long = false;
                     // (MODE 4: a resumed pixel's iters count this launch's bounces, so the rates are taken over this launch's samples)
-                    const int taken = MODE == 4 ? sample - k0 : sample;
+                    const int taken = M::resumes ? sample - k0 : sample;
                     if ((taken & (RT_LONG_CHECK - 1)) == 0 && sample + 8 <= ns) {
-                        const unsigned int long_thr = MODE != 1 ? cold_args()->queue[kQueueThr] : 0u;
+                        const unsigned int long_thr = M::schedules ? cold_args()->queue[kQueueThr] : 0u;
                         // (MODE 3: the pass that set the threshold predicted a launch of min_spp samples a pixel — the chain is predicted for as many)
                         unsigned int thr_ns = (unsigned int)ns;
-                        if constexpr (MODE == 3) thr_ns = (unsigned int)fused_args(*cold_args()).min_spp;
+                        if constexpr (M::rule_in_lane && !M::resumes) thr_ns = (unsigned int)fused_args(*cold_args()).min_spp;
                         now_long = iters >= (unsigned int)((COOPG == 2 ? RT_LONG_RATE_DENSE : RT_LONG_RATE) * taken) ||
                                    (long_thr != 0u && (unsigned long long)iters * thr_ns >= (unsigned long long)long_thr * (unsigned int)taken);
                     }
@@ -1684,11 +1660,10 @@ __global__ __launch_bounds__(256) void k_tile_cost(RenderArgs A, int* __restrict
     static_assert(RT_PILOT_SAMPLES == 1 || RT_PILOT_SAMPLES == 2 || RT_PILOT_SAMPLES == 4, "pilot samples per pixel");
     const long long local_tile = ((long long)blockIdx.x * 4 + (threadIdx.x >> 6)) * kTilesPerWave + lane / kPerTile;
     const bool tile_ok = local_tile < A.n_local_tiles;
-    const long long tile = part_tile(tile_ok ? local_tile : 0, A.part, A.nparts, A.tile_begin, A.tile_end);
-    const int tx = (int)(tile % A.tiles_x), ty = (int)(tile / A.tiles_x);
+    int tx, ty; local_tile_xy(A, tile_ok ? local_tile : 0, tx, ty);
     const int sub = (lane % kPerTile) / RT_PILOT_SAMPLES, smp = lane % RT_PILOT_SAMPLES;
     const int lx = 2 * (sub & 3), ly = 2 * (sub >> 2);
-    const int i = tx * 8 + lx, j = ty * 8 + ly;
+    const int i = tile_px(tx, lx), j = tile_px(ty, ly);
     const bool inside = tile_ok && (i < A.max_x) && (j < A.max_y);
     // PILOT path: one sample per pixel on a private RNG stream (seeded away from the pixel's own 1984 + pixel_index
     // stream, which is not touched), same camera / closest-hit / scatter code as the render kernel; only the number
@@ -1871,17 +1846,16 @@ __global__ __launch_bounds__(256) void k_render_init(rt_rand_state* rand_state, 
     const int lane = threadIdx.x & 63;
     const long long local_tile = (long long)blockIdx.x * 4 + (threadIdx.x >> 6);
     if (local_tile >= n_local_tiles) return;
-    const long long tile = part_tile(local_tile, part, nparts, begin, end);
-    const int tx = (int)(tile % tiles_x), ty = (int)(tile / tiles_x);
-    const int i = tx * 8 + (lane & 7), j = ty * 8 + (lane >> 3);
+    const AdaptFrame fr{max_x, max_y, tiles_x, part, nparts, begin, end};
+    int i, j; local_pixel(fr, local_tile, lane, i, j);
     const bool inside = (i < max_x) && (j < max_y);
-    const bool whole = part_whole(nparts, begin, end);
+    const bool whole = frame_whole(fr);
     if (whole && !inside) return;
-    const long long idx = whole ? (long long)j * max_x + i : local_tile * 64 + lane;
+    const long long idx = pixel_elem(fr, i, j, local_tile, lane);
     const int pixel_index = j * max_x + i;
     Rng s; rng_seed(s, 1984ull + (unsigned long long)(long long)pixel_index);
     rt_rand_state out;
-    out.d = s.d; out.v[0] = s.v0; out.v[1] = s.v1; out.v[2] = s.v2; out.v[3] = s.v3; out.v[4] = s.v4;
+    rng_store(&out, s);
     out.boxmuller_flag = 0; out.boxmuller_flag_double = 0; out.boxmuller_extra = 0.f; out.pad_ = 0; out.boxmuller_extra_double = 0.0;
     rand_state[idx] = out;
 }

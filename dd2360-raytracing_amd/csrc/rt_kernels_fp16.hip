@@ -31,7 +31,6 @@ RT_DEV float fl(R r) { return r.f(); }
 RT_DEV R rsqrt_(R x) { return half_t(sqrtf(x.f())); }      // sqrt(real_t) / real_t::sqrt: float sqrt, converted back
 RT_DEV R rneg(R x) { R r; r.bits = (uint16_t)(x.bits ^ 0x8000u); return r; }
 
-struct Rng { uint32_t d, v0, v1, v2, v3, v4; };
 RT_DEV float rng_uniform(Rng& s) {
     const uint32_t t = s.v0 ^ (s.v0 >> 2);
     s.v0 = s.v1; s.v1 = s.v2; s.v2 = s.v3; s.v3 = s.v4;
@@ -843,7 +842,7 @@ __global__ __launch_bounds__(256, RT_H16_MINWAVES) void k_render_h(RenderArgs A)
 
     auto start_pixel = [&]() {
         const rt_rand_state* st = A.rand_state + idx;
-        s.d = st->d; s.v0 = st->v[0]; s.v1 = st->v[1]; s.v2 = st->v[2]; s.v3 = st->v[3]; s.v4 = st->v[4];
+        rng_load(s, st);
         col = {ri(0), ri(0), ri(0)}; att = {rd(1.0), rd(1.0), rd(1.0)}; sample = 0; depth = 0;
         r = primary_ray(cam, i, j, A.max_x, A.max_y, s);
     };
@@ -852,17 +851,11 @@ __global__ __launch_bounds__(256, RT_H16_MINWAVES) void k_render_h(RenderArgs A)
         while (slot < n_slots) {
             // consecutive slots are the same pixel position of 64 different tiles (in hand-out order): the pixels of a tile never travel together
             constexpr int kIl = RT_H16_INTERLEAVE;                   // (rt_tuning.h: tiles whose pixels interleave)
-            const long long blk = slot / (64 * kIl);
-            const long long tiles_in_blk = (A.n_local_tiles - blk * kIl) < kIl ? (A.n_local_tiles - blk * kIl) : kIl;
-            const long long within = slot % (64 * kIl);
-            const long long rank = blk * kIl + within % tiles_in_blk;
-            const int l = (int)(within / tiles_in_blk);
+            int l; const long long rank = slot_rank<kIl>(slot, A.n_local_tiles, l);
             const long long local_tile = A.order ? (long long)A.order[rank] : rank;
-            const long long tile = part_tile(local_tile, A.part, A.nparts, A.tile_begin, A.tile_end);
-            const int tx = (int)(tile % A.tiles_x), ty = (int)(tile / A.tiles_x);
-            i = tx * 8 + (l & 7); j = ty * 8 + (l >> 3);
+            local_pixel(A, local_tile, l, i, j);
             const bool taken = use_long && A.long_flag[local_tile * 64 + l];      // long chains are handed out separately
-            if (i < A.max_x && j < A.max_y && !taken) { idx = part_whole(A.nparts, A.tile_begin, A.tile_end) ? (long long)j * A.max_x + i : local_tile * 64 + l; live = true; break; }
+            if (i < A.max_x && j < A.max_y && !taken) { idx = frame_whole(A) ? (long long)j * A.max_x + i : local_tile * 64 + l; live = true; break; }      // (pixel_elem of rt_device.h, restated: the call changes this kernel's text)
             slot = first_free + (long long)atomicAdd(A.queue, 1u);
         }
         if (!live) retired = true;
@@ -873,21 +866,18 @@ __global__ __launch_bounds__(256, RT_H16_MINWAVES) void k_render_h(RenderArgs A)
         if (!use_long || long_done) return false;
         const unsigned int h = atomicAdd(A.queue + 3, 1u);
         if (h >= n_long) { long_done = true; return false; }
-        const unsigned int stride = n_long % 257u ? 257u : (n_long % 263u ? 263u : 269u);
-        const long long pid = (long long)A.long_list[(unsigned int)(((unsigned long long)h * stride) % n_long)];
+        const long long pid = (long long)A.long_list[long_list_at(h, n_long)];
         const long long local_tile = pid >> 6;
         const int l = (int)(pid & 63);
-        const long long tile = part_tile(local_tile, A.part, A.nparts, A.tile_begin, A.tile_end);
-        const int tx = (int)(tile % A.tiles_x), ty = (int)(tile / A.tiles_x);
-        i = tx * 8 + (l & 7); j = ty * 8 + (l >> 3);
-        idx = part_whole(A.nparts, A.tile_begin, A.tile_end) ? (long long)j * A.max_x + i : pid;
+        int tx, ty; local_tile_xy(A, local_tile, tx, ty);
+        i = tx * 8 + (l & 7); j = ty * 8 + (l >> 3);                   // (local_pixel's last line and pixel_elem of rt_device.h, restated: local_pixel,
+        idx = frame_whole(A) ? (long long)j * A.max_x + i : pid;      // tile_px or pixel_elem here change the text of k_render_h<true, *>)
         live = true; is_long = true;
         start_pixel();
         return true;
     };
     auto end_pixel = [&]() {
-        rt_rand_state* st = A.rand_state + idx;
-        st->d = s.d; st->v[0] = s.v0; st->v[1] = s.v1; st->v[2] = s.v2; st->v[3] = s.v3; st->v[4] = s.v4;
+        rng_store(A.rand_state + idx, s);
         uint16_t* fb = (uint16_t*)A.fb + idx * 3;
         if (MODE == 0) {
             const R k = rd(1.0 / (double)fl(ri(A.ns)));                      // vec3::operator/=(real_t): k = 1.0/t in double
@@ -972,11 +962,10 @@ __global__ __launch_bounds__(256, RT_H16_MINWAVES) void k_tile_cost_h(RenderArgs
     // a wave covers two tiles: 16 blocks x 2 samples each
     const long long local_tile = ((long long)blockIdx.x * 4 + (threadIdx.x >> 6)) * 2 + lane / 32;
     const bool tile_ok = local_tile < A.n_local_tiles;
-    const long long tile = part_tile(tile_ok ? local_tile : 0, A.part, A.nparts, A.tile_begin, A.tile_end);
-    const int tx = (int)(tile % A.tiles_x), ty = (int)(tile / A.tiles_x);
+    int tx, ty; local_tile_xy(A, tile_ok ? local_tile : 0, tx, ty);
     const int sub = (lane % 32) / 2, smp = lane % 2;
     const int lx = 2 * (sub & 3), ly = 2 * (sub >> 2);
-    const int i = tx * 8 + lx, j = ty * 8 + ly;
+    const int i = tile_px(tx, lx), j = tile_px(ty, ly);
     const bool inside = tile_ok && (i < A.max_x) && (j < A.max_y);
     // a private stream: any state that is not all zero will do (this is not curand_init; nothing is compared with it)
     Rng ps;

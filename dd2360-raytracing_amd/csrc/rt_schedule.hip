@@ -47,8 +47,7 @@ __global__ __launch_bounds__(256) void k_long_select(RenderArgs A, const unsigne
     if (g >= A.n_local_tiles * 16) return;
     const long long local_tile = g >> 4;
     const int sub = (int)(g & 15);
-    const long long tile = part_tile(local_tile, A.part, A.nparts, A.tile_begin, A.tile_end);
-    const int tx = (int)(tile % A.tiles_x), ty = (int)(tile / A.tiles_x);
+    int tx, ty; local_tile_xy(A, local_tile, tx, ty);
     const int bx = tx * 4 + (sub & 3), by = ty * 4 + (sub >> 2);
     const int sum = block_sum3x3(A, pilot, g, bx, by);
     if (sum8) sum8[g] = (unsigned char)(sum < 255 ? sum : 255);                    // for the tail sort (k_tail_hist / k_tail_scatter)
@@ -59,7 +58,7 @@ __global__ __launch_bounds__(256) void k_long_select(RenderArgs A, const unsigne
 #pragma unroll
     for (int q = 0; q < 4; ++q) {                          // the 2x2 block this pilot pixel stands for
         const int px = lx + (q & 1), py = ly + (q >> 1);
-        const bool in_img = (tx * 8 + px < A.max_x) && (ty * 8 + py < A.max_y);
+        const bool in_img = (tile_px(tx, px) < A.max_x) && (tile_px(ty, py) < A.max_y);
         const long long pid = local_tile * 64 + py * 8 + px;
         long_flag[pid] = (is_long && in_img) ? 1 : 0;
         // the longest of them (3x3 sum >= solo_sum) are listed apart, from the end of the array: k_render starts each in a wave of its own
@@ -80,12 +79,11 @@ __global__ __launch_bounds__(256) void k_count_cost(RenderArgs A, const unsigned
     const int lane = threadIdx.x & 63;
     const long long local_tile = (long long)blockIdx.x * 4 + (threadIdx.x >> 6);
     if (local_tile >= A.n_local_tiles) return;                                      // (wave-uniform)
-    const long long tile = part_tile(local_tile, A.part, A.nparts, A.tile_begin, A.tile_end);
-    const int tx = (int)(tile % A.tiles_x), ty = (int)(tile / A.tiles_x);
+    int tx, ty; local_tile_xy(A, local_tile, tx, ty);
     const int px = lane & 7, py = lane >> 3;
-    const int i = tx * 8 + px, j = ty * 8 + py;
+    const int i = tile_px(tx, px), j = tile_px(ty, py);
     const bool in_img = (i < A.max_x) && (j < A.max_y);
-    const long long idx = part_whole(A.nparts, A.tile_begin, A.tile_end) ? (long long)j * A.max_x + i : local_tile * 64 + lane;
+    const long long idx = pixel_elem(A, i, j, local_tile, lane);
     const unsigned int v = in_img ? (unsigned int)iters[idx] : 0u;
     unsigned int b = v;                                                              // the 2x2 block: lanes l, l ^ 1, l ^ 8, l ^ 9
     b += (unsigned int)__shfl_xor((int)b, 1); b += (unsigned int)__shfl_xor((int)b, 8);
@@ -106,22 +104,21 @@ __global__ __launch_bounds__(256) void k_count_select(RenderArgs A, const unsign
     if (g >= A.n_local_tiles * 16) return;
     const long long local_tile = g >> 4;
     const int sub = (int)(g & 15);
-    const long long tile = part_tile(local_tile, A.part, A.nparts, A.tile_begin, A.tile_end);
-    const int tx = (int)(tile % A.tiles_x), ty = (int)(tile / A.tiles_x);
+    int tx, ty; local_tile_xy(A, local_tile, tx, ty);
     const int sum = block_sum3x3(A, pilot, g, tx * 4 + (sub & 3), ty * 4 + (sub >> 2));
     if (sum8) sum8[g] = (unsigned char)(sum < 255 ? sum : 255);
     const unsigned int thr = A.queue[kQueueThr], top = A.queue[kQueueMaxCount];
     if (g == 0 && extra) { extra[0] = top; extra[1] = solo_cap; }
     const float solo_from = solo_frac * (float)top;
-    const bool whole = part_whole(A.nparts, A.tile_begin, A.tile_end);
+    const bool whole = frame_whole(A);
     const int lx = 2 * (sub & 3), ly = 2 * (sub >> 2);
 #pragma unroll
     for (int q = 0; q < 4; ++q) {
         const int px = lx + (q & 1), py = ly + (q >> 1);
-        const int i = tx * 8 + px, j = ty * 8 + py;
+        const int i = tile_px(tx, px), j = tile_px(ty, py);
         const bool in_img = (i < A.max_x) && (j < A.max_y);
         const long long pid = local_tile * 64 + py * 8 + px;
-        const unsigned int count = in_img ? (unsigned int)iters[whole ? (long long)j * A.max_x + i : pid] : 0u;
+        const unsigned int count = in_img ? (unsigned int)iters[pixel_elem(A, whole, i, j, pid)] : 0u;
         const bool is_long = in_img && thr != 0u && count >= thr;
         long_flag[pid] = is_long ? 1 : 0;
         if (is_long) {
