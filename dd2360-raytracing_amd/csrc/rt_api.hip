@@ -1157,7 +1157,8 @@ int rt_render_progressive_on(rt_render_ctx* ctx, void* fb, int max_x, int max_y,
 // checks (its parameter block, the world, its buffers), evaluated where the order puts them.  The selections pass no world: their
 // workspace is the caller's context, nothing is rendered.  `kinds` is the world of a selection that reads kind[sphere] and nothing
 // else (the history-aware key): binary16 is refused where the order puts RT_ENOTSUP, a contracted world is not (nothing is rendered),
-// and it is uploaded without a tree, as rt_temporal_accumulate uploads it.
+// and it is uploaded without a tree, as rt_temporal_accumulate uploads it.  `half` (rt_render_adaptive_h16): the call is the binary16
+// one — at the same place of the order RT_ENOTSUP goes to every world that is NOT binary16 (the binary32 calls exist).
 struct FrameCall {
     hipStream_t st = nullptr; rt_render_ctx* C = nullptr;
     int64_t npx = 0;          // buffer elements (a part's padding included); 0 after frame_begin returned 0: the call has nothing to do
@@ -1165,14 +1166,15 @@ struct FrameCall {
     AdaptFrame fr{};
 };
 static int frame_begin(FrameCall& F, rt_render_ctx* ctx, bool params_ok, bool pointers_ok, int max_x, int max_y, rt_partition part,
-                       const rt_world* world, const rt_octree*& d_octree, void* stream, const rt_world* kinds = nullptr) {
+                       const rt_world* world, const rt_octree*& d_octree, void* stream, const rt_world* kinds = nullptr, bool half = false) {
     if (!params_ok || max_x <= 0 || max_y <= 0 || !valid_partition(part)) return RT_EINVAL;
     const int64_t npx = rt_part_pixels(max_x, max_y, part);
     if (npx < 0 || npx > (int64_t)0xffffffffll) return RT_EINVAL;       // ids of the active lists are 32-bit
     if (npx == 0) return 0;                                              // a part without tiles (more parts than tiles)
     if (!pointers_ok) return RT_EINVAL;
     if (world && d_octree && d_octree->precision != world->precision) return RT_EINVAL;
-    if (world && (world->precision == RT_PRECISION_FP16 || world->arith == RT_ARITH_CONTRACT)) return RT_ENOTSUP;
+    if (world && !half && (world->precision == RT_PRECISION_FP16 || world->arith == RT_ARITH_CONTRACT)) return RT_ENOTSUP;
+    if (world && half && world->precision != RT_PRECISION_FP16) return RT_ENOTSUP;
     if (kinds && kinds->precision == RT_PRECISION_FP16) return RT_ENOTSUP;
     F.st = (hipStream_t)stream;
     if (capturing(F.st)) return RT_EINVAL;                               // the workspace may grow, the launches read it: never captured
@@ -1367,6 +1369,41 @@ int rt_render_adaptive_refine_fused_on(rt_render_ctx* ctx, void* fb, int max_x, 
     return render_adaptive_refine_fused_common(ctx, fb, max_x, max_y, from, to, world, d_rand_state, d_octree, d_spp, d_state, part, stream);
 }
 
+// ---- adaptive sampling for binary16 worlds (DESIGN.md §5.9 "Binary16"; include/rt_amd_h16_adaptive.h) ---------------------------
+// render_adaptive_fused_common for RT_PRECISION_FP16 worlds: the same prologue (frame_begin, told that the call is the binary16 one),
+// the same scheduling pass under the same key, then ONE k_render_h<*, 3>.  The state keeps begin's layout; S_rgb holds the images of
+// the binary16 sums.  (No refinement for binary16: HISTORY.md, round 31.)
+static int render_adaptive_h16_common(rt_render_ctx* ctx, void* fb, int max_x, int max_y, const rt_adaptive* P, const rt_world* world,
+                                      rt_rand_state* d_rand_state, const rt_octree* d_octree, int32_t* d_spp, void* d_state, rt_partition part,
+                                      void* stream) {
+    FrameCall F;
+    const int rc = frame_begin(F, ctx, adaptive_params_ok(P) && world, fb && d_rand_state, max_x, max_y, part, world, d_octree, stream, nullptr, true);
+    if (rc || !F.npx) return rc;
+    rt_render_ctx& C = *F.C; const hipStream_t st = F.st;
+    RenderArgs A = frame_args(fb, max_x, max_y, P->min_spp, world, d_rand_state, d_octree, part);
+    const bool sched = P->min_spp >= 4;
+    if (sched) RT_TRY(ctx_reserve(C, A.n_local_tiles));
+    RT_TRY(ctx_wait_previous(C, st));
+    RT_TRY(scheduled_round(C, A, world, d_octree, P->min_spp, sched, false, st));
+    A.ns = P->max_spp;
+    fused_args_set(A, FusedArgs{P->min_spp, P->batch, P->rel_error, P->floor, d_state, d_spp});
+    RT_TRY(ctx_timed_begin(C, st));
+    RT_TRY(launch_render_h(A, F.tree, 3, st));
+    C.last_queue = A.queue;
+    RT_TRY(ctx_timed_end(C, st));
+    return ctx_mark_done(C, st);
+}
+int rt_render_adaptive_h16(void* fb, int max_x, int max_y, const rt_adaptive* params, const rt_world* world, rt_rand_state* d_rand_state,
+                           const rt_octree* d_octree, int32_t* d_spp, void* d_state, rt_partition part, void* stream) {
+    return render_adaptive_h16_common(nullptr, fb, max_x, max_y, params, world, d_rand_state, d_octree, d_spp, d_state, part, stream);
+}
+int rt_render_adaptive_h16_on(rt_render_ctx* ctx, void* fb, int max_x, int max_y, const rt_adaptive* params, const rt_world* world,
+                              rt_rand_state* d_rand_state, const rt_octree* d_octree, int32_t* d_spp, void* d_state, rt_partition part,
+                              void* stream) {
+    if (!ctx) return RT_EINVAL;
+    return render_adaptive_h16_common(ctx, fb, max_x, max_y, params, world, d_rand_state, d_octree, d_spp, d_state, part, stream);
+}
+
 // ---- adaptive sample budgets (DESIGN.md §5.9 "Budgets") ----------------------------------------------------------------
 float rt_adaptive_priority(float SL, float Q, int k, float floor) { return adapt_priority(SL, Q, k, floor); }
 float rt_adaptive_priority_filtered(float l, float v, float floor) { return adapt_priority_filtered(l, v, floor); }
@@ -1523,13 +1560,13 @@ int rt_render_adaptive_spend_temporal_on(rt_render_ctx* ctx, void* fb, int max_x
                                         stream, budget_key_temporal(in, temporal));
 }
 
-// the kernel rt_render (mode 0) / rt_render_progressive (mode 1) / rt_render_adaptive_fused (mode 3; binary32 only) /
-// rt_render_adaptive_refine_fused (mode 4; binary32 only) launches for this world and tree — the library's own
-// selection rule, for profiles and bench lines (rocprofv3 shows the same name)
+// the kernel rt_render (mode 0) / rt_render_progressive (mode 1) / rt_render_adaptive_fused or, on a binary16 world,
+// rt_render_adaptive_h16 (mode 3) / rt_render_adaptive_refine_fused (mode 4; binary32 only) launches for this world and tree —
+// the library's own selection rule, for profiles and bench lines (rocprofv3 shows the same name)
 int rt_render_kernel_name(const rt_world* world, const rt_octree* d_octree, int mode, char* out, int cap) {
     if (!world || !out || cap <= 0 || (mode != 0 && mode != 1 && mode != 3 && mode != 4)) return RT_EINVAL;
     if (d_octree && d_octree->precision != world->precision) return RT_EINVAL;
-    if ((mode == 3 || mode == 4) && world->precision == RT_PRECISION_FP16) return RT_ENOTSUP;
+    if (mode == 4 && world->precision == RT_PRECISION_FP16) return RT_ENOTSUP;
     if (!d_octree) d_octree = list_tree_of(world);
     const bool tree = d_octree != nullptr;
     std::string name;

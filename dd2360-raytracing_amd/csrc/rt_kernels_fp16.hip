@@ -15,6 +15,7 @@
 #include "rt_real.h"
 #include "rt_tuning.h"
 #include "rt_divshared.h"
+#include "rt_adapt_rule.h"
 
 #pragma clang fp contract(off)
 
@@ -810,6 +811,20 @@ RT_DEV V sky(const Ray& r, const V& att) {                 // main.cu:67-72
     return vmul(att, c);
 }
 
+// MODE | entry point                      | a pixel runs                                                        | and leaves                                   | RenderModeH<MODE>
+//  0   | rt_render                        | ns samples                                                          | its colour: / ns, sqrt                       | averages, schedules
+//  1   | rt_render_progressive            | one sample                                                          | the sample, accumulated                      |
+//  3   | rt_render_adaptive_h16           | up to ns = max_spp, adapt_rule after min_spp, min_spp + batch, ...  | MODE 0's colour at ns = its count, the count, | schedules, sums, rule_in_lane
+//      |                                  |                                                                     | the sums (FusedArgs)                         |
+// (the numbers are k_render's, rt_kernels.hip: there is no MODE 2 here — binary16 has no rounds — and no MODE 4: HISTORY.md, round 31.)  The colour sum stays the reference's,
+// in binary16; the rule's statistics are binary32 sums of the samples' luminance, formed from the exact images of the sample's colour
+// (DESIGN.md 5.9 "Binary16").  Every line that one mode alone needs sits behind `if constexpr` of a flag, so MODE 0 and 1 compile to what they were.
+template <int MODE> struct RenderModeH {
+    static constexpr bool averages = MODE == 0;                  // ends a pixel with its colour: / ns, sqrt
+    static constexpr bool schedules = MODE != 1;                 // looks for long chains in flight (RT_H16_LONG_RATE)
+    static constexpr bool sums = MODE == 3;                      // keeps the binary32 luminance sums sum_l, sum_q beside the binary16 colour sum
+    static constexpr bool rule_in_lane = MODE == 3;              // the lane applies adapt_rule at the checkpoints and ends the pixel (FusedArgs)
+};
 // LDS: the tree's nodes, then one WaveLds per wave.  (Staging the leaf sphere lists there too — C4's 89 KB of pairs fit next to
 // eight wave areas, one 512-thread block per CU — was built and measured: 97.6 ms against 83.8 ms from L2 at the same pass width:
 // two waves per SIMD instead of four cost the walk and the shading more than the scan gains; the pairs stay in L2.)
@@ -818,9 +833,10 @@ __global__ __launch_bounds__(256, RT_H16_MINWAVES) void k_render_h(RenderArgs A)
     extern __shared__ float4 s_nodes[];
     WaveLds* wl = TREE ? stage_tree(A.tree, s_nodes) : nullptr;       // this wave's pool (TREE only)
     const int lane = threadIdx.x & 63;
+    using M = RenderModeH<MODE>;
     const long long n_slots = A.n_local_tiles * 64;
     const long long first_free = 0;                                // every slot is handed out by the work counter
-    const int ns = (MODE == 0) ? A.ns : 1;
+    const int ns = (MODE == 1) ? 1 : A.ns;
     const Cam cam = load_camera(A.scene.cam);
     // scheduling as in k_render (rt_kernels.hip): tiles in the pilot pass's longest-first order, slots interleaved over blocks of 64
     // tiles, pre-classified long chains first, RT_H16_LONG_PER_WAVE to a wave that does not refill its other lanes while one is alive
@@ -839,11 +855,13 @@ __global__ __launch_bounds__(256, RT_H16_MINWAVES) void k_render_h(RenderArgs A)
     Ray r; r.o = col; r.d = att;
     int sample = 0, depth = 0;
     bool live = false;
+    float sum_l = 0.0f, sum_q = 0.0f;   // MODE 3: the pixel's running luminance sum and sum of squares, binary32
 
     auto start_pixel = [&]() {
         const rt_rand_state* st = A.rand_state + idx;
         rng_load(s, st);
         col = {ri(0), ri(0), ri(0)}; att = {rd(1.0), rd(1.0), rd(1.0)}; sample = 0; depth = 0;
+        if constexpr (M::sums) { sum_l = 0.0f; sum_q = 0.0f; }
         r = primary_ray(cam, i, j, A.max_x, A.max_y, s);
     };
     auto begin_pixel = [&]() {
@@ -879,7 +897,20 @@ __global__ __launch_bounds__(256, RT_H16_MINWAVES) void k_render_h(RenderArgs A)
     auto end_pixel = [&]() {
         rng_store(A.rand_state + idx, s);
         uint16_t* fb = (uint16_t*)A.fb + idx * 3;
-        if (MODE == 0) {
+        if constexpr (M::rule_in_lane) {
+            // MODE 0's colour for ns = sample, the count, and — with a state — the sums as rt_render_adaptive_begin's state holds them
+            const FusedArgs F = fused_args(A);
+            if (F.state) {
+                const AdaptState K = adapt_state(F.state, part_elems(A));
+                float* S = K.rgb + idx * 3;
+                S[0] = fl(col.x); S[1] = fl(col.y); S[2] = fl(col.z);
+                K.sl[idx] = sum_l; K.q[idx] = sum_q; K.k[idx] = sample;
+            }
+            const R k = rd(1.0 / (double)fl(ri(sample)));
+            col = {col.x * k, col.y * k, col.z * k};
+            fb[0] = rsqrt_(col.x).bits; fb[1] = rsqrt_(col.y).bits; fb[2] = rsqrt_(col.z).bits;
+            if (F.spp) F.spp[idx] = sample;
+        } else if (MODE == 0) {
             const R k = rd(1.0 / (double)fl(ri(A.ns)));                      // vec3::operator/=(real_t): k = 1.0/t in double
             col = {col.x * k, col.y * k, col.z * k};
             fb[0] = rsqrt_(col.x).bits; fb[1] = rsqrt_(col.y).bits; fb[2] = rsqrt_(col.z).bits;
@@ -922,21 +953,35 @@ __global__ __launch_bounds__(256, RT_H16_MINWAVES) void k_render_h(RenderArgs A)
         else closest_list(A.scene, r, a, closest, best);
         if (live) {
             bool done;
+            float lum = 0.0f;                                    // MODE 3: (c.x + c.y) + c.z of the sample's binary16 colour, in binary32 (0 for an absorbed path)
             ++iters;
             if (best >= 0) {
                 const bool cont = scatter(A.scene, best, closest, r, att, s);
                 ++depth;
                 done = !cont || depth >= 50;
             } else {
-                col = vadd(col, sky(r, att));
+                if constexpr (M::sums) {
+                    const V c = sky(r, att);
+                    col = vadd(col, c);
+                    lum = (fl(c.x) + fl(c.y)) + fl(c.z);
+                } else col = vadd(col, sky(r, att));
                 done = true;
             }
             if (done) {
+                if constexpr (M::sums) { sum_l += lum; sum_q += lum * lum; }
+                (void)lum;
                 ++sample; depth = 0; att = {rd(1.0), rd(1.0), rd(1.0)};
-                if (sample < ns) {
+                bool more = sample < ns;
+                if constexpr (M::rule_in_lane) {                 // the checkpoints: min_spp, min_spp + batch, ...
+                    const FusedArgs F = fused_args(A);
+                    if (more && sample >= F.min_spp && (unsigned int)(sample - F.min_spp) % (unsigned int)F.batch == 0u)
+                        more = !adapt_rule(sum_l, sum_q, sample, F.rel_error, F.floor);
+                }
+                if (more) {
                     r = primary_ray(cam, i, j, A.max_x, A.max_y, s);
 #if RT_H16_LONG_RATE
-                    if (MODE == 0 && (sample & (RT_H16_LONG_CHECK - 1)) == 0 && sample + 8 <= ns && iters >= (unsigned int)(RT_H16_LONG_RATE * sample)) is_long = true;
+                    // (MODE 3 runs under the pass made for min_spp samples a pixel: the rate is the pixel's own and needs no prediction, as in k_render<*,3,*>)
+                    if (M::schedules && (sample & (RT_H16_LONG_CHECK - 1)) == 0 && sample + 8 <= ns && iters >= (unsigned int)(RT_H16_LONG_RATE * sample)) is_long = true;
 #endif
                 } else {
                     end_pixel();
@@ -1032,7 +1077,9 @@ __global__ __launch_bounds__(256) void k_trace_h(DevScene S, DevTree T, const fl
 template <class F> static auto with_tree(bool tree, F&& f) { return tree ? f(std::true_type{}) : f(std::false_type{}); }
 
 const char* render_kernel_name_h(bool tree, int mode) {
-    return tree ? (mode == 0 ? "k_render_h<true,0>" : "k_render_h<true,1>") : (mode == 0 ? "k_render_h<false,0>" : "k_render_h<false,1>");
+    static const char* const names[2][4] = {{"k_render_h<false,0>", "k_render_h<false,1>", nullptr, "k_render_h<false,3>"},
+                                            {"k_render_h<true,0>", "k_render_h<true,1>", nullptr, "k_render_h<true,3>"}};       // (modes 2 and 4: not for binary16, refused by the caller)
+    return names[tree ? 1 : 0][mode];
 }
 
 // LDS of a block of the binary16 tree kernels: the nodes (stage_tree), then one WaveLds per wave
@@ -1060,7 +1107,10 @@ hipError_t launch_render_h(const RenderArgs& A, bool tree, int mode, hipStream_t
     if (A.n_local_tiles <= 0) return hipSuccess;
     const unsigned need = (unsigned)((A.n_local_tiles + 3) / 4);
     const size_t lds = h16_lds_bytes(tree, A.tree);
-    void (*k)(RenderArgs) = with_tree(tree, [&](auto t) { return mode == 0 ? h16::k_render_h<decltype(t)::value, 0> : h16::k_render_h<decltype(t)::value, 1>; });
+    void (*k)(RenderArgs) = with_tree(tree, [&](auto t) {
+        constexpr bool T = decltype(t)::value;
+        return mode == 0 ? h16::k_render_h<T, 0> : mode == 3 ? h16::k_render_h<T, 3> : h16::k_render_h<T, 1>;
+    });
     const unsigned cap = resident_blocks((const void*)k, lds);
     const unsigned blocks = need < cap ? need : cap;
     hipLaunchKernelGGL(k, dim3(blocks), dim3(256), lds, st, A);

@@ -304,10 +304,16 @@ SYMBOLS_FUSED = {
     "rt_multi_set_adaptive_fused": (_i, [_vp, _i]),
 }
 
-# every symbol include/rt_amd_refine_fused.h declares (the header rt_amd.h includes last): (restype, argtypes)
+# every symbol include/rt_amd_refine_fused.h declares (the header rt_amd.h includes after it): (restype, argtypes)
 SYMBOLS_REFINE_FUSED = {
     "rt_render_adaptive_refine_fused": (_i, [_vp, _i, _i, _P(Adaptive), _P(Adaptive), _vp, _vp, _vp, _vp, _vp, Partition, _vp]),
     "rt_render_adaptive_refine_fused_on": (_i, [_vp, _vp, _i, _i, _P(Adaptive), _P(Adaptive), _vp, _vp, _vp, _vp, _vp, Partition, _vp]),
+}
+
+# every symbol include/rt_amd_h16_adaptive.h declares (adaptive sampling of binary16 worlds; the header rt_amd.h includes last): (restype, argtypes)
+SYMBOLS_H16_ADAPTIVE = {
+    "rt_render_adaptive_h16": (_i, [_vp, _i, _i, _P(Adaptive), _vp, _vp, _vp, _vp, _vp, Partition, _vp]),
+    "rt_render_adaptive_h16_on": (_i, [_vp, _vp, _i, _i, _P(Adaptive), _vp, _vp, _vp, _vp, _vp, Partition, _vp]),
 }
 
 
@@ -328,7 +334,7 @@ def lib():
             L = C.CDLL(LIB_PATH)
         except OSError as e:
             raise RtError("cannot load %s: %s" % (LIB_PATH, e))
-        for name, (res, args) in list(SYMBOLS.items()) + list(SYMBOLS_REBUILD.items()) + list(SYMBOLS_FUSED.items()) + list(SYMBOLS_REFINE_FUSED.items()):
+        for name, (res, args) in list(SYMBOLS.items()) + list(SYMBOLS_REBUILD.items()) + list(SYMBOLS_FUSED.items()) + list(SYMBOLS_REFINE_FUSED.items()) + list(SYMBOLS_H16_ADAPTIVE.items()):
             try:
                 fn = getattr(L, name)
             except AttributeError:
@@ -484,6 +490,11 @@ def _render_adaptive_refine_fused(fb, max_x, max_y, frm, to, world, d_rand_state
            _h(octree), _dev(d_spp), _dev(d_state), part or WHOLE)
 
 
+def _render_adaptive_h16(fb, max_x, max_y, params, world, d_rand_state, d_state, octree, d_spp, part, ctx=None, stream=None):
+    _frame("rt_render_adaptive_h16", ctx, stream, _dev(fb), max_x, max_y, C.byref(params), world.h, _dev(d_rand_state), _h(octree), _dev(d_spp),
+           _dev(d_state), part or WHOLE)
+
+
 def _render_adaptive_spend(fb, max_x, max_y, params, world, d_rand_state, d_state, octree, d_spp, part, d_picked, ctx=None, stream=None):
     _frame("rt_render_adaptive_spend", ctx, stream, _dev(fb), max_x, max_y, C.byref(params), world.h, _dev(d_rand_state), _h(octree), _dev(d_spp),
            _dev(d_state), part or WHOLE, _dev(d_picked))
@@ -502,8 +513,8 @@ def _render_adaptive_spend_temporal(fb, max_x, max_y, params, inputs, temporal, 
 
 
 def render_kernel_name(world, octree=None, mode=0):
-    """the kernel rt_render (mode 0) / rt_render_progressive (mode 1) / rt_render_adaptive_fused (mode 3) /
-    rt_render_adaptive_refine_fused (mode 4) launches for this world and tree (the library's own rule)"""
+    """the kernel rt_render (mode 0) / rt_render_progressive (mode 1) / rt_render_adaptive_fused or, binary16, rt_render_adaptive_h16
+    (mode 3) / rt_render_adaptive_refine_fused (mode 4, binary32 only) launches for this world and tree"""
     buf = C.create_string_buffer(64)
     _call("rt_render_kernel_name", world.h, _h(octree), mode, buf, 64)
     return buf.value.decode()
@@ -548,6 +559,10 @@ class RenderCtx(_Scheduled):
     def render_adaptive_refine_fused(self, fb, max_x, max_y, frm, to, world, d_rand_state, d_state, octree=None, d_spp=None, part=None, stream=None):
         """rt_render_adaptive_refine_fused_on: render_adaptive_refine's result from the seed pass and one render launch"""
         _render_adaptive_refine_fused(fb, max_x, max_y, frm, to, world, d_rand_state, d_state, octree, d_spp, part, self, stream)
+
+    def render_adaptive_h16(self, fb, max_x, max_y, params, world, d_rand_state, d_state=None, octree=None, d_spp=None, part=None, stream=None):
+        """rt_render_adaptive_h16_on: the adaptive frame of a binary16 world in one launch (fb: 3 halves per element)"""
+        _render_adaptive_h16(fb, max_x, max_y, params, world, d_rand_state, d_state, octree, d_spp, part, self, stream)
 
     def render_adaptive_spend(self, fb, max_x, max_y, params, world, d_rand_state, d_state, octree=None, d_spp=None, part=None, d_picked=None,
                               stream=None):
@@ -946,6 +961,12 @@ def render_adaptive_refine_fused(fb, max_x, max_y, frm, to, world, d_rand_state,
     """rt_render_adaptive_refine_fused on the current stream: what render_adaptive_refine leaves, from its seed pass and one render
     launch - every listed pixel resumes from the state and the stop rule runs inside the kernel"""
     _render_adaptive_refine_fused(fb, max_x, max_y, frm, to, world, d_rand_state, d_state, octree, d_spp, part)
+
+
+def render_adaptive_h16(fb, max_x, max_y, params, world, d_rand_state, d_state=None, octree=None, d_spp=None, part=WHOLE):
+    """rt_render_adaptive_h16 on the current stream: the adaptive frame of a binary16 world in one launch — every pixel is
+    render(ns = its count)'s pixel; d_state (alloc_adaptive_state, optional) takes every pixel's sums and count"""
+    _render_adaptive_h16(fb, max_x, max_y, params, world, d_rand_state, d_state, octree, d_spp, part)
 
 
 def adaptive_priority(SL, Q, k, floor):

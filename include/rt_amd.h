@@ -938,4 +938,5 @@ int rt_write_image(const char* path, int nx, int ny, const void* fb, int precisi
 #include "rt_amd_rebuild.h"   /* part of this ABI: the declarations that follow the ones above, in a file of their own */
 #include "rt_amd_fused.h"     /* ... and the adaptive frame in one launch */
 #include "rt_amd_refine_fused.h"   /* ... and its refinement in one launch */
+#include "rt_amd_h16_adaptive.h"   /* ... and the adaptive frame of binary16 worlds */
 #endif /* RT_AMD_H */

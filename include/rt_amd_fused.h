@@ -29,7 +29,8 @@ extern "C" {
  * RT_PRECISION_FP16 and RT_ARITH_CONTRACT worlds; 0 and nothing launched for a part without tiles.
  * rt_render_ctx_times / rt_world_render_times report the render kernel's device time, rt_render_ctx_counters and
  * rt_render_ctx_schedule its launch; rt_render_kernel_name(world, d_octree, 3, ...) names the kernel.
- * Not offered: stream capture, a fused spend (a spend selects between its rounds).  The fused refine: rt_amd_refine_fused.h. */
+ * Not offered: stream capture, a fused spend (a spend selects between its rounds).  The fused refine: rt_amd_refine_fused.h.
+ * A binary16 world has a call of its own, rt_render_adaptive_h16 (rt_amd_h16_adaptive.h). */
 int rt_render_adaptive_fused(void* fb, int max_x, int max_y, const rt_adaptive* params, const rt_world* world,
                              rt_rand_state* d_rand_state, const rt_octree* d_octree, int32_t* d_spp, void* d_state,
                              rt_partition part, void* stream);

@@ -32,7 +32,8 @@ extern "C" {
  * RT_ARITH_CONTRACT worlds; 0 and nothing launched for a part without tiles.
  * rt_render_ctx_times / rt_world_render_times report the device time of the seed and the render kernel together, as
  * rt_render_adaptive_refine reports its seed and rounds; rt_render_kernel_name(world, d_octree, 4, ...) names the kernel.
- * Not offered: stream capture, a fused spend (a spend selects between its rounds). */
+ * Not offered: stream capture, a fused spend (a spend selects between its rounds), binary16 worlds (rt_amd_h16_adaptive.h has the
+ * adaptive frame for them, and no refinement: DESIGN.md 5.9 "Binary16"). */
 int rt_render_adaptive_refine_fused(void* fb, int max_x, int max_y, const rt_adaptive* from, const rt_adaptive* to, const rt_world* world,
                                     rt_rand_state* d_rand_state, const rt_octree* d_octree, int32_t* d_spp, void* d_state,
                                     rt_partition part, void* stream);
