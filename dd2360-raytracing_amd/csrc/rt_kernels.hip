@@ -42,6 +42,8 @@
 //   RT_TU_CONTRACT (rt_kernels_contract.hip): FMA contraction ALLOWED — what nvcc's default -fmad=true does to the reference
 //     (Makefile:9) — in namespace rt::fmac, for rt_world_set_arith(RT_ARITH_CONTRACT), never the parity mode: launch_render and
 //     the k_render<*, 0|1, *> behind it, list variants included.  The pilot, the ordering pass and everything else stay IEEE.
+// A unit exports ONE render launcher, launch_render(A, tree, mode), and — where it holds list kernels — ONE list launcher,
+// launch_render_list(A, mode), for the modes with_mode gives it: 0 to 4 in the main and the list unit, 0 and 1 in the contract unit.
 // Without RT_SPLIT_LIST (the diagnostic one-unit builds: librt_amd_stats*.so, librt_amd_wpass.so) the main unit holds the list launchers too.
 // The kernels that trace no ray live in rt_schedule.hip, rt_adaptive.hip and rt_assemble.hip.
 #if defined(RT_TU_CONTRACT)
@@ -1793,12 +1795,34 @@ static hipError_t launch_k_render(const RenderArgs& A, size_t lds, hipStream_t s
     return hipGetLastError();
 }
 
+// The TWO ladders from what a call chooses at run time to k_render's template arguments, each written once: f is called with a
+// std::integral_constant<int, ...> and instantiates what it launches.
+// with_walk: a tree variant (render_variant; never kVariantList) to COOPG.
+template <class F> static auto with_walk(int variant, F&& f) {
+    if (variant == kVariantSolo) return f(std::integral_constant<int, kVariantSolo>{});
+    if (variant == kVariantSparse) return f(std::integral_constant<int, kVariantSparse>{});
+    if (variant == kVariantDense) return f(std::integral_constant<int, kVariantDense>{});
+    return f(std::integral_constant<int, kVariantTree>{});
+}
+// with_mode: a MODE of k_render to itself, cut to the modes this unit has — the contract unit emits k_render<*, 0|1, *> and nothing
+// above.  A mode the unit does not have is hipErrorInvalidValue, never another mode's kernel.
+template <class F> static hipError_t with_mode(int mode, F&& f) {
+    if (mode == 0) return f(std::integral_constant<int, 0>{});
+    if (mode == 1) return f(std::integral_constant<int, 1>{});
+#ifndef RT_TU_CONTRACT
+    if (mode == 2) return f(std::integral_constant<int, 2>{});
+    if (mode == 3) return f(std::integral_constant<int, 3>{});
+    if (mode == 4) return f(std::integral_constant<int, 4>{});
+#endif
+    return hipErrorInvalidValue;
+}
+
 // The hitable_list instantiations live in their own translation unit (rt_kernels_list.hip = this file with RT_TU_LIST):
 // SLP vectorisation (packed fp32, v_pk_*_f32) makes the list scan 10 % faster and the tree walk 4 % slower on gfx950, so
 // the two are compiled with different flags (Makefile).  The contract unit holds its own contracted k_render<false, 0|1, 1>.
 #ifdef RT_TU_HAS_LIST
 hipError_t launch_render_list(const RenderArgs& A, int mode, hipStream_t st) {
-    return mode == 0 ? launch_k_render<false, 0, 1>(A, 0, st) : launch_k_render<false, 1, 1>(A, 0, st);
+    return with_mode(mode, [&](auto m) { return launch_k_render<false, decltype(m)::value, 1>(A, 0, st); });
 }
 #ifndef RT_TU_CONTRACT
 hipError_t launch_tile_cost_list(const RenderArgs& A, unsigned blocks, int* cost, unsigned char* pilot, hipStream_t st) {
@@ -1813,30 +1837,19 @@ hipError_t launch_guides_list(const RenderArgs& A, unsigned blocks, long long n,
     hipLaunchKernelGGL((k_guides<false>), dim3(blocks), dim3(256), 0, st, A, n, out);
     return hipGetLastError();
 }
-hipError_t launch_render_adaptive_list(const RenderArgs& A, hipStream_t st) { return launch_k_render<false, 2, 1>(A, 0, st); }
-hipError_t launch_render_fused_list(const RenderArgs& A, hipStream_t st) { return launch_k_render<false, 3, 1>(A, 0, st); }
-hipError_t launch_render_refine_fused_list(const RenderArgs& A, hipStream_t st) { return launch_k_render<false, 4, 1>(A, 0, st); }
 #endif
 #endif
 
 #ifndef RT_TU_LIST
-// ---- the main unit and the contract unit: launch_render and what it needs
-// The ONE ladder from a tree variant chosen at run time (render_variant; never kVariantList) to the kernels' template argument:
-// f is called with a std::integral_constant<int, COOPG> and instantiates what it launches.
-template <class F> static auto with_walk(int variant, F&& f) {
-    if (variant == kVariantSolo) return f(std::integral_constant<int, kVariantSolo>{});
-    if (variant == kVariantSparse) return f(std::integral_constant<int, kVariantSparse>{});
-    if (variant == kVariantDense) return f(std::integral_constant<int, kVariantDense>{});
-    return f(std::integral_constant<int, kVariantTree>{});
-}
-
-// (the mode ladder stays 0 | 1 here: the contract unit emits no k_render<*, 2, *>)
+// ---- the main unit and the contract unit: launch_render, the ONE render launcher a unit exports — k_render<TREE, MODE, COOPG> of the
+// variant render_variant names, for every MODE (rt_device.h) the unit has: 0 rt_render, 1 rt_render_progressive, 2 a round of
+// rt_render_adaptive, 3 rt_render_adaptive_fused (A.ns = max_spp; FusedArgs), 4 rt_render_adaptive_refine_fused (the list in A.iters_out)
 hipError_t launch_render(const RenderArgs& A, bool tree, int mode, hipStream_t st) {
     if (A.n_local_tiles <= 0) return hipSuccess;
     const int variant = render_variant(tree, A.tree.acc);
     if (variant == kVariantList) return RT_TU_NAMESPACE::launch_render_list(A, mode, st);      // (qualified: the contract unit's own, not rt::'s that the argument's namespace offers too)
     const size_t lds = variant_lds_bytes(A.tree.n_nodes, variant);
-    return with_walk(variant, [&](auto w) { return mode == 0 ? launch_k_render<true, 0, decltype(w)::value>(A, lds, st) : launch_k_render<true, 1, decltype(w)::value>(A, lds, st); });
+    return with_mode(mode, [&](auto m) { return with_walk(variant, [&](auto w) { return launch_k_render<true, decltype(m)::value, decltype(w)::value>(A, lds, st); }); });
 }
 #endif
 
@@ -1946,30 +1959,6 @@ hipError_t launch_count_order(const RenderArgs& A, const unsigned short* iters, 
     { const hipError_t e = launch_count_cost(B, iters, cost, flags + (size_t)A.n_local_tiles * 64, st); if (e != hipSuccess) return e; }
     const CountedSelect cs{iters, solo_frac, solo_cap_den > 0 ? (unsigned int)(B.n_lanes / 64 / solo_cap_den) : 0u, extra};
     return launch_select_and_order(B, cost, order, flags, long_list, st, 0, 0x7fffffff, &cs);
-}
-
-// one round of rt_render_adaptive: k_render<*, 2, *> of the variant rt_render would launch (the contracted arithmetic has no adaptive mode)
-hipError_t launch_render_adaptive(const RenderArgs& A, bool tree, hipStream_t st) {
-    if (A.n_local_tiles <= 0) return hipSuccess;
-    const int variant = render_variant(tree, A.tree.acc);
-    if (variant == kVariantList) return launch_render_adaptive_list(A, st);
-    return with_walk(variant, [&](auto w) { return launch_k_render<true, 2, decltype(w)::value>(A, variant_lds_bytes(A.tree.n_nodes, variant), st); });
-}
-
-// rt_render_adaptive_fused: k_render<*, 3, *> of the same variant, once for the whole frame (A.ns = max_spp; FusedArgs: the rule and where a pixel's end goes)
-hipError_t launch_render_fused(const RenderArgs& A, bool tree, hipStream_t st) {
-    if (A.n_local_tiles <= 0) return hipSuccess;
-    const int variant = render_variant(tree, A.tree.acc);
-    if (variant == kVariantList) return launch_render_fused_list(A, st);
-    return with_walk(variant, [&](auto w) { return launch_k_render<true, 3, decltype(w)::value>(A, variant_lds_bytes(A.tree.n_nodes, variant), st); });
-}
-
-// rt_render_adaptive_refine_fused: k_render<*, 4, *> of the same variant, once over the seed's list (A.ns = to.max_spp; the list travels in A.iters_out, rt_device.h)
-hipError_t launch_render_refine_fused(const RenderArgs& A, bool tree, hipStream_t st) {
-    if (A.n_local_tiles <= 0) return hipSuccess;
-    const int variant = render_variant(tree, A.tree.acc);
-    if (variant == kVariantList) return launch_render_refine_fused_list(A, st);
-    return with_walk(variant, [&](auto w) { return launch_k_render<true, 4, decltype(w)::value>(A, variant_lds_bytes(A.tree.n_nodes, variant), st); });
 }
 
 // What launch_trace and launch_guides share — n records, one lane each, in blocks of 256: list(blocks) launches the list scan's kernel,

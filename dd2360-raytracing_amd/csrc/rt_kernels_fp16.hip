@@ -1076,10 +1076,15 @@ __global__ __launch_bounds__(256) void k_trace_h(DevScene S, DevTree T, const fl
 // the ONE ladder from the run-time `tree` to the kernels' TREE argument: f is called with std::true_type or std::false_type
 template <class F> static auto with_tree(bool tree, F&& f) { return tree ? f(std::true_type{}) : f(std::false_type{}); }
 
+// "k_render_h<TREE,MODE>" as rocprofv3 prints it, from one format as rt::render_kernel_name does it (never NULL; modes 2 and 4 name
+// what launch_render_h refuses)
 const char* render_kernel_name_h(bool tree, int mode) {
-    static const char* const names[2][4] = {{"k_render_h<false,0>", "k_render_h<false,1>", nullptr, "k_render_h<false,3>"},
-                                            {"k_render_h<true,0>", "k_render_h<true,1>", nullptr, "k_render_h<true,3>"}};       // (modes 2 and 4: not for binary16, refused by the caller)
-    return names[tree ? 1 : 0][mode];
+    struct Names {
+        char s[2][5][24];      // [tree][mode]
+        Names() { for (int t = 0; t < 2; ++t) for (int m = 0; m < 5; ++m) snprintf(s[t][m], sizeof s[t][m], "k_render_h<%s,%d>", t ? "true" : "false", m); }
+    };
+    static const Names names;
+    return names.s[tree ? 1 : 0][mode >= 0 && mode < 5 ? mode : 1];
 }
 
 // LDS of a block of the binary16 tree kernels: the nodes (stage_tree), then one WaveLds per wave
@@ -1103,14 +1108,16 @@ hipError_t launch_tile_order_h(const RenderArgs& A, bool tree, int* cost, unsign
     return launch_select_and_order(A, cost, order, flags, long_list, st, RT_H16_PILOT_LONG_SUM, 0x7fffffff);
 }
 
+// k_render_h<TREE, MODE> for the modes binary16 has: 0, 1 and 3 (no rounds, no refinement) — any other is hipErrorInvalidValue
 hipError_t launch_render_h(const RenderArgs& A, bool tree, int mode, hipStream_t st) {
     if (A.n_local_tiles <= 0) return hipSuccess;
     const unsigned need = (unsigned)((A.n_local_tiles + 3) / 4);
     const size_t lds = h16_lds_bytes(tree, A.tree);
-    void (*k)(RenderArgs) = with_tree(tree, [&](auto t) {
+    void (*k)(RenderArgs) = with_tree(tree, [&](auto t) -> void (*)(RenderArgs) {
         constexpr bool T = decltype(t)::value;
-        return mode == 0 ? h16::k_render_h<T, 0> : mode == 3 ? h16::k_render_h<T, 3> : h16::k_render_h<T, 1>;
+        return mode == 0 ? h16::k_render_h<T, 0> : mode == 1 ? h16::k_render_h<T, 1> : mode == 3 ? h16::k_render_h<T, 3> : nullptr;
     });
+    if (!k) return hipErrorInvalidValue;
     const unsigned cap = resident_blocks((const void*)k, lds);
     const unsigned blocks = need < cap ? need : cap;
     hipLaunchKernelGGL(k, dim3(blocks), dim3(256), lds, st, A);

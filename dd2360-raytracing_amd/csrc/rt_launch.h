@@ -14,10 +14,8 @@ hipError_t launch_pilot(const RenderArgs& A, bool tree, int* cost, unsigned char
 hipError_t launch_tile_order(const RenderArgs& A, bool tree, int* cost, unsigned int* order, unsigned char* flags, unsigned int* long_list, hipStream_t st);
 hipError_t launch_count_order(const RenderArgs& A, const unsigned short* iters, int* cost, unsigned int* order, unsigned char* flags, unsigned int* long_list,
                               float solo_frac, int solo_cap_den, unsigned int* extra, hipStream_t st);
+// (the ONE render launcher of a backend: k_render's MODE 0 to 4, rt_device.h; a mode the backend has no kernel for is hipErrorInvalidValue)
 hipError_t launch_render(const RenderArgs& A, bool tree, int mode, hipStream_t st);
-hipError_t launch_render_adaptive(const RenderArgs& A, bool tree, hipStream_t st);
-hipError_t launch_render_fused(const RenderArgs& A, bool tree, hipStream_t st);
-hipError_t launch_render_refine_fused(const RenderArgs& A, bool tree, hipStream_t st);
 hipError_t launch_trace(const DevScene& S, const DevTree& T, bool tree, const float* rays, long long n, rt_hit_record* out, hipStream_t st);
 hipError_t launch_guides(const DevScene& S, const DevTree& T, bool tree, int max_x, int max_y, rt_hit_record* out, hipStream_t st);
 int render_variant(bool tree, const DevAccel& acc);             // a kVariant* of rt_variant.h
@@ -35,10 +33,7 @@ hipError_t launch_tile_cost_list(const RenderArgs& A, unsigned blocks, int* cost
 hipError_t launch_render_list(const RenderArgs& A, int mode, hipStream_t st);
 hipError_t launch_trace_list(const RenderArgs& A, unsigned blocks, const float* rays, long long n, rt_hit_record* out, hipStream_t st);
 hipError_t launch_guides_list(const RenderArgs& A, unsigned blocks, long long n, rt_hit_record* out, hipStream_t st);
-hipError_t launch_render_adaptive_list(const RenderArgs& A, hipStream_t st);
-hipError_t launch_render_fused_list(const RenderArgs& A, hipStream_t st);
-hipError_t launch_render_refine_fused_list(const RenderArgs& A, hipStream_t st);
-// ---- rt_kernels_contract.hip: k_render with FMA contraction allowed (rt_world_set_arith(RT_ARITH_CONTRACT)); nothing else is contracted
+// ---- rt_kernels_contract.hip: k_render with FMA contraction allowed (rt_world_set_arith(RT_ARITH_CONTRACT)), modes 0 and 1; nothing else is contracted
 namespace fmac { hipError_t launch_render(const RenderArgs& A, bool tree, int mode, hipStream_t st); }
 
 // ---- rt_schedule.hip: the integer kernels of the scheduling pass and the counters of a launch's queue slot
@@ -71,7 +66,7 @@ hipError_t launch_adapt_zero(unsigned int* p, int n, hipStream_t st);
 enum GatherElem { kGatherF32x3, kGatherF16x3, kGatherI32x1 };
 hipError_t launch_gather(GatherElem elem, void* full, const void* parts, int max_x, int max_y, int nparts, const long long* starts, long long part_stride_px, hipStream_t st);
 
-// ---- rt_kernels_fp16.hip: the render path in binary16
+// ---- rt_kernels_fp16.hip: the render path in binary16 (launch_render_h: modes 0, 1 and 3)
 hipError_t launch_pilot_h(const RenderArgs& A, bool tree, int* cost, unsigned char* pilot, hipStream_t st);
 hipError_t launch_tile_order_h(const RenderArgs& A, bool tree, int* cost, unsigned int* order, unsigned char* flags, unsigned int* long_list, hipStream_t st);
 hipError_t launch_render_h(const RenderArgs& A, bool tree, int mode, hipStream_t st);

@@ -46,6 +46,7 @@ PATHS = {
     "solo_chains": (500, 30, None, (203, 77), "k_render<true,3,5>"),
     "list": (500, None, 0, (131, 71), "k_render<false,3,1>"),               # (the reference's list scan: without it the list takes a grid of its own)
     "dense_grid": (100000, 320, 1, (131, 71), "k_render<true,3,2>"),
+    "per_lane_tree": (500, 30, 0, (131, 71), "k_render<true,3,1>"),         # (the reference's tree walk: no candidate grid)
 }
 
 

@@ -157,12 +157,14 @@ def test_frame_with_the_long_chain_pass(rt, cuda):
     assert np.array_equal(states_of(st)[:, :6], want_st[:, :6])
 
 
-@pytest.mark.parametrize("name,variant,mode,spl", [("centre_bound", None, "list", 30), ("clamps", "huge", "tree", 30)], ids=["centre_bound", "huge"])
+@pytest.mark.parametrize("name,variant,mode,spl", [("centre_bound", None, "list", 30), ("clamps", "huge", "tree", 30), ("switches", "sparse", "tree", 64)],
+                         ids=["centre_bound", "huge", "sparse"])
 def test_parts_and_progressive_passes(rt, cuda, name, variant, mode, spl):
-    """a render in three parts, assembled, and two progressive passes equal the oracle: through a grid stretched to the centre bound and
-    through an enabled grid without entries"""
+    """a render in three parts, assembled, and two progressive passes equal the oracle: through a grid stretched to the centre bound,
+    through an enabled grid without entries, and through the dense walk (k_render<true,1,2>: no other test takes a progressive pass there)"""
     torch = cuda
     sp, c, W, O = make(rt, name, variant, mode, spl)
+    assert rt.render_kernel_name(W, O, 1) == kernel(name, variant, mode, 1)
     want, _ = oracle_frame(name, variant, mode, spl, "own", NS)
     nparts = 3
     per = rt.part_pixels(NX, NY, rt.Partition(0, nparts))

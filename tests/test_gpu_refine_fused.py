@@ -69,6 +69,7 @@ PATHS = {
     "solo_chains": (500, 30, None, (203, 77), "k_render<true,4,5>"),
     "list": (500, None, 0, (131, 71), "k_render<false,4,1>"),
     "dense_grid": (100000, 320, 1, (131, 71), "k_render<true,4,2>"),
+    "per_lane_tree": (500, 30, 0, (131, 71), "k_render<true,4,1>"),
 }
 SWEEP = (0.02, 0.03, 0.05, 0.07, 0.1, 0.15, 0.2, 0.3, 0.5)          # adaptive_frames.pick_rel_error's targets
 
